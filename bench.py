@@ -6,8 +6,13 @@ ranks are independent replicas of the path over disjoint batches (no data-path
 collective: weak scaling); a barrier + synchronize brackets the timed region
 and the slowest rank's time is used.
 
-Prints ONE JSON line on rank 0:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the
+`--steps` forwards and reports only the headline:
   value     spectrograms/s over all ranks, inputs resident in HBM
+  ms_per_step  milliseconds of one timed step (slowest rank)
+`--dump-outputs DIR` writes rank 0's outputs of the last timed step as
+DIR/<name>.npy (float32; the inputs are seeded, so two builds compare output
+for output).  Everything below is measured only with `--full`:
   roofline  the dominant kernel (by summed in-library HIP-event time inside the
             timed region) priced on its algorithmic FLOPs against the dense
             16-bit matrix peak divided by the MFMA terms per product (default
@@ -43,6 +48,29 @@ import torch  # noqa: E402
 FP32_MATRIX_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32
 BF16_MATRIX_PEAK_TFLOPS = 2500.0  # dense bf16 MFMA
 HBM_PEAK_GBS = 8000.0
+DUMP_LIMIT_BYTES = 60 * 10**6     # --dump-outputs stays below 64 MB in all
+
+
+def _dump_outputs(out, directory, seed=0):
+    """VQVAE.forward's outputs (reconstruction, latent loss, both perplexities, both code maps) as <name>.npy in float32
+    (code indices < 2^24 are exact in it).  A batch too large for DUMP_LIMIT_BYTES is cut to a fixed, seeded sample of
+    its spectrograms, whose positions go to batch_index.npy."""
+    import numpy as np
+    names = ("reconstruction", "latent_loss", "perplexity_t", "perplexity_b", "id_t", "id_b")
+    arrays = {n: t.detach().float().cpu() for n, t in zip(names, out) if t is not None}
+    per_sample = [n for n in ("reconstruction", "id_t", "id_b") if n in arrays]
+    batch = arrays["reconstruction"].shape[0]
+    sample_bytes = sum(arrays[n][:1].numel() * 4 for n in per_sample)
+    if batch * sample_bytes > DUMP_LIMIT_BYTES:
+        k = max(1, DUMP_LIMIT_BYTES // sample_bytes)
+        idx = torch.randperm(batch, generator=torch.Generator().manual_seed(seed))[:k].sort().values
+        for n in per_sample:
+            arrays[n] = arrays[n][idx]
+        arrays["batch_index"] = idx.double()
+    directory = pathlib.Path(directory)
+    directory.mkdir(parents=True, exist_ok=True)
+    for n, a in arrays.items():
+        np.save(directory / f"{n}.npy", a.numpy())
 
 
 def _pick_distinct_rows(flat, K, g, min_rel=0.1):
@@ -673,6 +701,11 @@ def main():
     ap.add_argument("--train-steps", type=int, default=20, help="timed steps of the VQ-VAE training leg")
     ap.add_argument("--prior-bottom-batch", type=int, default=2, help="codemaps per step of the bottom prior's training row")
     ap.add_argument("--prior-bottom-steps", type=int, default=8)
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel timers and roofline, the other precision modes, the training / attention / "
+                         "front-end / prior legs and the CPU baseline (the --no-* and --prior-* options apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -729,23 +762,25 @@ def main():
         for _ in range(args.warmup):
             out = model(x)
         barrier()
-        # kernel timers on every `--timer-stride`-th step of the timed region only: a timed launch carries a
+        # --full: kernel timers on every `--timer-stride`-th step of the timed region only: a timed launch carries a
         # start / stop event pair and costs ~4 us of stream time (4 % of a step if every launch is timed)
         # The library takes a launch's event pair from a pool that grows on demand: the pool is filled HERE, by as many
         # instrumented forwards as the timed region will sample -- created inside it, the ~50 events of a sampled forward
         # cost that step 0.4-0.7 ms of host time (the headline lost 3-9 % to it, box by box: 1.95 ms against the 1.77 ms of
         # the same loop without timers, `alt_precision_single_gpu.split_f16`).
-        L.isi_prof_enable(1)
-        for _ in range((args.steps + args.timer_stride - 1) // args.timer_stride):
-            out = model(x)
-        torch.cuda.synchronize(device)
-        L.isi_prof_enable(1)          # records cleared, the pool stays
-        L.isi_prof_enable(0)
-        barrier()
+        timer_stride = args.timer_stride if args.full else 0
+        if timer_stride:
+            L.isi_prof_enable(1)
+            for _ in range((args.steps + timer_stride - 1) // timer_stride):
+                out = model(x)
+            torch.cuda.synchronize(device)
+            L.isi_prof_enable(1)          # records cleared, the pool stays
+            L.isi_prof_enable(0)
+            barrier()
         timed_steps = 0
         t0 = time.perf_counter()
         for i in range(args.steps):
-            sampled = i % args.timer_stride == 0
+            sampled = timer_stride and i % timer_stride == 0
             if sampled:
                 L.isi_prof_enable(2)
                 timed_steps += 1
@@ -760,6 +795,43 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(out, args.dump_outputs)
+    head = {
+        "metric": "spectrograms/sec VQ-VAE fwd+quantize @B64",
+        "value": round(world * args.batch * args.steps / dt, 2),
+        "unit": "spectrograms/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "spinup_ms": args.spinup_ms,
+        **({"process_group_before_first_gpu_call": pg_before_gpu} if world > 1 else {}),
+        "ms_per_step": round(dt * 1e3 / args.steps, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": {"f32": "f32", "split_f16": "f32 (products split into two f16 pieces, three terms)"}.get(
+            default_precision, "f32 (products split into bf16 pieces: x6 / x3)"),
+        "precision": {"mode": default_precision,
+                      "note": "fp32 data and fp32 accumulation everywhere; split_f16 (default): every product as "
+                              "hi.hi+hi.lo+lo.hi of two 11-bit f16 pieces of the operands (scaled by powers of "
+                              "two) on the f16 matrix pipe -- per-product error ~2^-23, error vs fp64 at or below "
+                              "the fp32 pipe's own; codebook search: candidates on the f16 pipe, the decision "
+                              "between the two best in fp32 (index differences from the fp32 CPU reference are at "
+                              "the level of the reference's own rounding, DESIGN section 2); "
+                              "operand range |activation| < 16384, |weight| < 64 (weights checked at "
+                              "plan time, an activation beyond it gives NaN / index -1). split_bf16: six-term "
+                              "bf16 split (no range limit) in index-feeding layers, three-term in the final "
+                              "decoder. The other modes are timed in alt_precision_single_gpu (--full)"},
+        "data": "synthetic",
+        "config": {"workload": "VQVAE.forward (encode + quantize x2 + decode), eval, default ctor "
+                               "(128 hidden, 2 res blocks, D=64, K=512, factors 4/2)",
+                   "batch_per_gpu": args.batch, "input": "[2,128,512] fp32 randn",
+                   "weights": "random init, codebooks calibrated on encoder outputs",
+                   "parallelism": f"replicas x{world} (no data-path collective)"},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- BASELINE configs[2] on every rank: data-parallel VQ-VAE training step (collectives inside)
     train_leg = None
@@ -867,32 +939,7 @@ def main():
         for key in ("TFLOPs", "frac_of_mfma_ceiling", "GBs", "frac_of_hbm_peak", "max_frac"):
             roof["whole_forward_" + key] = roof["whole_forward"][key]
         line = {
-            "metric": "spectrograms/sec VQ-VAE fwd+quantize @B64",
-            "value": round(world * args.batch * args.steps / dt, 2),
-            "unit": "spectrograms/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "spinup_ms": args.spinup_ms,
-            **({"process_group_before_first_gpu_call": pg_before_gpu} if world > 1 else {}),
-            "ms_per_step": round(dt * 1e3 / args.steps, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": {"f32": "f32", "split_f16": "f32 (products split into two f16 pieces, three terms)"}.get(
-                default_precision, "f32 (products split into bf16 pieces: x6 / x3)"),
-            "precision": {"mode": default_precision,
-                          "note": "fp32 data and fp32 accumulation everywhere; split_f16 (default): every product as "
-                                  "hi.hi+hi.lo+lo.hi of two 11-bit f16 pieces of the operands (scaled by powers of "
-                                  "two) on the f16 matrix pipe -- per-product error ~2^-23, error vs fp64 at or below "
-                                  "the fp32 pipe's own; codebook search: candidates on the f16 pipe, the decision "
-                                  "between the two best in fp32 (index differences from the fp32 CPU reference are at "
-                                  "the level of the reference's own rounding, DESIGN section 2); "
-                                  "operand range |activation| < 16384, |weight| < 64 (weights checked at "
-                                  "plan time, an activation beyond it gives NaN / index -1). split_bf16: six-term "
-                                  "bf16 split (no range limit) in index-feeding layers, three-term in the final "
-                                  "decoder. The other modes are timed in alt_precision_single_gpu"},
-            "data": "synthetic",
-            "config": {"workload": "VQVAE.forward (encode + quantize x2 + decode), eval, default ctor "
-                                   "(128 hidden, 2 res blocks, D=64, K=512, factors 4/2)",
-                       "batch_per_gpu": args.batch, "input": "[2,128,512] fp32 randn",
-                       "weights": "random init, codebooks calibrated on encoder outputs",
-                       "parallelism": f"replicas x{world} (no data-path collective)"},
+            **head,
             "roofline": roof,
             "kernel_timers": f"HIP events on every launch of {timed_steps} of the {args.steps} timed steps (every "
                              f"{args.timer_stride}th)",

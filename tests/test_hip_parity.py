@@ -597,7 +597,7 @@ def test_bench_batch_codes_certified_against_oracle():
     """bench.py's own model and batch (B = 64, default split-f16 products): the codes of ALL 64 spectrograms against the
     CPU oracle, level by level (bottom teacher-forced on the GPU's top codes) -- every code that differs must be a
     certified near-tie of the reference's fp32 distance formula (normalised float64 gap < 1e-6) and there may be only a
-    handful of them, in the exact-fp32 mode as well.  bench.py prints the same
+    handful of them, in the exact-fp32 mode as well.  bench.py --full prints the same
     figures as `codes_moved_vs_oracle` / `certified_near_ties`."""
     import pathlib
     import sys

@@ -613,6 +613,7 @@ typedef struct isi_prior_state {
   float *scratch;          /* device, isi_prior_decode_scratch_floats(w, B) floats                    */
   size_t scratch_floats;
   int S_t, S_src, S, B, start_len;
+  const float *cross_out;  /* [n_layers, S_src, B, d] or NULL: single-source cross-attention (below)          */
 } isi_prior_state;
 size_t isi_prior_decode_scratch_floats(const isi_prior_w *w, int B);
 /* Enqueues positions [p_begin, p_end) of the decoder (one new row each, all layers),
@@ -624,7 +625,13 @@ size_t isi_prior_decode_scratch_floats(const isi_prior_w *w, int B);
  * library, keyed on the bytes of *w, *state (the host mask aside), the sampling parameters and the switches -- a later call
  * with equal arguments replays them, nothing is captured again and the call never waits for the stream (at most 8 argument
  * sets are kept; the least recently used one is dropped once its last replay has finished).  While the CALLER is capturing `stream`
- * and with ISI_PRIOR_GRAPH = 0: ~66 direct launches per position.  Same kernels, same codes either way. */
+ * and with ISI_PRIOR_GRAPH = 0: ~66 direct launches per position.  Same kernels, same codes either way.
+ * Single-source cross-attention (state->cross_out != NULL): decoder row p attends source row p / Cd only (the aligned
+ * decoder layer, the identity memory mask).  The softmax over one key is 1, so a layer's cross-attention block at row p
+ * is row p / Cd of cross_out[l] = out_proj(V(memory)) (biases included); one launch per layer forms
+ * LN1(y1) + cross_out[l][p / Cd] in place of the query GEMV, the cached attention and the out-projection, and
+ * memory_kv may be NULL (it is not read).  Requires Ce == 1 (else ISI_E_UNSUPPORTED) and (S_t - 1) / Cd < S_src
+ * (else ISI_E_INVALID), both checked before any launch. */
 int isi_prior_sample_run(const isi_prior_w *w, const isi_prior_state *state, int p_begin,
                          int p_end, float temperature, int top_k, float top_p, void *stream);
 

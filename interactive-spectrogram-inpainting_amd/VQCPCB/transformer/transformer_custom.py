@@ -365,8 +365,9 @@ class TransformerAlignedDecoderLayerCustom(TransformerDecoderLayerCustom):
 
     (for the bottom prior: the four codes of a 2 x 2 patch attend to the one top code above them; the start symbols are event 0 on
     both sides) -- as an additive mask handed to the attention kernels, combined with whatever `memory_mask` the caller passes.
-    Self-attention, feed-forward and every parameter are the parent's, so state dicts are interchangeable.  KV-cached sampling is
-    not built for it (priors/_decode.py raises)."""
+    Self-attention, feed-forward and every parameter are the parent's, so state dicts are interchangeable.  The native sampling
+    loop runs its cross-attention as rows of a table (one source token per event: priors/_decode.py, NativeSampler);
+    IncrementalDecoder refuses it."""
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)

@@ -11,6 +11,9 @@
 // 5.8 us on this multi-die part (attention + out-projection + residual in one kernel: 22.7 us against 16 us for the
 // three launches; linear1 + linear2: 16.3 against 9.6 us).  What is folded is what needs no dependency of its own: the
 // LayerNorms and the merge of the attention key splits run in the prologue of the consuming GEMV.
+// Models whose decoder rows attend ONE source row each (aligned decoder, identity memory mask: isi_prior_state.cross_out)
+// replace the three cross-attention launches of a layer (LN1 + query, attention, out-projection) by one
+// (single_source_cross_kernel): 6 dependent launches per layer.
 //
 // One call runs, for every sequence position in [p_begin, p_end), the whole
 // decoder stack on ONE new row (8 dependent launches per layer, below), the logits head, the
@@ -1002,6 +1005,76 @@ int launch_stage_rows(const RowLinArgs &a, const float *part, int ns, int hd, fl
   return ISI_OK;
 }
 
+// ---- single-source cross-attention (isi_prior_state.cross_out): every decoder row p may attend ONE source row,
+// j = p / Cd (the aligned decoder layer with one source token per event; the identity memory mask).  The softmax over one
+// allowed key is exactly 1, so the attention output is that row's value vector whatever the query and the relative bias,
+// and the whole cross-attention block of layer l is row j of a table formed once per call, T_l[j] = out_proj(V_l(memory[j])).
+// One launch replaces the query GEMV, the cached attention and the out-projection:
+//   y2 = LN1(y1) + T_l[p / Cd]
+// LN1 with the residual-LN formula of the row kernels (lane-strided sums, wave reductions); the statistics of y2 are formed
+// the same way and handed to linear2, which normalises y2 as its residual (RowLinArgs.res_stat).  The statistics of y1
+// have no earlier producer (the launch that forms y1 writes it in pieces across workgroups), so this kernel forms them.
+constexpr int SS_RS = 16;      // floats per lane of a row held in registers: d <= 1024
+constexpr int SS_ROWS = 4;     // rows per workgroup, one per wave
+struct SingleSourceArgs {
+  const float *y1;             // [B, d] pre-norm rows
+  const float *ln_g, *ln_b;    // LN1
+  const float *table;          // this layer's [S_src, B, d]
+  float *y2;                   // [B, d]
+  float *stat_out;             // [B][2] mean, 1 / std of the y2 rows (nullable)
+  const int *pos;              // replayable launches: the position from device memory (else `p`)
+  int p, Cd, S_src, B, d;
+  float eps;
+};
+
+__global__ __launch_bounds__(64 * SS_ROWS) void single_source_cross_kernel(SingleSourceArgs a) {
+  const int lane = threadIdx.x & 63, m = blockIdx.x * SS_ROWS + (threadIdx.x >> 6);
+  const int p = a.pos ? *a.pos : a.p;
+  const int j = p / a.Cd;
+  if (m >= a.B || j >= a.S_src) return;       // (j: checked on the host for every position of the call)
+  const float *r = a.y1 + (size_t)m * a.d;
+  const float *t = a.table + ((size_t)j * a.B + m) * a.d;
+  float rv[SS_RS], tv[SS_RS];
+#pragma unroll
+  for (int i = 0; i < SS_RS; ++i) {
+    const int c = lane + 64 * i;
+    rv[i] = c < a.d ? r[c] : 0.f;
+    tv[i] = c < a.d ? t[c] : 0.f;
+  }
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < SS_RS; ++i) if (lane + 64 * i < a.d) s += rv[i];
+  const float mean = wave_sum(s) / (float)a.d;
+  float var = 0.f;
+#pragma unroll
+  for (int i = 0; i < SS_RS; ++i) if (lane + 64 * i < a.d) { const float dv = rv[i] - mean; var += dv * dv; }
+  const float rstd = 1.0f / sqrtf(wave_sum(var) / (float)a.d + a.eps);
+  float *o = a.y2 + (size_t)m * a.d;
+  float ys = 0.f;
+#pragma unroll
+  for (int i = 0; i < SS_RS; ++i) {
+    const int c = lane + 64 * i;
+    if (c < a.d) {
+      const float v = tv[i] + ((rv[i] - mean) * rstd * a.ln_g[c] + a.ln_b[c]);   // (out-projection + bias) + LN1 residual
+      tv[i] = v;
+      o[c] = v;
+      ys += v;
+    }
+  }
+  if (!a.stat_out) return;
+  const float ymean = wave_sum(ys) / (float)a.d;
+  float yvar = 0.f;
+#pragma unroll
+  for (int i = 0; i < SS_RS; ++i) if (lane + 64 * i < a.d) { const float dv = tv[i] - ymean; yvar += dv * dv; }
+  const float yrstd = 1.0f / sqrtf(wave_sum(yvar) / (float)a.d + a.eps);
+  if (lane == 0) *reinterpret_cast<float2 *>(a.stat_out + 2 * (size_t)m) = make_float2(ymean, yrstd);
+}
+
+int launch_single_source_cross(const SingleSourceArgs &a, hipStream_t st) {
+  hipLaunchKernelGGL(single_source_cross_kernel, dim3((a.B + SS_ROWS - 1) / SS_ROWS), dim3(64 * SS_ROWS), 0, st, a);
+  return check_launch("single_source_cross");
+}
+
 }  // namespace
 
 // A decoding-loop stage on its own (isi_decode_stage_f32): out[M][N] = act(LN(x)[M][K] W[N][K]^T + bias + LN_res(res)), the
@@ -1096,8 +1169,15 @@ int prior_sample_run(const isi_prior_w *w, const isi_prior_state *s, int p_begin
   if (w->n_layers <= 0 || w->n_layers > ISI_MAX_LAYERS) return invalid("prior_sample_run: bad layer count");
   if (s->B <= 0 || s->B > 256) return unsupported("prior_sample_run: batch size must be 1..256");
   if (p_begin < 0 || p_end > s->S_t || p_begin > p_end) return invalid("prior_sample_run: bad position range");
-  if (!s->x_seq || !s->kv_cache || !s->memory_kv || !s->codes || !s->mask || !s->uniforms || !s->scratch)
+  const bool single_source = s->cross_out != nullptr;     // memory_kv is not read then
+  if (!s->x_seq || !s->kv_cache || (!single_source && !s->memory_kv) || !s->codes || !s->mask || !s->uniforms || !s->scratch)
     return invalid("prior_sample_run: null state pointer");
+  if (single_source) {
+    if (w->Ce != 1) return unsupported("prior_sample_run: single-source cross-attention needs one source token per event (Ce == 1)");
+    if (w->Cd <= 0 || s->S_src <= 0 || (s->S_t - 1) / w->Cd >= s->S_src)
+      return invalid("prior_sample_run: single-source cross-attention: a target position without a source row ((S_t - 1) / Cd >= S_src)");
+    if (w->d_model > 64 * SS_RS) return unsupported("prior_sample_run: single-source cross-attention needs d_model <= 1024");
+  }
   if (s->scratch_floats < prior_decode_scratch_floats(w, s->B)) {
     set_last_error("prior_sample_run: scratch too small");
     return ISI_E_WORKSPACE;
@@ -1158,7 +1238,6 @@ int prior_sample_run(const isi_prior_w *w, const isi_prior_state *s, int p_begin
     for (int l = 0; l < w->n_layers; ++l) {
       const isi_decoder_layer_w &L = w->layers[l];
       float *cache = s->kv_cache + l * cache_layer;
-      const float *memkv = s->memory_kv + l * mem_layer;
       float *y3 = (l & 1) ? y3b : y3a;
       RowLinArgs a;
       int rc;
@@ -1180,24 +1259,35 @@ int prior_sample_run(const isi_prior_w *w, const isi_prior_state *s, int p_begin
       const bool defer_s = merge_in_gemv && ns_self > 1;
       if ((rc = rel_attention_decode_launch(&g, p < 0 ? 0 : p, pos_arg, 1, attn_ws, defer_s ? 0 : 1, q_st))) return rc;
       if ((rc = defer_s ? launch_rows(a_o, attn_ws, ns_self) : launch_rows(a_o))) return rc;
-      // cross-attention query from LN1(y1)
-      a = RowLinArgs{y1, d, L.norm1_w, L.norm1_b, L.cross_attn.in_proj_weight, L.cross_attn.in_proj_bias, nullptr, 0,
-                     nullptr, nullptr, q, d, nullptr, 0, d, B, d, d, 0, 1e-5f, nullptr, 0, 0, 0};
-      RowLinArgs a_o2{ao, d, nullptr, nullptr, L.cross_attn.out_proj_weight, L.cross_attn.out_proj_bias, y1, d,
-                      L.norm1_w, L.norm1_b, y2, d, nullptr, 0, d, B, d, d, 0, 1e-5f, nullptr, 0, 0, 0};
-      hand_stats(a, a_o2, merge_in_gemv && ns_cross > 1);
-      if ((rc = launch_rows(a))) return rc;
-      g.k = memkv; g.v = memkv + d; g.rel_embeddings = L.cross_attn.rel_embeddings; g.Sk = s->S_src;
-      g.Ck = w->Ce; g.Ek = w->Ee; g.rel_rows = L.cross_attn.rel_rows;
-      const bool defer_c = merge_in_gemv && ns_cross > 1;
-      if ((rc = rel_attention_decode_launch(&g, p < 0 ? 0 : p, pos_arg, 0, attn_ws, defer_c ? 0 : 1, q_st))) return rc;
-      if ((rc = defer_c ? launch_rows(a_o2, attn_ws, ns_cross) : launch_rows(a_o2))) return rc;
       // feed-forward on LN2(y2)
-      a = RowLinArgs{y2, d, L.norm2_w, L.norm2_b, L.linear1_w, L.linear1_b, nullptr, 0, nullptr, nullptr, hid, ff,
-                     nullptr, 0, ff, B, ff, d, 1, 1e-5f, nullptr, 0, 0, 0};
+      RowLinArgs a_f1{y2, d, L.norm2_w, L.norm2_b, L.linear1_w, L.linear1_b, nullptr, 0, nullptr, nullptr, hid, ff,
+                      nullptr, 0, ff, B, ff, d, 1, 1e-5f, nullptr, 0, 0, 0};
       RowLinArgs a_f2{hid, ff, nullptr, nullptr, L.linear2_w, L.linear2_b, y2, d, L.norm2_w, L.norm2_b, y3, d, nullptr,
                       0, d, B, d, ff, 0, 1e-5f, nullptr, 0, 0, 0};
-      hand_stats(a, a_f2);
+      if (single_source) {
+        // y2 = LN1(y1) + T_l[p / Cd]: one launch for the cross-attention block; y2's statistics go to linear2
+        const bool handoff = !knobs().decode_no_stat_handoff;
+        const SingleSourceArgs ss{y1, L.norm1_w, L.norm1_b, s->cross_out + (size_t)l * s->S_src * B * d, y2,
+                                  handoff ? rowstat : nullptr, pos_arg, p < 0 ? 0 : p, w->Cd, s->S_src, B, d, 1e-5f};
+        if ((rc = launch_single_source_cross(ss, q_st))) return rc;
+        if (handoff) a_f2.res_stat = rowstat;
+      } else {
+        const float *memkv = s->memory_kv + l * mem_layer;
+        // cross-attention query from LN1(y1)
+        a = RowLinArgs{y1, d, L.norm1_w, L.norm1_b, L.cross_attn.in_proj_weight, L.cross_attn.in_proj_bias, nullptr, 0,
+                       nullptr, nullptr, q, d, nullptr, 0, d, B, d, d, 0, 1e-5f, nullptr, 0, 0, 0};
+        RowLinArgs a_o2{ao, d, nullptr, nullptr, L.cross_attn.out_proj_weight, L.cross_attn.out_proj_bias, y1, d,
+                        L.norm1_w, L.norm1_b, y2, d, nullptr, 0, d, B, d, d, 0, 1e-5f, nullptr, 0, 0, 0};
+        hand_stats(a, a_o2, merge_in_gemv && ns_cross > 1);
+        if ((rc = launch_rows(a))) return rc;
+        g.k = memkv; g.v = memkv + d; g.rel_embeddings = L.cross_attn.rel_embeddings; g.Sk = s->S_src;
+        g.Ck = w->Ce; g.Ek = w->Ee; g.rel_rows = L.cross_attn.rel_rows;
+        const bool defer_c = merge_in_gemv && ns_cross > 1;
+        if ((rc = rel_attention_decode_launch(&g, p < 0 ? 0 : p, pos_arg, 0, attn_ws, defer_c ? 0 : 1, q_st))) return rc;
+        if ((rc = defer_c ? launch_rows(a_o2, attn_ws, ns_cross) : launch_rows(a_o2))) return rc;
+        hand_stats(a_f1, a_f2);
+      }
+      a = a_f1;
       if ((rc = launch_rows(a))) return rc;
       if ((rc = launch_rows(a_f2))) return rc;
       yin = y3; yin_pos = 0; ln_g = L.norm3_w; ln_b = L.norm3_b;

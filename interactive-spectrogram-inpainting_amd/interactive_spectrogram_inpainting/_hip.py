@@ -122,7 +122,7 @@ class isi_prior_state(C.Structure):
     _fields_ = [("x_seq", C.c_void_p), ("kv_cache", C.c_void_p), ("memory_kv", C.c_void_p), ("codes", C.c_void_p),
                 ("mask", C.c_void_p), ("uniforms", C.c_void_p), ("scratch", C.c_void_p),
                 ("scratch_floats", C.c_size_t), ("S_t", C.c_int), ("S_src", C.c_int), ("S", C.c_int),
-                ("B", C.c_int), ("start_len", C.c_int)]
+                ("B", C.c_int), ("start_len", C.c_int), ("cross_out", C.c_void_p)]
 
 
 class isi_reduce_job(C.Structure):

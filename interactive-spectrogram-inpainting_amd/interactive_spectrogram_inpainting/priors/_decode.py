@@ -16,11 +16,34 @@ import torch
 from . import _ops
 
 
+def _is_aligned(layers) -> bool:
+    from VQCPCB.transformer.transformer_custom import TransformerAlignedDecoderLayerCustom
+    return any(isinstance(l, TransformerAlignedDecoderLayerCustom) for l in layers)
+
+
 def _refuse_aligned(layers) -> None:
     """The key/value-cached loops attend over ALL memory rows; the aligned decoder layer restricts them per target event."""
-    from VQCPCB.transformer.transformer_custom import TransformerAlignedDecoderLayerCustom
-    if any(isinstance(l, TransformerAlignedDecoderLayerCustom) for l in layers):
+    if _is_aligned(layers):
         raise NotImplementedError("KV-cached sampling is not built for use_aligned_decoder=True (full passes work)")
+
+
+def _single_source_check(model, layers, S_t: int, S_src: int, device) -> bool:
+    """True when every decoder row attends ONE source row, j = p // Cd: an aligned decoder (source events of one token) or the
+    identity memory mask.  Raises ValueError where the full forward fails for the geometry, NotImplementedError for source
+    events of more than one token (Ce > 1)."""
+    aligned, identity = _is_aligned(layers), bool(getattr(model, "use_identity_memory_mask", False))
+    if not (aligned or identity):
+        return False
+    if model.source_num_channels != 1:
+        raise NotImplementedError("single-source cross-attention needs one source token per event (Ce == 1)")
+    if aligned:
+        layers[0].alignment_mask(S_t, S_src, device)        # ValueError: a target event without a source event
+    if identity:
+        if S_t != S_src:
+            raise ValueError(f"identity memory mask: {S_t} target rows against {S_src} source rows")
+        if model.target_num_channels != 1:
+            raise NotImplementedError("identity memory mask with more than one target token per event")
+    return True
 
 
 class IncrementalDecoder:
@@ -29,6 +52,9 @@ class IncrementalDecoder:
         dec = model.transformer.decoder
         self.layers = list(dec.layers)
         _refuse_aligned(self.layers)
+        if getattr(model, "use_identity_memory_mask", False):
+            raise NotImplementedError("incremental decoding attends over every memory row: not built for "
+                                      "use_identity_memory_mask=True (NativeSampler is)")
         self.model = model
         d = model.d_model
         S_t = model.target_transformer_sequence_length_with_start_symbol
@@ -99,7 +125,7 @@ class NativeSampler:
         from .transformer import Seq2SeqInputKind
         self._C, self._hip = C, _hip
         dec_layers = list(model.transformer.decoder.layers)
-        _refuse_aligned(dec_layers)
+        self.single_source = _single_source_check(model, dec_layers, x_seq.shape[0], memory.shape[0], memory.device)
         if len(dec_layers) > _hip.ISI_MAX_LAYERS:
             raise NotImplementedError(f"more than {_hip.ISI_MAX_LAYERS} decoder layers")
         dev = memory.device
@@ -146,7 +172,14 @@ class NativeSampler:
         self.w = w
 
         memory = memory.contiguous()
-        self.memory_kv = torch.stack([l.multihead_attn.project_kv(memory) for l in dec_layers]).contiguous()
+        self.memory_kv = self.cross_out = None
+        if self.single_source:
+            # every row attends one source row: a layer's cross-attention block is a row of out_proj(V(memory)), formed here
+            # by the full pass's own two products (the values of its k|v projection, then the out-projection)
+            self.cross_out = torch.stack([l.multihead_attn.out_proj.run(l.multihead_attn.project_kv(memory)[..., d:].contiguous())
+                                          for l in dec_layers]).contiguous()
+        else:
+            self.memory_kv = torch.stack([l.multihead_attn.project_kv(memory) for l in dec_layers]).contiguous()
         S_t = x_seq.shape[0]
         self.kv_cache = torch.zeros(len(dec_layers), S_t, B, 2 * d, dtype=torch.float32, device=dev)
         self.x_seq, self.codes = x_seq, codes
@@ -155,7 +188,11 @@ class NativeSampler:
         n_scratch = _hip.lib().isi_prior_decode_scratch_floats(C.byref(w), B)
         self.scratch = torch.empty(n_scratch, dtype=torch.float32, device=dev)
         st = _hip.isi_prior_state()
-        st.x_seq, st.kv_cache, st.memory_kv = x_seq.data_ptr(), self.kv_cache.data_ptr(), self.memory_kv.data_ptr()
+        st.x_seq, st.kv_cache = x_seq.data_ptr(), self.kv_cache.data_ptr()
+        if self.single_source:
+            st.cross_out = self.cross_out.data_ptr()
+        else:
+            st.memory_kv = self.memory_kv.data_ptr()
         st.codes, st.mask = codes.data_ptr(), self.mask_host.ctypes.data
         st.uniforms, st.scratch, st.scratch_floats = self.uniforms.data_ptr(), self.scratch.data_ptr(), n_scratch
         st.S_t, st.S_src, st.S, st.B = S_t, memory.shape[0], codes.shape[1], B
@@ -172,6 +209,8 @@ class NativeSampler:
         from VQCPCB.transformer.transformer_custom import _add_norm
         d = self.model.d_model
         x = self.x_seq[:p0].contiguous()
+        if self.single_source:
+            src_row = torch.arange(p0, device=x.device) // self.model.target_num_channels
         for l, layer in enumerate(self.model.transformer.decoder.layers):
             sa = layer.self_attn
             qkv = sa._project(x, 0)                                  # [p0, B, 3d]
@@ -179,8 +218,11 @@ class NativeSampler:
             a = _ops.rel_attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], sa.rel_embeddings, sa.nhead,
                                    sa.Cq, sa.Ck, sa.Ek, mask_mode=1)
             x1 = _add_norm(layer, sa.out_proj, a, x, layer.norm1)
-            c = layer.multihead_attn(x1, None, None, kv=self.memory_kv[l])
-            x2 = _add_norm(layer, layer.multihead_attn.out_proj, c, x1, layer.norm2)
+            if self.single_source:
+                x2 = layer.norm2.run(self.cross_out[l].index_select(0, src_row), residual=x1)   # the loop's table rows
+            else:
+                c = layer.multihead_attn(x1, None, None, kv=self.memory_kv[l])
+                x2 = _add_norm(layer, layer.multihead_attn.out_proj, c, x1, layer.norm2)
             h = layer.linear1.run(x2, relu=True)
             x = _add_norm(layer, layer.linear2, h, x2, layer.norm3)
 

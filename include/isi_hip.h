@@ -41,7 +41,8 @@ const char *isi_last_error(void);
  * bindings can verify their own layout: which = 0 isi_src, 1 isi_dst,
  * 2 isi_conv_w, 3 isi_encoder_w, 4 isi_decoder_w, 5 isi_codebook_w,
  * 6 isi_vqvae_w, 7 isi_vqvae_out, 8 isi_attn_args, 9 isi_prior_w,
- * 10 isi_prior_state, 11 isi_attn_bwd_args.  Returns 0 for an unknown id. */
+ * 10 isi_prior_state, 11 isi_attn_bwd_args, 12 isi_reduce_job, 13 isi_prior_rows.
+ * Returns 0 for an unknown id. */
 size_t isi_abi_struct_bytes(int which);
 
 /* x = max(x, 0) in place over n floats: the in-place nn.ReLU with which
@@ -634,6 +635,33 @@ size_t isi_prior_decode_scratch_floats(const isi_prior_w *w, int B);
  * (else ISI_E_INVALID), both checked before any launch. */
 int isi_prior_sample_run(const isi_prior_w *w, const isi_prior_state *state, int p_begin,
                          int p_end, float temperature, int top_k, float top_p, void *stream);
+
+/* Ragged batches: independent requests decoded together, each row at its OWN position.  Step t of the plan moves row b
+ * to decoder position pos[t][b] (the whole stack on that row, its k|v into cache slot pos[t][b]) and, where
+ * commit[t][b], draws token pos[t][b] - (start_len - 1) of row b with uniform u[(pos - start_len + 1) * B + b] and writes
+ * the code and the token's embedding into input row pos + 1.  Rows advance by 0 or 1 per step; a row that has finished
+ * stays at its last position with commit = 0 (it recomputes the same cache slot with the same bits and writes nothing
+ * else).  Per-row sampling parameters: temperature / top_k / top_p [B] on the device, or NULL for the call's scalars. */
+typedef struct isi_prior_rows {
+  const int32_t *pos;          /* [n_steps, B] device: decoder position of row b at step t                 */
+  const uint8_t *commit;       /* [n_steps, B] device: 1 = draw and commit row b's token at step t          */
+  const int32_t *pos_host;     /* [n_steps, B] HOST copy of pos: validation and planning only               */
+  const uint8_t *commit_host;  /* [n_steps, B] HOST copy of commit: validation, and which steps sample       */
+  const float *temperature;    /* [B] device or NULL (then the call's scalar); likewise top_k, top_p        */
+  const int32_t *top_k;
+  const float *top_p;
+  int n_steps;
+} isi_prior_rows;
+/* Steps [t_begin, t_end) of the plan *rows (isi_abi_struct_bytes(13) = sizeof(isi_prior_rows)).  state->mask is not
+ * read.  Before any launch the host checks, from the host copies, 0 <= pos < S_t, steps of 0 or 1 per row, and that
+ * every commit names a token in [0, S) (else ISI_E_INVALID); B outside 1..256 gives ISI_E_UNSUPPORTED (a single request
+ * is better served by isi_prior_sample_run).  The library never reads a device array on the host.  Graph replay as isi_prior_sample_run:
+ * W = ISI_PRIOR_GRAPH steps per graph, windows whose steps all sample (some row commits) or all keep; the cache key
+ * holds the bytes of *rows except its two host pointers.  Same kernels as isi_prior_sample_run, instantiated with the
+ * row's own position in every position-dependent address (x / residual rows, cache slot, key count and relative term of
+ * the attention, source row of single-source cross-attention, uniform, commit). */
+int isi_prior_sample_run_rows(const isi_prior_w *w, const isi_prior_state *state, const isi_prior_rows *rows,
+                              int t_begin, int t_end, float temperature, int top_k, float top_p, void *stream);
 
 /* ----------------------------------------------------------- quantization */
 

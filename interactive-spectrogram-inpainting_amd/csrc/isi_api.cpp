@@ -107,6 +107,7 @@ size_t isi_abi_struct_bytes(int which) {
     case 9: return sizeof(isi_prior_w);
     case 10: return sizeof(isi_prior_state);
     case 12: return sizeof(isi_reduce_job);
+    case 13: return sizeof(isi_prior_rows);
     default: return 0;
   }
 }
@@ -356,6 +357,10 @@ size_t isi_prior_decode_scratch_floats(const isi_prior_w *w, int B) { return pri
 int isi_prior_sample_run(const isi_prior_w *w, const isi_prior_state *state, int p_begin, int p_end,
                          float temperature, int top_k, float top_p, void *stream) {
   return prior_sample_run(w, state, p_begin, p_end, temperature, top_k, top_p, S(stream));
+}
+int isi_prior_sample_run_rows(const isi_prior_w *w, const isi_prior_state *state, const isi_prior_rows *rows, int t_begin,
+                              int t_end, float temperature, int top_k, float top_p, void *stream) {
+  return prior_sample_run_rows(w, state, rows, t_begin, t_end, temperature, top_k, top_p, S(stream));
 }
 
 size_t isi_conv_wgrad_workspace_floats(int Cout, int K, int M, int nphase) {

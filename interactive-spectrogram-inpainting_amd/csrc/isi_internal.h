@@ -118,9 +118,20 @@ struct SampleCommit {
   int *advance;      // ONE row only (a single workgroup: no other reader of the counter in the launch): *advance = position + 1
                      // behind the commit -- the decode loop's set_pos launch (4.3 us of a 280 us token) folded in
 };
+// ragged batches (isi_prior_sample_run_rows): row r of the launch stands at position row_pos[t * rows + r] of step
+// t = *pos (replayable) or t = 0 (row_pos, commit already offset to the step); it draws with u[(position - pos_off) * rows + r]
+// and commits only where commit[t * rows + r] and the token lies in [0, S).  Per-row temperature / top_k / top_p or NULL.
+struct SampleRows {
+  const int *row_pos;
+  const uint8_t *commit;
+  const float *temperature;
+  const int *top_k;
+  const float *top_p;
+  int S;
+};
 int sample_row_commit_f32(const float *logits, int stride, int rows, int n, float temperature, int top_k, float top_p,
                           const float *u, int64_t *out, float *filtered, const int *pos, int pos_off,
-                          const SampleCommit &cm, hipStream_t stream);
+                          const SampleCommit &cm, hipStream_t stream, const SampleRows *ragged = nullptr);
 int sample_row_pos_f32(const float *logits, int stride, int rows, int n, float temperature, int top_k, float top_p,
                        const float *u, int64_t *out, float *filtered, const int *pos, int pos_off,
                        hipStream_t stream);
@@ -129,8 +140,10 @@ int sample_row_f32(const float *logits, int stride, int rows, int n, float tempe
 
 int rel_attention_decode_splits(int Sk, int pairs);
 int attention_tail_rows(int S, int mask_mode, bool dense_mask);   // rel_attention_f32.hip
+// row_pos != nullptr (ragged batches): batch row b queries from position row_pos[t * B + b], t = *pos or 0 (row_pos
+// then already offset to the step); self-attention reads that position + 1 keys, g->Sk is their upper bound
 int rel_attention_decode_launch(const isi_attn_args *g, int q_pos, const int *pos, int self_keys, float *workspace,
-                                int combine, hipStream_t stream);
+                                int combine, hipStream_t stream, const int *row_pos = nullptr);
 size_t decode_stage_workspace_floats(int M, int N, int K);
 int decode_stage_f32(const float *x, int x_stride, const float *ln_g, const float *ln_b, const float *W, const float *bias,
                      const float *res, int res_stride, const float *res_g, const float *res_b, float *out, int out_stride,
@@ -138,6 +151,8 @@ int decode_stage_f32(const float *x, int x_stride, const float *ln_g, const floa
 size_t prior_decode_scratch_floats(const isi_prior_w *w, int B);
 int prior_sample_run(const isi_prior_w *w, const isi_prior_state *s, int p_begin, int p_end, float temperature,
                      int top_k, float top_p, hipStream_t stream);
+int prior_sample_run_rows(const isi_prior_w *w, const isi_prior_state *s, const isi_prior_rows *rows, int t_begin, int t_end,
+                          float temperature, int top_k, float top_p, hipStream_t stream);
 
 bool gemm_split_applicable(int M, int N, int K, int split_mode);
 // Optional extras of gemm_split_f32: a batch of nz independent products (grid y; element strides between them) and a

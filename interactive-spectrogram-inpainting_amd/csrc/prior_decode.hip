@@ -67,6 +67,10 @@ struct RowLinArgs {
   // residual rows again in every workgroup and reducing them (6 % of a decoding step at B = 32, measured by ablation)
   float *stat_out;
   const float *res_stat;
+  // ragged batches (isi_prior_sample_run_rows; the RAG instantiations): row m stands at position row_pos[t * M + m] of step
+  // t = *pos (replayable) or t = 0 (row_pos already offset to the step), and x / res / out2 of row m advance by that
+  // position times x_pos / res_pos / out2_pos
+  const int *row_pos;
 };
 
 __device__ __forceinline__ float wave_sum(float v) { return wave64_sum(v); }   // DPP path (isi_common.h)
@@ -384,13 +388,19 @@ __global__ __launch_bounds__(256) void row_gemv1_kernel(Gemv1Args g) {
 // once and used for every row, the rows pass through in groups of MR (round 5: ALL rows of a stage in one launch; groups of
 // 8 rows used to be launches of their own, 4 per stage at batch 32).  Per row the operations of row_gemv1_kernel /
 // row_linear_ln_kernel, in their order: a row's result does not depend on the rows it shares a launch with.
-template <int KQ, int MR>
+template <int KQ, int MR, bool RAG = false>
 __global__ __launch_bounds__(256) void row_gemvm_kernel(RowLinArgs a) {
   touch_args(a);
   long ppos = 0;
   if (a.pos) ppos = *a.pos;
-  if (a.x_pos) a.x += ppos * a.x_pos;
-  if (a.res && a.res_pos) a.res += ppos * a.res_pos;
+  const int *rp = nullptr;             // RAG: the rows' positions
+  if constexpr (RAG) {
+    rp = a.row_pos + ppos * a.M;
+    ppos = 0;
+  } else {
+    if (a.x_pos) a.x += ppos * a.x_pos;
+    if (a.res && a.res_pos) a.res += ppos * a.res_pos;
+  }
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nq = a.K >> 2;
   constexpr int RPW = KQ >= 4 ? 1 : 2;
@@ -428,11 +438,13 @@ __global__ __launch_bounds__(256) void row_gemvm_kernel(RowLinArgs a) {
     for (int i = 0; i < KQ; ++i) {
       const int qd = lane + 64 * i;
       xv[m][i] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (m < Mg && qd < nq) xv[m][i] = reinterpret_cast<const float4 *>(xg + (size_t)m * a.x_stride)[qd];
+      if (m < Mg && qd < nq)
+        xv[m][i] = reinterpret_cast<const float4 *>(xg + (size_t)m * a.x_stride + (RAG ? (long)rp[m0 + m] * a.x_pos : 0))[qd];
     }
   float res_v[MR];
 #pragma unroll
-  for (int m = 0; m < MR; ++m) res_v[m] = (writer && resg && m < Mg) ? resg[(size_t)m * a.res_stride + n] : 0.f;
+  for (int m = 0; m < MR; ++m)
+    res_v[m] = (writer && resg && m < Mg) ? resg[(size_t)m * a.res_stride + (RAG ? (long)rp[m0 + m] * a.res_pos : 0) + n] : 0.f;
   constexpr int RS = 8;
   float rrow[MR][RS];
   float2 rstat[MR];        // the residual rows' statistics from the launch that formed them (RowLinArgs.res_stat)
@@ -447,7 +459,7 @@ __global__ __launch_bounds__(256) void row_gemvm_kernel(RowLinArgs a) {
 #pragma unroll
       for (int i = 0; i < RS; ++i) {
         const int c = lane + 64 * i;
-        rrow[m][i] = (m < Mg && c < a.N) ? resg[(size_t)m * a.res_stride + c] : 0.f;
+        rrow[m][i] = (m < Mg && c < a.N) ? resg[(size_t)m * a.res_stride + (RAG ? (long)rp[m0 + m] * a.res_pos : 0) + c] : 0.f;
       }
   }
   // the group's rows go through each phase TOGETHER (statistics, normalisation, products, reductions): MR independent chains
@@ -535,7 +547,7 @@ __global__ __launch_bounds__(256) void row_gemvm_kernel(RowLinArgs a) {
       if (a.relu) v = fmaxf(v, 0.f);
       const size_t mr = (size_t)(m0 + m);
       if (n < a.split) a.out[mr * a.out_stride + n] = v;
-      else a.out2[ppos * a.out2_pos + mr * a.out2_stride + (n - a.split)] = v;
+      else a.out2[(RAG ? (long)rp[mr] : ppos) * a.out2_pos + mr * a.out2_stride + (n - a.split)] = v;
     }
   }
   }
@@ -561,9 +573,9 @@ constexpr size_t kRowMfmaLds = (size_t)(32 * MF_LD + 128 + 4 * 32 * 33) * sizeof
 typedef float mf_f32x16 __attribute__((ext_vector_type(16)));
 
 // LayerNorm statistics of this wave's 8 rows of the tile (KQS float4 per lane and row, 16 / KQS rows per batch of loads)
-template <int KQS>
-__device__ __forceinline__ void mfma_row_stats(const RowLinArgs &a, float *__restrict__ stat, int m0, int Mt, int nq, int lane,
-                                               int wave) {
+template <int KQS, bool RAG>
+__device__ __forceinline__ void mfma_row_stats(const RowLinArgs &a, const int *rp, float *__restrict__ stat, int m0, int Mt, int nq,
+                                               int lane, int wave) {
   constexpr int RB = 16 / KQS;
   for (int r0 = 8 * wave; r0 < 8 * wave + 8; r0 += RB) {
     float4 xr[RB][KQS];
@@ -572,7 +584,8 @@ __device__ __forceinline__ void mfma_row_stats(const RowLinArgs &a, float *__res
 #pragma unroll
       for (int i = 0; i < KQS; ++i) {
         const int r = r0 + rr, qd = lane + 64 * i;
-        xr[rr][i] = (r < Mt && qd < nq) ? reinterpret_cast<const float4 *>(a.x + (size_t)(m0 + r) * a.x_stride)[qd]
+        xr[rr][i] = (r < Mt && qd < nq) ? reinterpret_cast<const float4 *>(a.x + (size_t)(m0 + r) * a.x_stride +
+                                                                           (RAG ? (long)rp[m0 + r] * a.x_pos : 0))[qd]
                                         : make_float4(0.f, 0.f, 0.f, 0.f);
       }
 #pragma unroll
@@ -630,6 +643,7 @@ __device__ __forceinline__ void mfma_row_stats_lds(const float *__restrict__ xs,
 // `ksplit_ws` != nullptr (K beyond one chunk on a grid too small to fill the chip: linear2 of a feed-forward block, 16 tiles at
 // N = 512): grid z = the K chunk, a workgroup multiplies ONE chunk and leaves its raw 32 x 32 sums in ksplit_ws[z][M][N];
 // row_mfma_finish_kernel adds the chunks in order and applies bias / residual / ReLU (33.8 -> ~13 us for that stage at B = 32).
+template <bool RAG = false>
 __global__ __launch_bounds__(256) void row_mfma32_kernel(RowLinArgs a, float *__restrict__ ksplit_ws, int knobs_decode_stats_global) {
   touch_args(a);
   asm volatile("" ::"s"(ksplit_ws));
@@ -639,8 +653,14 @@ __global__ __launch_bounds__(256) void row_mfma32_kernel(RowLinArgs a, float *__
   float *red = stat + 128;                // [4][32][33] the waves' accumulators
   long ppos = 0;
   if (a.pos) ppos = *a.pos;
-  if (a.x_pos) a.x += ppos * a.x_pos;
-  if (a.res && a.res_pos) a.res += ppos * a.res_pos;
+  const int *rp = nullptr;             // RAG: the rows' positions
+  if constexpr (RAG) {
+    rp = a.row_pos + ppos * a.M;
+    ppos = 0;
+  } else {
+    if (a.x_pos) a.x += ppos * a.x_pos;
+    if (a.res && a.res_pos) a.res += ppos * a.res_pos;
+  }
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n0 = blockIdx.x * 32, m0 = blockIdx.y * 32;
   const int Mt = a.M - m0 < 32 ? a.M - m0 : 32;
@@ -662,7 +682,8 @@ __global__ __launch_bounds__(256) void row_mfma32_kernel(RowLinArgs a, float *__
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
       const int f = tid + 256 * u, r = csh >= 0 ? f >> csh : f / cq, c4 = f - r * cq;
-      sv[u] = (f < 32 * cq && r < Mt) ? *reinterpret_cast<const float4 *>(a.x + (size_t)(m0 + r) * a.x_stride + kc + 4 * c4)
+      sv[u] = (f < 32 * cq && r < Mt) ? *reinterpret_cast<const float4 *>(a.x + (size_t)(m0 + r) * a.x_stride +
+                                                                          (RAG ? (long)rp[m0 + r] * a.x_pos : 0) + kc + 4 * c4)
                                       : make_float4(0.f, 0.f, 0.f, 0.f);
     }
   };
@@ -679,7 +700,8 @@ __global__ __launch_bounds__(256) void row_mfma32_kernel(RowLinArgs a, float *__
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int i = (tid >> 5) + 8 * q;
-    resv[q] = (a.res && !ksplit_ws && nok && i < Mt) ? a.res[(size_t)(m0 + i) * a.res_stride + nj] : 0.f;
+    resv[q] = (a.res && !ksplit_ws && nok && i < Mt)
+                  ? a.res[(size_t)(m0 + i) * a.res_stride + (RAG ? (long)rp[m0 + i] * a.res_pos : 0) + nj] : 0.f;
   }
   // ---- row statistics (wave w: rows 8 w .. 8 w + 7)
   // one K chunk of at most 128 float4 per row (the prior's d_model-wide LayerNorm inputs): statistics from the staged rows
@@ -695,9 +717,9 @@ __global__ __launch_bounds__(256) void row_mfma32_kernel(RowLinArgs a, float *__
   if (a.ln_g && !stats_from_lds) {
 #endif
     const int kq = (nq + 63) >> 6;                       // float4 per lane and row
-    if (kq <= 2) mfma_row_stats<2>(a, stat, m0, Mt, nq, lane, wave);
-    else if (kq <= 4) mfma_row_stats<4>(a, stat, m0, Mt, nq, lane, wave);
-    else mfma_row_stats<8>(a, stat, m0, Mt, nq, lane, wave);
+    if (kq <= 2) mfma_row_stats<2, RAG>(a, rp, stat, m0, Mt, nq, lane, wave);
+    else if (kq <= 4) mfma_row_stats<4, RAG>(a, rp, stat, m0, Mt, nq, lane, wave);
+    else mfma_row_stats<8, RAG>(a, rp, stat, m0, Mt, nq, lane, wave);
   }
 #ifdef ISI_ROWMFMA_ABL_RES
   if (rln && tid < 32) { stat[4 * tid + 2] = 0.f; stat[4 * tid + 3] = 1.f; }
@@ -717,7 +739,7 @@ __global__ __launch_bounds__(256) void row_mfma32_kernel(RowLinArgs a, float *__
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const int r = 8 * wave + rr, c = lane + 64 * i;
-        rv[rr][i] = (r < Mt && c < a.N) ? a.res[(size_t)(m0 + r) * a.res_stride + c] : 0.f;
+        rv[rr][i] = (r < Mt && c < a.N) ? a.res[(size_t)(m0 + r) * a.res_stride + (RAG ? (long)rp[m0 + r] * a.res_pos : 0) + c] : 0.f;
       }
 #pragma unroll
     for (int rr = 0; rr < 8; ++rr) {
@@ -825,19 +847,21 @@ __global__ __launch_bounds__(256) void row_mfma32_kernel(RowLinArgs a, float *__
       if (a.relu) v = fmaxf(v, 0.f);
       const size_t m = (size_t)(m0 + i);
       if (nj < a.split) a.out[m * a.out_stride + nj] = v;
-      else a.out2[ppos * a.out2_pos + m * a.out2_stride + (nj - a.split)] = v;
+      else a.out2[(RAG ? (long)rp[m] : ppos) * a.out2_pos + m * a.out2_stride + (nj - a.split)] = v;
     }
   }
 }
 
 // one workgroup per row: the K chunks' sums in chunk order, then bias / (normalised) residual / ReLU as in the tile kernel
+template <bool RAG = false>
 __global__ __launch_bounds__(256) void row_mfma_finish_kernel(RowLinArgs a, const float *__restrict__ ws, int nz) {
   touch_args(a);
   __shared__ float red[8];
   long ppos = 0;
   if (a.pos) ppos = *a.pos;
-  if (a.res && a.res_pos) a.res += ppos * a.res_pos;
   const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if constexpr (RAG) ppos = a.row_pos[ppos * a.M + m];    // this row's position
+  if (a.res && a.res_pos) a.res += ppos * a.res_pos;
   const bool rln = a.res && a.res_g;
   float rmean = 0.f, rrstd = 1.f;
   if (rln && a.res_stat) {
@@ -878,23 +902,24 @@ bool row_mfma_supported(const RowLinArgs &a) {
          (reinterpret_cast<uintptr_t>(a.W) & 15) == 0 && (!a.ln_g || ((reinterpret_cast<uintptr_t>(a.ln_g) | reinterpret_cast<uintptr_t>(a.ln_b)) & 15) == 0);
 }
 
+template <bool RAG = false>
 int launch_row_mfma(const RowLinArgs &a, hipStream_t st, float *ksplit_ws = nullptr, size_t ksplit_floats = 0) {
   static DeviceOnce attr_set;       // once, outside any stream capture (the first position runs direct)
   if (!attr_set.done()) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(row_mfma32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(row_mfma32_kernel<RAG>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)kRowMfmaLds) != hipSuccess)
       return check_launch("hipFuncSetAttribute(row_mfma32)");
     attr_set.mark();
   }
   const int tiles = ((a.N + 31) / 32) * ((a.M + 31) / 32), nz = (a.K + MF_KC - 1) / MF_KC;
   if (nz > 1 && tiles < 128 && ksplit_ws && (size_t)nz * a.M * a.N <= ksplit_floats) {
-    hipLaunchKernelGGL(row_mfma32_kernel, dim3((a.N + 31) / 32, (a.M + 31) / 32, nz), dim3(256), kRowMfmaLds, st, a, ksplit_ws, knobs().decode_stats_global);
+    hipLaunchKernelGGL(row_mfma32_kernel<RAG>, dim3((a.N + 31) / 32, (a.M + 31) / 32, nz), dim3(256), kRowMfmaLds, st, a, ksplit_ws, knobs().decode_stats_global);
     int rc = check_launch("row_mfma32 (K chunks)");
     if (rc) return rc;
-    hipLaunchKernelGGL(row_mfma_finish_kernel, dim3(a.M), dim3(256), 0, st, a, ksplit_ws, nz);
+    hipLaunchKernelGGL(row_mfma_finish_kernel<RAG>, dim3(a.M), dim3(256), 0, st, a, ksplit_ws, nz);
     return check_launch("row_mfma_finish");
   }
-  hipLaunchKernelGGL(row_mfma32_kernel, dim3((a.N + 31) / 32, (a.M + 31) / 32), dim3(256), kRowMfmaLds, st, a, (float *)nullptr, knobs().decode_stats_global);
+  hipLaunchKernelGGL(row_mfma32_kernel<RAG>, dim3((a.N + 31) / 32, (a.M + 31) / 32), dim3(256), kRowMfmaLds, st, a, (float *)nullptr, knobs().decode_stats_global);
   return check_launch("row_mfma32");
 }
 
@@ -911,11 +936,12 @@ bool row_gemvm_supported(const RowLinArgs &a) {
   return row_gemvm_group(a.M, kq) >= 2;
 }
 
+template <bool RAG = false>
 int launch_row_gemvm(const RowLinArgs &a, hipStream_t st) {
   const int kq = a.K <= 256 ? 1 : a.K <= 512 ? 2 : a.K <= 1024 ? 4 : 8;
   const int mr = row_gemvm_group(a.M, kq);
   dim3 grid(kq >= 4 ? (a.N + 3) / 4 : (a.N + NPB - 1) / NPB), block(256);
-#define ISI_GM(KQ_, MR_) hipLaunchKernelGGL((row_gemvm_kernel<KQ_, MR_>), grid, block, 0, st, a)
+#define ISI_GM(KQ_, MR_) hipLaunchKernelGGL((row_gemvm_kernel<KQ_, MR_, RAG>), grid, block, 0, st, a)
   if (kq == 1) { if (mr == 2) ISI_GM(1, 2); else if (mr == 4) ISI_GM(1, 4); else ISI_GM(1, 8); }
   else if (kq == 2) { if (mr == 2) ISI_GM(2, 2); else if (mr == 4) ISI_GM(2, 4); else ISI_GM(2, 8); }
   else if (kq == 4) { if (mr == 2) ISI_GM(4, 2); else ISI_GM(4, 4); }
@@ -987,6 +1013,11 @@ __global__ void set_pos_kernel(int *pos, int value, int add) { *pos = add ? *pos
 // One stage of the decoding loop on M rows: the kernel by row count.  `part` != nullptr (one row): the input row is the
 // merge of that attention's key-split partials.
 int launch_stage_rows(const RowLinArgs &a, const float *part, int ns, int hd, float *mf_ws, size_t mf_ws_floats, hipStream_t q_st) {
+  if (a.row_pos) {       // ragged batches: the two batched kernels, instantiated with per-row addressing
+    if (a.M > knobs().decode_mfma_rows && row_mfma_supported(a)) return launch_row_mfma<true>(a, q_st, mf_ws, mf_ws_floats);
+    if (row_gemvm_supported(a)) return launch_row_gemvm<true>(a, q_st);
+    return unsupported("decode stage: ragged rows need the batched kernels (K <= 2048)");
+  }
   if (row_gemv1_supported(a, part != nullptr)) return launch_row_gemv1(a, part, ns, hd, q_st);
   // batches: beyond `decode_mfma_rows` rows the stage is a tile GEMM on the fp32 matrix pipe; up to there every row in one
   // launch of the register-resident GEMV kernel (the rows pass through in groups)
@@ -1025,11 +1056,14 @@ struct SingleSourceArgs {
   const int *pos;              // replayable launches: the position from device memory (else `p`)
   int p, Cd, S_src, B, d;
   float eps;
+  const int *row_pos;          // RAG: row m at position row_pos[t * B + m], t = *pos or 0 (RowLinArgs.row_pos)
 };
 
+template <bool RAG = false>
 __global__ __launch_bounds__(64 * SS_ROWS) void single_source_cross_kernel(SingleSourceArgs a) {
   const int lane = threadIdx.x & 63, m = blockIdx.x * SS_ROWS + (threadIdx.x >> 6);
-  const int p = a.pos ? *a.pos : a.p;
+  if (RAG && m >= a.B) return;
+  const int p = RAG ? a.row_pos[(size_t)(a.pos ? *a.pos : 0) * a.B + m] : a.pos ? *a.pos : a.p;
   const int j = p / a.Cd;
   if (m >= a.B || j >= a.S_src) return;       // (j: checked on the host for every position of the call)
   const float *r = a.y1 + (size_t)m * a.d;
@@ -1071,7 +1105,8 @@ __global__ __launch_bounds__(64 * SS_ROWS) void single_source_cross_kernel(Singl
 }
 
 int launch_single_source_cross(const SingleSourceArgs &a, hipStream_t st) {
-  hipLaunchKernelGGL(single_source_cross_kernel, dim3((a.B + SS_ROWS - 1) / SS_ROWS), dim3(64 * SS_ROWS), 0, st, a);
+  if (a.row_pos) hipLaunchKernelGGL(single_source_cross_kernel<true>, dim3((a.B + SS_ROWS - 1) / SS_ROWS), dim3(64 * SS_ROWS), 0, st, a);
+  else hipLaunchKernelGGL(single_source_cross_kernel<false>, dim3((a.B + SS_ROWS - 1) / SS_ROWS), dim3(64 * SS_ROWS), 0, st, a);
   return check_launch("single_source_cross");
 }
 
@@ -1121,8 +1156,8 @@ struct DecodeGraphs {
 };
 static std::mutex &decode_graph_mutex() { static std::mutex m; return m; }
 // (called with the mutex held)  nullptr: no device / allocation failure -- the caller then launches directly
-static DecodeGraphs *decode_graphs_for(const isi_prior_w *w, const isi_prior_state *s, float temperature, int top_k, float top_p,
-                                       int W) {
+static DecodeGraphs *decode_graphs_for(const isi_prior_w *w, const isi_prior_state *s, const isi_prior_rows *rows,
+                                       float temperature, int top_k, float top_p, int W) {
   static std::vector<DecodeGraphs *> cache;
   static uint64_t clock_ = 0;
   int device = -1;
@@ -1137,6 +1172,14 @@ static DecodeGraphs *decode_graphs_for(const isi_prior_w *w, const isi_prior_sta
   std::memcpy(k, &sk, sizeof(isi_prior_state)); k += sizeof(isi_prior_state);
   std::memcpy(k, &kn, sizeof(Knobs)); k += sizeof(Knobs);
   std::memcpy(k, &tail, sizeof(Tail));
+  if (rows) {                                          // a ragged plan: its device arrays and sizes, not its host copies
+    isi_prior_rows rk = *rows;
+    rk.pos_host = nullptr;
+    rk.commit_host = nullptr;
+    const size_t at = key.size();
+    key.resize(at + sizeof(isi_prior_rows));
+    std::memcpy(key.data() + at, &rk, sizeof(isi_prior_rows));
+  }
   for (DecodeGraphs *g : cache)
     if (g->key == key) { g->used = ++clock_; return g; }
   if (cache.size() >= kDecodeGraphCacheMax) {
@@ -1163,14 +1206,18 @@ static DecodeGraphs *decode_graphs_for(const isi_prior_w *w, const isi_prior_sta
   return g;
 }
 
-int prior_sample_run(const isi_prior_w *w, const isi_prior_state *s, int p_begin, int p_end, float temperature,
-                     int top_k, float top_p, hipStream_t st) {
+// rows == nullptr: isi_prior_sample_run, p_begin / p_end are positions.  rows != nullptr: isi_prior_sample_run_rows, they
+// are steps of the plan (validated by the caller) and every position-dependent address is the row's own
+static int sample_run_impl(const isi_prior_w *w, const isi_prior_state *s, const isi_prior_rows *rows, int p_begin, int p_end,
+                           float temperature, int top_k, float top_p, hipStream_t st) {
+  const bool rag = rows != nullptr;
   if (!w || !s) return invalid("prior_sample_run: null pointer");
   if (w->n_layers <= 0 || w->n_layers > ISI_MAX_LAYERS) return invalid("prior_sample_run: bad layer count");
   if (s->B <= 0 || s->B > 256) return unsupported("prior_sample_run: batch size must be 1..256");
-  if (p_begin < 0 || p_end > s->S_t || p_begin > p_end) return invalid("prior_sample_run: bad position range");
+  if (p_begin < 0 || p_end > (rag ? rows->n_steps : s->S_t) || p_begin > p_end) return invalid("prior_sample_run: bad position range");
   const bool single_source = s->cross_out != nullptr;     // memory_kv is not read then
-  if (!s->x_seq || !s->kv_cache || (!single_source && !s->memory_kv) || !s->codes || !s->mask || !s->uniforms || !s->scratch)
+  if (!s->x_seq || !s->kv_cache || (!single_source && !s->memory_kv) || !s->codes || (!rag && !s->mask) || !s->uniforms ||
+      !s->scratch)
     return invalid("prior_sample_run: null state pointer");
   if (single_source) {
     if (w->Ce != 1) return unsupported("prior_sample_run: single-source cross-attention needs one source token per event (Ce == 1)");
@@ -1203,10 +1250,22 @@ int prior_sample_run(const isi_prior_w *w, const isi_prior_state *s, int p_begin
   // from *pos, so the same sequence can be captured once into a hipGraph and replayed per position.
   // `p` >= 0: direct launches, the position is passed by value (no dependent load of the counter at the head of
   // every kernel, no counter update); p < 0: replayable launches reading the device counter.
+  // Ragged plans: `p` / the device counter is the STEP t, and the rows' positions are rows->pos[t][.]: direct launches get the
+  // arrays offset to the step, replayable ones the arrays and the counter.
   auto enqueue_position = [&](bool sample, int p, hipStream_t q_st) -> int {
     const int *pos_arg = p < 0 ? pos : nullptr;
+    const int *row_pos = rag ? rows->pos + (p < 0 ? 0 : (size_t)p * B) : nullptr;
     // `part` != nullptr: the input row is the merge of that attention's key-split partials
     auto launch_rows = [&](RowLinArgs a, const float *part = nullptr, int ns = 1) -> int {
+      if (rag) {
+        if (a.x_pos || a.res_pos || a.out2_pos) {
+          a.row_pos = row_pos;
+          a.pos = pos_arg;
+        } else {
+          a.pos = nullptr;
+        }
+        return launch_stage_rows(a, part, ns, hd, mf_ws, mf_ws_floats, q_st);
+      }
       if (p >= 0) {
         a.x += (long)p * a.x_pos;
         if (a.res) a.res += (long)p * a.res_pos;
@@ -1220,7 +1279,7 @@ int prior_sample_run(const isi_prior_w *w, const isi_prior_state *s, int p_begin
     auto on_tiles = [&](const RowLinArgs &a) { return a.M > knobs().decode_mfma_rows && row_mfma_supported(a); };
     auto hand_stats = [&](RowLinArgs &producer, RowLinArgs &consumer, bool consumer_merges = false) {
       const bool tiles = on_tiles(producer) && on_tiles(consumer);
-      const bool one_row = row_gemv1_supported(producer, false) && row_gemv1_supported(consumer, consumer_merges);   // batch 1
+      const bool one_row = !rag && row_gemv1_supported(producer, false) && row_gemv1_supported(consumer, consumer_merges);   // batch 1
       // batches of up to `decode_mfma_rows` rows: the rows-in-registers kernel (launch_stage_rows picks it in this order)
       const bool few_rows = producer.M > 1 && producer.M <= knobs().decode_mfma_rows && row_gemvm_supported(producer) &&
                             row_gemvm_supported(consumer) && !consumer_merges;
@@ -1231,7 +1290,7 @@ int prior_sample_run(const isi_prior_w *w, const isi_prior_state *s, int p_begin
     };
     // the attention's splits are merged by the out-projection when that runs as the one-row kernel
     const int ns_self = rel_attention_decode_splits(s->S_t, B * w->nhead), ns_cross = rel_attention_decode_splits(s->S_src, B * w->nhead);
-    const bool merge_in_gemv = B == 1 && d <= 512 && (d & 3) == 0;
+    const bool merge_in_gemv = !rag && B == 1 && d <= 512 && (d & 3) == 0;
     const float *yin = s->x_seq;     // + p * B * d through x_pos / res_pos
     long yin_pos = (long)B * d;
     const float *ln_g = nullptr, *ln_b = nullptr;
@@ -1257,7 +1316,7 @@ int prior_sample_run(const isi_prior_w *w, const isi_prior_state *s, int p_begin
       g.v_ss = g.k_ss; g.v_sb = g.k_sb; g.v_sh = hd; g.o_sb = d; g.o_sh = hd;
       g.Cq = w->Cd; g.Ck = w->Cd; g.Ek = w->Ed; g.rel_rows = L.self_attn.rel_rows; g.scale = scale;
       const bool defer_s = merge_in_gemv && ns_self > 1;
-      if ((rc = rel_attention_decode_launch(&g, p < 0 ? 0 : p, pos_arg, 1, attn_ws, defer_s ? 0 : 1, q_st))) return rc;
+      if ((rc = rel_attention_decode_launch(&g, p < 0 ? 0 : p, pos_arg, 1, attn_ws, defer_s ? 0 : 1, q_st, row_pos))) return rc;
       if ((rc = defer_s ? launch_rows(a_o, attn_ws, ns_self) : launch_rows(a_o))) return rc;
       // feed-forward on LN2(y2)
       RowLinArgs a_f1{y2, d, L.norm2_w, L.norm2_b, L.linear1_w, L.linear1_b, nullptr, 0, nullptr, nullptr, hid, ff,
@@ -1268,7 +1327,7 @@ int prior_sample_run(const isi_prior_w *w, const isi_prior_state *s, int p_begin
         // y2 = LN1(y1) + T_l[p / Cd]: one launch for the cross-attention block; y2's statistics go to linear2
         const bool handoff = !knobs().decode_no_stat_handoff;
         const SingleSourceArgs ss{y1, L.norm1_w, L.norm1_b, s->cross_out + (size_t)l * s->S_src * B * d, y2,
-                                  handoff ? rowstat : nullptr, pos_arg, p < 0 ? 0 : p, w->Cd, s->S_src, B, d, 1e-5f};
+                                  handoff ? rowstat : nullptr, pos_arg, p < 0 ? 0 : p, w->Cd, s->S_src, B, d, 1e-5f, row_pos};
         if ((rc = launch_single_source_cross(ss, q_st))) return rc;
         if (handoff) a_f2.res_stat = rowstat;
       } else {
@@ -1283,7 +1342,7 @@ int prior_sample_run(const isi_prior_w *w, const isi_prior_state *s, int p_begin
         g.k = memkv; g.v = memkv + d; g.rel_embeddings = L.cross_attn.rel_embeddings; g.Sk = s->S_src;
         g.Ck = w->Ce; g.Ek = w->Ee; g.rel_rows = L.cross_attn.rel_rows;
         const bool defer_c = merge_in_gemv && ns_cross > 1;
-        if ((rc = rel_attention_decode_launch(&g, p < 0 ? 0 : p, pos_arg, 0, attn_ws, defer_c ? 0 : 1, q_st))) return rc;
+        if ((rc = rel_attention_decode_launch(&g, p < 0 ? 0 : p, pos_arg, 0, attn_ws, defer_c ? 0 : 1, q_st, row_pos))) return rc;
         if ((rc = defer_c ? launch_rows(a_o2, attn_ws, ns_cross) : launch_rows(a_o2))) return rc;
         hand_stats(a_f1, a_f2);
       }
@@ -1298,11 +1357,13 @@ int prior_sample_run(const isi_prior_w *w, const isi_prior_state *s, int p_begin
       int rc;
       if ((rc = launch_rows(a))) return rc;
       // (a replayed position of ONE sequence: the commit also advances the position counter)
-      const bool fold_advance = p < 0 && B == 1;
+      const bool fold_advance = !rag && p < 0 && B == 1;
       const SampleCommit cm{w->embed_table, w->eff_dim, s->codes, s->S, p, i_off, s->S_t, s->x_seq, d, fold_advance ? pos : nullptr};
+      SampleRows sr{row_pos, rag ? rows->commit + (p < 0 ? 0 : (size_t)p * B) : nullptr, rag ? rows->temperature : nullptr,
+                    rag ? rows->top_k : nullptr, rag ? rows->top_p : nullptr, s->S};
       if ((rc = sample_row_commit_f32(logits, w->n_class, B, w->n_class, temperature, top_k, top_p,
-                                      p < 0 ? s->uniforms : s->uniforms + (size_t)(p - i_off) * B, sampled, nullptr, pos_arg,
-                                      i_off, cm, q_st)))
+                                      (p < 0 || rag) ? s->uniforms : s->uniforms + (size_t)(p - i_off) * B, sampled, nullptr,
+                                      pos_arg, i_off, cm, q_st, rag ? &sr : nullptr)))
         return rc;
       if (fold_advance) return ISI_OK;
     }
@@ -1311,6 +1372,10 @@ int prior_sample_run(const isi_prior_w *w, const isi_prior_state *s, int p_begin
     return check_launch("advance_position");
   };
   auto sampled_at = [&](int p) {
+    if (rag) {             // some row commits at step p
+      for (int b = 0; b < B; ++b) if (rows->commit_host[(size_t)p * B + b]) return true;
+      return false;
+    }
     const int i = p - i_off;
     return i >= 0 && i < s->S && s->mask[i];
   };
@@ -1340,7 +1405,7 @@ int prior_sample_run(const isi_prior_w *w, const isi_prior_state *s, int p_begin
     // point.  At most kDecodeGraphCacheMax argument sets are kept; the least recently used one is dropped once the event
     // recorded behind its last replay has passed.
     std::lock_guard<std::mutex> lock(decode_graph_mutex());
-    DecodeGraphs *G = decode_graphs_for(w, s, temperature, top_k, top_p, W);
+    DecodeGraphs *G = decode_graphs_for(w, s, rows, temperature, top_k, top_p, W);
     hipStream_t cap = nullptr;
     bool ok = G != nullptr;
     auto build = [&](int k) -> bool {      // k = 1: every position of the window samples
@@ -1384,6 +1449,36 @@ int prior_sample_run(const isi_prior_w *w, const isi_prior_state *s, int p_begin
   for (; p < p_end; ++p)
     if ((rc = enqueue_position(sampled_at(p), p, st))) return rc;
   return ISI_OK;
+}
+
+int prior_sample_run(const isi_prior_w *w, const isi_prior_state *s, int p_begin, int p_end, float temperature,
+                     int top_k, float top_p, hipStream_t st) {
+  return sample_run_impl(w, s, nullptr, p_begin, p_end, temperature, top_k, top_p, st);
+}
+
+// Ragged batches: the plan is checked on the host, from its host copies, before anything is launched.
+int prior_sample_run_rows(const isi_prior_w *w, const isi_prior_state *s, const isi_prior_rows *rows, int t_begin, int t_end,
+                          float temperature, int top_k, float top_p, hipStream_t st) {
+  if (!w || !s || !rows) return invalid("prior_sample_run_rows: null pointer");
+  if (s->B <= 0 || s->B > 256) return unsupported("prior_sample_run_rows: batch size must be 1..256");
+  if (!rows->pos || !rows->commit || !rows->pos_host || !rows->commit_host) return invalid("prior_sample_run_rows: null plan pointer");
+  if (rows->n_steps < 0 || t_begin < 0 || t_end > rows->n_steps || t_begin > t_end) return invalid("prior_sample_run_rows: bad step range");
+  if (w->d_model > 2048) return unsupported("prior_sample_run_rows: ragged rows need d_model <= 2048");
+  const int B = s->B, i_off = s->start_len - 1;
+  for (int t = 0; t < rows->n_steps; ++t) {
+    for (int b = 0; b < B; ++b) {
+      const size_t tb = (size_t)t * B + b;
+      const int p = rows->pos_host[tb];
+      if (p < 0 || p >= s->S_t) return invalid("prior_sample_run_rows: a position outside [0, S_t)");
+      if (t > 0) {
+        const int dp = p - rows->pos_host[tb - B];
+        if (dp != 0 && dp != 1) return invalid("prior_sample_run_rows: a row moves by other than 0 or 1 position per step");
+      }
+      if (rows->commit_host[tb] && (p - i_off < 0 || p - i_off >= s->S))
+        return invalid("prior_sample_run_rows: a commit outside the token range [0, S)");
+    }
+  }
+  return sample_run_impl(w, s, rows, t_begin, t_end, temperature, top_k, top_p, st);
 }
 
 }  // namespace isi

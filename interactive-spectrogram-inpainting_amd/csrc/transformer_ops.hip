@@ -183,13 +183,15 @@ int linear_rows_f32(const float *x, int x_stride, const float *W, const float *b
 // kernel (4.7 us + a dispatch gap, 16 times per decoding step of a batch of 17 .. 63 sequences) and the round trip of the
 // partials through memory go away.  The two halves take the same path (by the split length, not by their own key count)
 // and an empty half walks it with zero keys: every barrier is met by all 512 threads.
-template <int HD, int NG = 1>
+// RAG (ragged batches): row b = blockIdx.y queries from its own position row_pos[t * gridDim.y + b] (t = *pos, or 0 with
+// row_pos already offset to the step); its self-attention key count and split length follow from that position.
+template <int HD, int NG = 1, bool RAG = false>
 __global__ __launch_bounds__(256 * NG) void rel_attention_decode_f32_kernel(
     const float *__restrict__ q, const float *__restrict__ k, const float *__restrict__ v,
     const float *__restrict__ e, float *__restrict__ out, int Sk, int64_t q_sb, int64_t q_sh, int64_t k_ss,
     int64_t k_sb, int64_t k_sh, int64_t v_ss, int64_t v_sb, int64_t v_sh, int64_t o_sb, int64_t o_sh,
     int q_pos, int Cq, int Ck, int Ek, int R, float scale, int chunk, float *__restrict__ partial,
-    const int *__restrict__ pos, int self_keys) {
+    const int *__restrict__ pos, int self_keys, const int *__restrict__ row_pos) {
   // (every argument "used" here: the compiler otherwise fetches them in four dependent scalar-memory round trips ahead of
   // the first key request -- prior_decode.hip: touch_args)
   asm volatile("" ::"s"(q), "s"(k), "s"(v), "s"(e), "s"(out), "s"(Sk), "s"(q_sb), "s"(q_sh), "s"(k_ss), "s"(k_sb), "s"(k_sh),
@@ -199,7 +201,13 @@ __global__ __launch_bounds__(256 * NG) void rel_attention_decode_f32_kernel(
   // Replayable form (hipGraph): the position comes from device memory; for self-attention the key
   // count is position + 1 and the (fixed) number of splits shares it evenly.
   const int nsplit = NG == 2 ? 2 : (int)gridDim.z;
-  if (pos) {
+  if constexpr (RAG) {
+    q_pos = row_pos[(size_t)(pos ? *pos : 0) * gridDim.y + blockIdx.y];
+    if (self_keys) {
+      Sk = q_pos + 1;
+      chunk = (Sk + nsplit - 1) / nsplit;
+    }
+  } else if (pos) {
     q_pos = *pos;
     if (self_keys) {
       Sk = q_pos + 1;
@@ -464,14 +472,14 @@ int rel_attention_decode_pos_f32(const isi_attn_args *g, int q_pos, const int *p
 // split's maximum and sum) stay in `workspace` for the caller to merge (the decoding loop merges them in the prologue
 // of the out-projection: one dependent launch less); g->out is then not written.
 int rel_attention_decode_launch(const isi_attn_args *g, int q_pos, const int *pos, int self_keys, float *workspace,
-                                int combine, hipStream_t stream) {
+                                int combine, hipStream_t stream, const int *row_pos) {
   if (!g || !g->q || !g->k || !g->v || !g->out) return invalid("attention_decode: null pointer");
   if (g->Sk <= 0 || g->B <= 0 || g->H <= 0 || g->Cq <= 0 || g->Ck <= 0) return invalid("attention_decode: bad shape");
   if (g->Sk > 65536) return unsupported("attention_decode: more than 65536 keys");
   const int ns = workspace ? rel_attention_decode_splits(g->Sk, g->B * g->H) : 1;
   // self_keys with the position by value: position + 1 keys, shared by the split count of the upper bound g->Sk
   // (the same split as the replayable form derives on the device)
-  const int Sk = (self_keys && !pos) ? q_pos + 1 : g->Sk;
+  const int Sk = (self_keys && !pos && !row_pos) ? q_pos + 1 : g->Sk;
   if (Sk > g->Sk) return invalid("attention_decode: position beyond the key capacity");
   const int chunk = (Sk + ns - 1) / ns;
   // two splits that are merged right away: both in one workgroup, no partials, no combine launch (NG = 2)
@@ -484,7 +492,8 @@ int rel_attention_decode_launch(const isi_attn_args *g, int q_pos, const int *po
   dim3 grid(g->H, g->B, both ? 1 : ns), block(both ? 512 : 256);
 #define ISI_DEC(HD)                                                                                         \
   do {                                                                                                      \
-    auto kern = both ? rel_attention_decode_f32_kernel<HD, 2> : rel_attention_decode_f32_kernel<HD, 1>;     \
+    auto kern = row_pos ? (both ? rel_attention_decode_f32_kernel<HD, 2, true> : rel_attention_decode_f32_kernel<HD, 1, true>) \
+                        : (both ? rel_attention_decode_f32_kernel<HD, 2> : rel_attention_decode_f32_kernel<HD, 1>); \
     if (smem > 48 * 1024 &&                                                                                 \
         hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
                             (int)smem) != hipSuccess)                                                       \
@@ -492,7 +501,7 @@ int rel_attention_decode_launch(const isi_attn_args *g, int q_pos, const int *po
     hipLaunchKernelGGL(kern, grid, block, smem, stream, g->q, g->k, g->v, g->rel_embeddings, g->out, Sk,    \
                        g->q_sb, g->q_sh, g->k_ss, g->k_sb, g->k_sh, g->v_ss, g->v_sb, g->v_sh, g->o_sb,     \
                        g->o_sh, q_pos, g->Cq, g->Ck, g->Ek, g->rel_rows, g->scale, chunk, workspace, pos,  \
-                       self_keys);                                                                          \
+                       self_keys, row_pos);                                                                 \
   } while (0)
   switch (g->head_dim) {
     case 16: ISI_DEC(16); break;
@@ -540,14 +549,29 @@ __device__ __forceinline__ float block_inclusive_scan(float v, float *wave_tot, 
   return pre + v;
 }
 
+template <bool RAG = false>
 __global__ __launch_bounds__(1024) void sample_row_f32_kernel(const float *__restrict__ logits, int stride,
                                                               int n, float inv_temperature, int top_k,
                                                               float top_p, const float *__restrict__ u,
                                                               int64_t *__restrict__ out,
                                                               float *__restrict__ filtered,
                                                               const int *__restrict__ pos, int pos_off,
-                                                              const SampleCommit cm) {
-  if (pos) u += (size_t)(*pos - pos_off) * gridDim.x;  // replayable launch: this token's uniforms
+                                                              const SampleCommit cm, const SampleRows rg) {
+  float ur = 0.f;          // this row's uniform
+  int rp = 0;              // RAG: the row's position
+  bool commit = true;
+  if constexpr (RAG) {     // (one row per workgroup: the row's parameters are uniform over the block)
+    const size_t tr = (size_t)(pos ? *pos : 0) * gridDim.x + blockIdx.x;
+    rp = rg.row_pos[tr];
+    const int i = rp - pos_off;
+    commit = rg.commit[tr] && i >= 0 && i < rg.S;
+    if (commit) ur = u[(size_t)i * gridDim.x + blockIdx.x];
+    if (rg.temperature) inv_temperature = 1.0f / rg.temperature[blockIdx.x];
+    if (rg.top_k) top_k = rg.top_k[blockIdx.x];
+    if (rg.top_p) top_p = rg.top_p[blockIdx.x];
+  } else {
+    if (pos) u += (size_t)(*pos - pos_off) * gridDim.x;  // replayable launch: this token's uniforms
+  }
   __shared__ float val[1024];
   __shared__ int idx[1024];
   __shared__ int keep[1024];
@@ -625,12 +649,13 @@ __global__ __launch_bounds__(1024) void sample_row_f32_kernel(const float *__res
   const float inc = block_inclusive_scan(pe, wave_tot, &total);
   if (tid == 0) sh_i = n - 1;
   __syncthreads();
-  if (tid < n && inc > u[row] * total) atomicMin(&sh_i, tid);
+  if constexpr (!RAG) ur = u[row];
+  if (tid < n && inc > ur * total) atomicMin(&sh_i, tid);
   __syncthreads();
   if (tid == 0) out[row] = sh_i;
   // the decoding loop's commit, in the same launch: code row, and the token's embedding into the next input row
-  if (cm.table) {
-    const int p = pos ? *pos : cm.p_value;
+  if (cm.table && commit) {
+    const int p = RAG ? rp : pos ? *pos : cm.p_value;
     const int tok = sh_i;
     if (tid == 0) cm.codes[(size_t)row * cm.codes_stride + (p - cm.i_off)] = tok;
     if (p + 1 < cm.S_t) {
@@ -661,14 +686,22 @@ int sample_row_pos_f32(const float *logits, int stride, int rows, int n, float t
 
 int sample_row_commit_f32(const float *logits, int stride, int rows, int n, float temperature, int top_k, float top_p,
                           const float *u, int64_t *out, float *filtered, const int *pos, int pos_off,
-                          const SampleCommit &cm, hipStream_t stream) {
+                          const SampleCommit &cm, hipStream_t stream, const SampleRows *ragged) {
   if (!logits || !u || !out || rows <= 0 || n <= 0 || temperature <= 0.f) return invalid("sample_row: bad argument");
   if (n > 1024) return unsupported("sample_row: at most 1024 classes");
   if (cm.advance && (rows != 1 || !cm.table)) return invalid("sample_row: the position counter is advanced by a one-row commit only");
   int np = 64;
   while (np < n) np <<= 1;
-  hipLaunchKernelGGL(sample_row_f32_kernel, dim3(rows), dim3(np), 0, stream, logits, stride, n, 1.0f / temperature,
-                     top_k, top_p, u, out, filtered, pos, pos_off, cm);
+  if (ragged) {
+    if (!ragged->row_pos || !ragged->commit || !cm.table || cm.advance) return invalid("sample_row: bad ragged commit");
+    hipLaunchKernelGGL(sample_row_f32_kernel<true>, dim3(rows), dim3(np), 0, stream, logits, stride, n, 1.0f / temperature,
+                       top_k, top_p, u, out, filtered, pos, pos_off, cm, *ragged);
+    return check_launch("sample_row_f32 (ragged)");
+  }
+  SampleRows none_rows;
+  memset(&none_rows, 0, sizeof none_rows);
+  hipLaunchKernelGGL(sample_row_f32_kernel<false>, dim3(rows), dim3(np), 0, stream, logits, stride, n, 1.0f / temperature,
+                     top_k, top_p, u, out, filtered, pos, pos_off, cm, none_rows);
   return check_launch("sample_row_f32");
 }
 

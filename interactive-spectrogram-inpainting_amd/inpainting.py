@@ -6,6 +6,7 @@ routes (flask_server.py), free of HTTP so that they can be called, tested and ti
   timerange_change    regenerate the masked zone of the top (and then bottom) or of the bottom
                       codemap inside the window starting at `start_index_top`
                       (flask_server.py:685-870)
+  timerange_change_batch   independent timerange_change requests in one ragged top and one ragged bottom call
   erase               attenuate the log-magnitude under the mask and re-encode (:873-931)
   generate            new top + bottom codemaps from scratch (:376-443)
   codes_to_audio      VQ-VAE decode + spectrogram inversion (:1003-1021)
@@ -21,7 +22,7 @@ from __future__ import annotations
 
 import struct
 import zlib
-from typing import List, Mapping, Optional, Tuple
+from typing import List, Mapping, Optional, Sequence, Tuple
 
 import torch
 
@@ -92,6 +93,88 @@ def timerange_change(transformer_top, transformer_bottom, top_code: torch.Tensor
     else:
         raise ValueError(f"unknown layer {layer}")
     return top_code, bottom_code
+
+
+def _cat_classes(dicts) -> Mapping[str, torch.Tensor]:
+    return {k: torch.cat([torch.as_tensor(d[k]).long().reshape(-1) for d in dicts]) for k in dicts[0]}
+
+
+@torch.no_grad()
+def timerange_change_batch(transformer_top, transformer_bottom, requests: Sequence[Mapping], device
+                           ) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+    """Independent `timerange_change` requests in at most two ragged `sample_model` calls: every `layer='top'` request
+    through the top prior together, then every request through the bottom prior together (a top request with the mask
+    up-sampled over its new top map).  A request is a mapping with the arguments of `timerange_change` -- top_code,
+    bottom_code, mask, layer, start_index_top, temperature, class_conditioning_top, class_conditioning_bottom and
+    optionally top_k_sampling_k, top_p_sampling_p, uniform_sampling -- and its own `generator`, from which its uniforms
+    are drawn in the order `timerange_change` draws them (top stage, then bottom): result r equals `timerange_change` of
+    request r alone with an equally seeded generator.  Returns one (top, bottom) pair per request."""
+    ratio_f = transformer_bottom.shape[0] // transformer_top.shape[0]
+    jobs = []
+    for r in requests:
+        if r['layer'] not in ('top', 'bottom'):
+            raise ValueError(f"unknown layer {r['layer']}")
+        (s_top, e_top), (s_bot, e_bot), ratio_t = _windows(r['top_code'], r['bottom_code'], transformer_top,
+                                                            transformer_bottom, r['start_index_top'])
+        jobs.append(dict(req=r, top=r['top_code'].clone(), bottom=r['bottom_code'].clone(), s_top=s_top, e_top=e_top,
+                         s_bot=s_bot, e_bot=e_bot, ratio_t=ratio_t, mask=r['mask'].to(device), g=r.get('generator'),
+                         ti_top=make_time_indexes(s_top, r['top_code'].shape[-1], transformer_top.shape[-1]),
+                         ti_bottom=make_time_indexes(s_bot, r['bottom_code'].shape[-1], transformer_bottom.shape[-1])))
+
+    def run(model, batch, condition, initial, masks, cls_key, ti_src, ti_tgt, uniforms):
+        req = [j['req'] for j in batch]
+        return sample_model(
+            model=model, device=device, batch_size=len(batch), codemap_size=model.shape,
+            temperature=[float(q['temperature']) for q in req],
+            condition=torch.cat(condition) if condition is not None else None,
+            class_conditioning=_cat_classes([q[cls_key] for q in req]), initial_code=torch.cat(initial).to(device),
+            mask=torch.cat(masks).to(device), time_indexes_source=torch.tensor(ti_src),
+            time_indexes_target=torch.tensor(ti_tgt),
+            top_k_sampling_k=[int(q.get('top_k_sampling_k', 0)) for q in req],
+            top_p_sampling_p=[float(q.get('top_p_sampling_p', 0.0)) for q in req],
+            uniforms=torch.cat(uniforms, 1))
+
+    def draw(model, j, frame):        # timerange_change's draws from the request's generator, in its order
+        if j['req'].get('uniform_sampling', False):
+            return torch.randint(0, model.n_class_target, frame.shape, generator=j['g'])
+        return torch.rand(model.target_transformer_sequence_length, 1, generator=j['g'])
+
+    # stage 1: the top prior, every layer='top' request in one ragged call
+    tops = [j for j in jobs if j['req']['layer'] == 'top']
+    for j in tops:
+        frame = j['top'][..., j['s_top']:j['e_top']]
+        d = draw(transformer_top, j, frame)
+        if j['req'].get('uniform_sampling', False):
+            j['top'][..., j['s_top']:j['e_top']] = torch.where(j['mask'], d.to(frame.device), frame)
+        else:
+            j['u_top'] = d
+    sampled = [j for j in tops if 'u_top' in j]
+    if sampled:
+        frames = [j['top'][..., j['s_top']:j['e_top']] for j in sampled]
+        new_top = run(transformer_top, sampled, frames if transformer_top.self_conditional_model else None, frames,
+                      [j['mask'] for j in sampled], 'class_conditioning_top', [j['ti_top'] for j in sampled],
+                      [j['ti_top'] for j in sampled], [j['u_top'] for j in sampled])
+        for k, j in enumerate(sampled):
+            j['top'][..., j['s_top']:j['e_top']] = new_top[k:k + 1].to(j['top'].device)
+    # stage 2: the bottom prior, every request in one ragged call
+    for j in jobs:
+        if j['req']['layer'] == 'top':
+            j['mask'] = j['mask'].repeat_interleave(ratio_f, -2).repeat_interleave(j['ratio_t'], -1)
+        frame = j['bottom'][..., j['s_bot']:j['e_bot']]
+        d = draw(transformer_bottom, j, frame)
+        if j['req'].get('uniform_sampling', False):
+            j['bottom'][..., j['s_bot']:j['e_bot']] = torch.where(j['mask'], d.to(frame.device), frame)
+        else:
+            j['u_bot'] = d
+    sampled = [j for j in jobs if 'u_bot' in j]
+    if sampled:
+        new_bottom = run(transformer_bottom, sampled, [j['top'][..., j['s_top']:j['e_top']] for j in sampled],
+                         [j['bottom'][..., j['s_bot']:j['e_bot']] for j in sampled], [j['mask'] for j in sampled],
+                         'class_conditioning_bottom', [j['ti_top'] for j in sampled], [j['ti_bottom'] for j in sampled],
+                         [j['u_bot'] for j in sampled])
+        for k, j in enumerate(sampled):
+            j['bottom'][..., j['s_bot']:j['e_bot']] = new_bottom[k:k + 1].to(j['bottom'].device)
+    return [(j['top'], j['bottom']) for j in jobs]
 
 
 @torch.no_grad()

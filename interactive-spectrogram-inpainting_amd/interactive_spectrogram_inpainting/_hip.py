@@ -125,6 +125,11 @@ class isi_prior_state(C.Structure):
                 ("B", C.c_int), ("start_len", C.c_int), ("cross_out", C.c_void_p)]
 
 
+class isi_prior_rows(C.Structure):
+    _fields_ = [("pos", C.c_void_p), ("commit", C.c_void_p), ("pos_host", C.c_void_p), ("commit_host", C.c_void_p),
+                ("temperature", C.c_void_p), ("top_k", C.c_void_p), ("top_p", C.c_void_p), ("n_steps", C.c_int)]
+
+
 class isi_reduce_job(C.Structure):
     _fields_ = [("partial", C.c_void_p), ("out", C.c_void_p), ("n", C.c_int64), ("stride", C.c_int64),
                 ("nsplit", C.c_int32), ("accumulate", C.c_int32), ("vec", C.c_int32),
@@ -218,6 +223,8 @@ SIGNATURES = {
     "isi_prior_decode_scratch_floats": (C.c_size_t, [C.POINTER(isi_prior_w), C.c_int]),
     "isi_prior_sample_run": (C.c_int, [C.POINTER(isi_prior_w), C.POINTER(isi_prior_state), C.c_int, C.c_int,
                                        C.c_float, C.c_int, C.c_float, _P]),
+    "isi_prior_sample_run_rows": (C.c_int, [C.POINTER(isi_prior_w), C.POINTER(isi_prior_state), C.POINTER(isi_prior_rows),
+                                            C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, _P]),
     "isi_conv_wgrad_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "isi_conv_wgrad_f32": (C.c_int, [C.POINTER(isi_src), C.POINTER(isi_src), _P, _P, _P, _P, C.c_size_t, C.c_int,
                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
@@ -289,7 +296,7 @@ def lib() -> C.CDLL:
                     fn.argtypes = args
                 structs = [isi_src, isi_dst, isi_conv_w, isi_encoder_w, isi_decoder_w, isi_codebook_w,
                            isi_vqvae_w, isi_vqvae_out, isi_attn_args, isi_prior_w, isi_prior_state, isi_attn_bwd_args,
-                           isi_reduce_job]
+                           isi_reduce_job, isi_prior_rows]
                 for i, st in enumerate(structs):
                     if handle.isi_abi_struct_bytes(i) != C.sizeof(st):
                         raise HipLibraryError(f"ABI mismatch for {st.__name__}: library "

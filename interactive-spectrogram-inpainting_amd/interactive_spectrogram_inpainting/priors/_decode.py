@@ -233,3 +233,40 @@ class NativeSampler:
                                              float(temperature), int(top_k), float(top_p),
                                              C.c_void_p(_hip.stream_ptr(self.x_seq.device)))
         _hip.check(rc, "isi_prior_sample_run")
+
+    def plan_rows(self, pos, commit, temperature=None, top_k=None, top_p=None) -> int:
+        """A ragged plan (`isi_prior_sample_run_rows`): pos / commit [n_steps, B] host arrays -- row b stands at decoder
+        position pos[t, b] in step t and draws its token there where commit[t, b]; optional per-row temperature / top-k /
+        top-p tensors [B].  Returns the number of steps."""
+        import numpy as np
+        C, _hip = self._C, self._hip
+        dev = self.x_seq.device
+        self.pos_host = np.ascontiguousarray(np.asarray(pos, dtype=np.int32))
+        self.commit_host = np.ascontiguousarray(np.asarray(commit, dtype=np.uint8))
+        if self.pos_host.ndim != 2 or self.pos_host.shape != self.commit_host.shape or self.pos_host.shape[1] != self.state.B:
+            raise ValueError(f"ragged plan: pos {self.pos_host.shape} / commit {self.commit_host.shape} for a batch of "
+                             f"{self.state.B}")
+        self.pos_dev = torch.from_numpy(self.pos_host).to(dev)
+        self.commit_dev = torch.from_numpy(self.commit_host).to(dev)
+        r = _hip.isi_prior_rows()
+        r.pos, r.commit = self.pos_dev.data_ptr(), self.commit_dev.data_ptr()
+        r.pos_host, r.commit_host = self.pos_host.ctypes.data, self.commit_host.ctypes.data
+        self.row_params = []
+        for name, value, dtype in (("temperature", temperature, torch.float32), ("top_k", top_k, torch.int32),
+                                   ("top_p", top_p, torch.float32)):
+            if value is not None:
+                t = torch.as_tensor(value).to(device=dev, dtype=dtype).reshape(-1).contiguous()
+                self.row_params.append(t)
+                setattr(r, name, t.data_ptr())
+        r.n_steps = self.pos_host.shape[0]
+        self.rows = r
+        return r.n_steps
+
+    @torch.no_grad()
+    def run_rows(self, t_begin: int, t_end: int, temperature: float, top_k: int, top_p: float) -> None:
+        """Steps [t_begin, t_end) of the plan set by `plan_rows`; the scalars stand for rows without per-row values."""
+        C, _hip = self._C, self._hip
+        rc = _hip.lib().isi_prior_sample_run_rows(C.byref(self.w), C.byref(self.state), C.byref(self.rows), t_begin, t_end,
+                                                  float(temperature), int(top_k), float(top_p),
+                                                  C.c_void_p(_hip.stream_ptr(self.x_seq.device)))
+        _hip.check(rc, "isi_prior_sample_run_rows")

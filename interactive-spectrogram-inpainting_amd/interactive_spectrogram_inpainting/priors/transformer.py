@@ -428,6 +428,12 @@ class VQNSynthTransformer(nn.Module):
         else:
             raise ValueError(f"Unexpected value {kind} for kind option")
         pos = pos.reshape(1, F_, T_, -1)
+        if torch.is_tensor(time_indexes) and time_indexes.dim() == 2:
+            # one list per row ([B, T]: independent requests of a ragged batch, each window at its own place)
+            if time_indexes.shape[0] != batch_size:
+                raise ValueError(f"time indexes for {time_indexes.shape[0]} rows, batch of {batch_size}")
+            pos = pos[0][:, time_indexes.long().to(pos.device), :].permute(1, 0, 2, 3)       # [B, F, T, dim]
+            return torch.cat([sequence, helper.to_sequence(pos.to(sequence.device))], dim=embedding_dim)
         if time_indexes is not None:
             pos = pos[:, :, list(time_indexes), :]
         pos_seq = helper.to_sequence(pos.to(sequence.device)).expand(batch_size, -1, -1)

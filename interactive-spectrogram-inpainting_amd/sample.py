@@ -15,8 +15,9 @@ instead of torch.multinomial's stream.
 """
 from __future__ import annotations
 
-from typing import Iterable, Mapping, Optional, Union
+from typing import Iterable, Mapping, Optional, Sequence, Union
 
+import numpy as np
 import torch
 
 from interactive_spectrogram_inpainting.priors import _ops
@@ -37,23 +38,74 @@ def top_k_top_p_filtering(logits: torch.Tensor, top_k: int = 0, top_p: float = 0
     return logits
 
 
+def _per_row(value, batch_size: int, name: str):
+    """A sampling parameter given once or per row: (scalar, None) when every row shares it, else (first, tensor [B])."""
+    if not torch.is_tensor(value) and not isinstance(value, (list, tuple, np.ndarray)):
+        return value, None
+    t = torch.as_tensor(value).reshape(-1).cpu()
+    if t.numel() != batch_size:
+        raise ValueError(f"{name}: {t.numel()} values for a batch of {batch_size}")
+    if bool((t == t[0]).all()):
+        return t[0].item(), None
+    return t[0].item(), t
+
+
+def _ragged_plan(mask_rows: np.ndarray, i_off: int):
+    """Steps of a ragged batch: row b walks from the decoder position of its first masked token to that of its last, one
+    position per step, then idles at its last position; it commits where its own token is masked.  A row with nothing
+    masked idles at position 0 and never commits.  Returns (pos, commit) [n_steps, B] and the prefill length."""
+    B = mask_rows.shape[0]
+    spans = []
+    for b in range(B):
+        idx = np.flatnonzero(mask_rows[b])
+        spans.append((idx[0] + i_off, idx[-1] + i_off + 1) if idx.size else None)
+    n_steps = max((e - f for f, e in (sp for sp in spans if sp)), default=0)
+    prefill = max((f for f, _ in (sp for sp in spans if sp)), default=0)
+    t = np.arange(n_steps)[:, None]
+    pos = np.zeros((n_steps, B), dtype=np.int32)
+    commit = np.zeros((n_steps, B), dtype=np.uint8)
+    for b, sp in enumerate(spans):
+        if sp is None:
+            continue
+        f, e = sp
+        p = np.minimum(f + t[:, 0], e - 1)
+        pos[:, b] = p
+        commit[:, b] = (t[:, 0] < e - f) & mask_rows[b][p - i_off]
+    return pos, commit, prefill
+
+
 @torch.no_grad()
 def sample_model(model: VQNSynthTransformer, device: Union[torch.device, str], batch_size: int,
-                 codemap_size: Iterable[int], temperature: float,
+                 codemap_size: Iterable[int], temperature: Union[float, Sequence[float], torch.Tensor],
                  condition: Optional[torch.Tensor] = None, constraint: Optional[torch.Tensor] = None,
                  class_conditioning: Mapping[str, Iterable[int]] = {},
                  initial_code: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
                  local_class_conditioning_map=None,
                  time_indexes_source: Optional[Iterable[int]] = None,
                  time_indexes_target: Optional[Iterable[int]] = None,
-                 top_k_sampling_k: int = 0, top_p_sampling_p: float = 0.0,
+                 top_k_sampling_k: Union[int, Sequence[int], torch.Tensor] = 0,
+                 top_p_sampling_p: Union[float, Sequence[float], torch.Tensor] = 0.0,
                  progressbar_decorator=None, use_predictive_sampling: bool = False,
                  generator: Optional[torch.Generator] = None,
                  uniforms: Optional[torch.Tensor] = None,
                  gumbel_noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Ragged batches: rows are independent requests.  `mask` [B, F, T] may differ per row (each row walks its own span),
+    `time_indexes_source` / `time_indexes_target` may be [B, T] tensors, and `temperature`, `top_k_sampling_k`,
+    `top_p_sampling_p` may be length-B sequences or tensors.  A [1, F, T] mask or one whose rows are all equal, with
+    shared parameters, samples exactly as a single request does."""
     if constraint is not None:
         raise NotImplementedError
     device = torch.device(device)
+    if mask is not None and mask.dim() == 3 and mask.shape[0] not in (1, batch_size):
+        raise ValueError(f"mask for {mask.shape[0]} rows, batch of {batch_size}")
+    rows_differ = (mask is not None and mask.dim() == 3 and mask.shape[0] > 1 and
+                   not bool((mask == mask[:1]).all()))
+    if use_predictive_sampling and rows_differ:
+        raise ValueError("predictive sampling decodes every row at the same positions: the rows' masks must be equal")
+    row_params = [_per_row(v, batch_size, n) for v, n in ((temperature, "temperature"), (top_k_sampling_k, "top_k_sampling_k"),
+                                                        (top_p_sampling_p, "top_p_sampling_p"))]
+    if use_predictive_sampling and any(t is not None for _, t in row_params):
+        raise ValueError("predictive sampling takes one temperature / top-k / top-p for all rows")
     model.eval()
     if batch_size > 256:
         # the native loop decodes up to 256 sequences at a time: larger requests run chunk by chunk (rows are
@@ -66,6 +118,12 @@ def sample_model(model: VQNSynthTransformer, device: Union[torch.device, str], b
                 return t
             return t[lo:hi]
 
+        def param_rows(v, lo, hi):           # a per-row sampling parameter (else the shared value)
+            return v[1][lo:hi] if v[1] is not None else v[0]
+
+        def time_rows(ti, lo, hi):           # [B, T] per-row time indexes (a 1-D list is shared)
+            return ti[lo:hi] if torch.is_tensor(ti) and ti.dim() == 2 else ti
+
         parts = []
         for lo in range(0, batch_size, 256):
             hi = min(batch_size, lo + 256)
@@ -73,10 +131,11 @@ def sample_model(model: VQNSynthTransformer, device: Union[torch.device, str], b
                    for k, v in class_conditioning.items()}
             # every per-row input is sliced (a mask with a batch dimension included); options are passed through
             parts.append(sample_model(
-                model, device, hi - lo, codemap_size, temperature, condition=rows(condition, lo, hi),
+                model, device, hi - lo, codemap_size, param_rows(row_params[0], lo, hi), condition=rows(condition, lo, hi),
                 class_conditioning=cls, initial_code=rows(initial_code, lo, hi), mask=rows(mask, lo, hi),
-                time_indexes_source=time_indexes_source, time_indexes_target=time_indexes_target,
-                top_k_sampling_k=top_k_sampling_k, top_p_sampling_p=top_p_sampling_p,
+                time_indexes_source=time_rows(time_indexes_source, lo, hi),
+                time_indexes_target=time_rows(time_indexes_target, lo, hi),
+                top_k_sampling_k=param_rows(row_params[1], lo, hi), top_p_sampling_p=param_rows(row_params[2], lo, hi),
                 progressbar_decorator=progressbar_decorator, use_predictive_sampling=use_predictive_sampling,
                 uniforms=uniforms[:, lo:hi], gumbel_noise=rows(gumbel_noise, lo, hi)))
         return torch.cat(parts, 0)
@@ -105,10 +164,18 @@ def sample_model(model: VQNSynthTransformer, device: Union[torch.device, str], b
     S = model.target_transformer_sequence_length
     start_len = model.target_start_symbol.shape[1]
     code_seq = model.target_codemaps_helper.to_sequence(codemap).clone()
+    (temperature, temp_rows), (top_k_sampling_k, top_k_rows), (top_p_sampling_p, top_p_rows) = row_params
+    mask_rows = None
     if mask is not None:
-        mask_seq = model.target_codemaps_helper.to_sequence(mask).reshape(-1, S)[0].cpu().numpy()
+        mseq = model.target_codemaps_helper.to_sequence(mask).reshape(-1, S).cpu().numpy()
+        mask_seq = mseq[0]
+        if rows_differ:
+            mask_rows = mseq
     else:
         mask_seq = [True] * S
+    ragged = mask_rows is not None or any(t is not None for t in (temp_rows, top_k_rows, top_p_rows))
+    if ragged and mask_rows is None:
+        mask_rows = np.broadcast_to(np.asarray(mask_seq, dtype=bool), (batch_size, S))
     if use_predictive_sampling:
         return _predictive_sampling(model, source_seq, target_seq, code_seq, mask_seq, start_len, temperature,
                                     top_k_sampling_k, top_p_sampling_p, gumbel_noise, progressbar_decorator)
@@ -122,6 +189,23 @@ def sample_model(model: VQNSynthTransformer, device: Union[torch.device, str], b
     x_seq = target_seq.transpose(0, 1).contiguous()          # [S_t, B, d]; rows are rewritten as we sample
     if not code_seq.is_contiguous():
         code_seq = code_seq.contiguous()
+    if ragged:
+        # independent requests: every row walks its own span (isi_prior_sample_run_rows); one causal prefill covers every
+        # row's unmasked prefix -- slots it fills beyond a row's own first position are rewritten by that row's steps
+        # before any later position reads them
+        pos, commit, p0 = _ragged_plan(np.asarray(mask_rows, dtype=bool), start_len - 1)
+        if pos.shape[0] == 0:
+            return model.target_codemaps_helper.to_time_frequency_map(code_seq).long()
+        sampler = NativeSampler(model, memory, x_seq, code_seq, mask_seq, uniforms)
+        n_steps = sampler.plan_rows(pos, commit, temp_rows, top_k_rows, top_p_rows)
+        sampler.prefill(p0)
+        chunk = n_steps if progressbar_decorator is None else 64
+        starts = range(0, n_steps, chunk)
+        if progressbar_decorator is not None:
+            starts = progressbar_decorator(starts)
+        for t0 in starts:
+            sampler.run_rows(t0, min(n_steps, t0 + chunk), temperature, top_k_sampling_k, top_p_sampling_p)
+        return model.target_codemaps_helper.to_time_frequency_map(code_seq).long()
     n_pos = S + start_len - 1
     # Token i is drawn from decoder position i + start_len - 1.  Positions behind the last masked token are
     # never read; positions before the first one only contribute keys / values, which one batched causal

@@ -587,8 +587,7 @@ static int launch_cfg(const ConvKArgs &a, int nphase, hipStream_t stream) {
 static int launch_conv(const ConvKArgs &a_in, bool scalar_a, int nphase, hipStream_t stream) {
   ConvKArgs a = a_in;
   const int mode = scalar_a ? 2 : (a.src_uniform ? 0 : 1);
-  const bool tap_major = knobs().conv_tap_major != 0;   // measurements
-  a.chunk_major = (mode == 0 && a.KH * a.KW > 1 && a.C0 % kBK == 0 && a.Cin % kBK == 0 && !tap_major) ? 1 : 0;
+  a.chunk_major = (mode == 0 && a.KH * a.KW > 1 && a.C0 % kBK == 0 && a.Cin % kBK == 0) ? 1 : 0;
   const bool two = a.Cin > a.C0;
   // the LDS-DMA kernel of the pair pipeline (conv_pair_f16.hip): pair8 sources, blocked weight pieces, whole
   // 64-column output tiles, channels-last output, no residual

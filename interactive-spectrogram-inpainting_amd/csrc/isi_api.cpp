@@ -35,9 +35,7 @@ const KnobEntry kKnobTable[] = {
     {"ISI_GEMM_NARROW_BELOW", &Knobs::gemm_narrow_below, 0, false},
     {"ISI_CONV_PAIR_BM", &Knobs::conv_pair_bm, 0, false},
     {"ISI_CONV_PAIR_ALL", &Knobs::conv_pair_all, 0, false},
-    {"ISI_CONV_TAP_MAJOR", &Knobs::conv_tap_major, 0, false},
     {"ISI_RESPAIR_TH", &Knobs::respair_th, 0, false},
-    {"ISI_RESPAIR_ONE_WAVE_PER_ROW", &Knobs::respair_one_wave_per_row, 0, false},
     {"ISI_RES_TH", &Knobs::res_th, 0, false},
     {"ISI_CONVT_TH", &Knobs::convt_th, 0, false},
     {"ISI_CONVT_PAIR_TH", &Knobs::convt_pair_th, 0, false},
@@ -51,7 +49,6 @@ const KnobEntry kKnobTable[] = {
     {"ISI_ATTN_FULL_ZERO", &Knobs::attn_full_zero, 0, false},
     {"ISI_WGRAD_SPLIT_TARGET", &Knobs::wgrad_split_target, 0, false},
     {"ISI_ATTN_G_FROM_KV", &Knobs::attn_g_from_kv, 1, false},
-    {"ISI_ATTN_OLD_FWD", &Knobs::attn_old_fwd, 0, false},
     {"ISI_ATTN_NO_FWD3", &Knobs::attn_no_fwd3, 0, false},
     {"ISI_ATTN_FWD3_ALL", &Knobs::attn_fwd3_all, 0, false},
     {"ISI_CONV_ABLATE", &Knobs::conv_ablate, 0, true},
@@ -164,7 +161,6 @@ int isi_debug_conv_pair_stamps(long long *host, int n) { return conv_pair_debug_
 int isi_debug_convT_pair_stamps(long long *host, int n) { return convT_pair_debug_stamps(host, n); }
 int isi_debug_resblock_pair_stamps(long long *host, int n) { return resblock_pair_debug_stamps(host, n); }
 int isi_debug_vq_stamps(long long *host, int n) { return vq_debug_stamps(host, n); }
-int isi_debug_attention_stamps(long long *host, int n) { return rel_attention_debug_stamps(host, n); }
 int isi_debug_attention_fwd2_stamps(long long *host, int n) { return rel_attention_fwd2_debug_stamps(host, n); }
 int isi_debug_attention_fwd3_stamps(long long *host, int n) { return rel_attention_fwd3_debug_stamps(host, n); }
 int isi_set_dropout_seed_base(const void *device_u64) {

@@ -22,14 +22,11 @@ struct Knobs {
   int no_wgrad_halo;            // ISI_NO_WGRAD_HALO: per-tap im2col weight-gradient kernel instead of the halo-staged one
   int conv_pair_bm;             // ISI_CONV_PAIR_BM: 128 / 256 forces the tile height of the LDS-DMA convolution (0: per shape)
   int conv_pair_all;            // ISI_CONV_PAIR_ALL: DMA kernel also for the shapes it is not preferred on
-  int conv_tap_major;           // ISI_CONV_TAP_MAJOR: K order of the register-staged kernel (measurement)
   int respair_th, res_th, convt_th, convt_pair_th;   // forced tile heights (tests, measurement)
-  int respair_one_wave_per_row; // ISI_RESPAIR_ONE_WAVE_PER_ROW: the 4-row residual-block tiles with four waves (one per row, until round 6) instead of eight
   int decode_nt;                // ISI_DECODE_NT: non-temporal weight loads in the batch-1 decode GEMVs (default 1)
   int attn_g_from_kv;           // ISI_ATTN_G_FROM_KV: (kept logits) the key-stationary backward kernel stores dS into G (default 1)
   int wgrad_split_target;       // ISI_WGRAD_SPLIT_TARGET: workgroups the split weight-gradient kernel aims at (0 = 768)
   int attn_full_zero;           // ISI_ATTN_FULL_ZERO: the attention backward zeroes all of G, not only the margins of its band
-  int attn_old_fwd;             // ISI_ATTN_OLD_FWD: the round-3 forward kernel (32-key tiles) for the 16-bit modes (A/B switch)
   int attn_no_fwd3;             // ISI_ATTN_NO_FWD3: the round-4 forward kernel (rel_attention_fwd2.hip) where the plane-staged one would run
   int attn_fwd3_all;            // ISI_ATTN_FWD3_ALL: the plane-staged forward kernel for the single-term modes too (default: three-term only)
   int prior_graph;              // ISI_PRIOR_GRAPH: positions per replayed hipGraph of the decode loop (8; 0 = direct launches)

@@ -1,5 +1,6 @@
-// Kernel-side arguments of the relative-attention forward kernels (rel_attention_f32.hip: exact-fp32 and the round-2/3
-// split kernels; rel_attention_fwd2.hip: the 64-key-tile kernels) and the launcher the dispatcher hands over to.
+// Kernel-side arguments of the relative-attention forward kernels (rel_attention_f32.hip: exact fp32 and the one-row
+// tail kernel; rel_attention_fwd2.hip: the 64-key-tile kernels; rel_attention_fwd3.hip: the plane-staged kernel) and the
+// launchers the dispatcher hands over to.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,19 +11,18 @@ struct AttnKArgs {
   float *out, *lse;
   unsigned q_bytes, k_bytes, v_bytes, e_bytes;
   int Sq, Sk, H, B;
-  int nblk;       // query blocks the split kernels run (all, or only the full ones: the tail rows go to the one-row kernel)
+  int nblk;       // query blocks the 16-bit kernels run (all, or only the full ones: the tail rows go to the one-row kernel)
   int q_ss, q_sb, q_sh, k_ss, k_sb, k_sh, v_ss, v_sb, v_sh, o_ss, o_sb, o_sh;  // element strides
   int Cq, Ck, Ek, R;
   int mask_mode;  // 0 none, 1 causal (j <= i), 2 anti-causal (j >= i)
   float scale;
-  int split;      // 1: three-term split-bf16 products (rel_attention_split_kernel), 2: single-term bf16
+  int split;      // 16-bit precision class of the call: 0 exact fp32, 1 three-term split-bf16 products, 2 single-term
   float *logits;  // optional [B,H,Sq,ldl]: base-2 logits of the allowed pairs, kept for the backward (rel_attention_fwd2.hip)
   int ldl;
 };
 
-// rel_attention_fwd2.hip.  precision: 1 three-term split-bf16, 2 single-term bf16, 3 single-term f16.  Returns
-// ISI_E_UNSUPPORTED (without touching the last-error text) for a shape it does not take.
-bool rel_attention_fwd2_ok(const AttnKArgs &a, int head_dim);
+// rel_attention_fwd2.hip: any Cq, Ck >= 1, head_dim 16 / 32 / 64.  precision: 1 three-term split-bf16, 2 single-term bf16,
+// 3 single-term f16.
 int rel_attention_fwd2(const AttnKArgs &a, int head_dim, int precision, hipStream_t stream);
 int rel_attention_fwd2_debug_stamps(long long *host, int n);
 

@@ -574,7 +574,7 @@ __global__ __launch_bounds__(256) void rel_attention_bwd_kv_kernel(const AttnBwd
 
 // ================================================================== split-bf16 variants (fwd.precision = 1)
 // Same mathematics with every contraction on the bf16 matrix pipe as a three-term split product
-// (split_bf16.h) and fp32 everywhere else.  Layout of rel_attention_split_kernel (forward): workgroup =
+// (split_bf16.h) and fp32 everywhere else.  Layout: workgroup =
 // 8 waves in two groups, a group per tile of the streamed pair; operands pre-split once per workgroup into
 // swizzled hi/lo bf16 planes in LDS -- row planes [row][HD] where the contraction runs over the head dim,
 // transposed planes [d][32 rows] where it runs over the streamed rows; band of e in a 192-row ring.  The

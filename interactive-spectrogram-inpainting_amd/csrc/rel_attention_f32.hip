@@ -22,13 +22,14 @@
 //                             read back through a per-wave LDS buffer: the skew)
 //   O^T  += V^T P^T          (P^T is already the B fragment: accumulator r of a
 //                             lane is the k-slot of MFMA step r)
-#include <algorithm>
-
+//
+// This file holds the exact-fp32 kernel (precision 0), the one-row tail kernel and the public dispatcher
+// rel_attention_f32(); the 16-bit precisions run the kernels of rel_attention_fwd2.hip / rel_attention_fwd3.hip
+// (attn_fwd_route below decides which).
 #include "isi_common.h"
 #include "isi_internal.h"
 #include "knobs.h"
 #include "prof.h"
-#include "split_bf16.h"
 #include "rel_attention.h"
 
 namespace isi {
@@ -352,397 +353,6 @@ __global__ __launch_bounds__(512) void rel_attention_f32_kernel(const AttnKArgs 
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// Split-bf16 variant (args->precision = 1, the Python default): the three contractions run on the bf16
-// matrix pipe as THREE-term split products (x = hi + lo in bf16; hi.hi + hi.lo + lo.hi, fp32
-// accumulation: relative error of a product ~2^-16), everything else -- logits, skew, online softmax,
-// merge -- stays fp32.  The exact-fp32 kernel above is matrix-bound (the band GEMM doubles the QK^T
-// work); here the matrix time drops 5x and the kernel becomes bound by the softmax / skew arithmetic.
-//   S^T  = K Q^T     A = K rows from LDS bf16 planes [key][HD], B = the lane's Q fragment (registers)
-//   band = E Q^T     A = ring rows of e
-//   O^T += V^T P^T   A = V^T from LDS planes [d][32 keys] (V is transposed while staged: a thread stages a
-//                    4 keys x 4 dims block), B = P packed from the accumulator layout; MFMA k-slot (half h, e)
-//                    of key block t is key 16 t + 8 (e >> 2) + 4 h + (e & 3), i.e. exactly the lane's registers
-// LDS rows are unpadded and XOR-swizzled: 16-B slot s of row r of a [.][HD] plane sits at s ^ ((r / (128/HD))
-// mod (HD/8)); 8-B unit u of row d of a V^T plane at u ^ ((d >> 2) & 7)  (conflict-free ds_read_b128 / b64).
-// ONE = true (args->precision = 2): SINGLE-term bf16 products (north_star's "MFMA bf16" mode): the lo planes are
-// neither computed, stored nor multiplied -- a third of the matrix work, half of the staging conversions and LDS
-// traffic; operands are rounded to bf16 (8 significand bits), accumulation / logits / softmax stay fp32.
-// phase timestamps (-DISI_MEASURE builds; tools/stamps_attention.py): the heaviest full workgroup (blockIdx.x == 1 of
-// (h, b) = (0, 0)), waves 0 and 4, key-pair iteration 4
-#ifdef ISI_MEASURE
-__device__ long long g_attn_stamps[64];
-#define ISI_ATT_STAMP(i_) do { if (blockIdx.x == 8 && (wave & 3) == 0 && lane == 0 && kp == k_begin + 4 * 64) \
-    g_attn_stamps[(wave >> 2) * 16 + (i_)] = __builtin_readcyclecounter(); } while (0)
-#else
-#define ISI_ATT_STAMP(i_) do { } while (0)
-#endif
-template <int HD, bool ONE = false>
-__global__ __launch_bounds__(512) void rel_attention_split_kernel(const AttnKArgs p) {
-  constexpr int NKB = HD / 16;           // 16-deep k-blocks of the head dim
-  constexpr int NSL = HD / 8;            // 16-B slots per [.][HD] row
-  constexpr int RPB = 128 / HD;          // rows per 256-B bank row
-  constexpr int NDB = (HD + 31) / 32;    // 32-row blocks of O^T
-  constexpr int VR = NDB * 32;           // rows of a V^T plane (rows >= HD stay zero)
-  constexpr int NQD = HD / 4;            // dim quads per key row
-  constexpr int NKQ = (HD / 4 + 7) / 8;  // band quads per thread and row
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  unsigned short *Kp = reinterpret_cast<unsigned short *>(smem);   // [tile 2][plane 2][32][HD]
-  unsigned short *Vp = Kp + 2 * 2 * 32 * HD;                       // [tile 2][plane 2][VR][32]
-  unsigned short *Ep = Vp + 2 * 2 * VR * 32;                       // [plane 2][RING][HD]
-  float *Sr = reinterpret_cast<float *>(Ep + 2 * RING * HD);       // [8][32][SRLD]
-  int *evk = reinterpret_cast<int *>(Sr + 8 * 32 * SRLD);          // [2][32]
-  auto swz = [](int row, int slot) { return (slot ^ ((row / RPB) % NSL)) * 8; };
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int grp = wave >> 2, wq = wave & 3;
-  const int ql = lane & 31, half = lane >> 5;
-  // (tile, head, batch) from the 1-D launch: the query blocks of one (batch, head) share an XCD's L2 (xcd_tile)
-  const int nqb = p.nblk;
-  int qt, pair;
-  if (!xcd_tile(nqb, p.H * p.B, p.mask_mode != 0, qt, pair)) return;
-  const int h = pair % p.H, b = pair / p.H;
-  const int qblk = p.mask_mode == 1 ? nqb - 1 - qt : qt;      // heavy blocks first
-  // causal masks: the ragged block (Sq % QB rows: the ONE extra row of a 1025-row sequence) is block 0, where the key
-  // range is shortest, instead of the last block, where it cost as much as a full one (9 of 45 block-steps at
-  // Sq = 1025).  Blocks then start at rag + 128 (qblk - 1); the band logic takes any origin when Cq = 1.
-  const int rag = (p.mask_mode == 1 && p.Cq == 1 && nqb * QB >= p.Sq) ? p.Sq % QB : 0;
-  const int q0 = rag ? (qblk ? rag + (qblk - 1) * QB : 0) : qblk * QB;
-  const int q_end = (rag && qblk == 0) ? rag : p.Sq;           // first row beyond this block's valid ones
-  const int qw0 = q0 + 32 * wq, qi = qw0 + ql;
-  const bool has_e = p.e != nullptr;
-
-  const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.q), 0, p.q_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.k), 0, p.k_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.v), 0, p.v_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t re = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(has_e ? p.e : p.q), 0, has_e ? p.e_bytes : 4u, 0x00020000);
-
-  // ---- Q fragment of this lane's query, split once: k-block t holds dims 16 t + 8 half + 0..7
-  s16x8_t qh[NKB], qlo[NKB];
-#pragma unroll
-  for (int t = 0; t < NKB; ++t) {
-    const unsigned off = qi < q_end ? (unsigned)(qi * p.q_ss + b * p.q_sb + h * p.q_sh + 16 * t + 8 * half) * 4u : OOB;
-    uint2 h0, l0, h1, l1;
-    split_f4(buf_load4(rq, off), h0, l0);
-    split_f4(buf_load4(rq, off == OOB ? OOB : off + 16u), h1, l1);
-    qh[t] = __builtin_bit_cast(s16x8_t, make_uint4(h0.x, h0.y, h1.x, h1.y));
-    qlo[t] = __builtin_bit_cast(s16x8_t, make_uint4(l0.x, l0.y, l1.x, l1.y));   // dead when ONE
-  }
-  const int evq = qi / p.Cq;
-  const int evq_w0 = qw0 / p.Cq, evq_b0 = q0 / p.Cq;
-
-  float m_run = NEG, l_run = 0.f;
-  f32x16 O[NDB];
-#pragma unroll
-  for (int d = 0; d < NDB; ++d)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) O[d][r] = 0.f;
-
-  int k_begin = 0, k_end = p.Sk;
-  if (p.mask_mode == 1) k_end = min(p.Sk, q0 + QB);
-  if (p.mask_mode == 2) k_begin = (q0 / 32) * 32;
-
-  // staging roles.  K / V: a 4 keys x 4 dims block per thread (threads [0, 16 NQD) stage K, [256, 256 + 16 NQD) V);
-  // band: row 32 st + srow of the pair's 64 new rows, quads squad + 8 i
-  const int kind = tid >> 8, bidx = tid & 255;
-  const int bqd = bidx % NQD, bkg = (bidx / NQD) & 7, btile = bidx / (8 * NQD);
-  const bool blk_on = btile < 2;
-  const int st = tid >> 8, srow = (tid >> 3) & 31, squad = tid & 7;
-  float4 pb[4], pe[NKQ];
-  auto band0 = [&](int k) { return evq_b0 - (k + 31) / p.Ck + p.Ek - 1; };
-  auto prefetch = [&](int k0) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int kj = k0 + 32 * btile + 4 * bkg + j;
-      const bool ok = blk_on && kj < p.Sk;
-      const unsigned ko = (unsigned)(kj * p.k_ss + b * p.k_sb + h * p.k_sh + bqd * 4) * 4u;
-      const unsigned vo = (unsigned)(kj * p.v_ss + b * p.v_sb + h * p.v_sh + bqd * 4) * 4u;
-      pb[j] = kind == 0 ? buf_load4(rk, ok ? ko : OOB) : buf_load4(rv, ok ? vo : OOB);
-    }
-    const int r = band0(k0 + 32) + 32 * st + srow;
-    const bool rok = has_e && r >= 0 && r < p.R;
-#pragma unroll
-    for (int i = 0; i < NKQ; ++i) {
-      const int qd = squad + 8 * i;
-      pe[i] = buf_load4(re, rok && qd < NQD ? (unsigned)((h * p.R + r) * HD + qd * 4) * 4u : OOB);
-    }
-  };
-  auto commit = [&](int k0) {
-    if (blk_on) {
-      if (kind == 0) {   // K rows: 8 bytes (4 dims) per key and plane
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int row = 4 * bkg + j;
-          uint2 hi, lo;
-          split_f4(pb[j], hi, lo);
-          const int o = ((btile * 2) * 32 + row) * HD + swz(row, bqd >> 1) + (bqd & 1) * 4;
-          *reinterpret_cast<uint2 *>(Kp + o) = hi;
-          if constexpr (!ONE) *reinterpret_cast<uint2 *>(Kp + o + 32 * HD) = lo;
-        }
-      } else {           // V transposed: per dim the 4 keys of the block as one 8-byte unit
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int d = 4 * bqd + e;
-          const float a0 = e == 0 ? pb[0].x : e == 1 ? pb[0].y : e == 2 ? pb[0].z : pb[0].w;
-          const float a1 = e == 0 ? pb[1].x : e == 1 ? pb[1].y : e == 2 ? pb[1].z : pb[1].w;
-          const float a2 = e == 0 ? pb[2].x : e == 1 ? pb[2].y : e == 2 ? pb[2].z : pb[2].w;
-          const float a3 = e == 0 ? pb[3].x : e == 1 ? pb[3].y : e == 2 ? pb[3].z : pb[3].w;
-          uint2 hi, lo;
-          split2(a0, a1, hi.x, lo.x);
-          split2(a2, a3, hi.y, lo.y);
-          const int o = ((btile * 2) * VR + d) * 32 + ((bkg ^ ((d >> 2) & 7)) * 4);
-          *reinterpret_cast<uint2 *>(Vp + o) = hi;
-          if constexpr (!ONE) *reinterpret_cast<uint2 *>(Vp + o + VR * 32) = lo;
-        }
-      }
-    }
-    if (has_e) {
-      const int slot = ring_slot(band0(k0 + 32) + 32 * st + srow);
-#pragma unroll
-      for (int i = 0; i < NKQ; ++i) {
-        const int qd = squad + 8 * i;
-        if (qd < NQD) {
-          uint2 hi, lo;
-          split_f4(pe[i], hi, lo);
-          const int o = slot * HD + swz(slot, qd >> 1) + (qd & 1) * 4;
-          *reinterpret_cast<uint2 *>(Ep + o) = hi;
-          if constexpr (!ONE) *reinterpret_cast<uint2 *>(Ep + o + RING * HD) = lo;
-        }
-      }
-    }
-    if (tid < 64) {
-      const int kt = k0 + (tid & 32);
-      evk[tid] = (kt + 31) / p.Ck - (kt + (tid & 31)) / p.Ck;
-    }
-  };
-
-  // ---- prologue
-  if (VR > HD) {   // rows of V^T beyond the head dim feed zero products
-    for (int i = tid; i < 2 * 2 * VR * 32 / 2; i += 512) reinterpret_cast<unsigned *>(Vp)[i] = 0u;
-    __syncthreads();
-  }
-  if (k_begin < k_end) {
-    prefetch(k_begin);
-    commit(k_begin);
-    if (has_e) {
-      const int rb = band0(k_begin + 32);
-      for (int row = 64 + (tid >> 3); row < BAND2; row += 64) {
-        const int r = rb + row;
-        const bool ok = r >= 0 && r < p.R;
-        const int slot = ring_slot(r);
-        for (int qd = squad; qd < NQD; qd += 8) {
-          uint2 hi, lo;
-          split_f4(buf_load4(re, ok ? (unsigned)((h * p.R + r) * HD + qd * 4) * 4u : OOB), hi, lo);
-          const int o = slot * HD + swz(slot, qd >> 1) + (qd & 1) * 4;
-          *reinterpret_cast<uint2 *>(Ep + o) = hi;
-          if constexpr (!ONE) *reinterpret_cast<uint2 *>(Ep + o + RING * HD) = lo;
-        }
-      }
-    }
-  }
-  __builtin_amdgcn_s_waitcnt(0x0F70);
-  __syncthreads();
-  const float scale2 = p.scale * LOG2E;
-  const bool ck_regular = (32 % p.Ck) == 0;
-  int evoff[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) evoff[r] = 31 / p.Ck - mfma_row(r, half) / p.Ck;
-  const unsigned short *Kb = Kp + (grp * 2) * 32 * HD, *Vb = Vp + (grp * 2) * VR * 32;
-  const int *evkb = evk + grp * 32;
-
-  for (int kp = k_begin; kp < k_end; kp += 64) {
-    const bool more = kp + 64 < k_end;
-    ISI_ATT_STAMP(0);
-    if (more) prefetch(kp + 64);
-    ISI_ATT_STAMP(1);
-    const int k0 = kp + 32 * grp;
-    const int rb = band0(k0);
-
-    bool live = qw0 < q_end && k0 < k_end;
-    if (p.mask_mode == 1) live = live && k0 <= qw0 + 31;
-    if (p.mask_mode == 2) live = live && k0 + 31 >= qw0;
-    if (live) {
-      // ---- S^T = K Q^T
-      f32x16 sacc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sacc[r] = 0.f;
-#pragma unroll
-      for (int t = 0; t < NKB; ++t) {
-        const int o = ql * HD + swz(ql, 2 * t + half);
-        const s16x8_t kh = *reinterpret_cast<const s16x8_t *>(Kb + o);
-        if constexpr (!ONE) {
-          const s16x8_t kl = *reinterpret_cast<const s16x8_t *>(Kb + o + 32 * HD);
-          sacc = ISI_MFB(kl, qh[t], sacc);
-          sacc = ISI_MFB(kh, qlo[t], sacc);
-        }
-        sacc = ISI_MFB(kh, qh[t], sacc);
-      }
-      float sv[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sv[r] = sacc[r];
-      ISI_ATT_STAMP(2);
-
-      // ---- relative logits through the skew buffer
-      if (has_e) {
-        float *sr = Sr + wave * 32 * SRLD + ql * SRLD;
-        const int wrow0 = rb + evq_w0 - evq_b0;
-        const int nt = (31 / p.Cq + 31 / p.Ck) < 32 ? 1 : 2;
-        for (int tb = 0; tb < nt; ++tb) {
-          f32x16 racc;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) racc[r] = 0.f;
-          const int slot = ring_slot(wrow0 + 32 * tb + ql);
-#pragma unroll
-          for (int t = 0; t < NKB; ++t) {
-            const int o = slot * HD + swz(slot, 2 * t + half);
-            const s16x8_t eh = *reinterpret_cast<const s16x8_t *>(Ep + o);
-            if constexpr (!ONE) {
-              const s16x8_t el = *reinterpret_cast<const s16x8_t *>(Ep + o + RING * HD);
-              racc = ISI_MFB(el, qh[t], racc);
-              racc = ISI_MFB(eh, qlo[t], racc);
-            }
-            racc = ISI_MFB(eh, qh[t], racc);
-          }
-#pragma unroll
-          for (int r = 0; r < 16; ++r) sr[32 * tb + mfma_row(r, half)] = racc[r];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const int dq = evq - evq_w0;
-        if (ck_regular) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) sv[r] += sr[dq + evoff[r]];
-        } else {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) sv[r] += sr[dq + evkb[mfma_row(r, half)]];
-        }
-        __builtin_amdgcn_wave_barrier();
-      }
-
-      ISI_ATT_STAMP(3);
-      // ---- scale, mask, online softmax (base 2)
-      float tmax = NEG;
-      bool full = !p.mask && k0 + 31 < p.Sk && qw0 + 31 < q_end;
-      if (p.mask_mode == 1) full = full && k0 + 31 <= qw0;
-      if (p.mask_mode == 2) full = full && k0 >= qw0 + 31;
-      if (full) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          sv[r] *= scale2;
-          tmax = fmaxf(tmax, sv[r]);
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int kj = k0 + mfma_row(r, half);
-          bool ok = kj < p.Sk;
-          if (p.mask_mode == 1) ok = ok && kj <= qi;
-          if (p.mask_mode == 2) ok = ok && kj >= qi;
-          float sc = sv[r] * scale2;
-          if (p.mask && ok && qi < q_end) sc += p.mask[(size_t)qi * p.Sk + kj] * LOG2E;
-          sc = ok ? sc : NEG;
-          sv[r] = sc;
-          tmax = fmaxf(tmax, sc);
-        }
-      }
-      tmax = fmaxf(tmax, xor32_f32(tmax));
-      const float m_new = fmaxf(m_run, tmax);
-      const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-      float psum = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float pr = sv[r] <= -1e29f ? 0.f : __builtin_amdgcn_exp2f(sv[r] - m_new);
-        sv[r] = pr;
-        psum += pr;
-      }
-      psum += xor32_f32(psum);
-      l_run = l_run * alpha + psum;
-      m_run = m_new;
-
-      ISI_ATT_STAMP(4);
-      // ---- P split: key block t = registers 8 t .. 8 t + 7
-      s16x8_t ph[2], pl[2];
-      split_acc16(sv, ph, pl);
-      // ---- O^T = alpha * O^T + V^T P^T
-      const bool rescale = __any(alpha != 1.f);
-#pragma unroll
-      for (int d = 0; d < NDB; ++d) {
-        if (rescale) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) O[d][r] *= alpha;
-        }
-        const int drow = d * 32 + ql;
-        const int sx = (drow >> 2) & 7;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          const unsigned short *vr = Vb + drow * 32;
-          const uint2 h0 = *reinterpret_cast<const uint2 *>(vr + (((4 * t + half) ^ sx) * 4));
-          const uint2 h1 = *reinterpret_cast<const uint2 *>(vr + (((4 * t + 2 + half) ^ sx) * 4));
-          const s16x8_t vh = __builtin_bit_cast(s16x8_t, make_uint4(h0.x, h0.y, h1.x, h1.y));
-          if constexpr (!ONE) {
-            const uint2 l0 = *reinterpret_cast<const uint2 *>(vr + VR * 32 + (((4 * t + half) ^ sx) * 4));
-            const uint2 l1 = *reinterpret_cast<const uint2 *>(vr + VR * 32 + (((4 * t + 2 + half) ^ sx) * 4));
-            const s16x8_t vl = __builtin_bit_cast(s16x8_t, make_uint4(l0.x, l0.y, l1.x, l1.y));
-            O[d] = ISI_MFB(vl, ph[t], O[d]);
-            O[d] = ISI_MFB(vh, pl[t], O[d]);
-          }
-          O[d] = ISI_MFB(vh, ph[t], O[d]);
-        }
-      }
-    }
-    ISI_ATT_STAMP(5);
-    __syncthreads();
-    ISI_ATT_STAMP(6);
-    if (more) commit(kp + 64);
-    ISI_ATT_STAMP(7);
-    __syncthreads();
-    ISI_ATT_STAMP(8);
-  }
-
-  // ---- merge the two groups' softmax states (group 1 -> LDS -> group 0)
-  float *mg = smem;
-  constexpr int MGW = (NDB * 16 + 2) * 64;
-  if (grp == 1) {
-    float *dst = mg + wq * MGW + lane;
-#pragma unroll
-    for (int d = 0; d < NDB; ++d)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) dst[(d * 16 + r) * 64] = O[d][r];
-    dst[NDB * 16 * 64] = m_run;
-    dst[(NDB * 16 + 1) * 64] = l_run;
-  }
-  __syncthreads();
-  if (grp == 1) return;
-  {
-    const float *src = mg + wq * MGW + lane;
-    const float m1 = src[NDB * 16 * 64], l1 = src[(NDB * 16 + 1) * 64];
-    const float m = fmaxf(m_run, m1);
-    const float a0 = __builtin_amdgcn_exp2f(m_run - m), a1 = __builtin_amdgcn_exp2f(m1 - m);
-    l_run = l_run * a0 + l1 * a1;
-    m_run = m;
-#pragma unroll
-    for (int d = 0; d < NDB; ++d)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) O[d][r] = O[d][r] * a0 + src[(d * 16 + r) * 64] * a1;
-  }
-  if (qi < q_end) {
-    const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
-    float *orow = p.out + (size_t)qi * p.o_ss + (size_t)b * p.o_sb + (size_t)h * p.o_sh;
-    if (p.lse && half == 0)
-      p.lse[((size_t)b * p.H + h) * p.Sq + qi] = l_run > 0.f ? m_run * LN2 + logf(l_run) : 1e30f;
-#pragma unroll
-    for (int d = 0; d < NDB; ++d)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int dd = d * 32 + 8 * g + 4 * half;
-        if (dd < HD)
-          *reinterpret_cast<float4 *>(orow + dd) =
-              make_float4(O[d][4 * g] * inv, O[d][4 * g + 1] * inv, O[d][4 * g + 2] * inv, O[d][4 * g + 3] * inv);
-      }
-  }
-}
-
 // ---- one query row per workgroup, unmasked, exact fp32 (rel_attention_f32 below gives the one or two rows beyond the last
 // full query block to this kernel instead of a block of their own).  G = HD / 4 lanes own a key row (one coalesced
 // 16-byte load per lane for k, v and the relative row), 512 / G x 8 keys are in flight per step; every lane group keeps
@@ -824,36 +434,37 @@ __global__ __launch_bounds__(512) void attn_fwd_tail_row_kernel(const AttnKArgs 
   }
 }
 
-int rel_attention_debug_stamps(long long *host, int n) {
-#ifdef ISI_MEASURE
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_attn_stamps), sizeof(long long) * (size_t)(n < 64 ? n : 64)) == hipSuccess ? 0 : -2;
-#else
-  (void)host; (void)n;
-  return unsupported("phase timestamps need a -DISI_MEASURE build");
-#endif
-}
-
 template <int HD>
 static int launch_attn(const AttnKArgs &a, int B, hipStream_t stream) {
-  auto kern = a.split == 2 ? rel_attention_split_kernel<HD, true> : a.split ? rel_attention_split_kernel<HD, false> : rel_attention_f32_kernel<HD>;
-  constexpr int VR = ((HD + 31) / 32) * 32;
-  constexpr size_t smem_f = (size_t)((128 + RING) * (HD + 4) + 8 * 32 * SRLD) * sizeof(float) + 64 * sizeof(int);
-  constexpr size_t smem_s = (size_t)(2 * 2 * 32 * HD + 2 * 2 * VR * 32 + 2 * RING * HD) * sizeof(unsigned short) +
-                            (size_t)(8 * 32 * SRLD) * sizeof(float) + 64 * sizeof(int);
-  const size_t smem = a.split ? smem_s : smem_f;
-  static DeviceOnce attr_set[3];
-  if (!attr_set[a.split].done()) {
+  auto kern = rel_attention_f32_kernel<HD>;
+  constexpr size_t smem = (size_t)((128 + RING) * (HD + 4) + 8 * 32 * SRLD) * sizeof(float) + 64 * sizeof(int);
+  static DeviceOnce attr_set;
+  if (!attr_set.done()) {
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
       return check_launch("hipFuncSetAttribute(rel_attention)");
-    attr_set[a.split].mark();
+    attr_set.mark();
   }
   const double pairs = (double)a.Sq * a.Sk * (a.mask_mode ? 0.5 : 1.0) * a.H * B;
   prof::Scope scope(prof::K_REL_ATTENTION, 2.0 * pairs * HD * (a.e ? 3 : 2),
                     4.0 * B * a.H * HD * (2.0 * a.Sq + 2.0 * a.Sk), stream);
-  if (a.split) ISI_PROF_LAUNCH(scope, kern, dim3(xcd_grid(a.nblk, a.H * B)), dim3(512), smem, stream, a);   // (xcd_tile)
-  else ISI_PROF_LAUNCH(scope, kern, dim3((a.Sq + QB - 1) / QB, a.H, B), dim3(512), smem, stream, a);
+  ISI_PROF_LAUNCH(scope, kern, dim3((a.Sq + QB - 1) / QB, a.H, B), dim3(512), smem, stream, a);
   return check_launch("rel_attention_f32");
+}
+
+// The one routing decision of the forward.  Exact fp32 has its own kernel; the 16-bit precisions run the 64-key-tile
+// kernels (rel_attention_fwd2.hip) or, with a workspace for its operand planes, the plane-staged kernel
+// (rel_attention_fwd3.hip) where that one takes the shape.
+enum class AttnFwd { F32, Tiles64, Planes };
+enum class AttnWs { None, Given, Query };   // Query: no workspace yet, the caller asks whether to bring one
+static AttnFwd attn_fwd_route(const AttnKArgs &a, int head_dim, int precision, AttnWs ws) {
+  if (precision == 0) return AttnFwd::F32;
+  // the plane-staged kernel pays a pack launch (10-13 us at B 8 x H 8 x S 1025): measured, it wins with three-term products
+  // (causal 91 vs 96 us, unmasked 127 vs 141) and loses 3-4 us with single-term ones -- those ask for no workspace unless
+  // ISI_ATTN_FWD3_ALL is set (a caller that hands one over anyway gets the plane-staged kernel)
+  if (ws == AttnWs::Query && precision != 1 && !knobs().attn_fwd3_all) return AttnFwd::Tiles64;
+  if (ws == AttnWs::None || knobs().attn_no_fwd3 || !rel_attention_fwd3_ok(a, head_dim, precision)) return AttnFwd::Tiles64;
+  return AttnFwd::Planes;
 }
 
 static int64_t span(int64_t S, int64_t ss, int64_t B, int64_t sb, int64_t H, int64_t sh, int64_t hd) {
@@ -891,14 +502,15 @@ int rel_attention_f32(const isi_attn_args *g, hipStream_t stream) {
   a.Cq = g->Cq; a.Ck = g->Ck; a.Ek = g->Ek;
   a.mask_mode = g->mask_mode; a.scale = g->scale;
   if (g->precision < 0 || g->precision > 3) return invalid("rel_attention: precision must be 0 .. 3");
-  // 0 fp32 pipe | 1 three-term split-bf16 | 2 single-term bf16 | 3 single-term f16 (rel_attention_fwd2.hip only)
+  // 0 fp32 pipe | 1 three-term split-bf16 | 2 single-term bf16 | 3 single-term f16
   a.split = g->precision == 1 ? 1 : g->precision >= 2 ? 2 : 0;
+  const AttnFwd route = attn_fwd_route(a, g->head_dim, g->precision, g->workspace ? AttnWs::Given : AttnWs::None);
   a.logits = g->logits; a.ldl = (int)g->logits_ld;
   if (a.logits) {
     if (g->logits_ld < ((g->Sk + 31) & ~31) || (g->logits_ld & 3) || (reinterpret_cast<uintptr_t>(a.logits) & 15))
       return invalid("rel_attention: logits_ld must be a multiple of 4, at least Sk rounded up to 32; logits 16-byte aligned");
     if ((int64_t)g->B * g->H * g->Sq * g->logits_ld > ((int64_t)1 << 40)) return unsupported("rel_attention: logits buffer too large");
-    if (!a.split || (g->precision != 3 && knobs().attn_old_fwd) || !rel_attention_fwd2_ok(a, g->head_dim))
+    if (route == AttnFwd::F32)
       return unsupported("rel_attention: the logits are stored by the 64-key-tile kernels only (precision >= 1)");
   }
   if (a.e && a.R <= 0) return invalid("rel_attention: rel_rows must be positive");
@@ -910,11 +522,10 @@ int rel_attention_f32(const isi_attn_args *g, hipStream_t stream) {
   const bool split_tail = a.split && tail > 0;
   a.nblk = split_tail ? g->Sq / QB : (g->Sq + QB - 1) / QB;
   int rc;
-  if (a.split && g->workspace && !knobs().attn_no_fwd3 && !knobs().attn_old_fwd && rel_attention_fwd3_ok(a, g->head_dim, g->precision)) {
-    // operands as 16-bit planes in the caller's workspace, staged by LDS-DMA (rel_attention_fwd3.hip)
+  if (route == AttnFwd::Planes) {
+    // operands as 16-bit planes in the caller's workspace, staged by LDS-DMA
     rc = rel_attention_fwd3(a, g->head_dim, g->precision, g->workspace, g->workspace_bytes, stream);
-  } else
-  if (a.split && (g->precision == 3 || !knobs().attn_old_fwd) && rel_attention_fwd2_ok(a, g->head_dim)) {
+  } else if (route == AttnFwd::Tiles64) {
     rc = rel_attention_fwd2(a, g->head_dim, g->precision, stream);
   } else
   switch (g->head_dim) {
@@ -938,11 +549,7 @@ size_t rel_attention_workspace_bytes(const isi_attn_args *g) {
   if (!g || g->Sq <= 0 || g->Sk <= 0 || g->B <= 0 || g->H <= 0 || g->precision < 1 || g->precision > 3) return 0;
   AttnKArgs a{};
   a.e = g->rel_embeddings; a.R = g->rel_rows; a.Sq = g->Sq; a.Sk = g->Sk; a.H = g->H; a.B = g->B; a.Cq = g->Cq; a.Ck = g->Ck;
-  // the plane-staged kernel pays a pack launch (10-13 us at B 8 x H 8 x S 1025): measured, it wins with three-term products
-  // (causal 91 vs 96 us, unmasked 127 vs 141) and loses 3-4 us with single-term ones -- those ask for no workspace unless
-  // ISI_ATTN_FWD3_ALL is set (a caller that hands one over anyway gets the plane-staged kernel)
-  if (g->precision != 1 && !knobs().attn_fwd3_all) return 0;
-  if (knobs().attn_no_fwd3 || knobs().attn_old_fwd) return 0;
+  if (attn_fwd_route(a, g->head_dim, g->precision, AttnWs::Query) != AttnFwd::Planes) return 0;
   return rel_attention_fwd3_workspace_bytes(a, g->head_dim, g->precision);
 }
 

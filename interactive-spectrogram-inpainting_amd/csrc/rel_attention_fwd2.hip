@@ -6,8 +6,8 @@
 // The operator behind the reference's VQCPCB.transformer.transformer_custom layers
 // (priors/transformer.py:370-417,756-777); specification: oracle/prior_oracle.py (parity unpinned).
 //
-// What changed against rel_attention_split_kernel (rel_attention_f32.hip), which this kernel replaces for the
-// 16-bit modes (precision 1 = three-term split-bf16, 2 = single-term bf16, 3 = single-term f16):
+// What changed against the first 16-bit kernel (32-key tiles, one 128-query block per workgroup; since removed), which
+// this kernel replaced for the 16-bit modes (precision 1 = three-term split-bf16, 2 = single-term bf16, 3 = single-term f16):
 //   * a PERSISTENT workgroup walks several 128-query blocks of one (batch, head) pair, dealt in "snake" order over
 //     the blocks sorted by cost: under a causal mask every workgroup gets the same number of key steps (the
 //     B8 H8 S1025 case: 256 workgroups x 11 steps instead of 576 workgroups of 1..9 steps on 256 CUs);
@@ -623,12 +623,6 @@ int rel_attention_fwd2_debug_stamps(long long *host, int n) {
   (void)host; (void)n;
   return unsupported("phase timestamps need a -DISI_MEASURE build");
 #endif
-}
-
-bool rel_attention_fwd2_ok(const AttnKArgs &a, int head_dim) {
-  (void)head_dim;
-  // the band ring holds 127/Cq + (KS-1)/Ck + 1 rows for any Cq, Ck >= 1
-  return a.Cq >= 1 && a.Ck >= 1;
 }
 
 namespace {

@@ -512,8 +512,7 @@ int resblock_pair_f16(const float *in, const float *w1_16, const float *b1, cons
     return C == 128 ? launch_res_pair<8, 4>(a, stream) : launch_res_pair<8, 2>(a, stream);
   }
   a.tiles_y = (H + 3) / 4;
-  if (!knobs().respair_one_wave_per_row) return C == 128 ? launch_res_pair<4, 4, 2>(a, stream) : launch_res_pair<4, 2, 2>(a, stream);
-  return C == 128 ? launch_res_pair<4, 4>(a, stream) : launch_res_pair<4, 2>(a, stream);
+  return C == 128 ? launch_res_pair<4, 4, 2>(a, stream) : launch_res_pair<4, 2, 2>(a, stream);
 }
 
 }  // namespace isi

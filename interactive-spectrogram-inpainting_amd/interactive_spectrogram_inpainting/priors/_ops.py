@@ -368,13 +368,9 @@ def _attn_args(q, k, v, rel, out, Sq, Sk, B, H, hd, Cq, Ck, Ek, mask_mode, dense
 
 
 def attention_logits_buffer(B: int, nhead: int, Sq: int, Sk: int, device) -> Optional[torch.Tensor]:
-    """[B,H,Sq,ld] buffer for the logits a training forward keeps (None when they are recomputed: exact-fp32 mode,
-    ISI_ATTN_SAVE_LOGITS=0, or the round-3 forward kernels selected)."""
+    """[B,H,Sq,ld] buffer for the logits a training forward keeps (None when they are recomputed: exact-fp32 mode or
+    ISI_ATTN_SAVE_LOGITS=0)."""
     if not SAVE_ATTENTION_LOGITS or ATTENTION_PRECISION == "f32":
-        return None
-    old = C.c_int()
-    _hip.check(_hip.lib().isi_knob_get(b"ISI_ATTN_OLD_FWD", C.byref(old)), "isi_knob_get")
-    if old.value and ATTENTION_PRECISION != "f16":
         return None
     ld = (Sk + 31) // 32 * 32
     if B * nhead * Sq * ld * 4 > ATTENTION_LOGITS_MAX_MB * (1 << 20):

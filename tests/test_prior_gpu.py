@@ -1182,7 +1182,7 @@ def test_rel_attention_persistent_blocks(hd, H, B, Sq, Sk, Cq, Ck, mode, precisi
     """rel_attention_fwd2.hip deals a (batch, head) pair's query blocks to fewer, persistent workgroups once the launch
     would exceed one workgroup per CU (snake order over the blocks sorted by cost; the next block's first key step is
     requested during the last step of the current one): against the exact-fp32 kernel, which runs one block per
-    workgroup, and against the round-3 kernel behind ISI_ATTN_OLD_FWD."""
+    workgroup."""
     from interactive_spectrogram_inpainting import _hip
     from interactive_spectrogram_inpainting.priors import _ops
     torch.manual_seed(Sq + B)
@@ -1200,7 +1200,3 @@ def test_rel_attention_persistent_blocks(hd, H, B, Sq, Sk, Cq, Ck, mode, precisi
     tol = 3e-5 if precision == "bf16x3" else 2.5e-3
     _close(got, ref, tol, f"persistent blocks {precision}")
     assert (lse - lse0).abs().max().item() < 30 * tol
-    if precision == "bf16x3":
-        with _hip.knob("ISI_ATTN_OLD_FWD", 1):
-            old = _ops.rel_attention(q, k, v, rel, H, Cq, Ck, Ek, mask_mode=mode)
-        _close(got, old, 3e-5, "64-key-tile kernel vs round-3 kernel")

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Forward relative attention: the 64-key-tile kernels (rel_attention_fwd2.hip) against the exact-fp32 kernel over a
-sweep of shapes / masks / channel layouts, and their time at the top prior's shape next to the round-3 kernels
-(ISI_ATTN_OLD_FWD=1)."""
+sweep of shapes / masks / channel layouts, and their time at the top prior's shape."""
 import argparse
 import pathlib
 import sys
@@ -9,7 +8,6 @@ import sys
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "interactive-spectrogram-inpainting_amd"))
 import torch  # noqa: E402
-from interactive_spectrogram_inpainting import _hip  # noqa: E402
 from interactive_spectrogram_inpainting.priors import _ops  # noqa: E402
 
 
@@ -40,7 +38,6 @@ def main():
     ap.add_argument("--hd", type=int, default=64)
     ap.add_argument("--modes", type=int, nargs="*", default=[1, 0, 2])
     ap.add_argument("--precs", nargs="*", default=["bf16x3", "bf16", "f16"])
-    ap.add_argument("--new-only", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -80,14 +77,10 @@ def main():
     for mode in a.modes:
         ref = run(q, k, v, rel, H, 1, 1, S, mode, "f32")
         for prec in a.precs:
-            for old in (0, 1):
-                if old and (prec == "f16" or a.new_only):
-                    continue
-                with _hip.knob("ISI_ATTN_OLD_FWD", old):
-                    t = timed(lambda: run(q, k, v, rel, H, 1, 1, S, mode, prec))
-                    got = run(q, k, v, rel, H, 1, 1, S, mode, prec)
-                err = ((got - ref).abs().max() / ref.abs().max()).item()
-                print(f"mode {mode} {prec:7s} {'old' if old else 'new'}: {t:7.1f} us  {3 * dense / t / 1e6:7.1f} TF(dense)  err/max {err:.2e}", flush=True)
+            t = timed(lambda: run(q, k, v, rel, H, 1, 1, S, mode, prec))
+            got = run(q, k, v, rel, H, 1, 1, S, mode, prec)
+            err = ((got - ref).abs().max() / ref.abs().max()).item()
+            print(f"mode {mode} {prec:7s}: {t:7.1f} us  {3 * dense / t / 1e6:7.1f} TF(dense)  err/max {err:.2e}", flush=True)
     return 1 if bad else 0
 
 

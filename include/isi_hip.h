@@ -571,6 +571,15 @@ int isi_decode_stage_f32(const float *x, int x_stride, const float *ln_g, const 
 size_t isi_rel_attention_decode_workspace_floats(int B, int H, int head_dim);
 int isi_rel_attention_decode_f32(const isi_attn_args *args, int q_pos, float *workspace,
                                  void *stream);
+/* The same step with args->k / args->v read as bf16 arrays (one 16-bit plane, the upper half of the fp32 pattern;
+ * strides in elements as before): every element is widened exactly (bits << 16), then q, the relative table,
+ * logits, softmax, accumulation and out are fp32 as in isi_rel_attention_decode_f32 -- the result is that entry's on
+ * keys / values rounded to bf16 beforehand, up to the order in which the keys are summed (a lane holds 8 elements of
+ * a row instead of 4, so twice the rows are in flight).  Rows beyond the keys in use may hold anything.  q, k, v and
+ * rel_embeddings 16-byte aligned, k / v strides multiples of 8 elements, q strides of 4 (else ISI_E_INVALID).  Same
+ * workspace, same split rule.  This is the cached attention of isi_prior_state.kv_format = ISI_KV_BF16. */
+int isi_rel_attention_decode_kv16_f32(const isi_attn_args *args, int q_pos, float *workspace,
+                                      void *stream);
 
 /* One categorical draw per row (sample.py:286-295): logits/temperature ->
  * top_k_top_p_filtering (sample.py:36-65) -> softmax -> inverse-CDF draw with the
@@ -615,7 +624,11 @@ typedef struct isi_prior_state {
   size_t scratch_floats;
   int S_t, S_src, S, B, start_len;
   const float *cross_out;  /* [n_layers, S_src, B, d] or NULL: single-source cross-attention (below)          */
+  int kv_format;           /* ISI_KV_F32 (0): kv_cache / memory_kv are fp32 arrays; ISI_KV_BF16 (1): bf16 arrays of  */
+                           /* the same logical shape (below); anything else: ISI_E_INVALID                            */
 } isi_prior_state;
+#define ISI_KV_F32 0
+#define ISI_KV_BF16 1
 size_t isi_prior_decode_scratch_floats(const isi_prior_w *w, int B);
 /* Enqueues positions [p_begin, p_end) of the decoder (one new row each, all layers),
  * and for every masked position the logits head, the draw (isi_sample_row_f32
@@ -632,7 +645,14 @@ size_t isi_prior_decode_scratch_floats(const isi_prior_w *w, int B);
  * is row p / Cd of cross_out[l] = out_proj(V(memory)) (biases included); one launch per layer forms
  * LN1(y1) + cross_out[l][p / Cd] in place of the query GEMV, the cached attention and the out-projection, and
  * memory_kv may be NULL (it is not read).  Requires Ce == 1 (else ISI_E_UNSUPPORTED) and (S_t - 1) / Cd < S_src
- * (else ISI_E_INVALID), both checked before any launch. */
+ * (else ISI_E_INVALID), both checked before any launch.
+ * 16-bit caches (state->kv_format = ISI_KV_BF16, opt-in; fp32 is the default and is bit for bit what it was): kv_cache
+ * and memory_kv point at bf16 arrays -- half the bytes the cached attention streams per position, half the footprint.  The
+ * launch that forms q | k,v rounds k,v to nearest-even as it stores them into the cache slot (NaN stays NaN; bf16 has
+ * fp32's range, nothing overflows); the caller fills memory_kv and any prefilled cache rows in the same format.  The
+ * cached attention widens the rows exactly and computes in fp32 (isi_rel_attention_decode_kv16_f32); x_seq, cross_out,
+ * the scratch rows and every weight stay fp32.  Sampled codes may differ from an fp32-cache run's (keys and values
+ * carry 8 significand bits); the format is part of the graph cache key. */
 int isi_prior_sample_run(const isi_prior_w *w, const isi_prior_state *state, int p_begin,
                          int p_end, float temperature, int top_k, float top_p, void *stream);
 

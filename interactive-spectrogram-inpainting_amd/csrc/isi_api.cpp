@@ -341,6 +341,9 @@ int isi_decode_stage_f32(const float *x, int x_stride, const float *ln_g, const 
 int isi_rel_attention_decode_f32(const isi_attn_args *args, int q_pos, float *workspace, void *stream) {
   return rel_attention_decode_f32(args, q_pos, workspace, S(stream));
 }
+int isi_rel_attention_decode_kv16_f32(const isi_attn_args *args, int q_pos, float *workspace, void *stream) {
+  return rel_attention_decode_kv16_f32(args, q_pos, workspace, S(stream));
+}
 size_t isi_rel_attention_decode_workspace_floats(int B, int H, int head_dim) {
   return rel_attention_decode_workspace_floats(B, H, head_dim);
 }

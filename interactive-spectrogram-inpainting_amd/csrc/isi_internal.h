@@ -142,7 +142,9 @@ int attention_tail_rows(int S, int mask_mode, bool dense_mask);   // rel_attenti
 // row_pos != nullptr (ragged batches): batch row b queries from position row_pos[t * B + b], t = *pos or 0 (row_pos
 // then already offset to the step); self-attention reads that position + 1 keys, g->Sk is their upper bound
 int rel_attention_decode_launch(const isi_attn_args *g, int q_pos, const int *pos, int self_keys, float *workspace,
-                                int combine, hipStream_t stream, const int *row_pos = nullptr);
+                                int combine, hipStream_t stream, const int *row_pos = nullptr, int kv_format = 0);
+// args->k / args->v read as bf16 (isi_rel_attention_decode_kv16_f32)
+int rel_attention_decode_kv16_f32(const isi_attn_args *g, int q_pos, float *workspace, hipStream_t stream);
 size_t decode_stage_workspace_floats(int M, int N, int K);
 int decode_stage_f32(const float *x, int x_stride, const float *ln_g, const float *ln_b, const float *W, const float *bias,
                      const float *res, int res_stride, const float *res_g, const float *res_b, float *out, int out_stride,

@@ -71,7 +71,29 @@ struct RowLinArgs {
   // t = *pos (replayable) or t = 0 (row_pos already offset to the step), and x / res / out2 of row m advance by that
   // position times x_pos / res_pos / out2_pos
   const int *row_pos;
+  // 16-bit key/value cache (isi_prior_state.kv_format = ISI_KV_BF16): out2 points at a bf16 array -- out2_stride / out2_pos still
+  // count elements -- and the epilogue rounds to nearest-even as it stores (the KV16 instantiations; the launchers pick them
+  // by this flag, the fp32 instantiations are the code they were)
+  int out2_bf16;
 };
+
+// the out2 epilogue: fp32 as it was, or (KV16) the value rounded to nearest-even into a bf16 slot -- v_cvt_pk_bf16_f32 on
+// gfx950 (NaN stays NaN, bf16 has fp32's exponent: nothing overflows) and a two-byte vector store
+template <bool KV16>
+__device__ __forceinline__ void store_out2(float *out2, long idx, float v) {
+  if constexpr (KV16) reinterpret_cast<__bf16 *>(out2)[idx] = (__bf16)v;
+  else out2[idx] = v;
+}
+template <bool KV16>
+__device__ __forceinline__ float *out2_at(float *out2, long elems) {
+  if constexpr (KV16) return reinterpret_cast<float *>(reinterpret_cast<uint16_t *>(out2) + elems);
+  else return out2 + elems;
+}
+// (host) out2 moved on by `elems` elements of its format
+static void advance_out2(RowLinArgs &a, long elems) {
+  if (!a.out2) return;
+  a.out2 = a.out2_bf16 ? reinterpret_cast<float *>(reinterpret_cast<uint16_t *>(a.out2) + elems) : a.out2 + elems;
+}
 
 __device__ __forceinline__ float wave_sum(float v) { return wave64_sum(v); }   // DPP path (isi_common.h)
 // Every field of a launch's argument block is "used" by an empty asm statement at the head of the kernel: the compiler
@@ -86,7 +108,7 @@ __device__ __forceinline__ void touch_args(const RowLinArgs &a) {
   asm volatile("" ::"s"(a.stat_out), "s"(a.res_stat));
 }
 
-template <int MR>
+template <int MR, bool KV16 = false>
 __global__ __launch_bounds__(256) void row_linear_ln_kernel(RowLinArgs a) {
   touch_args(a);
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -94,7 +116,7 @@ __global__ __launch_bounds__(256) void row_linear_ln_kernel(RowLinArgs a) {
     const long p = *a.pos;
     a.x += p * a.x_pos;
     if (a.res) a.res += p * a.res_pos;
-    if (a.out2) a.out2 += p * a.out2_pos;
+    if (a.out2) a.out2 = out2_at<KV16>(a.out2, p * a.out2_pos);
   }
   float *xs = sm;                    // [MR][K]
   float *stat = sm + MR * a.K;       // [MR][2] residual mean / rstd
@@ -196,7 +218,7 @@ __global__ __launch_bounds__(256) void row_linear_ln_kernel(RowLinArgs a) {
         }
         if (a.relu) v = fmaxf(v, 0.f);
         if (n < a.split) a.out[(size_t)m * a.out_stride + n] = v;
-        else a.out2[(size_t)m * a.out2_stride + (n - a.split)] = v;
+        else store_out2<KV16>(a.out2, (size_t)m * a.out2_stride + (n - a.split), v);
       }
     }
   }
@@ -212,7 +234,7 @@ struct Gemv1Args {
   int nt;              // non-temporal weight loads (ISI_DECODE_NT, default on)
 };
 
-template <int KQ>   // float4 per lane of a K-long row: K <= 256 KQ
+template <int KQ, bool KV16 = false>   // float4 per lane of a K-long row: K <= 256 KQ
 __global__ __launch_bounds__(256) void row_gemv1_kernel(Gemv1Args g) {
   touch_args(g.r);
   asm volatile("" ::"s"(g.part), "s"(g.NS), "s"(g.HD), "s"(g.nt));
@@ -380,7 +402,7 @@ __global__ __launch_bounds__(256) void row_gemv1_kernel(Gemv1Args g) {
     }
     if (a.relu) v = fmaxf(v, 0.f);
     if (n < a.split) a.out[n] = v;
-    else a.out2[ppos * a.out2_pos + (n - a.split)] = v;
+    else store_out2<KV16>(a.out2, ppos * a.out2_pos + (n - a.split), v);
   }
 }
 
@@ -388,7 +410,7 @@ __global__ __launch_bounds__(256) void row_gemv1_kernel(Gemv1Args g) {
 // once and used for every row, the rows pass through in groups of MR (round 5: ALL rows of a stage in one launch; groups of
 // 8 rows used to be launches of their own, 4 per stage at batch 32).  Per row the operations of row_gemv1_kernel /
 // row_linear_ln_kernel, in their order: a row's result does not depend on the rows it shares a launch with.
-template <int KQ, int MR, bool RAG = false>
+template <int KQ, int MR, bool RAG = false, bool KV16 = false>
 __global__ __launch_bounds__(256) void row_gemvm_kernel(RowLinArgs a) {
   touch_args(a);
   long ppos = 0;
@@ -547,7 +569,7 @@ __global__ __launch_bounds__(256) void row_gemvm_kernel(RowLinArgs a) {
       if (a.relu) v = fmaxf(v, 0.f);
       const size_t mr = (size_t)(m0 + m);
       if (n < a.split) a.out[mr * a.out_stride + n] = v;
-      else a.out2[(RAG ? (long)rp[mr] : ppos) * a.out2_pos + mr * a.out2_stride + (n - a.split)] = v;
+      else store_out2<KV16>(a.out2, (RAG ? (long)rp[mr] : ppos) * a.out2_pos + mr * a.out2_stride + (n - a.split), v);
     }
   }
   }
@@ -643,7 +665,7 @@ __device__ __forceinline__ void mfma_row_stats_lds(const float *__restrict__ xs,
 // `ksplit_ws` != nullptr (K beyond one chunk on a grid too small to fill the chip: linear2 of a feed-forward block, 16 tiles at
 // N = 512): grid z = the K chunk, a workgroup multiplies ONE chunk and leaves its raw 32 x 32 sums in ksplit_ws[z][M][N];
 // row_mfma_finish_kernel adds the chunks in order and applies bias / residual / ReLU (33.8 -> ~13 us for that stage at B = 32).
-template <bool RAG = false>
+template <bool RAG = false, bool KV16 = false>
 __global__ __launch_bounds__(256) void row_mfma32_kernel(RowLinArgs a, float *__restrict__ ksplit_ws, int knobs_decode_stats_global) {
   touch_args(a);
   asm volatile("" ::"s"(ksplit_ws));
@@ -847,13 +869,13 @@ __global__ __launch_bounds__(256) void row_mfma32_kernel(RowLinArgs a, float *__
       if (a.relu) v = fmaxf(v, 0.f);
       const size_t m = (size_t)(m0 + i);
       if (nj < a.split) a.out[m * a.out_stride + nj] = v;
-      else a.out2[(RAG ? (long)rp[m] : ppos) * a.out2_pos + m * a.out2_stride + (nj - a.split)] = v;
+      else store_out2<KV16>(a.out2, (RAG ? (long)rp[m] : ppos) * a.out2_pos + m * a.out2_stride + (nj - a.split), v);
     }
   }
 }
 
 // one workgroup per row: the K chunks' sums in chunk order, then bias / (normalised) residual / ReLU as in the tile kernel
-template <bool RAG = false>
+template <bool RAG = false, bool KV16 = false>
 __global__ __launch_bounds__(256) void row_mfma_finish_kernel(RowLinArgs a, const float *__restrict__ ws, int nz) {
   touch_args(a);
   __shared__ float red[8];
@@ -893,7 +915,7 @@ __global__ __launch_bounds__(256) void row_mfma_finish_kernel(RowLinArgs a, cons
     }
     if (a.relu) v = fmaxf(v, 0.f);
     if (n < a.split) a.out[(size_t)m * a.out_stride + n] = v;
-    else a.out2[ppos * a.out2_pos + (size_t)m * a.out2_stride + (n - a.split)] = v;
+    else store_out2<KV16>(a.out2, ppos * a.out2_pos + (size_t)m * a.out2_stride + (n - a.split), v);
   }
 }
 
@@ -902,24 +924,27 @@ bool row_mfma_supported(const RowLinArgs &a) {
          (reinterpret_cast<uintptr_t>(a.W) & 15) == 0 && (!a.ln_g || ((reinterpret_cast<uintptr_t>(a.ln_g) | reinterpret_cast<uintptr_t>(a.ln_b)) & 15) == 0);
 }
 
-template <bool RAG = false>
+template <bool RAG = false, bool KV16 = false>
 int launch_row_mfma(const RowLinArgs &a, hipStream_t st, float *ksplit_ws = nullptr, size_t ksplit_floats = 0) {
+  if constexpr (!KV16) {
+    if (a.out2 && a.out2_bf16) return launch_row_mfma<RAG, true>(a, st, ksplit_ws, ksplit_floats);
+  }
   static DeviceOnce attr_set;       // once, outside any stream capture (the first position runs direct)
   if (!attr_set.done()) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(row_mfma32_kernel<RAG>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(row_mfma32_kernel<RAG, KV16>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)kRowMfmaLds) != hipSuccess)
       return check_launch("hipFuncSetAttribute(row_mfma32)");
     attr_set.mark();
   }
   const int tiles = ((a.N + 31) / 32) * ((a.M + 31) / 32), nz = (a.K + MF_KC - 1) / MF_KC;
   if (nz > 1 && tiles < 128 && ksplit_ws && (size_t)nz * a.M * a.N <= ksplit_floats) {
-    hipLaunchKernelGGL(row_mfma32_kernel<RAG>, dim3((a.N + 31) / 32, (a.M + 31) / 32, nz), dim3(256), kRowMfmaLds, st, a, ksplit_ws, knobs().decode_stats_global);
+    hipLaunchKernelGGL((row_mfma32_kernel<RAG, KV16>), dim3((a.N + 31) / 32, (a.M + 31) / 32, nz), dim3(256), kRowMfmaLds, st, a, ksplit_ws, knobs().decode_stats_global);
     int rc = check_launch("row_mfma32 (K chunks)");
     if (rc) return rc;
-    hipLaunchKernelGGL(row_mfma_finish_kernel<RAG>, dim3(a.M), dim3(256), 0, st, a, ksplit_ws, nz);
+    hipLaunchKernelGGL((row_mfma_finish_kernel<RAG, KV16>), dim3(a.M), dim3(256), 0, st, a, ksplit_ws, nz);
     return check_launch("row_mfma_finish");
   }
-  hipLaunchKernelGGL(row_mfma32_kernel<RAG>, dim3((a.N + 31) / 32, (a.M + 31) / 32), dim3(256), kRowMfmaLds, st, a, (float *)nullptr, knobs().decode_stats_global);
+  hipLaunchKernelGGL((row_mfma32_kernel<RAG, KV16>), dim3((a.N + 31) / 32, (a.M + 31) / 32), dim3(256), kRowMfmaLds, st, a, (float *)nullptr, knobs().decode_stats_global);
   return check_launch("row_mfma32");
 }
 
@@ -936,12 +961,15 @@ bool row_gemvm_supported(const RowLinArgs &a) {
   return row_gemvm_group(a.M, kq) >= 2;
 }
 
-template <bool RAG = false>
+template <bool RAG = false, bool KV16 = false>
 int launch_row_gemvm(const RowLinArgs &a, hipStream_t st) {
+  if constexpr (!KV16) {
+    if (a.out2 && a.out2_bf16) return launch_row_gemvm<RAG, true>(a, st);
+  }
   const int kq = a.K <= 256 ? 1 : a.K <= 512 ? 2 : a.K <= 1024 ? 4 : 8;
   const int mr = row_gemvm_group(a.M, kq);
   dim3 grid(kq >= 4 ? (a.N + 3) / 4 : (a.N + NPB - 1) / NPB), block(256);
-#define ISI_GM(KQ_, MR_) hipLaunchKernelGGL((row_gemvm_kernel<KQ_, MR_, RAG>), grid, block, 0, st, a)
+#define ISI_GM(KQ_, MR_) hipLaunchKernelGGL((row_gemvm_kernel<KQ_, MR_, RAG, KV16>), grid, block, 0, st, a)
   if (kq == 1) { if (mr == 2) ISI_GM(1, 2); else if (mr == 4) ISI_GM(1, 4); else ISI_GM(1, 8); }
   else if (kq == 2) { if (mr == 2) ISI_GM(2, 2); else if (mr == 4) ISI_GM(2, 4); else ISI_GM(2, 8); }
   else if (kq == 4) { if (mr == 2) ISI_GM(4, 2); else ISI_GM(4, 4); }
@@ -959,6 +987,13 @@ bool row_gemv1_supported(const RowLinArgs &a, bool merged) {
 int launch_row_gemv1(const RowLinArgs &a, const float *part, int NS, int HD, hipStream_t st) {
   Gemv1Args g{a, part, NS, HD, knobs().decode_nt};
   dim3 grid((a.N + NPB - 1) / NPB), grid1((a.N + 3) / 4), block(256);   // grid1: one output feature per wave
+  if (a.out2 && a.out2_bf16) {
+    if (a.K <= 256) hipLaunchKernelGGL((row_gemv1_kernel<1, true>), grid, block, 0, st, g);
+    else if (a.K <= 512) hipLaunchKernelGGL((row_gemv1_kernel<2, true>), grid, block, 0, st, g);
+    else if (a.K <= 1024) hipLaunchKernelGGL((row_gemv1_kernel<4, true>), grid1, block, 0, st, g);
+    else hipLaunchKernelGGL((row_gemv1_kernel<8, true>), grid1, block, 0, st, g);
+    return check_launch("row_gemv1 (bf16 k|v)");
+  }
   if (a.K <= 256) hipLaunchKernelGGL(row_gemv1_kernel<1>, grid, block, 0, st, g);
   else if (a.K <= 512) hipLaunchKernelGGL(row_gemv1_kernel<2>, grid, block, 0, st, g);
   else if (a.K <= 1024) hipLaunchKernelGGL(row_gemv1_kernel<4>, grid1, block, 0, st, g);
@@ -976,7 +1011,7 @@ int launch_row_linear(const RowLinArgs &a0, hipStream_t st) {
     a.x += (size_t)m0 * a.x_stride;
     if (a.res) a.res += (size_t)m0 * a.res_stride;
     a.out += (size_t)m0 * a.out_stride;
-    if (a.out2) a.out2 += (size_t)m0 * a.out2_stride;
+    advance_out2(a, (long)m0 * a.out2_stride);
     const int rc = launch_row_linear_8(a, st);
     if (rc) return rc;
   }
@@ -989,7 +1024,11 @@ int launch_row_linear_8(const RowLinArgs &a, hipStream_t st) {
   dim3 grid((a.N + NPB - 1) / NPB), block(256);
 #define ISI_RL(MR)                                                                                      \
   do {                                                                                                  \
-    auto kern = row_linear_ln_kernel<MR>;                                                               \
+    if (a.out2 && a.out2_bf16) { ISI_RL_(MR, true); } else { ISI_RL_(MR, false); }                      \
+  } while (0)
+#define ISI_RL_(MR, KV16_)                                                                              \
+  do {                                                                                                  \
+    auto kern = row_linear_ln_kernel<MR, KV16_>;                                                        \
     static DeviceOnce attr_set;  /* once, outside any stream capture (the first position runs direct) */ \
     if (!attr_set.done()) {                                                                                    \
       if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                                     \
@@ -1005,6 +1044,7 @@ int launch_row_linear_8(const RowLinArgs &a, hipStream_t st) {
   else if (a.M <= 4) ISI_RL(4);
   else ISI_RL(8);
 #undef ISI_RL
+#undef ISI_RL_
   return check_launch("row_linear_ln");
 }
 
@@ -1029,7 +1069,7 @@ int launch_stage_rows(const RowLinArgs &a, const float *part, int ns, int hd, fl
     g8.x += (size_t)m0 * a.x_stride;
     if (g8.res) g8.res += (size_t)m0 * a.res_stride;
     g8.out += (size_t)m0 * a.out_stride;
-    if (g8.out2) g8.out2 += (size_t)m0 * a.out2_stride;
+    advance_out2(g8, (long)m0 * a.out2_stride);
     const int rc8 = row_gemvm_supported(g8) ? launch_row_gemvm(g8, q_st) : launch_row_linear(g8, q_st);
     if (rc8) return rc8;
   }
@@ -1230,6 +1270,16 @@ static int sample_run_impl(const isi_prior_w *w, const isi_prior_state *s, const
     return ISI_E_WORKSPACE;
   }
   if (w->d_model % 4 || w->dim_feedforward % 4 || w->d_model % w->nhead) return invalid("prior_sample_run: bad dims");
+  if (s->kv_format != ISI_KV_F32 && s->kv_format != ISI_KV_BF16)
+    return invalid("prior_sample_run: state->kv_format must be ISI_KV_F32 (0) or ISI_KV_BF16 (1)");
+  const bool kv16 = s->kv_format == ISI_KV_BF16;
+  if (kv16 && (w->d_model % 8 || ((reinterpret_cast<uintptr_t>(s->kv_cache) | reinterpret_cast<uintptr_t>(s->memory_kv)) & 15)))
+    return invalid("prior_sample_run: bf16 kv_cache / memory_kv need d_model % 8 == 0 and 16-byte aligned arrays");
+  // element `elems` of a cache array in its format (layer strides, the k / v halves: all counted in elements)
+  auto kv_at = [kv16](const float *base, size_t elems) -> float * {
+    return kv16 ? reinterpret_cast<float *>(reinterpret_cast<uint16_t *>(const_cast<float *>(base)) + elems)
+                : const_cast<float *>(base) + elems;
+  };
   const int d = w->d_model, B = s->B, hd = d / w->nhead, ff = w->dim_feedforward;
   float *q = s->scratch, *ao = q + (size_t)B * d, *y1 = ao + (size_t)B * d, *y2 = y1 + (size_t)B * d;
   float *y3a = y2 + (size_t)B * d, *y3b = y3a + (size_t)B * d, *hid = y3b + (size_t)B * d;
@@ -1269,7 +1319,7 @@ static int sample_run_impl(const isi_prior_w *w, const isi_prior_state *s, const
       if (p >= 0) {
         a.x += (long)p * a.x_pos;
         if (a.res) a.res += (long)p * a.res_pos;
-        if (a.out2) a.out2 += (long)p * a.out2_pos;
+        advance_out2(a, (long)p * a.out2_pos);
         a.pos = nullptr;
       }
       if (!a.x_pos && !a.res_pos && !a.out2_pos) a.pos = nullptr;      // nothing of this launch depends on the position
@@ -1296,13 +1346,14 @@ static int sample_run_impl(const isi_prior_w *w, const isi_prior_state *s, const
     const float *ln_g = nullptr, *ln_b = nullptr;
     for (int l = 0; l < w->n_layers; ++l) {
       const isi_decoder_layer_w &L = w->layers[l];
-      float *cache = s->kv_cache + l * cache_layer;
+      float *cache = kv_at(s->kv_cache, l * cache_layer);
       float *y3 = (l & 1) ? y3b : y3a;
       RowLinArgs a;
       int rc;
       // q | k,v  (k,v straight into the cache slot of this position)
       a = RowLinArgs{yin, d, ln_g, ln_b, L.self_attn.in_proj_weight, L.self_attn.in_proj_bias, nullptr, 0, nullptr,
                      nullptr, q, d, cache, 2 * d, d, B, 3 * d, d, 0, 1e-5f, pos, yin_pos, 0, (long)B * 2 * d};
+      a.out2_bf16 = kv16 ? 1 : 0;
       // y1 = LN_in(yin) + ao Wo^T + bo   (its launch follows the attention)
       RowLinArgs a_o{ao, d, nullptr, nullptr, L.self_attn.out_proj_weight, L.self_attn.out_proj_bias, yin, d, ln_g,
                      ln_b, y1, d, nullptr, 0, d, B, d, d, 0, 1e-5f, pos, 0, yin_pos, 0};
@@ -1310,13 +1361,13 @@ static int sample_run_impl(const isi_prior_w *w, const isi_prior_state *s, const
       if ((rc = launch_rows(a))) return rc;
       isi_attn_args g;
       memset(&g, 0, sizeof g);
-      g.q = q; g.k = cache; g.v = cache + d; g.rel_embeddings = L.self_attn.rel_embeddings; g.out = ao;
+      g.q = q; g.k = cache; g.v = kv_at(cache, d); g.rel_embeddings = L.self_attn.rel_embeddings; g.out = ao;
       g.Sq = 1; g.Sk = s->S_t; g.B = B; g.H = w->nhead; g.head_dim = hd;
       g.q_sb = d; g.q_sh = hd; g.k_ss = (int64_t)B * 2 * d; g.k_sb = 2 * d; g.k_sh = hd;
       g.v_ss = g.k_ss; g.v_sb = g.k_sb; g.v_sh = hd; g.o_sb = d; g.o_sh = hd;
       g.Cq = w->Cd; g.Ck = w->Cd; g.Ek = w->Ed; g.rel_rows = L.self_attn.rel_rows; g.scale = scale;
       const bool defer_s = merge_in_gemv && ns_self > 1;
-      if ((rc = rel_attention_decode_launch(&g, p < 0 ? 0 : p, pos_arg, 1, attn_ws, defer_s ? 0 : 1, q_st, row_pos))) return rc;
+      if ((rc = rel_attention_decode_launch(&g, p < 0 ? 0 : p, pos_arg, 1, attn_ws, defer_s ? 0 : 1, q_st, row_pos, s->kv_format))) return rc;
       if ((rc = defer_s ? launch_rows(a_o, attn_ws, ns_self) : launch_rows(a_o))) return rc;
       // feed-forward on LN2(y2)
       RowLinArgs a_f1{y2, d, L.norm2_w, L.norm2_b, L.linear1_w, L.linear1_b, nullptr, 0, nullptr, nullptr, hid, ff,
@@ -1331,7 +1382,7 @@ static int sample_run_impl(const isi_prior_w *w, const isi_prior_state *s, const
         if ((rc = launch_single_source_cross(ss, q_st))) return rc;
         if (handoff) a_f2.res_stat = rowstat;
       } else {
-        const float *memkv = s->memory_kv + l * mem_layer;
+        const float *memkv = kv_at(s->memory_kv, l * mem_layer);
         // cross-attention query from LN1(y1)
         a = RowLinArgs{y1, d, L.norm1_w, L.norm1_b, L.cross_attn.in_proj_weight, L.cross_attn.in_proj_bias, nullptr, 0,
                        nullptr, nullptr, q, d, nullptr, 0, d, B, d, d, 0, 1e-5f, nullptr, 0, 0, 0};
@@ -1339,10 +1390,10 @@ static int sample_run_impl(const isi_prior_w *w, const isi_prior_state *s, const
                         L.norm1_w, L.norm1_b, y2, d, nullptr, 0, d, B, d, d, 0, 1e-5f, nullptr, 0, 0, 0};
         hand_stats(a, a_o2, merge_in_gemv && ns_cross > 1);
         if ((rc = launch_rows(a))) return rc;
-        g.k = memkv; g.v = memkv + d; g.rel_embeddings = L.cross_attn.rel_embeddings; g.Sk = s->S_src;
+        g.k = memkv; g.v = kv_at(memkv, d); g.rel_embeddings = L.cross_attn.rel_embeddings; g.Sk = s->S_src;
         g.Ck = w->Ce; g.Ek = w->Ee; g.rel_rows = L.cross_attn.rel_rows;
         const bool defer_c = merge_in_gemv && ns_cross > 1;
-        if ((rc = rel_attention_decode_launch(&g, p < 0 ? 0 : p, pos_arg, 0, attn_ws, defer_c ? 0 : 1, q_st, row_pos))) return rc;
+        if ((rc = rel_attention_decode_launch(&g, p < 0 ? 0 : p, pos_arg, 0, attn_ws, defer_c ? 0 : 1, q_st, row_pos, s->kv_format))) return rc;
         if ((rc = defer_c ? launch_rows(a_o2, attn_ws, ns_cross) : launch_rows(a_o2))) return rc;
         hand_stats(a_f1, a_f2);
       }

@@ -402,6 +402,251 @@ __global__ __launch_bounds__(256 * NG) void rel_attention_decode_f32_kernel(
   }
 }
 
+// ---- bf16 key / value rows (isi_rel_attention_decode_kv16_f32; isi_prior_state.kv_format = ISI_KV_BF16): the cached rows
+// are the bandwidth of batched decoding, so an opt-in cache stores them in 16 bits -- bf16, one plane,
+// fp32's range -- and this kernel widens them on the fly: float(k) = bits << 16 (exact), then the fp32 kernel's arithmetic.
+// q, the relative table, logits, softmax, accumulation and out stay fp32.  The 16-byte load per lane is kept: a lane holds
+// EIGHT elements, a group of G = HD/8 lanes owns a row and 2 x the rows are in flight per pass (RPP = 256/G), so the register
+// blocking is re-derived: UMAX = 5 (splits of up to 5 RPP = 160 / 320 / 640 keys at head_dim 64 / 32 / 16, at least the fp32
+// kernel's 9 x 256/(HD/4); 16 registers per row -- 4 k, 4 v, 8 table -- against 12), UB = 8 (the same 16 x 256/(HD/4) keys in
+// flight per step of the long path).  A row's dot product is the fp32 kernel's tree (quads pairwise, then lanes); the SUMS
+// OVER KEYS (softmax denominator, p.v) run over twice the lane groups with half the keys each, so their order differs from
+// the fp32 kernel's: equal up to rounding, not bit for bit.  The short / long decision is taken by the split length for NG = 1
+// as well, so the one-workgroup and the two-launch form of a two-split call walk the same path: same bits.
+// LDS: [8] + [4][HD] wave partials + the scores of one split (the long path), per half.
+template <int G> __device__ __forceinline__ float kv16_group_sum(float v) {
+  if constexpr (G == 8) return group8_sum(v);
+  else if constexpr (G == 4) return group4_sum(v);
+  else return v + dpp_f32<0xB1>(v);      // quad_perm [1,0,3,2]: lane pairs
+}
+__device__ __forceinline__ void kv16_widen(const uint4 w, float4 &lo, float4 &hi) {
+  lo = make_float4(__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u), __uint_as_float(w.y << 16),
+                   __uint_as_float(w.y & 0xffff0000u));
+  hi = make_float4(__uint_as_float(w.z << 16), __uint_as_float(w.z & 0xffff0000u), __uint_as_float(w.w << 16),
+                   __uint_as_float(w.w & 0xffff0000u));
+}
+__device__ __forceinline__ float kv16_dot(const float4 qa, const float4 qb, const uint4 kw, const float4 ea, const float4 eb) {
+  float4 ka, kb;
+  kv16_widen(kw, ka, kb);
+  const float4 xa = make_float4(ka.x + ea.x, ka.y + ea.y, ka.z + ea.z, ka.w + ea.w);
+  const float4 xb = make_float4(kb.x + eb.x, kb.y + eb.y, kb.z + eb.z, kb.w + eb.w);
+  return ((qa.x * xa.x + qa.y * xa.y) + (qa.z * xa.z + qa.w * xa.w)) + ((qb.x * xb.x + qb.y * xb.y) + (qb.z * xb.z + qb.w * xb.w));
+}
+__device__ __forceinline__ void kv16_axpy(float4 &oa, float4 &ob, const float p, const uint4 vw) {
+  float4 va, vb;
+  kv16_widen(vw, va, vb);
+  oa.x += p * va.x; oa.y += p * va.y; oa.z += p * va.z; oa.w += p * va.w;
+  ob.x += p * vb.x; ob.y += p * vb.y; ob.z += p * vb.z; ob.w += p * vb.w;
+}
+
+template <int HD, int NG = 1, bool RAG = false>
+__global__ __launch_bounds__(256 * NG) void rel_attention_decode_kv16_kernel(
+    const float *__restrict__ q, const uint16_t *__restrict__ k, const uint16_t *__restrict__ v,
+    const float *__restrict__ e, float *__restrict__ out, int Sk, int64_t q_sb, int64_t q_sh, int64_t k_ss,
+    int64_t k_sb, int64_t k_sh, int64_t v_ss, int64_t v_sb, int64_t v_sh, int64_t o_sb, int64_t o_sh,
+    int q_pos, int Cq, int Ck, int Ek, int R, float scale, int chunk, float *__restrict__ partial,
+    const int *__restrict__ pos, int self_keys, const int *__restrict__ row_pos) {
+  asm volatile("" ::"s"(q), "s"(k), "s"(v), "s"(e), "s"(out), "s"(Sk), "s"(q_sb), "s"(q_sh), "s"(k_ss), "s"(k_sb), "s"(k_sh),
+               "s"(v_ss), "s"(v_sb), "s"(v_sh));
+  asm volatile("" ::"s"(o_sb), "s"(o_sh), "s"(q_pos), "s"(Cq), "s"(Ck), "s"(Ek), "s"(R), "s"(scale), "s"(chunk), "s"(partial),
+               "s"(pos), "s"(self_keys));
+  const int nsplit = NG == 2 ? 2 : (int)gridDim.z;
+  if constexpr (RAG) {
+    q_pos = row_pos[(size_t)(pos ? *pos : 0) * gridDim.y + blockIdx.y];
+    if (self_keys) {
+      Sk = q_pos + 1;
+      chunk = (Sk + nsplit - 1) / nsplit;
+    }
+  } else if (pos) {
+    q_pos = *pos;
+    if (self_keys) {
+      Sk = q_pos + 1;
+      chunk = (Sk + nsplit - 1) / nsplit;
+    }
+  }
+  constexpr int G = HD / 8;        // lanes per row: 2, 4 or 8 (eight bf16 = one 16-B load per lane)
+  constexpr int RPP = 256 / G;     // rows per pass
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int kg = NG == 2 ? (int)(threadIdx.x >> 8) : 0;
+  const int split = NG == 2 ? kg : (int)blockIdx.z;
+  const int sc_len = (chunk + 3) & ~3;
+  float *red = sm + kg * (8 + 4 * HD + sc_len);                    // [8]
+  float *part = red + 8;           // [4][HD] the waves' partial outputs
+  float *sc = part + 4 * HD;       // [chunk]
+  float *mg = sm + NG * (8 + 4 * HD + sc_len);                     // NG = 2: [2][HD + 2] the halves' (o, max, sum)
+  const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
+  const int grp = tid / G, gl = tid % G;
+  const int h = blockIdx.x, b = blockIdx.y;
+  const int kbeg = split * chunk;
+  k += (size_t)kbeg * k_ss;
+  v += (size_t)kbeg * v_ss;
+  const int key0 = kbeg;
+  Sk = max(min(Sk - kbeg, chunk), 0);
+  if (NG == 1 && Sk <= 0) {           // empty split (only with a fixed split count): neutral partial
+    if (gridDim.z > 1 && tid < HD) {
+      float *pp = partial + (((size_t)b * gridDim.x + h) * gridDim.z + blockIdx.z) * (HD + 4);
+      pp[tid] = 0.f;
+      if (tid == 0) { pp[HD] = -1e30f; pp[HD + 1] = 0.f; }
+    }
+    return;
+  }
+  const float *qb = q + b * q_sb + h * q_sh + gl * 8;
+  const float4 qa = *reinterpret_cast<const float4 *>(qb), qc = *reinterpret_cast<const float4 *>(qb + 4);
+  const int evq = q_pos / Cq;
+  const uint16_t *kb = k + b * k_sb + h * k_sh + gl * 8;
+  const uint16_t *vb = v + b * v_sb + h * v_sh + gl * 8;
+  const float *eb = e ? e + (size_t)h * R * HD + gl * 8 : nullptr;
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 o0 = zero4, o1 = zero4;
+  float gmax, gsum;
+  constexpr int UMAX = 5;
+  if (chunk <= UMAX * RPP) {
+    // ---- short split: K, V and relative rows are all requested up front -- one memory round trip
+    uint4 kk[UMAX], vv[UMAX];
+    float4 ea[UMAX], ec[UMAX];
+#pragma unroll
+    for (int u = 0; u < UMAX; ++u) {
+      const int j = grp + u * RPP;
+      const int jc = j < Sk ? j : 0;
+      ea[u] = ec[u] = zero4;
+      if (NG == 2 && Sk == 0) {        // (an empty half reads nothing: its rows may hold anything)
+        kk[u] = vv[u] = make_uint4(0u, 0u, 0u, 0u);
+        continue;
+      }
+      kk[u] = *reinterpret_cast<const uint4 *>(kb + (size_t)jc * k_ss);
+      vv[u] = *reinterpret_cast<const uint4 *>(vb + (size_t)jc * v_ss);
+      if (eb) {
+        int r = evq - (key0 + jc) / Ck + Ek - 1;
+        r = r < 0 ? 0 : (r >= R ? R - 1 : r);
+        ea[u] = *reinterpret_cast<const float4 *>(eb + (size_t)r * HD);
+        ec[u] = *reinterpret_cast<const float4 *>(eb + (size_t)r * HD + 4);
+      }
+    }
+    float sv[UMAX];
+    float lmax = -1e30f;
+#pragma unroll
+    for (int u = 0; u < UMAX; ++u) {
+      float acc = kv16_group_sum<G>(kv16_dot(qa, qc, kk[u], ea[u], ec[u]));
+      acc *= scale;
+      sv[u] = acc;
+      if (grp + u * RPP < Sk) lmax = fmaxf(lmax, acc);
+    }
+    lmax = wave64_max(lmax);
+    if (lane == 0) red[wave] = lmax;
+    __syncthreads();
+    gmax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    float lsum = 0.f;
+#pragma unroll
+    for (int u = 0; u < UMAX; ++u) {
+      const float pj = grp + u * RPP < Sk ? __expf(sv[u] - gmax) : 0.f;
+      if (gl == 0) lsum += pj;
+      kv16_axpy(o0, o1, pj, vv[u]);
+    }
+    lsum = wave64_sum(lsum);
+    if (lane == 0) red[4 + wave] = lsum;
+    __syncthreads();
+    gsum = (red[4] + red[5]) + (red[6] + red[7]);
+  } else {
+    // ---- long split: scores, then values, 8 rows of a lane group in flight per step
+    constexpr int UB = 8;
+    float lmax = -1e30f;
+    for (int j0 = grp; j0 < Sk; j0 += UB * RPP) {
+      uint4 kk[UB];
+      float4 ea[UB], ec[UB];
+#pragma unroll
+      for (int u = 0; u < UB; ++u) {
+        const int j = j0 + u * RPP;
+        const int jc = j < Sk ? j : j0;
+        kk[u] = *reinterpret_cast<const uint4 *>(kb + (size_t)jc * k_ss);
+        ea[u] = ec[u] = zero4;
+        if (eb) {
+          int r = evq - (key0 + jc) / Ck + Ek - 1;
+          r = r < 0 ? 0 : (r >= R ? R - 1 : r);
+          ea[u] = *reinterpret_cast<const float4 *>(eb + (size_t)r * HD);
+          ec[u] = *reinterpret_cast<const float4 *>(eb + (size_t)r * HD + 4);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < UB; ++u) {
+        const int j = j0 + u * RPP;
+        float acc = kv16_group_sum<G>(kv16_dot(qa, qc, kk[u], ea[u], ec[u]));
+        if (j < Sk) {
+          acc *= scale;
+          if (gl == 0) sc[j] = acc;
+          lmax = fmaxf(lmax, acc);
+        }
+      }
+    }
+    lmax = wave64_max(lmax);
+    if (lane == 0) red[wave] = lmax;
+    __syncthreads();
+    gmax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    float lsum = 0.f;
+    for (int j = tid; j < Sk; j += 256) {
+      const float pj = __expf(sc[j] - gmax);
+      sc[j] = pj;
+      lsum += pj;
+    }
+    lsum = wave64_sum(lsum);
+    if (lane == 0) red[4 + wave] = lsum;
+    __syncthreads();
+    gsum = (red[4] + red[5]) + (red[6] + red[7]);
+    for (int j0 = grp; j0 < Sk; j0 += UB * RPP) {
+      uint4 vv[UB];
+#pragma unroll
+      for (int u = 0; u < UB; ++u) {
+        const int j = j0 + u * RPP;
+        vv[u] = *reinterpret_cast<const uint4 *>(vb + (size_t)(j < Sk ? j : j0) * v_ss);
+      }
+#pragma unroll
+      for (int u = 0; u < UB; ++u) {
+        const int j = j0 + u * RPP;
+        kv16_axpy(o0, o1, j < Sk ? sc[j] : 0.f, vv[u]);
+      }
+    }
+  }
+  // the wave's 64 / G lane groups are added up in registers, then one row per wave goes through LDS
+#pragma unroll
+  for (int o = G; o < 64; o <<= 1) {
+    o0.x += __shfl_xor(o0.x, o); o0.y += __shfl_xor(o0.y, o); o0.z += __shfl_xor(o0.z, o); o0.w += __shfl_xor(o0.w, o);
+    o1.x += __shfl_xor(o1.x, o); o1.y += __shfl_xor(o1.y, o); o1.z += __shfl_xor(o1.z, o); o1.w += __shfl_xor(o1.w, o);
+  }
+  if (lane < G) {
+    *reinterpret_cast<float4 *>(part + wave * HD + lane * 8) = o0;
+    *reinterpret_cast<float4 *>(part + wave * HD + lane * 8 + 4) = o1;
+  }
+  __syncthreads();
+  if (NG == 2) {                       // the two halves' partials meet in LDS: rel_attention_combine_kernel's merge
+    if (tid < HD) {
+      mg[kg * (HD + 2) + tid] = (part[tid] + part[HD + tid]) + (part[2 * HD + tid] + part[3 * HD + tid]);
+      if (tid == 0) { mg[kg * (HD + 2) + HD] = gmax; mg[kg * (HD + 2) + HD + 1] = gsum; }
+    }
+    __syncthreads();
+    if (kg == 0 && tid < HD) {
+      float M = -1e30f;
+      for (int s_ = 0; s_ < 2; ++s_) M = fmaxf(M, mg[s_ * (HD + 2) + HD]);
+      float num = 0.f, den = 0.f;
+      for (int s_ = 0; s_ < 2; ++s_) {
+        const float w = __expf(mg[s_ * (HD + 2) + HD] - M);
+        num += w * mg[s_ * (HD + 2) + tid];
+        den += w * mg[s_ * (HD + 2) + HD + 1];
+      }
+      out[b * o_sb + h * o_sh + tid] = num * (1.0f / den);
+    }
+    return;
+  }
+  if (tid < HD) {
+    const float acc = (part[tid] + part[HD + tid]) + (part[2 * HD + tid] + part[3 * HD + tid]);
+    if (gridDim.z == 1) {
+      out[b * o_sb + h * o_sh + tid] = acc / gsum;
+    } else {
+      float *pp = partial + (((size_t)b * gridDim.x + h) * gridDim.z + blockIdx.z) * (HD + 4);
+      pp[tid] = acc;
+      if (tid == 0) { pp[HD] = gmax; pp[HD + 1] = gsum; }
+    }
+  }
+}
+
 // Merge the key splits of one (batch, head): softmax-weighted sum of the partials.
 __global__ void rel_attention_combine_kernel(const float *__restrict__ partial, float *__restrict__ out,
                                              int HD, int NS, int64_t o_sb, int64_t o_sh) {
@@ -461,6 +706,10 @@ int rel_attention_decode_f32(const isi_attn_args *g, int q_pos, float *workspace
   return rel_attention_decode_pos_f32(g, q_pos, nullptr, 0, workspace, stream);
 }
 
+int rel_attention_decode_kv16_f32(const isi_attn_args *g, int q_pos, float *workspace, hipStream_t stream) {
+  return rel_attention_decode_launch(g, q_pos, nullptr, 0, workspace, /*combine*/ 1, stream, nullptr, ISI_KV_BF16);
+}
+
 // pos != nullptr: the query position is read from device memory at run time (replayable launch); with
 // self_keys the key count is position + 1 and g->Sk is its upper bound (it fixes grid and LDS sizes).
 int rel_attention_decode_pos_f32(const isi_attn_args *g, int q_pos, const int *pos, int self_keys, float *workspace,
@@ -472,8 +721,15 @@ int rel_attention_decode_pos_f32(const isi_attn_args *g, int q_pos, const int *p
 // split's maximum and sum) stay in `workspace` for the caller to merge (the decoding loop merges them in the prologue
 // of the out-projection: one dependent launch less); g->out is then not written.
 int rel_attention_decode_launch(const isi_attn_args *g, int q_pos, const int *pos, int self_keys, float *workspace,
-                                int combine, hipStream_t stream, const int *row_pos) {
+                                int combine, hipStream_t stream, const int *row_pos, int kv_format) {
   if (!g || !g->q || !g->k || !g->v || !g->out) return invalid("attention_decode: null pointer");
+  if (kv_format != ISI_KV_F32 && kv_format != ISI_KV_BF16) return invalid("attention_decode: kv_format must be ISI_KV_F32 or ISI_KV_BF16");
+  const bool kv16 = kv_format == ISI_KV_BF16;
+  // bf16 rows: a lane's eight elements are one 16-byte load
+  if (kv16 && (((reinterpret_cast<uintptr_t>(g->q) | reinterpret_cast<uintptr_t>(g->k) | reinterpret_cast<uintptr_t>(g->v) |
+                 reinterpret_cast<uintptr_t>(g->rel_embeddings)) & 15) ||
+               ((g->k_ss | g->k_sb | g->k_sh | g->v_ss | g->v_sb | g->v_sh) & 7) || ((g->q_sb | g->q_sh) & 3)))
+    return invalid("attention_decode (bf16 keys/values): q, k, v, rel_embeddings 16-byte aligned, k / v strides multiples of 8, q strides of 4");
   if (g->Sk <= 0 || g->B <= 0 || g->H <= 0 || g->Cq <= 0 || g->Ck <= 0) return invalid("attention_decode: bad shape");
   if (g->Sk > 65536) return unsupported("attention_decode: more than 65536 keys");
   const int ns = workspace ? rel_attention_decode_splits(g->Sk, g->B * g->H) : 1;
@@ -487,7 +743,9 @@ int rel_attention_decode_launch(const isi_attn_args *g, int q_pos, const int *po
   // CU where three of the 256-thread ones do -- at 48 sequences x 8 heads the launch became a round and a half, 35.5 against
   // 37.2 k codes/s)
   const bool both = ns == 2 && combine && !knobs().decode_attn_separate_splits && g->B * g->H <= current_device_cu_count();
-  const size_t per_group = 8 + 256 * 4 + (((g->Sk + ns - 1) / ns + 3) & ~3);          // red + part[256/G][HD] + scores
+  // (the one-workgroup form's gate is the fp32 kernel's for bf16 rows as well: that workgroup holds two of its four
+  // 256-thread shares of a CU's registers either way -- profiles/kv16_resource_usage.txt)
+  const size_t per_group = 8 + (kv16 ? 4 * (size_t)g->head_dim : 256 * 4) + (((g->Sk + ns - 1) / ns + 3) & ~3);   // red + part + scores
   const size_t smem = (both ? 2 * per_group + 2 * (size_t)(g->head_dim + 2) : per_group) * sizeof(float);
   dim3 grid(g->H, g->B, both ? 1 : ns), block(both ? 512 : 256);
 #define ISI_DEC(HD)                                                                                         \
@@ -503,6 +761,28 @@ int rel_attention_decode_launch(const isi_attn_args *g, int q_pos, const int *po
                        g->o_sh, q_pos, g->Cq, g->Ck, g->Ek, g->rel_rows, g->scale, chunk, workspace, pos,  \
                        self_keys, row_pos);                                                                 \
   } while (0)
+#define ISI_DEC16(HD)                                                                                       \
+  do {                                                                                                      \
+    auto kern = row_pos ? (both ? rel_attention_decode_kv16_kernel<HD, 2, true> : rel_attention_decode_kv16_kernel<HD, 1, true>) \
+                        : (both ? rel_attention_decode_kv16_kernel<HD, 2> : rel_attention_decode_kv16_kernel<HD, 1>); \
+    if (smem > 48 * 1024 &&                                                                                 \
+        hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                            (int)smem) != hipSuccess)                                                       \
+      return check_launch("hipFuncSetAttribute(attention_decode)");                                         \
+    hipLaunchKernelGGL(kern, grid, block, smem, stream, g->q, reinterpret_cast<const uint16_t *>(g->k),     \
+                       reinterpret_cast<const uint16_t *>(g->v), g->rel_embeddings, g->out, Sk,             \
+                       g->q_sb, g->q_sh, g->k_ss, g->k_sb, g->k_sh, g->v_ss, g->v_sb, g->v_sh, g->o_sb,     \
+                       g->o_sh, q_pos, g->Cq, g->Ck, g->Ek, g->rel_rows, g->scale, chunk, workspace, pos,  \
+                       self_keys, row_pos);                                                                 \
+  } while (0)
+  if (kv16) {
+    switch (g->head_dim) {
+      case 16: ISI_DEC16(16); break;
+      case 32: ISI_DEC16(32); break;
+      case 64: ISI_DEC16(64); break;
+      default: return unsupported("attention_decode: head_dim must be 16, 32 or 64");
+    }
+  } else
   switch (g->head_dim) {
     case 16: ISI_DEC(16); break;
     case 32: ISI_DEC(32); break;
@@ -510,7 +790,8 @@ int rel_attention_decode_launch(const isi_attn_args *g, int q_pos, const int *po
     default: return unsupported("attention_decode: head_dim must be 16, 32 or 64");
   }
 #undef ISI_DEC
-  int rc = check_launch("rel_attention_decode_f32");
+#undef ISI_DEC16
+  int rc = check_launch(kv16 ? "rel_attention_decode_kv16_f32" : "rel_attention_decode_f32");
   if (rc || ns == 1 || !combine || both) return rc;
   hipLaunchKernelGGL(rel_attention_combine_kernel, dim3(g->H, g->B), dim3(g->head_dim), 0, stream, workspace,
                      g->out, g->head_dim, ns, g->o_sb, g->o_sh);

@@ -58,9 +58,11 @@ def timerange_change(transformer_top, transformer_bottom, top_code: torch.Tensor
                      class_conditioning_top: Mapping[str, torch.Tensor],
                      class_conditioning_bottom: Mapping[str, torch.Tensor], device,
                      uniform_sampling: bool = False, generator: Optional[torch.Generator] = None,
+                     kv_cache_dtype: Optional[torch.dtype] = None,
                      **sampling_kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
     """top_code [1,F_t,T], bottom_code [1,F_b,T_b] (T may exceed the models' duration), mask bool
-    [1,F,W] in the resolution of `layer` over the model window.  Returns the updated (top, bottom)."""
+    [1,F,W] in the resolution of `layer` over the model window.  Returns the updated (top, bottom).
+    kv_cache_dtype: `sample_model`'s key/value cache format (None: the switch ISI_DECODE_KV)."""
     (s_top, e_top), (s_bot, e_bot), ratio_t = _windows(top_code, bottom_code, transformer_top, transformer_bottom,
                                                         start_index_top)
     top_frame = top_code[..., s_top:e_top]
@@ -68,7 +70,8 @@ def timerange_change(transformer_top, transformer_bottom, top_code: torch.Tensor
     mask = mask.to(device)
     ti_top = make_time_indexes(s_top, top_code.shape[-1], transformer_top.shape[-1])
     ti_bottom = make_time_indexes(s_bot, bottom_code.shape[-1], transformer_bottom.shape[-1])
-    common = dict(device=device, batch_size=1, temperature=temperature, generator=generator, **sampling_kwargs)
+    common = dict(device=device, batch_size=1, temperature=temperature, generator=generator,
+                  kv_cache_dtype=kv_cache_dtype, **sampling_kwargs)
 
     def resample(model, condition, initial, m, cls, ti_src, ti_tgt):
         if uniform_sampling:
@@ -100,8 +103,8 @@ def _cat_classes(dicts) -> Mapping[str, torch.Tensor]:
 
 
 @torch.no_grad()
-def timerange_change_batch(transformer_top, transformer_bottom, requests: Sequence[Mapping], device
-                           ) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+def timerange_change_batch(transformer_top, transformer_bottom, requests: Sequence[Mapping], device,
+                           kv_cache_dtype: Optional[torch.dtype] = None) -> List[Tuple[torch.Tensor, torch.Tensor]]:
     """Independent `timerange_change` requests in at most two ragged `sample_model` calls: every `layer='top'` request
     through the top prior together, then every request through the bottom prior together (a top request with the mask
     up-sampled over its new top map).  A request is a mapping with the arguments of `timerange_change` -- top_code,
@@ -132,7 +135,7 @@ def timerange_change_batch(transformer_top, transformer_bottom, requests: Sequen
             time_indexes_target=torch.tensor(ti_tgt),
             top_k_sampling_k=[int(q.get('top_k_sampling_k', 0)) for q in req],
             top_p_sampling_p=[float(q.get('top_p_sampling_p', 0.0)) for q in req],
-            uniforms=torch.cat(uniforms, 1))
+            uniforms=torch.cat(uniforms, 1), kv_cache_dtype=kv_cache_dtype)
 
     def draw(model, j, frame):        # timerange_change's draws from the request's generator, in its order
         if j['req'].get('uniform_sampling', False):
@@ -181,7 +184,9 @@ def timerange_change_batch(transformer_top, transformer_bottom, requests: Sequen
 def generate(transformer_top, transformer_bottom, temperature: float,
              class_conditioning_top: Mapping[str, torch.Tensor],
              class_conditioning_bottom: Mapping[str, torch.Tensor], device,
-             generator: Optional[torch.Generator] = None, **sampling_kwargs):
+             generator: Optional[torch.Generator] = None, kv_cache_dtype: Optional[torch.dtype] = None,
+             **sampling_kwargs):
+    sampling_kwargs = dict(sampling_kwargs, kv_cache_dtype=kv_cache_dtype)
     top = sample_model(model=transformer_top, device=device, batch_size=1, codemap_size=transformer_top.shape,
                        temperature=temperature, class_conditioning=class_conditioning_top, generator=generator,
                        **sampling_kwargs)
@@ -219,7 +224,7 @@ def codes_to_audio(vqvae, spectrograms_helper, top_code: torch.Tensor, bottom_co
 @torch.no_grad()
 def top_conditioned_sample(vqvae, transformer_bottom, spectrograms_helper, top_code: torch.Tensor, temperature: float,
                            class_conditioning_bottom, device, top_k_sampling_k: int = 0, top_p_sampling_p: float = 0.0,
-                           generator=None, uniforms=None):
+                           generator=None, uniforms=None, kv_cache_dtype: Optional[torch.dtype] = None):
     """The compute of `/top-conditioned-sample` (flask_server.py:1049-1110): ONE top codemap, a batch of bottom codemaps
     drawn from the bottom prior -- one per entry of the per-row class conditioning (the route passes a pitch range:
     `make_conditioning_tensors({'pitch': (lo, hi), ...})`, sample.py:68-101) --, decoded and turned into audio.
@@ -230,7 +235,8 @@ def top_conditioned_sample(vqvae, transformer_bottom, spectrograms_helper, top_c
     top = top_code.to(device).expand(n, -1, -1)
     bottom = sample_model(transformer_bottom, device, n, transformer_bottom.shape, temperature, condition=top,
                           class_conditioning=class_conditioning_bottom, top_k_sampling_k=top_k_sampling_k,
-                          top_p_sampling_p=top_p_sampling_p, generator=generator, uniforms=uniforms)
+                          top_p_sampling_p=top_p_sampling_p, generator=generator, uniforms=uniforms,
+                          kv_cache_dtype=kv_cache_dtype)
     audio = spectrograms_helper.to_audio(vqvae.decode_code(top, bottom))
     return bottom, audio
 

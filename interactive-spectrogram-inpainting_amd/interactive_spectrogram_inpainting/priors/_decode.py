@@ -16,6 +16,16 @@ import torch
 from . import _ops
 
 
+def kv_cache_format(kv_cache_dtype) -> int:
+    """`isi_prior_state.kv_format` of a cache dtype: float32 (the default) or bfloat16 (opt-in: half the bytes the cached
+    attention streams per position, keys / values rounded to 8 significand bits).  Anything else: ValueError."""
+    if kv_cache_dtype is torch.float32:
+        return 0
+    if kv_cache_dtype is torch.bfloat16:
+        return 1
+    raise ValueError(f"kv_cache_dtype must be torch.float32 or torch.bfloat16, not {kv_cache_dtype!r}")
+
+
 def _is_aligned(layers) -> bool:
     from VQCPCB.transformer.transformer_custom import TransformerAlignedDecoderLayerCustom
     return any(isinstance(l, TransformerAlignedDecoderLayerCustom) for l in layers)
@@ -47,8 +57,10 @@ def _single_source_check(model, layers, S_t: int, S_src: int, device) -> bool:
 
 
 class IncrementalDecoder:
-    def __init__(self, model, memory: torch.Tensor, batch_size: int):
-        """memory: [S_src, B, d] encoder output."""
+    def __init__(self, model, memory: torch.Tensor, batch_size: int, kv_cache_dtype: torch.dtype = torch.float32):
+        """memory: [S_src, B, d] encoder output.  kv_cache_dtype: float32, or bfloat16 for 16-bit caches."""
+        kv_cache_format(kv_cache_dtype)
+        self.kv_cache_dtype = kv_cache_dtype
         dec = model.transformer.decoder
         self.layers = list(dec.layers)
         _refuse_aligned(self.layers)
@@ -63,9 +75,10 @@ class IncrementalDecoder:
         self.Ce, self.Ee = model.source_num_channels, model.source_num_events_with_start_symbol
         memory = memory.contiguous()
         self.S_src = memory.shape[0]
-        self.memory_kv: List[torch.Tensor] = [l.multihead_attn.project_kv(memory) for l in self.layers]
+        # (a 16-bit cache: torch's copy rounds to nearest-even)
+        self.memory_kv: List[torch.Tensor] = [l.multihead_attn.project_kv(memory).to(kv_cache_dtype) for l in self.layers]
         self.cache: List[torch.Tensor] = [
-            torch.zeros(S_t, batch_size, 2 * d, dtype=torch.float32, device=memory.device) for _ in self.layers]
+            torch.zeros(S_t, batch_size, 2 * d, dtype=kv_cache_dtype, device=memory.device) for _ in self.layers]
         if batch_size > 32:
             raise NotImplementedError("incremental decoding supports batch sizes up to 32 (NativeSampler: 256)")
 
@@ -91,7 +104,10 @@ class IncrementalDecoder:
             sa, ca = layer.self_attn, layer.multihead_attn
             W, b = sa.in_proj_weight, sa.in_proj_bias
             q = self._linear(x, W[:d], b[:d])
-            self._linear(x, W[d:], b[d:], out=self.cache[l][p])           # k|v of this row -> cache slot p
+            if self.kv_cache_dtype is torch.float32:
+                self._linear(x, W[d:], b[d:], out=self.cache[l][p])       # k|v of this row -> cache slot p
+            else:
+                self.cache[l][p].copy_(self._linear(x, W[d:], b[d:]))     # ... rounded to the cache's format
             kc = self.cache[l]
             a = _ops.rel_attention_decode(q, kc[..., :d], kc[..., d:], sa.rel_embeddings, sa.nhead,
                                           n_keys=p + 1, q_pos=p, Cq=self.Cd, Ck=self.Cd, Ek=self.Ed)
@@ -118,8 +134,10 @@ class NativeSampler:
     host synchronisation; sampled indices stay on the device."""
 
     def __init__(self, model, memory: torch.Tensor, x_seq: torch.Tensor, codes: torch.Tensor,
-                 mask_seq, uniforms: torch.Tensor):
+                 mask_seq, uniforms: torch.Tensor, kv_cache_dtype: torch.dtype = torch.float32):
         import ctypes as C
+        kv_format = kv_cache_format(kv_cache_dtype)        # before anything is allocated
+        self.kv_cache_dtype = kv_cache_dtype
         import numpy as np
         from .. import _hip
         from .transformer import Seq2SeqInputKind
@@ -179,9 +197,10 @@ class NativeSampler:
             self.cross_out = torch.stack([l.multihead_attn.out_proj.run(l.multihead_attn.project_kv(memory)[..., d:].contiguous())
                                           for l in dec_layers]).contiguous()
         else:
-            self.memory_kv = torch.stack([l.multihead_attn.project_kv(memory) for l in dec_layers]).contiguous()
+            # (a 16-bit cache: layer by layer through torch's copy, round-to-nearest-even)
+            self.memory_kv = torch.stack([l.multihead_attn.project_kv(memory).to(kv_cache_dtype) for l in dec_layers]).contiguous()
         S_t = x_seq.shape[0]
-        self.kv_cache = torch.zeros(len(dec_layers), S_t, B, 2 * d, dtype=torch.float32, device=dev)
+        self.kv_cache = torch.zeros(len(dec_layers), S_t, B, 2 * d, dtype=kv_cache_dtype, device=dev)
         self.x_seq, self.codes = x_seq, codes
         self.mask_host = np.ascontiguousarray(np.asarray(mask_seq, dtype=np.uint8))
         self.uniforms = uniforms.to(device=dev, dtype=torch.float32).contiguous()
@@ -197,6 +216,7 @@ class NativeSampler:
         st.uniforms, st.scratch, st.scratch_floats = self.uniforms.data_ptr(), self.scratch.data_ptr(), n_scratch
         st.S_t, st.S_src, st.S, st.B = S_t, memory.shape[0], codes.shape[1], B
         st.start_len = model.target_start_symbol.shape[1]
+        st.kv_format = kv_format
         self.state = st
 
     @torch.no_grad()
@@ -214,14 +234,18 @@ class NativeSampler:
         for l, layer in enumerate(self.model.transformer.decoder.layers):
             sa = layer.self_attn
             qkv = sa._project(x, 0)                                  # [p0, B, 3d]
-            self.kv_cache[l, :p0] = qkv[..., d:]
-            a = _ops.rel_attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], sa.rel_embeddings, sa.nhead,
+            self.kv_cache[l, :p0] = qkv[..., d:]                     # (a 16-bit cache: torch's copy, round-to-nearest-even)
+            kv = qkv[..., d:]
+            if self.kv_cache_dtype is not torch.float32:
+                kv = self.kv_cache[l, :p0].float()                   # the pass attends what the later single steps will read
+            a = _ops.rel_attention(qkv[..., :d], kv[..., :d], kv[..., d:], sa.rel_embeddings, sa.nhead,
                                    sa.Cq, sa.Ck, sa.Ek, mask_mode=1)
             x1 = _add_norm(layer, sa.out_proj, a, x, layer.norm1)
             if self.single_source:
                 x2 = layer.norm2.run(self.cross_out[l].index_select(0, src_row), residual=x1)   # the loop's table rows
             else:
-                c = layer.multihead_attn(x1, None, None, kv=self.memory_kv[l])
+                # (the batched pass attends with fp32 operands: a 16-bit memory_kv is widened, exactly)
+                c = layer.multihead_attn(x1, None, None, kv=self.memory_kv[l].float())
                 x2 = _add_norm(layer, layer.multihead_attn.out_proj, c, x1, layer.norm2)
             h = layer.linear1.run(x2, relu=True)
             x = _add_norm(layer, layer.linear2, h, x2, layer.norm3)

@@ -412,8 +412,16 @@ def rel_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rel: Option
 
 def rel_attention_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rel: Optional[torch.Tensor],
                          nhead: int, n_keys: int, q_pos: int, Cq: int, Ck: int, Ek: int) -> torch.Tensor:
-    """q [B,d] (one position), k/v caches [S_max,B,d]; attends to keys 0..n_keys-1."""
+    """q [B,d] (one position), k/v caches [S_max,B,d]; attends to keys 0..n_keys-1.  k / v both float32, or both
+    bfloat16 (a 16-bit cache: `isi_rel_attention_decode_kv16_f32` widens the rows and computes in fp32)."""
     _hip.require_gpu(q, "attention input")
+    kv16 = k.dtype == torch.bfloat16 and v.dtype == torch.bfloat16
+    for name, t in (("attention keys", k), ("attention values", v)):
+        if not t.is_cuda:
+            _hip.require_gpu(t, name)
+        if not kv16 and t.dtype != torch.float32:
+            raise _hip.HipLibraryError(f"{name} have dtype {t.dtype}; expected k and v both float32 or both bfloat16 "
+                                       f"(k {k.dtype}, v {v.dtype})")
     B, d = q.shape
     hd = d // nhead
     out = torch.empty(B, d, dtype=torch.float32, device=q.device)
@@ -425,8 +433,12 @@ def rel_attention_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rel:
     L = _hip.lib()
     ws = torch.empty(L.isi_rel_attention_decode_workspace_floats(B, nhead, hd), dtype=torch.float32,
                      device=q.device)
-    _hip.check(L.isi_rel_attention_decode_f32(C.byref(a), q_pos, ws.data_ptr(), _s(q)),
-               "isi_rel_attention_decode_f32")
+    if kv16:
+        _hip.check(L.isi_rel_attention_decode_kv16_f32(C.byref(a), q_pos, ws.data_ptr(), _s(q)),
+                   "isi_rel_attention_decode_kv16_f32")
+    else:
+        _hip.check(L.isi_rel_attention_decode_f32(C.byref(a), q_pos, ws.data_ptr(), _s(q)),
+                   "isi_rel_attention_decode_f32")
     return out
 
 

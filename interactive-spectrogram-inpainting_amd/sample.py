@@ -15,13 +15,14 @@ instead of torch.multinomial's stream.
 """
 from __future__ import annotations
 
+import os
 from typing import Iterable, Mapping, Optional, Sequence, Union
 
 import numpy as np
 import torch
 
 from interactive_spectrogram_inpainting.priors import _ops
-from interactive_spectrogram_inpainting.priors._decode import NativeSampler
+from interactive_spectrogram_inpainting.priors._decode import NativeSampler, kv_cache_format
 from interactive_spectrogram_inpainting.priors.transformer import Seq2SeqInputKind, VQNSynthTransformer
 
 
@@ -36,6 +37,19 @@ def top_k_top_p_filtering(logits: torch.Tensor, top_k: int = 0, top_p: float = 0
     _, filt = _ops.sample_rows(rows, 1.0, top_k, top_p, u, return_filtered=True)
     logits.copy_(filt.reshape(logits.shape))
     return logits
+
+
+def _kv_cache_dtype(kv_cache_dtype: Optional[torch.dtype]) -> torch.dtype:
+    """The key/value cache format of the KV-cached loop: the argument, or (None) the switch ISI_DECODE_KV = f32 | bf16
+    (default f32).  bf16 halves the bytes a position streams from the two caches; keys and values then carry 8
+    significand bits and the sampled codes may differ from an fp32-cache run's."""
+    if kv_cache_dtype is None:
+        name = os.environ.get("ISI_DECODE_KV", "f32")
+        if name not in ("f32", "bf16"):
+            raise ValueError(f"ISI_DECODE_KV must be f32 or bf16, not {name!r}")
+        kv_cache_dtype = torch.bfloat16 if name == "bf16" else torch.float32
+    kv_cache_format(kv_cache_dtype)            # ValueError for anything but float32 / bfloat16
+    return kv_cache_dtype
 
 
 def _per_row(value, batch_size: int, name: str):
@@ -88,13 +102,20 @@ def sample_model(model: VQNSynthTransformer, device: Union[torch.device, str], b
                  progressbar_decorator=None, use_predictive_sampling: bool = False,
                  generator: Optional[torch.Generator] = None,
                  uniforms: Optional[torch.Tensor] = None,
-                 gumbel_noise: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Ragged batches: rows are independent requests.  `mask` [B, F, T] may differ per row (each row walks its own span),
+                 gumbel_noise: Optional[torch.Tensor] = None,
+                 kv_cache_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """kv_cache_dtype: format of the loop's two key/value caches -- torch.float32, torch.bfloat16, or None for the switch
+    ISI_DECODE_KV (f32 | bf16, default f32).  Predictive sampling runs full passes and has no cache.
+    Ragged batches: rows are independent requests.  `mask` [B, F, T] may differ per row (each row walks its own span),
     `time_indexes_source` / `time_indexes_target` may be [B, T] tensors, and `temperature`, `top_k_sampling_k`,
     `top_p_sampling_p` may be length-B sequences or tensors.  A [1, F, T] mask or one whose rows are all equal, with
     shared parameters, samples exactly as a single request does."""
     if constraint is not None:
         raise NotImplementedError
+    kv_cache_dtype = _kv_cache_dtype(kv_cache_dtype)
+    if use_predictive_sampling and kv_cache_dtype is not torch.float32:
+        raise ValueError("predictive sampling runs full decoder passes and has no key/value cache: kv_cache_dtype / "
+                         "ISI_DECODE_KV do not apply")
     device = torch.device(device)
     if mask is not None and mask.dim() == 3 and mask.shape[0] not in (1, batch_size):
         raise ValueError(f"mask for {mask.shape[0]} rows, batch of {batch_size}")
@@ -137,7 +158,7 @@ def sample_model(model: VQNSynthTransformer, device: Union[torch.device, str], b
                 time_indexes_target=time_rows(time_indexes_target, lo, hi),
                 top_k_sampling_k=param_rows(row_params[1], lo, hi), top_p_sampling_p=param_rows(row_params[2], lo, hi),
                 progressbar_decorator=progressbar_decorator, use_predictive_sampling=use_predictive_sampling,
-                uniforms=uniforms[:, lo:hi], gumbel_noise=rows(gumbel_noise, lo, hi)))
+                uniforms=uniforms[:, lo:hi], gumbel_noise=rows(gumbel_noise, lo, hi), kv_cache_dtype=kv_cache_dtype))
         return torch.cat(parts, 0)
     if initial_code is None:
         fill = model.mask_token_index if model.self_conditional_model else 0
@@ -196,7 +217,7 @@ def sample_model(model: VQNSynthTransformer, device: Union[torch.device, str], b
         pos, commit, p0 = _ragged_plan(np.asarray(mask_rows, dtype=bool), start_len - 1)
         if pos.shape[0] == 0:
             return model.target_codemaps_helper.to_time_frequency_map(code_seq).long()
-        sampler = NativeSampler(model, memory, x_seq, code_seq, mask_seq, uniforms)
+        sampler = NativeSampler(model, memory, x_seq, code_seq, mask_seq, uniforms, kv_cache_dtype=kv_cache_dtype)
         n_steps = sampler.plan_rows(pos, commit, temp_rows, top_k_rows, top_p_rows)
         sampler.prefill(p0)
         chunk = n_steps if progressbar_decorator is None else 64
@@ -215,7 +236,7 @@ def sample_model(model: VQNSynthTransformer, device: Union[torch.device, str], b
         return model.target_codemaps_helper.to_time_frequency_map(code_seq).long()
     p_first, n_pos = masked[0] + start_len - 1, min(n_pos, masked[-1] + start_len)
     # the whole loop natively: no per-token return to Python, no host sync
-    sampler = NativeSampler(model, memory, x_seq, code_seq, mask_seq, uniforms)
+    sampler = NativeSampler(model, memory, x_seq, code_seq, mask_seq, uniforms, kv_cache_dtype=kv_cache_dtype)
     if p_first < 8:
         p_first = 0                                        # a few rows: not worth a batched pass
     sampler.prefill(p_first)

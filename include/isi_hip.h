@@ -580,6 +580,19 @@ int isi_rel_attention_decode_f32(const isi_attn_args *args, int q_pos, float *wo
  * workspace, same split rule.  This is the cached attention of isi_prior_state.kv_format = ISI_KV_BF16. */
 int isi_rel_attention_decode_kv16_f32(const isi_attn_args *args, int q_pos, float *workspace,
                                       void *stream);
+/* The same step against keys / values WITHOUT a batch dimension: every one of the args->B query rows attends the same
+ * args->Sk rows of args->k / args->v (N variations of one request share the encoder memory).  args->k_sb and args->v_sb
+ * must be 0 (else ISI_E_INVALID); kv_format = ISI_KV_F32 or ISI_KV_BF16 says how k / v are read (bf16 widened exactly, as
+ * above).  One workgroup owns a head, a key split and a block of 16 rows and fetches every key / value / table row once
+ * for all of them: the bytes read per call do not grow with B beyond the number of row blocks.  Logits, softmax and
+ * accumulation in fp32 as in isi_rel_attention_decode_f32; the keys are summed in another order (equal up to rounding).
+ * B 1..256, head_dim 16 / 32 / 64; q, k, v, rel_embeddings 16-byte aligned, k / v strides multiples of 4 elements (bf16:
+ * 8), q strides of 4.  Rows beyond the keys in use may hold anything.  workspace:
+ * isi_rel_attention_decode_shared_workspace_floats(B, H, head_dim) floats (up to 8 key splits and the merge launch of
+ * the entries above), or NULL for one split.  isi_prior_state.memory_shared = 1 runs the cross-attention this way. */
+size_t isi_rel_attention_decode_shared_workspace_floats(int B, int H, int head_dim);
+int isi_rel_attention_decode_shared_f32(const isi_attn_args *args, int q_pos, float *workspace, int kv_format,
+                                        void *stream);
 
 /* One categorical draw per row (sample.py:286-295): logits/temperature ->
  * top_k_top_p_filtering (sample.py:36-65) -> softmax -> inverse-CDF draw with the
@@ -623,6 +636,10 @@ typedef struct isi_prior_state {
   float *scratch;          /* device, isi_prior_decode_scratch_floats(w, B) floats                    */
   size_t scratch_floats;
   int S_t, S_src, S, B, start_len;
+  int memory_shared;       /* 0 (default): memory_kv / cross_out carry a batch dimension.  1: all B rows share ONE source */
+                           /* -- memory_kv is [n_layers, S_src, 1, 2d], cross_out [n_layers, S_src, 1, d] (below).  The    */
+                           /* field takes the four bytes that padded start_len up to the next pointer: size and every      */
+                           /* other offset of the struct are what they were, and a zeroed struct means 0                   */
   const float *cross_out;  /* [n_layers, S_src, B, d] or NULL: single-source cross-attention (below)          */
   int kv_format;           /* ISI_KV_F32 (0): kv_cache / memory_kv are fp32 arrays; ISI_KV_BF16 (1): bf16 arrays of  */
                            /* the same logical shape (below); anything else: ISI_E_INVALID                            */
@@ -652,7 +669,14 @@ size_t isi_prior_decode_scratch_floats(const isi_prior_w *w, int B);
  * fp32's range, nothing overflows); the caller fills memory_kv and any prefilled cache rows in the same format.  The
  * cached attention widens the rows exactly and computes in fp32 (isi_rel_attention_decode_kv16_f32); x_seq, cross_out,
  * the scratch rows and every weight stay fp32.  Sampled codes may differ from an fp32-cache run's (keys and values
- * carry 8 significand bits); the format is part of the graph cache key. */
+ * carry 8 significand bits); the format is part of the graph cache key.
+ * Shared memory (state->memory_shared = 1, opt-in; 0 takes exactly the launches it took): the B rows are variations of ONE
+ * request -- same source sequence, hence one encoder memory.  memory_kv is [n_layers, S_src, 1, 2d] (in kv_format) and
+ * cross_out [n_layers, S_src, 1, d]: B times fewer bytes to hold and, per position, to read.  From 48 rows on the
+ * cross-attention runs as isi_rel_attention_decode_shared_f32; below, the per-row kernel reads the one copy with batch stride
+ * 0 (the launches of a batched memory, every row on the same cache lines); the single-source launch reads its table row
+ * with batch stride 0.  kv_cache, x_seq, codes and uniforms keep their batch dimension.  Part of the
+ * graph cache key like every field.  isi_prior_sample_run_rows refuses it (ISI_E_UNSUPPORTED). */
 int isi_prior_sample_run(const isi_prior_w *w, const isi_prior_state *state, int p_begin,
                          int p_end, float temperature, int top_k, float top_p, void *stream);
 

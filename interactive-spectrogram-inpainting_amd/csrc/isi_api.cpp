@@ -344,6 +344,12 @@ int isi_rel_attention_decode_f32(const isi_attn_args *args, int q_pos, float *wo
 int isi_rel_attention_decode_kv16_f32(const isi_attn_args *args, int q_pos, float *workspace, void *stream) {
   return rel_attention_decode_kv16_f32(args, q_pos, workspace, S(stream));
 }
+int isi_rel_attention_decode_shared_f32(const isi_attn_args *args, int q_pos, float *workspace, int kv_format, void *stream) {
+  return rel_attention_decode_shared_launch(args, q_pos, nullptr, workspace, /*combine*/ 1, kv_format, S(stream));
+}
+size_t isi_rel_attention_decode_shared_workspace_floats(int B, int H, int head_dim) {
+  return rel_attention_decode_workspace_floats(B, H, head_dim);
+}
 size_t isi_rel_attention_decode_workspace_floats(int B, int H, int head_dim) {
   return rel_attention_decode_workspace_floats(B, H, head_dim);
 }

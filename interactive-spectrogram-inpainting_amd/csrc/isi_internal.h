@@ -145,6 +145,12 @@ int rel_attention_decode_launch(const isi_attn_args *g, int q_pos, const int *po
                                 int combine, hipStream_t stream, const int *row_pos = nullptr, int kv_format = 0);
 // args->k / args->v read as bf16 (isi_rel_attention_decode_kv16_f32)
 int rel_attention_decode_kv16_f32(const isi_attn_args *g, int q_pos, float *workspace, hipStream_t stream);
+int rel_attention_decode_combine(const float *partial, float *out, int B, int H, int head_dim, int ns, int64_t o_sb,
+                                 int64_t o_sh, hipStream_t stream);
+// keys / values without a batch dimension (rel_attention_decode_shared.hip): one workgroup per (head, row block, key split)
+int rel_attention_decode_shared_splits(int Sk, int B, int H);
+int rel_attention_decode_shared_launch(const isi_attn_args *g, int q_pos, const int *pos, float *workspace, int combine,
+                                       int kv_format, hipStream_t stream);
 size_t decode_stage_workspace_floats(int M, int N, int K);
 int decode_stage_f32(const float *x, int x_stride, const float *ln_g, const float *ln_b, const float *W, const float *bias,
                      const float *res, int res_stride, const float *res_g, const float *res_b, float *out, int out_stride,

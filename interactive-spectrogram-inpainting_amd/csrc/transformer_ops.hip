@@ -798,6 +798,13 @@ int rel_attention_decode_launch(const isi_attn_args *g, int q_pos, const int *po
   return check_launch("rel_attention_combine");
 }
 
+// the merge launch on its own: the shared-memory kernel (rel_attention_decode_shared.hip) leaves the same partial rows
+int rel_attention_decode_combine(const float *partial, float *out, int B, int H, int head_dim, int ns, int64_t o_sb,
+                                 int64_t o_sh, hipStream_t stream) {
+  hipLaunchKernelGGL(rel_attention_combine_kernel, dim3(H, B), dim3(head_dim), 0, stream, partial, out, head_dim, ns, o_sb, o_sh);
+  return check_launch("rel_attention_combine");
+}
+
 // ------------------------------------------------------------------ sampling
 // One categorical draw per row from logits[row, 0:n] (sample.py:286-295 of the
 // reference: temperature, top_k_top_p_filtering (sample.py:36-65), softmax,

@@ -58,11 +58,19 @@ def timerange_change(transformer_top, transformer_bottom, top_code: torch.Tensor
                      class_conditioning_top: Mapping[str, torch.Tensor],
                      class_conditioning_bottom: Mapping[str, torch.Tensor], device,
                      uniform_sampling: bool = False, generator: Optional[torch.Generator] = None,
-                     kv_cache_dtype: Optional[torch.dtype] = None,
+                     kv_cache_dtype: Optional[torch.dtype] = None, num_variations: Optional[int] = None,
                      **sampling_kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
     """top_code [1,F_t,T], bottom_code [1,F_b,T_b] (T may exceed the models' duration), mask bool
     [1,F,W] in the resolution of `layer` over the model window.  Returns the updated (top, bottom).
-    kv_cache_dtype: `sample_model`'s key/value cache format (None: the switch ISI_DECODE_KV)."""
+    kv_cache_dtype: `sample_model`'s key/value cache format (None: the switch ISI_DECODE_KV).
+    num_variations = N: N alternatives for the request, returned as (top [N,F_t,T], bottom [N,F_b,T_b]).  The prior of
+    `layer` samples N variations over one shared source (`sample_model(num_variations=N)`); after a top-layer change the
+    bottom prior has N different conditions and runs as an ordinary batch of N."""
+    if num_variations is not None:
+        return _timerange_change_variations(transformer_top, transformer_bottom, top_code, bottom_code, mask, layer,
+                                            start_index_top, temperature, class_conditioning_top,
+                                            class_conditioning_bottom, device, uniform_sampling, generator, kv_cache_dtype,
+                                            int(num_variations), sampling_kwargs)
     (s_top, e_top), (s_bot, e_bot), ratio_t = _windows(top_code, bottom_code, transformer_top, transformer_bottom,
                                                         start_index_top)
     top_frame = top_code[..., s_top:e_top]
@@ -96,6 +104,55 @@ def timerange_change(transformer_top, transformer_bottom, top_code: torch.Tensor
     else:
         raise ValueError(f"unknown layer {layer}")
     return top_code, bottom_code
+
+
+def _timerange_change_variations(transformer_top, transformer_bottom, top_code, bottom_code, mask, layer, start_index_top,
+                                 temperature, class_conditioning_top, class_conditioning_bottom, device, uniform_sampling,
+                                 generator, kv_cache_dtype, N, sampling_kwargs):
+    if N < 1:
+        raise ValueError(f"num_variations must be at least 1, not {N}")
+    if layer not in ('top', 'bottom'):
+        raise ValueError(f"unknown layer {layer}")
+    (s_top, e_top), (s_bot, e_bot), ratio_t = _windows(top_code, bottom_code, transformer_top, transformer_bottom,
+                                                        start_index_top)
+    top_frame = top_code[..., s_top:e_top]
+    bottom_frame = bottom_code[..., s_bot:e_bot]
+    mask = mask.to(device)
+    ti_top = make_time_indexes(s_top, top_code.shape[-1], transformer_top.shape[-1])
+    ti_bottom = make_time_indexes(s_bot, bottom_code.shape[-1], transformer_bottom.shape[-1])
+    common = dict(device=device, temperature=temperature, generator=generator, kv_cache_dtype=kv_cache_dtype,
+                  **sampling_kwargs)
+
+    def variations(model, condition, initial, m, cls, ti_src, ti_tgt):      # N rows over one request
+        if uniform_sampling:
+            rnd = torch.randint(0, model.n_class_target, (N,) + tuple(initial.shape[1:]), generator=generator).to(initial.device)
+            return torch.where(m, rnd, initial)
+        return sample_model(model=model, batch_size=1, num_variations=N, condition=condition, codemap_size=model.shape,
+                            class_conditioning=cls, initial_code=initial, mask=m, time_indexes_source=ti_src,
+                            time_indexes_target=ti_tgt, **common)
+
+    top_out = top_code.repeat(N, 1, 1)
+    bottom_out = bottom_code.repeat(N, 1, 1)
+    if layer == 'bottom':
+        bottom_out[..., s_bot:e_bot] = variations(transformer_bottom, top_frame, bottom_frame, mask,
+                                                  class_conditioning_bottom, ti_top, ti_bottom)
+        return top_out, bottom_out
+    condition = top_frame if transformer_top.self_conditional_model else None
+    new_top = variations(transformer_top, condition, top_frame, mask, class_conditioning_top, ti_top, ti_top)
+    top_out[..., s_top:e_top] = new_top
+    ratio_f = transformer_bottom.shape[0] // transformer_top.shape[0]
+    mask_bottom = mask.repeat_interleave(ratio_f, -2).repeat_interleave(ratio_t, -1)
+    initial = bottom_frame.repeat(N, 1, 1)
+    if uniform_sampling:
+        rnd = torch.randint(0, transformer_bottom.n_class_target, initial.shape, generator=generator).to(initial.device)
+        bottom_out[..., s_bot:e_bot] = torch.where(mask_bottom, rnd, initial)
+    else:
+        # N different conditions: an ordinary batch of N (one class value expands over the rows)
+        bottom_out[..., s_bot:e_bot] = sample_model(
+            model=transformer_bottom, batch_size=N, condition=new_top, codemap_size=transformer_bottom.shape,
+            class_conditioning=class_conditioning_bottom, initial_code=initial, mask=mask_bottom,
+            time_indexes_source=ti_top, time_indexes_target=ti_bottom, **common)
+    return top_out, bottom_out
 
 
 def _cat_classes(dicts) -> Mapping[str, torch.Tensor]:

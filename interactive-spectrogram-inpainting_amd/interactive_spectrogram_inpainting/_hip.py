@@ -122,7 +122,8 @@ class isi_prior_state(C.Structure):
     _fields_ = [("x_seq", C.c_void_p), ("kv_cache", C.c_void_p), ("memory_kv", C.c_void_p), ("codes", C.c_void_p),
                 ("mask", C.c_void_p), ("uniforms", C.c_void_p), ("scratch", C.c_void_p),
                 ("scratch_floats", C.c_size_t), ("S_t", C.c_int), ("S_src", C.c_int), ("S", C.c_int),
-                ("B", C.c_int), ("start_len", C.c_int), ("cross_out", C.c_void_p), ("kv_format", C.c_int)]
+                ("B", C.c_int), ("start_len", C.c_int), ("memory_shared", C.c_int), ("cross_out", C.c_void_p),
+                ("kv_format", C.c_int)]
 
 
 ISI_KV_F32, ISI_KV_BF16 = 0, 1
@@ -215,6 +216,8 @@ SIGNATURES = {
     "isi_rel_attention_decode_f32": (C.c_int, [C.POINTER(isi_attn_args), C.c_int, _P, _P]),
     "isi_rel_attention_decode_kv16_f32": (C.c_int, [C.POINTER(isi_attn_args), C.c_int, _P, _P]),
     "isi_rel_attention_decode_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "isi_rel_attention_decode_shared_f32": (C.c_int, [C.POINTER(isi_attn_args), C.c_int, _P, C.c_int, _P]),
+    "isi_rel_attention_decode_shared_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "isi_layernorm_f32": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int, C.c_float, _P]),
     "isi_set_dropout_seed_base": (C.c_int, [_P]),
     "isi_layernorm_dropout_f32": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int, C.c_float, C.c_float, C.c_uint64, _P]),

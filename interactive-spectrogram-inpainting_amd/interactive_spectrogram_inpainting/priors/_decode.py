@@ -134,10 +134,17 @@ class NativeSampler:
     host synchronisation; sampled indices stay on the device."""
 
     def __init__(self, model, memory: torch.Tensor, x_seq: torch.Tensor, codes: torch.Tensor,
-                 mask_seq, uniforms: torch.Tensor, kv_cache_dtype: torch.dtype = torch.float32):
+                 mask_seq, uniforms: torch.Tensor, kv_cache_dtype: torch.dtype = torch.float32,
+                 shared_memory: bool = False):
+        """shared_memory: the B rows of x_seq are variations of ONE request -- memory is [S_src, 1, d], its projected keys /
+        values (or the single-source table) are formed once at batch 1 and every row reads them
+        (`isi_prior_state.memory_shared`)."""
         import ctypes as C
         kv_format = kv_cache_format(kv_cache_dtype)        # before anything is allocated
         self.kv_cache_dtype = kv_cache_dtype
+        self.shared_memory = bool(shared_memory)
+        if self.shared_memory and memory.shape[1] != 1:
+            raise ValueError(f"shared_memory: memory is [S_src, 1, d], not {tuple(memory.shape)}")
         import numpy as np
         from .. import _hip
         from .transformer import Seq2SeqInputKind
@@ -217,6 +224,8 @@ class NativeSampler:
         st.S_t, st.S_src, st.S, st.B = S_t, memory.shape[0], codes.shape[1], B
         st.start_len = model.target_start_symbol.shape[1]
         st.kv_format = kv_format
+        if self.shared_memory:
+            st.memory_shared = 1
         self.state = st
 
     @torch.no_grad()
@@ -228,7 +237,9 @@ class NativeSampler:
             return
         from VQCPCB.transformer.transformer_custom import _add_norm
         d = self.model.d_model
-        x = self.x_seq[:p0].contiguous()
+        # a shared memory: the rows are identical up to the first sampled position -- the pass runs on row 0 alone and its
+        # keys / values are broadcast into the B slots of the cache (one copy)
+        x = self.x_seq[:p0, :1].contiguous() if self.shared_memory else self.x_seq[:p0].contiguous()
         if self.single_source:
             src_row = torch.arange(p0, device=x.device) // self.model.target_num_channels
         for l, layer in enumerate(self.model.transformer.decoder.layers):
@@ -237,7 +248,7 @@ class NativeSampler:
             self.kv_cache[l, :p0] = qkv[..., d:]                     # (a 16-bit cache: torch's copy, round-to-nearest-even)
             kv = qkv[..., d:]
             if self.kv_cache_dtype is not torch.float32:
-                kv = self.kv_cache[l, :p0].float()                   # the pass attends what the later single steps will read
+                kv = self.kv_cache[l, :p0, :x.shape[1]].float()      # the pass attends what the later single steps will read
             a = _ops.rel_attention(qkv[..., :d], kv[..., :d], kv[..., d:], sa.rel_embeddings, sa.nhead,
                                    sa.Cq, sa.Ck, sa.Ek, mask_mode=1)
             x1 = _add_norm(layer, sa.out_proj, a, x, layer.norm1)

@@ -411,9 +411,12 @@ def rel_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rel: Option
 
 
 def rel_attention_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rel: Optional[torch.Tensor],
-                         nhead: int, n_keys: int, q_pos: int, Cq: int, Ck: int, Ek: int) -> torch.Tensor:
+                         nhead: int, n_keys: int, q_pos: int, Cq: int, Ck: int, Ek: int,
+                         shared: Optional[bool] = None) -> torch.Tensor:
     """q [B,d] (one position), k/v caches [S_max,B,d]; attends to keys 0..n_keys-1.  k / v both float32, or both
-    bfloat16 (a 16-bit cache: `isi_rel_attention_decode_kv16_f32` widens the rows and computes in fp32)."""
+    bfloat16 (a 16-bit cache: `isi_rel_attention_decode_kv16_f32` widens the rows and computes in fp32).
+    Shared keys / values: k / v [S_max,1,d] against B > 1 query rows (or `shared=True` at any B) -- every row attends the
+    same keys, `isi_rel_attention_decode_shared_f32` fetches them once per block of rows."""
     _hip.require_gpu(q, "attention input")
     kv16 = k.dtype == torch.bfloat16 and v.dtype == torch.bfloat16
     for name, t in (("attention keys", k), ("attention values", v)):
@@ -424,6 +427,10 @@ def rel_attention_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rel:
                                        f"(k {k.dtype}, v {v.dtype})")
     B, d = q.shape
     hd = d // nhead
+    if shared is None:
+        shared = B > 1 and k.shape[1] == 1 and v.shape[1] == 1
+    if shared and (k.shape[1] != 1 or v.shape[1] != 1):
+        raise _hip.HipLibraryError(f"shared keys / values are [S, 1, d], not k {tuple(k.shape)} / v {tuple(v.shape)}")
     out = torch.empty(B, d, dtype=torch.float32, device=q.device)
     a = _attn_args(q, k, v, rel, out, 1, n_keys, B, nhead, hd, Cq, Ck, Ek, 0, None)
     a.q_ss, a.q_sb, a.q_sh = 0, q.stride(0), hd
@@ -431,6 +438,14 @@ def rel_attention_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rel:
     a.v_ss, a.v_sb, a.v_sh = v.stride(0), v.stride(1), hd
     a.o_ss, a.o_sb, a.o_sh = 0, out.stride(0), hd
     L = _hip.lib()
+    if shared:
+        a.k_sb = a.v_sb = 0
+        ws = torch.empty(L.isi_rel_attention_decode_shared_workspace_floats(B, nhead, hd), dtype=torch.float32,
+                         device=q.device)
+        _hip.check(L.isi_rel_attention_decode_shared_f32(C.byref(a), q_pos, ws.data_ptr(),
+                                                         _hip.ISI_KV_BF16 if kv16 else _hip.ISI_KV_F32, _s(q)),
+                   "isi_rel_attention_decode_shared_f32")
+        return out
     ws = torch.empty(L.isi_rel_attention_decode_workspace_floats(B, nhead, hd), dtype=torch.float32,
                      device=q.device)
     if kv16:

@@ -103,8 +103,13 @@ def sample_model(model: VQNSynthTransformer, device: Union[torch.device, str], b
                  generator: Optional[torch.Generator] = None,
                  uniforms: Optional[torch.Tensor] = None,
                  gumbel_noise: Optional[torch.Tensor] = None,
-                 kv_cache_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
-    """kv_cache_dtype: format of the loop's two key/value caches -- torch.float32, torch.bfloat16, or None for the switch
+                 kv_cache_dtype: Optional[torch.dtype] = None,
+                 num_variations: Optional[int] = None) -> torch.Tensor:
+    """num_variations: N alternatives for ONE request -- `batch_size` is 1 and condition, initial code, mask and class
+    conditioning are that request's; the result is [N, F, T], row n drawn with `uniforms[:, n]` ([S, N], from `generator`
+    when not given).  The source sequence, the encoder and the prefix pass run once at batch 1 and every row reads one copy
+    of the projected memory (`_sample_variations`).  The codes are those of `batch_size=N` with the inputs repeated N times.
+    kv_cache_dtype: format of the loop's two key/value caches -- torch.float32, torch.bfloat16, or None for the switch
     ISI_DECODE_KV (f32 | bf16, default f32).  Predictive sampling runs full passes and has no cache.
     Ragged batches: rows are independent requests.  `mask` [B, F, T] may differ per row (each row walks its own span),
     `time_indexes_source` / `time_indexes_target` may be [B, T] tensors, and `temperature`, `top_k_sampling_k`,
@@ -112,6 +117,11 @@ def sample_model(model: VQNSynthTransformer, device: Union[torch.device, str], b
     shared parameters, samples exactly as a single request does."""
     if constraint is not None:
         raise NotImplementedError
+    if num_variations is not None:
+        return _sample_variations(model, device, batch_size, codemap_size, temperature, condition, class_conditioning,
+                                  initial_code, mask, time_indexes_source, time_indexes_target, top_k_sampling_k,
+                                  top_p_sampling_p, progressbar_decorator, use_predictive_sampling, generator, uniforms,
+                                  kv_cache_dtype, num_variations)
     kv_cache_dtype = _kv_cache_dtype(kv_cache_dtype)
     if use_predictive_sampling and kv_cache_dtype is not torch.float32:
         raise ValueError("predictive sampling runs full decoder passes and has no key/value cache: kv_cache_dtype / "
@@ -247,6 +257,99 @@ def sample_model(model: VQNSynthTransformer, device: Union[torch.device, str], b
     for p0 in starts:
         sampler.run(p0, min(n_pos, p0 + chunk), temperature, top_k_sampling_k, top_p_sampling_p)
     return model.target_codemaps_helper.to_time_frequency_map(code_seq).long()
+
+
+def _one_value(value, name: str):
+    """A sampling parameter of variations mode: one value for all rows (a scalar, or equal entries)."""
+    if torch.is_tensor(value) or isinstance(value, (list, tuple, np.ndarray)):
+        t = torch.as_tensor(value).reshape(-1).cpu()
+        if t.numel() == 0 or not bool((t == t[0]).all()):
+            raise ValueError(f"num_variations: {name} is one value for all variations (rows of one request), not per row")
+        return t[0].item()
+    return value
+
+
+def _sample_variations(model, device, batch_size, codemap_size, temperature, condition, class_conditioning, initial_code,
+                       mask, time_indexes_source, time_indexes_target, top_k, top_p, progressbar_decorator,
+                       use_predictive_sampling, generator, uniforms, kv_cache_dtype, num_variations):
+    """`sample_model(num_variations=N)`: N rows over ONE source.  Everything that does not depend on the draws is formed once at
+    batch 1 -- source sequence, encoder memory, its projected keys / values (or the single-source table) and the keys / values
+    of the unmasked prefix; the target rows, the codes and the self-attention cache have N rows.  All checks come before any
+    device work."""
+    N = int(num_variations)
+    if N < 1:
+        raise ValueError(f"num_variations must be at least 1, not {num_variations}")
+    if use_predictive_sampling:
+        raise ValueError("num_variations runs the KV-cached loop: use_predictive_sampling does not apply")
+    if batch_size != 1:
+        raise ValueError(f"num_variations samples N rows of ONE request: batch_size must be 1, not {batch_size}")
+    for name, t in (("condition", condition), ("initial_code", initial_code)):
+        if t is not None and t.shape[0] != 1:
+            raise ValueError(f"num_variations: {name} is one request's ([1, ...]), not {tuple(t.shape)}")
+    if mask is not None and mask.dim() == 3 and mask.shape[0] != 1:
+        if not bool((mask == mask[:1]).all()):
+            raise ValueError("num_variations: the rows are variations of one request, their masks cannot differ")
+        mask = mask[:1]
+    for name, ti in (("time_indexes_source", time_indexes_source), ("time_indexes_target", time_indexes_target)):
+        if torch.is_tensor(ti) and ti.dim() == 2 and ti.shape[0] != 1:
+            raise ValueError(f"num_variations: {name} is one request's, not {tuple(ti.shape)}")
+    for name, value in class_conditioning.items():
+        if torch.as_tensor(value).numel() != 1:
+            raise ValueError(f"num_variations: class_conditioning[{name!r}] is one request's value")
+    temperature = _one_value(temperature, "temperature")
+    top_k, top_p = _one_value(top_k, "top_k_sampling_k"), _one_value(top_p, "top_p_sampling_p")
+    kv_cache_dtype = _kv_cache_dtype(kv_cache_dtype)
+    S = model.target_transformer_sequence_length
+    if uniforms is not None and tuple(uniforms.shape) != (S, N):
+        raise ValueError(f"num_variations: uniforms are [S, N] = [{S}, {N}], not {tuple(uniforms.shape)}")
+    device = torch.device(device)
+    model.eval()
+    if uniforms is None:
+        uniforms = torch.rand(S, N, generator=generator)
+    if initial_code is None:
+        fill = model.mask_token_index if model.self_conditional_model else 0
+        codemap = torch.full([1] + list(codemap_size), fill, dtype=torch.int64, device=device)
+    else:
+        codemap = initial_code.to(device)
+    cls = {name: torch.as_tensor(value).long().reshape(1, 1).to(device) for name, value in class_conditioning.items()}
+    if model.self_conditional_model:
+        condition = codemap
+    if mask is not None:
+        mask = mask.to(device)
+    target_codemap = codemap.clamp(max=model.n_class_target - 1) if initial_code is None else codemap
+    source_seq, target_seq = model.to_sequences(
+        target_codemap, condition.to(device), class_conditioning=cls, mask=mask,
+        time_indexes_source=time_indexes_source, time_indexes_target=time_indexes_target)
+    start_len = model.target_start_symbol.shape[1]
+    code_row = model.target_codemaps_helper.to_sequence(codemap)                           # [1, S]
+    mask_seq = (model.target_codemaps_helper.to_sequence(mask).reshape(-1, S).cpu().numpy()[0] if mask is not None
+                else [True] * S)
+    masked = [i for i, mk in enumerate(mask_seq) if mk]
+    if not masked:
+        return model.target_codemaps_helper.to_time_frequency_map(code_row.repeat(N, 1).contiguous()).long()
+    # one encoder pass for all variations (anti-causal for the self-conditional top prior)
+    memory, *_ = model.transformer.encoder(source_seq.transpose(0, 1).contiguous(),
+                                           mask='anticausal' if model.self_conditional_model else None)
+    x_row = target_seq.transpose(0, 1).contiguous()                                        # [S_t, 1, d]
+    p_first, n_pos = masked[0] + start_len - 1, min(S + start_len - 1, masked[-1] + start_len)
+    if p_first < 8:
+        p_first = 0
+    parts = []
+    for lo in range(0, N, 256):                    # the native loop decodes up to 256 rows at a time
+        n = min(N, lo + 256) - lo
+        x_seq = x_row.repeat(1, n, 1).contiguous()
+        code_seq = code_row.repeat(n, 1).contiguous()
+        sampler = NativeSampler(model, memory, x_seq, code_seq, mask_seq, uniforms[:, lo:lo + n].to(device=device, dtype=torch.float32),
+                                kv_cache_dtype=kv_cache_dtype, shared_memory=True)
+        sampler.prefill(p_first)
+        chunk = n_pos if progressbar_decorator is None else 64
+        starts = range(p_first, n_pos, chunk)
+        if progressbar_decorator is not None:
+            starts = progressbar_decorator(starts)
+        for p0 in starts:
+            sampler.run(p0, min(n_pos, p0 + chunk), temperature, top_k, top_p)
+        parts.append(model.target_codemaps_helper.to_time_frequency_map(code_seq).long())
+    return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
 
 
 def _predictive_sampling(model, source_seq, target_seq, code_seq, mask_seq, start_len, temperature, top_k, top_p,

@@ -602,6 +602,20 @@ int isi_rel_attention_decode_shared_f32(const isi_attn_args *args, int q_pos, fl
 int isi_sample_row_f32(const float *logits, int stride, int rows, int n, float temperature,
                        int top_k, float top_p, const float *u, int64_t *out,
                        float *filtered, void *stream);
+/* The same draw, and log_prob[row] = the MODEL's log-probability of the drawn token: log softmax of the row's raw
+ * logits (temperature 1, nothing filtered, natural log, fp32) at out[row] -- the value does not depend on temperature,
+ * top_k or top_p.  It is the decode loop's kernel and arithmetic (isi_prior_state.token_log_probs) and agrees bit for
+ * bit with isi_token_log_prob_f32 on the same logits.  n <= 1024, stride >= n. */
+int isi_sample_row_log_prob_f32(const float *logits, int stride, int rows, int n, float temperature,
+                                int top_k, float top_p, const float *u, int64_t *out,
+                                float *log_prob, void *stream);
+/* Log-probabilities of GIVEN codes: out[r] = log softmax(logits[r, 0:n])[codes[r]] = logit - max - log sum exp(logit - max),
+ * natural log, fp32; one workgroup per row, any n >= 1 (rows beyond 1024 classes are walked by 1024 threads).  The
+ * reductions run in a fixed order (wave reductions, one exchange of the wave totals): for n <= 1024 the result equals
+ * the in-loop value of isi_prior_state.token_log_probs bit for bit on equal logits.  A code outside [0, n) gives NaN for
+ * its row and reads nothing out of range.  Null pointers, rows <= 0, n <= 0 or stride < n: ISI_E_INVALID before any launch. */
+int isi_token_log_prob_f32(const float *logits, int stride, int rows, int n, const int64_t *codes, float *out,
+                           void *stream);
 
 /* Native key/value-cached sampling loop of the decoder (replaces the per-token
  * full decoder pass of sample.py:268-305).  Weights are the torch-layout
@@ -643,6 +657,9 @@ typedef struct isi_prior_state {
   const float *cross_out;  /* [n_layers, S_src, B, d] or NULL: single-source cross-attention (below)          */
   int kv_format;           /* ISI_KV_F32 (0): kv_cache / memory_kv are fp32 arrays; ISI_KV_BF16 (1): bf16 arrays of  */
                            /* the same logical shape (below); anything else: ISI_E_INVALID                            */
+  float *token_log_probs;  /* [B, S] device or NULL (default): beside every committed code, the model's log-probability of */
+                           /* it (below); other entries are left untouched.  Appended behind kv_format: every other offset  */
+                           /* is what it was, the struct grows by one pointer, and a zeroed struct means off               */
 } isi_prior_state;
 #define ISI_KV_F32 0
 #define ISI_KV_BF16 1
@@ -676,7 +693,15 @@ size_t isi_prior_decode_scratch_floats(const isi_prior_w *w, int B);
  * cross-attention runs as isi_rel_attention_decode_shared_f32; below, the per-row kernel reads the one copy with batch stride
  * 0 (the launches of a batched memory, every row on the same cache lines); the single-source launch reads its table row
  * with batch stride 0.  kv_cache, x_seq, codes and uniforms keep their batch dimension.  Part of the
- * graph cache key like every field.  isi_prior_sample_run_rows refuses it (ISI_E_UNSUPPORTED). */
+ * graph cache key like every field.  isi_prior_sample_run_rows refuses it (ISI_E_UNSUPPORTED).
+ * Token log-probabilities (state->token_log_probs != NULL, opt-in; NULL takes exactly the launches it took): the draw of
+ * every committed token also stores token_log_probs[b * S + i] = log softmax(logits)[token] of the MODEL's distribution --
+ * the row's raw logits, temperature 1, nothing filtered, natural log, fp32 -- so the value does not depend on temperature,
+ * top_k or top_p, scores of calls with different sampling settings compare, and they equal what a teacher-forced pass
+ * followed by isi_token_log_prob_f32 gives.  Two more block reductions in the draw's workgroup (fixed order: the value
+ * does not depend on the launch form); no other launch of a position changes.  Works in every form of the loop: ragged
+ * plans (rows that do not commit write nothing), memory_shared, single-source cross-attention, both kv_formats, direct
+ * launches and graph replay -- the pointer is part of the graph cache key like every field. */
 int isi_prior_sample_run(const isi_prior_w *w, const isi_prior_state *state, int p_begin,
                          int p_end, float temperature, int top_k, float top_p, void *stream);
 

@@ -357,6 +357,14 @@ int isi_sample_row_f32(const float *logits, int stride, int rows, int n, float t
                        float top_p, const float *u, int64_t *out, float *filtered, void *stream) {
   return sample_row_f32(logits, stride, rows, n, temperature, top_k, top_p, u, out, filtered, S(stream));
 }
+int isi_sample_row_log_prob_f32(const float *logits, int stride, int rows, int n, float temperature, int top_k,
+                                float top_p, const float *u, int64_t *out, float *log_prob, void *stream) {
+  return sample_row_log_prob_f32(logits, stride, rows, n, temperature, top_k, top_p, u, out, log_prob, S(stream));
+}
+int isi_token_log_prob_f32(const float *logits, int stride, int rows, int n, const int64_t *codes, float *out,
+                           void *stream) {
+  return token_log_prob_f32(logits, stride, rows, n, codes, out, S(stream));
+}
 
 size_t isi_prior_decode_scratch_floats(const isi_prior_w *w, int B) { return prior_decode_scratch_floats(w, B); }
 int isi_prior_sample_run(const isi_prior_w *w, const isi_prior_state *state, int p_begin, int p_end,

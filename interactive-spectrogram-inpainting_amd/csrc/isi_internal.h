@@ -109,13 +109,19 @@ int rel_attention_decode_pos_f32(const isi_attn_args *g, int q_pos, const int *p
                                  hipStream_t stream);
 size_t rel_attention_decode_workspace_floats(int B, int H, int head_dim);
 // optional tail of the sampling kernel (the decoding loop): codes[row, p - i_off] = token; x_seq[p + 1][row, 0:eff] = table[token]
-struct SampleCommit {
+// (SampleCommitCore is what the draw kernel's instantiations without a log-probability receive: its 64 bytes are the kernel
+// argument they always had)
+struct SampleCommitCore {
   const float *table; int eff;
   int64_t *codes; int codes_stride;
   int p_value, i_off, S_t;
   float *x_seq; int x_stride;
   int *advance;      // ONE row only (a single workgroup: no other reader of the counter in the launch): *advance = position + 1
                      // behind the commit -- the decode loop's set_pos launch (4.3 us of a 280 us token) folded in
+};
+struct SampleCommit : SampleCommitCore {
+  float *log_probs;  // [rows, codes_stride] or nullptr: beside every committed code, the MODEL's log-probability of it --
+                     // log softmax of the row's raw logits (temperature 1, nothing filtered) at the token (isi_prior_state.token_log_probs)
 };
 // ragged batches (isi_prior_sample_run_rows): row r of the launch stands at position row_pos[t * rows + r] of step
 // t = *pos (replayable) or t = 0 (row_pos, commit already offset to the step); it draws with u[(position - pos_off) * rows + r]
@@ -136,6 +142,11 @@ int sample_row_pos_f32(const float *logits, int stride, int rows, int n, float t
                        hipStream_t stream);
 int sample_row_f32(const float *logits, int stride, int rows, int n, float temperature, int top_k, float top_p,
                    const float *u, int64_t *out, float *filtered, hipStream_t stream);
+// the draw, and log_prob[row] = the model's log-probability of the drawn token (the decode loop's kernel and arithmetic)
+int sample_row_log_prob_f32(const float *logits, int stride, int rows, int n, float temperature, int top_k, float top_p,
+                            const float *u, int64_t *out, float *log_prob, hipStream_t stream);
+// out[r] = log softmax(logits[r, 0:n])[codes[r]]; NaN for a code outside [0, n)
+int token_log_prob_f32(const float *logits, int stride, int rows, int n, const int64_t *codes, float *out, hipStream_t stream);
 
 int rel_attention_decode_splits(int Sk, int pairs);
 int attention_tail_rows(int S, int mask_mode, bool dense_mask);   // rel_attention_f32.hip

@@ -1428,7 +1428,9 @@ static int sample_run_impl(const isi_prior_w *w, const isi_prior_state *s, const
       if ((rc = launch_rows(a))) return rc;
       // (a replayed position of ONE sequence: the commit also advances the position counter)
       const bool fold_advance = !rag && p < 0 && B == 1;
-      const SampleCommit cm{w->embed_table, w->eff_dim, s->codes, s->S, p, i_off, s->S_t, s->x_seq, d, fold_advance ? pos : nullptr};
+      // (state->token_log_probs: the draw's instantiation that also stores the committed token's model log-probability)
+      const SampleCommit cm{{w->embed_table, w->eff_dim, s->codes, s->S, p, i_off, s->S_t, s->x_seq, d, fold_advance ? pos : nullptr},
+                            s->token_log_probs};
       SampleRows sr{row_pos, rag ? rows->commit + (p < 0 ? 0 : (size_t)p * B) : nullptr, rag ? rows->temperature : nullptr,
                     rag ? rows->top_k : nullptr, rag ? rows->top_p : nullptr, s->S};
       if ((rc = sample_row_commit_f32(logits, w->n_class, B, w->n_class, temperature, top_k, top_p,

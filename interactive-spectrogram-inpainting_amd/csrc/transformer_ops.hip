@@ -3,6 +3,7 @@
 // They implement the non-attention parts of the layers specified in
 // oracle/prior_oracle.py (the reference reaches them through the absent
 // VQCPCB package, priors/transformer.py:370-417).
+#include <type_traits>
 #include "isi_common.h"
 #include "isi_internal.h"
 
@@ -837,14 +838,46 @@ __device__ __forceinline__ float block_inclusive_scan(float v, float *wave_tot, 
   return pre + v;
 }
 
-template <bool RAG = false>
+// log softmax(row[0:n])[tok] by the whole workgroup, for the MODEL's distribution: raw logits, temperature 1, nothing filtered.
+// Each thread walks the row with stride blockDim.x (one element per thread for n <= blockDim.x), the partial maxima / sums
+// are reduced inside the wave (`__shfl_xor`: every lane ends with the same bits) and the wave totals are exchanged once and
+// combined in fixed order by every thread -- two block barriers per reduction, as block_inclusive_scan.  The value is a
+// function of (row, n, tok, blockDim.x) alone: the draw kernel and token_log_prob_kernel agree bit for bit on equal logits
+// and an equal workgroup size.  tok in [0, n) (the caller's check); wave_tot: 16 floats, free on entry and on return.
+__device__ __forceinline__ float block_token_log_prob(const float *__restrict__ row, int n, int tok, float *wave_tot) {
+  const int tid = threadIdx.x, np = blockDim.x, nw = (np + 63) >> 6;
+  float m = -INFINITY;
+  for (int i = tid; i < n; i += np) m = fmaxf(m, row[i]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  if ((tid & 63) == 0) wave_tot[tid >> 6] = m;
+  __syncthreads();
+  m = wave_tot[0];
+  for (int w = 1; w < nw; ++w) m = fmaxf(m, wave_tot[w]);
+  __syncthreads();
+  float sum = 0.f;
+  for (int i = tid; i < n; i += np) sum += expf(row[i] - m);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+  if ((tid & 63) == 0) wave_tot[tid >> 6] = sum;
+  __syncthreads();
+  float tot = 0.f;
+  for (int w = 0; w < nw; ++w) tot += wave_tot[w];     // fixed order: the same sum on every thread
+  __syncthreads();
+  return (row[tok] - m) - logf(tot);
+}
+
+// LP: the commit also stores the model's log-probability of the token (SampleCommit.log_probs); the instantiations
+// without it take the commit arguments they always took (SampleCommitCore) and are instruction for instruction what they were
+template <bool RAG = false, bool LP = false>
 __global__ __launch_bounds__(1024) void sample_row_f32_kernel(const float *__restrict__ logits, int stride,
                                                               int n, float inv_temperature, int top_k,
                                                               float top_p, const float *__restrict__ u,
                                                               int64_t *__restrict__ out,
                                                               float *__restrict__ filtered,
                                                               const int *__restrict__ pos, int pos_off,
-                                                              const SampleCommit cm, const SampleRows rg) {
+                                                              const std::conditional_t<LP, SampleCommit, SampleCommitCore> cm,
+                                                              const SampleRows rg) {
   float ur = 0.f;          // this row's uniform
   int rp = 0;              // RAG: the row's position
   bool commit = true;
@@ -946,6 +979,10 @@ __global__ __launch_bounds__(1024) void sample_row_f32_kernel(const float *__res
     const int p = RAG ? rp : pos ? *pos : cm.p_value;
     const int tok = sh_i;
     if (tid == 0) cm.codes[(size_t)row * cm.codes_stride + (p - cm.i_off)] = tok;
+    if constexpr (LP) {                // (cm.table, commit and p are uniform over the workgroup: every thread takes the barriers)
+      const float lp = block_token_log_prob(logits + (size_t)row * stride, n, tok, wave_tot);
+      if (tid == 0) cm.log_probs[(size_t)row * cm.codes_stride + (p - cm.i_off)] = lp;
+    }
     if (p + 1 < cm.S_t) {
       float *x_next = cm.x_seq + ((size_t)(p + 1) * gridDim.x + row) * cm.x_stride;
       for (int e = tid; e < cm.eff; e += np) x_next[e] = cm.table[(size_t)tok * cm.eff + e];
@@ -978,19 +1015,71 @@ int sample_row_commit_f32(const float *logits, int stride, int rows, int n, floa
   if (!logits || !u || !out || rows <= 0 || n <= 0 || temperature <= 0.f) return invalid("sample_row: bad argument");
   if (n > 1024) return unsupported("sample_row: at most 1024 classes");
   if (cm.advance && (rows != 1 || !cm.table)) return invalid("sample_row: the position counter is advanced by a one-row commit only");
+  if (cm.log_probs && !cm.table) return invalid("sample_row: log-probabilities are stored by a commit only");
+  const bool lp = cm.log_probs != nullptr;
+  const SampleCommitCore &core = cm;
   int np = 64;
   while (np < n) np <<= 1;
   if (ragged) {
     if (!ragged->row_pos || !ragged->commit || !cm.table || cm.advance) return invalid("sample_row: bad ragged commit");
-    hipLaunchKernelGGL(sample_row_f32_kernel<true>, dim3(rows), dim3(np), 0, stream, logits, stride, n, 1.0f / temperature,
-                       top_k, top_p, u, out, filtered, pos, pos_off, cm, *ragged);
+    if (lp)
+      hipLaunchKernelGGL((sample_row_f32_kernel<true, true>), dim3(rows), dim3(np), 0, stream, logits, stride, n,
+                         1.0f / temperature, top_k, top_p, u, out, filtered, pos, pos_off, cm, *ragged);
+    else
+      hipLaunchKernelGGL((sample_row_f32_kernel<true, false>), dim3(rows), dim3(np), 0, stream, logits, stride, n,
+                         1.0f / temperature, top_k, top_p, u, out, filtered, pos, pos_off, core, *ragged);
     return check_launch("sample_row_f32 (ragged)");
   }
   SampleRows none_rows;
   memset(&none_rows, 0, sizeof none_rows);
-  hipLaunchKernelGGL(sample_row_f32_kernel<false>, dim3(rows), dim3(np), 0, stream, logits, stride, n, 1.0f / temperature,
-                     top_k, top_p, u, out, filtered, pos, pos_off, cm, none_rows);
+  if (lp)
+    hipLaunchKernelGGL((sample_row_f32_kernel<false, true>), dim3(rows), dim3(np), 0, stream, logits, stride, n,
+                       1.0f / temperature, top_k, top_p, u, out, filtered, pos, pos_off, cm, none_rows);
+  else
+    hipLaunchKernelGGL((sample_row_f32_kernel<false, false>), dim3(rows), dim3(np), 0, stream, logits, stride, n,
+                       1.0f / temperature, top_k, top_p, u, out, filtered, pos, pos_off, core, none_rows);
   return check_launch("sample_row_f32");
+}
+
+// The draw with the drawn token's log-probability: the decode loop's commit into a [rows, 1] code array at token 0 -- no
+// embedding row (eff = 0), no next input row (S_t = 0); `table` only has to be non-null.
+int sample_row_log_prob_f32(const float *logits, int stride, int rows, int n, float temperature, int top_k, float top_p,
+                            const float *u, int64_t *out, float *log_prob, hipStream_t stream) {
+  if (!logits || !u || !out || !log_prob) return invalid("sample_row_log_prob: null pointer");
+  if (stride < n) return invalid("sample_row_log_prob: stride < n");
+  SampleCommit cm;
+  memset(&cm, 0, sizeof cm);
+  cm.table = logits;
+  cm.codes = out;
+  cm.codes_stride = 1;
+  cm.log_probs = log_prob;
+  return sample_row_commit_f32(logits, stride, rows, n, temperature, top_k, top_p, u, out, nullptr, nullptr, 0, cm, stream);
+}
+
+// ------------------------------------------------------------------ log-probabilities of given codes
+// out[r] = log softmax(logits[r, 0:n])[codes[r]]: one workgroup per row, the draw kernel's block_token_log_prob -- for
+// n <= 1024 with the draw's workgroup size (the two agree bit for bit on equal logits), beyond that 1024 threads walking the
+// row.  A code outside [0, n) gives NaN and reads nothing.
+__global__ __launch_bounds__(1024) void token_log_prob_kernel(const float *__restrict__ logits, int stride, int n,
+                                                              const int64_t *__restrict__ codes, float *__restrict__ out) {
+  __shared__ float wave_tot[16];
+  const int row = blockIdx.x;
+  const int64_t code = codes[row];
+  if (code < 0 || code >= n) {         // (uniform over the workgroup: no thread reaches a barrier)
+    if (threadIdx.x == 0) out[row] = __builtin_nanf("");
+    return;
+  }
+  const float lp = block_token_log_prob(logits + (size_t)row * stride, n, (int)code, wave_tot);
+  if (threadIdx.x == 0) out[row] = lp;
+}
+
+int token_log_prob_f32(const float *logits, int stride, int rows, int n, const int64_t *codes, float *out, hipStream_t stream) {
+  if (!logits || !codes || !out) return invalid("token_log_prob: null pointer");
+  if (rows <= 0 || n <= 0 || stride < n) return invalid("token_log_prob: rows, n must be positive and stride >= n");
+  int np = 64;
+  while (np < n && np < 1024) np <<= 1;
+  hipLaunchKernelGGL(token_log_prob_kernel, dim3(rows), dim3(np), 0, stream, logits, stride, n, codes, out);
+  return check_launch("token_log_prob_f32");
 }
 
 }  // namespace isi

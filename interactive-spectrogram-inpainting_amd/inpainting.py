@@ -59,18 +59,27 @@ def timerange_change(transformer_top, transformer_bottom, top_code: torch.Tensor
                      class_conditioning_bottom: Mapping[str, torch.Tensor], device,
                      uniform_sampling: bool = False, generator: Optional[torch.Generator] = None,
                      kv_cache_dtype: Optional[torch.dtype] = None, num_variations: Optional[int] = None,
-                     **sampling_kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
+                     return_scores: bool = False, sort_by_likelihood: bool = False,
+                     **sampling_kwargs) -> Tuple[torch.Tensor, ...]:
     """top_code [1,F_t,T], bottom_code [1,F_b,T_b] (T may exceed the models' duration), mask bool
     [1,F,W] in the resolution of `layer` over the model window.  Returns the updated (top, bottom).
     kv_cache_dtype: `sample_model`'s key/value cache format (None: the switch ISI_DECODE_KV).
     num_variations = N: N alternatives for the request, returned as (top [N,F_t,T], bottom [N,F_b,T_b]).  The prior of
     `layer` samples N variations over one shared source (`sample_model(num_variations=N)`); after a top-layer change the
-    bottom prior has N different conditions and runs as an ordinary batch of N."""
+    bottom prior has N different conditions and runs as an ordinary batch of N.
+    return_scores: the result is (top, bottom, log_likelihood) -- log_likelihood float32 [N] ([1] without num_variations):
+    the sum of the sampled tokens' model log-probabilities (`sample_model(return_log_probs=True)`) over the stages that ran,
+    top then bottom.  sort_by_likelihood (needs return_scores): the variations in descending order of that score, ties in
+    their original order.  Uniform sampling draws from no model distribution: it has no score (ValueError)."""
+    if sort_by_likelihood and not return_scores:
+        raise ValueError("sort_by_likelihood orders the variations by their scores: it needs return_scores=True")
+    if return_scores and uniform_sampling:
+        raise ValueError("return_scores: uniform_sampling draws from no model distribution, there is no likelihood to report")
     if num_variations is not None:
         return _timerange_change_variations(transformer_top, transformer_bottom, top_code, bottom_code, mask, layer,
                                             start_index_top, temperature, class_conditioning_top,
                                             class_conditioning_bottom, device, uniform_sampling, generator, kv_cache_dtype,
-                                            int(num_variations), sampling_kwargs)
+                                            int(num_variations), sampling_kwargs, return_scores, sort_by_likelihood)
     (s_top, e_top), (s_bot, e_bot), ratio_t = _windows(top_code, bottom_code, transformer_top, transformer_bottom,
                                                         start_index_top)
     top_frame = top_code[..., s_top:e_top]
@@ -80,14 +89,19 @@ def timerange_change(transformer_top, transformer_bottom, top_code: torch.Tensor
     ti_bottom = make_time_indexes(s_bot, bottom_code.shape[-1], transformer_bottom.shape[-1])
     common = dict(device=device, batch_size=1, temperature=temperature, generator=generator,
                   kv_cache_dtype=kv_cache_dtype, **sampling_kwargs)
+    scores = []                        # per stage: [1] float64 sums of the sampled tokens' log-probabilities
 
     def resample(model, condition, initial, m, cls, ti_src, ti_tgt):
         if uniform_sampling:
             rnd = torch.randint(0, model.n_class_target, initial.shape, generator=generator).to(initial.device)
             return torch.where(m, rnd, initial)
-        return sample_model(model=model, condition=condition, codemap_size=model.shape, class_conditioning=cls,
-                            initial_code=initial, mask=m, time_indexes_source=ti_src, time_indexes_target=ti_tgt,
-                            **common)
+        out = sample_model(model=model, condition=condition, codemap_size=model.shape, class_conditioning=cls,
+                           initial_code=initial, mask=m, time_indexes_source=ti_src, time_indexes_target=ti_tgt,
+                           return_log_probs=return_scores, **common)
+        if return_scores:
+            scores.append(_stage_score(out[1]))
+            return out[0]
+        return out
 
     top_code, bottom_code = top_code.clone(), bottom_code.clone()
     if layer == 'bottom':
@@ -103,12 +117,33 @@ def timerange_change(transformer_top, transformer_bottom, top_code: torch.Tensor
                                                  class_conditioning_bottom, ti_top, ti_bottom)
     else:
         raise ValueError(f"unknown layer {layer}")
+    if return_scores:
+        return _ranked(top_code, bottom_code, scores, sort_by_likelihood)
     return top_code, bottom_code
+
+
+def _stage_score(log_probs: torch.Tensor) -> torch.Tensor:
+    """[B, F, T] token log-probabilities of one stage (0.0 where nothing was sampled) -> [B] sums, in float64."""
+    return log_probs.double().sum(dim=(1, 2))
+
+
+def _ranked(top, bottom, scores, sort_by_likelihood: bool):
+    """(top, bottom, log_likelihood [N] float32): the stages' sums added in the order they ran; sorted on request by
+    descending score (a stable sort: ties keep their original order)."""
+    total = scores[0]
+    for s in scores[1:]:
+        total = total + s
+    total = total.float()
+    if sort_by_likelihood:
+        order = torch.argsort(total, descending=True, stable=True)
+        top, bottom, total = top[order.to(top.device)], bottom[order.to(bottom.device)], total[order]
+    return top, bottom, total
 
 
 def _timerange_change_variations(transformer_top, transformer_bottom, top_code, bottom_code, mask, layer, start_index_top,
                                  temperature, class_conditioning_top, class_conditioning_bottom, device, uniform_sampling,
-                                 generator, kv_cache_dtype, N, sampling_kwargs):
+                                 generator, kv_cache_dtype, N, sampling_kwargs, return_scores=False,
+                                 sort_by_likelihood=False):
     if N < 1:
         raise ValueError(f"num_variations must be at least 1, not {N}")
     if layer not in ('top', 'bottom'):
@@ -121,21 +156,30 @@ def _timerange_change_variations(transformer_top, transformer_bottom, top_code, 
     ti_top = make_time_indexes(s_top, top_code.shape[-1], transformer_top.shape[-1])
     ti_bottom = make_time_indexes(s_bot, bottom_code.shape[-1], transformer_bottom.shape[-1])
     common = dict(device=device, temperature=temperature, generator=generator, kv_cache_dtype=kv_cache_dtype,
-                  **sampling_kwargs)
+                  return_log_probs=return_scores, **sampling_kwargs)
+    scores = []
+
+    def scored(out):                   # a sample_model result: the codes; the stage's score is kept aside
+        if return_scores:
+            scores.append(_stage_score(out[1]))
+            return out[0]
+        return out
 
     def variations(model, condition, initial, m, cls, ti_src, ti_tgt):      # N rows over one request
         if uniform_sampling:
             rnd = torch.randint(0, model.n_class_target, (N,) + tuple(initial.shape[1:]), generator=generator).to(initial.device)
             return torch.where(m, rnd, initial)
-        return sample_model(model=model, batch_size=1, num_variations=N, condition=condition, codemap_size=model.shape,
-                            class_conditioning=cls, initial_code=initial, mask=m, time_indexes_source=ti_src,
-                            time_indexes_target=ti_tgt, **common)
+        return scored(sample_model(model=model, batch_size=1, num_variations=N, condition=condition, codemap_size=model.shape,
+                                   class_conditioning=cls, initial_code=initial, mask=m, time_indexes_source=ti_src,
+                                   time_indexes_target=ti_tgt, **common))
 
     top_out = top_code.repeat(N, 1, 1)
     bottom_out = bottom_code.repeat(N, 1, 1)
     if layer == 'bottom':
         bottom_out[..., s_bot:e_bot] = variations(transformer_bottom, top_frame, bottom_frame, mask,
                                                   class_conditioning_bottom, ti_top, ti_bottom)
+        if return_scores:
+            return _ranked(top_out, bottom_out, scores, sort_by_likelihood)
         return top_out, bottom_out
     condition = top_frame if transformer_top.self_conditional_model else None
     new_top = variations(transformer_top, condition, top_frame, mask, class_conditioning_top, ti_top, ti_top)
@@ -148,10 +192,12 @@ def _timerange_change_variations(transformer_top, transformer_bottom, top_code, 
         bottom_out[..., s_bot:e_bot] = torch.where(mask_bottom, rnd, initial)
     else:
         # N different conditions: an ordinary batch of N (one class value expands over the rows)
-        bottom_out[..., s_bot:e_bot] = sample_model(
+        bottom_out[..., s_bot:e_bot] = scored(sample_model(
             model=transformer_bottom, batch_size=N, condition=new_top, codemap_size=transformer_bottom.shape,
             class_conditioning=class_conditioning_bottom, initial_code=initial, mask=mask_bottom,
-            time_indexes_source=ti_top, time_indexes_target=ti_bottom, **common)
+            time_indexes_source=ti_top, time_indexes_target=ti_bottom, **common))
+    if return_scores:
+        return _ranked(top_out, bottom_out, scores, sort_by_likelihood)
     return top_out, bottom_out
 
 
@@ -161,19 +207,24 @@ def _cat_classes(dicts) -> Mapping[str, torch.Tensor]:
 
 @torch.no_grad()
 def timerange_change_batch(transformer_top, transformer_bottom, requests: Sequence[Mapping], device,
-                           kv_cache_dtype: Optional[torch.dtype] = None) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+                           kv_cache_dtype: Optional[torch.dtype] = None,
+                           return_scores: bool = False) -> List[Tuple[torch.Tensor, ...]]:
     """Independent `timerange_change` requests in at most two ragged `sample_model` calls: every `layer='top'` request
     through the top prior together, then every request through the bottom prior together (a top request with the mask
     up-sampled over its new top map).  A request is a mapping with the arguments of `timerange_change` -- top_code,
     bottom_code, mask, layer, start_index_top, temperature, class_conditioning_top, class_conditioning_bottom and
     optionally top_k_sampling_k, top_p_sampling_p, uniform_sampling -- and its own `generator`, from which its uniforms
     are drawn in the order `timerange_change` draws them (top stage, then bottom): result r equals `timerange_change` of
-    request r alone with an equally seeded generator.  Returns one (top, bottom) pair per request."""
+    request r alone with an equally seeded generator.  Returns one (top, bottom) pair per request; with return_scores one
+    (top, bottom, log_likelihood [1]) triple, `timerange_change(return_scores=True)`'s (a request with uniform_sampling
+    has no score: ValueError)."""
     ratio_f = transformer_bottom.shape[0] // transformer_top.shape[0]
     jobs = []
     for r in requests:
         if r['layer'] not in ('top', 'bottom'):
             raise ValueError(f"unknown layer {r['layer']}")
+        if return_scores and r.get('uniform_sampling', False):
+            raise ValueError("return_scores: uniform_sampling draws from no model distribution, there is no likelihood to report")
         (s_top, e_top), (s_bot, e_bot), ratio_t = _windows(r['top_code'], r['bottom_code'], transformer_top,
                                                             transformer_bottom, r['start_index_top'])
         jobs.append(dict(req=r, top=r['top_code'].clone(), bottom=r['bottom_code'].clone(), s_top=s_top, e_top=e_top,
@@ -192,7 +243,14 @@ def timerange_change_batch(transformer_top, transformer_bottom, requests: Sequen
             time_indexes_target=torch.tensor(ti_tgt),
             top_k_sampling_k=[int(q.get('top_k_sampling_k', 0)) for q in req],
             top_p_sampling_p=[float(q.get('top_p_sampling_p', 0.0)) for q in req],
-            uniforms=torch.cat(uniforms, 1), kv_cache_dtype=kv_cache_dtype)
+            uniforms=torch.cat(uniforms, 1), kv_cache_dtype=kv_cache_dtype, return_log_probs=return_scores)
+
+    def scored(out, batch):            # a sample_model result: the codes; every row's stage score goes to its job
+        if not return_scores:
+            return out
+        for k, j in enumerate(batch):
+            j.setdefault('scores', []).append(_stage_score(out[1][k:k + 1]))
+        return out[0]
 
     def draw(model, j, frame):        # timerange_change's draws from the request's generator, in its order
         if j['req'].get('uniform_sampling', False):
@@ -211,9 +269,9 @@ def timerange_change_batch(transformer_top, transformer_bottom, requests: Sequen
     sampled = [j for j in tops if 'u_top' in j]
     if sampled:
         frames = [j['top'][..., j['s_top']:j['e_top']] for j in sampled]
-        new_top = run(transformer_top, sampled, frames if transformer_top.self_conditional_model else None, frames,
-                      [j['mask'] for j in sampled], 'class_conditioning_top', [j['ti_top'] for j in sampled],
-                      [j['ti_top'] for j in sampled], [j['u_top'] for j in sampled])
+        new_top = scored(run(transformer_top, sampled, frames if transformer_top.self_conditional_model else None, frames,
+                             [j['mask'] for j in sampled], 'class_conditioning_top', [j['ti_top'] for j in sampled],
+                             [j['ti_top'] for j in sampled], [j['u_top'] for j in sampled]), sampled)
         for k, j in enumerate(sampled):
             j['top'][..., j['s_top']:j['e_top']] = new_top[k:k + 1].to(j['top'].device)
     # stage 2: the bottom prior, every request in one ragged call
@@ -228,12 +286,14 @@ def timerange_change_batch(transformer_top, transformer_bottom, requests: Sequen
             j['u_bot'] = d
     sampled = [j for j in jobs if 'u_bot' in j]
     if sampled:
-        new_bottom = run(transformer_bottom, sampled, [j['top'][..., j['s_top']:j['e_top']] for j in sampled],
-                         [j['bottom'][..., j['s_bot']:j['e_bot']] for j in sampled], [j['mask'] for j in sampled],
-                         'class_conditioning_bottom', [j['ti_top'] for j in sampled], [j['ti_bottom'] for j in sampled],
-                         [j['u_bot'] for j in sampled])
+        new_bottom = scored(run(transformer_bottom, sampled, [j['top'][..., j['s_top']:j['e_top']] for j in sampled],
+                                [j['bottom'][..., j['s_bot']:j['e_bot']] for j in sampled], [j['mask'] for j in sampled],
+                                'class_conditioning_bottom', [j['ti_top'] for j in sampled],
+                                [j['ti_bottom'] for j in sampled], [j['u_bot'] for j in sampled]), sampled)
         for k, j in enumerate(sampled):
             j['bottom'][..., j['s_bot']:j['e_bot']] = new_bottom[k:k + 1].to(j['bottom'].device)
+    if return_scores:
+        return [_ranked(j['top'], j['bottom'], j['scores'], False) for j in jobs]
     return [(j['top'], j['bottom']) for j in jobs]
 
 

@@ -118,12 +118,23 @@ class isi_prior_w(C.Structure):
                 ("logits_b", C.c_void_p), ("embed_table", C.c_void_p), ("eff_dim", C.c_int)]
 
 
+# fields appended to the C struct behind kv_format (include/isi_hip.h), in order
+_PRIOR_STATE_APPENDED = [("token_log_probs", C.c_void_p)]
+
+
 class isi_prior_state(C.Structure):
     _fields_ = [("x_seq", C.c_void_p), ("kv_cache", C.c_void_p), ("memory_kv", C.c_void_p), ("codes", C.c_void_p),
                 ("mask", C.c_void_p), ("uniforms", C.c_void_p), ("scratch", C.c_void_p),
                 ("scratch_floats", C.c_size_t), ("S_t", C.c_int), ("S_src", C.c_int), ("S", C.c_int),
                 ("B", C.c_int), ("start_len", C.c_int), ("memory_shared", C.c_int), ("cross_out", C.c_void_p),
-                ("kv_format", C.c_int)]
+                ("kv_format", C.c_int)] + _PRIOR_STATE_APPENDED
+
+
+# ctypes has laid the struct out by now (the descriptors, offsets and the size above are final and include the appended
+# fields: `isi_prior_state.token_log_probs.offset`, `sizeof`); the list object itself is only read again for positional
+# construction.  It keeps ending at kv_format, the form callers written against the earlier layout index it in -- the fields
+# the C struct gained behind it are listed in _PRIOR_STATE_APPENDED.
+del isi_prior_state._fields_[-len(_PRIOR_STATE_APPENDED):]
 
 
 ISI_KV_F32, ISI_KV_BF16 = 0, 1
@@ -227,6 +238,9 @@ SIGNATURES = {
                                       C.c_int, _P]),
     "isi_sample_row_f32": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, _P, _P, _P,
                                      _P]),
+    "isi_sample_row_log_prob_f32": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, _P, _P, _P,
+                                              _P]),
+    "isi_token_log_prob_f32": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "isi_prior_decode_scratch_floats": (C.c_size_t, [C.POINTER(isi_prior_w), C.c_int]),
     "isi_prior_sample_run": (C.c_int, [C.POINTER(isi_prior_w), C.POINTER(isi_prior_state), C.c_int, C.c_int,
                                        C.c_float, C.c_int, C.c_float, _P]),

@@ -135,10 +135,12 @@ class NativeSampler:
 
     def __init__(self, model, memory: torch.Tensor, x_seq: torch.Tensor, codes: torch.Tensor,
                  mask_seq, uniforms: torch.Tensor, kv_cache_dtype: torch.dtype = torch.float32,
-                 shared_memory: bool = False):
+                 shared_memory: bool = False, log_probs: bool = False):
         """shared_memory: the B rows of x_seq are variations of ONE request -- memory is [S_src, 1, d], its projected keys /
         values (or the single-source table) are formed once at batch 1 and every row reads them
-        (`isi_prior_state.memory_shared`)."""
+        (`isi_prior_state.memory_shared`).
+        log_probs: the loop also stores the model's log-probability of every token it commits
+        (`isi_prior_state.token_log_probs`) into `self.log_probs` [B, S] float32, zero where nothing was sampled."""
         import ctypes as C
         kv_format = kv_cache_format(kv_cache_dtype)        # before anything is allocated
         self.kv_cache_dtype = kv_cache_dtype
@@ -226,6 +228,10 @@ class NativeSampler:
         st.kv_format = kv_format
         if self.shared_memory:
             st.memory_shared = 1
+        self.log_probs = None
+        if log_probs:
+            self.log_probs = torch.zeros(B, codes.shape[1], dtype=torch.float32, device=dev)
+            st.token_log_probs = self.log_probs.data_ptr()
         self.state = st
 
     @torch.no_grad()

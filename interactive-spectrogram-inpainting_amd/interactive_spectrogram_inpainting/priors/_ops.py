@@ -472,3 +472,40 @@ def sample_rows(logits: torch.Tensor, temperature: float, top_k: int, top_p: flo
                                        filt.data_ptr() if filt is not None else None, _s(logits))
     _hip.check(rc, "isi_sample_row_f32")
     return (out, filt) if return_filtered else out
+
+
+def sample_rows_log_probs(logits: torch.Tensor, temperature: float, top_k: int, top_p: float, u: torch.Tensor):
+    """logits [rows, n] -> (int64 [rows], float32 [rows]): the draw of `sample_rows` and the model's log-probability of
+    each drawn token -- log softmax of the raw logits, whatever the temperature and the filters (the decode loop's kernel)."""
+    _hip.require_gpu(logits, "logits")
+    rows, n = logits.shape
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    out = torch.empty(rows, dtype=torch.int64, device=logits.device)
+    lp = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    u = u.to(device=logits.device, dtype=torch.float32).contiguous()
+    rc = _hip.lib().isi_sample_row_log_prob_f32(logits.data_ptr(), logits.stride(0), rows, n, float(temperature),
+                                                int(top_k), float(top_p), u.data_ptr(), out.data_ptr(), lp.data_ptr(),
+                                                _s(logits))
+    _hip.check(rc, "isi_sample_row_log_prob_f32")
+    return out, lp
+
+
+def token_log_probs(logits: torch.Tensor, codes: torch.Tensor) -> torch.Tensor:
+    """logits [..., n] fp32, codes [...] int64 -> float32 [...]: log softmax(logits)[code] per row (`isi_token_log_prob_f32`;
+    NaN where a code lies outside [0, n)).  Rows may be strided (a view of a wider buffer), the class dimension not."""
+    _hip.require_gpu(logits, "logits")
+    _hip.require_gpu(codes, "codes")
+    if logits.dtype != torch.float32 or codes.dtype != torch.int64:
+        raise _hip.HipLibraryError(f"token_log_probs: logits {logits.dtype} / codes {codes.dtype}; expected float32 / int64")
+    n = logits.shape[-1]
+    if tuple(codes.shape) != tuple(logits.shape[:-1]):
+        raise ValueError(f"token_log_probs: codes {tuple(codes.shape)} for logits {tuple(logits.shape)}")
+    rows2 = logits if logits.dim() == 2 and logits.stride(1) == 1 else logits.reshape(-1, n).contiguous()
+    codes1 = codes.reshape(-1).contiguous()
+    out = torch.empty(codes1.shape[0], dtype=torch.float32, device=logits.device)
+    if codes1.shape[0]:
+        rc = _hip.lib().isi_token_log_prob_f32(rows2.data_ptr(), rows2.stride(0), rows2.shape[0], n, codes1.data_ptr(),
+                                               out.data_ptr(), _s(logits))
+        _hip.check(rc, "isi_token_log_prob_f32")
+    return out.reshape(codes.shape)

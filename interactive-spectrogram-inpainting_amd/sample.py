@@ -104,8 +104,12 @@ def sample_model(model: VQNSynthTransformer, device: Union[torch.device, str], b
                  uniforms: Optional[torch.Tensor] = None,
                  gumbel_noise: Optional[torch.Tensor] = None,
                  kv_cache_dtype: Optional[torch.dtype] = None,
-                 num_variations: Optional[int] = None) -> torch.Tensor:
-    """num_variations: N alternatives for ONE request -- `batch_size` is 1 and condition, initial code, mask and class
+                 num_variations: Optional[int] = None, return_log_probs: bool = False):
+    """return_log_probs: the result is (codes [B, F, T], log_probs [B, F, T] float32) -- beside every sampled code the
+    MODEL's log-probability of it (log softmax of the raw logits: it does not depend on temperature, top-k or top-p, and it
+    is what `score_codemap` gives for the result), exactly 0.0 where nothing was sampled.  The draw kernel stores it as it
+    commits the token (`isi_prior_state.token_log_probs`); the codes are those of the call without the option.
+    num_variations: N alternatives for ONE request -- `batch_size` is 1 and condition, initial code, mask and class
     conditioning are that request's; the result is [N, F, T], row n drawn with `uniforms[:, n]` ([S, N], from `generator`
     when not given).  The source sequence, the encoder and the prefix pass run once at batch 1 and every row reads one copy
     of the projected memory (`_sample_variations`).  The codes are those of `batch_size=N` with the inputs repeated N times.
@@ -117,11 +121,14 @@ def sample_model(model: VQNSynthTransformer, device: Union[torch.device, str], b
     shared parameters, samples exactly as a single request does."""
     if constraint is not None:
         raise NotImplementedError
+    if return_log_probs and use_predictive_sampling:
+        raise ValueError("return_log_probs reads the KV-cached loop's draw kernel: predictive sampling draws by Gumbel-max "
+                         "over full passes and reports no log-probabilities")
     if num_variations is not None:
         return _sample_variations(model, device, batch_size, codemap_size, temperature, condition, class_conditioning,
                                   initial_code, mask, time_indexes_source, time_indexes_target, top_k_sampling_k,
                                   top_p_sampling_p, progressbar_decorator, use_predictive_sampling, generator, uniforms,
-                                  kv_cache_dtype, num_variations)
+                                  kv_cache_dtype, num_variations, return_log_probs)
     kv_cache_dtype = _kv_cache_dtype(kv_cache_dtype)
     if use_predictive_sampling and kv_cache_dtype is not torch.float32:
         raise ValueError("predictive sampling runs full decoder passes and has no key/value cache: kv_cache_dtype / "
@@ -168,7 +175,10 @@ def sample_model(model: VQNSynthTransformer, device: Union[torch.device, str], b
                 time_indexes_target=time_rows(time_indexes_target, lo, hi),
                 top_k_sampling_k=param_rows(row_params[1], lo, hi), top_p_sampling_p=param_rows(row_params[2], lo, hi),
                 progressbar_decorator=progressbar_decorator, use_predictive_sampling=use_predictive_sampling,
-                uniforms=uniforms[:, lo:hi], gumbel_noise=rows(gumbel_noise, lo, hi), kv_cache_dtype=kv_cache_dtype))
+                uniforms=uniforms[:, lo:hi], gumbel_noise=rows(gumbel_noise, lo, hi), kv_cache_dtype=kv_cache_dtype,
+                return_log_probs=return_log_probs))
+        if return_log_probs:
+            return torch.cat([c for c, _ in parts], 0), torch.cat([lp for _, lp in parts], 0)
         return torch.cat(parts, 0)
     if initial_code is None:
         fill = model.mask_token_index if model.self_conditional_model else 0
@@ -226,8 +236,9 @@ def sample_model(model: VQNSynthTransformer, device: Union[torch.device, str], b
         # before any later position reads them
         pos, commit, p0 = _ragged_plan(np.asarray(mask_rows, dtype=bool), start_len - 1)
         if pos.shape[0] == 0:
-            return model.target_codemaps_helper.to_time_frequency_map(code_seq).long()
-        sampler = NativeSampler(model, memory, x_seq, code_seq, mask_seq, uniforms, kv_cache_dtype=kv_cache_dtype)
+            return _maps(model, code_seq, return_log_probs, None)
+        sampler = NativeSampler(model, memory, x_seq, code_seq, mask_seq, uniforms, kv_cache_dtype=kv_cache_dtype,
+                                log_probs=return_log_probs)
         n_steps = sampler.plan_rows(pos, commit, temp_rows, top_k_rows, top_p_rows)
         sampler.prefill(p0)
         chunk = n_steps if progressbar_decorator is None else 64
@@ -236,17 +247,18 @@ def sample_model(model: VQNSynthTransformer, device: Union[torch.device, str], b
             starts = progressbar_decorator(starts)
         for t0 in starts:
             sampler.run_rows(t0, min(n_steps, t0 + chunk), temperature, top_k_sampling_k, top_p_sampling_p)
-        return model.target_codemaps_helper.to_time_frequency_map(code_seq).long()
+        return _maps(model, code_seq, return_log_probs, sampler.log_probs)
     n_pos = S + start_len - 1
     # Token i is drawn from decoder position i + start_len - 1.  Positions behind the last masked token are
     # never read; positions before the first one only contribute keys / values, which one batched causal
     # pass over that prefix provides (an inpainting request masks a window, not the whole map).
     masked = [i for i, mk in enumerate(mask_seq) if mk]
     if not masked:
-        return model.target_codemaps_helper.to_time_frequency_map(code_seq).long()
+        return _maps(model, code_seq, return_log_probs, None)
     p_first, n_pos = masked[0] + start_len - 1, min(n_pos, masked[-1] + start_len)
     # the whole loop natively: no per-token return to Python, no host sync
-    sampler = NativeSampler(model, memory, x_seq, code_seq, mask_seq, uniforms, kv_cache_dtype=kv_cache_dtype)
+    sampler = NativeSampler(model, memory, x_seq, code_seq, mask_seq, uniforms, kv_cache_dtype=kv_cache_dtype,
+                            log_probs=return_log_probs)
     if p_first < 8:
         p_first = 0                                        # a few rows: not worth a batched pass
     sampler.prefill(p_first)
@@ -256,7 +268,61 @@ def sample_model(model: VQNSynthTransformer, device: Union[torch.device, str], b
         starts = progressbar_decorator(starts)
     for p0 in starts:
         sampler.run(p0, min(n_pos, p0 + chunk), temperature, top_k_sampling_k, top_p_sampling_p)
-    return model.target_codemaps_helper.to_time_frequency_map(code_seq).long()
+    return _maps(model, code_seq, return_log_probs, sampler.log_probs)
+
+
+def _maps(model, code_seq, return_log_probs: bool, log_probs: Optional[torch.Tensor]):
+    """The sampled sequences as codemaps: codes [B, F, T], and with `return_log_probs` the tokens' log-probabilities in the
+    same layout (all zero when nothing was sampled)."""
+    codes = model.target_codemaps_helper.to_time_frequency_map(code_seq).long()
+    if not return_log_probs:
+        return codes
+    if log_probs is None:
+        log_probs = torch.zeros(code_seq.shape, dtype=torch.float32, device=code_seq.device)
+    return codes, model.target_codemaps_helper.to_time_frequency_map(log_probs)
+
+
+@torch.no_grad()
+def score_codemap(model: VQNSynthTransformer, device: Union[torch.device, str], codemap: torch.Tensor,
+                  condition: Optional[torch.Tensor] = None, class_conditioning: Mapping[str, Iterable[int]] = {},
+                  mask: Optional[torch.Tensor] = None, time_indexes_source: Optional[Iterable[int]] = None,
+                  time_indexes_target: Optional[Iterable[int]] = None) -> torch.Tensor:
+    """float32 [B, F, T]: the model's log-probability of every code of `codemap` [B, F, T] given the codes before it (in
+    the target helper's order) and the source -- a sampled map, an edited one, or one encoded from audio.  ONE teacher-forced
+    full pass: the sequences are built by `model.to_sequences` exactly as `sample_model` builds them, the forward kernels
+    give the logits of all B S rows and `isi_token_log_prob_f32` reads the codes' entries of their log softmax.
+    condition: the source codemap (the top codes for a bottom prior); a self-conditional model may leave it out (the
+    codemap itself).  mask: `sample_model`'s inpainting mask -- it hides the source side as it did when sampling, and
+    positions outside it are 0.0.  For a result c of `sample_model(..., initial_code=i, condition=x, mask=m)`,
+    `score_codemap(model, device, c, condition=(i if model.self_conditional_model else x), mask=m)` with the same
+    conditioning reproduces the loop's `return_log_probs`."""
+    device = torch.device(device)
+    model.eval()
+    codemap = codemap.to(device)
+    batch_size = codemap.shape[0]
+    if condition is None:
+        if not model.self_conditional_model:
+            raise ValueError("score_codemap: a model that is not self-conditional needs its condition codemap")
+        condition = codemap
+    if mask is not None:
+        if mask.dim() == 3 and mask.shape[0] not in (1, batch_size):
+            raise ValueError(f"mask for {mask.shape[0]} rows, batch of {batch_size}")
+        mask = mask.to(device)
+    cls = {}
+    for name, value in class_conditioning.items():
+        value = torch.as_tensor(value).long().reshape(-1)
+        cls[name] = (value.expand(batch_size) if value.numel() == 1 else value).reshape(batch_size, 1).to(device)
+    source_seq, target_seq = model.to_sequences(
+        codemap, condition.to(device), class_conditioning=cls, mask=mask,
+        time_indexes_source=time_indexes_source, time_indexes_target=time_indexes_target)
+    logits, _ = model(target_seq, source_seq)                                  # [B, S, n_class]
+    code_seq = model.target_codemaps_helper.to_sequence(codemap).contiguous()
+    log_probs = _ops.token_log_probs(logits.contiguous(), code_seq)            # [B, S]
+    if mask is not None:
+        S = model.target_transformer_sequence_length
+        mask_seq = model.target_codemaps_helper.to_sequence(mask).reshape(-1, S)
+        log_probs = torch.where(mask_seq, log_probs, torch.zeros((), dtype=torch.float32, device=device))
+    return model.target_codemaps_helper.to_time_frequency_map(log_probs)
 
 
 def _one_value(value, name: str):
@@ -271,7 +337,8 @@ def _one_value(value, name: str):
 
 def _sample_variations(model, device, batch_size, codemap_size, temperature, condition, class_conditioning, initial_code,
                        mask, time_indexes_source, time_indexes_target, top_k, top_p, progressbar_decorator,
-                       use_predictive_sampling, generator, uniforms, kv_cache_dtype, num_variations):
+                       use_predictive_sampling, generator, uniforms, kv_cache_dtype, num_variations,
+                       return_log_probs=False):
     """`sample_model(num_variations=N)`: N rows over ONE source.  Everything that does not depend on the draws is formed once at
     batch 1 -- source sequence, encoder memory, its projected keys / values (or the single-source table) and the keys / values
     of the unmasked prefix; the target rows, the codes and the self-attention cache have N rows.  All checks come before any
@@ -326,7 +393,7 @@ def _sample_variations(model, device, batch_size, codemap_size, temperature, con
                 else [True] * S)
     masked = [i for i, mk in enumerate(mask_seq) if mk]
     if not masked:
-        return model.target_codemaps_helper.to_time_frequency_map(code_row.repeat(N, 1).contiguous()).long()
+        return _maps(model, code_row.repeat(N, 1).contiguous(), return_log_probs, None)
     # one encoder pass for all variations (anti-causal for the self-conditional top prior)
     memory, *_ = model.transformer.encoder(source_seq.transpose(0, 1).contiguous(),
                                            mask='anticausal' if model.self_conditional_model else None)
@@ -340,7 +407,7 @@ def _sample_variations(model, device, batch_size, codemap_size, temperature, con
         x_seq = x_row.repeat(1, n, 1).contiguous()
         code_seq = code_row.repeat(n, 1).contiguous()
         sampler = NativeSampler(model, memory, x_seq, code_seq, mask_seq, uniforms[:, lo:lo + n].to(device=device, dtype=torch.float32),
-                                kv_cache_dtype=kv_cache_dtype, shared_memory=True)
+                                kv_cache_dtype=kv_cache_dtype, shared_memory=True, log_probs=return_log_probs)
         sampler.prefill(p_first)
         chunk = n_pos if progressbar_decorator is None else 64
         starts = range(p_first, n_pos, chunk)
@@ -348,7 +415,9 @@ def _sample_variations(model, device, batch_size, codemap_size, temperature, con
             starts = progressbar_decorator(starts)
         for p0 in starts:
             sampler.run(p0, min(n_pos, p0 + chunk), temperature, top_k, top_p)
-        parts.append(model.target_codemaps_helper.to_time_frequency_map(code_seq).long())
+        parts.append(_maps(model, code_seq, return_log_probs, sampler.log_probs))
+    if return_log_probs:
+        return torch.cat([c for c, _ in parts], 0), torch.cat([lp for _, lp in parts], 0)
     return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
 
 

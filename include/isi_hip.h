@@ -596,9 +596,11 @@ int isi_rel_attention_decode_shared_f32(const isi_attn_args *args, int q_pos, fl
 
 /* One categorical draw per row (sample.py:286-295): logits/temperature ->
  * top_k_top_p_filtering (sample.py:36-65) -> softmax -> inverse-CDF draw with the
- * host-supplied uniform u[row] (first index whose cumulative probability exceeds
- * u * total).  filtered [rows, n] (optional) receives the filtered logits
- * (-inf where removed).  n <= 1024. */
+ * host-supplied uniform u[row] in [0, 1) (first class of non-zero probability whose
+ * cumulative probability exceeds u * total; if rounding leaves none, the last such
+ * class): a class removed by a filter or given as -inf is never drawn.  filtered
+ * [rows, n] (optional) receives the filtered logits (-inf where removed).  n <= 1024;
+ * every row has a finite logit. */
 int isi_sample_row_f32(const float *logits, int stride, int rows, int n, float temperature,
                        int top_k, float top_p, const float *u, int64_t *out,
                        float *filtered, void *stream);

@@ -3,6 +3,7 @@
 // They implement the non-attention parts of the layers specified in
 // oracle/prior_oracle.py (the reference reaches them through the absent
 // VQCPCB package, priors/transformer.py:370-417).
+#include <climits>
 #include <type_traits>
 #include "isi_common.h"
 #include "isi_internal.h"
@@ -898,7 +899,7 @@ __global__ __launch_bounds__(1024) void sample_row_f32_kernel(const float *__res
   __shared__ int keep[1024];
   __shared__ float wave_tot[16];
   __shared__ float sh_f[2];
-  __shared__ int sh_i;
+  __shared__ int sh_i, sh_last;
   const int tid = threadIdx.x, np = blockDim.x, row = blockIdx.x;
   const float NEGI = -INFINITY;
   const float lg = tid < n ? logits[(size_t)row * stride + tid] * inv_temperature : NEGI;
@@ -968,16 +969,25 @@ __global__ __launch_bounds__(1024) void sample_row_f32_kernel(const float *__res
   const float pe = kp ? expf(lg - vmax) : 0.f;
   float total;
   const float inc = block_inclusive_scan(pe, wave_tot, &total);
-  if (tid == 0) sh_i = n - 1;
+  if (tid == 0) { sh_i = INT_MAX; sh_last = -1; }
   __syncthreads();
   if constexpr (!RAG) ur = u[row];
-  if (tid < n && inc > ur * total) atomicMin(&sh_i, tid);
+  // Only a class of non-zero probability bids.  The wave scan sums neighbouring lanes' terms in different groupings, so
+  // `inc` is not monotone in fp32: it can rise by an ulp across a lane whose own term is 0 (removed by top-k / top-p,
+  // masked with -inf by the caller, or a padding lane), and such a lane must not win the draw.
+  if (pe > 0.f && inc > ur * total) atomicMin(&sh_i, tid);
   __syncthreads();
-  if (tid == 0) out[row] = sh_i;
+  int tok = sh_i;
+  if (tok == INT_MAX) {                // (uniform) nobody bid: rounding left the last prefix <= u * total -- the last
+    const unsigned long long nzm = __ballot(pe > 0.f);     // class of non-zero probability, never a removed one
+    if ((tid & 63) == 0 && nzm) atomicMax(&sh_last, tid + 63 - __builtin_clzll(nzm));
+    __syncthreads();
+    tok = sh_last < 0 ? n - 1 : sh_last;                   // (< 0: a row without a finite logit, outside the contract)
+  }
+  if (tid == 0) out[row] = tok;
   // the decoding loop's commit, in the same launch: code row, and the token's embedding into the next input row
   if (cm.table && commit) {
     const int p = RAG ? rp : pos ? *pos : cm.p_value;
-    const int tok = sh_i;
     if (tid == 0) cm.codes[(size_t)row * cm.codes_stride + (p - cm.i_off)] = tok;
     if constexpr (LP) {                // (cm.table, commit and p are uniform over the workgroup: every thread takes the barriers)
       const float lp = block_token_log_prob(logits + (size_t)row * stride, n, tok, wave_tot);

@@ -618,6 +618,24 @@ int isi_sample_row_log_prob_f32(const float *logits, int stride, int rows, int n
  * its row and reads nothing out of range.  Null pointers, rows <= 0, n <= 0 or stride < n: ISI_E_INVALID before any launch. */
 int isi_token_log_prob_f32(const float *logits, int stride, int rows, int n, const int64_t *codes, float *out,
                            void *stream);
+/* Statistics of the MODEL's distribution per row (raw logits, temperature 1, nothing filtered, natural log, fp32), one
+ * workgroup per row, one read of the row; any n >= 1 (beyond 1024 classes 1024 threads walk the row), stride >= n:
+ *   log_prob[r]  = log softmax(logits[r, 0:n])[codes[r]] -- isi_token_log_prob_f32's arithmetic and workgroup size: equal to
+ *                  it bit for bit on equal logits;
+ *   entropy[r]   = -sum_i p_i ln p_i in nats; a -inf logit contributes 0;
+ *   rank[r]      = the number of classes with a larger logit than codes[r], plus the number with an equal logit and a lower
+ *                  index (the tie rule of isi_sample_row_f32's sort): 0 is the mode.  An integer, exact;
+ *   top_codes[r, 0:top_n], top_log_probs[r, 0:top_n] = the top_n classes in descending logit order, ties by lower index, and
+ *                  their log-probabilities (each bit-equal to isi_token_log_prob_f32 of that class); 0 <= top_n <= 16, and
+ *                  where n < top_n the tail holds -1 and -inf.
+ * Every output pointer may be NULL: that output is skipped.  codes may be NULL when log_prob and rank are.  A code outside
+ * [0, n) gives NaN for log_prob and -1 for rank, reads nothing out of range and leaves the row's other outputs correct.
+ * The reductions run in a fixed order (wave reductions, one exchange of the wave totals): the results are functions of the
+ * row, n and the workgroup size alone.  Every row has a finite logit; NaN logits are outside the contract.  Null logits,
+ * rows <= 0, n <= 0, stride < n, top_n outside 0 .. 16, or codes == NULL with log_prob or rank given: ISI_E_INVALID before
+ * any launch. */
+int isi_token_stats_f32(const float *logits, int stride, int rows, int n, const int64_t *codes, float *log_prob,
+                        float *entropy, int32_t *rank, int top_n, int64_t *top_codes, float *top_log_probs, void *stream);
 
 /* Native key/value-cached sampling loop of the decoder (replaces the per-token
  * full decoder pass of sample.py:268-305).  Weights are the torch-layout

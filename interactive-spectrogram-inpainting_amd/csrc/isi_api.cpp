@@ -365,6 +365,10 @@ int isi_token_log_prob_f32(const float *logits, int stride, int rows, int n, con
                            void *stream) {
   return token_log_prob_f32(logits, stride, rows, n, codes, out, S(stream));
 }
+int isi_token_stats_f32(const float *logits, int stride, int rows, int n, const int64_t *codes, float *log_prob,
+                        float *entropy, int32_t *rank, int top_n, int64_t *top_codes, float *top_log_probs, void *stream) {
+  return token_stats_f32(logits, stride, rows, n, codes, log_prob, entropy, rank, top_n, top_codes, top_log_probs, S(stream));
+}
 
 size_t isi_prior_decode_scratch_floats(const isi_prior_w *w, int B) { return prior_decode_scratch_floats(w, B); }
 int isi_prior_sample_run(const isi_prior_w *w, const isi_prior_state *state, int p_begin, int p_end,

@@ -147,6 +147,8 @@ int sample_row_log_prob_f32(const float *logits, int stride, int rows, int n, fl
                             const float *u, int64_t *out, float *log_prob, hipStream_t stream);
 // out[r] = log softmax(logits[r, 0:n])[codes[r]]; NaN for a code outside [0, n)
 int token_log_prob_f32(const float *logits, int stride, int rows, int n, const int64_t *codes, float *out, hipStream_t stream);
+int token_stats_f32(const float *logits, int stride, int rows, int n, const int64_t *codes, float *log_prob, float *entropy,
+                    int *rank, int top_n, int64_t *top_codes, float *top_log_probs, hipStream_t stream);
 
 int rel_attention_decode_splits(int Sk, int pairs);
 int attention_tail_rows(int S, int mask_mode, bool dense_mask);   // rel_attention_f32.hip

@@ -843,9 +843,18 @@ __device__ __forceinline__ float block_inclusive_scan(float v, float *wave_tot, 
 // Each thread walks the row with stride blockDim.x (one element per thread for n <= blockDim.x), the partial maxima / sums
 // are reduced inside the wave (`__shfl_xor`: every lane ends with the same bits) and the wave totals are exchanged once and
 // combined in fixed order by every thread -- two block barriers per reduction, as block_inclusive_scan.  The value is a
-// function of (row, n, tok, blockDim.x) alone: the draw kernel and token_log_prob_kernel agree bit for bit on equal logits
-// and an equal workgroup size.  tok in [0, n) (the caller's check); wave_tot: 16 floats, free on entry and on return.
-__device__ __forceinline__ float block_token_log_prob(const float *__restrict__ row, int n, int tok, float *wave_tot) {
+// function of (row, n, tok, blockDim.x) alone: the draw kernel, token_log_prob_kernel and token_stats_kernel agree bit for
+// bit on equal logits and an equal workgroup size.  tok in [0, n) (the caller's check); wave_tot: 16 floats, free on entry
+// and on return.
+// STATS (token_stats_kernel): the reductions themselves are handed out as well -- st = {m, log(tot), -sum p_i ln p_i}, the
+// entropy from sum exp(row[i] - m) * (row[i] - m) gathered by the same walk (a -inf logit adds 0) through wave_ent (16 more
+// floats) inside the sum's barriers; the value at tok stays (row[tok] - m) - log(tot), and tok may be any class.
+struct RowStats {
+  float m, lse, entropy;
+};
+template <bool STATS = false>
+__device__ __forceinline__ float block_token_log_prob(const float *__restrict__ row, int n, int tok, float *wave_tot,
+                                                      float *wave_ent = nullptr, RowStats *st = nullptr) {
   const int tid = threadIdx.x, np = blockDim.x, nw = (np + 63) >> 6;
   float m = -INFINITY;
   for (int i = tid; i < n; i += np) m = fmaxf(m, row[i]);
@@ -856,16 +865,38 @@ __device__ __forceinline__ float block_token_log_prob(const float *__restrict__ 
   m = wave_tot[0];
   for (int w = 1; w < nw; ++w) m = fmaxf(m, wave_tot[w]);
   __syncthreads();
-  float sum = 0.f;
-  for (int i = tid; i < n; i += np) sum += expf(row[i] - m);
+  float sum = 0.f, es = 0.f;
+  for (int i = tid; i < n; i += np) {
+    if constexpr (STATS) {
+      const float d = row[i] - m, e = expf(d);
+      sum += e;
+      es += d == -INFINITY ? 0.f : e * d;
+    } else {
+      sum += expf(row[i] - m);
+    }
+  }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+  for (int o = 32; o > 0; o >>= 1) {
+    sum += __shfl_xor(sum, o);
+    if constexpr (STATS) es += __shfl_xor(es, o);
+  }
   if ((tid & 63) == 0) wave_tot[tid >> 6] = sum;
+  if constexpr (STATS)
+    if ((tid & 63) == 0) wave_ent[tid >> 6] = es;
   __syncthreads();
-  float tot = 0.f;
-  for (int w = 0; w < nw; ++w) tot += wave_tot[w];     // fixed order: the same sum on every thread
+  float tot = 0.f, et = 0.f;
+  for (int w = 0; w < nw; ++w) {       // fixed order: the same sums on every thread
+    tot += wave_tot[w];
+    if constexpr (STATS) et += wave_ent[w];
+  }
   __syncthreads();
-  return (row[tok] - m) - logf(tot);
+  if constexpr (STATS) {
+    const float lse = logf(tot);
+    *st = {m, lse, lse - et / tot};
+    return (row[tok] - m) - lse;
+  } else {
+    return (row[tok] - m) - logf(tot);
+  }
 }
 
 // LP: the commit also stores the model's log-probability of the token (SampleCommit.log_probs); the instantiations
@@ -1090,6 +1121,104 @@ int token_log_prob_f32(const float *logits, int stride, int rows, int n, const i
   while (np < n && np < 1024) np <<= 1;
   hipLaunchKernelGGL(token_log_prob_kernel, dim3(rows), dim3(np), 0, stream, logits, stride, n, codes, out);
   return check_launch("token_log_prob_f32");
+}
+
+// ------------------------------------------------------------------ statistics of a logit row
+// A class as one orderable 64-bit key: the logit's bits mapped so that unsigned order is numeric order (-0 counts as +0, as
+// it compares), then the inverted index -- a larger key comes first in "descending logit, ties by lower index", the order
+// of the draw kernel's sort.  No class has key 0 (that takes a NaN's bits).
+__device__ __forceinline__ unsigned long long class_key(float x, int i) {
+  unsigned int u = __float_as_uint(x == 0.f ? 0.f : x);
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((unsigned long long)u << 32) | (unsigned int)~i;
+}
+
+// One workgroup per row, one pass of block_token_log_prob<STATS> over it (every log-probability is its expression on its m
+// and log(tot): bit-equal to token_log_prob_kernel at an equal workgroup size):
+//   log_prob[r] = log softmax(row)[codes[r]];  entropy[r] = log(tot) - sum e_i (x_i - m) / tot = -sum p_i ln p_i;
+//   rank[r] = the number of classes whose key is larger than the code's (ballots and popcounts, exact);
+//   top_codes / top_log_probs[r, 0:top_n]: top_n rounds of a block arg-max over the keys below the previous winner -- a
+//   wave reduction and one exchange of the wave maxima through a double-buffered array: one barrier per round.
+// Every output may be null; codes may be null when log_prob and rank are.  A code outside [0, n): NaN, -1, nothing read.
+__global__ __launch_bounds__(1024) void token_stats_kernel(const float *__restrict__ logits, int stride, int n,
+                                                           const int64_t *__restrict__ codes, float *__restrict__ log_prob,
+                                                           float *__restrict__ entropy, int *__restrict__ rank, int top_n,
+                                                           int64_t *__restrict__ top_codes,
+                                                           float *__restrict__ top_log_probs) {
+  __shared__ float wave_tot[16], wave_ent[16];
+  __shared__ int wave_cnt[16];
+  __shared__ unsigned long long wave_key[2][16];
+  const int tid = threadIdx.x, np = blockDim.x, nw = (np + 63) >> 6, row = blockIdx.x;
+  const float *x = logits + (size_t)row * stride;
+  RowStats st;
+  block_token_log_prob<true>(x, n, 0, wave_tot, wave_ent, &st);
+  const float m = st.m, lse = st.lse;
+  if (entropy && tid == 0) entropy[row] = st.entropy;
+  if (codes) {                         // (the code is uniform over the workgroup: every thread takes the barrier or none does)
+    const int64_t code = codes[row];
+    const bool ok = code >= 0 && code < n;
+    if (log_prob && tid == 0) log_prob[row] = ok ? (x[code] - m) - lse : __builtin_nanf("");
+    if (rank) {
+      int r = -1;
+      if (ok) {
+        const unsigned long long kc = class_key(x[code], (int)code);
+        int cnt = 0;                   // of this wave (every lane holds the same count)
+        for (int i0 = 0; i0 < n; i0 += np) {
+          const int i = i0 + tid;
+          cnt += __popcll(__ballot(i < n && class_key(x[i], i) > kc));
+        }
+        if ((tid & 63) == 0) wave_cnt[tid >> 6] = cnt;
+        __syncthreads();
+        r = 0;
+        for (int w = 0; w < nw; ++w) r += wave_cnt[w];
+      }
+      if (tid == 0) rank[row] = r;
+    }
+  }
+  if (top_n <= 0 || (!top_codes && !top_log_probs)) return;
+  const unsigned long long k0 = tid < n ? class_key(x[tid], tid) : 0ull;
+  unsigned long long prev = ~0ull;     // the previous round's winner: only keys below it bid
+  for (int r = 0; r < top_n; ++r) {
+    int cls = -1;
+    float lp = -INFINITY;
+    if (r < n) {                       // (uniform) else: fewer classes than top_n, the tail holds -1 / -inf
+      unsigned long long best = k0 < prev ? k0 : 0ull;
+      for (int i = tid + np; i < n; i += np) {
+        const unsigned long long k = class_key(x[i], i);
+        if (k < prev && k > best) best = k;
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long t = __shfl_xor(best, o);
+        best = t > best ? t : best;
+      }
+      unsigned long long *ex = wave_key[r & 1];          // round r + 1 writes the other buffer: no second barrier
+      if ((tid & 63) == 0) ex[tid >> 6] = best;
+      __syncthreads();
+      best = ex[0];
+      for (int w = 1; w < nw; ++w) best = ex[w] > best ? ex[w] : best;
+      prev = best;
+      cls = (int)~(unsigned int)best;
+      if (tid == 0 && top_log_probs) lp = (x[cls] - m) - lse;
+    }
+    if (tid == 0) {
+      if (top_codes) top_codes[(size_t)row * top_n + r] = cls;
+      if (top_log_probs) top_log_probs[(size_t)row * top_n + r] = lp;
+    }
+  }
+}
+
+int token_stats_f32(const float *logits, int stride, int rows, int n, const int64_t *codes, float *log_prob, float *entropy,
+                    int *rank, int top_n, int64_t *top_codes, float *top_log_probs, hipStream_t stream) {
+  if (!logits) return invalid("token_stats: null logits");
+  if (rows <= 0 || n <= 0 || stride < n) return invalid("token_stats: rows, n must be positive and stride >= n");
+  if (top_n < 0 || top_n > 16) return invalid("token_stats: top_n must be 0 .. 16");
+  if (!codes && (log_prob || rank)) return invalid("token_stats: log_prob and rank need codes");
+  int np = 64;                         // token_log_prob_f32's workgroup size: the log-probabilities agree bit for bit
+  while (np < n && np < 1024) np <<= 1;
+  hipLaunchKernelGGL(token_stats_kernel, dim3(rows), dim3(np), 0, stream, logits, stride, n, codes, log_prob, entropy, rank,
+                     top_n, top_codes, top_log_probs);
+  return check_launch("token_stats_f32");
 }
 
 }  // namespace isi

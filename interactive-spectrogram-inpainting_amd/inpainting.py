@@ -20,13 +20,15 @@ The heavy work is `sample.sample_model` (encoder pass + KV-cached native decodin
 """
 from __future__ import annotations
 
+import inspect
+import math
 import struct
 import zlib
 from typing import List, Mapping, Optional, Sequence, Tuple
 
 import torch
 
-from sample import sample_model
+from sample import codemap_statistics, sample_model
 
 
 def make_time_indexes(start_index: int, codemap_duration: int, transformer_duration: int) -> List[int]:
@@ -52,6 +54,14 @@ def _windows(top_code, bottom_code, transformer_top, transformer_bottom, start_i
     return (s_top, e_top), (s_bot, e_bot), ratio_t
 
 
+def _check_score_options(return_scores, sort_by_likelihood, uniform_sampling) -> None:
+    """The combinations of `timerange_change`'s score options that have no meaning (ValueError)."""
+    if sort_by_likelihood and not return_scores:
+        raise ValueError("sort_by_likelihood orders the variations by their scores: it needs return_scores=True")
+    if return_scores and uniform_sampling:
+        raise ValueError("return_scores: uniform_sampling draws from no model distribution, there is no likelihood to report")
+
+
 @torch.no_grad()
 def timerange_change(transformer_top, transformer_bottom, top_code: torch.Tensor, bottom_code: torch.Tensor,
                      mask: torch.Tensor, layer: str, start_index_top: int, temperature: float,
@@ -71,10 +81,7 @@ def timerange_change(transformer_top, transformer_bottom, top_code: torch.Tensor
     the sum of the sampled tokens' model log-probabilities (`sample_model(return_log_probs=True)`) over the stages that ran,
     top then bottom.  sort_by_likelihood (needs return_scores): the variations in descending order of that score, ties in
     their original order.  Uniform sampling draws from no model distribution: it has no score (ValueError)."""
-    if sort_by_likelihood and not return_scores:
-        raise ValueError("sort_by_likelihood orders the variations by their scores: it needs return_scores=True")
-    if return_scores and uniform_sampling:
-        raise ValueError("return_scores: uniform_sampling draws from no model distribution, there is no likelihood to report")
+    _check_score_options(return_scores, sort_by_likelihood, uniform_sampling)
     if num_variations is not None:
         return _timerange_change_variations(transformer_top, transformer_bottom, top_code, bottom_code, mask, layer,
                                             start_index_top, temperature, class_conditioning_top,
@@ -120,6 +127,107 @@ def timerange_change(transformer_top, transformer_bottom, top_code: torch.Tensor
     if return_scores:
         return _ranked(top_code, bottom_code, scores, sort_by_likelihood)
     return top_code, bottom_code
+
+
+# what `timerange_change` accepts by keyword beyond its positional arguments: its own options and, through **sampling_kwargs,
+# those of `sample_model` that it does not set itself
+_TIMERANGE_CHANGE_KEYWORDS = frozenset(
+    {name for name, par in inspect.signature(timerange_change).parameters.items()
+     if par.kind is par.POSITIONAL_OR_KEYWORD and par.default is not par.empty}
+    | set(inspect.signature(sample_model).parameters)
+    - {'model', 'device', 'batch_size', 'temperature', 'condition', 'codemap_size', 'class_conditioning', 'initial_code',
+       'mask', 'time_indexes_source', 'time_indexes_target', 'return_log_probs', 'num_variations', 'generator',
+       'kv_cache_dtype'})
+
+
+@torch.no_grad()
+def uncertainty(transformer_top, transformer_bottom, top_code: torch.Tensor, bottom_code: torch.Tensor,
+                mask: Optional[torch.Tensor], layer: str, start_index_top: int,
+                class_conditioning_top: Mapping[str, torch.Tensor], class_conditioning_bottom: Mapping[str, torch.Tensor],
+                device, top_n: int = 0):
+    """`sample.codemap_statistics` of the prior of `layer` over the model window starting at `start_index_top` -- the
+    window, the source and the time indexes `timerange_change` would sample with: the top prior reads the top window
+    through its encoder (mask tokens under `mask`), the bottom prior the top window as its condition.  top_code [1, F_t, T],
+    bottom_code [1, F_b, T_b], mask bool [1, F, W] in the resolution of `layer` (None: every position, and see
+    `codemap_statistics` on a self-conditional prior without a mask).  Returns its maps over the window: log_probs, entropy,
+    rank [1, F, W], top_codes, top_log_probs [1, F, W, top_n]."""
+    (s_top, e_top), (s_bot, e_bot), _ = _windows(top_code, bottom_code, transformer_top, transformer_bottom, start_index_top)
+    top_frame = top_code[..., s_top:e_top]
+    ti_top = make_time_indexes(s_top, top_code.shape[-1], transformer_top.shape[-1])
+    if layer == 'top':
+        condition = top_frame if transformer_top.self_conditional_model else None
+        return codemap_statistics(transformer_top, device, top_frame, condition=condition,
+                                  class_conditioning=class_conditioning_top, mask=mask, time_indexes_source=ti_top,
+                                  time_indexes_target=ti_top, top_n=top_n)
+    if layer == 'bottom':
+        ti_bottom = make_time_indexes(s_bot, bottom_code.shape[-1], transformer_bottom.shape[-1])
+        return codemap_statistics(transformer_bottom, device, bottom_code[..., s_bot:e_bot], condition=top_frame,
+                                  class_conditioning=class_conditioning_bottom, mask=mask, time_indexes_source=ti_top,
+                                  time_indexes_target=ti_bottom, top_n=top_n)
+    raise ValueError(f"unknown layer {layer}")
+
+
+def select_unlikely(log_probs: torch.Tensor, region: torch.Tensor, fraction: Optional[float] = None,
+                    log_prob_below: Optional[float] = None) -> torch.Tensor:
+    """The tokens of `region` (bool, the shape of `log_probs`) to sample again -- a bool mask of that shape, a subset of the
+    region.  Exactly one rule (else ValueError): fraction in [0, 1] -- the ceil(fraction * |region|) tokens of lowest
+    log-probability, equal values in the order of the flattened tensors (`resample_unlikely` passes sequences: ties go in
+    the order the prior decodes them); log_prob_below -- every token whose log-probability lies below the threshold.
+    Values outside the region are never looked at.  A pure function of its tensors."""
+    if (fraction is None) == (log_prob_below is None):
+        raise ValueError("select_unlikely: give exactly one of fraction and log_prob_below")
+    if tuple(region.shape) != tuple(log_probs.shape) or region.dtype != torch.bool:
+        raise ValueError(f"select_unlikely: region {region.dtype} {tuple(region.shape)} for log_probs {tuple(log_probs.shape)}")
+    region = region.to(log_probs.device)
+    if log_prob_below is not None:
+        return region & (log_probs < log_prob_below)
+    if not 0.0 <= fraction <= 1.0:
+        raise ValueError(f"select_unlikely: fraction must lie in [0, 1], not {fraction}")
+    inside = region.reshape(-1).nonzero()[:, 0]
+    count = math.ceil(fraction * inside.numel())
+    order = torch.argsort(log_probs.reshape(-1)[inside], stable=True)[:count]
+    selected = torch.zeros(region.numel(), dtype=torch.bool, device=region.device)
+    selected[inside[order]] = True
+    return selected.reshape(region.shape)
+
+
+@torch.no_grad()
+def resample_unlikely(transformer_top, transformer_bottom, top_code: torch.Tensor, bottom_code: torch.Tensor,
+                      mask: torch.Tensor, layer: str, start_index_top: int, temperature: float,
+                      class_conditioning_top: Mapping[str, torch.Tensor],
+                      class_conditioning_bottom: Mapping[str, torch.Tensor], device, fraction: Optional[float] = None,
+                      log_prob_below: Optional[float] = None, **timerange_change_kwargs) -> Tuple[torch.Tensor, ...]:
+    """"Fix what sounds wrong, keep the rest": `mask` (bool [1, F, W] in the resolution of `layer`) is the region the caller
+    allows to change; the window is scored under it (`uncertainty`), `select_unlikely` picks the tokens inside it --
+    `fraction`: that share of the region, least likely first; `log_prob_below`: every token below the threshold; exactly
+    one of the two -- and `timerange_change` samples the selection again: after a top change the bottom prior runs under
+    the up-sampled selection, as always.  Everything else (generator, kv_cache_dtype, num_variations, return_scores,
+    sort_by_likelihood, top_k_sampling_k, top_p_sampling_p, ...) goes to `timerange_change` unchanged.  Returns its result
+    with the selected mask appended: (top, bottom[, log_likelihood], selected).  An empty selection samples nothing and
+    returns the inputs -- with num_variations = N as N equal rows, with return_scores a log-likelihood of 0."""
+    if (fraction is None) == (log_prob_below is None):
+        raise ValueError("resample_unlikely: give exactly one of fraction and log_prob_below")
+    kw = timerange_change_kwargs
+    _check_score_options(kw.get('return_scores'), kw.get('sort_by_likelihood'), kw.get('uniform_sampling'))
+    unknown = set(kw) - _TIMERANGE_CHANGE_KEYWORDS      # (checked here: an empty selection never reaches timerange_change)
+    if unknown:
+        raise TypeError(f"resample_unlikely: unexpected keyword argument(s) {sorted(unknown)}")
+    stats = uncertainty(transformer_top, transformer_bottom, top_code, bottom_code, mask, layer, start_index_top,
+                        class_conditioning_top, class_conditioning_bottom, device)
+    helper = (transformer_top if layer == 'top' else transformer_bottom).target_codemaps_helper
+    selected = helper.to_time_frequency_map(select_unlikely(
+        helper.to_sequence(stats.log_probs), helper.to_sequence(mask.to(stats.log_probs.device)), fraction, log_prob_below))
+    if not bool(selected.any()):
+        N = kw.get('num_variations')
+        rows = 1 if N is None else int(N)
+        if rows < 1:
+            raise ValueError(f"num_variations must be at least 1, not {N}")
+        out = (top_code.clone(), bottom_code.clone()) if N is None else (top_code.repeat(rows, 1, 1), bottom_code.repeat(rows, 1, 1))
+        if kw.get('return_scores'):
+            out += (torch.zeros(rows, dtype=torch.float32, device=stats.log_probs.device),)
+        return out + (selected,)
+    return timerange_change(transformer_top, transformer_bottom, top_code, bottom_code, selected, layer, start_index_top,
+                            temperature, class_conditioning_top, class_conditioning_bottom, device, **kw) + (selected,)
 
 
 def _stage_score(log_probs: torch.Tensor) -> torch.Tensor:

@@ -241,6 +241,7 @@ SIGNATURES = {
     "isi_sample_row_log_prob_f32": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, _P, _P, _P,
                                               _P]),
     "isi_token_log_prob_f32": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "isi_token_stats_f32": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
     "isi_prior_decode_scratch_floats": (C.c_size_t, [C.POINTER(isi_prior_w), C.c_int]),
     "isi_prior_sample_run": (C.c_int, [C.POINTER(isi_prior_w), C.POINTER(isi_prior_state), C.c_int, C.c_int,
                                        C.c_float, C.c_int, C.c_float, _P]),

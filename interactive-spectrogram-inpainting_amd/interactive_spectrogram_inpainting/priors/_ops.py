@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -509,3 +509,52 @@ def token_log_probs(logits: torch.Tensor, codes: torch.Tensor) -> torch.Tensor:
                                                out.data_ptr(), _s(logits))
         _hip.check(rc, "isi_token_log_prob_f32")
     return out.reshape(codes.shape)
+
+
+class TokenStats(NamedTuple):
+    """`token_stats`' result; a field that was not asked for is None."""
+    log_probs: Optional[torch.Tensor]
+    entropy: torch.Tensor
+    rank: Optional[torch.Tensor]
+    top_codes: Optional[torch.Tensor]
+    top_log_probs: Optional[torch.Tensor]
+
+
+def token_stats(logits: torch.Tensor, codes: Optional[torch.Tensor] = None, top_n: int = 0) -> TokenStats:
+    """logits [..., n] fp32, codes [...] int64 or None -> statistics of the model's distribution per row
+    (`isi_token_stats_f32`, one read of the row): entropy float32 [...] in nats; with `codes`, log_probs float32 [...] (bit-equal
+    to `token_log_probs`; NaN where a code lies outside [0, n)) and rank int32 [...] (classes ahead of the code in descending
+    logit order, ties by lower index: 0 is the mode; -1 for such a code); with top_n in 1 .. 16, top_codes int64 [..., top_n]
+    and top_log_probs float32 [..., top_n] in that order (-1 / -inf behind the n-th class).  Rows may be strided (a view of
+    a wider buffer), the class dimension not."""
+    _hip.require_gpu(logits, "logits")
+    if logits.dtype != torch.float32:
+        raise _hip.HipLibraryError(f"token_stats: logits {logits.dtype}; expected float32")
+    if not 0 <= int(top_n) <= 16:
+        raise ValueError(f"token_stats: top_n must be 0 .. 16, not {top_n}")
+    top_n = int(top_n)
+    n = logits.shape[-1]
+    lead = tuple(logits.shape[:-1])
+    if codes is not None:
+        _hip.require_gpu(codes, "codes")
+        if codes.dtype != torch.int64:
+            raise _hip.HipLibraryError(f"token_stats: codes {codes.dtype}; expected int64")
+        if tuple(codes.shape) != lead:
+            raise ValueError(f"token_stats: codes {tuple(codes.shape)} for logits {tuple(logits.shape)}")
+    rows2 = logits if logits.dim() == 2 and logits.stride(1) == 1 else logits.reshape(-1, n).contiguous()
+    rows, dev = rows2.shape[0], logits.device
+    codes1 = codes.reshape(-1).contiguous() if codes is not None else None
+    entropy = torch.empty(rows, dtype=torch.float32, device=dev)
+    log_probs = torch.empty(rows, dtype=torch.float32, device=dev) if codes is not None else None
+    rank = torch.empty(rows, dtype=torch.int32, device=dev) if codes is not None else None
+    top_codes = torch.empty(rows, top_n, dtype=torch.int64, device=dev) if top_n else None
+    top_log_probs = torch.empty(rows, top_n, dtype=torch.float32, device=dev) if top_n else None
+    if rows:
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        rc = _hip.lib().isi_token_stats_f32(rows2.data_ptr(), rows2.stride(0), rows, n, ptr(codes1), ptr(log_probs),
+                                            entropy.data_ptr(), ptr(rank), top_n, ptr(top_codes), ptr(top_log_probs),
+                                            _s(logits))
+        _hip.check(rc, "isi_token_stats_f32")
+    shaped = lambda t, *tail: t.reshape(lead + tail) if t is not None else None
+    return TokenStats(shaped(log_probs), shaped(entropy), shaped(rank), shaped(top_codes, top_n),
+                      shaped(top_log_probs, top_n))

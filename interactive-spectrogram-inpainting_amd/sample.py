@@ -16,7 +16,7 @@ instead of torch.multinomial's stream.
 from __future__ import annotations
 
 import os
-from typing import Iterable, Mapping, Optional, Sequence, Union
+from typing import Iterable, Mapping, NamedTuple, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -296,13 +296,25 @@ def score_codemap(model: VQNSynthTransformer, device: Union[torch.device, str], 
     positions outside it are 0.0.  For a result c of `sample_model(..., initial_code=i, condition=x, mask=m)`,
     `score_codemap(model, device, c, condition=(i if model.self_conditional_model else x), mask=m)` with the same
     conditioning reproduces the loop's `return_log_probs`."""
+    logits, code_seq, mask_seq = _teacher_forced_logits("score_codemap", model, device, codemap, condition,
+                                                        class_conditioning, mask, time_indexes_source, time_indexes_target)
+    log_probs = _ops.token_log_probs(logits, code_seq)                         # [B, S]
+    if mask_seq is not None:
+        log_probs = torch.where(mask_seq, log_probs, torch.zeros((), dtype=torch.float32, device=logits.device))
+    return model.target_codemaps_helper.to_time_frequency_map(log_probs)
+
+
+def _teacher_forced_logits(who: str, model, device, codemap, condition, class_conditioning, mask, time_indexes_source,
+                           time_indexes_target):
+    """The one teacher-forced full pass behind `score_codemap` and `codemap_statistics`: (logits [B, S, n_class] contiguous,
+    the codemap as sequences [B, S] int64, the mask as sequences [B or 1, S] bool or None)."""
     device = torch.device(device)
     model.eval()
     codemap = codemap.to(device)
     batch_size = codemap.shape[0]
     if condition is None:
         if not model.self_conditional_model:
-            raise ValueError("score_codemap: a model that is not self-conditional needs its condition codemap")
+            raise ValueError(f"{who}: a model that is not self-conditional needs its condition codemap")
         condition = codemap
     if mask is not None:
         if mask.dim() == 3 and mask.shape[0] not in (1, batch_size):
@@ -317,12 +329,57 @@ def score_codemap(model: VQNSynthTransformer, device: Union[torch.device, str], 
         time_indexes_source=time_indexes_source, time_indexes_target=time_indexes_target)
     logits, _ = model(target_seq, source_seq)                                  # [B, S, n_class]
     code_seq = model.target_codemaps_helper.to_sequence(codemap).contiguous()
-    log_probs = _ops.token_log_probs(logits.contiguous(), code_seq)            # [B, S]
+    mask_seq = None
     if mask is not None:
         S = model.target_transformer_sequence_length
         mask_seq = model.target_codemaps_helper.to_sequence(mask).reshape(-1, S)
-        log_probs = torch.where(mask_seq, log_probs, torch.zeros((), dtype=torch.float32, device=device))
-    return model.target_codemaps_helper.to_time_frequency_map(log_probs)
+    return logits.contiguous(), code_seq, mask_seq
+
+
+class CodemapStatistics(NamedTuple):
+    """`codemap_statistics`' maps, [B, F, T] each (the top-n maps [B, F, T, top_n])."""
+    log_probs: torch.Tensor
+    entropy: torch.Tensor
+    rank: torch.Tensor
+    top_codes: torch.Tensor
+    top_log_probs: torch.Tensor
+
+
+@torch.no_grad()
+def codemap_statistics(model: VQNSynthTransformer, device: Union[torch.device, str], codemap: torch.Tensor,
+                       condition: Optional[torch.Tensor] = None, class_conditioning: Mapping[str, Iterable[int]] = {},
+                       mask: Optional[torch.Tensor] = None, time_indexes_source: Optional[Iterable[int]] = None,
+                       time_indexes_target: Optional[Iterable[int]] = None, top_n: int = 0) -> CodemapStatistics:
+    """What the model thinks of every code of `codemap` [B, F, T], from `score_codemap`'s single teacher-forced pass (the
+    same arguments, the same logits) and one `isi_token_stats_f32` call over its B S rows:
+      log_probs      float32 [B, F, T]: `score_codemap`'s result, bit for bit;
+      entropy        float32 [B, F, T]: the entropy in nats of the model's distribution at the position (raw logits,
+                     temperature 1, nothing filtered) -- high: the model is unsure; low with a low log-probability: the code
+                     surprises it;
+      rank           int32 [B, F, T]: how many classes the model ranks ahead of the code that is there (0: its first choice);
+      top_codes      int64 [B, F, T, top_n] and top_log_probs float32 [B, F, T, top_n]: the model's top_n (0 .. 16) classes
+                     for the position, most likely first (equal logits: lower class first), and their log-probabilities.
+    Outside `mask`: log_probs 0.0, entropy 0.0, rank -1, top_codes -1, top_log_probs -inf.
+    The values are teacher-forced: the decoder is causal, so position i is scored given the codes of `codemap` before it,
+    as the sampling loop saw them.  The SOURCE side is different: a self-conditional prior scored WITHOUT a mask reads the
+    whole codemap through its encoder, the scored position included -- its statistics are then those of a model that
+    already knows the answer (log-probabilities near 0, entropies near 0, ranks 0).  To ask what the model would put in a
+    region, pass the region as `mask`: the encoder then sees mask tokens there, as it did when sampling."""
+    if not 0 <= int(top_n) <= 16:
+        raise ValueError(f"codemap_statistics: top_n must be 0 .. 16, not {top_n}")
+    logits, code_seq, mask_seq = _teacher_forced_logits("codemap_statistics", model, device, codemap, condition,
+                                                        class_conditioning, mask, time_indexes_source, time_indexes_target)
+    st = _ops.token_stats(logits, code_seq, int(top_n))
+    top_codes, top_log_probs = st.top_codes, st.top_log_probs
+    if top_codes is None:
+        top_codes = torch.empty(code_seq.shape + (0,), dtype=torch.int64, device=logits.device)
+        top_log_probs = torch.empty(code_seq.shape + (0,), dtype=torch.float32, device=logits.device)
+    maps = [st.log_probs, st.entropy, st.rank, top_codes, top_log_probs]
+    if mask_seq is not None:
+        outside = (0.0, 0.0, -1, -1, float("-inf"))
+        maps = [torch.where(mask_seq if t.dim() == 2 else mask_seq[..., None], t,
+                            torch.full((), v, dtype=t.dtype, device=t.device)) for t, v in zip(maps, outside)]
+    return CodemapStatistics(*(model.target_codemaps_helper.to_time_frequency_map(t) for t in maps))
 
 
 def _one_value(value, name: str):

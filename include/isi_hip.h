@@ -528,8 +528,10 @@ int isi_layernorm_bwd_f32(const float *x, const float *residual, const float *ga
 
 /* LabelSmoothingLoss (utils/losses/prediction.py:5-20) over rows of logits [M,K] with
  * int64 targets [M]: row_loss[m] = sum_k -true_dist[k] log_softmax(logits[m])[k]; when
- * dlogits is not NULL also (softmax - true_dist) * grad_scale (the gradient of the mean
- * loss for grad_scale = upstream / M), in the same pass. */
+ * dlogits is not NULL also (softmax * sum_k true_dist[k] - true_dist) * grad_scale (the
+ * gradient of the mean loss for grad_scale = upstream / M), in the same pass.  true_dist is
+ * smoothing / (num_classes - 1) in all K columns and 1 - smoothing at the target: it sums to 1
+ * for K == num_classes, and the gradient is then (softmax - true_dist) * grad_scale. */
 int isi_label_smoothing_loss_f32(const float *logits, const int64_t *target, float *row_loss,
                                  float *dlogits, int64_t M, int K, int num_classes,
                                  float smoothing, float grad_scale, void *stream);

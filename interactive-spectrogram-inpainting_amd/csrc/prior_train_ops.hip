@@ -220,11 +220,14 @@ int layernorm_bwd_f32(const float *x, const float *res, const float *gamma, cons
 
 // Label smoothing (prediction.py:5-20): true_dist = smoothing / (num_classes - 1) everywhere, 1 - smoothing at the
 // target; row loss = sum_k -true_dist[k] * log_softmax(logits)[k].  One wave per row; writes the row loss
-// and d(mean loss)/d(logits) = (softmax - true_dist) * grad_scale  (grad_scale = upstream / rows).
+// and d(mean loss)/d(logits) = (softmax * sum_k true_dist[k] - true_dist) * grad_scale  (grad_scale = upstream / rows).
+// true_dist sums to td_sum = 1 - smoothing + (K - 1) smoothing / (num_classes - 1): 1 when K == num_classes, not when the
+// logits carry a class more than the criterion counts (a mask token) -- the softmax term then weighs td_sum, not 1.
 __global__ __launch_bounds__(256) void label_smoothing_kernel(const float *__restrict__ logits,
                                                               const int64_t *__restrict__ target,
                                                               float *__restrict__ row_loss, float *__restrict__ dlogits,
-                                                              int M, int K, int num_classes, float smoothing, float grad_scale) {
+                                                              int M, int K, int num_classes, float smoothing, float grad_scale,
+                                                              float td_sum) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
@@ -253,7 +256,7 @@ __global__ __launch_bounds__(256) void label_smoothing_kernel(const float *__res
     const float inv = 1.f / se;
     for (int c = lane; c < K; c += 64) {
       const float pr = expf(lr[c] - mx) * inv;
-      dr[c] = (pr - (c == t ? on : off)) * grad_scale;
+      dr[c] = (pr * td_sum - (c == t ? on : off)) * grad_scale;
     }
   }
 }
@@ -262,8 +265,11 @@ int label_smoothing_loss_f32(const float *logits, const int64_t *target, float *
                              int K, int num_classes, float smoothing, float grad_scale, hipStream_t stream) {
   if (!logits || !target || !row_loss || M <= 0 || M > INT32_MAX || K <= 1 || num_classes <= 1)
     return invalid("label_smoothing_loss: bad argument");
+  // exactly 1 for K == num_classes: the product with the softmax is then the identity, bit for bit
+  const float td_sum = K == num_classes ? 1.f
+                                        : (float)((1.0 - (double)smoothing) + (K - 1) * ((double)smoothing / (num_classes - 1)));
   hipLaunchKernelGGL(label_smoothing_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, stream, logits, target,
-                     row_loss, dlogits, (int)M, K, num_classes, smoothing, grad_scale);
+                     row_loss, dlogits, (int)M, K, num_classes, smoothing, grad_scale, td_sum);
   return check_launch("label_smoothing_loss");
 }
 

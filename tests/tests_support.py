@@ -1,5 +1,6 @@
 """Helpers shared by CPU and GPU tests (test infrastructure)."""
 import collections
+import math
 
 import numpy as np
 import torch
@@ -255,3 +256,169 @@ def sampling_grid_rows():
 
 def sampling_grid_uniforms():
     return ((np.arange(2 ** 18, dtype=np.float64) + 0.5) / 2.0 ** 18).astype(np.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Float64 specifications of the prior's row-wise kernels (LayerNorm forward and backward with the fused residual and
+# dropout, the label-smoothing criterion, the few-rows linear layer): closed forms in torch float64 on the CPU, no autograd
+# and none of the project's kernels.  tests/test_prior_row_ops_host.py holds them to float64 autograd and shows what
+# `compare_rows` accepts and rejects; tests/test_prior_row_ops_gpu.py holds the kernels to them.
+ROW_OPS_MARGIN = 8.0           # a kernel may be this many times as far from the float64 spec as float32 torch is
+ROW_OPS_FLOOR = 2.0 ** -23     # ... or as one float32 ulp, where float32 torch happens to be exact
+RowCheck = collections.namedtuple("RowCheck", "what err yardstick ratio")
+
+
+def _f64(t):
+    return None if t is None else torch.as_tensor(t).detach().cpu().double()
+
+
+def _ln_stats(x, res, eps, keep, p):
+    """z = drop(x) + res, its row mean, 1 / sqrt(biased variance + eps) and xhat, all float64."""
+    z = _f64(x)
+    if keep is not None:
+        z = z * _f64(keep) / (1.0 - p)
+    if res is not None:
+        z = z + _f64(res)
+    mean = z.mean(dim=-1, keepdim=True)
+    var = (z - mean).pow(2).mean(dim=-1, keepdim=True)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    return rstd, (z - mean) * rstd
+
+
+def layernorm_spec(x, res, gamma, beta, eps, keep=None, p=0.0):
+    """y = LayerNorm(drop(x) + res) * gamma + beta over the last dimension; drop = x * keep / (1 - p) for a boolean keep
+    mask (None: no dropout)."""
+    _, xhat = _ln_stats(x, res, eps, keep, p)
+    return xhat * _f64(gamma) + _f64(beta)
+
+
+def layernorm_bwd_spec(x, res, gamma, dy, eps, keep=None, p=0.0):
+    """(dz, dx, dgamma, dbeta) of layernorm_spec for the upstream gradient dy [M, D], by the formulas in the header of
+    layernorm_bwd_kernel: g = dy * gamma, dz = rstd * (g - mean(g) - xhat * mean(g * xhat)) is the gradient of z (and of
+    the residual), dx = dz * keep / (1 - p) that of x (dz itself without dropout), dgamma = sum over rows of dy * xhat,
+    dbeta = sum over rows of dy."""
+    rstd, xhat = _ln_stats(x, res, eps, keep, p)
+    dy = _f64(dy)
+    g = dy * _f64(gamma)
+    dz = rstd * (g - g.mean(dim=-1, keepdim=True) - xhat * (g * xhat).mean(dim=-1, keepdim=True))
+    dx = dz if keep is None else dz * _f64(keep) / (1.0 - p)
+    return dz, dx, (dy * xhat).sum(dim=0), dy.sum(dim=0)
+
+
+def label_smoothing_spec(logits, target, num_classes, smoothing, grad_scale):
+    """(row_loss [M], dlogits [M, K]) of the reference's LabelSmoothingLoss (oracle/prior_oracle.py::label_smoothing_loss):
+    true_dist = smoothing / (num_classes - 1) in every one of the K columns and 1 - smoothing at the target;
+    row_loss = -sum_k true_dist[k] * log_softmax(logits)[k]; dlogits = d(sum of row_loss)/d(logits) * grad_scale
+    = (softmax * sum_k true_dist[k] - true_dist) * grad_scale.  For K == num_classes true_dist sums to 1 and this is
+    (softmax - true_dist) * grad_scale; for K != num_classes (a mask token among the logits) it does not, and
+    (softmax - true_dist) is not the gradient of the loss (tests/test_prior_row_ops_host.py holds this form to autograd)."""
+    lg = _f64(logits)
+    v = lg - lg.max(dim=1, keepdim=True).values
+    logp = v - torch.log(torch.exp(v).sum(dim=1, keepdim=True))
+    true = torch.full_like(logp, smoothing / (num_classes - 1))
+    true[torch.arange(lg.shape[0]), torch.as_tensor(target).cpu().long()] = 1.0 - smoothing
+    return -(true * logp).sum(dim=1), (torch.exp(logp) * true.sum(dim=1, keepdim=True) - true) * grad_scale
+
+
+def linear_rows_spec(x, W, bias, res, relu):
+    """[relu](x W^T + bias + res) with the torch weight layout W [N, K]."""
+    y = _f64(x) @ _f64(W).t()
+    if bias is not None:
+        y = y + _f64(bias)
+    if res is not None:
+        y = y + _f64(res)
+    return y.clamp(min=0.0) if relu else y
+
+
+def row_error(got, ref):
+    """The metric of compare_rows.  A tensor with rows (two or more dimensions; rows = the last dimension): the largest
+    over rows of max|err_row| / max|ref_row|, the scale clamped from below at 2^-100 (an all-zero reference row).  A
+    vector: max|err| / max|ref|.  A non-finite value anywhere in `got` gives inf."""
+    got, ref = _f64(got), _f64(ref)
+    assert got.shape == ref.shape, f"shape {tuple(got.shape)} against {tuple(ref.shape)}"
+    if not bool(torch.isfinite(got).all()):
+        return float("inf")
+    err = (got - ref).abs()
+    if ref.dim() >= 2:
+        scale = ref.abs().amax(dim=-1).clamp(min=2.0 ** -100)
+        return float((err.amax(dim=-1) / scale).max())
+    return float(err.max() / ref.abs().max().clamp(min=2.0 ** -100))
+
+
+def compare_rows(got, ref, yardstick, what, margin=ROW_OPS_MARGIN):
+    """Holds `got` (a kernel's output) to the float64 reference `ref`, with the error of `yardstick` -- a float32 torch
+    evaluation of the same operation on the same data -- as the measure of what float32 can do there:
+        row_error(got, ref) <= margin * max(row_error(yardstick, ref), 2^-23).
+    Both round O(log D) to O(D) times in different orders, hence the margin of 8; a poorly conditioned (cancelling) sum
+    raises the yardstick's error with the kernel's, so the conditioning is priced in, not guessed.  Returns the RowCheck
+    (what, err, yardstick, ratio) for the record; raises AssertionError past the bound."""
+    err = row_error(got, ref)
+    yard = max(row_error(yardstick, ref), ROW_OPS_FLOOR)
+    assert math.isfinite(yard), f"{what}: the float32 yardstick itself is not finite"
+    ratio = err / yard
+    assert ratio <= margin, f"{what}: error {err:.3e} is {ratio:.1f} times the float32 yardstick {yard:.3e} (margin {margin:g})"
+    return RowCheck(what, err, yard, ratio)
+
+
+# float32 torch evaluations of the same operations, written with plain tensor operations on the CPU: the yardsticks of the
+# GPU tests, and what the host tests apply their mutants to
+def layernorm_f32(x, res, gamma, beta, eps, keep=None, p=0.0, mean_count=None, one_pass=False):
+    """(y, rstd, xhat) in float32.  The two switches are the host tests' mutants: `mean_count` divides the row sums by
+    this count, not by D; `one_pass` takes the variance as E[z^2] - mean^2."""
+    z = x.float()
+    D = z.shape[-1]
+    if keep is not None:
+        z = z * keep.float() / (1.0 - p)
+    if res is not None:
+        z = z + res.float()
+    mean = z.sum(dim=-1, keepdim=True) / float(mean_count or D)
+    if one_pass:
+        var = (z * z).sum(dim=-1, keepdim=True) / float(D) - mean * mean
+    else:
+        var = (z - mean).pow(2).sum(dim=-1, keepdim=True) / float(D)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    xhat = (z - mean) * rstd
+    return xhat * gamma.float() + beta.float(), rstd, xhat
+
+
+def layernorm_bwd_f32(x, res, gamma, dy, eps, keep=None, p=0.0):
+    _, rstd, xhat = layernorm_f32(x, res, gamma, torch.zeros_like(gamma), eps, keep, p)
+    dy = dy.float()
+    g = dy * gamma.float()
+    dz = rstd * (g - g.mean(dim=-1, keepdim=True) - xhat * (g * xhat).mean(dim=-1, keepdim=True))
+    dx = dz if keep is None else dz * keep.float() / (1.0 - p)
+    return dz, dx, (dy * xhat).sum(dim=0), dy.sum(dim=0)
+
+
+def label_smoothing_f32(logits, target, num_classes, smoothing, grad_scale, off=None, unit_sum=False):
+    """The host tests' mutants: `off`, another value for the off-target entries of true_dist; `unit_sum`, the gradient
+    (softmax - true_dist) whatever true_dist sums to."""
+    logp = logits.float().log_softmax(dim=1)
+    true = torch.full_like(logp, smoothing / (num_classes - 1) if off is None else off)
+    true[torch.arange(logp.shape[0]), target.long()] = 1.0 - smoothing
+    return -(true * logp).sum(dim=1), (logp.exp() * (1.0 if unit_sum else true.sum(dim=1, keepdim=True)) - true) * grad_scale
+
+
+def linear_rows_f32(x, W, bias, res, relu):
+    y = x.float() @ W.float().t()
+    if bias is not None:
+        y = y + bias.float()
+    if res is not None:
+        y = y + res.float()
+    return y.clamp(min=0.0) if relu else y
+
+
+def layernorm_data(kind, M, D, gen):
+    """x [M, D] float32: "randn"; "offset": rows of mean 100 and standard deviation 1, every third of standard deviation 1e-3
+    (poorly conditioned: a one-pass variance fails here); "const": randn with the first and the last row constant
+    (variance 0: rstd = 1 / sqrt(eps), y = beta)."""
+    x = torch.randn(M, D, generator=gen)
+    if kind == "offset":
+        x[2::3] *= 1e-3
+        x += 100.0
+    elif kind == "const":
+        x[0] = 3.75                                      # (few significant bits: a row's sum is exact in fp32 in any order)
+        x[-1] = -0.25
+    else:
+        assert kind == "randn", kind
+    return x

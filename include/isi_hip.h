@@ -41,7 +41,8 @@ const char *isi_last_error(void);
  * bindings can verify their own layout: which = 0 isi_src, 1 isi_dst,
  * 2 isi_conv_w, 3 isi_encoder_w, 4 isi_decoder_w, 5 isi_codebook_w,
  * 6 isi_vqvae_w, 7 isi_vqvae_out, 8 isi_attn_args, 9 isi_prior_w,
- * 10 isi_prior_state, 11 isi_attn_bwd_args, 12 isi_reduce_job, 13 isi_prior_rows.
+ * 10 isi_prior_state, 11 isi_attn_bwd_args, 12 isi_reduce_job, 13 isi_prior_rows,
+ * 14 isi_prior_code_bias.
  * Returns 0 for an unknown id. */
 size_t isi_abi_struct_bytes(int which);
 
@@ -606,6 +607,20 @@ int isi_rel_attention_decode_shared_f32(const isi_attn_args *args, int q_pos, fl
 int isi_sample_row_f32(const float *logits, int stride, int rows, int n, float temperature,
                        int top_k, float top_p, const float *u, int64_t *out,
                        float *filtered, void *stream);
+/* The same draw with a logit bias: row r adds bias[bias_row[r] * bias_stride + c] to logit c BEFORE temperature and
+ * filters -- lg = (logit + bias) * (1 / temperature), two separately rounded fp32 operations, then isi_sample_row_f32's
+ * filters and draw unchanged.  bias is a table [bias_count, bias_stride] on the device, bias_stride >= n; bias_row [rows]
+ * int32 on the device picks a table row per launch row, or NULL: table row 0 on every row.  An index outside
+ * [0, bias_count) (-1 by convention) means no bias for that row; the table is not read for it, whatever the value.  A
+ * bias of -inf bans the class: it takes the path of a -inf logit and is never drawn.  +inf and NaN biases are outside the
+ * contract (the library never reads a device array on the host: the caller checks), and every row keeps a finite biased
+ * logit.  filtered receives the biased, scaled, filtered logits.  NULL bias, bias_count <= 0, bias_stride < n, stride < n
+ * or isi_sample_row_f32's bad arguments: ISI_E_INVALID before any launch.  It is the decode loop's kernel and arithmetic
+ * (isi_prior_code_bias, isi_prior_sample_run_bias). */
+int isi_sample_row_bias_f32(const float *logits, int stride, int rows, int n, float temperature,
+                            int top_k, float top_p, const float *u, int64_t *out, float *filtered,
+                            const float *bias, int bias_stride, int bias_count, const int32_t *bias_row,
+                            void *stream);
 /* The same draw, and log_prob[row] = the MODEL's log-probability of the drawn token: log softmax of the row's raw
  * logits (temperature 1, nothing filtered, natural log, fp32) at out[row] -- the value does not depend on temperature,
  * top_k or top_p.  It is the decode loop's kernel and arithmetic (isi_prior_state.token_log_probs) and agrees bit for
@@ -753,6 +768,33 @@ typedef struct isi_prior_rows {
  * the attention, source row of single-source cross-attention, uniform, commit). */
 int isi_prior_sample_run_rows(const isi_prior_w *w, const isi_prior_state *state, const isi_prior_rows *rows,
                               int t_begin, int t_end, float temperature, int top_k, float top_p, void *stream);
+
+/* Code palettes and logit bias in the loop: a table of bias rows and, per token, the index of the row its draw uses.  The
+ * struct travels BESIDE isi_prior_state (whose size and offsets are what they were) into the two entries below. */
+typedef struct isi_prior_code_bias {
+  const float *code_bias;          /* [code_bias_count, n_class] device: logit bias rows; -inf bans a class                */
+  const int32_t *code_bias_index;  /* [code_bias_batch, S] device, SEQUENCE order (that of codes): the row of every token, */
+                                   /* -1 = none                                                                             */
+  int code_bias_count;             /* rows of code_bias                                                                     */
+  int code_bias_batch;             /* 1: one index row for all B rows; B: one per row                                       */
+} isi_prior_code_bias;
+/* isi_prior_sample_run / isi_prior_sample_run_rows with a code bias (isi_abi_struct_bytes(14) = sizeof(isi_prior_code_bias)).
+ * bias == NULL or a zeroed struct means off: exactly the launches of the entry without the argument.  On: the draw of
+ * token i of row b adds code_bias[r, 0:n_class], r = code_bias_index[(code_bias_batch == 1 ? 0 : b) * S + i], to the logits
+ * before temperature and filters (isi_sample_row_bias_f32's arithmetic: (logit + bias) * (1 / temperature)).  r outside
+ * [0, code_bias_count) -- -1 by convention -- means no bias for that token and reads nothing from the table.  A -inf bias
+ * bans a class (a palette is a row of 0 and -inf); +inf and NaN are outside the contract and every row keeps a finite
+ * biased logit -- the caller's checks: the library never reads a device array on the host.  state->token_log_probs stays
+ * the MODEL's log-probability: it is unaffected by the bias, as by temperature and filters.  Checked before any launch
+ * (ISI_E_INVALID): exactly one of the two pointers set, code_bias_count <= 0 with the pointers set, code_bias_batch not 1
+ * or B.  Works in every form of the loop: ragged plans (the index is by token, not by step), memory_shared, single-source
+ * cross-attention, both kv_formats, token_log_probs, direct launches and graph replay -- the bytes of *bias are part of the
+ * graph cache key beside those of *state, and the arrays' contents are read at replay time, as the uniforms are. */
+int isi_prior_sample_run_bias(const isi_prior_w *w, const isi_prior_state *state, const isi_prior_code_bias *bias,
+                              int p_begin, int p_end, float temperature, int top_k, float top_p, void *stream);
+int isi_prior_sample_run_rows_bias(const isi_prior_w *w, const isi_prior_state *state, const isi_prior_rows *rows,
+                                   const isi_prior_code_bias *bias, int t_begin, int t_end, float temperature, int top_k,
+                                   float top_p, void *stream);
 
 /* ----------------------------------------------------------- quantization */
 

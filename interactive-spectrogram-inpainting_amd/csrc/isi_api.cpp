@@ -105,6 +105,7 @@ size_t isi_abi_struct_bytes(int which) {
     case 10: return sizeof(isi_prior_state);
     case 12: return sizeof(isi_reduce_job);
     case 13: return sizeof(isi_prior_rows);
+    case 14: return sizeof(isi_prior_code_bias);
     default: return 0;
   }
 }
@@ -357,6 +358,12 @@ int isi_sample_row_f32(const float *logits, int stride, int rows, int n, float t
                        float top_p, const float *u, int64_t *out, float *filtered, void *stream) {
   return sample_row_f32(logits, stride, rows, n, temperature, top_k, top_p, u, out, filtered, S(stream));
 }
+int isi_sample_row_bias_f32(const float *logits, int stride, int rows, int n, float temperature, int top_k, float top_p,
+                            const float *u, int64_t *out, float *filtered, const float *bias, int bias_stride,
+                            int bias_count, const int32_t *bias_row, void *stream) {
+  return sample_row_bias_f32(logits, stride, rows, n, temperature, top_k, top_p, u, out, filtered, bias, bias_stride,
+                             bias_count, bias_row, S(stream));
+}
 int isi_sample_row_log_prob_f32(const float *logits, int stride, int rows, int n, float temperature, int top_k,
                                 float top_p, const float *u, int64_t *out, float *log_prob, void *stream) {
   return sample_row_log_prob_f32(logits, stride, rows, n, temperature, top_k, top_p, u, out, log_prob, S(stream));
@@ -378,6 +385,15 @@ int isi_prior_sample_run(const isi_prior_w *w, const isi_prior_state *state, int
 int isi_prior_sample_run_rows(const isi_prior_w *w, const isi_prior_state *state, const isi_prior_rows *rows, int t_begin,
                               int t_end, float temperature, int top_k, float top_p, void *stream) {
   return prior_sample_run_rows(w, state, rows, t_begin, t_end, temperature, top_k, top_p, S(stream));
+}
+int isi_prior_sample_run_bias(const isi_prior_w *w, const isi_prior_state *state, const isi_prior_code_bias *bias, int p_begin,
+                              int p_end, float temperature, int top_k, float top_p, void *stream) {
+  return prior_sample_run(w, state, p_begin, p_end, temperature, top_k, top_p, S(stream), bias);
+}
+int isi_prior_sample_run_rows_bias(const isi_prior_w *w, const isi_prior_state *state, const isi_prior_rows *rows,
+                                   const isi_prior_code_bias *bias, int t_begin, int t_end, float temperature, int top_k,
+                                   float top_p, void *stream) {
+  return prior_sample_run_rows(w, state, rows, t_begin, t_end, temperature, top_k, top_p, S(stream), bias);
 }
 
 size_t isi_conv_wgrad_workspace_floats(int Cout, int K, int M, int nphase) {

@@ -134,9 +134,28 @@ struct SampleRows {
   const float *top_p;
   int S;
 };
+// logit bias (isi_prior_code_bias, isi_sample_row_bias_f32): the launch row at token i of its sequence -- the token the
+// commit computes, position - i_off; 0 without a commit -- adds table[index[row * index_stride + i], 0:n] to its logits
+// before temperature and filters.  index == nullptr: table row 0 on every row.  An index outside [0, count), or a token
+// outside [0, S), means no bias and reads nothing from the table.  -inf bans a class.
+struct SampleBias {
+  const float *table; int table_stride;   // [count, table_stride], table_stride >= n
+  int count;
+  const int *index; int index_stride;     // [rows, S] (index_stride = S) or [S] shared by every row (index_stride = 0)
+  int S;
+};
+// (what the draw kernel's BIAS instantiations receive in place of SampleRows: the others take the bytes they always took)
+struct SampleRowsBias : SampleRows {
+  SampleBias bias;
+};
 int sample_row_commit_f32(const float *logits, int stride, int rows, int n, float temperature, int top_k, float top_p,
                           const float *u, int64_t *out, float *filtered, const int *pos, int pos_off,
-                          const SampleCommit &cm, hipStream_t stream, const SampleRows *ragged = nullptr);
+                          const SampleCommit &cm, hipStream_t stream, const SampleRows *ragged = nullptr,
+                          const SampleBias *bias = nullptr);
+// isi_sample_row_f32 with bias[bias_row[row], 0:n] (bias_row == nullptr: row 0) added to every row's logits
+int sample_row_bias_f32(const float *logits, int stride, int rows, int n, float temperature, int top_k, float top_p,
+                        const float *u, int64_t *out, float *filtered, const float *bias, int bias_stride, int bias_count,
+                        const int32_t *bias_row, hipStream_t stream);
 int sample_row_pos_f32(const float *logits, int stride, int rows, int n, float temperature, int top_k, float top_p,
                        const float *u, int64_t *out, float *filtered, const int *pos, int pos_off,
                        hipStream_t stream);
@@ -169,10 +188,12 @@ int decode_stage_f32(const float *x, int x_stride, const float *ln_g, const floa
                      const float *res, int res_stride, const float *res_g, const float *res_b, float *out, int out_stride,
                      int M, int N, int K, int relu, float eps, float *workspace, size_t workspace_floats, hipStream_t st);
 size_t prior_decode_scratch_floats(const isi_prior_w *w, int B);
+// bias: isi_prior_sample_run_bias / isi_prior_sample_run_rows_bias; nullptr or a zeroed struct: off
 int prior_sample_run(const isi_prior_w *w, const isi_prior_state *s, int p_begin, int p_end, float temperature,
-                     int top_k, float top_p, hipStream_t stream);
+                     int top_k, float top_p, hipStream_t stream, const isi_prior_code_bias *bias = nullptr);
 int prior_sample_run_rows(const isi_prior_w *w, const isi_prior_state *s, const isi_prior_rows *rows, int t_begin, int t_end,
-                          float temperature, int top_k, float top_p, hipStream_t stream);
+                          float temperature, int top_k, float top_p, hipStream_t stream,
+                          const isi_prior_code_bias *bias = nullptr);
 
 bool gemm_split_applicable(int M, int N, int K, int split_mode);
 // Optional extras of gemm_split_f32: a batch of nz independent products (grid y; element strides between them) and a

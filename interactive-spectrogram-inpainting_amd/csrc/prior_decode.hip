@@ -1201,7 +1201,7 @@ struct DecodeGraphs {
 static std::mutex &decode_graph_mutex() { static std::mutex m; return m; }
 // (called with the mutex held)  nullptr: no device / allocation failure -- the caller then launches directly
 static DecodeGraphs *decode_graphs_for(const isi_prior_w *w, const isi_prior_state *s, const isi_prior_rows *rows,
-                                       float temperature, int top_k, float top_p, int W) {
+                                       const isi_prior_code_bias *cb, float temperature, int top_k, float top_p, int W) {
   static std::vector<DecodeGraphs *> cache;
   static uint64_t clock_ = 0;
   int device = -1;
@@ -1223,6 +1223,11 @@ static DecodeGraphs *decode_graphs_for(const isi_prior_w *w, const isi_prior_sta
     const size_t at = key.size();
     key.resize(at + sizeof(isi_prior_rows));
     std::memcpy(key.data() + at, &rk, sizeof(isi_prior_rows));
+  }
+  if (cb) {                                            // a code bias: its pointers and sizes (the contents are read at replay)
+    const size_t at = key.size();
+    key.resize(at + sizeof(isi_prior_code_bias));
+    std::memcpy(key.data() + at, cb, sizeof(isi_prior_code_bias));
   }
   for (DecodeGraphs *g : cache)
     if (g->key == key) { g->used = ++clock_; return g; }
@@ -1250,15 +1255,28 @@ static DecodeGraphs *decode_graphs_for(const isi_prior_w *w, const isi_prior_sta
   return g;
 }
 
+// isi_prior_code_bias: both pointers or neither, a positive row count, one index row or one per batch row
+static int check_code_bias(const isi_prior_code_bias *cb, int B) {
+  if (!cb) return ISI_OK;
+  if ((cb->code_bias != nullptr) != (cb->code_bias_index != nullptr))
+    return invalid("prior_sample_run: code_bias and code_bias_index go together");
+  if (!cb->code_bias) return ISI_OK;
+  if (cb->code_bias_count <= 0) return invalid("prior_sample_run: code_bias_count must be positive");
+  if (cb->code_bias_batch != 1 && cb->code_bias_batch != B) return invalid("prior_sample_run: code_bias_batch must be 1 or B");
+  return ISI_OK;
+}
+
 // rows == nullptr: isi_prior_sample_run, p_begin / p_end are positions.  rows != nullptr: isi_prior_sample_run_rows, they
 // are steps of the plan (validated by the caller) and every position-dependent address is the row's own
 static int sample_run_impl(const isi_prior_w *w, const isi_prior_state *s, const isi_prior_rows *rows, int p_begin, int p_end,
-                           float temperature, int top_k, float top_p, hipStream_t st) {
+                           float temperature, int top_k, float top_p, hipStream_t st, const isi_prior_code_bias *cb) {
   const bool rag = rows != nullptr;
   if (!w || !s) return invalid("prior_sample_run: null pointer");
   if (w->n_layers <= 0 || w->n_layers > ISI_MAX_LAYERS) return invalid("prior_sample_run: bad layer count");
   if (s->B <= 0 || s->B > 256) return unsupported("prior_sample_run: batch size must be 1..256");
   if (p_begin < 0 || p_end > (rag ? rows->n_steps : s->S_t) || p_begin > p_end) return invalid("prior_sample_run: bad position range");
+  if (int rc = check_code_bias(cb, s->B)) return rc;
+  if (cb && !cb->code_bias) cb = nullptr;               // a zeroed struct: off
   const bool single_source = s->cross_out != nullptr;     // memory_kv is not read then
   if (!s->x_seq || !s->kv_cache || (!single_source && !s->memory_kv) || !s->codes || (!rag && !s->mask) || !s->uniforms ||
       !s->scratch)
@@ -1433,9 +1451,13 @@ static int sample_run_impl(const isi_prior_w *w, const isi_prior_state *s, const
                             s->token_log_probs};
       SampleRows sr{row_pos, rag ? rows->commit + (p < 0 ? 0 : (size_t)p * B) : nullptr, rag ? rows->temperature : nullptr,
                     rag ? rows->top_k : nullptr, rag ? rows->top_p : nullptr, s->S};
+      // (a code bias: the instantiation that adds the token's bias row to the logits)
+      SampleBias sb{nullptr, w->n_class, 0, nullptr, 0, s->S};
+      if (cb) sb = SampleBias{cb->code_bias, w->n_class, cb->code_bias_count, cb->code_bias_index,
+                              cb->code_bias_batch == 1 ? 0 : s->S, s->S};
       if ((rc = sample_row_commit_f32(logits, w->n_class, B, w->n_class, temperature, top_k, top_p,
                                       (p < 0 || rag) ? s->uniforms : s->uniforms + (size_t)(p - i_off) * B, sampled, nullptr,
-                                      pos_arg, i_off, cm, q_st, rag ? &sr : nullptr)))
+                                      pos_arg, i_off, cm, q_st, rag ? &sr : nullptr, cb ? &sb : nullptr)))
         return rc;
       if (fold_advance) return ISI_OK;
     }
@@ -1477,7 +1499,7 @@ static int sample_run_impl(const isi_prior_w *w, const isi_prior_state *s, const
     // point.  At most kDecodeGraphCacheMax argument sets are kept; the least recently used one is dropped once the event
     // recorded behind its last replay has passed.
     std::lock_guard<std::mutex> lock(decode_graph_mutex());
-    DecodeGraphs *G = decode_graphs_for(w, s, rows, temperature, top_k, top_p, W);
+    DecodeGraphs *G = decode_graphs_for(w, s, rows, cb, temperature, top_k, top_p, W);
     hipStream_t cap = nullptr;
     bool ok = G != nullptr;
     auto build = [&](int k) -> bool {      // k = 1: every position of the window samples
@@ -1524,15 +1546,16 @@ static int sample_run_impl(const isi_prior_w *w, const isi_prior_state *s, const
 }
 
 int prior_sample_run(const isi_prior_w *w, const isi_prior_state *s, int p_begin, int p_end, float temperature,
-                     int top_k, float top_p, hipStream_t st) {
-  return sample_run_impl(w, s, nullptr, p_begin, p_end, temperature, top_k, top_p, st);
+                     int top_k, float top_p, hipStream_t st, const isi_prior_code_bias *cb) {
+  return sample_run_impl(w, s, nullptr, p_begin, p_end, temperature, top_k, top_p, st, cb);
 }
 
 // Ragged batches: the plan is checked on the host, from its host copies, before anything is launched.
 int prior_sample_run_rows(const isi_prior_w *w, const isi_prior_state *s, const isi_prior_rows *rows, int t_begin, int t_end,
-                          float temperature, int top_k, float top_p, hipStream_t st) {
+                          float temperature, int top_k, float top_p, hipStream_t st, const isi_prior_code_bias *cb) {
   if (!w || !s || !rows) return invalid("prior_sample_run_rows: null pointer");
   if (s->B <= 0 || s->B > 256) return unsupported("prior_sample_run_rows: batch size must be 1..256");
+  if (int rc = check_code_bias(cb, s->B)) return rc;
   if (s->memory_shared)
     return unsupported("prior_sample_run_rows: memory_shared (one source for all rows) is not built for ragged plans -- rows of "
                        "a plan are independent requests");
@@ -1553,7 +1576,7 @@ int prior_sample_run_rows(const isi_prior_w *w, const isi_prior_state *s, const 
         return invalid("prior_sample_run_rows: a commit outside the token range [0, S)");
     }
   }
-  return sample_run_impl(w, s, rows, t_begin, t_end, temperature, top_k, top_p, st);
+  return sample_run_impl(w, s, rows, t_begin, t_end, temperature, top_k, top_p, st, cb);
 }
 
 }  // namespace isi

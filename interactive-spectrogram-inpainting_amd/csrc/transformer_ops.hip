@@ -900,8 +900,13 @@ __device__ __forceinline__ float block_token_log_prob(const float *__restrict__ 
 }
 
 // LP: the commit also stores the model's log-probability of the token (SampleCommit.log_probs); the instantiations
-// without it take the commit arguments they always took (SampleCommitCore) and are instruction for instruction what they were
-template <bool RAG = false, bool LP = false>
+// without it take the commit arguments they always took (SampleCommitCore) and are instruction for instruction what they were.
+// BIAS: a row of a bias table, chosen per launch row and token (SampleBias behind the SampleRows bytes), is added to the
+// logits before temperature and filters -- two separately rounded fp32 operations, (logit + bias) * inv_temperature, so the
+// float64 specification of the draw holds unchanged on float32(logits + bias).  The sort, the filters, the scans, the bidding
+// rule and the fallback are untouched; a -inf bias takes the path of a -inf logit and is never drawn.  The LP value stays the
+// MODEL's: block_token_log_prob reads the raw row.  The instantiations without BIAS take the bytes they always took.
+template <bool RAG = false, bool LP = false, bool BIAS = false>
 __global__ __launch_bounds__(1024) void sample_row_f32_kernel(const float *__restrict__ logits, int stride,
                                                               int n, float inv_temperature, int top_k,
                                                               float top_p, const float *__restrict__ u,
@@ -909,7 +914,7 @@ __global__ __launch_bounds__(1024) void sample_row_f32_kernel(const float *__res
                                                               float *__restrict__ filtered,
                                                               const int *__restrict__ pos, int pos_off,
                                                               const std::conditional_t<LP, SampleCommit, SampleCommitCore> cm,
-                                                              const SampleRows rg) {
+                                                              const std::conditional_t<BIAS, SampleRowsBias, SampleRows> rg) {
   float ur = 0.f;          // this row's uniform
   int rp = 0;              // RAG: the row's position
   bool commit = true;
@@ -933,7 +938,21 @@ __global__ __launch_bounds__(1024) void sample_row_f32_kernel(const float *__res
   __shared__ int sh_i, sh_last;
   const int tid = threadIdx.x, np = blockDim.x, row = blockIdx.x;
   const float NEGI = -INFINITY;
-  const float lg = tid < n ? logits[(size_t)row * stride + tid] * inv_temperature : NEGI;
+  float lg;
+  if constexpr (BIAS) {    // (the bias row is uniform over the workgroup)
+    const SampleBias &bs = rg.bias;
+    const int i = (RAG ? rp : pos ? *pos : cm.p_value) - cm.i_off;     // the token the commit writes
+    int br = 0;
+    if (bs.index) br = (i >= 0 && i < bs.S) ? bs.index[(size_t)row * bs.index_stride + i] : -1;
+    const float *brow = (br >= 0 && br < bs.count) ? bs.table + (size_t)br * bs.table_stride : nullptr;
+    lg = NEGI;
+    if (tid < n) {
+      const float x = logits[(size_t)row * stride + tid];
+      lg = __fmul_rn(brow ? __fadd_rn(x, brow[tid]) : x, inv_temperature);
+    }
+  } else {
+    lg = tid < n ? logits[(size_t)row * stride + tid] * inv_temperature : NEGI;
+  }
   float vmax;
   bool kp = tid < n;
   if (top_k > 0 || top_p > 0.f) {
@@ -1052,8 +1071,10 @@ int sample_row_pos_f32(const float *logits, int stride, int rows, int n, float t
 
 int sample_row_commit_f32(const float *logits, int stride, int rows, int n, float temperature, int top_k, float top_p,
                           const float *u, int64_t *out, float *filtered, const int *pos, int pos_off,
-                          const SampleCommit &cm, hipStream_t stream, const SampleRows *ragged) {
+                          const SampleCommit &cm, hipStream_t stream, const SampleRows *ragged, const SampleBias *bias) {
   if (!logits || !u || !out || rows <= 0 || n <= 0 || temperature <= 0.f) return invalid("sample_row: bad argument");
+  if (bias && (!bias->table || bias->count <= 0 || bias->table_stride < n || bias->index_stride < 0 || bias->S <= 0))
+    return invalid("sample_row: bad bias table");
   if (n > 1024) return unsupported("sample_row: at most 1024 classes");
   if (cm.advance && (rows != 1 || !cm.table)) return invalid("sample_row: the position counter is advanced by a one-row commit only");
   if (cm.log_probs && !cm.table) return invalid("sample_row: log-probabilities are stored by a commit only");
@@ -1063,7 +1084,17 @@ int sample_row_commit_f32(const float *logits, int stride, int rows, int n, floa
   while (np < n) np <<= 1;
   if (ragged) {
     if (!ragged->row_pos || !ragged->commit || !cm.table || cm.advance) return invalid("sample_row: bad ragged commit");
-    if (lp)
+    if (bias) {
+      SampleRowsBias rb;
+      static_cast<SampleRows &>(rb) = *ragged;
+      rb.bias = *bias;
+      if (lp)
+        hipLaunchKernelGGL((sample_row_f32_kernel<true, true, true>), dim3(rows), dim3(np), 0, stream, logits, stride, n,
+                           1.0f / temperature, top_k, top_p, u, out, filtered, pos, pos_off, cm, rb);
+      else
+        hipLaunchKernelGGL((sample_row_f32_kernel<true, false, true>), dim3(rows), dim3(np), 0, stream, logits, stride, n,
+                           1.0f / temperature, top_k, top_p, u, out, filtered, pos, pos_off, core, rb);
+    } else if (lp)
       hipLaunchKernelGGL((sample_row_f32_kernel<true, true>), dim3(rows), dim3(np), 0, stream, logits, stride, n,
                          1.0f / temperature, top_k, top_p, u, out, filtered, pos, pos_off, cm, *ragged);
     else
@@ -1073,7 +1104,17 @@ int sample_row_commit_f32(const float *logits, int stride, int rows, int n, floa
   }
   SampleRows none_rows;
   memset(&none_rows, 0, sizeof none_rows);
-  if (lp)
+  if (bias) {
+    SampleRowsBias rb;
+    static_cast<SampleRows &>(rb) = none_rows;
+    rb.bias = *bias;
+    if (lp)
+      hipLaunchKernelGGL((sample_row_f32_kernel<false, true, true>), dim3(rows), dim3(np), 0, stream, logits, stride, n,
+                         1.0f / temperature, top_k, top_p, u, out, filtered, pos, pos_off, cm, rb);
+    else
+      hipLaunchKernelGGL((sample_row_f32_kernel<false, false, true>), dim3(rows), dim3(np), 0, stream, logits, stride, n,
+                         1.0f / temperature, top_k, top_p, u, out, filtered, pos, pos_off, core, rb);
+  } else if (lp)
     hipLaunchKernelGGL((sample_row_f32_kernel<false, true>), dim3(rows), dim3(np), 0, stream, logits, stride, n,
                        1.0f / temperature, top_k, top_p, u, out, filtered, pos, pos_off, cm, none_rows);
   else
@@ -1095,6 +1136,20 @@ int sample_row_log_prob_f32(const float *logits, int stride, int rows, int n, fl
   cm.codes_stride = 1;
   cm.log_probs = log_prob;
   return sample_row_commit_f32(logits, stride, rows, n, temperature, top_k, top_p, u, out, nullptr, nullptr, 0, cm, stream);
+}
+
+// The draw with a logit bias and no commit: every row stands at token 0 of a one-token sequence, bias_row is its index row.
+int sample_row_bias_f32(const float *logits, int stride, int rows, int n, float temperature, int top_k, float top_p,
+                        const float *u, int64_t *out, float *filtered, const float *bias, int bias_stride, int bias_count,
+                        const int32_t *bias_row, hipStream_t stream) {
+  if (!bias || bias_count <= 0) return invalid("sample_row_bias: no bias table");
+  if (bias_stride < n) return invalid("sample_row_bias: bias_stride < n");
+  if (stride < n) return invalid("sample_row_bias: stride < n");
+  SampleCommit none;
+  memset(&none, 0, sizeof none);
+  const SampleBias sb{bias, bias_stride, bias_count, bias_row, 1, 1};
+  return sample_row_commit_f32(logits, stride, rows, n, temperature, top_k, top_p, u, out, filtered, nullptr, 0, none, stream,
+                               nullptr, &sb);
 }
 
 // ------------------------------------------------------------------ log-probabilities of given codes

@@ -28,7 +28,7 @@ from typing import List, Mapping, Optional, Sequence, Tuple
 
 import torch
 
-from sample import codemap_statistics, sample_model
+from sample import _code_bias_rows, codemap_statistics, sample_model
 
 
 def make_time_indexes(start_index: int, codemap_duration: int, transformer_duration: int) -> List[int]:
@@ -62,6 +62,27 @@ def _check_score_options(return_scores, sort_by_likelihood, uniform_sampling) ->
         raise ValueError("return_scores: uniform_sampling draws from no model distribution, there is no likelihood to report")
 
 
+# Per-layer steering of what may be drawn (`sample_model`'s allowed_codes / code_bias / code_bias_map): a request changes up to
+# two layers, each with its own classes, so the options are given per layer -- allowed_codes_top, code_bias_bottom, ... --
+# with code_bias_map_* [F, W] or [1, F, W] over the model window in that layer's resolution.
+_CODE_BIAS_OPTIONS = ('allowed_codes', 'code_bias', 'code_bias_map')
+_CODE_BIAS_KEYWORDS = frozenset(f"{name}_{layer}" for name in _CODE_BIAS_OPTIONS for layer in ('top', 'bottom'))
+
+
+def _split_code_bias(kwargs: Mapping, uniform_sampling: bool = False):
+    """(the other keywords, {'top': sample_model's options for the top prior, 'bottom': ...}) of a keyword mapping."""
+    plain = set(kwargs) & set(_CODE_BIAS_OPTIONS)
+    if plain:
+        raise TypeError(f"{sorted(plain)}: the two layers have their own classes -- give "
+                        f"{', '.join(sorted(f'{n}_top / {n}_bottom' for n in plain))}")
+    rest = {k: v for k, v in kwargs.items() if k not in _CODE_BIAS_KEYWORDS}
+    bias = {layer: {name: kwargs[f"{name}_{layer}"] for name in _CODE_BIAS_OPTIONS if kwargs.get(f"{name}_{layer}") is not None}
+            for layer in ('top', 'bottom')}
+    if uniform_sampling and (bias['top'] or bias['bottom']):
+        raise ValueError("uniform_sampling draws from no model distribution: allowed_codes / code_bias do not apply")
+    return rest, bias
+
+
 @torch.no_grad()
 def timerange_change(transformer_top, transformer_bottom, top_code: torch.Tensor, bottom_code: torch.Tensor,
                      mask: torch.Tensor, layer: str, start_index_top: int, temperature: float,
@@ -80,9 +101,14 @@ def timerange_change(transformer_top, transformer_bottom, top_code: torch.Tensor
     return_scores: the result is (top, bottom, log_likelihood) -- log_likelihood float32 [N] ([1] without num_variations):
     the sum of the sampled tokens' model log-probabilities (`sample_model(return_log_probs=True)`) over the stages that ran,
     top then bottom.  sort_by_likelihood (needs return_scores): the variations in descending order of that score, ties in
-    their original order.  Uniform sampling draws from no model distribution: it has no score (ValueError)."""
+    their original order.  Uniform sampling draws from no model distribution: it has no score (ValueError).
+    allowed_codes_top / allowed_codes_bottom, code_bias_top / code_bias_bottom (with code_bias_map_top / code_bias_map_bottom
+    over the window): `sample_model`'s options for the stage of that layer -- e.g. allowed_codes_top =
+    `sample.codes_in_use(other_top, n)` regenerates the region from another sound's palette."""
     _check_score_options(return_scores, sort_by_likelihood, uniform_sampling)
+    sampling_kwargs, bias = _split_code_bias(sampling_kwargs, uniform_sampling)
     if num_variations is not None:
+        sampling_kwargs = dict(sampling_kwargs, _code_bias=bias)
         return _timerange_change_variations(transformer_top, transformer_bottom, top_code, bottom_code, mask, layer,
                                             start_index_top, temperature, class_conditioning_top,
                                             class_conditioning_bottom, device, uniform_sampling, generator, kv_cache_dtype,
@@ -98,13 +124,13 @@ def timerange_change(transformer_top, transformer_bottom, top_code: torch.Tensor
                   kv_cache_dtype=kv_cache_dtype, **sampling_kwargs)
     scores = []                        # per stage: [1] float64 sums of the sampled tokens' log-probabilities
 
-    def resample(model, condition, initial, m, cls, ti_src, ti_tgt):
+    def resample(model, condition, initial, m, cls, ti_src, ti_tgt, steer):
         if uniform_sampling:
             rnd = torch.randint(0, model.n_class_target, initial.shape, generator=generator).to(initial.device)
             return torch.where(m, rnd, initial)
         out = sample_model(model=model, condition=condition, codemap_size=model.shape, class_conditioning=cls,
                            initial_code=initial, mask=m, time_indexes_source=ti_src, time_indexes_target=ti_tgt,
-                           return_log_probs=return_scores, **common)
+                           return_log_probs=return_scores, **steer, **common)
         if return_scores:
             scores.append(_stage_score(out[1]))
             return out[0]
@@ -113,15 +139,15 @@ def timerange_change(transformer_top, transformer_bottom, top_code: torch.Tensor
     top_code, bottom_code = top_code.clone(), bottom_code.clone()
     if layer == 'bottom':
         bottom_code[..., s_bot:e_bot] = resample(transformer_bottom, top_frame, bottom_frame, mask,
-                                                 class_conditioning_bottom, ti_top, ti_bottom)
+                                                 class_conditioning_bottom, ti_top, ti_bottom, bias['bottom'])
     elif layer == 'top':
         condition = top_frame if transformer_top.self_conditional_model else None
-        new_top = resample(transformer_top, condition, top_frame, mask, class_conditioning_top, ti_top, ti_top)
+        new_top = resample(transformer_top, condition, top_frame, mask, class_conditioning_top, ti_top, ti_top, bias['top'])
         top_code[..., s_top:e_top] = new_top
         ratio_f = transformer_bottom.shape[0] // transformer_top.shape[0]
         mask_bottom = mask.repeat_interleave(ratio_f, -2).repeat_interleave(ratio_t, -1)
         bottom_code[..., s_bot:e_bot] = resample(transformer_bottom, new_top, bottom_frame, mask_bottom,
-                                                 class_conditioning_bottom, ti_top, ti_bottom)
+                                                 class_conditioning_bottom, ti_top, ti_bottom, bias['bottom'])
     else:
         raise ValueError(f"unknown layer {layer}")
     if return_scores:
@@ -209,7 +235,7 @@ def resample_unlikely(transformer_top, transformer_bottom, top_code: torch.Tenso
         raise ValueError("resample_unlikely: give exactly one of fraction and log_prob_below")
     kw = timerange_change_kwargs
     _check_score_options(kw.get('return_scores'), kw.get('sort_by_likelihood'), kw.get('uniform_sampling'))
-    unknown = set(kw) - _TIMERANGE_CHANGE_KEYWORDS      # (checked here: an empty selection never reaches timerange_change)
+    unknown = set(kw) - _TIMERANGE_CHANGE_KEYWORDS - _CODE_BIAS_KEYWORDS      # (checked here: an empty selection never reaches timerange_change)
     if unknown:
         raise TypeError(f"resample_unlikely: unexpected keyword argument(s) {sorted(unknown)}")
     stats = uncertainty(transformer_top, transformer_bottom, top_code, bottom_code, mask, layer, start_index_top,
@@ -263,6 +289,8 @@ def _timerange_change_variations(transformer_top, transformer_bottom, top_code, 
     mask = mask.to(device)
     ti_top = make_time_indexes(s_top, top_code.shape[-1], transformer_top.shape[-1])
     ti_bottom = make_time_indexes(s_bot, bottom_code.shape[-1], transformer_bottom.shape[-1])
+    sampling_kwargs = dict(sampling_kwargs)
+    bias = sampling_kwargs.pop('_code_bias')           # timerange_change's per-layer options
     common = dict(device=device, temperature=temperature, generator=generator, kv_cache_dtype=kv_cache_dtype,
                   return_log_probs=return_scores, **sampling_kwargs)
     scores = []
@@ -273,24 +301,24 @@ def _timerange_change_variations(transformer_top, transformer_bottom, top_code, 
             return out[0]
         return out
 
-    def variations(model, condition, initial, m, cls, ti_src, ti_tgt):      # N rows over one request
+    def variations(model, condition, initial, m, cls, ti_src, ti_tgt, steer):      # N rows over one request
         if uniform_sampling:
             rnd = torch.randint(0, model.n_class_target, (N,) + tuple(initial.shape[1:]), generator=generator).to(initial.device)
             return torch.where(m, rnd, initial)
         return scored(sample_model(model=model, batch_size=1, num_variations=N, condition=condition, codemap_size=model.shape,
                                    class_conditioning=cls, initial_code=initial, mask=m, time_indexes_source=ti_src,
-                                   time_indexes_target=ti_tgt, **common))
+                                   time_indexes_target=ti_tgt, **steer, **common))
 
     top_out = top_code.repeat(N, 1, 1)
     bottom_out = bottom_code.repeat(N, 1, 1)
     if layer == 'bottom':
         bottom_out[..., s_bot:e_bot] = variations(transformer_bottom, top_frame, bottom_frame, mask,
-                                                  class_conditioning_bottom, ti_top, ti_bottom)
+                                                  class_conditioning_bottom, ti_top, ti_bottom, bias['bottom'])
         if return_scores:
             return _ranked(top_out, bottom_out, scores, sort_by_likelihood)
         return top_out, bottom_out
     condition = top_frame if transformer_top.self_conditional_model else None
-    new_top = variations(transformer_top, condition, top_frame, mask, class_conditioning_top, ti_top, ti_top)
+    new_top = variations(transformer_top, condition, top_frame, mask, class_conditioning_top, ti_top, ti_top, bias['top'])
     top_out[..., s_top:e_top] = new_top
     ratio_f = transformer_bottom.shape[0] // transformer_top.shape[0]
     mask_bottom = mask.repeat_interleave(ratio_f, -2).repeat_interleave(ratio_t, -1)
@@ -303,7 +331,7 @@ def _timerange_change_variations(transformer_top, transformer_bottom, top_code, 
         bottom_out[..., s_bot:e_bot] = scored(sample_model(
             model=transformer_bottom, batch_size=N, condition=new_top, codemap_size=transformer_bottom.shape,
             class_conditioning=class_conditioning_bottom, initial_code=initial, mask=mask_bottom,
-            time_indexes_source=ti_top, time_indexes_target=ti_bottom, **common))
+            time_indexes_source=ti_top, time_indexes_target=ti_bottom, **bias['bottom'], **common))
     if return_scores:
         return _ranked(top_out, bottom_out, scores, sort_by_likelihood)
     return top_out, bottom_out
@@ -321,7 +349,9 @@ def timerange_change_batch(transformer_top, transformer_bottom, requests: Sequen
     through the top prior together, then every request through the bottom prior together (a top request with the mask
     up-sampled over its new top map).  A request is a mapping with the arguments of `timerange_change` -- top_code,
     bottom_code, mask, layer, start_index_top, temperature, class_conditioning_top, class_conditioning_bottom and
-    optionally top_k_sampling_k, top_p_sampling_p, uniform_sampling -- and its own `generator`, from which its uniforms
+    optionally top_k_sampling_k, top_p_sampling_p, uniform_sampling, allowed_codes_top / allowed_codes_bottom, code_bias_top /
+    code_bias_bottom, code_bias_map_top / code_bias_map_bottom (the requests' distinct tables are stacked into one and a
+    per-row map selects each request's rows; a request without them draws unbiased) -- and its own `generator`, from which its uniforms
     are drawn in the order `timerange_change` draws them (top stage, then bottom): result r equals `timerange_change` of
     request r alone with an equally seeded generator.  Returns one (top, bottom) pair per request; with return_scores one
     (top, bottom, log_likelihood [1]) triple, `timerange_change(return_scores=True)`'s (a request with uniform_sampling
@@ -335,14 +365,39 @@ def timerange_change_batch(transformer_top, transformer_bottom, requests: Sequen
             raise ValueError("return_scores: uniform_sampling draws from no model distribution, there is no likelihood to report")
         (s_top, e_top), (s_bot, e_bot), ratio_t = _windows(r['top_code'], r['bottom_code'], transformer_top,
                                                             transformer_bottom, r['start_index_top'])
-        jobs.append(dict(req=r, top=r['top_code'].clone(), bottom=r['bottom_code'].clone(), s_top=s_top, e_top=e_top,
+        _, steer = _split_code_bias(r, r.get('uniform_sampling', False))
+        steer = {'top': _code_bias_rows(transformer_top, 1, **{n: steer['top'].get(n) for n in _CODE_BIAS_OPTIONS}),
+                 'bottom': _code_bias_rows(transformer_bottom, 1, **{n: steer['bottom'].get(n) for n in _CODE_BIAS_OPTIONS})}
+        jobs.append(dict(req=r, steer=steer, top=r['top_code'].clone(), bottom=r['bottom_code'].clone(), s_top=s_top, e_top=e_top,
                          s_bot=s_bot, e_bot=e_bot, ratio_t=ratio_t, mask=r['mask'].to(device), g=r.get('generator'),
                          ti_top=make_time_indexes(s_top, r['top_code'].shape[-1], transformer_top.shape[-1]),
                          ti_bottom=make_time_indexes(s_bot, r['bottom_code'].shape[-1], transformer_bottom.shape[-1])))
 
+    def stacked_bias(model, batch, layer):      # one table of the batch's distinct tables, one map row per request
+        tables, offsets, maps, n_rows = [], [], [], 0
+        for j in batch:
+            table, m = j['steer'][layer]
+            if table is None:
+                maps.append(torch.full((1,) + tuple(model.shape), -1, dtype=torch.int64))
+                continue
+            same = [k for k, t in enumerate(tables) if t.shape == table.shape and torch.equal(t, table)]
+            if same:
+                off = offsets[same[0]]
+            else:
+                off = n_rows
+                tables.append(table)
+                offsets.append(off)
+                n_rows += table.shape[0]
+            m = torch.zeros((1,) + tuple(model.shape), dtype=torch.int64) if m is None else m
+            maps.append(torch.where(m >= 0, m + off, m))
+        if not tables:
+            return {}
+        return dict(code_bias=torch.cat(tables), code_bias_map=torch.cat(maps))
+
     def run(model, batch, condition, initial, masks, cls_key, ti_src, ti_tgt, uniforms):
         req = [j['req'] for j in batch]
         return sample_model(
+            **stacked_bias(model, batch, 'top' if cls_key == 'class_conditioning_top' else 'bottom'),
             model=model, device=device, batch_size=len(batch), codemap_size=model.shape,
             temperature=[float(q['temperature']) for q in req],
             condition=torch.cat(condition) if condition is not None else None,

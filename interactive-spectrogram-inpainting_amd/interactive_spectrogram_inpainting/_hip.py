@@ -145,6 +145,11 @@ class isi_prior_rows(C.Structure):
                 ("temperature", C.c_void_p), ("top_k", C.c_void_p), ("top_p", C.c_void_p), ("n_steps", C.c_int)]
 
 
+class isi_prior_code_bias(C.Structure):
+    _fields_ = [("code_bias", C.c_void_p), ("code_bias_index", C.c_void_p), ("code_bias_count", C.c_int),
+                ("code_bias_batch", C.c_int)]
+
+
 class isi_reduce_job(C.Structure):
     _fields_ = [("partial", C.c_void_p), ("out", C.c_void_p), ("n", C.c_int64), ("stride", C.c_int64),
                 ("nsplit", C.c_int32), ("accumulate", C.c_int32), ("vec", C.c_int32),
@@ -238,11 +243,19 @@ SIGNATURES = {
                                       C.c_int, _P]),
     "isi_sample_row_f32": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, _P, _P, _P,
                                      _P]),
+    "isi_sample_row_bias_f32": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, _P, _P, _P,
+                                          _P, C.c_int, C.c_int, _P, _P]),
     "isi_sample_row_log_prob_f32": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, _P, _P, _P,
                                               _P]),
     "isi_token_log_prob_f32": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "isi_token_stats_f32": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
     "isi_prior_decode_scratch_floats": (C.c_size_t, [C.POINTER(isi_prior_w), C.c_int]),
+    "isi_prior_sample_run_bias": (C.c_int, [C.POINTER(isi_prior_w), C.POINTER(isi_prior_state),
+                                            C.POINTER(isi_prior_code_bias), C.c_int, C.c_int, C.c_float, C.c_int,
+                                            C.c_float, _P]),
+    "isi_prior_sample_run_rows_bias": (C.c_int, [C.POINTER(isi_prior_w), C.POINTER(isi_prior_state),
+                                                 C.POINTER(isi_prior_rows), C.POINTER(isi_prior_code_bias), C.c_int,
+                                                 C.c_int, C.c_float, C.c_int, C.c_float, _P]),
     "isi_prior_sample_run": (C.c_int, [C.POINTER(isi_prior_w), C.POINTER(isi_prior_state), C.c_int, C.c_int,
                                        C.c_float, C.c_int, C.c_float, _P]),
     "isi_prior_sample_run_rows": (C.c_int, [C.POINTER(isi_prior_w), C.POINTER(isi_prior_state), C.POINTER(isi_prior_rows),

@@ -135,12 +135,16 @@ class NativeSampler:
 
     def __init__(self, model, memory: torch.Tensor, x_seq: torch.Tensor, codes: torch.Tensor,
                  mask_seq, uniforms: torch.Tensor, kv_cache_dtype: torch.dtype = torch.float32,
-                 shared_memory: bool = False, log_probs: bool = False):
+                 shared_memory: bool = False, log_probs: bool = False, code_bias: torch.Tensor = None,
+                 code_bias_index: torch.Tensor = None):
         """shared_memory: the B rows of x_seq are variations of ONE request -- memory is [S_src, 1, d], its projected keys /
         values (or the single-source table) are formed once at batch 1 and every row reads them
         (`isi_prior_state.memory_shared`).
         log_probs: the loop also stores the model's log-probability of every token it commits
-        (`isi_prior_state.token_log_probs`) into `self.log_probs` [B, S] float32, zero where nothing was sampled."""
+        (`isi_prior_state.token_log_probs`) into `self.log_probs` [B, S] float32, zero where nothing was sampled.
+        code_bias / code_bias_index: a float32 table [R, n_class] of logit bias rows (-inf bans a class) and an integer
+        index [S] or [1, S] (every row) or [B, S], in sequence order, of the table row each token is drawn with; -1: none
+        (`isi_prior_code_bias`, passed beside the state to `isi_prior_sample_run_bias`).  The sampler keeps both alive; their contents are read when the loop runs."""
         import ctypes as C
         kv_format = kv_cache_format(kv_cache_dtype)        # before anything is allocated
         self.kv_cache_dtype = kv_cache_dtype
@@ -232,6 +236,22 @@ class NativeSampler:
         if log_probs:
             self.log_probs = torch.zeros(B, codes.shape[1], dtype=torch.float32, device=dev)
             st.token_log_probs = self.log_probs.data_ptr()
+        self.code_bias = self.code_bias_index = self.bias = None
+        if (code_bias is None) != (code_bias_index is None):
+            raise ValueError("code_bias and code_bias_index go together")
+        if code_bias is not None:
+            S = codes.shape[1]
+            if code_bias.dim() != 2 or code_bias.shape[1] != w.n_class or code_bias.shape[0] < 1:
+                raise ValueError(f"code_bias {tuple(code_bias.shape)}: expected [R, {w.n_class}]")
+            index = code_bias_index.reshape(1, -1) if code_bias_index.dim() == 1 else code_bias_index
+            if index.dim() != 2 or index.shape[1] != S or index.shape[0] not in (1, B):
+                raise ValueError(f"code_bias_index {tuple(code_bias_index.shape)}: expected [{S}], [1, {S}] or [{B}, {S}]")
+            self.code_bias = code_bias.detach().to(device=dev, dtype=torch.float32).contiguous()
+            self.code_bias_index = index.to(device=dev, dtype=torch.int32).contiguous()
+            cb = _hip.isi_prior_code_bias()
+            cb.code_bias, cb.code_bias_index = self.code_bias.data_ptr(), self.code_bias_index.data_ptr()
+            cb.code_bias_count, cb.code_bias_batch = self.code_bias.shape[0], self.code_bias_index.shape[0]
+            self.bias = cb
         self.state = st
 
     @torch.no_grad()
@@ -270,6 +290,12 @@ class NativeSampler:
     @torch.no_grad()
     def run(self, p_begin: int, p_end: int, temperature: float, top_k: int, top_p: float) -> None:
         C, _hip = self._C, self._hip
+        if self.bias is not None:          # (without one: the entry and the launches it always took)
+            rc = _hip.lib().isi_prior_sample_run_bias(C.byref(self.w), C.byref(self.state), C.byref(self.bias), p_begin, p_end,
+                                                      float(temperature), int(top_k), float(top_p),
+                                                      C.c_void_p(_hip.stream_ptr(self.x_seq.device)))
+            _hip.check(rc, "isi_prior_sample_run_bias")
+            return
         rc = _hip.lib().isi_prior_sample_run(C.byref(self.w), C.byref(self.state), p_begin, p_end,
                                              float(temperature), int(top_k), float(top_p),
                                              C.c_void_p(_hip.stream_ptr(self.x_seq.device)))
@@ -307,6 +333,12 @@ class NativeSampler:
     def run_rows(self, t_begin: int, t_end: int, temperature: float, top_k: int, top_p: float) -> None:
         """Steps [t_begin, t_end) of the plan set by `plan_rows`; the scalars stand for rows without per-row values."""
         C, _hip = self._C, self._hip
+        if self.bias is not None:
+            rc = _hip.lib().isi_prior_sample_run_rows_bias(C.byref(self.w), C.byref(self.state), C.byref(self.rows),
+                                                           C.byref(self.bias), t_begin, t_end, float(temperature), int(top_k),
+                                                           float(top_p), C.c_void_p(_hip.stream_ptr(self.x_seq.device)))
+            _hip.check(rc, "isi_prior_sample_run_rows_bias")
+            return
         rc = _hip.lib().isi_prior_sample_run_rows(C.byref(self.w), C.byref(self.state), C.byref(self.rows), t_begin, t_end,
                                                   float(temperature), int(top_k), float(top_p),
                                                   C.c_void_p(_hip.stream_ptr(self.x_seq.device)))

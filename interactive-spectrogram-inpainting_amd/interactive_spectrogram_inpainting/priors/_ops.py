@@ -458,8 +458,11 @@ def rel_attention_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rel:
 
 
 def sample_rows(logits: torch.Tensor, temperature: float, top_k: int, top_p: float, u: torch.Tensor,
-                return_filtered: bool = False):
-    """logits [rows, n] -> int64 [rows] (and the filtered logits when asked)."""
+                return_filtered: bool = False, bias: torch.Tensor = None, bias_rows: torch.Tensor = None):
+    """logits [rows, n] -> int64 [rows] (and the filtered logits when asked).
+    bias: float32 [n] or [count, n] (any row stride >= n), added to the logits before temperature and filters
+    (`isi_sample_row_bias_f32`); -inf bans a class.  bias_rows: int [rows] -- the table row of every launch row, anything
+    outside [0, count) meaning no bias -- or None: table row 0 on every row."""
     _hip.require_gpu(logits, "logits")
     rows, n = logits.shape
     if logits.stride(1) != 1:
@@ -467,6 +470,27 @@ def sample_rows(logits: torch.Tensor, temperature: float, top_k: int, top_p: flo
     out = torch.empty(rows, dtype=torch.int64, device=logits.device)
     filt = torch.empty(rows, n, dtype=torch.float32, device=logits.device) if return_filtered else None
     u = u.to(device=logits.device, dtype=torch.float32).contiguous()
+    if bias is None and bias_rows is not None:
+        raise ValueError("sample_rows: bias_rows without a bias table")
+    if bias is not None:
+        if bias.dim() == 1:
+            bias = bias.unsqueeze(0)
+        if bias.dim() != 2 or bias.shape[1] != n or bias.shape[0] < 1 or bias.dtype != torch.float32:
+            raise ValueError(f"sample_rows: bias {tuple(bias.shape)} {bias.dtype} for {n} classes; expected float32 [count, {n}]")
+        _hip.require_gpu(bias, "bias")
+        if bias.stride(1) != 1 or (bias.shape[0] > 1 and bias.stride(0) < n):
+            bias = bias.contiguous()
+        if bias_rows is not None:
+            if bias_rows.numel() != rows:
+                raise ValueError(f"sample_rows: bias_rows {tuple(bias_rows.shape)} for {rows} rows")
+            bias_rows = bias_rows.to(device=logits.device, dtype=torch.int32).reshape(-1).contiguous()
+        rc = _hip.lib().isi_sample_row_bias_f32(logits.data_ptr(), logits.stride(0), rows, n, float(temperature),
+                                                int(top_k), float(top_p), u.data_ptr(), out.data_ptr(),
+                                                filt.data_ptr() if filt is not None else None, bias.data_ptr(),
+                                                max(bias.stride(0), n) if bias.shape[0] > 1 else n, bias.shape[0],
+                                                bias_rows.data_ptr() if bias_rows is not None else None, _s(logits))
+        _hip.check(rc, "isi_sample_row_bias_f32")
+        return (out, filt) if return_filtered else out
     rc = _hip.lib().isi_sample_row_f32(logits.data_ptr(), logits.stride(0), rows, n, float(temperature),
                                        int(top_k), float(top_p), u.data_ptr(), out.data_ptr(),
                                        filt.data_ptr() if filt is not None else None, _s(logits))

@@ -88,6 +88,85 @@ def _ragged_plan(mask_rows: np.ndarray, i_off: int):
     return pos, commit, prefill
 
 
+def codes_in_use(codemaps, n_class: int) -> torch.Tensor:
+    """bool [n_class]: the classes that occur in a codemap or in any of several (a tensor of any shape, or a collection of
+    tensors) -- the codes an encoder has produced, or the palette of a sound; `sample_model(allowed_codes=...)` takes it as
+    it is.  Values outside [0, n_class) (the top prior's mask token) are not classes and are left out."""
+    maps = [codemaps] if torch.is_tensor(codemaps) else list(codemaps)
+    used = torch.zeros(int(n_class), dtype=torch.bool)
+    for m in maps:
+        v = torch.as_tensor(m).reshape(-1).long().cpu()
+        used[v[(v >= 0) & (v < n_class)]] = True
+    return used
+
+
+def _code_bias_rows(model, batch_size: int, code_bias, code_bias_map, allowed_codes):
+    """The options `code_bias` / `code_bias_map` / `allowed_codes` of `sample_model`, checked: a float32 table [R, n_class]
+    and an int64 map [1 or B, F, T] of its rows in codemap layout (None: row 0 in every cell), host tensors, or
+    (None, None) with the options off.  Every refusal is a ValueError raised here, before any device work."""
+    if code_bias is None and allowed_codes is None:
+        if code_bias_map is not None:
+            raise ValueError("code_bias_map selects rows of code_bias (or the one row of allowed_codes): neither is given")
+        return None, None
+    if code_bias is not None and allowed_codes is not None:
+        raise ValueError("allowed_codes is shorthand for a code_bias row of 0 and -inf: give one of the two")
+    n = int(model.n_class_target)
+    if allowed_codes is not None:
+        a = allowed_codes if torch.is_tensor(allowed_codes) else torch.as_tensor(
+            np.asarray(allowed_codes if isinstance(allowed_codes, (list, tuple, np.ndarray)) else sorted(allowed_codes)))
+        a = a.detach().cpu()
+        if a.dtype == torch.bool:
+            if tuple(a.shape) != (n,):
+                raise ValueError(f"allowed_codes: a bool mask is [{n}] (n_class_target), not {tuple(a.shape)}")
+            allowed = a
+        else:
+            if a.numel() and (a.is_floating_point() or a.is_complex()):
+                raise ValueError("allowed_codes: a bool [n_class] mask or a collection of integer class indices")
+            a = a.reshape(-1).long()
+            if a.numel() and (int(a.min()) < 0 or int(a.max()) >= n):
+                raise ValueError(f"allowed_codes: class indices lie in [0, {n})")
+            allowed = torch.zeros(n, dtype=torch.bool)
+            allowed[a] = True
+        table = torch.full((1, n), -float("inf"), dtype=torch.float32)
+        table[0, allowed] = 0.0
+    else:
+        if not torch.is_tensor(code_bias) or not code_bias.is_floating_point():
+            raise ValueError("code_bias: a float tensor [n_class] or [R, n_class]")
+        table = code_bias.detach().to(device="cpu", dtype=torch.float32)
+        if table.dim() == 1:
+            table = table.unsqueeze(0)
+        if table.dim() != 2 or table.shape[0] < 1 or table.shape[1] != n:
+            raise ValueError(f"code_bias {tuple(code_bias.shape)}: expected [{n}] or [R, {n}] (n_class_target)")
+        if table.shape[0] > 1 and code_bias_map is None:
+            raise ValueError(f"code_bias with {table.shape[0]} rows needs a code_bias_map to choose among them")
+    if bool(torch.isnan(table).any()) or bool((table == float("inf")).any()):
+        raise ValueError("code_bias: NaN and +inf are not biases (-inf bans a class)")
+    if not bool(torch.isfinite(table).any(dim=1).all()):
+        raise ValueError("code_bias / allowed_codes: a row that bans every class")
+    if code_bias_map is None:
+        return table.contiguous(), None
+    helper = model.target_codemaps_helper
+    m = code_bias_map
+    if not torch.is_tensor(m) or m.is_floating_point() or m.is_complex() or m.dtype == torch.bool:
+        raise ValueError("code_bias_map: an integer tensor [F, T], [1, F, T] or [B, F, T]; -1 = no bias")
+    m = m.detach().cpu().long()
+    if m.dim() == 2:
+        m = m.unsqueeze(0)
+    if m.dim() != 3 or tuple(m.shape[1:]) != (helper.frequencies, helper.duration) or m.shape[0] not in (1, batch_size):
+        raise ValueError(f"code_bias_map {tuple(code_bias_map.shape)}: expected [{helper.frequencies}, {helper.duration}] with "
+                         f"no, 1 or {batch_size} leading rows")
+    if int(m.max()) >= table.shape[0]:
+        raise ValueError(f"code_bias_map: index {int(m.max())} into a table of {table.shape[0]} rows")
+    return table.contiguous(), m.clamp(min=-1)
+
+
+def _code_bias_index(model, bias_map) -> torch.Tensor:
+    """int32 [1 or B, S]: a checked map of bias rows in the order the loop samples in (the mask's way into that order)."""
+    if bias_map is None:
+        return torch.zeros(1, model.target_transformer_sequence_length, dtype=torch.int32)
+    return model.target_codemaps_helper.to_sequence(bias_map).to(torch.int32).contiguous()
+
+
 @torch.no_grad()
 def sample_model(model: VQNSynthTransformer, device: Union[torch.device, str], batch_size: int,
                  codemap_size: Iterable[int], temperature: Union[float, Sequence[float], torch.Tensor],
@@ -104,8 +183,17 @@ def sample_model(model: VQNSynthTransformer, device: Union[torch.device, str], b
                  uniforms: Optional[torch.Tensor] = None,
                  gumbel_noise: Optional[torch.Tensor] = None,
                  kv_cache_dtype: Optional[torch.dtype] = None,
-                 num_variations: Optional[int] = None, return_log_probs: bool = False):
-    """return_log_probs: the result is (codes [B, F, T], log_probs [B, F, T] float32) -- beside every sampled code the
+                 num_variations: Optional[int] = None, return_log_probs: bool = False,
+                 code_bias: Optional[torch.Tensor] = None, code_bias_map: Optional[torch.Tensor] = None,
+                 allowed_codes=None):
+    """code_bias / code_bias_map / allowed_codes: steer WHAT may be drawn, per codemap cell.  `code_bias` is a float tensor
+    [n_class] added to the logits of every sampled cell before temperature and filters, or a table [R, n_class] together
+    with `code_bias_map`, an integer tensor [F, T], [1, F, T] or [B, F, T] in codemap layout naming the table row of every
+    cell (-1: no bias there).  -inf bans a class -- it is never drawn; NaN, +inf and a row that bans every class are
+    refused.  `allowed_codes` (a bool [n_class], e.g. `codes_in_use(...)`, or a collection of class indices) is shorthand
+    for one row of 0 and -inf.  The draw kernel adds the row (`isi_prior_code_bias`); log-probabilities reported with
+    `return_log_probs` stay the MODEL's.  With the options off the call is what it was.
+    return_log_probs: the result is (codes [B, F, T], log_probs [B, F, T] float32) -- beside every sampled code the
     MODEL's log-probability of it (log softmax of the raw logits: it does not depend on temperature, top-k or top-p, and it
     is what `score_codemap` gives for the result), exactly 0.0 where nothing was sampled.  The draw kernel stores it as it
     commits the token (`isi_prior_state.token_log_probs`); the codes are those of the call without the option.
@@ -124,11 +212,16 @@ def sample_model(model: VQNSynthTransformer, device: Union[torch.device, str], b
     if return_log_probs and use_predictive_sampling:
         raise ValueError("return_log_probs reads the KV-cached loop's draw kernel: predictive sampling draws by Gumbel-max "
                          "over full passes and reports no log-probabilities")
+    bias_table, bias_map = _code_bias_rows(model, batch_size, code_bias, code_bias_map, allowed_codes)
+    bias_index = _code_bias_index(model, bias_map) if bias_table is not None else None
+    if bias_table is not None and use_predictive_sampling:
+        raise ValueError("code_bias / allowed_codes are applied by the KV-cached loop's draw kernel: predictive sampling "
+                         "draws by Gumbel-max over full passes")
     if num_variations is not None:
         return _sample_variations(model, device, batch_size, codemap_size, temperature, condition, class_conditioning,
                                   initial_code, mask, time_indexes_source, time_indexes_target, top_k_sampling_k,
                                   top_p_sampling_p, progressbar_decorator, use_predictive_sampling, generator, uniforms,
-                                  kv_cache_dtype, num_variations, return_log_probs)
+                                  kv_cache_dtype, num_variations, return_log_probs, bias_table, bias_index)
     kv_cache_dtype = _kv_cache_dtype(kv_cache_dtype)
     if use_predictive_sampling and kv_cache_dtype is not torch.float32:
         raise ValueError("predictive sampling runs full decoder passes and has no key/value cache: kv_cache_dtype / "
@@ -162,6 +255,9 @@ def sample_model(model: VQNSynthTransformer, device: Union[torch.device, str], b
         def time_rows(ti, lo, hi):           # [B, T] per-row time indexes (a 1-D list is shared)
             return ti[lo:hi] if torch.is_tensor(ti) and ti.dim() == 2 else ti
 
+        def bias_map_rows(lo, hi):           # the checked table goes through as it is; a per-row map is sliced
+            return bias_map[lo:hi] if bias_map is not None and bias_map.shape[0] > 1 else bias_map
+
         parts = []
         for lo in range(0, batch_size, 256):
             hi = min(batch_size, lo + 256)
@@ -176,7 +272,7 @@ def sample_model(model: VQNSynthTransformer, device: Union[torch.device, str], b
                 top_k_sampling_k=param_rows(row_params[1], lo, hi), top_p_sampling_p=param_rows(row_params[2], lo, hi),
                 progressbar_decorator=progressbar_decorator, use_predictive_sampling=use_predictive_sampling,
                 uniforms=uniforms[:, lo:hi], gumbel_noise=rows(gumbel_noise, lo, hi), kv_cache_dtype=kv_cache_dtype,
-                return_log_probs=return_log_probs))
+                return_log_probs=return_log_probs, code_bias=bias_table, code_bias_map=bias_map_rows(lo, hi)))
         if return_log_probs:
             return torch.cat([c for c, _ in parts], 0), torch.cat([lp for _, lp in parts], 0)
         return torch.cat(parts, 0)
@@ -238,7 +334,7 @@ def sample_model(model: VQNSynthTransformer, device: Union[torch.device, str], b
         if pos.shape[0] == 0:
             return _maps(model, code_seq, return_log_probs, None)
         sampler = NativeSampler(model, memory, x_seq, code_seq, mask_seq, uniforms, kv_cache_dtype=kv_cache_dtype,
-                                log_probs=return_log_probs)
+                                log_probs=return_log_probs, code_bias=bias_table, code_bias_index=bias_index)
         n_steps = sampler.plan_rows(pos, commit, temp_rows, top_k_rows, top_p_rows)
         sampler.prefill(p0)
         chunk = n_steps if progressbar_decorator is None else 64
@@ -258,7 +354,7 @@ def sample_model(model: VQNSynthTransformer, device: Union[torch.device, str], b
     p_first, n_pos = masked[0] + start_len - 1, min(n_pos, masked[-1] + start_len)
     # the whole loop natively: no per-token return to Python, no host sync
     sampler = NativeSampler(model, memory, x_seq, code_seq, mask_seq, uniforms, kv_cache_dtype=kv_cache_dtype,
-                            log_probs=return_log_probs)
+                            log_probs=return_log_probs, code_bias=bias_table, code_bias_index=bias_index)
     if p_first < 8:
         p_first = 0                                        # a few rows: not worth a batched pass
     sampler.prefill(p_first)
@@ -395,7 +491,7 @@ def _one_value(value, name: str):
 def _sample_variations(model, device, batch_size, codemap_size, temperature, condition, class_conditioning, initial_code,
                        mask, time_indexes_source, time_indexes_target, top_k, top_p, progressbar_decorator,
                        use_predictive_sampling, generator, uniforms, kv_cache_dtype, num_variations,
-                       return_log_probs=False):
+                       return_log_probs=False, bias_table=None, bias_index=None):
     """`sample_model(num_variations=N)`: N rows over ONE source.  Everything that does not depend on the draws is formed once at
     batch 1 -- source sequence, encoder memory, its projected keys / values (or the single-source table) and the keys / values
     of the unmasked prefix; the target rows, the codes and the self-attention cache have N rows.  All checks come before any
@@ -464,7 +560,8 @@ def _sample_variations(model, device, batch_size, codemap_size, temperature, con
         x_seq = x_row.repeat(1, n, 1).contiguous()
         code_seq = code_row.repeat(n, 1).contiguous()
         sampler = NativeSampler(model, memory, x_seq, code_seq, mask_seq, uniforms[:, lo:lo + n].to(device=device, dtype=torch.float32),
-                                kv_cache_dtype=kv_cache_dtype, shared_memory=True, log_probs=return_log_probs)
+                                kv_cache_dtype=kv_cache_dtype, shared_memory=True, log_probs=return_log_probs,
+                                code_bias=bias_table, code_bias_index=bias_index)
         sampler.prefill(p_first)
         chunk = n_pos if progressbar_decorator is None else 64
         starts = range(p_first, n_pos, chunk)

@@ -422,3 +422,322 @@ def layernorm_data(kind, M, D, gen):
     else:
         assert kind == "randn", kind
     return x
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Float64 specification, float32 yardstick and split-product models of the convolution weight gradients
+# (csrc/conv_wgrad_f32.hip), in the style of the row-ops block above: plain torch on the CPU, no autograd and none of the
+# project's kernels.  A weight gradient is an im2col contraction over pixels,
+#     dW2d[r][c] = sum over (b, l) of rows[b][l][r] * cols[b][c][l],
+# with, for a plain convolution, rows = dY [B, OH OW, Cout] and cols = unfold(zero-padded cat(x, x2)) [B, Cin k k, OH OW]:
+#     dW[co, ci, kh, kw] = sum_{b, oy, ox} dY[b, oy, ox, co] * xpad[b, ci, oy s + kh, ox s + kw],
+# and for ConvTranspose2d(4, 2, 1) rows = x [B, H W, Cin] and cols = unfold(dY, 4, padding 1, stride 2) [B, Cout 16, H W]:
+#     dW[ci, co, kh, kw] = sum_{b, iy, ix} x[b, ci, iy, ix] * dY[b, co, 2 iy - 1 + kh, 2 ix - 1 + kw]   (out of range: dropped).
+# db is the column sum of dY.  A "row" for compare_rows is one output channel's gradient: reshape dW to [rows, -1].
+# tests/test_conv_wgrad_host.py holds the spec to float64 autograd and shows what the comparison rejects;
+# tests/test_conv_wgrad_gpu.py holds the kernels to it.
+def _wgrad_operands(x, x2, dy_nhwc, k, stride, pad, transposed, dtype, clamp_border=False, swap_sources=False):
+    """(rows [B, L, R], cols [B, Ccols, L], dY as [B L', Cout]) of the contraction above in `dtype`.  The two switches are the
+    host tests' mutants: `clamp_border` replicates the border instead of zero padding, `swap_sources` concatenates (x2, x)."""
+    x, dy = torch.as_tensor(x).detach().cpu().to(dtype), torch.as_tensor(dy_nhwc).detach().cpu().to(dtype)
+    if x2 is not None:
+        x2 = torch.as_tensor(x2).detach().cpu().to(dtype)
+        x = torch.cat([x2, x] if swap_sources else [x, x2], dim=1)
+    B = x.shape[0]
+    dy2d = dy.reshape(-1, dy.shape[-1])
+    if transposed:
+        assert (k, stride, pad) == (4, 2, 1) and x2 is None
+        src, rows = dy.permute(0, 3, 1, 2), x.permute(0, 2, 3, 1).reshape(B, -1, x.shape[1])
+    else:
+        src, rows = x, dy.reshape(B, -1, dy.shape[-1])
+    if clamp_border and pad:
+        src, pad = torch.nn.functional.pad(src, (pad,) * 4, mode="replicate"), 0
+    cols = torch.nn.functional.unfold(src, k, padding=pad, stride=stride)
+    assert cols.shape[2] == rows.shape[1], (cols.shape, rows.shape)
+    return rows, cols, dy2d
+
+
+def _wgrad_shape(dw2d, k, groups):
+    """[R, C k k] -> torch's weight layout [R, C / groups, k, k]: the block-diagonal part of the dense gradient."""
+    R = dw2d.shape[0]
+    dw = dw2d.reshape(R, -1, k, k)
+    if groups == 1:
+        return dw
+    r, c = R // groups, dw.shape[1] // groups
+    return torch.cat([dw[g * r:(g + 1) * r, g * c:(g + 1) * c] for g in range(groups)], 0)
+
+
+def _wgrad_contract(rows, cols, pixels=None):
+    if pixels is not None:                                # the pixels (b, l) that are summed, as a flat boolean mask
+        rows = rows * pixels.reshape(rows.shape[0], -1, 1).to(rows.dtype)
+    return torch.einsum("blr,bcl->rc", rows, cols)
+
+
+def conv_wgrad_spec(x, x2, dy_nhwc, k, stride, pad, transposed, groups=1):
+    """(dW in torch's layout, db) in float64: Conv2d [Cout, Cin / groups, k, k], ConvTranspose2d [Cin, Cout / groups, 4, 4]."""
+    rows, cols, dy2d = _wgrad_operands(x, x2, dy_nhwc, k, stride, pad, transposed, torch.float64)
+    return _wgrad_shape(_wgrad_contract(rows, cols), k, groups), dy2d.sum(dim=0)
+
+
+def conv_wgrad_f32_yardstick(x, x2, dy_nhwc, k, stride, pad, transposed, groups=1, pixels=None, db_pixels=None,
+                             clamp_border=False, swap_sources=False, x_hi_only=False):
+    """The same contraction in float32 on the CPU: what float32 can do on that data.  The switches are the host tests' mutants:
+    `pixels` / `db_pixels` (flat boolean masks over the summed pixels) drop pixels from dW / db, `clamp_border`,
+    `swap_sources` (see _wgrad_operands), `x_hi_only` carries the layer input as its bf16 hi piece alone."""
+    rows, cols, dy2d = _wgrad_operands(x, x2, dy_nhwc, k, stride, pad, transposed, torch.float32, clamp_border, swap_sources)
+    if x_hi_only:
+        if transposed:
+            rows = rows.bfloat16().float()
+        else:
+            cols = cols.bfloat16().float()
+    db = dy2d.sum(dim=0) if db_pixels is None else (dy2d * db_pixels.reshape(-1, 1).float()).sum(dim=0)
+    return _wgrad_shape(_wgrad_contract(rows, cols, pixels), k, groups), db
+
+
+def bf16_pieces(v, pieces):
+    """The split of csrc/conv_wgrad_f32.hip::split4<NP> on a float32 tensor, as float64 tensors: NP = 2: (hi, lo) with
+    hi = rne_bf16(v), lo = rne_bf16(v - hi); NP = 3: (hi, mid, lo) with mid = rne_bf16(v - hi), lo = rne_bf16(v - hi - mid)
+    (the subtractions are exact in float32, so v = hi + mid + lo exactly)."""
+    v = v.float()
+    rne = lambda t: t.bfloat16().float()
+    hi = rne(v)
+    r = v - hi
+    if pieces == 2:
+        return hi.double(), rne(r).double()
+    assert pieces == 3
+    mid = rne(r)
+    return hi.double(), mid.double(), rne(r - mid).double()
+
+
+def conv_wgrad_split_model(x, x2, dy_nhwc, k, stride, pad, transposed, pieces, groups=1, drop_lo=False):
+    """Float64 evaluation of the products the split-bf16 kernels document: its distance from conv_wgrad_spec is the truncation
+    a precision mode accepts by design.  Every element of dY (D) and of the im2col operand (X) is split by `bf16_pieces` and
+    the sum runs over the terms the kernel keeps.  conv_wgrad_split_kernel<NP> (piece index 0 hi, 1 lo, 2 mid; term(qa, qb)
+    multiplies piece qa of dY with piece qb of the input):
+        } else if constexpr (NP == 3) {   // smallest terms first: lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi
+          term(1, 0); term(0, 1); term(2, 2); term(2, 0); term(0, 2); term(0, 0);
+        } else {
+          term(1, 0); term(0, 1); term(0, 0);
+    so pieces = 2 keeps D.hi X.hi + D.hi X.lo + D.lo X.hi and pieces = 3 those plus D.hi X.mid + D.mid X.hi + D.mid X.mid (with
+    the three-piece lo).  conv_wgrad_halo_kernel stages both operands with split4<2> and issues
+        mfma(al, bh[c]) ; mfma(ah, bl[c]) ; mfma(ah, bh[c])
+    the same three terms as pieces = 2.  A pair-format source (x_pair) is decoded first -- "the staging decodes (hi + lo) / 4 --
+    exactly the value the forward's products saw" -- and that float32 value is split into bf16 pieces like any other: model it
+    by passing `pair_round_f16(x)` as the input, with pieces = 2.  The one-hot form (vq_embed_sum) keeps D.lo, D.mid, D.hi
+    against an operand that is exact in its hi piece, i.e. the exact float32 terms: its yardstick is the float32 evaluation.
+    `drop_lo` is a host-test mutant: the lo piece of both operands is left out."""
+    rows, cols, _ = _wgrad_operands(x, x2, dy_nhwc, k, stride, pad, transposed, torch.float32)
+    R, Cc = bf16_pieces(rows, pieces), bf16_pieces(cols, pieces)
+    if pieces == 2:
+        hi, lo = 0, 1
+        terms = [(hi, hi), (hi, lo), (lo, hi)]
+    else:
+        hi, mid, lo = 0, 1, 2
+        terms = [(hi, hi), (hi, mid), (mid, hi), (mid, mid), (hi, lo), (lo, hi)]
+    if drop_lo:
+        terms = [t for t in terms if lo not in t]
+    # (which operand is dY and which the input differs between the plain and the transposed form; the term list is symmetric)
+    dw = sum(_wgrad_contract(R[a], Cc[b]) for a, b in terms)
+    return _wgrad_shape(dw, k, groups)
+
+
+def pair_round_f16(x):
+    """The float32 value a split-f16 pair holds (csrc/split_f16.h: x s = hi + lo, hi = f16(x s), lo = f16(x s - hi), s = 4):
+    (hi + lo) / 4."""
+    xs = x.float() * 4.0
+    hi = xs.half().float()
+    return (hi + (xs - hi).half().float()) / 4.0
+
+
+def larger_error(a, b, ref):
+    """Element-wise, whichever of a and b lies further from ref: as a yardstick, its row error is the larger of the two's."""
+    a, b, ref = _f64(a), _f64(b), _f64(ref)
+    return torch.where((a - ref).abs() >= (b - ref).abs(), a, b)
+
+
+# The six-term mode (flags 4) keeps the project's margin of 8 although its yardstick, the float64 evaluation of the six kept
+# terms, prices the truncation only (~1e-8 of a row: the bound is the floor, 8 x 2^-23, whatever the number of pixels), while
+# the kernel accumulates 6 M products in ONE float32 accumulator per split -- per 32-pixel chunk two steps of six MFMA each,
+# every one rounding the running sum: about 12 M / 32 roundings of 2^-24 of the row's scale, ~sqrt(12 M / 32) 2^-24.  The cases
+# below keep a split at or under 352 pixels, where that is within the bound: the largest ratio measured on the MI355X is 7.0
+# (128 x 128 tile, M = 666 in two splits; profiles/wgrad_checks.txt), the exact-fp32 kernel and the float32 evaluation on
+# the CPU sitting at 3.6 and 6.4 floors on the same data for the same reason.  A longer split would need a yardstick that
+# prices the accumulation (the float32 evaluation, as for flags 2), not a wider margin.
+def wgrad_split_tile(rows, K):
+    """The tile `wgrad_tile` of csrc/conv_wgrad_f32.hip selects for a [rows][K] gradient (rows = the GEMM's output channels)."""
+    Kpad = (K + 31) // 32 * 32
+    if Kpad <= 64:
+        return "64x64" if rows <= 64 else "128x64"
+    return "32x512" if rows <= 32 else "128x128"
+
+
+def wgrad_case_tile(c):
+    """Tile of a case: a transposed layer runs with the roles swapped (rows = its input channels, K = 16 x its output
+    channels, those padded to 4 when fewer), a source of fewer than 4 channels is padded to 4."""
+    if c.transposed:
+        return wgrad_split_tile(c.c0, 16 * max(c.cout, 4))
+    cin = c.c0 + c.c1
+    return wgrad_split_tile(c.cout, c.k * c.k * (4 if cin < 4 and not c.c1 else cin))
+
+
+def conv_wgrad_yardstick(flags, spec_dw, f32_dw, model2_dw=None, model3_dw=None):
+    """The yardstick of a precision mode (the flag bits of isi_conv_wgrad_f32): 0 (and every launch that runs the fp32 pipe):
+    the float32 evaluation; 2 (three-term products): per element the worse of the float32 evaluation and the pieces = 2
+    model; 4 (six-term): the pieces = 3 model."""
+    if flags == 0:
+        return f32_dw
+    if flags == 2:
+        return larger_error(f32_dw, model2_dw, spec_dw)
+    assert flags == 4
+    return model3_dw
+
+
+# ConvTranspose2d(4, 2, 1) as four stride-1 2x2 convolutions, one per output phase (py, px) = (oy % 2, ox % 2): the form of
+# isi_conv_wgrad_f32 with bit 0 of its flag word set.  Phase p = 2 py + px, tap (ty, tx) reads the input at
+# (oy - (1 - py) + ty, ox - (1 - px) + tx) and is torch's tap (ky, kx) = (3 - py - 2 ty, 3 - px - 2 tx) (csrc/pack.hip).
+def convT_phases_f32(x, dy_nhwc, pad_of=lambda p: 1 - p, dtype=torch.float32):
+    """Packed [4][Cout][4 Cin] (k = (ty 2 + tx) Cin + ci) weight gradient of the four-phase form.  `pad_of` (phase bit -> top /
+    left padding) is the host tests' mutant switch: the kernel's is 1 - p."""
+    x = torch.as_tensor(x).detach().cpu().to(dtype)
+    dy = torch.as_tensor(dy_nhwc).detach().cpu().to(dtype)
+    B, Cin, H, W = x.shape
+    Cout = dy.shape[-1]
+    out = torch.zeros(4, Cout, 4 * Cin, dtype=dtype)
+    for py in range(2):
+        for px in range(2):
+            dyp = dy[:, py::2, px::2, :].reshape(B, H * W, Cout)
+            pt, pl = pad_of(py), pad_of(px)
+            xp = torch.nn.functional.pad(x, (pl, 1 - pl, pt, 1 - pt))                        # [B, Cin, H + 1, W + 1]
+            cols = torch.nn.functional.unfold(xp, 2).reshape(B, Cin, 4, H * W)               # [b][ci][ty 2 + tx][l]
+            out[2 * py + px] = torch.einsum("blo,bctl->otc", dyp, cols).reshape(Cout, 4 * Cin)
+    return out
+
+
+def convT_unpack_phases(packed, Cin, Cout):
+    """[4][Cout][>= 4 Cin] packed phase gradients -> torch's ConvTranspose2d layout [Cin, Cout, 4, 4]."""
+    packed = torch.as_tensor(packed).detach().cpu()
+    dw = torch.zeros(Cin, Cout, 4, 4, dtype=packed.dtype)
+    for py in range(2):
+        for px in range(2):
+            m = packed[2 * py + px][:, :4 * Cin].reshape(Cout, 2, 2, Cin)
+            for ty in range(2):
+                for tx in range(2):
+                    dw[:, :, 3 - py - 2 * ty, 3 - px - 2 * tx] = m[:, ty, tx, :].t()
+    return dw
+
+
+def embed_sum_spec(z, idx, K):
+    """embed_sum [D, K] = z^T @ one_hot(idx) in float64, as an index_add over the rows of z [N, D]."""
+    z = _f64(z)
+    out = torch.zeros(K, z.shape[1], dtype=torch.float64)
+    out.index_add_(0, torch.as_tensor(idx).cpu().long().reshape(-1), z)
+    return out.t().contiguous()
+
+
+def embed_sum_f32(z, idx, K):
+    z = torch.as_tensor(z).detach().cpu().float()
+    out = torch.zeros(K, z.shape[1], dtype=torch.float32)
+    out.index_add_(0, torch.as_tensor(idx).cpu().long().reshape(-1), z)
+    return out.t().contiguous()
+
+
+# The cases of both weight-gradient test files.  route: the kernel family the dispatcher of conv_wgrad_batched_f32 sends the
+# case to under three-term products (flags 2); c1: channels of a second source (0: one source); layout of the layer input:
+# "nhwc" dense channels-last, "nchw" dense NCHW (not vectorisable: scalar gather), "pair" split-f16 pair tensors;
+# B, H, W: the layer INPUT.  `vec`: the operands are vectorisable (Cin % 4 == 0 per source, Cout % 4 == 0, channels-last), so
+# the precision bits select the kernel; otherwise the fp32 pipe runs whatever the flags.
+WgradCase = collections.namedtuple("WgradCase", "route c0 c1 cout k stride pad transposed groups B H W layout vec")
+
+
+def _wc(route, c0, c1, cout, k, stride, pad, B, H, W, transposed=False, groups=1, layout="nhwc", vec=True):
+    return WgradCase(route, c0, c1, cout, k, stride, pad, transposed, groups, B, H, W, layout, vec)
+
+
+WGRAD_CASES = [
+    # halo-staged kernel: 3x3 s1 p1 / k4 s2 p1, 32-multiple channels, OW % 32 == 0, OH % 2 == 0.  One 2 x 32 tile: ntiles / 4 = 0
+    # so one split; nco = 4 (Cout % 128 == 0), 2 (Cout % 64 == 0), 1
+    _wc("halo", 128, 0, 128, 3, 1, 1, 1, 2, 32), _wc("halo", 64, 0, 64, 3, 1, 1, 1, 2, 32), _wc("halo", 128, 0, 32, 3, 1, 1, 1, 2, 32),
+    # 12 tiles, 4 units: min(256 / 4, 12 / 4) = 3 splits of 4 tiles; 14 tiles: 3 splits of 5, 5 and 4
+    _wc("halo", 128, 0, 128, 3, 1, 1, 3, 4, 64), _wc("halo", 128, 0, 128, 3, 1, 1, 7, 2, 64),
+    _wc("halo", 64, 0, 128, 4, 2, 1, 1, 4, 64),                                              # k4 s2: both tap groups
+    _wc("halo", 128, 0, 128, 3, 1, 1, 2, 4, 32, layout="pair"), _wc("halo", 32, 32, 128, 3, 1, 1, 2, 4, 32, layout="pair"),
+    # the same three layers one column / one row off the halo kernel's whole tiles: OW % 32 != 0 or OH % 2 != 0 -> split kernel
+    *[_wc("split", ci, 0, co, 3, 1, 1, 1, h, w) for ci, co in ((128, 128), (64, 64), (128, 32)) for h, w in ((2, 33), (2, 31), (3, 32))],
+    # split 128 x 128 (Kpad > 64, Cout > 32).  M = 666: 21 chunks of 32 pixels, nsplit = min(768 / 5 tiles, 21 / 8) = 2 splits of
+    # 11 and 10 chunks, the last chunk 26 pixels
+    _wc("split", 64, 0, 128, 3, 1, 1, 2, 9, 37), _wc("split", 64, 64, 128, 3, 1, 1, 2, 9, 37),
+    # split 32 x 512 (Cout <= 32), Cout below the tile; M = 5 < 32
+    _wc("split", 128, 0, 32, 3, 1, 1, 2, 9, 37), _wc("split", 128, 0, 8, 3, 1, 1, 2, 9, 37),
+    _wc("split", 128, 0, 32, 3, 1, 1, 1, 1, 5), _wc("split", 128, 0, 8, 3, 1, 1, 1, 1, 5),
+    _wc("split", 32, 0, 128, 1, 1, 0, 2, 9, 37),                                             # split 128 x 64: K = 32 = Kpad <= 64
+    # split 64 x 64 (Kpad <= 64, Cout <= 64): the 2-channel side through isi_pad_channels4_f32, cin_keep = 2; M = 342 and M = 1
+    _wc("split", 2, 0, 32, 4, 2, 1, 2, 18, 38), _wc("split", 2, 0, 64, 4, 2, 1, 2, 18, 38),
+    _wc("split", 2, 0, 32, 4, 2, 1, 1, 2, 2), _wc("split", 2, 0, 64, 4, 2, 1, 1, 2, 2),
+    # K % 32 != 0: K = 72 -> Kpad = 96, K = 108 -> Kpad = 128 (split 32 x 512; M = 35)
+    _wc("split", 8, 0, 16, 3, 1, 1, 1, 5, 7), _wc("split", 12, 0, 16, 3, 1, 1, 1, 5, 7),
+    # scalar gather of conv_wgrad_f32_kernel (fp32 pipe whatever the flags): Cin % 4 != 0 (quads straddle taps); Cout % 4 != 0
+    # (dvec = 0); an NCHW source; two sources with C0 = 6 (quads straddle the sources)
+    *[_wc("scalar", ci, c1, co, 3, 1, 1, B, H, W, layout=lay, vec=False)
+      for B, H, W in ((1, 5, 7), (2, 9, 37)) for ci, c1, co, lay in ((6, 0, 16, "nhwc"), (64, 0, 6, "nhwc"), (64, 0, 64, "nchw"), (6, 10, 16, "nhwc"))],
+    # ConvTranspose2d through vqvae/_train.py conv_wgrad: the adjoint stride-2 convolution with the roles swapped (source = dY,
+    # a channel slice of a wider gradient; 2 and 1 channels go through isi_pad_channels4_f32), db by isi_colsum_f32
+    *[_wc("split", ci, 0, co, 4, 2, 1, B, H, W, transposed=True) for B, H, W in ((1, 3, 5), (2, 9, 19)) for ci, co in ((128, 64), (64, 2), (32, 1))],
+    _wc("split", 32, 0, 32, 3, 1, 1, 1, 5, 7, groups=2),                                     # layer.grouped(...) of the dense gradient
+]
+# the four-phase transposed C entry (bit 0 of isi_conv_wgrad_f32's flag word): (Cin, Cout, B, H, W, vectorisable)
+WGRAD_PHASE_CASES = [(32, 64, 1, 3, 5, True), (32, 64, 2, 9, 19, True), (6, 8, 1, 3, 5, False), (6, 8, 2, 9, 19, False)]
+
+
+def wgrad_case_id(c):
+    src = f"{c.c0}+{c.c1}" if c.c1 else f"{c.c0}"
+    return (f"{c.route}-{'convT' if c.transposed else 'conv'}{src}to{c.cout}k{c.k}s{c.stride}p{c.pad}"
+            f"{'g%d' % c.groups if c.groups > 1 else ''}-{c.B}x{c.H}x{c.W}-{c.layout}")
+
+
+def wgrad_case_data(c):
+    """(x [B, C0, H, W], x2 or None, dy [B, OH, OW, Cout]) float32 on the CPU: seeded randn, the layer input rectified as the
+    forward rectifies it (roughly half zeros), pair-format sources rounded to what their pairs hold."""
+    seed = 0
+    for v in (c.c0, c.c1, c.cout, c.k, c.stride, c.pad, int(c.transposed), c.groups, c.B, c.H, c.W, ("nhwc", "nchw", "pair").index(c.layout)):
+        seed = (seed * 131 + v) % (2 ** 31 - 1)
+    g = torch.Generator().manual_seed(seed)
+    x = torch.relu(torch.randn(c.B, c.c0, c.H, c.W, generator=g))
+    x2 = torch.relu(torch.randn(c.B, c.c1, c.H, c.W, generator=g)) if c.c1 else None
+    if c.transposed:
+        OH, OW = 2 * c.H, 2 * c.W
+    else:
+        OH, OW = (c.H + 2 * c.pad - c.k) // c.stride + 1, (c.W + 2 * c.pad - c.k) // c.stride + 1
+    dy = torch.randn(c.B, OH, OW, c.cout, generator=g)
+    if c.layout == "pair":
+        x, x2 = pair_round_f16(x), (pair_round_f16(x2) if x2 is not None else None)
+    return x, x2, dy
+
+
+def wgrad_phase_case_data(shape):
+    """(x [B, Cin, H, W] rectified, dy [B, 2H, 2W, Cout]) of a WGRAD_PHASE_CASES entry, float32 on the CPU."""
+    cin, cout, B, H, W, _ = shape
+    g = torch.Generator().manual_seed(cin * 1000 + cout * 10 + B)
+    return torch.relu(torch.randn(B, cin, H, W, generator=g)), torch.randn(B, 2 * H, 2 * W, cout, generator=g)
+
+
+WgradRefs = collections.namedtuple("WgradRefs", "spec_dw spec_db f32_dw f32_db model2 model3")
+_wgrad_refs_cache = {}
+
+
+def wgrad_case_refs(c):
+    """The spec, the float32 yardstick and the two split models of a case, computed once per process and left unchanged
+    (the models only where the precision bits can select a split kernel)."""
+    if c not in _wgrad_refs_cache:
+        x, x2, dy = wgrad_case_data(c)
+        a = (x, x2, dy, c.k, c.stride, c.pad, c.transposed)
+        spec_dw, spec_db = conv_wgrad_spec(*a, groups=c.groups)
+        f32_dw, f32_db = conv_wgrad_f32_yardstick(*a, groups=c.groups)
+        m2 = conv_wgrad_split_model(*a, pieces=2, groups=c.groups) if c.vec else None
+        m3 = conv_wgrad_split_model(*a, pieces=3, groups=c.groups) if c.vec else None
+        _wgrad_refs_cache[c] = WgradRefs(spec_dw, spec_db, f32_dw, f32_db, m2, m3)
+    return _wgrad_refs_cache[c]
+
+
+def rows2d(t):
+    """A weight gradient as [rows, -1] (a row = one output channel's gradient); vectors stay vectors."""
+    return t.reshape(t.shape[0], -1) if t.dim() > 1 else t

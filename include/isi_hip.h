@@ -42,7 +42,7 @@ const char *isi_last_error(void);
  * 2 isi_conv_w, 3 isi_encoder_w, 4 isi_decoder_w, 5 isi_codebook_w,
  * 6 isi_vqvae_w, 7 isi_vqvae_out, 8 isi_attn_args, 9 isi_prior_w,
  * 10 isi_prior_state, 11 isi_attn_bwd_args, 12 isi_reduce_job, 13 isi_prior_rows,
- * 14 isi_prior_code_bias.
+ * 14 isi_prior_code_bias, 15 isi_adam_tensor, 16 isi_adam_hyper.
  * Returns 0 for an unknown id. */
 size_t isi_abi_struct_bytes(int which);
 
@@ -373,6 +373,45 @@ int isi_conv_wgrad_deferred_f32(const isi_src *src0, const isi_src *src1, const 
                                 float *db, float *workspace, size_t workspace_floats, int B, int H, int W, int Cout, int KH,
                                 int KW, int stride, int pad, int flags, void *stream, isi_reduce_job *jobs_out, int *n_jobs);
 int isi_reduce_jobs_f32(const isi_reduce_job *jobs, int n_jobs, void *stream);
+
+/* ------------------------------------------------ Adam with device-resident hyper-parameters */
+/* `optim.Adam(params, lr, eps)` + `clip_grad_norm_` + `optimizer.step()` of the training scripts (train_vqvae.py:181-192,777,
+ * train_autoregressive_model.py:256-263,624-640): plain Adam, no amsgrad, no weight decay.  Per element:
+ *   g' = g * coef;  m = b1 m + (1-b1) g';  v = b2 v + (1-b2) g' g';  p -= step_size * m / (sqrt(v) * inv_sqrt_bc2 + eps)
+ * g' is an fp32 product (clip_grad_norm_ scales the fp32 gradient); the three other lines are evaluated in double from the
+ * double hyper-parameters and each result is rounded to fp32 once (torch's fused Adam evaluates its moment lines in double
+ * too: its betas are doubles).  Note that m and v of the p line are the unrounded double values.
+ * Every per-step quantity is READ FROM DEVICE MEMORY: `hyper` [n_groups] (one isi_adam_hyper per param group, written by the
+ * host in double: step_size = lr / (1 - b1^t), inv_sqrt_bc2 = 1 / sqrt(1 - b2^t); the step count is the host's) and `coef` (NULL: 1).  A step recorded into a HIP graph therefore follows any host-side schedule of lr and
+ * betas (utils/training/scheduler.py CycleScheduler moves beta1 every step): the host rewrites 64 bytes per group before a
+ * replay.  The tensor table travels by value in the kernel arguments (64 entries per launch; no address lives in device
+ * memory).  Every tensor is cut into chunks of 2048 elements counted from its own start, one workgroup each; a chunk whose
+ * four addresses agree mod 16 moves 16 bytes per lane (with < 4 leading / trailing elements one by one), any other chunk
+ * element by element -- sliced parameters and gradients that are views into a flat bucket need no copy.
+ * Global-norm clipping: isi_grad_sumsq_f32 writes sum(g^2) of every chunk to partials[isi_adam_num_chunks(table)] (same
+ * table form; only g and n are read), isi_grad_clip_coef_f32 (one workgroup, fixed order, double accumulation) writes
+ * norm_coef[0] = total_norm and norm_coef[1] = min(1, max_norm / (total_norm + 1e-6)); pass &norm_coef[1] as `coef`.  No
+ * atomics: results are bit-reproducible.  A non-finite norm gives a non-finite coefficient and propagates into p, like
+ * clip_grad_norm_(error_if_nonfinite=False).  g itself is left unscaled.
+ * Checked before any launch: ISI_E_INVALID for a null table / pointer, n <= 0, a pointer not aligned to a float, a group
+ * outside [0, n_groups), n_groups <= 0, a null hyper block, n_partials != isi_adam_num_chunks, max_norm <= 0 or NaN;
+ * ISI_E_UNSUPPORTED for a tensor beyond 2^35 elements.  An empty table is a no-op for isi_adam_step_f32. */
+typedef struct isi_adam_tensor {
+  float *p;                 /* parameter, n floats                    */
+  const float *g;           /* its gradient                           */
+  float *m, *v;             /* exp_avg, exp_avg_sq                    */
+  int64_t n;
+  int32_t group;            /* index into `hyper`                     */
+  int32_t reserved;
+} isi_adam_tensor;
+typedef struct isi_adam_hyper {
+  double b1, one_minus_b1, b2, one_minus_b2, eps, step_size, inv_sqrt_bc2, reserved;
+} isi_adam_hyper;
+int64_t isi_adam_num_chunks(const isi_adam_tensor *tensors, int n_tensors);
+int isi_grad_sumsq_f32(const isi_adam_tensor *tensors, int n_tensors, float *partials, int64_t n_partials, void *stream);
+int isi_grad_clip_coef_f32(const float *partials, int64_t n_partials, float max_norm, float *norm_coef, void *stream);
+int isi_adam_step_f32(const isi_adam_tensor *tensors, int n_tensors, const isi_adam_hyper *hyper, int n_groups,
+                      const float *coef, void *stream);
 /* dy *= (y > 0) : ReLU backward through an output rectified in the producer's epilogue. */
 int isi_relu_bwd_f32(float *dy, const float *y, int64_t n, void *stream);
 /* a += alpha * b */

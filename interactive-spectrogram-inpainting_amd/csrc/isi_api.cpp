@@ -106,6 +106,8 @@ size_t isi_abi_struct_bytes(int which) {
     case 12: return sizeof(isi_reduce_job);
     case 13: return sizeof(isi_prior_rows);
     case 14: return sizeof(isi_prior_code_bias);
+    case 15: return sizeof(isi_adam_tensor);
+    case 16: return sizeof(isi_adam_hyper);
     default: return 0;
   }
 }
@@ -420,6 +422,17 @@ int isi_conv_wgrad_deferred_f32(const isi_src *src0, const isi_src *src1, const 
                                  stride, pad, flags, S(stream), jobs_out, n_jobs);
 }
 int isi_reduce_jobs_f32(const isi_reduce_job *jobs, int n_jobs, void *stream) { return reduce_jobs_f32(jobs, n_jobs, S(stream)); }
+int64_t isi_adam_num_chunks(const isi_adam_tensor *tensors, int n_tensors) { return adam_num_chunks(tensors, n_tensors); }
+int isi_grad_sumsq_f32(const isi_adam_tensor *tensors, int n_tensors, float *partials, int64_t n_partials, void *stream) {
+  return grad_sumsq_f32(tensors, n_tensors, partials, n_partials, S(stream));
+}
+int isi_grad_clip_coef_f32(const float *partials, int64_t n_partials, float max_norm, float *norm_coef, void *stream) {
+  return grad_clip_coef_f32(partials, n_partials, max_norm, norm_coef, S(stream));
+}
+int isi_adam_step_f32(const isi_adam_tensor *tensors, int n_tensors, const isi_adam_hyper *hyper, int n_groups,
+                      const float *coef, void *stream) {
+  return adam_step_f32(tensors, n_tensors, hyper, n_groups, coef, S(stream));
+}
 int isi_relu_bwd_f32(float *dy, const float *y, int64_t n, void *stream) { return relu_bwd_f32(dy, y, n, S(stream)); }
 int isi_axpy_f32(float *a, const float *b, float alpha, int64_t n, void *stream) {
   return axpy_f32(a, b, alpha, n, S(stream));

@@ -15,6 +15,12 @@ int vq_bwd_rows_f32(float *dz, const float *dq, int64_t ldq, const float *z, con
 int pack_multi(const void *table_dev, int n, int blocks_per_entry, hipStream_t stream);
 bool conv_wgrad_halo_route(int Cout, int C0, int C1, int KH, int KW, int stride, int pad, int OH, int OW);
 int reduce_jobs_f32(const isi_reduce_job *jobs, int n_jobs, hipStream_t stream);
+// optimizer.hip
+int64_t adam_num_chunks(const isi_adam_tensor *tensors, int n_tensors);
+int grad_sumsq_f32(const isi_adam_tensor *tensors, int n_tensors, float *partials, int64_t n_partials, hipStream_t stream);
+int grad_clip_coef_f32(const float *partials, int64_t n_partials, float max_norm, float *norm_coef, hipStream_t stream);
+int adam_step_f32(const isi_adam_tensor *tensors, int n_tensors, const isi_adam_hyper *hyper, int n_groups, const float *coef,
+                  hipStream_t stream);
 int conv_wgrad_deferred_f32(const isi_src *s0, const isi_src *s1, const float *dy, float *dw, int cin_keep, float *db,
                             float *workspace, size_t workspace_floats, int B, int H, int W, int Cout, int KH, int KW, int stride,
                             int pad, int flags, hipStream_t stream, isi_reduce_job *jobs_out, int *n_jobs);

@@ -157,6 +157,16 @@ class isi_reduce_job(C.Structure):
                 ("map_keep", C.c_int32)]
 
 
+class isi_adam_tensor(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64),
+                ("group", C.c_int32), ("reserved", C.c_int32)]
+
+
+class isi_adam_hyper(C.Structure):
+    _fields_ = [("b1", C.c_double), ("one_minus_b1", C.c_double), ("b2", C.c_double), ("one_minus_b2", C.c_double),
+                ("eps", C.c_double), ("step_size", C.c_double), ("inv_sqrt_bc2", C.c_double), ("reserved", C.c_double)]
+
+
 # name -> (restype, argtypes); must list every symbol include/isi_hip.h declares
 _P = C.c_void_p
 SIGNATURES = {
@@ -270,6 +280,10 @@ SIGNATURES = {
                                               C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                               C.c_int, C.c_int, _P, C.POINTER(isi_reduce_job), C.POINTER(C.c_int)]),
     "isi_reduce_jobs_f32": (C.c_int, [C.POINTER(isi_reduce_job), C.c_int, _P]),
+    "isi_adam_num_chunks": (C.c_int64, [C.POINTER(isi_adam_tensor), C.c_int]),
+    "isi_grad_sumsq_f32": (C.c_int, [C.POINTER(isi_adam_tensor), C.c_int, _P, C.c_int64, _P]),
+    "isi_grad_clip_coef_f32": (C.c_int, [_P, C.c_int64, C.c_float, _P, _P]),
+    "isi_adam_step_f32": (C.c_int, [C.POINTER(isi_adam_tensor), C.c_int, _P, C.c_int, _P, _P]),
     "isi_relu_bwd_f32": (C.c_int, [_P, _P, C.c_int64, _P]),
     "isi_axpy_f32": (C.c_int, [_P, _P, C.c_float, C.c_int64, _P]),
     "isi_vq_bwd_f32": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _P]),
@@ -331,7 +345,7 @@ def lib() -> C.CDLL:
                     fn.argtypes = args
                 structs = [isi_src, isi_dst, isi_conv_w, isi_encoder_w, isi_decoder_w, isi_codebook_w,
                            isi_vqvae_w, isi_vqvae_out, isi_attn_args, isi_prior_w, isi_prior_state, isi_attn_bwd_args,
-                           isi_reduce_job, isi_prior_rows]
+                           isi_reduce_job, isi_prior_rows, isi_prior_code_bias, isi_adam_tensor, isi_adam_hyper]
                 for i, st in enumerate(structs):
                     if handle.isi_abi_struct_bytes(i) != C.sizeof(st):
                         raise HipLibraryError(f"ABI mismatch for {st.__name__}: library "

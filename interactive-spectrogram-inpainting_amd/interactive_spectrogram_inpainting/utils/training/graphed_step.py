@@ -27,7 +27,9 @@ What a recorded step must not do, and how each case is handled:
   * take new tensors as inputs -- batches are copied into the static tensors the recording used;
   * run a collective inside a segment -- see above.
 Losses / outputs of EARLIER eager steps must not be alive when the step is recorded (their autograd graphs pin gradient
-accumulators to the eager stream, which breaks the capture).  The optimizer must be capturable (`make_adam(..., capturable=True)`).
+accumulators to the eager stream, which breaks the capture).  The optimizer must be capturable (`make_adam(..., capturable=True)`: its
+learning rate and betas are then constants of the recording) or keep its hyper-parameters on the device (`make_adam(...,
+device_hyper=True)`, passed as `optimizers=[opt]`: the replays follow `param_groups`).
 Caches keyed on parameter versions (packed weights, embedding tables, codebooks) are refreshed by launches INSIDE the recording;
 `finish()` invalidates them for eager code that follows.
 
@@ -211,13 +213,17 @@ class GraphedTrainingStep:
     >>> loss = g(code_batch, mask_batch)       # copies the batch into the static tensors, replays, returns the loss tensor
 
     Data-parallel steps record like single-process ones: their collectives sit behind `host_boundary` (module docstring).
+    `optimizers`: optimizers of the step whose per-step hyper-parameters live in device memory (DeviceHyperAdam): their
+    `upload_hyper()` runs in front of every replay, on the replay's stream, so the replay applies what `param_groups` holds
+    at that moment -- a host scheduler stepped between the calls, or a hand edit.
     `range_params`: weights whose split-f16 operand range (|w| < 64, checked against half of it) is re-examined every
     `range_check_every` replays; `backend`: tests only."""
 
     def __init__(self, step_fn: Callable[..., torch.Tensor], static_inputs: Sequence[torch.Tensor], warmup: int = 3,
                  index_limits: Optional[Dict[int, int]] = None, range_params: Optional[Iterable[torch.Tensor]] = None,
-                 range_check_every: int = 256, backend=None):
+                 range_check_every: int = 256, backend=None, optimizers: Optional[Sequence] = None):
         self.static_inputs = list(static_inputs)
+        self.optimizers = list(optimizers or [])          # each has upload_hyper() (utils/training/optimizer.py DeviceHyperAdam)
         self.index_limits = dict(index_limits or {})      # input position -> exclusive upper bound of its symbols
         self._pending = []
         self._range_pending = []
@@ -304,6 +310,8 @@ class GraphedTrainingStep:
                 ev = torch.cuda.Event()
                 ev.record()
                 self._pending.append((bad, ev))
+        for opt in self.optimizers:
+            opt.upload_hyper()
         self.recording.replay()
         self.replays += 1
         if self._on_gpu:

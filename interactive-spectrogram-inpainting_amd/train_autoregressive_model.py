@@ -30,7 +30,7 @@ import torch.distributed as dist
 from interactive_spectrogram_inpainting.priors.sequence_mask import SequenceMask
 from interactive_spectrogram_inpainting.priors.transformer import VQNSynthTransformer
 from interactive_spectrogram_inpainting.utils.distributed import GradBucketReducer, is_distributed
-from interactive_spectrogram_inpainting.utils.training.optimizer import make_adam
+from interactive_spectrogram_inpainting.utils.training.optimizer import DeviceHyperAdam, clip_and_step, make_adam
 
 
 def num_satisfied_constraints(predicted: torch.Tensor, condition: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
@@ -42,10 +42,14 @@ def num_satisfied_constraints(predicted: torch.Tensor, condition: torch.Tensor, 
 def run_model(args, epoch: int, loader: Iterable, model: VQNSynthTransformer, optimizer, scheduler, device,
               criterion, tensorboard_writer=None, is_training: bool = True,
               mask_sampler: Optional[SequenceMask] = None, clip_grad_norm: Optional[float] = None,
-              reducer: Optional[GradBucketReducer] = None):
+              reducer: Optional[GradBucketReducer] = None, hip_graph: bool = False):
     """One epoch.  `args.hier` in {'top', 'bottom'}.  With torch.distributed initialised each rank
     runs its own shard of the data and `reducer` (built once over model.parameters()) averages the
-    gradients; the returned sums are this rank's."""
+    gradients; the returned sums are this rank's.  `hip_graph`: a training epoch replays one recorded
+    step (`_run_training_epoch_graphed`)."""
+    if hip_graph and is_training:
+        return _run_training_epoch_graphed(args, epoch, loader, model, optimizer, scheduler, device, criterion,
+                                           mask_sampler, clip_grad_norm, reducer)
     hier = args.hier
     model.train(is_training)
     loss_sum, total_accuracy, num_samples = 0.0, 0.0, 0
@@ -86,9 +90,7 @@ def run_model(args, epoch: int, loader: Iterable, model: VQNSynthTransformer, op
             loss.backward()
             if reducer is not None:
                 reducer.finish()
-            if clip_grad_norm is not None:
-                torch.nn.utils.clip_grad_norm_(model.parameters(), clip_grad_norm)
-            optimizer.step()
+            clip_and_step(model.parameters(), optimizer, clip_grad_norm)
             if scheduler is not None:
                 scheduler.step()
 
@@ -113,6 +115,168 @@ def run_model(args, epoch: int, loader: Iterable, model: VQNSynthTransformer, op
     model.check_indices()       # (end of the epoch: nothing pending may outlive it, e.g. into a checkpoint)
     run_model.last_satisfied_constraints = satisfied_total
     return loss_sum, total_accuracy, num_samples
+
+
+class GraphedPriorStep:
+    """The training branch of `run_model`'s loop body recorded into HIP graph segments (utils/training/graphed_step.py) and
+    replayed per batch.  Static inputs: the target codemap, the mask (top) or the top codemap (bottom), and the class
+    tensors in sorted key order.  The sample-weighted loss / accuracy / satisfied-constraint sums are accumulated by the
+    recording itself into `sums` (float64, on the device) and read once per epoch.  Like GraphedVQVAEStep, the model and
+    the optimizer's state are put back in place after the recording's eager warm-up steps.  The optimizer is a
+    DeviceHyperAdam (replays follow `param_groups`) or a capturable one (constant learning rate)."""
+
+    def __init__(self, hier: str, model: VQNSynthTransformer, optimizer, criterion, statics, class_keys, clip_grad_norm,
+                 reducer):
+        from interactive_spectrogram_inpainting import _hip
+        from interactive_spectrogram_inpainting.utils.training.graphed_step import GraphedTrainingStep
+        self.sums = torch.zeros(3, dtype=torch.float64, device=statics[0].device)
+        self.class_keys = list(class_keys)
+        batch = statics[0].shape[0]
+
+        def step(target, other, *cls):
+            if reducer is not None:
+                reducer.zero()
+            else:
+                optimizer.zero_grad(set_to_none=True)
+            class_conditioning = dict(zip(self.class_keys, cls))
+            if hier == 'top':
+                source = target
+                source_sequence, target_sequence = model.to_sequences(
+                    target, condition=source, class_conditioning=class_conditioning, mask=other)
+            else:
+                source_sequence, target_sequence = model.to_sequences(
+                    target, condition=other, class_conditioning=class_conditioning)
+            logits_sequence, _ = model(target_sequence, condition=source_sequence)
+            logits_map = model.to_time_frequency_map(logits_sequence, kind='target', permute_output_as_logits=True)
+            loss = criterion(logits_map, target)
+            loss.backward()
+            if reducer is not None:
+                reducer.finish()
+            clip_and_step(model.parameters(), optimizer, clip_grad_norm)
+            with torch.no_grad():
+                pred = logits_map.argmax(1)
+                accuracy = (pred == target).float().mean()
+                satisfied = (num_satisfied_constraints(pred, target, other) if model.self_conditional_model
+                             else torch.zeros((), device=target.device))
+                self.sums += torch.stack([loss.detach().double() * batch, accuracy.double() * batch, satisfied.double()])
+            return loss.detach()
+
+        tensors = list(model.parameters()) + list(model.buffers())
+        saved = [t.detach().clone() for t in tensors]
+        had_state = {id(p) for p in optimizer.state}
+        saved_opt = {id(p): {k: v.detach().clone() for k, v in st.items() if torch.is_tensor(v)}
+                     for p, st in optimizer.state.items()}
+        saved_steps = [g.get("step") for g in optimizer.param_groups]
+        device_hyper = isinstance(optimizer, DeviceHyperAdam)
+        limits = {0: model.n_class_target}
+        if hier == 'bottom':
+            limits[1] = model.n_class_source
+        for i, k in enumerate(self.class_keys):
+            limits[2 + i] = model.class_conditioning_num_classes_per_modality[k]
+        self.graphed = GraphedTrainingStep(step, [t.clone() for t in statics], warmup=2, index_limits=limits,
+                                           range_params=[p for p in model.parameters() if p.dim() == 2],
+                                           optimizers=[optimizer] if device_hyper else None)
+        with torch.no_grad():       # the warm-up steps trained on the first batch: put everything back IN PLACE
+            for t, sv in zip(tensors, saved):
+                t.copy_(sv)
+            for p_, st in optimizer.state.items():
+                for k, v in st.items():
+                    if torch.is_tensor(v):
+                        v.copy_(saved_opt[id(p_)][k]) if id(p_) in had_state else v.zero_()
+            self.sums.zero_()
+        if device_hyper:
+            for g, n in zip(optimizer.param_groups, saved_steps):
+                g["step"] = n
+        _hip._on_optimizer_step()      # (values moved without a version bump: caches keyed on versions are stale)
+
+    def __call__(self, *batch: torch.Tensor) -> None:
+        self.graphed(*batch)
+
+    def finish(self) -> None:
+        self.graphed.finish()
+
+
+def _run_training_epoch_graphed(args, epoch, loader, model, optimizer, scheduler, device, criterion, mask_sampler,
+                                clip_grad_norm, reducer):
+    """`run_model(is_training=True)` with the step replayed from a recording.  The order is the eager loop's: the step runs
+    with what `param_groups` holds, then `scheduler.step()`.  The recording is kept on the model across epochs; a batch
+    of another size than the recorded one (a ragged last batch) runs as one eager step with the same optimizer.  Symbols
+    outside their embedding tables raise the reference's IndexError (GraphedTrainingStep's `index_limits`)."""
+    hier = args.hier
+    if scheduler is not None and not isinstance(optimizer, DeviceHyperAdam):
+        raise NotImplementedError("a recorded step bakes the learning rate in: a host-side scheduler with hip_graph needs "
+                                  "make_adam(..., device_hyper=True)")
+    if hier == 'top' and not model.self_conditional_model:
+        raise NotImplementedError("the unconditional top model is not built (see priors/transformer.py)")
+    if hier not in ('top', 'bottom'):
+        raise ValueError(f"unknown hierarchy level {hier}")
+    if reducer is None and is_distributed() and dist.get_world_size() > 1:
+        raise RuntimeError("distributed training needs a GradBucketReducer")
+    model.train(True)
+    key = (id(optimizer), id(criterion), hier, clip_grad_norm, id(reducer))
+    cached = getattr(model, "_graphed_train_step", None)
+    graphed = cached[1] if cached is not None and cached[0][:5] == key else None
+    if cached is not None and graphed is None:
+        cached[1].finish()
+        model._graphed_train_step = None
+    loss_sum, total_accuracy, num_samples, satisfied_total = 0.0, 0.0, 0, 0.0
+    ok = False
+    try:
+        for top, bottom, class_conditioning_tensors in loader:
+            class_keys = sorted(class_conditioning_tensors)
+            cls = [class_conditioning_tensors[k].to(device, non_blocking=True).view(-1, 1) for k in class_keys]
+            top = top.to(device, non_blocking=True)
+            if hier == 'top':
+                # the sampler draws in sequence order [B,S]; the wrapper wants the time-frequency layout
+                mask_sequence = mask_sampler.sample_mask(top.shape[0])
+                mask = model.to_time_frequency_map(mask_sequence.to(device), kind='source')
+                statics = (top, mask, *cls)
+            else:
+                statics = (bottom.to(device, non_blocking=True), top, *cls)
+            shapes = tuple(tuple(t.shape) for t in statics)
+            if graphed is not None and shapes != cached[0][5]:
+                # one eager step with the same optimizer (and the mask already drawn for this batch)
+                fixed = _FixedMask(mask_sequence) if hier == 'top' else mask_sampler
+                ls, acc, n = run_model(args, epoch, [(top, bottom, class_conditioning_tensors)], model, optimizer, scheduler,
+                                       device, criterion, is_training=True, mask_sampler=fixed,
+                                       clip_grad_norm=clip_grad_norm, reducer=reducer)
+                loss_sum, total_accuracy, num_samples = loss_sum + ls, total_accuracy + acc, num_samples + n
+                satisfied_total += run_model.last_satisfied_constraints or 0.0
+                continue
+            if graphed is None:
+                graphed = GraphedPriorStep(hier, model, optimizer, criterion, statics, class_keys, clip_grad_norm, reducer)
+                cached = (key + (shapes,), graphed)
+                model._graphed_train_step = cached
+                graphed.sums.zero_()
+            graphed(*statics)
+            if scheduler is not None:
+                scheduler.step()
+            num_samples += top.shape[0]
+        ok = True
+    finally:
+        if graphed is not None:
+            try:
+                graphed.finish()       # waits for the replays; raises a pending index / range verdict
+            finally:
+                if not ok:
+                    model._graphed_train_step = None
+    if graphed is not None:
+        sums = graphed.sums.tolist()       # the epoch's one read-back
+        graphed.sums.zero_()
+        loss_sum, total_accuracy, satisfied_total = loss_sum + sums[0], total_accuracy + sums[1], satisfied_total + sums[2]
+    model.check_indices()
+    run_model.last_satisfied_constraints = satisfied_total if model.self_conditional_model else None
+    return loss_sum, total_accuracy, num_samples
+
+
+class _FixedMask:
+    """A mask sampler that returns one mask already drawn (sequence order, as `SequenceMask.sample_mask` gives it)."""
+
+    def __init__(self, mask_sequence: torch.Tensor):
+        self.mask_sequence = mask_sequence
+
+    def sample_mask(self, batch: int) -> torch.Tensor:
+        return self.mask_sequence
 
 
 class SyntheticCodes(torch.utils.data.Dataset):
@@ -151,6 +315,9 @@ def main(argv=None):
     ap.add_argument('--top_shape', type=int, nargs=2, default=[32, 32])
     ap.add_argument('--num_encoder_layers', type=int, default=6)
     ap.add_argument('--num_decoder_layers', type=int, default=8)
+    ap.add_argument('--hip_graph', action='store_true',
+                    help="record the training step into HIP graph segments and replay it per batch; the optimizer is "
+                         "then a DeviceHyperAdam, whose replays follow the scheduler")
     ap.add_argument('--database_path', default=None,
                     help="code database written by extract_code.py (LMDB, needs the `lmdb` package); "
                          "default: synthetic code maps")
@@ -187,7 +354,7 @@ def main(argv=None):
         data = SyntheticCodes(args.batch_size * args.num_batches, top_shape, bottom_shape, args.n_class, classes,
                               seed=dist.get_rank() if distributed else 0)
         loader = torch.utils.data.DataLoader(data, batch_size=args.batch_size, shuffle=False)
-    optimizer = make_adam(model.parameters(), lr=args.lr)
+    optimizer = make_adam(model.parameters(), lr=args.lr, device_hyper=args.hip_graph)
     scheduler = CycleScheduler(optimizer, args.lr, n_iter=len(loader) * args.num_epochs)
     criterion = LabelSmoothingLoss(args.n_class, args.label_smoothing, dim=1)
     reducer = GradBucketReducer(model.parameters()) if distributed else None
@@ -199,7 +366,7 @@ def main(argv=None):
         t0 = time.time()
         loss_sum, acc_sum, n = run_model(args, epoch, loader, model, optimizer, scheduler, device, criterion,
                                          is_training=True, mask_sampler=sampler, clip_grad_norm=args.clip_grad_norm,
-                                         reducer=reducer)
+                                         reducer=reducer, hip_graph=args.hip_graph)
         torch.cuda.synchronize()
         if not distributed or dist.get_rank() == 0:
             print(f"epoch {epoch + 1}: loss {loss_sum / n:.5f} acc {acc_sum / n:.5f} "

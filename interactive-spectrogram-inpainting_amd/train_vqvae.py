@@ -37,7 +37,7 @@ from torch import nn  # noqa: E402
 from interactive_spectrogram_inpainting.utils.distributed import (  # noqa: E402
     DistributedEvalSampler, DistributedTrainSampler, assert_same_step_count, is_distributed, is_master_process)
 from interactive_spectrogram_inpainting.vqvae.vqvae import VQVAE  # noqa: E402
-from interactive_spectrogram_inpainting.utils.training.optimizer import make_adam  # noqa: E402
+from interactive_spectrogram_inpainting.utils.training.optimizer import DeviceHyperAdam, clip_and_step, make_adam  # noqa: E402
 
 
 class RunningMeans:
@@ -64,8 +64,9 @@ class GraphedVQVAEStep:
     batch: the host's ~200 launches per step become one call per segment (data parallel: segments are cut at the EMA
     messages and the gradient buckets).  The recording's eager warm-up steps would train on the first batch; the model,
     its codebook buffers and the optimizer's moments are therefore put back IN PLACE afterwards (the graph holds their
-    addresses), so the replayed epoch follows the eager epoch's trajectory.  Needs a capturable optimizer
-    (`make_adam(..., capturable=True)`), no host-side scheduler, batches of one shape."""
+    addresses), so the replayed epoch follows the eager epoch's trajectory.  Needs batches of one shape and either a
+    capturable optimizer (`make_adam(..., capturable=True)`; no host-side scheduler then) or a DeviceHyperAdam
+    (`make_adam(..., device_hyper=True)`): its replays read lr / betas from `param_groups`, and its clipping is fused."""
 
     def __init__(self, model: VQVAE, reconstruction_criterion: Callable, optimizer, img: torch.Tensor,
                  latent_loss_weight: float, clip_grad_norm: Optional[float]):
@@ -79,9 +80,7 @@ class GraphedVQVAEStep:
             latent_loss = latent_loss.mean()
             loss = reconstruction_loss + latent_loss_weight * latent_loss
             loss.backward()
-            if clip_grad_norm is not None:
-                nn.utils.clip_grad_norm_(model.parameters(), clip_grad_norm)
-            optimizer.step()
+            clip_and_step(model.parameters(), optimizer, clip_grad_norm)
             # (detached views of the static result tensors: a kept autograd graph would pin the warm-up steps' gradient
             # accumulators to their stream)
             self.outs = {"reconstruction_loss": reconstruction_loss.detach(), "latent_loss": latent_loss.detach(),
@@ -91,7 +90,9 @@ class GraphedVQVAEStep:
         had_state = {id(p) for p in optimizer.state}
         saved_opt = {id(p): {k: v.detach().clone() for k, v in st.items() if torch.is_tensor(v)}
                      for p, st in optimizer.state.items()}
-        self.graphed = GraphedTrainingStep(step, (img.clone(),), warmup=2)
+        device_hyper = isinstance(optimizer, DeviceHyperAdam)
+        saved_steps = [g.get("step") for g in optimizer.param_groups]      # (DeviceHyperAdam: the host's step counts)
+        self.graphed = GraphedTrainingStep(step, (img.clone(),), warmup=2, optimizers=[optimizer] if device_hyper else None)
         with torch.no_grad():
             for t, sv in zip(list(model.parameters()) + list(model.buffers()), saved):
                 t.copy_(sv)
@@ -99,6 +100,9 @@ class GraphedVQVAEStep:
                 for k, v in st.items():
                     if torch.is_tensor(v):
                         v.copy_(saved_opt[id(p_)][k]) if id(p_) in had_state else v.zero_()
+        if device_hyper:
+            for g, n in zip(optimizer.param_groups, saved_steps):
+                g["step"] = n
         from interactive_spectrogram_inpainting import _hip
         _hip._on_optimizer_step()      # (the values moved without a version bump: packed-weight caches are stale)
         for q in (model.quantize_t, model.quantize_b):
@@ -122,7 +126,7 @@ def train(epoch: int, loader: Iterable, model: VQVAE, reconstruction_criterion: 
         assert_same_step_count(len(loader), torch.device(device) if is_distributed() and
                                dist.get_backend() == "nccl" else None)
     if hip_graph:
-        if scheduler is not None:
+        if scheduler is not None and not isinstance(optimizer, DeviceHyperAdam):
             raise NotImplementedError("a recorded step bakes the learning rate in: no host-side scheduler with hip_graph")
         # the recorded step is kept ACROSS epochs on the model (every train() call used to pay two eager warm-up
         # steps, a re-capture, a new graph pool and a clone / restore of all parameters and optimizer state); it is bound to
@@ -148,9 +152,9 @@ def train(epoch: int, loader: Iterable, model: VQVAE, reconstruction_criterion: 
                         reconstruction_loss = reconstruction_criterion(out, img)
                         latent_loss = latent_loss.mean()
                         (reconstruction_loss + latent_loss_weight * latent_loss).backward()
-                        if clip_grad_norm is not None:
-                            nn.utils.clip_grad_norm_(model.parameters(), clip_grad_norm)
-                        optimizer.step()
+                        clip_and_step(model.parameters(), optimizer, clip_grad_norm)
+                        if scheduler is not None:
+                            scheduler.step()
                         stats.update(img.shape[0], reconstruction_loss, latent_loss, perplexity_t, perplexity_b)
                         continue
                 if graphed is None:
@@ -158,6 +162,8 @@ def train(epoch: int, loader: Iterable, model: VQVAE, reconstruction_criterion: 
                     cached = (key + (tuple(img.shape),), graphed)
                     model._graphed_train_step = cached
                 o = graphed(img)
+                if scheduler is not None:     # (the eager loop's order: the replay applied what param_groups held)
+                    scheduler.step()
                 stats.update(img.shape[0], o["reconstruction_loss"], o["latent_loss"], o["perplexity_t"], o["perplexity_b"])
                 if dry_run:
                     break
@@ -180,9 +186,7 @@ def train(epoch: int, loader: Iterable, model: VQVAE, reconstruction_criterion: 
         latent_loss = latent_loss.mean()
         loss = reconstruction_loss + latent_loss_weight * latent_loss
         loss.backward()
-        if clip_grad_norm is not None:
-            nn.utils.clip_grad_norm_(model.parameters(), clip_grad_norm)
-        optimizer.step()
+        clip_and_step(model.parameters(), optimizer, clip_grad_norm)
         if scheduler is not None:
             scheduler.step()
         stats.update(img.shape[0], reconstruction_loss, latent_loss, perplexity_t, perplexity_b)

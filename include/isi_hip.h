@@ -452,6 +452,29 @@ int isi_vq_embed_sum_f32(const float *z, const int64_t *idx, float *embed_sum_dk
 int isi_vq_ema_update_f32(float *embed, float *cluster_size, float *embed_avg,
                           const float *counts, const float *embed_sum_dk, int D, int K,
                           float decay, float eps, void *stream);
+/* EMA codebook with random restarts of dead codes (QuantizedBottleneckWithRestarts; the
+ * specification is DESIGN.md's and tests/restarts_spec.py's).  restart_state: device int64 [4] =
+ * {seed, step, restarts at the last step, restarts in total}.
+ * isi_vq_restart_row: the batch row code k is redrawn from (host export of the function the
+ * kernel calls): mix(mix(seed ^ mix(step)) + k) mod N, mix = splitmix64's finaliser.
+ * isi_vq_restart_candidates_f32: cand_out [K*D + K] = the candidate vector of every code
+ * k with k mod world == rank, gathered from this rank's z [N,D] (zeros for the other codes),
+ * followed by K flag words (1.0f: the chosen row has a non-finite component and was written
+ * as zeros).  seed and step are read from restart_state on the device.
+ * isi_vq_ema_update_restart_f32: isi_vq_ema_update_f32 that replaces every code whose updated
+ * cluster size is below `threshold` (every code when `initialize` and step == 0), unless
+ * flagged, by its candidate: cluster_size = threshold, embed_avg = threshold * cand, embed = cand
+ * exactly.  cand: [K*D + K] as written above (summed over the ranks).  Advances
+ * restart_state.  K <= 65536. */
+uint64_t isi_vq_restart_row(uint64_t seed, uint64_t step, int k, int64_t N);
+int isi_vq_restart_candidates_f32(const float *z, int64_t N, int D, int K,
+                                  const int64_t *restart_state, int rank, int world,
+                                  float *cand_out, void *stream);
+int isi_vq_ema_update_restart_f32(float *embed, float *cluster_size, float *embed_avg,
+                                  const float *counts, const float *embed_sum_dk,
+                                  const float *cand, int D, int K, float decay, float eps,
+                                  float threshold, int initialize, int64_t *restart_state,
+                                  void *stream);
 
 /* ------------------------------------------------------ transformer prior */
 /* The prior's layers are instantiated by the reference from the absent package

@@ -472,6 +472,19 @@ int isi_vq_ema_update_f32(float *embed, float *cluster_size, float *embed_avg, c
                           const float *embed_sum_dk, int D, int K, float decay, float eps, void *stream) {
   return vq_ema_update_f32(embed, cluster_size, embed_avg, counts, embed_sum_dk, D, K, decay, eps, S(stream));
 }
+uint64_t isi_vq_restart_row(uint64_t seed, uint64_t step, int k, int64_t N) {
+  return N > 0 ? vq_restart_row(seed, step, k, N) : 0;
+}
+int isi_vq_restart_candidates_f32(const float *z, int64_t N, int D, int K, const int64_t *restart_state, int rank,
+                                  int world, float *cand_out, void *stream) {
+  return vq_restart_candidates_f32(z, N, D, K, restart_state, rank, world, cand_out, S(stream));
+}
+int isi_vq_ema_update_restart_f32(float *embed, float *cluster_size, float *embed_avg, const float *counts,
+                                  const float *embed_sum_dk, const float *cand, int D, int K, float decay, float eps,
+                                  float threshold, int initialize, int64_t *restart_state, void *stream) {
+  return vq_ema_update_restart_f32(embed, cluster_size, embed_avg, counts, embed_sum_dk, cand, D, K, decay, eps, threshold,
+                                   initialize, restart_state, S(stream));
+}
 
 int isi_vq_nearest_f32(const float *z, const float *codes_kd, const float *e2, int64_t *idx_out,
                        float *q_out, int32_t *counts, float *sse_part, int64_t N, int D, int K,

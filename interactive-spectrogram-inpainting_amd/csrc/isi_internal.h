@@ -266,6 +266,23 @@ int vq_embed_sum_f32(const float *z, const int64_t *idx, float *embed_sum_dk, fl
                      size_t workspace_floats, int64_t N, int D, int K, hipStream_t stream);
 int vq_ema_update_f32(float *embed, float *cluster_size, float *embed_avg, const float *counts,
                       const float *embed_sum_dk, int D, int K, float decay, float eps, hipStream_t st);
+// Random restarts of dead codes ("EMA codebook with random restarts"): the batch row that code k is redrawn
+// from at `step`, a counter-based function (splitmix64's finaliser, all arithmetic modulo 2^64) shared by the device
+// kernel and the host export isi_vq_restart_row.
+__host__ __device__ inline uint64_t vq_restart_mix(uint64_t x) {
+  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27; x *= 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return x;
+}
+__host__ __device__ inline uint64_t vq_restart_row(uint64_t seed, uint64_t step, int k, int64_t N) {
+  return vq_restart_mix(vq_restart_mix(seed ^ vq_restart_mix(step)) + (uint64_t)(int64_t)k) % (uint64_t)N;
+}
+int vq_restart_candidates_f32(const float *z, int64_t N, int D, int K, const int64_t *restart_state, int rank, int world,
+                              float *cand_out, hipStream_t st);
+int vq_ema_update_restart_f32(float *embed, float *cluster_size, float *embed_avg, const float *counts,
+                              const float *embed_sum_dk, const float *cand, int D, int K, float decay, float eps,
+                              float threshold, int initialize, int64_t *restart_state, hipStream_t st);
 
 int vq_nearest_f32(const float *z, const float *codes, const float *e2, int64_t *idx, float *q,
                    int32_t *counts, float *sse_part, int64_t N, int D, int K, int flags, hipStream_t stream);

@@ -113,6 +113,107 @@ __global__ __launch_bounds__(1024) void vq_ema_update_kernel(float *__restrict__
   }
 }
 
+// Random restarts of dead codes ("EMA codebook with random restarts").  One wave per code k: the codes of this
+// rank (k mod world == rank) copy row vq_restart_row(seed, step, k, N) of z, the others write zeros; a row with a non-finite
+// component is written as zeros and flagged.  seed / step come from device memory: a replayed graph carries no step.
+// VEC: float4 accesses (D % 4 == 0, 16-byte aligned z and cand).
+template <bool VEC>
+__global__ __launch_bounds__(256) void vq_restart_candidates_kernel(const float *__restrict__ z, int64_t N, int D, int K,
+                                                                    const int64_t *__restrict__ restart_state, int rank,
+                                                                    int world, float *__restrict__ cand) {
+  const int lane = threadIdx.x & 63;
+  const int k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (k >= K) return;      // (whole waves: no barrier below)
+  float *dst = cand + (size_t)k * D;
+  const bool mine = k % world == rank;
+  const float *src = z;
+  bool bad = false;
+  if (mine) {
+    const uint64_t row = vq_restart_row((uint64_t)restart_state[0], (uint64_t)restart_state[1], k, N);
+    src = z + row * (uint64_t)D;
+    if (VEC) {
+      for (int d = lane; d < D / 4; d += 64) {
+        const float4 v = reinterpret_cast<const float4 *>(src)[d];
+        bad |= !(isfinite(v.x) && isfinite(v.y) && isfinite(v.z) && isfinite(v.w));
+      }
+    } else {
+      for (int d = lane; d < D; d += 64) bad |= !isfinite(src[d]);
+    }
+    bad = __any(bad);
+  }
+  const bool copy = mine && !bad;
+  if (VEC) {
+    for (int d = lane; d < D / 4; d += 64)
+      reinterpret_cast<float4 *>(dst)[d] = copy ? reinterpret_cast<const float4 *>(src)[d] : make_float4(0.f, 0.f, 0.f, 0.f);
+  } else {
+    for (int d = lane; d < D; d += 64) dst[d] = copy ? src[d] : 0.f;
+  }
+  if (lane == 0) cand[(size_t)K * D + k] = bad ? 1.f : 0.f;
+}
+
+// vq_ema_update_kernel with restarts: a code whose updated cluster size is below `threshold` (every code at step 0 when
+// `initialize`), unless its candidate is flagged, becomes its candidate: cluster_size = threshold, embed_avg = threshold *
+// cand, embed = cand exactly.  Same single workgroup and reduction tree for n; threshold = 0, initialize = 0 gives
+// vq_ema_update_kernel's bits.  cand: [K][D] | flags [K].  Advances restart_state = {seed, step, restarts, total}.
+constexpr int kRestartMaxK = 65536;
+__global__ __launch_bounds__(1024) void vq_ema_update_restart_kernel(float *__restrict__ embed, float *__restrict__ cluster_size,
+                                                                     float *__restrict__ embed_avg,
+                                                                     const float *__restrict__ counts,
+                                                                     const float *__restrict__ embed_sum_dk,
+                                                                     const float *__restrict__ cand, int D, int K, float decay,
+                                                                     float eps, float threshold, int initialize,
+                                                                     int64_t *__restrict__ restart_state) {
+  __shared__ float red[1024];
+  __shared__ int nred[1024];
+  __shared__ unsigned dead[kRestartMaxK / 32];
+  const int tid = threadIdx.x;
+  const bool all = initialize && restart_state[1] == 0;
+  const float *cand_bad = cand + (size_t)K * D;
+  for (int w = tid; w < (K + 31) / 32; w += blockDim.x) dead[w] = 0u;
+  __syncthreads();
+  float s = 0.f;
+  int nd = 0;
+  for (int k = tid; k < K; k += blockDim.x) {
+    float cs = cluster_size[k] * decay + (1.f - decay) * counts[k];
+    if ((cs < threshold || all) && cand_bad[k] == 0.f) {
+      cs = threshold;
+      atomicOr(&dead[k >> 5], 1u << (k & 31));
+      ++nd;
+    }
+    cluster_size[k] = cs;
+    s += cs;
+  }
+  red[tid] = s;
+  nred[tid] = nd;
+  __syncthreads();
+  for (int o = blockDim.x >> 1; o > 0; o >>= 1) {
+    if (tid < o) {
+      red[tid] += red[tid + o];
+      nred[tid] += nred[tid + o];
+    }
+    __syncthreads();
+  }
+  const float n = red[0];
+  for (int i = tid; i < D * K; i += blockDim.x) {
+    const int k = i % K;
+    float ea = embed_avg[i] * decay + (1.f - decay) * embed_sum_dk[i];
+    if (dead[k >> 5] >> (k & 31) & 1u) {
+      const float c = cand[(size_t)k * D + i / K];
+      embed_avg[i] = threshold * c;
+      embed[i] = c;
+    } else {
+      embed_avg[i] = ea;
+      const float csn = (cluster_size[k] + eps) / (n + K * eps) * n;
+      embed[i] = ea / csn;
+    }
+  }
+  if (tid == 0) {      // (every thread read the step before the first barrier)
+    restart_state[1] += 1;
+    restart_state[2] = nred[0];
+    restart_state[3] += nred[0];
+  }
+}
+
 // out[m][c] = gate(y[m][c]) * (a[m][c] + b[m][c]): the sum of two gradient contributions with the ReLU mask of the tensor
 // they belong to, in one pass; `a` may be a channel slice of a wider channels-last tensor (row stride lda >= C): replaces a
 // slice copy + axpy + relu_bwd (three passes over the bottom encoder's 134 MB output gradient).  y = nullptr: no mask.
@@ -396,6 +497,30 @@ int vq_ema_update_f32(float *embed, float *cluster_size, float *embed_avg, const
   hipLaunchKernelGGL(vq_ema_update_kernel, dim3(1), dim3(1024), 0, st, embed, cluster_size, embed_avg, counts,
                      embed_sum_dk, D, K, decay, eps);
   return check_launch("vq_ema_update_f32");
+}
+
+int vq_restart_candidates_f32(const float *z, int64_t N, int D, int K, const int64_t *restart_state, int rank, int world,
+                              float *cand_out, hipStream_t st) {
+  if (!z || !restart_state || !cand_out || N <= 0 || D <= 0 || K <= 0 || world <= 0 || rank < 0 || rank >= world)
+    return invalid("vq_restart_candidates: bad argument");
+  const bool vec = D % 4 == 0 && !((reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(cand_out)) & 15);
+  const dim3 grid((unsigned)((K + 3) / 4)), block(256);
+  if (vec)
+    hipLaunchKernelGGL(vq_restart_candidates_kernel<true>, grid, block, 0, st, z, N, D, K, restart_state, rank, world, cand_out);
+  else
+    hipLaunchKernelGGL(vq_restart_candidates_kernel<false>, grid, block, 0, st, z, N, D, K, restart_state, rank, world, cand_out);
+  return check_launch("vq_restart_candidates_f32");
+}
+
+int vq_ema_update_restart_f32(float *embed, float *cluster_size, float *embed_avg, const float *counts,
+                              const float *embed_sum_dk, const float *cand, int D, int K, float decay, float eps,
+                              float threshold, int initialize, int64_t *restart_state, hipStream_t st) {
+  if (!embed || !cluster_size || !embed_avg || !counts || !embed_sum_dk || !cand || !restart_state || D <= 0 || K <= 0 ||
+      K > kRestartMaxK)
+    return invalid("vq_ema_update_restart: bad argument");
+  hipLaunchKernelGGL(vq_ema_update_restart_kernel, dim3(1), dim3(1024), 0, st, embed, cluster_size, embed_avg, counts,
+                     embed_sum_dk, cand, D, K, decay, eps, threshold, initialize, restart_state);
+  return check_launch("vq_ema_update_restart_f32");
 }
 
 }  // namespace isi

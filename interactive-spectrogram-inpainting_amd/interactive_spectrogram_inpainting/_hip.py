@@ -295,6 +295,10 @@ SIGNATURES = {
     "isi_vq_embed_sum_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int64]),
     "isi_vq_embed_sum_f32": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_int64, C.c_int, C.c_int, _P]),
     "isi_vq_ema_update_f32": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_float, C.c_float, _P]),
+    "isi_vq_restart_row": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_int, C.c_int64]),
+    "isi_vq_restart_candidates_f32": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P]),
+    "isi_vq_ema_update_restart_f32": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_float, C.c_float,
+                                                C.c_float, C.c_int, _P, _P]),
     "isi_vq_nearest_f32": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, _P]),
     "isi_vq_nearest_flags_f32": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P]),
     "isi_vq_conv1x1_nearest_f32": (C.c_int, [C.POINTER(isi_src), C.POINTER(isi_src), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,

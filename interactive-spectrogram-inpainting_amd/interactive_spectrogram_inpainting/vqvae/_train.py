@@ -817,19 +817,33 @@ def _ema_collectives() -> bool:
     return dist.get_world_size() > 1 or FORCE_COLLECTIVES
 
 
-def exchange_ema_statistics(counts: torch.Tensor, embed_sum: torch.Tensor):
+def _rank_world() -> Tuple[int, int]:
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_rank(), dist.get_world_size()
+    return 0, 1
+
+
+def exchange_ema_statistics(counts: torch.Tensor, embed_sum: torch.Tensor, candidates: Optional[torch.Tensor] = None):
     """Data-parallel exchange of the EMA statistics of one quantiser: the per-code usage counts `onehot.sum(0)` [K]
     and the per-code vector sums `flatten^T @ onehot` [D, K] (bottleneck.py:80-84) of every rank's batch shard are
     summed in ONE all-reduce message ([K] + [D*K] floats), so that N ranks x B/N samples update the codebook exactly
     like one process with B samples (the reference lets DDP broadcast rank 0's buffers instead).
     Identity when not distributed.  Host logic only (any device: RCCL on the GPU, gloo in the CPU tests).
-    Blocking form (tests, stand-alone callers); the training step uses `PendingEma` below."""
+    Blocking form (tests, stand-alone callers); the training step uses `PendingEma` below.
+    `candidates` (a quantiser with restarts: the [K*D + K] table of isi_vq_restart_candidates_f32, zero outside this
+    rank's codes) travels in the same message and comes back summed -- the full table on every rank -- as a third part."""
     if not _ema_collectives():
-        return counts, embed_sum
+        return (counts, embed_sum) if candidates is None else (counts, embed_sum, candidates)
     K = counts.numel()
-    packed = torch.cat([counts.reshape(-1).float(), embed_sum.reshape(-1).float()])
+    parts = [counts.reshape(-1).float(), embed_sum.reshape(-1).float()]
+    if candidates is not None:
+        parts.append(candidates.reshape(-1).float())
+    packed = torch.cat(parts)
     dist.all_reduce(packed)
-    return packed[:K], packed[K:].reshape(embed_sum.shape)
+    n = K + embed_sum.numel()
+    if candidates is None:
+        return packed[:K], packed[K:].reshape(embed_sum.shape)
+    return packed[:K], packed[K:n].reshape(embed_sum.shape), packed[n:].reshape(candidates.shape)
 
 
 class PendingEma:
@@ -846,9 +860,13 @@ class PendingEma:
         self.items = []        # (quantiser, packed statistics [K + D K], D, K)
         self.handles = []
 
-    def submit(self, q, counts_f: torch.Tensor, embed_sum: torch.Tensor) -> None:
+    def submit(self, q, counts_f: torch.Tensor, embed_sum: torch.Tensor, candidates: Optional[torch.Tensor] = None) -> None:
+        """`candidates` (a quantiser with restarts): this rank's [K*D + K] candidate table, appended to the SAME message."""
         D, K = embed_sum.shape
-        packed = torch.cat([counts_f.reshape(-1), embed_sum.reshape(-1)])
+        parts = [counts_f.reshape(-1), embed_sum.reshape(-1)]
+        if candidates is not None:
+            parts.append(candidates.reshape(-1))
+        packed = torch.cat(parts)
         self.items.append((q, packed, D, K))
         if _ema_collectives():
             handles = self.handles
@@ -874,7 +892,18 @@ class PendingEma:
 
     @staticmethod
     def _update(q, packed: torch.Tensor, D: int, K: int) -> None:
-        """bottleneck.py:80-92 on the [D,K] buffers from the (summed) statistics `packed` = counts [K] | embed_sum [D K]."""
+        """bottleneck.py:80-92 on the [D,K] buffers from the (summed) statistics `packed` = counts [K] | embed_sum [D K]
+        (| candidates [K D] | flags [K] for a quantiser with restarts, whose kernel also redraws the dead codes)."""
+        if getattr(q, "restart_state", None) is not None:
+            if packed.numel() != 2 * K + 2 * D * K:
+                raise ValueError("a quantiser with restarts needs its candidate table in the statistics message")
+            _hip.check(_hip.lib().isi_vq_ema_update_restart_f32(
+                q.embed.data_ptr(), q.cluster_size.data_ptr(), q.embed_avg.data_ptr(), packed.data_ptr(),
+                packed.data_ptr() + 4 * K, packed.data_ptr() + 4 * (K + D * K), D, K, q.decay, q.eps, q.restart_threshold,
+                int(q.initialize), q.restart_state.data_ptr(), _s(packed)), "isi_vq_ema_update_restart_f32")
+            q._packed_key = None
+            q._ema_steps = getattr(q, "_ema_steps", 0) + 1
+            return
         _hip.check(_hip.lib().isi_vq_ema_update_f32(q.embed.data_ptr(), q.cluster_size.data_ptr(), q.embed_avg.data_ptr(),
                                                     packed.data_ptr(), packed.data_ptr() + 4 * K, D, K, q.decay, q.eps,
                                                     _s(packed)), "isi_vq_ema_update_f32")
@@ -939,10 +968,17 @@ def _ema_statistics(q, z_nhwc, idx, counts, pending: Optional[PendingEma]) -> No
     ws = torch.empty(nws, dtype=torch.float32, device=z_nhwc.device)
     _hip.check(L.isi_vq_embed_sum_f32(z_nhwc.data_ptr(), idx.data_ptr(), embed_sum.data_ptr(), ws.data_ptr(), nws,
                                       N, D, K, _s(z_nhwc)), "isi_vq_embed_sum_f32")
+    cand = None
+    if getattr(q, "restart_state", None) is not None:
+        # this rank's share of the restart candidates: rows of z chosen on the device from (seed, step, code index)
+        rank, world = _rank_world()
+        cand = torch.empty(K * D + K, dtype=torch.float32, device=z_nhwc.device)
+        _hip.check(L.isi_vq_restart_candidates_f32(z_nhwc.data_ptr(), N, D, K, q.restart_state.data_ptr(), rank, world,
+                                                   cand.data_ptr(), _s(z_nhwc)), "isi_vq_restart_candidates_f32")
     own = pending is None
     if own:
         pending = PendingEma()
-    pending.submit(q, counts.float(), embed_sum)
+    pending.submit(q, counts.float(), embed_sum, cand)
     if own:
         pending.flush()
 

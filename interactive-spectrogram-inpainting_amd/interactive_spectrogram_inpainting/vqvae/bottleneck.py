@@ -6,11 +6,15 @@ Drop-in for the reference's `vqvae/bottleneck.py:30-119`
 `(quantize, diff, embed_ind, perplexity)`.  The L2 nearest-neighbour search runs
 in `isi_vq_nearest_f32` (codebook resident in LDS, exact-fp32 matrix pipe,
 lane-local arg-min) without materialising the [N,K] distance / one-hot matrices.
-`QuantizedBottleneckWithRestarts` (`:122-166`) wraps an absent third-party
-package and is out of scope.
+`QuantizedBottleneckWithRestarts` (`:122-166`) wraps an absent third-party package
+in the reference; here it is the same EMA codebook whose dead codes -- EMA usage
+below a threshold -- are redrawn from the current batch's encoder outputs inside
+the update kernel, by a specification of this project's own ("EMA
+codebook with random restarts"; tests/restarts_spec.py).
 """
 from __future__ import annotations
 
+import warnings
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -65,6 +69,45 @@ class QuantizedBottleneck(nn.Module):
             raise IndexError("index out of range in self")  # same failure class as F.embedding
         codes, _ = self.packed()
         return _ops.embed_code(embed_id, codes)
+
+
+class QuantizedBottleneckWithRestarts(QuantizedBottleneck):
+    """EMA codebook with random restarts of dead codes (the reference's `bottleneck.py:122-166`, whose arithmetic sits in
+    the absent `discretization` package: the behaviour is this project's own specification).
+
+    Every training step, after the EMA update of `cluster_size` / `embed_avg`, a code whose `cluster_size` is below
+    `restart_threshold` (vectors per step) becomes a row of the batch's pre-quantisation vectors, chosen by a
+    counter-based hash of (`seed`, step, code index): `embed[:, k]` = that row exactly, `cluster_size[k]` = the threshold.
+    `initialize`: the first step of a fresh module redraws every code.  The choice is made on the device from the
+    `restart_state` buffer (int64 [4] = seed, step, restarts at the last step, restarts in total), so a step recorded
+    into a HIP graph keeps drawing new rows on every replay.  The forward itself -- search, `diff`, perplexity -- uses the
+    codebook from before the update and equals `QuantizedBottleneck`'s."""
+    restart_state: Tensor
+
+    def __init__(self, dim: int, n_embed: int, decay: float = 0.99, eps: float = 1e-5, restart_threshold: float = 1.,
+                 initialize: bool = True, seed: int = 0, embeddings_initial_variance: float = 1,
+                 corruption_weights: Optional[List[float]] = None):
+        if corruption_weights is not None:      # the reference sets corruption_weights = None in this class (:129)
+            warnings.warn("QuantizedBottleneckWithRestarts does not corrupt indices: corruption_weights is ignored")
+        super().__init__(dim, n_embed, decay=decay, eps=eps, embeddings_initial_variance=embeddings_initial_variance,
+                         corruption_weights=None)
+        self.restart_threshold = float(restart_threshold)
+        self.initialize = bool(initialize)
+        seed = int(seed) % (1 << 64)
+        self.register_buffer('restart_state',
+                             torch.tensor([seed - (1 << 64) if seed >= (1 << 63) else seed, 0, 0, 0], dtype=torch.int64))
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        key = prefix + 'restart_state'
+        if key not in state_dict:
+            # a checkpoint of the plain bottleneck: its codebook is trained, so `initialize` must not redraw it
+            warnings.warn(f"{key} is missing from the state dict (a QuantizedBottleneck checkpoint): the restart step "
+                          "starts at 1, the codebook is not re-initialised")
+            state = self.restart_state.clone()
+            state[1], state[2], state[3] = 1, 0, 0
+            state_dict = dict(state_dict)
+            state_dict[key] = state
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
 
 
 class UnquantizedBottleneck(QuantizedBottleneck):

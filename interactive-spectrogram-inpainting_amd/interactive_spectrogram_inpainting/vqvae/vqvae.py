@@ -18,6 +18,7 @@ storage, exactly like the reference's `.permute(0, 3, 1, 2)` results.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import json
 import os
 import pathlib
@@ -30,7 +31,7 @@ from torch import nn, Tensor
 
 from .. import _hip
 from .encoder_decoder import RosinalityEncoder, RosinalityDecoder, _ConvParams
-from .bottleneck import QuantizedBottleneck, UnquantizedBottleneck
+from .bottleneck import QuantizedBottleneck, QuantizedBottleneckWithRestarts, UnquantizedBottleneck
 
 # ISI_CONV_F16X3 scales weights and code vectors by 2^10 before the f16 split (include/isi_hip.h): 65520 / 1024 and
 # above rounds to inf
@@ -70,9 +71,6 @@ class VQVAE(nn.Module):
         if encoders is not None or decoders is not None:
             raise NotImplementedError("custom encoder/decoder modules (the fastai XResNet variant) "
                                       "are outside the MI355X hot path")
-        if restarts_usage_threshold != 1.:
-            raise NotImplementedError("QuantizedBottleneckWithRestarts needs the absent `discretization` "
-                                      "package and is not built")
         if output_activation_type is not None:
             raise NotImplementedError("decoder output activations ('threshold_gelu', vqvae.py:229-236) are not built")
 
@@ -110,7 +108,12 @@ class VQVAE(nn.Module):
             self.n_embed_t, self.n_embed_b = num_embeddings
 
         self.quantize_conv_t = _ConvParams(C_, D, 1)
-        bottleneck = UnquantizedBottleneck if disable_quantization else QuantizedBottleneck
+        if disable_quantization:
+            bottleneck = UnquantizedBottleneck
+        elif restarts_usage_threshold == 1.:      # the reference's contract and default (vqvae.py:153): the plain bottleneck
+            bottleneck = QuantizedBottleneck
+        else:
+            bottleneck = functools.partial(QuantizedBottleneckWithRestarts, restart_threshold=restarts_usage_threshold)
         self.disable_quantization = disable_quantization
         self.quantize_t = bottleneck(D, self.n_embed_t, decay=decay,
                                      corruption_weights=corruption_weights['top'],

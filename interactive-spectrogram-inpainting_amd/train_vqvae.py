@@ -59,6 +59,23 @@ class RunningMeans:
         return dict(zip(self.NAMES, m))
 
 
+class _RestartTotals:
+    """Codes redrawn during one epoch by the quantisers with restarts (`restart_state[3]`, counted on the device by the
+    update kernel): a device-side copy at the start, ONE read-back at the end of the epoch -- never per step."""
+
+    def __init__(self, model):
+        self.states = {name: getattr(model, attr).restart_state for name, attr in
+                       (("restarts_top", "quantize_t"), ("restarts_bottom", "quantize_b"))
+                       if getattr(getattr(model, attr, None), "restart_state", None) is not None}
+        self.before = {name: s[3].clone() for name, s in self.states.items()}
+
+    def add_to(self, means: Dict[str, float]) -> Dict[str, float]:
+        if self.states:
+            totals = torch.stack([s[3] - self.before[name] for name, s in self.states.items()]).tolist()
+            means.update(zip(self.states, (float(t) for t in totals)))
+        return means
+
+
 class GraphedVQVAEStep:
     """The loop body of `train` below recorded into HIP graph segments (utils/training/graphed_step.py) and replayed per
     batch: the host's ~200 launches per step become one call per segment (data parallel: segments are cut at the EMA
@@ -86,6 +103,8 @@ class GraphedVQVAEStep:
             self.outs = {"reconstruction_loss": reconstruction_loss.detach(), "latent_loss": latent_loss.detach(),
                          "perplexity_t": perplexity_t.detach(), "perplexity_b": perplexity_b.detach()}
             return loss.detach()
+        # (`model.buffers()` includes a quantiser's `restart_state`: the warm-up steps' restarts are undone with the
+        # codebooks, and the replays -- whose kernels read seed and step from that buffer -- go on from the step it held)
         saved = [t.detach().clone() for t in list(model.parameters()) + list(model.buffers())]
         had_state = {id(p) for p in optimizer.state}
         saved_opt = {id(p): {k: v.detach().clone() for k, v in st.items() if torch.is_tensor(v)}
@@ -122,6 +141,7 @@ def train(epoch: int, loader: Iterable, model: VQVAE, reconstruction_criterion: 
           clip_grad_norm: Optional[float] = None, dry_run: bool = False, hip_graph: bool = False) -> Dict[str, float]:
     model.train()
     stats = RunningMeans(device)
+    restarts = _RestartTotals(model)
     if hasattr(loader, "__len__") and not dry_run:
         assert_same_step_count(len(loader), torch.device(device) if is_distributed() and
                                dist.get_backend() == "nccl" else None)
@@ -177,7 +197,7 @@ def train(epoch: int, loader: Iterable, model: VQVAE, reconstruction_criterion: 
                 graphed.finish()
                 if not ok:
                     model._graphed_train_step = None
-        return stats.means()
+        return restarts.add_to(stats.means())
     for batch_index, (img, *_) in enumerate(loader):
         model.zero_grad()
         img = img.to(device, non_blocking=True)
@@ -192,7 +212,7 @@ def train(epoch: int, loader: Iterable, model: VQVAE, reconstruction_criterion: 
         stats.update(img.shape[0], reconstruction_loss, latent_loss, perplexity_t, perplexity_b)
         if dry_run:
             break
-    return stats.means()
+    return restarts.add_to(stats.means())
 
 
 @torch.no_grad()
@@ -267,6 +287,10 @@ def main():
     ap.add_argument("--dry-run", action="store_true")
     ap.add_argument("--hip-graph", action="store_true",
                     help="record the training step into HIP graph segments and replay it per batch (GraphedVQVAEStep)")
+    ap.add_argument("--restarts_usage_threshold", type=float, default=1.,
+                    help="EMA usage (vectors per step) below which a code is redrawn from the batch's encoder outputs; "
+                         "1.0 (default, as in the reference): the plain EMA codebook")
+    ap.add_argument("--restarts_seed", type=int, default=0, help="seed of the device-side choice of the redrawn rows")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -279,7 +303,11 @@ def main():
         dist.init_process_group("nccl", device_id=device)
 
     torch.manual_seed(1)   # identical initial weights on every rank
-    model = VQVAE(in_channel=2).to(device)
+    model = VQVAE(in_channel=2, restarts_usage_threshold=args.restarts_usage_threshold)
+    for i, q in enumerate((model.quantize_t, model.quantize_b)):
+        if getattr(q, "restart_state", None) is not None:
+            q.restart_state[0] = (args.restarts_seed + i + (1 << 63)) % (1 << 64) - (1 << 63)      # (one stream per level; 64 bits)
+    model = model.to(device)
     optimizer = make_adam(model.parameters(), lr=args.lr, **({"capturable": True} if args.hip_graph else {}))
     helper = None
     if args.reconstruction_criterion != "MSE":

@@ -102,6 +102,29 @@ int isi_spec_affine_mask_f32(const float *x, const float *ref, float *y, int64_t
                              float a0, float b0, float a1, float b1, float thr, int use_mask,
                              void *stream);
 
+/* ------------------------------------------------ sample-rate conversion */
+/* Band-limited resampling of uploads and of audio output: the reference's /analyze-audio hands whatever the
+ * browser recorded to `spectrograms_helper.from_wavfile(path, duration_n=...)`, which converts it to the models'
+ * rate with sox / torchaudio (flask_server.py:557-568, 624-667); those packages are absent, the arithmetic is
+ * specified in tests/resample_spec.py.  A polyphase Kaiser-windowed sinc ("kaiser best": 64 zero crossings,
+ * rolloff 0.9475937167399596, beta 14.769656459379492):
+ *   g = gcd(fs_in, fs_out), orig = fs_in / g, new = fs_out / g, f0 = rolloff * min(orig, new),
+ *   width = ceil(64 * orig / f0), taps = 2 * width + orig, N_out = ceil(L * new / orig),
+ *   y[q * new + r] = sum_i h[r][i] * x[q * orig + i - width], x = 0 outside [0, L), i ascending in fp32 fma.
+ * isi_resample_geometry (host only): ISI_E_INVALID for rates <= 0; ISI_E_UNSUPPORTED beyond the caps
+ * taps <= 16384 (one frame's stage fits 64 KB of LDS) and new * taps <= 2^22 table floats -- the four outputs
+ * are written in that case too (saturated at INT_MAX).
+ * isi_resample_out_len (host only): ceil(L * new / orig); ISI_E_INVALID for L < 0 or a ratio term <= 0.
+ * isi_resample_f32: y[b, 0:N_out] from x[b, 0:L], rows x_stride / y_stride floats apart, any float-aligned bases;
+ * table [taps, new] TAP-MAJOR fp32 on the device (h[r][i] at i * new + r), made by the caller.  No atomics, no
+ * host synchronisation, no allocation; stream-ordered; the summation order of an output does not depend on B
+ * or L.  Checked before any launch: null pointers, B / L / orig / new / width <= 0, a stride shorter than the
+ * row (ISI_E_INVALID); L >= 2^31 or the two caps above (ISI_E_UNSUPPORTED). */
+int isi_resample_geometry(int fs_in, int fs_out, int *orig, int *new_, int *width, int *taps);
+int64_t isi_resample_out_len(int64_t L, int orig, int new_);
+int isi_resample_f32(const float *x, int64_t x_stride, float *y, int64_t y_stride, int B, int64_t L,
+                     int orig, int new_, int width, const float *table, void *stream);
+
 /* ------------------------------------------------- measurement (bench.py) */
 /* Per-launch timing with HIP events recorded on the launch stream.  State is
  * per calling thread; `on` = 1 starts (earlier records cleared), 0 pauses, 2 resumes without

@@ -16,8 +16,10 @@ Compute: the windowed DFT is a convolution of the audio, viewed as [B, 1, L/hop,
 channels-last, with the DFT basis as a 1 x (n_fft/hop) kernel on the exact-fp32 matrix
 pipe (isi_conv2d_f32); mel projections are 1x1 convolutions; polar / unwrap / integrate /
 transpose stages and the overlap-add are the HBM-bound kernels of csrc/spectrogram.hip.
-No CPU path: tensors must live on the GPU.  `from_wavfile` needs an audio decoder
-(torchaudio / soundfile, not in this image) and is not built.
+No CPU path: tensors must live on the GPU.  `from_wavfile(path, duration_n)` reads a RIFF file
+with the standard library (GANsynth_pytorch/wavfile.py), converts it to `fs_hz` with the
+band-limited resampler of GANsynth_pytorch/resample.py (reference flask_server.py:557-568,
+624-667 hands uploads at the recorder's rate to it) and returns its spectrogram.
 """
 from __future__ import annotations
 
@@ -200,8 +202,21 @@ class SpectrogramsHelper:
                    "isi_spec_inverse_prepare_bwd_f32")
         return dspec
 
-    def from_wavfile(self, *args, **kwargs):
-        raise NotImplementedError("decoding audio files needs torchaudio / soundfile, which this image lacks")
+    def from_wavfile(self, path, duration_n: Optional[int] = None) -> torch.Tensor:
+        """A RIFF/WAVE file (PCM 16-bit or float32, any sampling rate the resampler takes) -> [1, 2, F, T] on the
+        helper's device: mono samples resampled to `fs_hz`, trimmed / zero-padded to `duration_n` samples when given
+        (reference flask_server.py:644-649)."""
+        from GANsynth_pytorch.resample import resample
+        from GANsynth_pytorch.wavfile import read_wav
+        with open(path, "rb") as f:
+            audio, rate = read_wav(f.read())
+        device = self.device if self.device is not None else torch.device("cuda")
+        x = resample(audio.to(device), rate, self.fs_hz)
+        if duration_n is not None:
+            x = x[:duration_n]
+            if x.numel() < duration_n:
+                x = torch.nn.functional.pad(x, (0, duration_n - x.numel()))
+        return self.to_spectrogram(x.unsqueeze(0))
 
 
 class _ToAudioFunction(torch.autograd.Function):

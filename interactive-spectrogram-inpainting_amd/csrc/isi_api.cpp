@@ -302,6 +302,14 @@ int isi_overlap_add_f32(const float *frames, float *audio, int B, int T, int n_f
                         void *stream) {
   return overlap_add_f32(frames, audio, B, T, n_fft, hop, left, L, S(stream));
 }
+int isi_resample_geometry(int fs_in, int fs_out, int *orig, int *new_, int *width, int *taps) {
+  return resample_geometry(fs_in, fs_out, orig, new_, width, taps);
+}
+int64_t isi_resample_out_len(int64_t L, int orig, int new_) { return resample_out_len(L, orig, new_); }
+int isi_resample_f32(const float *x, int64_t x_stride, float *y, int64_t y_stride, int B, int64_t L, int orig, int new_,
+                     int width, const float *table, void *stream) {
+  return resample_f32(x, x_stride, y, y_stride, B, L, orig, new_, width, table, S(stream));
+}
 int isi_rel_attention_f32(const isi_attn_args *args, void *stream) { return rel_attention_f32(args, S(stream)); }
 size_t isi_rel_attention_workspace_bytes(const isi_attn_args *args) { return rel_attention_workspace_bytes(args); }
 size_t isi_rel_attention_bwd_workspace_floats(const isi_attn_args *fwd) { return rel_attention_bwd_workspace_floats(fwd); }

@@ -327,6 +327,10 @@ int spec_inverse_prepare_bwd_f32(const float *spec, const float *da, const float
                                  hipStream_t st);
 int overlap_add_f32(const float *frames, float *audio, int B, int T, int n_fft, int hop, int left, int64_t L,
                     hipStream_t st);
+int resample_geometry(int fs_in, int fs_out, int *orig, int *new_, int *width, int *taps);
+int64_t resample_out_len(int64_t L, int orig, int new_);
+int resample_f32(const float *x, int64_t x_stride, float *y, int64_t y_stride, int B, int64_t L, int orig, int new_,
+                 int width, const float *table, hipStream_t st);
 
 size_t packed_conv_weight_floats(int Cout, int Cin, int KH, int KW);
 size_t packed_convT_k4s2_weight_floats(int Cin, int Cout);

@@ -6,9 +6,11 @@ query arguments and JSON schema for the operations built on MI355X
              top_conditioning, bottom_conditioning: {modality: value[F][T]}}          (:685-870,934-1000)
   GET/POST /generate?pitch=&instrument_family_str=&temperature=                         (:376-443)
   POST /erase?eraser_amplitude=&start_index_top=                                        (:873-931)
-  POST /get-audio   -> audio/wav (16-bit PCM written with the standard library)         (:1003-1021)
+  POST /get-audio[?fs_hz=]   -> audio/wav (16-bit PCM written with the standard library); `fs_hz` (not in the
+       reference) asks for the audio resampled to that rate                               (:1003-1021)
   POST /analyze-audio?pitch=&instrument_family_str=   multipart file `audio` (RIFF / PCM 16-bit or float32, mono or
-       averaged to mono, at the models' sampling rate: read with the standard library, no resampler)      (:624-667)
+       averaged to mono, at any sampling rate the resampler takes -- 44.1 and 48 kHz recordings are converted to
+       the models' rate on the GPU, GANsynth_pytorch/resample.py; read with the standard library)  (:557-568,624-667)
   POST /top-conditioned-sample?instrument_family_str=&min_pitch=&max_pitch=&temperature=&top_p=&top_k=
        body {top_code, bottom_code} -> application/zip of `{family}-{pitch}.wav`, one per pitch             (:1049-1115)
   GET/POST /sample-from-dataset?duration_top=&pitch=&pitch_class=&octave=&instrument_family_str=
@@ -33,6 +35,8 @@ import flask
 import torch
 
 import inpainting
+from GANsynth_pytorch import resample as _resample
+from GANsynth_pytorch.wavfile import read_wav
 
 
 def _wav_bytes(audio: torch.Tensor, fs_hz: int) -> bytes:
@@ -43,31 +47,8 @@ def _wav_bytes(audio: torch.Tensor, fs_hz: int) -> bytes:
 
 
 def _read_wav(data: bytes):
-    """RIFF/WAVE bytes -> (float32 mono tensor in [-1, 1], sampling rate): PCM 16-bit or IEEE float32, the two formats
-    the reference's front end uploads (the reference decodes with torchaudio, absent here)."""
-    if data[:4] != b"RIFF" or data[8:12] != b"WAVE":
-        raise ValueError("not a RIFF/WAVE file")
-    pos, fmt, payload = 12, None, None
-    while pos + 8 <= len(data):
-        tag, size = data[pos:pos + 4], struct.unpack("<I", data[pos + 4:pos + 8])[0]
-        body = data[pos + 8:pos + 8 + size]
-        if tag == b"fmt ":
-            fmt = struct.unpack("<HHIIHH", body[:16])
-        elif tag == b"data":
-            payload = body
-        pos += 8 + size + (size & 1)
-    if fmt is None or payload is None:
-        raise ValueError("WAVE file without fmt / data chunk")
-    code, channels, rate, _, _, bits = fmt
-    if code == 1 and bits == 16:
-        x = torch.frombuffer(bytearray(payload[:len(payload) // 2 * 2]), dtype=torch.int16).float() / 32768.0
-    elif code == 3 and bits == 32:
-        x = torch.frombuffer(bytearray(payload[:len(payload) // 4 * 4]), dtype=torch.float32).clone()
-    else:
-        raise ValueError(f"unsupported WAVE encoding (format {code}, {bits} bits)")
-    if channels > 1:
-        x = x[:x.numel() // channels * channels].reshape(-1, channels).mean(1)
-    return x, rate
+    """RIFF/WAVE bytes -> (float32 mono tensor in [-1, 1], sampling rate): `GANsynth_pytorch.wavfile.read_wav`."""
+    return read_wav(data)
 
 
 def create_app(vqvae, transformer_top, transformer_bottom, label_encoders_per_modality: Mapping[str, object],
@@ -145,8 +126,15 @@ def create_app(vqvae, transformer_top, transformer_bottom, label_encoders_per_mo
             flask.abort(501)
         top_code, bottom_code = codes(flask.request.get_json(force=True))
         audio = inpainting.codes_to_audio(vqvae, spectrograms_helper, top_code, bottom_code)[0]
-        return flask.send_file(io.BytesIO(_wav_bytes(audio, spectrograms_helper.fs_hz)), mimetype="audio/wav",
-                               max_age=0)
+        fs_hz = flask.request.args.get('fs_hz', type=int, default=None)
+        if fs_hz is None:
+            fs_hz = spectrograms_helper.fs_hz
+        else:
+            try:
+                audio = _resample.resample(audio, spectrograms_helper.fs_hz, fs_hz)
+            except ValueError as e:
+                flask.abort(400, description=str(e))
+        return flask.send_file(io.BytesIO(_wav_bytes(audio, fs_hz)), mimetype="audio/wav", max_age=0)
 
     @app.route('/analyze-audio', methods=['POST'])
     def analyze_audio():
@@ -159,7 +147,14 @@ def create_app(vqvae, transformer_top, transformer_bottom, label_encoders_per_mo
         except (KeyError, ValueError, struct.error) as e:
             flask.abort(400, description=str(e))
         if rate != spectrograms_helper.fs_hz:
-            flask.abort(400, description=f"audio at {rate} Hz: the models run at {spectrograms_helper.fs_hz} Hz (no resampler here)")
+            # flask_server.py:557-568,644-649: the upload is converted to the models' rate.  Only what survives the trim
+            # to max_sound_duration_s is converted (the filter reaches `width` input samples past an output's instant)
+            try:
+                _, _, width, _ = _resample.geometry(rate, spectrograms_helper.fs_hz)
+                audio = audio[:int(max_sound_duration_s * rate) + 2 * width]
+                audio = _resample.resample(audio.to(device), rate, spectrograms_helper.fs_hz)
+            except ValueError as e:
+                flask.abort(400, description=str(e))
         res_n = inpainting.top_resolution_n(vqvae, transformer_top, transformer_bottom, spectrograms_helper, device)
         duration_n = inpainting.adapt_duration(audio.numel(), spectrograms_helper.fs_hz, max_sound_duration_s, res_n,
                                                transformer_top.shape[1])

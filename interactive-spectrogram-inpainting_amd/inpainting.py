@@ -538,11 +538,16 @@ def top_resolution_n(vqvae, transformer_top, transformer_bottom, spectrograms_he
 
 
 @torch.no_grad()
-def analyze_audio(vqvae, spectrograms_helper, audio: torch.Tensor, duration_n: int, device):
+def analyze_audio(vqvae, spectrograms_helper, audio: torch.Tensor, duration_n: int, device, fs_hz: Optional[int] = None):
     """The compute of `/analyze-audio` (flask_server.py:624-667): mono audio [samples] at the models' rate, trimmed /
     zero-padded to `duration_n` (what `from_wavfile(path, duration_n=...)` does), -> spectrogram -> `VQVAE.encode` ->
-    (top_code, bottom_code)."""
-    x = audio.to(device=device, dtype=torch.float32).reshape(-1)[:duration_n]
+    (top_code, bottom_code).  `fs_hz`: the rate of `audio` when it is not the models' -- it is resampled first
+    (GANsynth_pytorch/resample.py; `duration_n` counts samples at the models' rate)."""
+    x = audio.to(device=device, dtype=torch.float32).reshape(-1)
+    if fs_hz is not None and int(fs_hz) != int(spectrograms_helper.fs_hz):
+        from GANsynth_pytorch.resample import resample
+        x = resample(x, fs_hz, spectrograms_helper.fs_hz)
+    x = x[:duration_n]
     if x.numel() < duration_n:
         x = torch.nn.functional.pad(x, (0, duration_n - x.numel()))
     spec = spectrograms_helper.to_spectrogram(x.unsqueeze(0))

@@ -932,6 +932,11 @@ size_t isi_vq_conv1x1_workspace_floats(int C0, int C1, int D);
  * weight laid out {packed [D][Kpad] | pair copy | fragments} with isi_vqvae_w.w16 = 2 lets isi_vqvae_run skip the pre-kernel in
  * front of each search (its two histograms are then zeroed by one launch). */
 int isi_vq_pack_fragments_f32(const float *packed_w16, float *frag_out, int Kpad, void *stream);
+/* The LDS content the fused search works on -- both f16 planes of the codebook, |e|^2 adjusted for far and non-finite
+ * codes, the far-code words -- as ONE image of isi_vq_planes_bytes(K) bytes (16-byte aligned), made once per codebook
+ * instead of by every workgroup of every launch (isi_codebook_w.planes).  D = 64. */
+size_t isi_vq_planes_bytes(int K);
+int isi_vq_pack_planes_f32(const float *codes_kd, const float *e2, void *planes_out, int D, int K, void *stream);
 /* 1 when the fused launch covers the shape (D = 64, 32-channel multiples, C0 + C1 <= 256, both code planes in LDS) */
 int isi_vq_conv1x1_fusable(int C0, int C1, int D, int K);
 
@@ -979,6 +984,8 @@ typedef struct isi_codebook_w {
   const float *codes_kd; /* [K][D] */
   const float *e2;       /* [K]    */
   int D, K;
+  const void *planes;    /* optional (NULL: derived per launch): isi_vq_pack_planes_f32 of codes_kd / e2, read by the
+                          * fused searches of isi_vqvae_run; must be re-made whenever the codebook changes */
 } isi_codebook_w;
 
 typedef struct isi_vqvae_w { /* VQVAE.__init__, vqvae.py:126-216 */

@@ -43,6 +43,8 @@ struct FirstArgs {
   float *out2;              // with out_pair: dense fp32 twin of the output (the training tape), or null
   const float *gate;        // fp32 output only: dense tensor laid out like it; out = gate > 0 ? value : 0 (the input gradient
                             // of the decoder's 2-channel last layer IS this convolution: its ReLU mask rides here)
+  int32_t *zero;            // optional: workgroup 0 zeroes zero[0 .. zero_words) -- the forward's two code histograms and the
+  int zero_words;           // ticket of its fused statistics (vqvae_run.cpp), consumed by LATER launches of the stream only
 };
 
 
@@ -113,6 +115,8 @@ __global__ __launch_bounds__(256) void conv_first_kernel(const FirstArgs p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int col = lane & 31, half = lane >> 5;
   float *tb = tbuf[wave];
+  if (p.zero && blockIdx.x == 0)
+    for (int i = tid; i < p.zero_words; i += 256) p.zero[i] = 0;
 
   // weights of this lane's output channels: k = 8 s + 4 half + e  (packed [Cout][32], k = tap * 2 + c)
   float4 bw[4][NT];
@@ -201,6 +205,8 @@ __global__ __launch_bounds__(256) void conv_first_f16x3_kernel(const FirstArgs p
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int col = lane & 31, half = lane >> 5;
   float *tb = tbuf[wave];
+  if (p.zero && blockIdx.x == 0)
+    for (int i = tid; i < p.zero_words; i += 256) p.zero[i] = 0;
 
   s16x8f bh[2][NT], bl[2][NT];
 #pragma unroll
@@ -313,8 +319,10 @@ bool conv_first_applicable(const isi_src *s0, const isi_src *s1, const isi_src *
 
 int conv_first_f32(const isi_src *s0, const float *packed_w, const float *bias, const isi_dst *dst, int B, int H,
                    int W, int Cout, int OH, int OW, int64_t in_extent, int flags, hipStream_t stream, float *twin,
-                   const float *gate) {
+                   const float *gate, int32_t *zero, int zero_words) {
   FirstArgs a;
+  if (zero && zero_words <= 0) return invalid("conv_first: bad zeroing request");
+  a.zero = zero; a.zero_words = zero ? zero_words : 0;
   if (twin && !(flags & ISI_CONV_OUT_PAIR)) return unsupported("conv_first: an fp32 twin accompanies a pair-format output");
   if (gate && (flags & (ISI_CONV_OUT_PAIR | ISI_CONV_GATE_PAIR))) return unsupported("conv_first: the gated epilogue writes and reads fp32");
   a.out2 = twin; a.gate = gate;

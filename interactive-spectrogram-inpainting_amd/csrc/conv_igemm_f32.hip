@@ -691,9 +691,10 @@ constexpr int64_t kMaxElems = (int64_t)1 << 30;  // 4 GiB of fp32: 32-bit byte o
 
 int conv2d_f32(const isi_src *s0, const isi_src *s1, const float *packed_w, const float *bias,
                const isi_src *res, const isi_dst *dst, int B, int H, int W, int Cout, int KH,
-               int KW, int stride, int pad, int relu, hipStream_t stream, const float *gate, float *twin) {
+               int KW, int stride, int pad, int relu, hipStream_t stream, const float *gate, float *twin, int32_t *zero,
+               int zero_words) {
   return conv2d_batched_f32(s0, s1, packed_w, bias, res, dst, B, H, W, Cout, KH, KW, stride, pad, relu, 1, 0, 0, 0, 0,
-                            stream, gate, twin);
+                            stream, gate, twin, zero, zero_words);
 }
 
 // nz independent convolutions of one shape in a single launch (grid z): set z reads source 0 at
@@ -702,7 +703,8 @@ int conv2d_f32(const isi_src *s0, const isi_src *s1, const float *packed_w, cons
 int conv2d_batched_f32(const isi_src *s0, const isi_src *s1, const float *packed_w, const float *bias,
                        const isi_src *res, const isi_dst *dst, int B, int H, int W, int Cout, int KH,
                        int KW, int stride, int pad, int relu, int nz, int64_t zs_in0, int64_t zs_w,
-                       int64_t zs_res, int64_t zs_out, hipStream_t stream, const float *gate, float *twin) {
+                       int64_t zs_res, int64_t zs_out, hipStream_t stream, const float *gate, float *twin, int32_t *zero,
+                       int zero_words) {
   if (nz < 1 || nz > 65535) return invalid("conv2d: bad batch count");
   if (twin && (gate || nz > 1 || !(relu & ISI_CONV_OUT_PAIR))) return unsupported("conv2d: an fp32 twin accompanies a single pair-format output");
   if (gate && (nz > 1 || (relu & (ISI_CONV_IN0_PAIR | ISI_CONV_IN1_PAIR | ISI_CONV_OUT_PAIR))))
@@ -728,7 +730,10 @@ int conv2d_batched_f32(const isi_src *s0, const isi_src *s1, const float *packed
       aligned16(packed_w) && conv_first_applicable(s0, s1, res, dst, Cout, KH, KW, stride, pad, OH, OW, nz)) {
     // the 2-channel first layer has its own HBM-oriented kernel (conv_first_f32.hip), bit-identical results
     if (relu & (ISI_CONV_IN0_PAIR | ISI_CONV_IN1_PAIR)) return unsupported("conv2d: pair-format source on the 2-channel layer");
-    return conv_first_f32(s0, packed_w, bias, dst, B, H, W, Cout, OH, OW, e0, relu, stream, twin, gate);
+    return conv_first_f32(s0, packed_w, bias, dst, B, H, W, Cout, OH, OW, e0, relu, stream, twin, gate, zero, zero_words);
+  }
+  if (zero) {   // no other kernel carries the request
+    if (const int rcz = vq_zero_counts(zero, zero_words, stream)) return rcz;
   }
   // the prior's linear layers: rows of a dense matrix, three-term products -> the GEMM kernel (gemm_split_f32.hip)
   if (nz == 1 && !(gate && (relu & ISI_CONV_GATE_PAIR)) && !two && KH == 1 && KW == 1 && stride == 1 && pad == 0 && B == 1 && H == 1 && s0->sc == 1 &&

@@ -25,6 +25,7 @@ const KnobEntry kKnobTable[] = {
     {"ISI_NO_PAIRS", &Knobs::no_pairs, 0, false},
     {"ISI_NO_CONV_FIRST", &Knobs::no_conv_first, 0, false},
     {"ISI_NO_VQ_FUSION", &Knobs::no_vq_fusion, 0, false},
+    {"ISI_NO_SETUP_FUSION", &Knobs::no_setup_fusion, 0, false},
     {"ISI_NO_CONV_PAIR_KERNEL", &Knobs::no_conv_pair_kernel, 0, false},
     {"ISI_NO_RESBLOCK_PAIR_KERNEL", &Knobs::no_resblock_pair_kernel, 0, false},
     {"ISI_NO_CONVT_PAIR_KERNEL", &Knobs::no_convt_pair_kernel, 0, false},
@@ -516,6 +517,10 @@ int isi_vq_conv1x1_nearest_tape_f32(const isi_src *src0, const isi_src *src1, co
 size_t isi_vq_conv1x1_workspace_floats(int C0, int C1, int D) { return vq_conv1x1_workspace_floats(C0, C1, D); }
 int isi_vq_pack_fragments_f32(const float *packed_w16, float *frag_out, int Kpad, void *stream) {
   return vq_pack_fragments_f32(packed_w16, frag_out, Kpad, S(stream));
+}
+size_t isi_vq_planes_bytes(int K) { return vq_planes_bytes(K); }
+int isi_vq_pack_planes_f32(const float *codes_kd, const float *e2, void *planes_out, int D, int K, void *stream) {
+  return vq_pack_planes_f32(codes_kd, e2, planes_out, D, K, S(stream));
 }
 int isi_vq_conv1x1_fusable(int C0, int C1, int D, int K) { return vq_conv1x1_fusable(C0, C1, D, K) ? 1 : 0; }
 int isi_vq_nearest_flags_f32(const float *z, const float *codes_kd, const float *e2, int64_t *idx_out,

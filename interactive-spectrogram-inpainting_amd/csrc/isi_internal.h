@@ -30,7 +30,7 @@ bool conv_first_applicable(const isi_src *s0, const isi_src *s1, const isi_src *
                            int KH, int KW, int stride, int pad, int OH, int OW, int nz);
 int conv_first_f32(const isi_src *s0, const float *packed_w, const float *bias, const isi_dst *dst, int B, int H,
                    int W, int Cout, int OH, int OW, int64_t in_extent, int flags, hipStream_t stream, float *twin = nullptr,
-                   const float *gate = nullptr);
+                   const float *gate = nullptr, int32_t *zero = nullptr, int zero_words = 0);
 bool conv_pair_sources_ok(int C0, int C1, int Cout, int taps);
 // conv_pair_f16.hip: the LDS-DMA implicit-GEMM kernel of the pair pipeline (pair8 sources, blocked W16 weights)
 struct PairConvArgs {
@@ -61,12 +61,14 @@ int convT_pair_f16(const float *in, const float *w16, const float *bias, float *
 int conv2d_f32(const isi_src *s0, const isi_src *s1, const float *packed_w, const float *bias,
                const isi_src *res, const isi_dst *dst, int B, int H, int W, int Cout, int KH,
                int KW, int stride, int pad, int relu, hipStream_t stream, const float *gate = nullptr,
-               float *twin = nullptr);
+               float *twin = nullptr, int32_t *zero = nullptr, int zero_words = 0);
 int conv2d_batched_f32(const isi_src *s0, const isi_src *s1, const float *packed_w, const float *bias,
                        const isi_src *res, const isi_dst *dst, int B, int H, int W, int Cout, int KH,
                        int KW, int stride, int pad, int relu, int nz, int64_t zs_in0, int64_t zs_w,
                        int64_t zs_res, int64_t zs_out, hipStream_t stream, const float *gate = nullptr,
-                       float *twin = nullptr);
+                       float *twin = nullptr, int32_t *zero = nullptr, int zero_words = 0);
+// (zero / zero_words: int32 words the launch clears for LATER launches of the stream -- by workgroup 0 of the 2-channel
+// first-layer kernel, by a launch of their own in front of any other kernel)
 int conv_transpose2d_k4s2_f32(const isi_src *s, const float *packed_w, const float *bias,
                               const isi_dst *dst, int B, int H, int W, int Cout, int relu,
                               hipStream_t stream, const float *gate = nullptr, float *twin = nullptr);
@@ -292,7 +294,11 @@ int vq_debug_stamps(long long *host, int n);
 int vq_conv1x1_nearest_f32(const isi_src *s0, const isi_src *s1, const float *w16, const float *bias, const float *codes,
                            const float *e2, int64_t *idx, float *q, float *q_pair, int32_t *counts, float *sse_part,
                            float *workspace, int B, int H, int W, int D, int K, hipStream_t stream, bool zero_counts = false,
-                           float *z_out = nullptr, const float *wfrag_packed = nullptr);
+                           float *z_out = nullptr, const float *wfrag_packed = nullptr, const void *planes = nullptr);
+// the pack-time image of a codebook's LDS content (planes, adjusted |e|^2, far words): what the fused search otherwise
+// derives from codes_kd / e2 in every workgroup of every launch
+size_t vq_planes_bytes(int K);
+int vq_pack_planes_f32(const float *codes_kd, const float *e2, void *planes_out, int D, int K, hipStream_t stream);
 int vq_pack_fragments_f32(const float *packed_w16, float *frag_out, int Kpad, hipStream_t stream);
 size_t vq_conv1x1_workspace_floats(int C0, int C1, int D);
 int vq_zero_counts(int32_t *counts, int K, hipStream_t stream);

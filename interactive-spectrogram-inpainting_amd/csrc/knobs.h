@@ -12,6 +12,8 @@ struct Knobs {
   int no_pairs;                 // ISI_NO_PAIRS: fused forward on fp32 activations instead of the pair pipeline
   int no_conv_first;            // ISI_NO_CONV_FIRST: generic gather kernel for the 2-channel first layer
   int no_vq_fusion;             // ISI_NO_VQ_FUSION: quantize_conv and search as two launches
+  int no_setup_fusion;          // ISI_NO_SETUP_FUSION: the forward as before the pack-time set-up: codebook planes filled by every workgroup of the
+                                // searches, histogram zeroing and both levels' statistics as launches of their own
   int no_conv_pair_kernel;      // ISI_NO_CONV_PAIR_KERNEL: register-staged kernel instead of the LDS-DMA one
   int no_resblock_pair_kernel;  // ISI_NO_RESBLOCK_PAIR_KERNEL
   int no_convt_pair_kernel;     // ISI_NO_CONVT_PAIR_KERNEL: four phase launches instead of the fused transposed conv

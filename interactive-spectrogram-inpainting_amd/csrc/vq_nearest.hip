@@ -17,6 +17,7 @@
 // half-waves (lanes l and l+32 hold interleaved code rows of the same vector)
 // are merged with a single cross-lane exchange at the end.
 #include "isi_common.h"
+#include "isi_internal.h"
 #include "knobs.h"
 #include "prof.h"
 #include "split_f16.h"
@@ -229,6 +230,25 @@ __device__ __forceinline__ void vq_fill_planes(unsigned short *cbh, unsigned sho
     const float n2 = e2g[k];
     if (!(n2 - n2 == 0.f)) e2[k] = -kVqPad;
   }
+}
+
+// The same LDS content from its pack-time IMAGE (vq_pack_planes_f32: the bytes vq_fill_planes leaves, made once per
+// codebook): [planes hi | planes lo | adjusted |e|^2] as they lie in LDS, then the far words padded to 16 bytes.  Nothing
+// is computed: 16-byte LDS-DMA copies (lane l of a wave's instruction lands at base + 16 l: the image is copied in
+// lane order), the far words through registers; only the histogram is zeroed.  The caller waits (the DMA counts in
+// vmcnt) and synchronises before it reads the planes.
+constexpr int vq_planes_main_bytes(int Kp) { return Kp * (64 * 2 * 2 + 4); }
+constexpr int vq_planes_far_words(int Kp) { return (1 + Kp / 32 + 3) & ~3; }
+__device__ __forceinline__ void vq_copy_planes(float *smem, int *hist, const char *image, int Kp, int tid) {
+  typedef __attribute__((address_space(1))) const void *gptr_t;
+  typedef __attribute__((address_space(3))) void *lptr_t;
+  const int n16 = vq_planes_main_bytes(Kp) / 16;
+  for (int i = tid; i < n16; i += VQ_BLOCK)
+    __builtin_amdgcn_global_load_lds((gptr_t)(image + (size_t)i * 16), (lptr_t)(reinterpret_cast<char *>(smem) + (size_t)i * 16), 16, 0, 0);
+  int *far = vq_far_area(hist, Kp);
+  const int *far_img = reinterpret_cast<const int *>(image + vq_planes_main_bytes(Kp));
+  for (int i = tid; i < 1 + Kp / 32; i += VQ_BLOCK) far[i] = far_img[i];
+  for (int i = tid; i < Kp; i += VQ_BLOCK) hist[i] = 0;
 }
 
 __device__ __forceinline__ float vq_quad_dot(const float4 a, const float4 b) {
@@ -555,12 +575,17 @@ __global__ __launch_bounds__(VQ_BLOCK) void vq_nearest_f16x3_kernel(
 __device__ long long g_vq_stamps[128];
 #define ISI_VQ_STAMP(i_) do { if (blockIdx.x == 8 && (wave & 3) == 0 && lane == 0 && it == (int64_t)blockIdx.x + (int64_t)gridDim.x) \
     g_vq_stamps[(wave >> 2) * 64 + (i_)] = __builtin_readcyclecounter(); } while (0)
+// (the set-up in front of the tile loop -- the codebook planes' fill: stamps 6 and 7, same workgroup and waves)
+#define ISI_VQ_STAMP_SETUP(i_) do { if (blockIdx.x == 8 && (wave & 3) == 0 && lane0 == 0) \
+    g_vq_stamps[(wave >> 2) * 64 + (i_)] = __builtin_readcyclecounter(); } while (0)
 #else
 #define ISI_VQ_STAMP(i_) do { } while (0)
+#define ISI_VQ_STAMP_SETUP(i_) do { } while (0)
 #endif
 struct VqFusedArgs {
   const float *in0, *in1, *w16, *bias, *codes, *e2;
   const float *wfrag;                    // fragment-major copy of w16 (vq_weight_fragments_kernel)
+  const char *planes;                    // nullable: pack-time image of the codebook's LDS content (vq_copy_planes); null: filled here
   int64_t *idx;
   float *q, *q_pair;
   float *z_out;                          // nullable: z itself ([N][64] fp32), for the training step's backward and EMA sums
@@ -605,8 +630,17 @@ __global__ __launch_bounds__(VQ_BLOCK) void vq_conv1x1_nearest_kernel(const VqFu
   const int lane0 = tid & 63;
   const int wave = tid >> 6;
 
-  vq_fill_planes(cbh, cbl, e2, hist, p.codes, p.e2, K, Kp, tid);
-  __syncthreads();
+  ISI_VQ_STAMP_SETUP(6);
+  // (uniform) the image's copy is only REQUESTED here: it travels together with the first tile's activations, and the
+  // workgroup meets behind that tile's 1x1 convolution, in front of the first read of the planes
+  bool planes_pending = p.planes != nullptr;
+  if (planes_pending) {
+    vq_copy_planes(smem, hist, p.planes, Kp, tid);
+  } else {
+    vq_fill_planes(cbh, cbl, e2, hist, p.codes, p.e2, K, Kp, tid);
+    __syncthreads();
+  }
+  ISI_VQ_STAMP_SETUP(7);
 
   const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.in0), 0, p.in0_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.in1), 0, p.in1_bytes, 0x00020000);
@@ -723,6 +757,10 @@ __global__ __launch_bounds__(VQ_BLOCK) void vq_conv1x1_nearest_kernel(const VqFu
       for (int j = 0; j < NQ; ++j) *reinterpret_cast<float4 *>(p.z_out + n * D + (2 * j + half) * 4) = zq[j];
     }
     ISI_VQ_STAMP(2);
+    if (planes_pending) {     // (uniform; every workgroup has a first tile.  hipcc retires the LDS-DMA, vmcnt(0), at the
+      __syncthreads();        // first use of a loaded register above at the latest)
+      planes_pending = false;
+    }
     // ---- search (candidates on the f16 pipe, decision in fp32; shared with the stand-alone kernel)
     VqCand cand{0.f, 1.f, (int)(n & 255), (int)(n & 255) + 256};
     if (!ISI_VQ_DBGBIT(p, 1)) cand = vq_candidates_f16(cbh, cbl, e2, Kp, zq, col, half);
@@ -975,6 +1013,41 @@ int vq_pack_fragments_f32(const float *packed_w16, float *frag_out, int Kpad, hi
   return check_launch("vq_pack_fragments");
 }
 
+// The image vq_copy_planes reads: ONE workgroup runs vq_fill_planes itself and writes its LDS out -- the same code, so
+// the same bytes, far and non-finite rows included.
+__global__ __launch_bounds__(VQ_BLOCK) void vq_pack_planes_kernel(const float *__restrict__ codes, const float *__restrict__ e2g,
+                                                                  int *__restrict__ image, int K) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int Kp = (K + 31) & ~31;
+  unsigned short *cbh = reinterpret_cast<unsigned short *>(smem);
+  unsigned short *cbl = cbh + (size_t)Kp * 64;
+  float *e2 = reinterpret_cast<float *>(cbl + (size_t)Kp * 64);
+  int *hist = reinterpret_cast<int *>(e2 + Kp + ISI_VQ_WAVES);
+  const int tid = threadIdx.x;
+  vq_fill_planes(cbh, cbl, e2, hist, codes, e2g, K, Kp, tid);
+  __syncthreads();
+  const int nmain = vq_planes_main_bytes(Kp) / 4, nfar = vq_planes_far_words(Kp);
+  const int *far = vq_far_area(hist, Kp);
+  for (int i = tid; i < nmain; i += VQ_BLOCK) image[i] = reinterpret_cast<const int *>(smem)[i];
+  for (int i = tid; i < nfar; i += VQ_BLOCK) image[nmain + i] = i < 1 + Kp / 32 ? far[i] : 0;
+}
+size_t vq_planes_bytes(int K) {
+  if (K <= 0) return 0;
+  const int Kp = (K + 31) & ~31;
+  return (size_t)vq_planes_main_bytes(Kp) + (size_t)vq_planes_far_words(Kp) * 4;
+}
+int vq_pack_planes_f32(const float *codes_kd, const float *e2, void *planes_out, int D, int K, hipStream_t stream) {
+  if (!codes_kd || !e2 || !planes_out || K <= 0 || ((reinterpret_cast<uintptr_t>(codes_kd) | reinterpret_cast<uintptr_t>(planes_out)) & 15))
+    return invalid("vq_pack_planes: bad argument (codes and image 16-byte aligned)");
+  const int Kp = (K + 31) & ~31;
+  if (D != 64 || vq_planes_lds_bytes(Kp) > 150 * 1024) return unsupported("vq_pack_planes: D = 64 with both planes in LDS");
+  const size_t smem = vq_planes_lds_bytes(Kp);
+  if (hipFuncSetAttribute(reinterpret_cast<const void *>(vq_pack_planes_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
+    return check_launch("hipFuncSetAttribute(vq_pack_planes)");
+  hipLaunchKernelGGL(vq_pack_planes_kernel, dim3(1), dim3(VQ_BLOCK), smem, stream, codes_kd, e2, static_cast<int *>(planes_out), K);
+  return check_launch("vq_pack_planes_f32");
+}
+
 int vq_debug_stamps(long long *host, int n) {
 #ifdef ISI_MEASURE
   return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_vq_stamps), sizeof(long long) * (size_t)(n < 128 ? n : 128)) == hipSuccess ? 0 : -2;
@@ -987,7 +1060,8 @@ int vq_debug_stamps(long long *host, int n) {
 int vq_conv1x1_nearest_f32(const isi_src *s0, const isi_src *s1, const float *w16, const float *bias, const float *codes,
                            const float *e2, int64_t *idx, float *q, float *q_pair, int32_t *counts, float *sse_part,
                            float *workspace, int B, int H, int W, int D, int K, hipStream_t stream, bool zero_counts,
-                           float *z_out, const float *wfrag_packed) {
+                           float *z_out, const float *wfrag_packed, const void *planes) {
+  if (planes && (reinterpret_cast<uintptr_t>(planes) & 15)) return invalid("vq_conv1x1: the planes image must be 16-byte aligned");
   if (!wfrag_packed && (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15))) return invalid("vq_conv1x1: workspace (vq_conv1x1_workspace_floats, 16-byte aligned)");
   if (wfrag_packed && (reinterpret_cast<uintptr_t>(wfrag_packed) & 15)) return invalid("vq_conv1x1: the packed fragments must be 16-byte aligned");
   if (!s0 || !s0->ptr || !w16 || !codes || !e2 || !idx || (!q && !q_pair) || !counts || !sse_part) return invalid("vq_conv1x1: null pointer");
@@ -1012,6 +1086,7 @@ int vq_conv1x1_nearest_f32(const isi_src *s0, const isi_src *s1, const float *w1
   const int Kp = (K + 31) & ~31;
   const size_t smem = vq_planes_lds_bytes(Kp);
   a.wfrag = wfrag_packed ? wfrag_packed : workspace;
+  a.planes = static_cast<const char *>(planes);
   if (wfrag_packed) {          // fragments made at pack time (isi_vq_pack_fragments_f32): no pre-kernel
     if (zero_counts) {
       const int rc0 = vq_zero_counts(counts, K, stream);

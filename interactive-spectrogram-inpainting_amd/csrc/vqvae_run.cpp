@@ -152,8 +152,10 @@ int run_res_stack(int n_res, const isi_conv_w *res3, const isi_conv_w *res1, Act
 
 // RosinalityEncoder (encoder_decoder.py:38-126).  `in` may be NCHW.
 // `in_pair`: the input is in the pair format; `pairs`: every tensor this encoder writes (including its output) is.
+// `zero` / `zero_words`: int32 words the encoder's FIRST launch clears for later launches of the stream (conv2d_f32).
 int run_encoder(const isi_encoder_w &e, isi_src in, int B, int H, int W, float *s0, float *s1,
-                float *hid, float *final_out, Act &out, int pf, bool in_pair, bool pairs, hipStream_t st) {
+                float *hid, float *final_out, Act &out, int pf, bool in_pair, bool pairs, hipStream_t st,
+                int32_t *zero = nullptr, int zero_words = 0) {
   Act cur{nullptr, in.C, H, W};
   isi_src cs = in;
   bool stack_pairs = false;
@@ -164,8 +166,10 @@ int run_encoder(const isi_encoder_w &e, isi_src in, int B, int H, int W, float *
     float *o = (cur.p == s0) ? s1 : s0;
     isi_dst d = dst_nhwc(o, e.down[i].Cout, OH, OW);
     int rc = conv2d_f32(&cs, nullptr, e.down[i].w, e.down[i].bias, nullptr, &d, B, cur.H, cur.W,
-                        e.down[i].Cout, 4, 4, 2, 1, 1 | pf | (cp ? ISI_CONV_IN0_PAIR : 0) | op, st);
+                        e.down[i].Cout, 4, 4, 2, 1, 1 | pf | (cp ? ISI_CONV_IN0_PAIR : 0) | op, st, nullptr, nullptr,
+                        zero, zero_words);
     if (rc) return rc;
+    zero = nullptr;
     cur = Act{o, e.down[i].Cout, OH, OW};
     cs = src_nhwc(cur.p, cur.C, cur.H, cur.W);
     cp = pairs;
@@ -175,7 +179,8 @@ int run_encoder(const isi_encoder_w &e, isi_src in, int B, int H, int W, float *
     isi_dst d = dst_nhwc(o, e.conv3.Cout, cur.H, cur.W);
     stack_pairs = res_stack_in_pairs(pairs, e.n_res, e.res3, B, cur.H, cur.W, e.conv3.Cout);
     int rc = conv2d_f32(&cs, nullptr, e.conv3.w, e.conv3.bias, nullptr, &d, B, cur.H, cur.W,
-                        e.conv3.Cout, 3, 3, 1, 1, 1 | pf | (cp ? ISI_CONV_IN0_PAIR : 0) | ((e.n_res && !stack_pairs) ? 0 : op), st);
+                        e.conv3.Cout, 3, 3, 1, 1, 1 | pf | (cp ? ISI_CONV_IN0_PAIR : 0) | ((e.n_res && !stack_pairs) ? 0 : op), st,
+                        nullptr, nullptr, zero, zero_words);
     if (rc) return rc;
     cur = Act{o, e.conv3.Cout, cur.H, cur.W};
   }
@@ -325,7 +330,8 @@ int run_quantizer_fused(const isi_codebook_w &cb, const isi_conv_w &w1x1, const 
   // both levels' histograms with one launch -- no pre-kernel in front of the search
   int rc = vq_conv1x1_nearest_f32(&a, b, w1x1.w + (size_t)w1x1.Cout * Kpad, w1x1.bias, cb.codes_kd, cb.e2, idx, q, q_pair,
                                   counts, sse_part, wfrag_ws, B, H, W, cb.D, cb.K, st, /*zero_counts*/ !frag_packed, nullptr,
-                                  frag_packed ? w1x1.w + (size_t)2 * w1x1.Cout * Kpad : nullptr);
+                                  frag_packed ? w1x1.w + (size_t)2 * w1x1.Cout * Kpad : nullptr,
+                                  knobs().no_setup_fusion ? nullptr : cb.planes);
   if (rc || !finalize) return rc;     // (finalize = false: the caller finishes both levels with one launch, vq_finalize2_f32)
   const int64_t N = (int64_t)B * H * W;
   return vq_finalize_f32(sse_part, vq_num_partials(N), counts, cb.K, N, cb.D, scalars2, st);
@@ -389,7 +395,11 @@ int plan(const isi_vqvae_w &w, int mode, const float *x, int B, int H, int W,
   // quantize_conv_{t,b} fused into the codebook searches: the pair pipeline only (pair8 sources, blocked weights)
   const bool fuse_vq = pairs && !w.no_quantize && !knobs().no_vq_fusion;
   const bool frag_packed = fuse_vq && w.w16 == 2 && (mode & ISI_MODE_ENCODE);
-  if (frag_packed) {
+  // Both histograms are zeroed by the first encoder launch (its workgroup 0: conv_first_f32.hip) instead of a launch of
+  // their own.  The workspace is the caller's and arrives with any content: zeroed per call.
+  // (ISI_NO_SETUP_FUSION: the zeroing launch, for the tests' A/B.)
+  const bool fuse_zero = frag_packed && !knobs().no_setup_fusion;
+  if (frag_packed && !fuse_zero) {
     rc = vq_zero_counts(counts, 2 * Kmax, st);
     if (rc) return rc;
   }
@@ -400,7 +410,8 @@ int plan(const isi_vqvae_w &w, int mode, const float *x, int B, int H, int W,
   if (mode & ISI_MODE_ENCODE) {
     if (!x) return invalid("vqvae: x is null");
     Act eb, et;
-    rc = run_encoder(w.enc_b, src_nchw(x, w.in_channel, H, W), B, H, W, s0, s1, hid, enc_b, eb, pf_enc, false, pairs, st);
+    rc = run_encoder(w.enc_b, src_nchw(x, w.in_channel, H, W), B, H, W, s0, s1, hid, enc_b, eb, pf_enc, false, pairs, st,
+                     fuse_zero ? counts : nullptr, 2 * Kmax);
     if (rc) return rc;
     rc = run_encoder(w.enc_t, src_nhwc(eb.p, eb.C, eb.H, eb.W), B, eb.H, eb.W, s0, s1, hid, enc_t, et, pf_enc, pairs,
                      pairs, st);

@@ -51,7 +51,7 @@ class isi_decoder_w(C.Structure):
 
 
 class isi_codebook_w(C.Structure):
-    _fields_ = [("codes_kd", C.c_void_p), ("e2", C.c_void_p), ("D", C.c_int), ("K", C.c_int)]
+    _fields_ = [("codes_kd", C.c_void_p), ("e2", C.c_void_p), ("D", C.c_int), ("K", C.c_int), ("planes", C.c_void_p)]
 
 
 class isi_vqvae_w(C.Structure):
@@ -196,6 +196,8 @@ SIGNATURES = {
     "isi_pair_decode_f32": (C.c_int, [_P, _P, C.c_int64, _P]),
     "isi_packed_convT_k4s2_weight_floats": (C.c_size_t, [C.c_int, C.c_int]),
     "isi_pack_codebook_f32": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
+    "isi_vq_planes_bytes": (C.c_size_t, [C.c_int]),
+    "isi_vq_pack_planes_f32": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
     "isi_conv2d_f32": (C.c_int, [C.POINTER(isi_src), C.POINTER(isi_src), _P, _P, C.POINTER(isi_src),
                                  C.POINTER(isi_dst), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                  C.c_int, C.c_int, C.c_int, C.c_int, _P]),

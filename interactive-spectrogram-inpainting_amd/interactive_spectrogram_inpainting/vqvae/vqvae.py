@@ -252,7 +252,15 @@ class VQVAE(nn.Module):
             # exactly by the kernel (vq_decide_f32: certificate or fp32 scan); only a non-finite code disqualifies.
             e = q.embed.detach()
             wmax.append(torch.where(torch.isfinite(e).all(), e.new_zeros(()), e.new_full((), float("inf"))))
-            return _hip.isi_codebook_w(codes.data_ptr(), e2.data_ptr(), q.dim, q.n_embed)
+            planes = None
+            if q.dim == 64 and _hip.lib().isi_vq_conv1x1_fusable(32, 0, q.dim, q.n_embed):
+                # the LDS image the fused searches copy instead of deriving it per workgroup and launch (csrc/vq_nearest.hip);
+                # it lives and dies with this plan, i.e. with the codebook's version
+                planes = torch.empty(_hip.lib().isi_vq_planes_bytes(q.n_embed), dtype=torch.uint8, device=codes.device)
+                _hip.check(_hip.lib().isi_vq_pack_planes_f32(codes.data_ptr(), e2.data_ptr(), planes.data_ptr(), q.dim, q.n_embed,
+                                                             C.c_void_p(_hip.stream_ptr(codes.device))), "isi_vq_pack_planes_f32")
+                keep.append(planes)
+            return _hip.isi_codebook_w(codes.data_ptr(), e2.data_ptr(), q.dim, q.n_embed, planes.data_ptr() if planes is not None else None)
 
         w = _hip.isi_vqvae_w()
         w.in_channel = self.in_channel

@@ -125,6 +125,36 @@ int64_t isi_resample_out_len(int64_t L, int orig, int new_);
 int isi_resample_f32(const float *x, int64_t x_stride, float *y, int64_t y_stride, int B, int64_t L,
                      int orig, int new_, int width, const float *table, void *stream);
 
+/* ------------------------------------------------ query-by-example search of a code database */
+/* "The stored sounds most like this one": weighted code-distance sums of Q query codemaps against N stored ones
+ * (specification tests/code_search_spec.py).  For one layer with codebook E [K, D]:
+ *   T[a][b]    = sum_d (E[a][d] - E[b][d])^2                      d ascending, fp32 fma
+ *   dist[j][n] = sum_c w[j][c] * T[query[j][c]][codes[n][c]]      query cells >= K (the priors' mask token) count nothing
+ * isi_code_distance_table_f32: codebook [K, D] row-major -> table [K, K].  T[a][a] is exactly 0 and T is bitwise
+ * symmetric; |T - T64| <= (D + 4) 2^-24 T64 against the float64 sum of the same fp32 codebook.  ISI_E_INVALID for a
+ * null or float-misaligned pointer, K <= 0, D <= 0; ISI_E_UNSUPPORTED for K > 65535.
+ * isi_code_search_workspace_bytes (host only): scratch of isi_code_search_f32, ceil(C / 256) * Q * N floats; 0 for
+ * sizes the search refuses.
+ * isi_code_search_f32: codes uint16 [N, C], query uint16 [Q, C], weights fp32 [Q, C] or NULL (1 on every cell),
+ * table fp32 [K, K], allowed uint8 [N] or NULL, dist fp32 [Q, N].  Items with allowed[n] == 0 get +inf.
+ * accumulate = 1 adds the sums to what dist holds (a second layer: the caller scales the weights by its factor).
+ * A stored code >= K is the index builder's error: it is clamped to K - 1, nothing is read outside the table.
+ * Deterministic and item-local: the bits of dist[j][n] depend on query[j], weights[j], codes[n] and the table only --
+ * not on N, Q, alignment, the launch geometry or the run.  Each product w * T is rounded once; the products of 256
+ * consecutive cells are added in cell order, the sums of those runs in run order; no atomics.  Against the float64
+ * sum of the same fp32 products' factors: |dist - spec| <= (C + 2) 2^-24 sum_c |w[c] T[..]|; exact when the table
+ * holds small non-negative integers, the weights are 0 or 1 and the sums stay below 2^24.
+ * No allocation, no host synchronisation; stream-ordered.  Checked before any launch: a null codes / query / table /
+ * dist / workspace, a misaligned pointer (2 bytes for codes and query, 4 for the others), N, C or K <= 0, Q outside
+ * 1..64, accumulate outside {0, 1} (ISI_E_INVALID); a workspace smaller than isi_code_search_workspace_bytes
+ * (ISI_E_WORKSPACE); K > 16384 -- one table row per staged cell must fit 64 KB of LDS; the quantiser's own limit is
+ * far below --, C > 256 * 65535, Q * N >= 2^39 (ISI_E_UNSUPPORTED).  isi_last_error() names the argument. */
+int isi_code_distance_table_f32(const float *codebook, float *table, int K, int D, void *stream);
+size_t isi_code_search_workspace_bytes(int64_t N, int64_t C, int K, int Q);
+int isi_code_search_f32(const uint16_t *codes, const uint16_t *query, const float *weights, const float *table,
+                        const uint8_t *allowed, float *dist, int64_t N, int64_t C, int K, int Q, int accumulate,
+                        void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------- measurement (bench.py) */
 /* Per-launch timing with HIP events recorded on the launch stream.  State is
  * per calling thread; `on` = 1 starts (earlier records cleared), 0 pauses, 2 resumes without

@@ -1,0 +1,254 @@
+// Query-by-example search of a code database (gfx950): weighted code-distance sums of Q query codemaps against N stored
+// ones.  The arithmetic is this project's own (specification tests/code_search_spec.py):
+//   T[a][b]    = sum_d (E[a][d] - E[b][d])^2                     (isi_code_distance_table_f32, fp32, d ascending)
+//   dist[j][n] = sum_c w[j][c] * T[query[j][c]][codes[n][c]]     (isi_code_search_f32; query cells >= K count nothing)
+//
+// Search.  One workgroup (512 threads) owns 512 IPT items of one query and one SPLIT of the cell range (CS_SPLIT = 256
+// consecutive cells).  It walks the split in chunks of `cc` cells: the chunk's table rows, already multiplied by the
+// cell's weight (rows[cl][k] = w[c] * T[query[c]][k], one rounding; zeros for a mask-token cell), are staged in LDS -- K
+// floats per cell, 64 KB per workgroup, two workgroups per CU -- and every lane then adds rows[cl][codes[n][c]] for its
+// own items, c ascending, into one fp32 register per item.  An item's codes are fetched into registers BEFORE the stage
+// is written.  At K <= 512 (32-cell chunks) a lane fetches the codes of TWO chunks at once -- the 128 bytes of a whole
+// cache line of its item's row -- for IPT = 2 items; measured against one chunk at a time with IPT = 4: 3-5 % faster on
+// the large cases, 26 % on the top maps with one query (twice as many workgroups in the launch's last wave).
+// The look-ups are random 4-byte LDS reads: a ds_read_b32 serves 2 groups of 32 lanes over 32 banks.  Per-split sums go
+// to the workspace [splits][Q][N]; a second kernel adds them, split ascending, and applies `allowed` and `accumulate`.
+// The order of every addition is a function of C and the cell index alone: no atomics, and dist[j][n] has the same
+// bits whatever N, Q, the item's place in the launch or the route the codes were read by.
+//
+// Limits: K <= 16384 (one table row per staged cell must fit the 64 KB stage), C <= 256 * 65535 (splits ride grid.y),
+// Q <= 64 (grid.z).  Codes are read as 16-byte vectors when C % 8 == 0, the base is 16-byte aligned and K <= 2048 (a
+// chunk then holds a multiple of 8 cells), one by one otherwise; table rows as float4 when K % 4 == 0 and the base is
+// 16-byte aligned.  A stored code >= K is clamped to K - 1: nothing is read outside the stage.
+#include "isi_common.h"
+#include "isi_internal.h"
+
+namespace isi {
+
+namespace {
+constexpr int CS_THREADS = 512;
+constexpr int CS_IPT = 4;                          // items per thread (2 on the whole-line route)
+constexpr int CS_SPLIT = 256;                      // cells per split: a function of nothing, so the summation order is C's alone
+constexpr int CS_STAGE_FLOATS = 16384;             // 64 KB
+constexpr int CS_MAX_CHUNK = 32;                   // cells per chunk at most (a multiple of 8 divides CS_SPLIT)
+constexpr int CS_MAX_K = CS_STAGE_FLOATS;
+constexpr int64_t CS_MAX_C = (int64_t)CS_SPLIT * 65535;
+constexpr int CS_MAX_Q = 64;
+
+int chunk_cells(int K) {
+  int cc = CS_STAGE_FLOATS / K;
+  if (cc > CS_MAX_CHUNK) cc = CS_MAX_CHUNK;
+  if (cc >= 8) cc &= ~7;
+  return cc;
+}
+int64_t num_splits(int64_t C) { return (C + CS_SPLIT - 1) / CS_SPLIT; }
+}  // namespace
+
+__global__ __launch_bounds__(256) void code_distance_table_kernel(const float *__restrict__ E, float *__restrict__ T, int K,
+                                                                  int D) {
+  const int b = (int)(blockIdx.x * 256 + threadIdx.x), a = (int)blockIdx.y;
+  if (b >= K) return;
+  const float *__restrict__ ea = E + (size_t)a * D, *__restrict__ eb = E + (size_t)b * D;
+  float acc = 0.f;
+  for (int d = 0; d < D; ++d) {
+    const float diff = ea[d] - eb[d];              // (a, b) and (b, a): the same square, the same order -> the same bits
+    acc = fmaf(diff, diff, acc);
+  }
+  T[(size_t)a * K + b] = acc;
+}
+
+// G > 0: chunks of 8 G cells, an item's codes read as 16-byte vectors, SUB chunks' worth at a time (SUB = 2 at G = 4: the
+// 128 bytes of a whole cache line per item); G == 0: chunks of cc cells, codes read one by one inside the look-up loop.
+template <int G, int IPT, int SUB>
+__global__ __launch_bounds__(CS_THREADS) void code_search_kernel(const uint16_t *__restrict__ codes,
+                                                                 const uint16_t *__restrict__ query,
+                                                                 const float *__restrict__ weights,
+                                                                 const float *__restrict__ table, float *__restrict__ partial,
+                                                                 int64_t N, int C, int K, int cc, int vec_table) {
+  extern __shared__ float rows[];                   // [cc][K]
+  constexpr int NV = G > 0 ? G * SUB : 1;
+  const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int split = (int)blockIdx.y, j = (int)blockIdx.z, Q = (int)gridDim.z;
+  const int64_t n0 = (int64_t)blockIdx.x * (CS_THREADS * IPT) + tid;
+  const int c_begin = split * CS_SPLIT;
+  const int c_end = C - c_begin < CS_SPLIT ? C : c_begin + CS_SPLIT;
+  const uint16_t *__restrict__ qj = query + (size_t)j * C;
+  const float *__restrict__ wj = weights ? weights + (size_t)j * C : nullptr;
+  const unsigned kmax = (unsigned)K - 1u;
+  if (G > 0) cc = 8 * G;
+  float acc[IPT];
+#pragma unroll
+  for (int it = 0; it < IPT; ++it) acc[it] = 0.f;
+  for (int cb = c_begin; cb < c_end; cb += cc * SUB) {
+    uint4 v[IPT][NV];
+    if (G > 0) {
+#pragma unroll
+      for (int it = 0; it < IPT; ++it) {
+        const int64_t n = n0 + (int64_t)it * CS_THREADS;
+#pragma unroll
+        for (int g = 0; g < NV; ++g) {
+          v[it][g] = make_uint4(0u, 0u, 0u, 0u);
+          if (n < N && cb + 8 * g < c_end) v[it][g] = *reinterpret_cast<const uint4 *>(codes + (size_t)n * C + cb + 8 * g);
+        }
+      }
+    }
+#pragma unroll
+    for (int sub = 0; sub < SUB; ++sub) {
+      const int c0 = cb + sub * cc;
+      if (c0 >= c_end) break;
+      const int ncell = c_end - c0 < cc ? c_end - c0 : cc;
+      // stage: wave w takes the cells w, w + 8, ...; the row index and the weight are wave-uniform
+      for (int cl = wave; cl < ncell; cl += CS_THREADS / 64) {
+        const unsigned r = qj[c0 + cl];
+        const bool live = r < (unsigned)K;
+        const float wv = wj ? wj[c0 + cl] : 1.f;
+        const float *__restrict__ src = table + (size_t)(live ? r : 0u) * K;
+        float *dst = rows + cl * K;
+        if (vec_table) {
+          for (int k4 = lane; k4 < (K >> 2); k4 += 64) {
+            float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (live) {
+              t = reinterpret_cast<const float4 *>(src)[k4];
+              t.x *= wv; t.y *= wv; t.z *= wv; t.w *= wv;
+            }
+            reinterpret_cast<float4 *>(dst)[k4] = t;
+          }
+        } else {
+          for (int k = lane; k < K; k += 64) dst[k] = live ? src[k] * wv : 0.f;
+        }
+      }
+      __syncthreads();
+      if (G > 0) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          if (8 * g < ncell) {                      // (ncell is a multiple of 8 on this route)
+            const float *rg = rows + 8 * g * K;
+#pragma unroll
+            for (int it = 0; it < IPT; ++it) {
+              const uint4 vv = v[it][sub * G + g];
+              const unsigned u[4] = {vv.x, vv.y, vv.z, vv.w};
+#pragma unroll
+              for (int e = 0; e < 4; ++e) {
+                unsigned x0 = u[e] & 0xFFFFu, x1 = u[e] >> 16;
+                x0 = x0 < kmax ? x0 : kmax;
+                x1 = x1 < kmax ? x1 : kmax;
+                acc[it] += rg[(2 * e) * K + x0];
+                acc[it] += rg[(2 * e + 1) * K + x1];
+              }
+            }
+          }
+        }
+      } else {
+#pragma unroll
+        for (int it = 0; it < IPT; ++it) {
+          const int64_t n = n0 + (int64_t)it * CS_THREADS;
+          if (n < N) {
+            const uint16_t *__restrict__ cn = codes + (size_t)n * C + c0;
+            for (int cl = 0; cl < ncell; ++cl) {
+              unsigned x = cn[cl];
+              x = x < kmax ? x : kmax;
+              acc[it] += rows[cl * K + x];
+            }
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+#pragma unroll
+  for (int it = 0; it < IPT; ++it) {
+    const int64_t n = n0 + (int64_t)it * CS_THREADS;
+    if (n < N) partial[((size_t)split * Q + j) * N + n] = acc[it];
+  }
+}
+
+__global__ __launch_bounds__(256) void code_search_reduce_kernel(const float *__restrict__ partial,
+                                                                 const uint8_t *__restrict__ allowed, float *__restrict__ dist,
+                                                                 int64_t N, int64_t QN, int splits, int accumulate) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;      // j * N + n
+  if (i >= QN) return;
+  float s = partial[i];
+  for (int sp = 1; sp < splits; ++sp) s += partial[(size_t)sp * QN + i];
+  if (accumulate) s = dist[i] + s;
+  if (allowed && !allowed[i % N]) s = __builtin_inff();
+  dist[i] = s;
+}
+
+int code_distance_table_f32(const float *codebook, float *table, int K, int D, hipStream_t st) {
+  if (!codebook) return invalid("code_distance_table: codebook is a null pointer");
+  if (!table) return invalid("code_distance_table: table is a null pointer");
+  if (K <= 0) return invalid("code_distance_table: K must be positive");
+  if (D <= 0) return invalid("code_distance_table: D must be positive");
+  if (reinterpret_cast<uintptr_t>(codebook) & 3) return invalid("code_distance_table: codebook must be aligned to a float");
+  if (reinterpret_cast<uintptr_t>(table) & 3) return invalid("code_distance_table: table must be aligned to a float");
+  if (K > 65535) return unsupported("code_distance_table: K beyond 65535 (stored codes are 16-bit)");
+  const dim3 grid((unsigned)((K + 255) / 256), (unsigned)K), block(256);
+  hipLaunchKernelGGL(code_distance_table_kernel, grid, block, 0, st, codebook, table, K, D);
+  return check_launch("code_distance_table");
+}
+
+size_t code_search_workspace_bytes(int64_t N, int64_t C, int K, int Q) {
+  if (N <= 0 || C <= 0 || K <= 0 || Q <= 0 || Q > CS_MAX_Q || C > CS_MAX_C) return 0;
+  const unsigned __int128 b = (unsigned __int128)num_splits(C) * (unsigned)Q * (unsigned __int128)N * sizeof(float);
+  return b > (unsigned __int128)SIZE_MAX ? 0 : (size_t)b;
+}
+
+int code_search_f32(const uint16_t *codes, const uint16_t *query, const float *weights, const float *table,
+                    const uint8_t *allowed, float *dist, int64_t N, int64_t C, int K, int Q, int accumulate, void *workspace,
+                    size_t workspace_bytes, hipStream_t st) {
+  if (!codes) return invalid("code_search: codes is a null pointer");
+  if (!query) return invalid("code_search: query is a null pointer");
+  if (!table) return invalid("code_search: table is a null pointer");
+  if (!dist) return invalid("code_search: dist is a null pointer");
+  if (!workspace) return invalid("code_search: workspace is a null pointer");
+  if (N <= 0) return invalid("code_search: N must be positive");
+  if (C <= 0) return invalid("code_search: C must be positive");
+  if (K <= 0) return invalid("code_search: K must be positive");
+  if (Q < 1 || Q > CS_MAX_Q) return invalid("code_search: Q must lie in 1..64");
+  if (accumulate != 0 && accumulate != 1) return invalid("code_search: accumulate must be 0 or 1");
+  if (reinterpret_cast<uintptr_t>(codes) & 1) return invalid("code_search: codes must be aligned to 2 bytes");
+  if (reinterpret_cast<uintptr_t>(query) & 1) return invalid("code_search: query must be aligned to 2 bytes");
+  if (reinterpret_cast<uintptr_t>(weights) & 3) return invalid("code_search: weights must be aligned to a float");
+  if (reinterpret_cast<uintptr_t>(table) & 3) return invalid("code_search: table must be aligned to a float");
+  if (reinterpret_cast<uintptr_t>(dist) & 3) return invalid("code_search: dist must be aligned to a float");
+  if (reinterpret_cast<uintptr_t>(workspace) & 3) return invalid("code_search: workspace must be aligned to a float");
+  if (K > 65535) return unsupported("code_search: K beyond 65535 (stored codes are 16-bit)");
+  if (K > CS_MAX_K) return unsupported("code_search: K beyond 16384 (one table row per staged cell must fit 64 KB of LDS)");
+  if (C > CS_MAX_C) return unsupported("code_search: C beyond 256 * 65535 cells");
+  if ((N + CS_THREADS - 1) / CS_THREADS >= ((int64_t)1 << 31) || (unsigned __int128)N * (unsigned)Q >= ((unsigned __int128)1 << 39))
+    return unsupported("code_search: N beyond 2^31 workgroups of items or Q * N beyond 2^39");
+  const size_t need = code_search_workspace_bytes(N, C, K, Q);
+  if (need == 0) return unsupported("code_search: the workspace size overflows size_t");
+  if (workspace_bytes < need) {
+    char buf[160];
+    snprintf(buf, sizeof buf, "code_search: workspace_bytes %zu < %zu (isi_code_search_workspace_bytes)", workspace_bytes, need);
+    set_last_error(buf);
+    return ISI_E_WORKSPACE;
+  }
+  const int splits = (int)num_splits(C);
+  const int cc = chunk_cells(K);
+  const bool vec_codes = cc >= 8 && (C % 8) == 0 && !(reinterpret_cast<uintptr_t>(codes) & 15);
+  const int vec_table = (K % 4) == 0 && !(reinterpret_cast<uintptr_t>(table) & 15);
+  const size_t lds = (size_t)cc * K * sizeof(float);
+  const bool lines = vec_codes && cc == CS_MAX_CHUNK;                  // two chunks = the 128 bytes of a whole line per item
+  const int ipt = lines ? 2 : CS_IPT;
+  const int64_t blocks = (N + CS_THREADS * ipt - 1) / (CS_THREADS * ipt);
+  const dim3 grid((unsigned)blocks, (unsigned)splits, (unsigned)Q), block(CS_THREADS);
+  float *partial = static_cast<float *>(workspace);
+  const int Ci = (int)C;
+#define ISI_CS_LAUNCH(G, IPT, SUB) \
+  hipLaunchKernelGGL((code_search_kernel<G, IPT, SUB>), grid, block, lds, st, codes, query, weights, table, partial, N, Ci, K, cc, vec_table)
+  if (!vec_codes) ISI_CS_LAUNCH(0, CS_IPT, 1);
+  else if (lines) ISI_CS_LAUNCH(4, 2, 2);
+  else if (cc == 24) ISI_CS_LAUNCH(3, CS_IPT, 1);
+  else if (cc == 16) ISI_CS_LAUNCH(2, CS_IPT, 1);
+  else ISI_CS_LAUNCH(1, CS_IPT, 1);
+#undef ISI_CS_LAUNCH
+  if (const int rc = check_launch("code_search")) return rc;
+  const int64_t QN = (int64_t)Q * N;
+  hipLaunchKernelGGL(code_search_reduce_kernel, dim3((unsigned)((QN + 255) / 256)), dim3(256), 0, st, partial, allowed, dist,
+                     N, QN, splits, accumulate);
+  return check_launch("code_search (reduce)");
+}
+
+}  // namespace isi

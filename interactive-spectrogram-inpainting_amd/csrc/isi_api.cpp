@@ -311,6 +311,16 @@ int isi_resample_f32(const float *x, int64_t x_stride, float *y, int64_t y_strid
                      int width, const float *table, void *stream) {
   return resample_f32(x, x_stride, y, y_stride, B, L, orig, new_, width, table, S(stream));
 }
+int isi_code_distance_table_f32(const float *codebook, float *table, int K, int D, void *stream) {
+  return code_distance_table_f32(codebook, table, K, D, S(stream));
+}
+size_t isi_code_search_workspace_bytes(int64_t N, int64_t C, int K, int Q) { return code_search_workspace_bytes(N, C, K, Q); }
+int isi_code_search_f32(const uint16_t *codes, const uint16_t *query, const float *weights, const float *table,
+                        const uint8_t *allowed, float *dist, int64_t N, int64_t C, int K, int Q, int accumulate,
+                        void *workspace, size_t workspace_bytes, void *stream) {
+  return code_search_f32(codes, query, weights, table, allowed, dist, N, C, K, Q, accumulate, workspace, workspace_bytes,
+                         S(stream));
+}
 int isi_rel_attention_f32(const isi_attn_args *args, void *stream) { return rel_attention_f32(args, S(stream)); }
 size_t isi_rel_attention_workspace_bytes(const isi_attn_args *args) { return rel_attention_workspace_bytes(args); }
 size_t isi_rel_attention_bwd_workspace_floats(const isi_attn_args *fwd) { return rel_attention_bwd_workspace_floats(fwd); }

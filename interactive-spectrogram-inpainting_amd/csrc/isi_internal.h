@@ -337,6 +337,12 @@ int resample_geometry(int fs_in, int fs_out, int *orig, int *new_, int *width, i
 int64_t resample_out_len(int64_t L, int orig, int new_);
 int resample_f32(const float *x, int64_t x_stride, float *y, int64_t y_stride, int B, int64_t L, int orig, int new_,
                  int width, const float *table, hipStream_t st);
+// code_search.hip
+int code_distance_table_f32(const float *codebook, float *table, int K, int D, hipStream_t st);
+size_t code_search_workspace_bytes(int64_t N, int64_t C, int K, int Q);
+int code_search_f32(const uint16_t *codes, const uint16_t *query, const float *weights, const float *table,
+                    const uint8_t *allowed, float *dist, int64_t N, int64_t C, int K, int Q, int accumulate, void *workspace,
+                    size_t workspace_bytes, hipStream_t st);
 
 size_t packed_conv_weight_floats(int Cout, int Cin, int KH, int KW);
 size_t packed_convT_k4s2_weight_floats(int Cin, int Cout);

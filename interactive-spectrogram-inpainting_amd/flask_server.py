@@ -16,6 +16,8 @@ query arguments and JSON schema for the operations built on MI355X
   GET/POST /sample-from-dataset?duration_top=&pitch=&pitch_class=&octave=&instrument_family_str=
        a stored codemap pair meeting the constraints (`codes_dataset`: the LMDB code database or any
        sequence of its items; 404 when nothing matches -- the reference searches for ever)                 (:333-372,446-514)
+       POST ...&nearest=1 with body {top_code, bottom_code} (not in the reference; needs `codes_index`): the stored
+       pair NEAREST to that sound among those meeting the constraints (utils/datasets/code_index.py)
   GET/POST /test-generate?pitch=&instrument_family_str=   uniformly random codemaps                         (:517-552)
   POST /get-spectrogram-image   body {top_code, bottom_code} -> image/png (viridis, standard library)       (:1024-1046)
   response {top_code, bottom_code, top_conditioning, bottom_conditioning}               (:991-1000)
@@ -54,9 +56,10 @@ def _read_wav(data: bytes):
 def create_app(vqvae, transformer_top, transformer_bottom, label_encoders_per_modality: Mapping[str, object],
                device, spectrograms_helper=None, top_k: int = 0, top_p: float = 0.0,
                seed: Optional[int] = None, max_sound_duration_s: float = 4.0, codes_dataset=None,
-               spectrograms_upsampling_factor: int = 1) -> flask.Flask:
+               spectrograms_upsampling_factor: int = 1, codes_index=None) -> flask.Flask:
     """`label_encoders_per_modality[name].transform([value]) -> [class index]` (sklearn LabelEncoder
-    in the reference, `utils/datasets/label_encoders.py`)."""
+    in the reference, `utils/datasets/label_encoders.py`).  codes_index: a `utils.datasets.code_index.CodeIndex` of the
+    code database, for the `nearest=1` form of /sample-from-dataset."""
     app = flask.Flask(__name__)
     device = torch.device(device)
     generator = torch.Generator().manual_seed(seed) if seed is not None else None
@@ -188,9 +191,11 @@ def create_app(vqvae, transformer_top, transformer_bottom, label_encoders_per_mo
 
     @app.route('/sample-from-dataset', methods=['GET', 'POST'])
     def sample_from_dataset():
-        if codes_dataset is None:
-            flask.abort(501)
         args = flask.request.args
+        nearest = flask.request.method == 'POST' and \
+            str(args.get('nearest', default='')).lower() in ('1', 'true', 'yes', 'y', 'on', 't')
+        if (codes_index if nearest else codes_dataset) is None:
+            flask.abort(501)
         constraints = {}
         pitch = args.get('pitch', type=int, default=None)
         if pitch is not None:
@@ -205,8 +210,13 @@ def create_app(vqvae, transformer_top, transformer_bottom, label_encoders_per_mo
         if family is not None:
             constraints['instrument_family_str'] = family
         try:
-            (top, bottom), attributes = inpainting.sample_from_database(
-                codes_dataset, label_encoders_per_modality, args.get('duration_top', type=int), constraints, generator)
+            if nearest:
+                (top, bottom), attributes = inpainting.sample_from_database(
+                    codes_dataset, label_encoders_per_modality, args.get('duration_top', type=int), constraints,
+                    similar_to=codes(flask.request.get_json(force=True)), index=codes_index)
+            else:
+                (top, bottom), attributes = inpainting.sample_from_database(
+                    codes_dataset, label_encoders_per_modality, args.get('duration_top', type=int), constraints, generator)
         except LookupError as e:
             flask.abort(404, description=str(e))
         values = {'pitch': int(attributes['pitch']), 'instrument_family_str': str(attributes['instrument_family_str'])}

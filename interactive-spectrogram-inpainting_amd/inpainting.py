@@ -12,7 +12,9 @@ routes (flask_server.py), free of HTTP so that they can be called, tested and ti
   codes_to_audio      VQ-VAE decode + spectrogram inversion (:1003-1021)
   top_conditioned_sample / analyze_audio    (:1049-1110 / :624-667)
   sample_from_database   a stored (top, bottom) pair whose attributes meet the request's constraints,
-                      cut / padded to the requested duration (:314-372, 446-514)
+                      cut / padded to the requested duration (:314-372, 446-514); optionally the one nearest to a sound
+  similar_sounds      the stored sounds most like a given one, optionally outside a masked region (not in the
+                      reference: utils/datasets/code_index.py, csrc/code_search.hip)
   spectrogram_png     the decoded log-mel magnitude as a viridis PNG (:103-143, 1024-1046)
 
 The heavy work is `sample.sample_model` (encoder pass + KV-cached native decoding loop),
@@ -24,6 +26,7 @@ import inspect
 import math
 import struct
 import zlib
+from types import SimpleNamespace
 from typing import List, Mapping, Optional, Sequence, Tuple
 
 import torch
@@ -568,14 +571,83 @@ def resize_codemaps_repeat_last(top_code: torch.Tensor, bottom_code: torch.Tenso
     return resize(top_code, duration_top), resize(bottom_code, ratio * duration_top)
 
 
+def similar_sounds(index, top_code: torch.Tensor, bottom_code: Optional[torch.Tensor], mask: Optional[torch.Tensor] = None,
+                   layer: str = 'top', start_index_top: int = 0, k: int = 8,
+                   attribute_constraints: Optional[Mapping[str, object]] = None):
+    """The k items of a `utils.datasets.code_index.CodeIndex` nearest to a sound, as a list of
+    ((top [1,F_t,T_t], bottom [1,F_b,T_b]), attributes, distance), nearest first (equal distances by item index).
+    top_code [1,F_t,T], bottom_code [1,F_b,T_b] or None (the top layer alone is compared): the query is the window of the
+    stored duration starting at `start_index_top`, cut as `timerange_change` cuts its model window; a map shorter than the
+    stored duration is continued with its last column (`resize_codemaps_repeat_last`) and the added columns weigh nothing.
+    mask bool [1,F,W] in the resolution of `layer` over the window: True = do not compare here ("the sounds that agree
+    with everything outside my hole"); a top-layer mask extends to the bottom layer as `timerange_change` extends it.
+    attribute_constraints: `sample_from_database`'s.  The comparison runs on the device (csrc/code_search.hip)."""
+    if layer not in ('top', 'bottom'):
+        raise ValueError(f"unknown layer {layer}")
+    two = bottom_code is not None and index.bottom_shape is not None
+    shape_top = index.top_shape
+    shape_bottom = index.bottom_shape if two else (shape_top[0], shape_top[1])
+    top_code = top_code.reshape(1, *top_code.shape[-2:])
+    bottom_ref = bottom_code.reshape(1, *bottom_code.shape[-2:]) if two else top_code
+    window = _windows(top_code, bottom_ref, SimpleNamespace(shape=shape_top), SimpleNamespace(shape=shape_bottom),
+                      start_index_top)
+    (s_top, e_top), (s_bot, e_bot), ratio_t = window
+    top_frame, bottom_frame = top_code[..., s_top:e_top], bottom_ref[..., s_bot:e_bot]
+    if top_frame.shape[-1] < 1:
+        raise ValueError(f"start_index_top {start_index_top} lies beyond the top map's {top_code.shape[-1]} columns")
+    known_top = top_frame.shape[-1]                   # columns of the window the sound really has
+    top_frame, bottom_frame = resize_codemaps_repeat_last(top_frame, bottom_frame, shape_top[1])
+    device = index.device
+    mask_top = torch.zeros((1,) + tuple(shape_top), dtype=torch.bool, device=device)
+    mask_top[..., known_top:] = True
+    mask_bottom = None
+    if two:
+        mask_bottom = torch.zeros((1,) + tuple(shape_bottom), dtype=torch.bool, device=device)
+        mask_bottom[..., ratio_t * known_top:] = True
+    if mask is not None:
+        mask = mask.to(device).reshape(1, *mask.shape[-2:])
+        rows = shape_top[0] if layer == 'top' else shape_bottom[0]
+        if mask.dtype != torch.bool or mask.shape[-2] != rows:
+            raise ValueError(f"mask: expected bool [1, {rows}, W] in the {layer} layer's resolution, got "
+                             f"{mask.dtype} {tuple(mask.shape)}")
+        if layer == 'top':
+            mask_top[..., :mask.shape[-1]] |= mask[..., :shape_top[1]]
+            if two:
+                ratio_f = shape_bottom[0] // shape_top[0]
+                up = mask.repeat_interleave(ratio_f, -2).repeat_interleave(ratio_t, -1)
+                mask_bottom[..., :up.shape[-1]] |= up[..., :shape_bottom[1]]
+        elif two:
+            mask_bottom[..., :mask.shape[-1]] |= mask[..., :shape_bottom[1]]
+        else:
+            raise ValueError("a bottom-layer mask needs bottom_code and an index that holds bottom maps")
+    indices, distances = index.search(top_frame.to(device), bottom_frame.to(device) if two else None, mask_top=mask_top,
+                                      mask_bottom=mask_bottom, k=k, attribute_constraints=attribute_constraints)
+    out = []
+    for i, d in zip(indices.tolist(), distances.tolist()):
+        top, bottom, _ = index[i]
+        out.append(((top.unsqueeze(0), None if bottom is None else bottom.unsqueeze(0)), index.decoded_attributes(i), d))
+    return out
+
+
 def sample_from_database(codes_dataset, label_encoders_per_modality: Mapping[str, object], duration_top: int,
-                         attribute_constraints: Mapping[str, object], generator: Optional[torch.Generator] = None):
+                         attribute_constraints: Mapping[str, object], generator: Optional[torch.Generator] = None, *,
+                         similar_to: Optional[Tuple[torch.Tensor, Optional[torch.Tensor]]] = None, index=None):
     """The lookup of `/sample-from-dataset` (flask_server.py:333-372): items of the code database
     (`utils.datasets.lmdb_dataset.LMDBDataset`: (top [F_t,T_t], bottom [F_b,T_b], {class name: tensor [1]})) are visited in
     a random order until one meets every constraint -- equality on the decoded attributes, `pitch_class` = pitch % 12 and
     `octave` = pitch // 12 derived from the pitch (the reference stores the octave under the `pitch_class` key, :351-353,
     so its octave constraint can never be met; the evident intent is built here).  The reference draws with replacement
-    for ever; a database without a match raises LookupError here.  Returns ((top [1,F_t,T], bottom [1,F_b,T_b]), attributes)."""
+    for ever; a database without a match raises LookupError here.  Returns ((top [1,F_t,T], bottom [1,F_b,T_b]), attributes).
+    similar_to=(top, bottom) with index=a `CodeIndex` of the database: the item NEAREST to that sound among those meeting
+    the constraints (`similar_sounds`, k = 1) instead of a random one; `codes_dataset` and `generator` are then not read."""
+    if (similar_to is None) != (index is None):
+        raise ValueError("sample_from_database: similar_to=(top, bottom) and index=CodeIndex go together")
+    if index is not None:
+        (top_code, bottom_code), attributes, _ = similar_sounds(index, similar_to[0], similar_to[1], k=1,
+                                                                attribute_constraints=attribute_constraints)[0]
+        if bottom_code is None:
+            raise ValueError("sample_from_database: the index holds no bottom maps")
+        return resize_codemaps_repeat_last(top_code, bottom_code, duration_top), attributes
     for index in torch.randperm(len(codes_dataset), generator=generator).tolist():
         top_code, bottom_code, encoded = codes_dataset[index]
         attributes = {key: label_encoders_per_modality[key].inverse_transform([int(torch.as_tensor(value).reshape(-1)[0])])[0]

@@ -27,6 +27,7 @@
 // The K order differs from the phase-per-launch kernel's (16-channel stages, taps inside), so the two agree to
 // rounding, not bit for bit.  Requirements (else the phase-per-launch kernel): pair8 channels-last dense input with
 // Cin % 16 == 0, Cout % 64 == 0, channels-last dense output.
+#include "device_prims.h"
 #include "isi_common.h"
 #include "isi_internal.h"
 #include "knobs.h"
@@ -37,8 +38,6 @@ namespace isi {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
 using f16s::f16x8;
@@ -61,14 +60,6 @@ struct ConvTPairK {
   float *out2;                                 // OUTP launches: dense fp32 twin of the output (training tape), or null
 };
 
-__device__ __forceinline__ void dma16(const unsigned lds_addr, const unsigned voff, const i32x4 rsrc, const unsigned soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :: "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
-__device__ __forceinline__ i32x4 make_rsrc(const void *ptr, const unsigned bytes) {
-  const unsigned long long b = (unsigned long long)ptr;
-  return i32x4{(int)(unsigned)b, (int)((unsigned)(b >> 32) & 0xffffu), (int)bytes, 0x00020000};
-}
 // phase timestamps (-DISI_MEASURE builds; tools/stamps_convT.py): workgroup 8, waves 0 and 4, its second work item
 #ifdef ISI_MEASURE
 __device__ long long g_convT_pair_stamps[128];

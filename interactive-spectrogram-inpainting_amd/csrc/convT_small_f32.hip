@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "device_prims.h"
 #include "isi_common.h"
 #include "isi_internal.h"
 #include "knobs.h"
@@ -28,8 +29,6 @@
 
 namespace isi {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 struct ConvTSmallArgs {
   const float *in, *wn, *bias;

@@ -17,6 +17,7 @@
 //     wave writes whole 256-byte pixel rows (fp32 or the split-f16 pair format, ISI_CONV_OUT_PAIR).
 #include <cstdlib>
 
+#include "device_prims.h"
 #include "isi_common.h"
 #include "isi_internal.h"
 #include "knobs.h"
@@ -27,8 +28,6 @@ namespace isi {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 constexpr unsigned OOB = 0xFFFFFFF0u;
 constexpr int TILES_PER_WAVE = 8;   // 2: 92 us, 8: 87 us at B = 64
 constexpr int LDT = 68;   // LDS row of the transpose buffer (floats): 16-byte aligned rows, shifted banks

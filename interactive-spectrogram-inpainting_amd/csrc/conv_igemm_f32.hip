@@ -19,17 +19,15 @@
 // and vqvae/vqvae.py:193-201,260,270-272,282.
 #include <cstdlib>
 
+#include "device_prims.h"
 #include "isi_common.h"
 #include "isi_internal.h"
 #include "knobs.h"
 #include "prof.h"
+#include "split_bf16.h"
 #include "split_f16.h"
 
 namespace isi {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 // All fields are scalars so the whole struct stays in SGPRs (s_load from the
 // kernarg segment); element strides / offsets are 32-bit (launchers reject
@@ -70,11 +68,6 @@ constexpr int LDK = 36;  // padded LDS row (floats): 144 B, 16-B aligned, bank-c
 template <int BN> constexpr int nbuf_for() { return BN == 64 ? 1 : 2; }
 constexpr unsigned OOB = 0xFFFFFFF0u;  // buffer_load beyond num_records returns 0: free zero padding
 
-__device__ __forceinline__ float4 buf_load4(__amdgpu_buffer_rsrc_t rsrc, unsigned byte_off) {
-  i32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, byte_off, 0, 0);
-  return *reinterpret_cast<float4 *>(&v);
-}
-
 // ---- split-bf16 ("bf16x3") products: x = hi + lo with hi = bf16(x), lo = bf16(x - hi);
 // a.b ~= a_hi.b_hi + a_hi.b_lo + a_lo.b_hi on v_mfma_f32_32x32x16_bf16 with fp32 accumulation.
 // The dropped a_lo.b_lo term and the rounding of lo bound the relative error of every product
@@ -84,39 +77,13 @@ typedef short s16x8 __attribute__((ext_vector_type(8)));
 constexpr int LDB = 32;  // LDS row of a bf16 plane (elements): 64 B, unpadded; the four 16-B slots of a row are
                          // XOR-swizzled with (row >> 2) & 3: the 16-lane groups of ds_read_b128 then hit 16 distinct
                          // slots, and the contiguous 16-lane groups of ds_write_b64 cover 32 distinct banks
-__device__ __forceinline__ int bf_slot(int row, int slot) { return (slot ^ ((row >> 2) & 3)) * 8; }
-
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-// hi = bf16(x) (round to nearest even: v_cvt_pk_bf16_f32), lo = bf16(x - hi): ~10 VALU per float4
-__device__ __forceinline__ void split_bf16x4(const float4 v, uint2 &hi, uint2 &lo) {
-  const f32x2 a = {v.x, v.y}, b = {v.z, v.w};
-  const bf16x2 ha = __builtin_convertvector(a, bf16x2), hb = __builtin_convertvector(b, bf16x2);
-  const bf16x2 la = __builtin_convertvector(a - __builtin_convertvector(ha, f32x2), bf16x2);
-  const bf16x2 lb = __builtin_convertvector(b - __builtin_convertvector(hb, f32x2), bf16x2);
-  hi = make_uint2(__builtin_bit_cast(unsigned, ha), __builtin_bit_cast(unsigned, hb));
-  lo = make_uint2(__builtin_bit_cast(unsigned, la), __builtin_bit_cast(unsigned, lb));
-}
-
-// x = hi + mid + lo exactly (3 x 8 significand bits): the six products hi.hi, hi.mid, mid.hi, hi.lo, lo.hi,
-// mid.mid carry every term above 2^-24 of the result ("bf16x6": fp32-grade products at 6/16 of the fp32 pipe's time)
-__device__ __forceinline__ void split3_bf16x4(const float4 v, uint2 &hi, uint2 &mid, uint2 &lo) {
-  const f32x2 a = {v.x, v.y}, b = {v.z, v.w};
-  const bf16x2 ha = __builtin_convertvector(a, bf16x2), hb = __builtin_convertvector(b, bf16x2);
-  const f32x2 ra = a - __builtin_convertvector(ha, f32x2), rb = b - __builtin_convertvector(hb, f32x2);
-  const bf16x2 ma = __builtin_convertvector(ra, bf16x2), mb = __builtin_convertvector(rb, bf16x2);
-  const bf16x2 la = __builtin_convertvector(ra - __builtin_convertvector(ma, f32x2), bf16x2);
-  const bf16x2 lb = __builtin_convertvector(rb - __builtin_convertvector(mb, f32x2), bf16x2);
-  hi = make_uint2(__builtin_bit_cast(unsigned, ha), __builtin_bit_cast(unsigned, hb));
-  mid = make_uint2(__builtin_bit_cast(unsigned, ma), __builtin_bit_cast(unsigned, mb));
-  lo = make_uint2(__builtin_bit_cast(unsigned, la), __builtin_bit_cast(unsigned, lb));
-}
+                         // (bf_slot, device_prims.h)
+// the splits themselves, split_bf16x4 and the six-product split3_bf16x4 ("bf16x6"): split_bf16.h
 
 // ---- split-f16 ("f16x3", ISI_CONV_F16X3), pack-time weight pieces (ISI_CONV_W16) and activation pairs
 // (ISI_CONV_*_PAIR): definitions and error / range analysis in split_f16.h
 using f16s::f16x8;
 constexpr float kF16ScaleA = f16s::kScaleA, kF16ScaleB = f16s::kScaleB, kF16Unscale = f16s::kUnscale;
-__device__ __forceinline__ void split_f16x4(const float4 v, const float s, uint2 &hi, uint2 &lo) { f16s::split4(v, s, hi, lo); }
 
 template <int BM, int BN, int WM, int WN, int MODE, int PREC = 0, bool OUTP = false>
 __global__ __launch_bounds__(256) void conv_igemm_f32_kernel(const ConvKArgs p) {

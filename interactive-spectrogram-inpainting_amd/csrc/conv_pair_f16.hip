@@ -37,6 +37,7 @@
 // vqvae/encoder_decoder.py:95-112,138,199-215 and vqvae/vqvae.py:193-201,260,270-272,282.
 #include <cstdlib>
 
+#include "device_prims.h"
 #include "isi_common.h"
 #include "isi_internal.h"
 #include "knobs.h"
@@ -47,8 +48,6 @@ namespace isi {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 using f16s::f16x8;
 
@@ -72,14 +71,6 @@ struct PairK {
   unsigned out2_bytes;
 };
 
-// one LDS-DMA: lane l's 16 bytes at rsrc.base + voff + soff land at lds_addr + 16 l; zeros when voff is out of range
-// (the range check looks at voff alone: tools/probes/lds_dma_probe.hip).  M0 carries the wave-uniform LDS address; it
-// is written here and never restored -- nothing else in this kernel uses M0 (no other m0 in the generated code).
-__device__ __forceinline__ void dma16(const unsigned lds_addr, const unsigned voff, const i32x4 rsrc, const unsigned soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :: "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
-
 // x / d for 0 <= x < 2^24, 1 <= d < 2^24
 __device__ __forceinline__ int udiv_small(const int x, const int d) {
   int q = (int)((float)x * __builtin_amdgcn_rcpf((float)d));
@@ -87,11 +78,6 @@ __device__ __forceinline__ int udiv_small(const int x, const int d) {
   if (r < 0) { --q; r += d; }
   if (r >= d) ++q;
   return q;
-}
-
-__device__ __forceinline__ i32x4 make_rsrc(const void *ptr, const unsigned bytes) {
-  const unsigned long long b = (unsigned long long)ptr;
-  return i32x4{(int)(unsigned)b, (int)((unsigned)(b >> 32) & 0xffffu), (int)bytes, 0x00020000};
 }
 
 // phase timestamps of the instrumented variant (ISI_CONV_ABLATE=32; tools/ablate_conv.py reads them back)

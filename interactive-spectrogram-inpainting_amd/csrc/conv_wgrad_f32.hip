@@ -18,15 +18,13 @@
 #include <type_traits>
 #include <vector>
 
+#include "device_prims.h"
 #include "isi_common.h"
 #include "isi_internal.h"
 #include "knobs.h"
 #include "split_f16.h"
 
 namespace isi {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 struct WgradKArgs {
   const float *x0, *x1, *dy;
@@ -52,10 +50,6 @@ struct WgradKArgs {
 namespace {
 constexpr int LDT = 132;  // LDS row (floats): 128 + 4
 constexpr unsigned OOB = 0xFFFFFFF0u;
-__device__ __forceinline__ float4 buf_load4(__amdgpu_buffer_rsrc_t rsrc, unsigned byte_off, unsigned uniform_off = 0) {
-  i32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, byte_off, uniform_off, 0);
-  return *reinterpret_cast<float4 *>(&v);
-}
 }  // namespace
 
 __global__ __launch_bounds__(256) void conv_wgrad_f32_kernel(const WgradKArgs p) {
@@ -224,7 +218,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 namespace {
 constexpr int LDB = 32;
-__device__ __forceinline__ int bf_slot(int row, int slot) { return (slot ^ ((row >> 2) & 3)) * 8; }
 // pieces of 4 values (one channel, 4 consecutive pixels): hi, lo(, mid); x = hi + mid + lo exactly when NP == 3
 template <int NP>
 __device__ __forceinline__ void split4(const float a, const float b, const float c, const float d, uint2 *out) {

@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "device_prims.h"
 #include "isi_common.h"
 #include "isi_internal.h"
 #include "knobs.h"
@@ -32,8 +33,6 @@
 namespace isi {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8g __attribute__((ext_vector_type(8)));
 
 struct GemmArgs {
@@ -58,10 +57,6 @@ struct GemmArgs {
 constexpr unsigned OOB = 0xFFFFFFF0u;
 constexpr int BM = 128;
 constexpr int kGemmTailRows = 16;   // M % BM up to this many rows: no tile row of their own (gemm_split_f32 below)
-__device__ __forceinline__ float4 buf_load4(__amdgpu_buffer_rsrc_t rsrc, unsigned byte_off, unsigned uniform_off = 0) {
-  i32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, byte_off, uniform_off, 0);
-  return *reinterpret_cast<float4 *>(&v);
-}
 __device__ __forceinline__ int swz(int row, int slot) { return (slot ^ ((row >> 2) & 3)) * 16; }
 
 template <bool F16>

@@ -24,16 +24,15 @@
 // oracle/prior_oracle.py::attention differentiated by torch autograd.
 #include <algorithm>
 
+#include "device_prims.h"
 #include "isi_common.h"
 #include "isi_internal.h"
 #include "knobs.h"
 #include "prof.h"
+#include "rel_attention.h"
 #include "split_bf16.h"
 
 namespace isi {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 struct AttnBwdKArgs {
   const float *q, *k, *v, *e, *mask, *dout, *out, *lse;
@@ -57,22 +56,10 @@ struct AttnBwdKArgs {
 };
 
 namespace {
-constexpr unsigned OOB = 0xFFFFFFF0u;
-constexpr int QB = 128;        // queries (keys) per workgroup
-constexpr int BAND = 160;      // rows of e a tile can touch
 constexpr int RING = 256;      // rows of the band ring (power of two, >= BAND + 32)
-constexpr float LOG2E = 1.4426950408889634f;
 constexpr int SRLD = 65;       // row of the per-wave skew buffer
 constexpr int TLD = 33;        // row of the per-wave transpose buffer (aliases the skew buffer)
 
-__device__ __forceinline__ float4 buf_load4(__amdgpu_buffer_rsrc_t rsrc, unsigned byte_off) {
-  i32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, byte_off, 0, 0);
-  return *reinterpret_cast<float4 *>(&v);
-}
-__device__ __forceinline__ float elem(const float4 &v, int e) {
-  return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w;
-}
-__device__ __forceinline__ int mfma_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -1722,10 +1709,6 @@ int launch_bwd_tails(const AttnBwdKArgs &a, int tail_q, int tail_k, hipStream_t 
   hipLaunchKernelGGL(attn_bwd_tail_kernel<HD>, dim3(a.H, a.B, tail_q + tail_k), dim3(TAIL_THREADS), 0, stream, a, tail_q, tail_k);
   return check_launch("attn_bwd_tail");
 }
-
-int64_t span(int64_t S, int64_t ss, int64_t B, int64_t sb, int64_t H, int64_t sh, int64_t hd) {
-  return (S - 1) * ss + (B - 1) * sb + (H - 1) * sh + hd;
-}
 }  // namespace
 
 size_t rel_attention_bwd_workspace_floats(const isi_attn_args *g) {
@@ -1803,33 +1786,19 @@ static int launch_bwd(const AttnBwdKArgs &a, hipStream_t stream) {
 int rel_attention_bwd_f32(const isi_attn_bwd_args *ga, hipStream_t stream) {
   if (!ga) return invalid("rel_attention_bwd: null pointer");
   const isi_attn_args *g = &ga->fwd;
-  if (!g->q || !g->k || !g->v || !g->out || !g->lse || !ga->d_out || !ga->dq || !ga->dk || !ga->dv || !ga->workspace)
-    return invalid("rel_attention_bwd: null pointer");
-  if (g->Sq <= 0 || g->Sk <= 0 || g->B <= 0 || g->H <= 0) return invalid("rel_attention_bwd: bad shape");
-  if (g->Cq <= 0 || g->Ck <= 0 || g->Ek <= 0) return invalid("rel_attention_bwd: bad event layout");
-  if (g->mask_mode < 0 || g->mask_mode > 2) return invalid("rel_attention_bwd: bad mask mode");
+  if (!g->lse || !ga->d_out || !ga->dq || !ga->dk || !ga->dv || !ga->workspace) return invalid("rel_attention_bwd: null pointer");
+  AttnSpans sp;
+  const uintptr_t own_ptrs = reinterpret_cast<uintptr_t>(ga->d_out) | reinterpret_cast<uintptr_t>(ga->dq) |
+                             reinterpret_cast<uintptr_t>(ga->dk) | reinterpret_cast<uintptr_t>(ga->dv) |
+                             reinterpret_cast<uintptr_t>(ga->workspace);
+  if (const int rc = attn_check_common(g, "rel_attention_bwd", own_ptrs, &sp)) return rc;
   if (g->head_dim != 16 && g->head_dim != 32 && g->head_dim != 64)
     return unsupported("rel_attention_bwd: head_dim must be 16, 32 or 64");
-  if (127 / g->Cq + 31 / g->Ck + 1 > BAND || 31 / g->Cq + 127 / g->Ck + 1 > BAND)
-    return unsupported("rel_attention_bwd: band too wide");
+  if (31 / g->Cq + 127 / g->Ck + 1 > BAND) return unsupported("rel_attention_bwd: band too wide");   // the key-stationary tiles
   const bool has_e = g->rel_embeddings != nullptr;
   if (has_e && (g->rel_rows <= 0 || !ga->d_rel)) return invalid("rel_attention_bwd: rel_rows / d_rel missing");
   const int64_t lim = (int64_t)1 << 30;
   const int HD = g->head_dim;
-  const int64_t eq = span(g->Sq, g->q_ss, g->B, g->q_sb, g->H, g->q_sh, HD);
-  const int64_t ek = span(g->Sk, g->k_ss, g->B, g->k_sb, g->H, g->k_sh, HD);
-  const int64_t ev = span(g->Sk, g->v_ss, g->B, g->v_sb, g->H, g->v_sh, HD);
-  const int64_t eo = span(g->Sq, g->o_ss, g->B, g->o_sb, g->H, g->o_sh, HD);
-  if (eq > lim || ek > lim || ev > lim || eo > lim) return unsupported("rel_attention_bwd: tensor spans 4 GiB or more");
-  const int64_t all = g->q_ss | g->q_sb | g->q_sh | g->k_ss | g->k_sb | g->k_sh | g->v_ss | g->v_sb | g->v_sh |
-                      g->o_ss | g->o_sb | g->o_sh;
-  const uintptr_t ptrs = reinterpret_cast<uintptr_t>(g->q) | reinterpret_cast<uintptr_t>(g->k) |
-                         reinterpret_cast<uintptr_t>(g->v) | reinterpret_cast<uintptr_t>(g->out) |
-                         reinterpret_cast<uintptr_t>(g->rel_embeddings) | reinterpret_cast<uintptr_t>(ga->d_out) |
-                         reinterpret_cast<uintptr_t>(ga->dq) | reinterpret_cast<uintptr_t>(ga->dk) |
-                         reinterpret_cast<uintptr_t>(ga->dv) | reinterpret_cast<uintptr_t>(ga->workspace);
-  if ((all & 3) || (ptrs & 15))
-    return invalid("rel_attention_bwd: strides must be multiples of 4 floats and pointers 16-byte aligned");
   int rho_lo = 0, rho_n = 0;
   if (has_e) rho_range(g, &rho_lo, &rho_n);
   const BwdLayout L = bwd_layout(g->B, g->H, g->Sq, rho_n, HD);
@@ -1838,22 +1807,13 @@ int rel_attention_bwd_f32(const isi_attn_bwd_args *ga, hipStream_t stream) {
 
   AttnBwdKArgs a;
   memset(&a, 0, sizeof a);
-  a.q = g->q; a.k = g->k; a.v = g->v; a.e = g->rel_embeddings; a.mask = g->dense_mask;
-  a.dout = ga->d_out; a.out = g->out; a.lse = g->lse;
+  attn_fill_common(a, g, sp);
+  a.dout = ga->d_out;
   a.dsum = ga->workspace + L.dsum;
   a.dq = ga->dq; a.dk = ga->dk; a.dv = ga->dv;
   a.g = has_e ? ga->workspace + L.g : nullptr;
-  a.q_bytes = (unsigned)(eq * 4); a.k_bytes = (unsigned)(ek * 4); a.v_bytes = (unsigned)(ev * 4);
-  a.o_bytes = (unsigned)(eo * 4);
-  a.R = g->rel_rows; a.Rp = L.Rp; a.rho_lo = rho_lo;
-  a.e_bytes = (unsigned)((size_t)g->H * g->rel_rows * HD * 4);
-  a.Sq = g->Sq; a.Sk = g->Sk; a.H = g->H; a.B = g->B;
-  a.q_ss = (int)g->q_ss; a.q_sb = (int)g->q_sb; a.q_sh = (int)g->q_sh;
-  a.k_ss = (int)g->k_ss; a.k_sb = (int)g->k_sb; a.k_sh = (int)g->k_sh;
-  a.v_ss = (int)g->v_ss; a.v_sb = (int)g->v_sb; a.v_sh = (int)g->v_sh;
-  a.o_ss = (int)g->o_ss; a.o_sb = (int)g->o_sb; a.o_sh = (int)g->o_sh;
-  a.Cq = g->Cq; a.Ck = g->Ck; a.Ek = g->Ek;
-  a.mask_mode = g->mask_mode; a.scale = g->scale;
+  a.o_bytes = (unsigned)(sp.o * 4);
+  a.Rp = L.Rp; a.rho_lo = rho_lo;
   if (g->logits) {      // the forward's logits (isi_attn_args.logits): read by the split kernels
     if (g->precision < 1) return unsupported("rel_attention_bwd: kept logits go with the 16-bit modes (precision >= 1)");
     if (g->logits_ld < ((g->Sk + 31) & ~31) || (g->logits_ld & 3) || (reinterpret_cast<uintptr_t>(g->logits) & 15) ||

@@ -26,6 +26,7 @@
 // This file holds the exact-fp32 kernel (precision 0), the one-row tail kernel and the public dispatcher
 // rel_attention_f32(); the 16-bit precisions run the kernels of rel_attention_fwd2.hip / rel_attention_fwd3.hip
 // (attn_fwd_route below decides which).
+#include "device_prims.h"
 #include "isi_common.h"
 #include "isi_internal.h"
 #include "knobs.h"
@@ -34,32 +35,14 @@
 
 namespace isi {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-
 namespace {
-constexpr unsigned OOB = 0xFFFFFFF0u;
-constexpr float NEG = -1e30f;
-constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
-constexpr int QB = 128;        // queries per workgroup
-constexpr int BAND = 160;      // rows of e a key tile can touch (>= 127/Cq + 31/Ck + 1)
-constexpr int BAND2 = 192;     // rows a PAIR of key tiles can touch (>= 127/Cq + 63/Ck + 1)
+constexpr int BAND2 = 192;    // rows a PAIR of key tiles can touch (>= 127/Cq + 63/Ck + 1)
 constexpr int RING = 192;      // rows of the band ring (>= BAND2: new rows replace rows no tile needs any more)
 __device__ __forceinline__ int ring_slot(int r) {
   r %= RING;
   return r < 0 ? r + RING : r;
 }
 constexpr int SRLD = 65;       // per-query row of the skew buffer (64 + 1: conflict-free)
-
-__device__ __forceinline__ float4 buf_load4(__amdgpu_buffer_rsrc_t rsrc, unsigned byte_off) {
-  i32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, byte_off, 0, 0);
-  return *reinterpret_cast<float4 *>(&v);
-}
-__device__ __forceinline__ float elem(const float4 &v, int e) {
-  return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w;
-}
-__device__ __forceinline__ int mfma_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 }  // namespace
 
 // Workgroup = 8 waves = 128 consecutive queries of one (batch, head), in two groups of four waves.
@@ -467,40 +450,11 @@ static AttnFwd attn_fwd_route(const AttnKArgs &a, int head_dim, int precision, A
   return AttnFwd::Planes;
 }
 
-static int64_t span(int64_t S, int64_t ss, int64_t B, int64_t sb, int64_t H, int64_t sh, int64_t hd) {
-  return (S - 1) * ss + (B - 1) * sb + (H - 1) * sh + hd;
-}
-
 int rel_attention_f32(const isi_attn_args *g, hipStream_t stream) {
-  if (!g || !g->q || !g->k || !g->v || !g->out) return invalid("rel_attention: null pointer");
-  if (g->Sq <= 0 || g->Sk <= 0 || g->B <= 0 || g->H <= 0) return invalid("rel_attention: bad shape");
-  if (g->Cq <= 0 || g->Ck <= 0 || g->Ek <= 0) return invalid("rel_attention: bad event layout");
-  if (g->mask_mode < 0 || g->mask_mode > 2) return invalid("rel_attention: bad mask mode");
-  if (127 / g->Cq + 31 / g->Ck + 1 > BAND) return unsupported("rel_attention: band too wide");
-  const int64_t lim = (int64_t)1 << 30;
-  const int64_t eq = span(g->Sq, g->q_ss, g->B, g->q_sb, g->H, g->q_sh, g->head_dim);
-  const int64_t ek = span(g->Sk, g->k_ss, g->B, g->k_sb, g->H, g->k_sh, g->head_dim);
-  const int64_t ev = span(g->Sk, g->v_ss, g->B, g->v_sb, g->H, g->v_sh, g->head_dim);
-  const int64_t eo = span(g->Sq, g->o_ss, g->B, g->o_sb, g->H, g->o_sh, g->head_dim);
-  if (eq > lim || ek > lim || ev > lim || eo > lim) return unsupported("rel_attention: tensor spans 4 GiB or more");
-  const int64_t all = g->q_ss | g->q_sb | g->q_sh | g->k_ss | g->k_sb | g->k_sh | g->v_ss | g->v_sb | g->v_sh |
-                      g->o_ss | g->o_sb | g->o_sh;
-  if ((all & 3) || ((reinterpret_cast<uintptr_t>(g->q) | reinterpret_cast<uintptr_t>(g->k) |
-                     reinterpret_cast<uintptr_t>(g->v) | reinterpret_cast<uintptr_t>(g->out) |
-                     reinterpret_cast<uintptr_t>(g->rel_embeddings)) & 15))
-    return invalid("rel_attention: strides must be multiples of 4 floats and pointers 16-byte aligned");
+  AttnSpans sp;
+  if (const int rc = attn_check_common(g, "rel_attention", 0, &sp)) return rc;
   AttnKArgs a;
-  a.q = g->q; a.k = g->k; a.v = g->v; a.e = g->rel_embeddings; a.mask = g->dense_mask; a.out = g->out; a.lse = g->lse;
-  a.q_bytes = (unsigned)(eq * 4); a.k_bytes = (unsigned)(ek * 4); a.v_bytes = (unsigned)(ev * 4);
-  a.R = g->rel_rows;
-  a.e_bytes = (unsigned)((size_t)g->H * g->rel_rows * g->head_dim * 4);
-  a.Sq = g->Sq; a.Sk = g->Sk; a.H = g->H; a.B = g->B;
-  a.q_ss = (int)g->q_ss; a.q_sb = (int)g->q_sb; a.q_sh = (int)g->q_sh;
-  a.k_ss = (int)g->k_ss; a.k_sb = (int)g->k_sb; a.k_sh = (int)g->k_sh;
-  a.v_ss = (int)g->v_ss; a.v_sb = (int)g->v_sb; a.v_sh = (int)g->v_sh;
-  a.o_ss = (int)g->o_ss; a.o_sb = (int)g->o_sb; a.o_sh = (int)g->o_sh;
-  a.Cq = g->Cq; a.Ck = g->Ck; a.Ek = g->Ek;
-  a.mask_mode = g->mask_mode; a.scale = g->scale;
+  attn_fill_common(a, g, sp);
   if (g->precision < 0 || g->precision > 3) return invalid("rel_attention: precision must be 0 .. 3");
   // 0 fp32 pipe | 1 three-term split-bf16 | 2 single-term bf16 | 3 single-term f16
   a.split = g->precision == 1 ? 1 : g->precision >= 2 ? 2 : 0;

@@ -23,6 +23,7 @@
 // [kp + g KT, kp + (g + 1) KT) of a step and keeps its own (m, l, O); the two states are merged per block.
 #include <algorithm>
 
+#include "device_prims.h"
 #include "isi_common.h"
 #include "isi_internal.h"
 #include "prof.h"
@@ -32,51 +33,6 @@
 namespace isi {
 
 namespace {
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-
-constexpr unsigned OOB = 0xFFFFFFF0u;
-constexpr float NEG = -1e30f;
-constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
-constexpr int QB = 128;    // queries per block
-constexpr int LD = 68;     // floats per query row of the skew buffer (64 band rows + 4)
-
-__device__ __forceinline__ float4 buf_load4(__amdgpu_buffer_rsrc_t rsrc, unsigned byte_off) {
-  i32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, byte_off, 0, 0);
-  return *reinterpret_cast<float4 *>(&v);
-}
-__device__ __forceinline__ float elem(const float4 &v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
-__device__ __forceinline__ int mfma_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
-// the 16-bit operand type of a mode: conversions (round to nearest even) and the matrix instruction
-template <bool F16> struct Prec;
-template <> struct Prec<false> {
-  static __device__ __forceinline__ unsigned pack2(const float a, const float b) {
-    const f32x2_t v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-  }
-  static __device__ __forceinline__ void split2(const float a, const float b, unsigned &hi, unsigned &lo) { isi::split2(a, b, hi, lo); }
-  static __device__ __forceinline__ f32x16 mfma(const s16x8_t a, const s16x8_t b, const f32x16 c) { return ISI_MFB(a, b, c); }
-};
-template <> struct Prec<true> {
-  static __device__ __forceinline__ unsigned pack2(const float a, const float b) {
-    const f32x2_t v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2_t));
-  }
-  static __device__ __forceinline__ void split2(const float a, const float b, unsigned &hi, unsigned &lo) {
-    const f32x2_t v = {a, b};
-    const f16x2_t h = __builtin_convertvector(v, f16x2_t);
-    const f16x2_t l = __builtin_convertvector(v - __builtin_convertvector(h, f32x2_t), f16x2_t);
-    hi = __builtin_bit_cast(unsigned, h);
-    lo = __builtin_bit_cast(unsigned, l);
-  }
-  static __device__ __forceinline__ f32x16 mfma(const s16x8_t a, const s16x8_t b, const f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-  }
-};
-
 template <int HD, int TERMS> struct Tile {
   static constexpr int KT = (TERMS == 3 && HD == 64) ? 32 : 64;   // keys per group and step
   static constexpr int NSB = KT / 32, KS = 2 * KT;

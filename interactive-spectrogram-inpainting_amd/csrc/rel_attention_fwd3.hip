@@ -31,6 +31,7 @@
 // block's 32-key sub-blocks, group 1 the second; each keeps its own (m, l, O), merged per block.
 #include <algorithm>
 
+#include "device_prims.h"
 #include "isi_common.h"
 #include "isi_internal.h"
 #include "prof.h"
@@ -40,23 +41,9 @@
 namespace isi {
 
 namespace {
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 typedef short s16x4_t __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4_t *lds_s16x4_t;
 
-constexpr unsigned OOB = 0xFFFFFFF0u;
-constexpr float NEG = -1e30f;
-constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
-constexpr int QB = 128;    // queries per block
-constexpr int LD = 68;     // floats per query row of the skew buffer (64 band rows + 4)
-
-__device__ __forceinline__ float4 buf_load4(__amdgpu_buffer_rsrc_t rsrc, unsigned byte_off) {
-  i32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, byte_off, 0, 0);
-  return *reinterpret_cast<float4 *>(&v);
-}
 __device__ __forceinline__ s16x8_t buf_load_frag(__amdgpu_buffer_rsrc_t rsrc, unsigned byte_off) {
   i32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, byte_off, 0, 0);
   return __builtin_bit_cast(s16x8_t, v);
@@ -70,51 +57,20 @@ __device__ __forceinline__ s16x8_t buf_load_frag_async(const i32x4 rsrc, const u
   asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:%4" : "=v"(v) : "v"(byte_off), "s"(rsrc), "s"(soff), "n"(IMM) : "memory");
   return __builtin_bit_cast(s16x8_t, v);
 }
-// one LDS-DMA: lane l's 16 bytes at rsrc.base + voff + soff + IMM land at (M0 + IMM) + 16 l (conv_pair_f16.hip has the
-// form that rewrites M0 per piece).  Here M0 is written ONCE per wave, at kernel entry, and a wave's pieces are told apart by
-// the instruction's immediate offset -- which the hardware adds to the memory address as well, hence `voff` carries - IMM
-// (the descriptors start DMA_MARGIN bytes early so that it stays non-negative).  Found the hard way: with `s_mov_b32 m0`
-// 1-5 wait states in front of the `buffer_load ... lds` (the documented requirement is 1) the DMA now and then still used
-// the PREVIOUS value of M0 -- a piece landed in its neighbour's slot -- whenever the vector-memory port happened to be
-// free at that moment: 8-18 of 32 runs wrong at S 1025, none with 8 wait states, all of them with the 8 wait states spent
-// anywhere else (profiles/r06_attention_m0_hazard.txt).  A value of M0 that never changes cannot be stale.
+// one LDS-DMA: lane l's 16 bytes at rsrc.base + voff + soff + IMM land at (M0 + IMM) + 16 l (device_prims.h has the form
+// that rewrites M0 for every piece).  This form does not touch M0: the kernel's set_m0() writes it once per step and twice
+// in a block's prologue -- the LDS stage the following requests go to -- always with `s_nop 7` behind the write, and in
+// the step loop a matrix segment ahead of the first DMA that reads it; the pieces of a stage are told apart by the instruction's immediate offset -- which the hardware adds to
+// the memory address as well, hence `voff` carries - IMM (the descriptors start DMA_MARGIN bytes early so that it stays
+// non-negative).  Why M0 is not rewritten per piece here: while this kernel was developed, with `s_mov_b32 m0` 1-5 wait
+// states in front of the `buffer_load ... lds` (the documented requirement is 1) the DMA now and then still used the
+// PREVIOUS value of M0 -- a piece landed in its neighbour's slot: 8-18 of 32 runs wrong at S 1025, none with 8 wait
+// states directly behind the write (the record of those runs was not kept in the tree).
 template <int IMM>
 __device__ __forceinline__ void dma16(const unsigned voff, const i32x4 rsrc, const unsigned soff) {
   asm volatile("buffer_load_dwordx4 %0, %1, %2 offen offset:%3 lds" :: "v"(voff), "s"(rsrc), "s"(soff), "n"(IMM) : "memory");
 }
 constexpr unsigned DMA_MARGIN = 4096;
-__device__ __forceinline__ i32x4 make_rsrc(const void *ptr, const unsigned bytes) {
-  const unsigned long long b = (unsigned long long)ptr;
-  return i32x4{(int)(unsigned)b, (int)((unsigned)(b >> 32) & 0xffffu), (int)bytes, 0x00020000};
-}
-
-// the 16-bit operand type of a mode: conversions (round to nearest even) and the matrix instruction
-template <bool F16> struct Prec;
-template <> struct Prec<false> {
-  static __device__ __forceinline__ unsigned pack2(const float a, const float b) {
-    const f32x2_t v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-  }
-  static __device__ __forceinline__ void split2(const float a, const float b, unsigned &hi, unsigned &lo) { isi::split2(a, b, hi, lo); }
-  static __device__ __forceinline__ f32x16 mfma(const s16x8_t a, const s16x8_t b, const f32x16 c) { return ISI_MFB(a, b, c); }
-};
-template <> struct Prec<true> {
-  static __device__ __forceinline__ unsigned pack2(const float a, const float b) {
-    const f32x2_t v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2_t));
-  }
-  static __device__ __forceinline__ void split2(const float a, const float b, unsigned &hi, unsigned &lo) {
-    const f32x2_t v = {a, b};
-    const f16x2_t h = __builtin_convertvector(v, f16x2_t);
-    const f16x2_t l = __builtin_convertvector(v - __builtin_convertvector(h, f32x2_t), f16x2_t);
-    hi = __builtin_bit_cast(unsigned, h);
-    lo = __builtin_bit_cast(unsigned, l);
-  }
-  static __device__ __forceinline__ f32x16 mfma(const s16x8_t a, const s16x8_t b, const f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-  }
-};
-
 // ---- operand planes: fp32 -> 16-bit hi (+ lo) pieces, row-major [row][HD]; K / V rows = (pair, key) with the key count
 // padded to a multiple of 32 (zero rows), e rows = (head, table row).  One thread = 8 consecutive dims of a row.
 struct PackArgs {

@@ -19,16 +19,15 @@
 // dense input/output, C % 32 == 0, C <= 128, R <= 32.
 #include <cstdlib>
 
+#include "device_prims.h"
 #include "isi_common.h"
 #include "isi_internal.h"
 #include "knobs.h"
 #include "prof.h"
+#include "split_bf16.h"
 #include "split_f16.h"
 
 namespace isi {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 struct ResKArgs {
   const float *in, *w1, *b1, *w2, *b2;
@@ -42,14 +41,6 @@ namespace {
 constexpr int LDK = 36;             // padded LDS row (floats)
 constexpr int TW = 64, HWD = TW + 2;   // output tile: TH rows x 64 pixels (TH = 2: 4 waves, TH = 4: 8 waves); halo row 66
 constexpr unsigned OOB = 0xFFFFFFF0u;
-
-__device__ __forceinline__ float4 buf_load4(__amdgpu_buffer_rsrc_t rsrc, unsigned byte_off) {
-  i32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, byte_off, 0, 0);
-  return *reinterpret_cast<float4 *>(&v);
-}
-__device__ __forceinline__ float elem(const float4 &v, int e) {
-  return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w;
-}
 }  // namespace
 
 // Workgroup = 2 x 64 output pixels.  Per 32-channel slice of the input the
@@ -62,34 +53,9 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 constexpr int LDB = 32;  // bf16 plane row (elements): 64 B unpadded; 16-B slots XOR-swizzled with (row >> 2) & 3
                          // (conflict-free ds_read_b128 lane groups and ds_write_b64 groups, see conv_igemm_f32.hip)
-__device__ __forceinline__ int bf_slot(int row, int slot) { return (slot ^ ((row >> 2) & 3)) * 8; }
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-// hi = bf16(x) (round to nearest even: v_cvt_pk_bf16_f32), lo = bf16(x - hi)
-__device__ __forceinline__ void split_bf16x4(const float4 v, uint2 &hi, uint2 &lo) {
-  const f32x2 a = {v.x, v.y}, b = {v.z, v.w};
-  const bf16x2 ha = __builtin_convertvector(a, bf16x2), hb = __builtin_convertvector(b, bf16x2);
-  const bf16x2 la = __builtin_convertvector(a - __builtin_convertvector(ha, f32x2), bf16x2);
-  const bf16x2 lb = __builtin_convertvector(b - __builtin_convertvector(hb, f32x2), bf16x2);
-  hi = make_uint2(__builtin_bit_cast(unsigned, ha), __builtin_bit_cast(unsigned, hb));
-  lo = make_uint2(__builtin_bit_cast(unsigned, la), __builtin_bit_cast(unsigned, lb));
-}
-// x = hi + mid + lo exactly ("bf16x6", ISI_CONV_BF16X6)
-__device__ __forceinline__ void split3_bf16x4(const float4 v, uint2 &hi, uint2 &mid, uint2 &lo) {
-  const f32x2 a = {v.x, v.y}, b = {v.z, v.w};
-  const bf16x2 ha = __builtin_convertvector(a, bf16x2), hb = __builtin_convertvector(b, bf16x2);
-  const f32x2 ra = a - __builtin_convertvector(ha, f32x2), rb = b - __builtin_convertvector(hb, f32x2);
-  const bf16x2 ma = __builtin_convertvector(ra, bf16x2), mb = __builtin_convertvector(rb, bf16x2);
-  const bf16x2 la = __builtin_convertvector(ra - __builtin_convertvector(ma, f32x2), bf16x2);
-  const bf16x2 lb = __builtin_convertvector(rb - __builtin_convertvector(mb, f32x2), bf16x2);
-  hi = make_uint2(__builtin_bit_cast(unsigned, ha), __builtin_bit_cast(unsigned, hb));
-  mid = make_uint2(__builtin_bit_cast(unsigned, ma), __builtin_bit_cast(unsigned, mb));
-  lo = make_uint2(__builtin_bit_cast(unsigned, la), __builtin_bit_cast(unsigned, lb));
-}
-// split-f16 pieces, pack-time weight pieces and activation pairs: split_f16.h
+// split-bf16 pieces: split_bf16.h; split-f16 pieces, pack-time weight pieces and activation pairs: split_f16.h
 using f16s::f16x8;
 constexpr float kF16ScaleA = f16s::kScaleA, kF16ScaleB = f16s::kScaleB, kF16Unscale = f16s::kUnscale;
-__device__ __forceinline__ void split_f16x4(const float4 v, const float s, uint2 &hi, uint2 &lo) { f16s::split4(v, s, hi, lo); }
 template <int PREC>
 __device__ __forceinline__ void split_x4(const float4 v, const float s16, uint2 &hi, uint2 &mid, uint2 &lo) {
   if constexpr (PREC == 2) split3_bf16x4(v, hi, mid, lo);

@@ -30,6 +30,7 @@
 // Requirements (else resblock_f32.hip): C % 32 == 0, C <= 128, R == 32, dense channels-last tensors.
 #include <cstdlib>
 
+#include "device_prims.h"
 #include "isi_common.h"
 #include "isi_internal.h"
 #include "knobs.h"
@@ -45,8 +46,6 @@ namespace isi {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 using f16s::f16x8;
 
@@ -71,14 +70,6 @@ struct ResPairK {
   float *out2, *hidden;
 };
 
-__device__ __forceinline__ void dma16(const unsigned lds_addr, const unsigned voff, const i32x4 rsrc, const unsigned soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :: "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
-__device__ __forceinline__ i32x4 make_rsrc(const void *ptr, const unsigned bytes) {
-  const unsigned long long b = (unsigned long long)ptr;
-  return i32x4{(int)(unsigned)b, (int)((unsigned)(b >> 32) & 0xffffu), (int)bytes, 0x00020000};
-}
 // phase timestamps (-DISI_MEASURE builds; tools/stamps_resblock.py): workgroup 8, waves 0 and 4, its second work item
 #ifdef ISI_MEASURE
 __device__ long long g_respair_stamps[128];

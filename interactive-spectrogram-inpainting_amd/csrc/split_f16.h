@@ -98,4 +98,7 @@ __device__ __forceinline__ float pair8_load(const unsigned short *base, const in
 }
 
 }  // namespace f16s
+
+// split4 under the name the convolution and residual-block kernels use next to split_bf16x4 / split3_bf16x4
+__device__ __forceinline__ void split_f16x4(const float4 v, const float s, uint2 &hi, uint2 &lo) { f16s::split4(v, s, hi, lo); }
 }  // namespace isi

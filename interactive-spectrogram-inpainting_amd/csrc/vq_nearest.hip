@@ -16,6 +16,7 @@
 // lane all belong to ONE vector and the running arg-min is lane-local; the two
 // half-waves (lanes l and l+32 hold interleaved code rows of the same vector)
 // are merged with a single cross-lane exchange at the end.
+#include "device_prims.h"
 #include "isi_common.h"
 #include "isi_internal.h"
 #include "knobs.h"
@@ -24,7 +25,6 @@
 
 namespace isi {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef short s16x8v __attribute__((ext_vector_type(8)));
 typedef int i32x4v __attribute__((ext_vector_type(4)));
 

@@ -155,6 +155,40 @@ int isi_code_search_f32(const uint16_t *codes, const uint16_t *query, const floa
                         const uint8_t *allowed, float *dist, int64_t N, int64_t C, int K, int Q, int accumulate,
                         void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------ shift-invariant search of a code database */
+/* "Which stored sound contains something like this fragment, wherever it sits in time" (DESIGN.md section 6c;
+ * specification tests/code_shift_search_spec.py).  codes uint16 [N, F, T], query uint16 [Q, F, W] with 1 <= W <= T,
+ * weights fp32 [Q, F, W] >= 0 or NULL (1 on every cell), table fp32 [K, K]; offsets o_s = shift0 + s * step for
+ * s = 0 .. S-1, every one inside the stored map: shift0 + (S - 1) * step + W <= T.
+ *   dist[j][s][n] = sum_f sum_t w[j][f][t] * T[query[j][f][t]][codes[n][f][t + o_s]]
+ * dist is fp32 [Q, S, N] (N innermost).  A query cell >= K counts nothing, a stored code >= K is clamped to K - 1, as in
+ * isi_code_search_f32.  Summation order (part of the contract): each product is rounded once; query cells are numbered
+ * c = f * W + t; the products of a run of 256 consecutive c are added in c order from 0, the run sums in run order; no
+ * atomics.  So the bits of dist[j][s][n] depend on query[j], weights[j], the item's codes, the table, W and o_s only --
+ * not on N, Q, S, step, alignment, the launch geometry or the run; at W == T, S == 1, shift0 == 0 they are
+ * isi_code_search_f32's with C = F * T; |dist - spec| <= (F W + 2) 2^-24 sum |w T[..]|; exact for small integer tables,
+ * 0/1 weights and sums below 2^24.  An item's codes are not fetched from memory once per offset: a fetched code serves up
+ * to min(W, S) look-ups.  accumulate = 1 adds to what dist holds (a second layer: step = the layers' time ratio r,
+ * shift0 = r * the top layer's, W = r * the top layer's, the same S; the caller scales the weights by the layer factor).
+ * isi_code_shift_search_workspace_bytes (host only): ceil(F W / 256) * Q * S * N floats of per-run sums when F W > 256;
+ * 16 bytes when F W <= 256 (one run: dist is written directly, but the pointer is still checked); 0 for sizes the
+ * search refuses.
+ * No allocation, no host synchronisation; stream-ordered.  Checked before any launch, isi_last_error() names the
+ * argument: a null codes / query / table / dist / workspace, a misaligned pointer (2 bytes for codes and query, 4 for the
+ * others), N, F, T, W, S, K or step <= 0, shift0 < 0, W > T, shift0 + (S - 1) * step + W > T, Q outside 1..64,
+ * accumulate outside {0, 1} (ISI_E_INVALID); a workspace smaller than isi_code_shift_search_workspace_bytes
+ * (ISI_E_WORKSPACE); K > 16384 (one table row per staged cell must fit 64 KB of LDS), F * W > 256 * 65535,
+ * F * T >= 2^31, Q * S * N >= 2^39, more than 2^31 - 1 workgroups (ISI_E_UNSUPPORTED).
+ * isi_code_shift_best_f32: best[j][n] = min_s dist[j][s][n] and best_shift[j][n] = the smallest s that attains it
+ * (int32); where allowed[n] == 0 (allowed uint8 [N] or NULL) best is +inf and best_shift -1.  ISI_E_INVALID for a null
+ * or misaligned dist / best / best_shift, N or S <= 0, Q outside 1..64; ISI_E_UNSUPPORTED for Q * S * N >= 2^39. */
+size_t isi_code_shift_search_workspace_bytes(int64_t N, int F, int T, int W, int S, int K, int Q);
+int isi_code_shift_search_f32(const uint16_t *codes, const uint16_t *query, const float *weights, const float *table,
+                              float *dist, int64_t N, int F, int T, int W, int shift0, int step, int S, int K, int Q,
+                              int accumulate, void *workspace, size_t workspace_bytes, void *stream);
+int isi_code_shift_best_f32(const float *dist, const uint8_t *allowed, float *best, int32_t *best_shift, int64_t N, int S,
+                            int Q, void *stream);
+
 /* ------------------------------------------------- measurement (bench.py) */
 /* Per-launch timing with HIP events recorded on the launch stream.  State is
  * per calling thread; `on` = 1 starts (earlier records cleared), 0 pauses, 2 resumes without

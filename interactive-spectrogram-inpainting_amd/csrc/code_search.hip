@@ -22,6 +22,7 @@
 // 16-byte aligned.  A stored code >= K is clamped to K - 1: nothing is read outside the stage.
 #include "isi_common.h"
 #include "isi_internal.h"
+#include "device_prims.h"
 
 namespace isi {
 
@@ -29,18 +30,11 @@ namespace {
 constexpr int CS_THREADS = 512;
 constexpr int CS_IPT = 4;                          // items per thread (2 on the whole-line route)
 constexpr int CS_SPLIT = 256;                      // cells per split: a function of nothing, so the summation order is C's alone
-constexpr int CS_STAGE_FLOATS = 16384;             // 64 KB
 constexpr int CS_MAX_CHUNK = 32;                   // cells per chunk at most (a multiple of 8 divides CS_SPLIT)
-constexpr int CS_MAX_K = CS_STAGE_FLOATS;
+constexpr int CS_MAX_K = kCodeStageFloats;
 constexpr int64_t CS_MAX_C = (int64_t)CS_SPLIT * 65535;
 constexpr int CS_MAX_Q = 64;
 
-int chunk_cells(int K) {
-  int cc = CS_STAGE_FLOATS / K;
-  if (cc > CS_MAX_CHUNK) cc = CS_MAX_CHUNK;
-  if (cc >= 8) cc &= ~7;
-  return cc;
-}
 int64_t num_splits(int64_t C) { return (C + CS_SPLIT - 1) / CS_SPLIT; }
 }  // namespace
 
@@ -67,7 +61,7 @@ __global__ __launch_bounds__(CS_THREADS) void code_search_kernel(const uint16_t 
                                                                  int64_t N, int C, int K, int cc, int vec_table) {
   extern __shared__ float rows[];                   // [cc][K]
   constexpr int NV = G > 0 ? G * SUB : 1;
-  const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int tid = (int)threadIdx.x;
   const int split = (int)blockIdx.y, j = (int)blockIdx.z, Q = (int)gridDim.z;
   const int64_t n0 = (int64_t)blockIdx.x * (CS_THREADS * IPT) + tid;
   const int c_begin = split * CS_SPLIT;
@@ -97,26 +91,7 @@ __global__ __launch_bounds__(CS_THREADS) void code_search_kernel(const uint16_t 
       const int c0 = cb + sub * cc;
       if (c0 >= c_end) break;
       const int ncell = c_end - c0 < cc ? c_end - c0 : cc;
-      // stage: wave w takes the cells w, w + 8, ...; the row index and the weight are wave-uniform
-      for (int cl = wave; cl < ncell; cl += CS_THREADS / 64) {
-        const unsigned r = qj[c0 + cl];
-        const bool live = r < (unsigned)K;
-        const float wv = wj ? wj[c0 + cl] : 1.f;
-        const float *__restrict__ src = table + (size_t)(live ? r : 0u) * K;
-        float *dst = rows + cl * K;
-        if (vec_table) {
-          for (int k4 = lane; k4 < (K >> 2); k4 += 64) {
-            float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (live) {
-              t = reinterpret_cast<const float4 *>(src)[k4];
-              t.x *= wv; t.y *= wv; t.z *= wv; t.w *= wv;
-            }
-            reinterpret_cast<float4 *>(dst)[k4] = t;
-          }
-        } else {
-          for (int k = lane; k < K; k += 64) dst[k] = live ? src[k] * wv : 0.f;
-        }
-      }
+      stage_code_rows<CS_THREADS>(rows, qj, wj, table, c0, ncell, K, vec_table);
       __syncthreads();
       if (G > 0) {
 #pragma unroll
@@ -226,7 +201,7 @@ int code_search_f32(const uint16_t *codes, const uint16_t *query, const float *w
     return ISI_E_WORKSPACE;
   }
   const int splits = (int)num_splits(C);
-  const int cc = chunk_cells(K);
+  const int cc = code_chunk_cells(K);
   const bool vec_codes = cc >= 8 && (C % 8) == 0 && !(reinterpret_cast<uintptr_t>(codes) & 15);
   const int vec_table = (K % 4) == 0 && !(reinterpret_cast<uintptr_t>(table) & 15);
   const size_t lds = (size_t)cc * K * sizeof(float);

@@ -1,6 +1,7 @@
 // Device primitives the MFMA kernels rest on, each defined ONCE: buffer loads, buffer descriptors, the LDS-DMA, the
-// 32x32 accumulator layout and the swizzle of the bf16 LDS planes.  All of them are __forceinline__: a kernel's machine
-// code does not depend on where they are written down.  Helpers with a single user stay in that user's file.
+// 32x32 accumulator layout and the swizzle of the bf16 LDS planes -- and the table-row stage the two code-database
+// searches share.  All of them are __forceinline__: a kernel's machine code does not depend on where they are written
+// down.  Helpers with a single user stay in that user's file.
 #pragma once
 #ifndef __HIPCC__
 #error "device_prims.h holds device code: include it from sources compiled by hipcc only"
@@ -41,6 +42,35 @@ __device__ __forceinline__ i32x4 make_rsrc(const void *ptr, const unsigned bytes
 __device__ __forceinline__ void dma16(const unsigned lds_addr, const unsigned voff, const i32x4 rsrc, const unsigned soff) {
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
                :: "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
+}
+
+// The stage of the code-database searches (code_search.hip, code_shift_search.hip): the weighted table rows of the `ncell`
+// query cells from c0 on, rows[cl][k] = w[c0 + cl] * T[query[c0 + cl]][k] (one rounding; zeros for a cell >= K, the priors'
+// mask token), written by a workgroup of THREADS threads.  Wave w takes the cells w, w + THREADS / 64, ...: the row index
+// and the weight are wave-uniform.  wj may be null (weight 1); vec_table: K % 4 == 0 and a 16-byte-aligned table.
+template <int THREADS>
+__device__ __forceinline__ void stage_code_rows(float *rows, const uint16_t *__restrict__ qj, const float *__restrict__ wj,
+                                                const float *__restrict__ table, int c0, int ncell, int K, int vec_table) {
+  const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+  for (int cl = wave; cl < ncell; cl += THREADS / 64) {
+    const unsigned r = qj[c0 + cl];
+    const bool live = r < (unsigned)K;
+    const float wv = wj ? wj[c0 + cl] : 1.f;
+    const float *__restrict__ src = table + (size_t)(live ? r : 0u) * K;
+    float *dst = rows + cl * K;
+    if (vec_table) {
+      for (int k4 = lane; k4 < (K >> 2); k4 += 64) {
+        float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (live) {
+          t = reinterpret_cast<const float4 *>(src)[k4];
+          t.x *= wv; t.y *= wv; t.z *= wv; t.w *= wv;
+        }
+        reinterpret_cast<float4 *>(dst)[k4] = t;
+      }
+    } else {
+      for (int k = lane; k < K; k += 64) dst[k] = live ? src[k] * wv : 0.f;
+    }
+  }
 }
 
 }  // namespace isi

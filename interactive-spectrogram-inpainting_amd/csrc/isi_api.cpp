@@ -321,6 +321,19 @@ int isi_code_search_f32(const uint16_t *codes, const uint16_t *query, const floa
   return code_search_f32(codes, query, weights, table, allowed, dist, N, C, K, Q, accumulate, workspace, workspace_bytes,
                          S(stream));
 }
+size_t isi_code_shift_search_workspace_bytes(int64_t N, int F, int T, int W, int S_, int K, int Q) {
+  return code_shift_search_workspace_bytes(N, F, T, W, S_, K, Q);
+}
+int isi_code_shift_search_f32(const uint16_t *codes, const uint16_t *query, const float *weights, const float *table,
+                              float *dist, int64_t N, int F, int T, int W, int shift0, int step, int S_, int K, int Q,
+                              int accumulate, void *workspace, size_t workspace_bytes, void *stream) {
+  return code_shift_search_f32(codes, query, weights, table, dist, N, F, T, W, shift0, step, S_, K, Q, accumulate, workspace,
+                               workspace_bytes, S(stream));
+}
+int isi_code_shift_best_f32(const float *dist, const uint8_t *allowed, float *best, int32_t *best_shift, int64_t N, int S_,
+                            int Q, void *stream) {
+  return code_shift_best_f32(dist, allowed, best, best_shift, N, S_, Q, S(stream));
+}
 int isi_rel_attention_f32(const isi_attn_args *args, void *stream) { return rel_attention_f32(args, S(stream)); }
 size_t isi_rel_attention_workspace_bytes(const isi_attn_args *args) { return rel_attention_workspace_bytes(args); }
 size_t isi_rel_attention_bwd_workspace_floats(const isi_attn_args *fwd) { return rel_attention_bwd_workspace_floats(fwd); }

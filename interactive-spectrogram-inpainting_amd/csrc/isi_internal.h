@@ -343,6 +343,22 @@ size_t code_search_workspace_bytes(int64_t N, int64_t C, int K, int Q);
 int code_search_f32(const uint16_t *codes, const uint16_t *query, const float *weights, const float *table,
                     const uint8_t *allowed, float *dist, int64_t N, int64_t C, int K, int Q, int accumulate, void *workspace,
                     size_t workspace_bytes, hipStream_t st);
+// the stage both searches share (device_prims.h: stage_code_rows): 64 KB of LDS hold `cc` table rows of K floats, at most 32,
+// a multiple of 8 from 8 cells on (code vectors hold 8 cells)
+constexpr int kCodeStageFloats = 16384;
+inline int code_chunk_cells(int K) {
+  int cc = kCodeStageFloats / K;
+  if (cc > 32) cc = 32;
+  if (cc >= 8) cc &= ~7;
+  return cc;
+}
+// code_shift_search.hip
+size_t code_shift_search_workspace_bytes(int64_t N, int F, int T, int W, int S, int K, int Q);
+int code_shift_search_f32(const uint16_t *codes, const uint16_t *query, const float *weights, const float *table, float *dist,
+                          int64_t N, int F, int T, int W, int shift0, int step, int S, int K, int Q, int accumulate,
+                          void *workspace, size_t workspace_bytes, hipStream_t st);
+int code_shift_best_f32(const float *dist, const uint8_t *allowed, float *best, int32_t *best_shift, int64_t N, int S, int Q,
+                        hipStream_t st);
 
 size_t packed_conv_weight_floats(int Cout, int Cin, int KH, int KW);
 size_t packed_convT_k4s2_weight_floats(int Cin, int Cout);

@@ -629,6 +629,131 @@ def similar_sounds(index, top_code: torch.Tensor, bottom_code: Optional[torch.Te
     return out
 
 
+def similar_fragments(index, top_code: torch.Tensor, bottom_code: Optional[torch.Tensor], start_index_top: int, width_top: int,
+                      mask: Optional[torch.Tensor] = None, layer: str = 'top', k: int = 8,
+                      shift_range: Optional[Tuple[int, int]] = None,
+                      attribute_constraints: Optional[Mapping[str, object]] = None):
+    """The k items of a `CodeIndex` that contain something nearest to a FRAGMENT of a sound, wherever it sits in time, as a
+    list of ((top [1,F_t,T_t], bottom [1,F_b,T_b]), attributes, distance, shift_top), nearest first (equal distances by
+    item index).  The query is the `width_top` top columns of the sound starting at `start_index_top` (and the matching
+    bottom columns, cut with the ratio `similar_sounds` uses); shift_top is the item's column under the window's first one.
+    mask bool [1,F,W] in the resolution of `layer` over that window: True = do not compare here; a top-layer mask extends to
+    the bottom layer as `timerange_change` extends it.  shift_range=(lo, hi): only offsets lo <= o < hi of the stored
+    maps.  The comparison runs on the device (`CodeIndex.search_shifted`, csrc/code_shift_search.hip)."""
+    if layer not in ('top', 'bottom'):
+        raise ValueError(f"unknown layer {layer}")
+    two = bottom_code is not None and index.bottom_shape is not None
+    top_code = top_code.reshape(1, *top_code.shape[-2:])
+    start, width = int(start_index_top), int(width_top)
+    if start < 0 or width < 1 or start + width > top_code.shape[-1]:
+        raise ValueError(f"the window [{start}, {start + width}) lies outside the top map's {top_code.shape[-1]} columns")
+    device = index.device
+    ratio_t = index.bottom_shape[1] // index.top_shape[1] if two else 1
+    ratio_f = index.bottom_shape[0] // index.top_shape[0] if two else 1
+    query_top = top_code[..., start:start + width]
+    query_bottom = bottom_code.reshape(1, *bottom_code.shape[-2:])[..., ratio_t * start:ratio_t * (start + width)] if two else None
+    mask_top = mask_bottom = None
+    if mask is not None:
+        mask = mask.to(device).reshape(1, *mask.shape[-2:])
+        want = (index.top_shape[0], width) if layer == 'top' else ((index.bottom_shape[0], ratio_t * width) if two else None)
+        if want is None:
+            raise ValueError("a bottom-layer mask needs bottom_code and an index that holds bottom maps")
+        if mask.dtype != torch.bool or tuple(mask.shape[-2:]) != want:
+            raise ValueError(f"mask: expected bool [1, {want[0]}, {want[1]}] over the window in the {layer} layer's "
+                             f"resolution, got {mask.dtype} {tuple(mask.shape)}")
+        if layer == 'top':
+            mask_top = mask
+            if two:
+                mask_bottom = mask.repeat_interleave(ratio_f, -2).repeat_interleave(ratio_t, -1)
+        else:
+            mask_bottom = mask
+    indices, shifts, distances = index.search_shifted(query_top.to(device), query_bottom.to(device) if two else None,
+                                                      mask_top=mask_top, mask_bottom=mask_bottom, k=k, shift_range=shift_range,
+                                                      attribute_constraints=attribute_constraints)
+    out = []
+    for i, o, d in zip(indices.tolist(), shifts.tolist(), distances.tolist()):
+        top, bottom, _ = index[i]
+        out.append(((top.unsqueeze(0), None if bottom is None else bottom.unsqueeze(0)), index.decoded_attributes(i), d, o))
+    return out
+
+
+def _paste_columns(sound: torch.Tensor, item: torch.Tensor, mask: torch.Tensor, start: int, shift: int) -> torch.Tensor:
+    """sound [1,F,T] with the cells under mask [1,F,W] (over the columns start .. start + W - 1) taken from item [1,F,T_i]:
+    column col from item column col - start + shift; columns outside the sound or the item stay as they are."""
+    sound = sound.clone()
+    columns = torch.arange(mask.shape[-1]) + int(start)
+    source = columns - int(start) + int(shift)
+    inside = (columns >= 0) & (columns < sound.shape[-1]) & (source >= 0) & (source < item.shape[-1])
+    chosen = mask.to(sound.device)[..., inside.to(sound.device)]
+    columns, source = columns[inside].to(sound.device), source[inside].to(sound.device)
+    sound[..., columns] = torch.where(chosen, item.to(sound.device, sound.dtype)[..., source], sound[..., columns])
+    return sound
+
+
+def paste_fragment(top_code: torch.Tensor, bottom_code: torch.Tensor, item_top: torch.Tensor, item_bottom: torch.Tensor,
+                   mask: torch.Tensor, layer: str, window_start_top: int, shift_top: int):
+    """Fill a hole with a retrieved sound's codes: the cells of (top_code [1,F_t,T], bottom_code [1,F_b,T_b]) under
+    mask bool [1,F,W] -- in the resolution of `layer`, over the window that starts at top column `window_start_top` -- take
+    the codes of (item_top, item_bottom), sound column `col` from item column `col - window_start_top + shift_top` (in
+    bottom columns: both scaled by the time ratio).  A top-layer mask extends to the bottom layer as `timerange_change`
+    extends it; a bottom-layer mask leaves the top map alone.  Cells whose source column falls outside the item stay
+    unchanged.  Pure indexing: works on CPU tensors.  Returns the new (top, bottom)."""
+    if layer not in ('top', 'bottom'):
+        raise ValueError(f"unknown layer {layer}")
+    top_code, bottom_code = top_code.reshape(1, *top_code.shape[-2:]), bottom_code.reshape(1, *bottom_code.shape[-2:])
+    item_top, item_bottom = item_top.reshape(1, *item_top.shape[-2:]), item_bottom.reshape(1, *item_bottom.shape[-2:])
+    mask = mask.reshape(1, *mask.shape[-2:])
+    ratio_t, ratio_f = bottom_code.shape[-1] // top_code.shape[-1], bottom_code.shape[-2] // top_code.shape[-2]
+    rows = top_code.shape[-2] if layer == 'top' else bottom_code.shape[-2]
+    if mask.dtype != torch.bool or mask.shape[-2] != rows:
+        raise ValueError(f"mask: expected bool [1, {rows}, W] in the {layer} layer's resolution, got "
+                         f"{mask.dtype} {tuple(mask.shape)}")
+    start, shift = int(window_start_top), int(shift_top)
+    if layer == 'top':
+        top_code = _paste_columns(top_code, item_top, mask, start, shift)
+        mask = mask.repeat_interleave(ratio_f, -2).repeat_interleave(ratio_t, -1)
+    else:
+        top_code = top_code.clone()
+    return top_code, _paste_columns(bottom_code, item_bottom, mask, ratio_t * start, ratio_t * shift)
+
+
+def patch_from_database(index, top_code: torch.Tensor, bottom_code: torch.Tensor, mask: torch.Tensor, layer: str = 'top',
+                        context_top: int = 4, k: int = 1, attribute_constraints: Optional[Mapping[str, object]] = None):
+    """Fill a hole from the code database instead of sampling it: mask bool [1,F,T] in the resolution of `layer` over the
+    WHOLE sound, its masked columns are the hole.  The query is the window from `context_top` top columns before the hole to
+    `context_top` after it, clipped to the sound, with the hole masked -- "agree with what surrounds my hole, anywhere in
+    time" (`similar_fragments`); each of the k nearest items is pasted into the hole at its best offset (`paste_fragment`).
+    Returns a list of ((top [1,F_t,T], bottom [1,F_b,T_b]), attributes, distance, shift_top), nearest first."""
+    if layer not in ('top', 'bottom'):
+        raise ValueError(f"unknown layer {layer}")
+    top_code, bottom_code = top_code.reshape(1, *top_code.shape[-2:]), bottom_code.reshape(1, *bottom_code.shape[-2:])
+    mask = mask.reshape(1, *mask.shape[-2:])
+    whole = top_code if layer == 'top' else bottom_code
+    if mask.dtype != torch.bool or tuple(mask.shape[-2:]) != tuple(whole.shape[-2:]):
+        raise ValueError(f"mask: expected bool [1, {whole.shape[-2]}, {whole.shape[-1]}] over the whole {layer} map, got "
+                         f"{mask.dtype} {tuple(mask.shape)}")
+    holed = mask.any(-2).reshape(-1).nonzero().reshape(-1)
+    if holed.numel() == 0:
+        raise ValueError("mask: nothing is masked, there is no hole to fill")
+    ratio_t = bottom_code.shape[-1] // top_code.shape[-1]
+    first, last = int(holed[0]), int(holed[-1]) + 1                  # the hole's columns [first, last) in `layer`
+    if layer == 'bottom':
+        first, last = first // ratio_t, -(-last // ratio_t)
+    start = max(0, first - int(context_top))
+    width = min(top_code.shape[-1], last + int(context_top)) - start
+    scale = 1 if layer == 'top' else ratio_t
+    window_mask = mask[..., scale * start:scale * (start + width)]
+    out = []
+    for (item_top, item_bottom), attributes, distance, shift in similar_fragments(
+            index, top_code, bottom_code, start, width, mask=window_mask, layer=layer, k=k,
+            attribute_constraints=attribute_constraints):
+        if item_bottom is None:
+            raise ValueError("patch_from_database: the index holds no bottom maps")
+        patched = paste_fragment(top_code, bottom_code, item_top, item_bottom, window_mask, layer, start, shift)
+        out.append((patched, attributes, distance, shift))
+    return out
+
+
 def sample_from_database(codes_dataset, label_encoders_per_modality: Mapping[str, object], duration_top: int,
                          attribute_constraints: Mapping[str, object], generator: Optional[torch.Generator] = None, *,
                          similar_to: Optional[Tuple[torch.Tensor, Optional[torch.Tensor]]] = None, index=None):

@@ -10,7 +10,10 @@ specification tests/code_search_spec.py): with the layer's codebook E [K, D],
 
 and a two-layer distance is alpha dist_top + beta dist_bottom.  The bits of an item's distance depend on the query, the
 weights, the item and the table only, so equal sounds stay tied and a ranking never flickers: results are ordered by
-(distance ascending, item index ascending).  No CPU path: the index, the VQ-VAE and the queries must live on the GPU."""
+(distance ascending, item index ascending).  `search_shifted` answers the fragment question -- "which stored sound contains
+something like this window, wherever it sits in time" -- with the same metric at every offset that fits
+(csrc/code_shift_search.hip, specification tests/code_shift_search_spec.py).  No CPU path: the index, the VQ-VAE and the
+queries must live on the GPU."""
 from __future__ import annotations
 
 import ctypes as C
@@ -23,6 +26,7 @@ import torch
 from ... import _hip
 
 MAX_QUERIES = 64          # isi_code_search_f32: 1 <= Q <= 64 per launch
+SHIFT_BUDGET_BYTES = 1 << 30      # search_shifted / distances_shifted: workspace + dist [Q, S, N] of one group of queries
 
 
 def _as_codes(codes, name: str, n_embed: int) -> torch.Tensor:
@@ -206,13 +210,20 @@ class CodeIndex:
         return cached[1]
 
     # ---- search
-    def _checked(self, layer: str, code, mask):
-        """(code [Q, F, T], mask or None, single) of one layer, shapes checked against the stored maps (ValueError)."""
+    def _checked(self, layer: str, code, mask, window: bool = False):
+        """(code [Q, F, T], mask or None, single) of one layer, shapes checked against the stored maps (ValueError).
+        window: the query may be narrower than the stored maps, [Q, F, W] with 1 <= W <= T."""
         stored = self.top if layer == 'top' else self.bottom
         if stored is None:
             raise ValueError(f"{layer}_code given, but the index holds no {layer} maps")
         shape = tuple(stored.shape[1:])
         code = torch.as_tensor(code)
+        if window:
+            if code.dim() not in (2, 3) or code.shape[-2] != shape[0] or not 1 <= code.shape[-1] <= shape[1] \
+                    or code.dtype.is_floating_point:
+                raise ValueError(f"{layer}_code: expected integer windows [{shape[0]}, W] (or [Q, ...]) with 1 <= W <= "
+                                 f"{shape[1]}, got {code.dtype} {tuple(code.shape)}")
+            shape = (shape[0], int(code.shape[-1]))
         if code.dim() not in (2, 3) or tuple(code.shape[-2:]) != shape or code.dtype.is_floating_point:
             raise ValueError(f"{layer}_code: expected integer codemaps [{shape[0]}, {shape[1]}] (or [Q, ...]) like the "
                              f"stored ones, got {code.dtype} {tuple(code.shape)}")
@@ -300,3 +311,126 @@ class CodeIndex:
         k = min(int(k), count)
         values, order = values[:, :k].contiguous(), order[:, :k].contiguous()
         return (order[0], values[0]) if single else (order, values)
+
+    # ---- shift-invariant search (csrc/code_shift_search.hip)
+    def _shift_plan(self, top_code, bottom_code, mask_top, mask_bottom, layer_weights, shift_range):
+        """Validation and geometry of a shifted search, before any device work: (checked layers, lo, count) with the
+        offsets lo .. lo + count - 1 in the columns of the first layer given."""
+        if top_code is None and bottom_code is None:
+            raise ValueError("search_shifted: give top_code, bottom_code or both")
+        if any(float(w) < 0 for w in layer_weights):
+            raise ValueError(f"layer_weights must be >= 0, got {tuple(layer_weights)}")
+        checked = [(layer, weight) + self._checked(layer, code, mask, window=True)
+                   for layer, code, mask, weight in (('top', top_code, mask_top, layer_weights[0]),
+                                                     ('bottom', bottom_code, mask_bottom, layer_weights[1])) if code is not None]
+        if len({c[2].shape[0] for c in checked}) != 1:
+            raise ValueError("top_code and bottom_code hold different numbers of queries")
+        stored = self.top if checked[0][0] == 'top' else self.bottom
+        T, W = int(stored.shape[2]), int(checked[0][2].shape[2])
+        if len(checked) == 2:
+            ratio = self.bottom.shape[2] // self.top.shape[2]
+            if ratio < 1 or ratio * self.top.shape[2] != self.bottom.shape[2]:
+                raise ValueError(f"the bottom maps' {self.bottom.shape[2]} columns are no multiple of the top maps' "
+                                 f"{self.top.shape[2]}: a two-layer shifted search has no common offset")
+            if checked[1][2].shape[2] != ratio * W:
+                raise ValueError(f"bottom_code: {checked[1][2].shape[2]} columns, but the top window's {W} columns span "
+                                 f"{ratio * W} of the bottom layer")
+        lo, hi = 0, T - W + 1
+        if shift_range is not None:
+            if len(shift_range) != 2:
+                raise ValueError(f"shift_range: expected (lo, hi), got {shift_range}")
+            lo, hi = max(lo, int(shift_range[0])), min(hi, int(shift_range[1]))
+            if lo >= hi:
+                raise ValueError(f"shift_range {tuple(shift_range)} holds no offset at which a window of {W} columns fits "
+                                 f"the stored {T}")
+        return checked, lo, hi - lo
+
+    def _shifted_jobs(self, checked):
+        jobs = []
+        for layer, weight, code, mask, single in checked:
+            query, weights = self._query(layer, code, mask, weight)
+            jobs.append((layer, query, weights, int(code.shape[2]), single))
+        return jobs
+
+    def _shifted_group_size(self, jobs, count) -> int:
+        """Queries per launch so that workspace + dist [g, S, N] stay under SHIFT_BUDGET_BYTES (at least 1)."""
+        N = len(self)
+        runs = max(-(-(self.top if layer == 'top' else self.bottom).shape[1] * W // 256) for layer, _, _, W, _ in jobs)
+        per_query = (1 + (runs if runs > 1 else 0)) * count * N * 4
+        return max(1, min(MAX_QUERIES, SHIFT_BUDGET_BYTES // per_query))
+
+    def _shifted_into(self, jobs, q0: int, q1: int, first: int, count: int, dist: torch.Tensor) -> None:
+        """dist [q1 - q0, count, N] (contiguous) of the queries q0 .. q1 - 1 at the offsets first .. first + count - 1."""
+        lib, stream = _hip.lib(), C.c_void_p(_hip.stream_ptr(self.device))
+        N, Q = len(self), q1 - q0
+        ratio = 1 if len(jobs) == 1 else self.bottom.shape[2] // self.top.shape[2]
+        for n_done, (layer, query, weights, W, _) in enumerate(jobs):
+            stored = self.top if layer == 'top' else self.bottom
+            table = self.table(layer)
+            F, T, K = int(stored.shape[1]), int(stored.shape[2]), table.shape[0]
+            step = ratio if n_done > 0 else 1
+            need = lib.isi_code_shift_search_workspace_bytes(N, F, T, W, count, K, Q)
+            if self._workspace is None or self._workspace.numel() * 4 < need:
+                self._workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=self.device)
+            _hip.check(lib.isi_code_shift_search_f32(
+                stored.data_ptr(), query[q0:q1].data_ptr(), None if weights is None else weights[q0:q1].data_ptr(),
+                table.data_ptr(), dist.data_ptr(), N, F, T, W, step * first, step, count, K, Q, int(n_done > 0),
+                self._workspace.data_ptr(), self._workspace.numel() * 4, stream), "isi_code_shift_search_f32")
+
+    def _shifted_groups(self, jobs, lo: int, count: int):
+        """Yields (q0, q1, dist [q1 - q0, count, N]) group by group.  The launch starts at a multiple of 8 columns (the
+        kernel reads aligned vectors from there); the offsets below `lo` are computed and dropped."""
+        Q, N = jobs[0][1].shape[0], len(self)
+        first = lo - lo % 8
+        group = self._shifted_group_size(jobs, count + lo - first)
+        for q0 in range(0, Q, group):
+            q1 = min(Q, q0 + group)
+            dist = torch.empty(q1 - q0, count + lo - first, N, dtype=torch.float32, device=self.device)
+            self._shifted_into(jobs, q0, q1, first, count + lo - first, dist)
+            yield q0, q1, (dist if first == lo else dist[:, lo - first:].contiguous())
+
+    def distances_shifted(self, top_code=None, bottom_code=None, *, mask_top=None, mask_bottom=None,
+                          layer_weights: Tuple[float, float] = (1., 1.), shift_range: Optional[Tuple[int, int]] = None):
+        """dist fp32 [Q, S, N]: the distance of every query window to every item at every offset of `search_shifted`
+        (dist[:, s] belongs to the offset lo + s, lo = the first allowed one).  Q S N floats: for callers that want
+        every offset, not for the whole of a large database at once."""
+        checked, lo, count = self._shift_plan(top_code, bottom_code, mask_top, mask_bottom, layer_weights, shift_range)
+        jobs = self._shifted_jobs(checked)
+        return torch.cat([dist for _, _, dist in self._shifted_groups(jobs, lo, count)], 0)
+
+    def search_shifted(self, top_code=None, bottom_code=None, *, mask_top=None, mask_bottom=None,
+                       layer_weights: Tuple[float, float] = (1., 1.), k: int = 8,
+                       shift_range: Optional[Tuple[int, int]] = None,
+                       attribute_constraints: Optional[Mapping[str, object]] = None, exclude: Optional[Sequence[int]] = None):
+        """The k stored items that CONTAIN something nearest to a fragment, wherever it sits in time:
+        (indices int64 [k], shifts int64 [k], distances float32 [k]); [Q, k] each for Q > 1 queries.
+        top_code [F_t, W_t] (or [Q, F_t, W_t]) with W_t <= T_t, bottom_code [F_b, r W_t] with r = T_b / T_t; the window is
+        laid over each item at every offset o with o + W <= T, an item counts once, at its best offset (the smallest of
+        equal ones), and `shifts` holds that absolute offset -- in top columns whenever a top query is given, in bottom
+        columns for a bottom query alone.  shift_range=(lo, hi): only offsets lo <= o < hi.  mask_*, layer_weights,
+        attribute_constraints, exclude, the (distance, item index) order, LookupError / ValueError / HipLibraryError: as
+        `search`.  The queries run in groups whose workspace and dist [Q, S, N] stay under SHIFT_BUDGET_BYTES; distances
+        are query- and item-local, so the grouping changes no bit."""
+        if int(k) < 1:
+            raise ValueError(f"k must be at least 1, not {k}")
+        checked, lo, count = self._shift_plan(top_code, bottom_code, mask_top, mask_bottom, layer_weights, shift_range)
+        allowed = self.allowed(attribute_constraints, exclude)
+        n_allowed = len(self) if allowed is None else int(allowed.sum())
+        if n_allowed < 1:
+            raise LookupError(f"no item of the index meets {dict(attribute_constraints or {})}"
+                              + (f" outside {list(exclude)}" if exclude is not None and len(exclude) else ""))
+        jobs = self._shifted_jobs(checked)
+        lib, stream = _hip.lib(), C.c_void_p(_hip.stream_ptr(self.device))
+        Q, N = jobs[0][1].shape[0], len(self)
+        best = torch.empty(Q, N, dtype=torch.float32, device=self.device)
+        best_shift = torch.empty(Q, N, dtype=torch.int32, device=self.device)
+        for q0, q1, dist in self._shifted_groups(jobs, lo, count):
+            _hip.check(lib.isi_code_shift_best_f32(dist.data_ptr(), None if allowed is None else allowed.data_ptr(),
+                                                   best[q0:q1].data_ptr(), best_shift[q0:q1].data_ptr(), N, count, q1 - q0,
+                                                   stream), "isi_code_shift_best_f32")
+        values, order = torch.sort(best, dim=1, stable=True)
+        k = min(int(k), n_allowed)
+        values, order = values[:, :k].contiguous(), order[:, :k].contiguous()
+        shifts = torch.gather(best_shift, 1, order).to(torch.int64) + lo
+        single = all(job[4] for job in jobs)
+        return (order[0], shifts[0], values[0]) if single else (order, shifts, values)

@@ -499,17 +499,22 @@ int isi_grad_sumsq_f32(const isi_adam_tensor *tensors, int n_tensors, float *par
 int isi_grad_clip_coef_f32(const float *partials, int64_t n_partials, float max_norm, float *norm_coef, void *stream);
 int isi_adam_step_f32(const isi_adam_tensor *tensors, int n_tensors, const isi_adam_hyper *hyper, int n_groups,
                       const float *coef, void *stream);
-/* dy *= (y > 0) : ReLU backward through an output rectified in the producer's epilogue. */
+/* The element-wise operators below read and write float4: a call whose arguments do not fit is refused with
+ * ISI_E_INVALID before any launch (tests/test_train_ops_host.py), never run on a slower path.
+ * dy = y > 0 ? dy : 0 (a selection: a NaN of dy under the mask gives 0): ReLU backward through an output rectified in
+ * the producer's epilogue.  Any n >= 0; dy and y 16-byte aligned. */
 int isi_relu_bwd_f32(float *dy, const float *y, int64_t n, void *stream);
-/* a += alpha * b */
+/* a += alpha * b.  n % 4 == 0; a and b 16-byte aligned. */
 int isi_axpy_f32(float *a, const float *b, float alpha, int64_t n, void *stream);
-/* Quantiser backward (bottleneck.py:94-95): dz = dq + 2 g_diff (z - q_st) / n. */
+/* Quantiser backward (bottleneck.py:94-95): dz = dq + 2 g_diff (z - q_st) / n.  n > 0, n % 4 == 0; dz, dq, z and q_st
+ * 16-byte aligned (g_diff: one float on the device). */
 int isi_vq_bwd_f32(float *dz, const float *dq, const float *z, const float *q_st,
                    const float *g_diff, int64_t n, void *stream);
 /* out[m][c] = (y[m][c] > 0) * (a[m][c] + b[m][c]) over M rows of C channels: two gradient contributions summed and masked by
  * the ReLU of the tensor they belong to in one pass; `a` may be a channel slice of a wider channels-last tensor (row stride
  * lda), b / y dense [M, C] or NULL (no second term / no mask).  Same, for the quantiser backward, with dq read through a
- * row stride (isi_vq_bwd_f32 on a channel slice without a dense copy first). */
+ * row stride (isi_vq_bwd_f32 on a channel slice without a dense copy first).  C (D) and lda (ldq) multiples of 4,
+ * lda >= C (ldq >= D); every pointer given 16-byte aligned. */
 /* src [B, C <= 4, H, W] (any strides) -> dense channels-last [B, H, W, 4] with the channels >= C zero: the 2-channel
  * spectrogram side as an operand of the vectorised weight-gradient kernels (train_vqvae.py:181 through vqvae/_train.py). */
 int isi_pad_channels4_f32(const isi_src *src, float *out_nhwc4, int B, int H, int W, void *stream);
@@ -523,7 +528,9 @@ int isi_mse_loss_num_partials(int64_t n);
 int isi_mse_loss_f32(const float *a, const float *b, int64_t n, float *workspace, float *out, void *stream);
 int isi_mse_loss_bwd_f32(const float *a, const float *b, const float *g, int64_t n, float *da, float *db, void *stream);
 
-/* out[C] = column sums of x [M, C] (bias gradients); workspace isi_colsum_num_partials(M)*C floats. */
+/* out[C] = column sums of x [M, C] (bias gradients); workspace isi_colsum_num_partials(M)*C floats.  x_stride >= C (floats
+ * between rows; less is refused); no alignment requirement: a dense, 16-byte aligned x with C a power of two <= 1024 and
+ * M * C % 4 == 0 is streamed as float4, everything else by scalar loads.  Fixed summation order on either route. */
 int isi_colsum_num_partials(int64_t M);
 int isi_colsum_f32(const float *x, int64_t x_stride, float *out, float *workspace, int64_t M,
                    int C, void *stream);
@@ -1011,7 +1018,8 @@ int isi_vq_finalize_f32(const float *sse_part, int n_part, const int32_t *counts
 
 /* embed_code: out[N, D] = codes_kd[idx[n], :]  (bottleneck.py:103-104).
  * Index range is not reported from the device: callers validate 0 <= idx < K
- * (out-of-range values are clamped so that no read leaves the codebook). */
+ * (out-of-range values are clamped so that no read leaves the codebook).  D % 4 == 0; codes_kd and out
+ * 16-byte aligned (rows are copied as float4; a misaligned pointer is refused with ISI_E_INVALID). */
 int isi_embed_code_f32(const int64_t *idx, const float *codes_kd, float *out,
                        int64_t N, int D, int K, void *stream);
 

@@ -287,6 +287,8 @@ int relu_bwd_f32(float *dy, const float *y, int64_t n, hipStream_t st) {
 
 int axpy_f32(float *a, const float *b, float alpha, int64_t n, hipStream_t st) {
   if (!a || !b || n < 0 || (n & 3)) return invalid("axpy: bad argument (n % 4 == 0 required)");
+  if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15)
+    return invalid("axpy: pointers must be 16-byte aligned");
   if (n == 0) return ISI_OK;
   hipLaunchKernelGGL(axpy_kernel, dim3(grid_for(n / 4)), dim3(256), 0, st, a, b, alpha, n / 4);
   return check_launch("axpy_f32");
@@ -323,6 +325,8 @@ int vq_bwd_rows_f32(float *dz, const float *dq, int64_t ldq, const float *z, con
 int vq_bwd_f32(float *dz, const float *dq, const float *z, const float *q_st, const float *g_diff, int64_t n,
                hipStream_t st) {
   if (!dz || !dq || !z || !q_st || !g_diff || n <= 0 || (n & 3)) return invalid("vq_bwd: bad argument");
+  if ((reinterpret_cast<uintptr_t>(dz) | reinterpret_cast<uintptr_t>(dq) | reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(q_st)) & 15)
+    return invalid("vq_bwd: pointers must be 16-byte aligned");
   hipLaunchKernelGGL(vq_bwd_kernel, dim3(grid_for(n / 4)), dim3(256), 0, st, dz, dq, z, q_st, g_diff,
                      1.0f / (float)n, n / 4);
   return check_launch("vq_bwd_f32");
@@ -394,6 +398,7 @@ __global__ __launch_bounds__(256) void colsum_flat_kernel(const float4 *__restri
 
 int colsum_f32(const float *x, int64_t x_stride, float *out, float *workspace, int64_t M, int C, hipStream_t st) {
   if (!x || !out || !workspace || M <= 0 || C <= 0) return invalid("colsum: bad argument");
+  if (x_stride < C) return invalid("colsum: x_stride must be at least C");
   const int nblk = colsum_num_partials(M);
   if (x_stride == C && C <= 1024 && (C & (C - 1)) == 0 && ((M * C) & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
     const int64_t n4 = M * C / 4;

@@ -1156,6 +1156,8 @@ int embed_code_f32(const int64_t *idx, const float *codes, float *out, int64_t N
                    hipStream_t stream) {
   if (!idx || !codes || !out || N <= 0 || D <= 0 || (D % 4) != 0 || K <= 0)
     return invalid("embed_code: bad argument");
+  if ((reinterpret_cast<uintptr_t>(codes) | reinterpret_cast<uintptr_t>(out)) & 15)
+    return invalid("embed_code: codes and out must be 16-byte aligned");
   const int64_t total = N * (D / 4);
   hipLaunchKernelGGL(embed_code_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
                      idx, codes, out, N, D / 4, K);

@@ -425,6 +425,191 @@ def layernorm_data(kind, M, D, gen):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Float64 specifications of the small kernels of the VQ-VAE training step (csrc/train_ops.hip, and vq_finalize / embed_code
+# of csrc/vq_nearest.hip), in the style of the row-ops block above: closed forms in torch float64 on the CPU, no autograd and
+# none of the project's kernels; beside each a float32 torch evaluation of the same operation, the yardstick of
+# `compare_rows`, whose keyword switches are the host tests' mutants.  tests/test_train_ops_host.py holds the specs to
+# float64 autograd of the reference formulation and shows what the comparisons reject; tests/test_train_ops_gpu.py holds
+# the kernels to them.  Operations that round nowhere (a selection, a gather) are held bit for bit: `same_bits`.
+TRAIN_OPS_GRID_CAP = 8192 * 256        # threads of the largest grid-stride launch of csrc/train_ops.hip (`grid_for`)
+
+
+def same_bits(got, want):
+    """Bit for bit (NaN payloads and the sign of zero included) after `want` is cast to float32."""
+    got, want = torch.as_tensor(got).detach().cpu(), torch.as_tensor(want).detach().cpu().float()
+    return got.dtype == torch.float32 and got.shape == want.shape and bool(torch.equal(got.contiguous().view(torch.int32),
+                                                                                     want.contiguous().view(torch.int32)))
+
+
+def relu_bwd_spec(dy, y):
+    """where(y > 0, dy, 0): a selection, as torch's threshold_backward -- a NaN or inf of dy where y <= 0 gives 0, and
+    y = -0.0 masks like +0.0."""
+    dy = _f64(dy)
+    return torch.where(_f64(y) > 0, dy, torch.zeros_like(dy))
+
+
+def relu_bwd_f32(dy, y, gate_ge=False, multiply=False):
+    """Mutants: `gate_ge`, the gate as y >= 0; `multiply`, the gate as a factor (a masked NaN leaks through)."""
+    dy, y = dy.float(), y.float()
+    keep = (y >= 0) if gate_ge else (y > 0)
+    return dy * keep.float() if multiply else torch.where(keep, dy, torch.zeros_like(dy))
+
+
+def relu_inplace_spec(x):
+    """x < 0 ? 0 : x -- NaN stays NaN, -0.0 stays -0.0."""
+    x = _f64(x)
+    return torch.where(x < 0, torch.zeros_like(x), x)
+
+
+def axpy_spec(a, b, alpha):
+    """a + alpha b, alpha the float32 value the C-ABI receives."""
+    return _f64(a) + float(np.float32(alpha)) * _f64(b)
+
+
+def axpy_f32(a, b, alpha):
+    return a.float() + torch.tensor(alpha, dtype=torch.float32) * b.float()
+
+
+def vq_bwd_spec(dq, z, q_st, g_diff):
+    """Quantiser backward (bottleneck.py:94-95): dz = dq + 2 g_diff (z - q_st) / numel(z) -- the straight-through gradient
+    plus that of diff = mean((q.detach() - z)^2), with the forward's q_st = z + (q - z) standing for q.  dq may be a
+    row-strided view: the values are the same."""
+    z = _f64(z)
+    return _f64(dq).reshape(z.shape) + 2.0 * float(g_diff) * (z - _f64(q_st)) / z.numel()
+
+
+def vq_bwd_f32(dq, z, q_st, g_diff, two=2.0):
+    """Mutant: `two`, the coefficient's numerator (1: the gradient of half the commitment term)."""
+    z = z.float()
+    coef = torch.tensor(two * float(g_diff), dtype=torch.float32) / float(z.numel())
+    return dq.float().reshape(z.shape) + coef * (z - q_st.float())
+
+
+def add_gate_rows_spec(a, b=None, y=None):
+    """where(y > 0, a + b, 0) over [M, C] rows; b = None: no second term; y = None: no gate.  A selection like
+    relu_bwd_spec."""
+    s = _f64(a) if b is None else _f64(a) + _f64(b)
+    return s if y is None else torch.where(_f64(y) > 0, s, torch.zeros_like(s))
+
+
+def add_gate_rows_f32(a, b=None, y=None, gate_ge=False, multiply=False):
+    """Mutants as relu_bwd_f32."""
+    s = a.float() if b is None else a.float() + b.float()
+    return s if y is None else relu_bwd_f32(s, y, gate_ge, multiply)
+
+
+def colsum_spec(x):
+    """Column sums of x [M, C]: the bias gradient of a layer whose output gradient has the rows of x."""
+    return _f64(x).sum(dim=0)
+
+
+def colsum_f32(x, rows=None, fold4=False):
+    """Mutants: `rows`, only the first `rows` rows are summed (a block's share dropped); `fold4`, for C < 4 column c takes
+    component c of every float4 of the flat array, as the fold for C >= 4 would."""
+    x = x.float()
+    if fold4:
+        assert x.shape[1] < 4 and x.numel() % 4 == 0
+        return x.reshape(-1, 4).sum(dim=0)[:x.shape[1]]
+    return (x if rows is None else x[:rows]).sum(dim=0)
+
+
+def colsum_route(M, C, x_stride, ptr):
+    """The kernel `colsum_f32` of csrc/train_ops.hip sends a call to, from its own conditions: "flat" (colsum_flat_kernel:
+    dense, C a power of two <= 1024, M C a multiple of 4, 16-byte aligned) or "partial" (colsum_partial_kernel)."""
+    flat = x_stride == C and C <= 1024 and C & (C - 1) == 0 and (M * C) % 4 == 0 and ptr % 16 == 0
+    return "flat" if flat else "partial"
+
+
+def mse_spec(a, b, g):
+    """(value [1], da, db) of mean((a - b)^2) under the incoming scalar gradient g: da = 2 (a - b) g / n, db = -da."""
+    d = _f64(a) - _f64(b)
+    da = 2.0 * d * float(g) / d.numel()
+    return d.pow(2).mean().reshape(1), da, -da
+
+
+def mse_f32(a, b, g, two=2.0, count=None):
+    """Mutants: `two` as in vq_bwd_f32; `count`, only the first `count` elements enter the sum (still divided by n)."""
+    d = a.float() - b.float()
+    n = d.numel()
+    da = d * (torch.tensor(two, dtype=torch.float32) / float(n) * torch.tensor(float(g), dtype=torch.float32))
+    return (d.reshape(-1)[:count].pow(2).sum() / float(n)).reshape(1), da, -da
+
+
+def vq_finalize_spec(sse_part, counts, N, D):
+    """(diff [1], perplexity [1]) (bottleneck.py:94, 97-100): diff = sum(sse_part) / (N D); perplexity =
+    exp(-sum p log(max(p, 1e-7))), p = counts / N."""
+    p = _f64(counts) / float(N)
+    h = (p * torch.log(p.clamp(min=1e-7))).sum()
+    return (_f64(sse_part).sum() / (float(N) * float(D))).reshape(1), torch.exp(-h).reshape(1)
+
+
+def vq_finalize_f32(sse_part, counts, N, D, clamp=True):
+    """Mutant: `clamp` = False, the logarithm of p itself (an unused code gives 0 * -inf)."""
+    p = counts.float() / float(N)
+    h = (p * torch.log(p.clamp(min=1e-7) if clamp else p)).sum()
+    return (sse_part.float().sum() / (float(N) * float(D))).reshape(1), torch.exp(-h).reshape(1)
+
+
+def ema_update_spec(embed, cluster_size, embed_avg, counts, embed_sum, decay, eps):
+    """(embed', cluster_size', embed_avg') of the EMA codebook update (bottleneck.py:80-92), layout [D][K]:
+    cs = decay cluster_size + (1 - decay) counts; ea = decay embed_avg + (1 - decay) embed_sum; n = sum(cs);
+    embed' = ea / ((cs + eps) / (n + K eps) n).  decay and eps are the float32 values the C-ABI receives (`embed` itself is
+    not read: the update replaces it)."""
+    decay, eps = float(np.float32(decay)), float(np.float32(eps))
+    cs = _f64(cluster_size) * decay + (1.0 - decay) * _f64(counts)
+    ea = _f64(embed_avg) * decay + (1.0 - decay) * _f64(embed_sum)
+    n = cs.sum()
+    csn = (cs + eps) / (n + cs.shape[0] * eps) * n
+    return ea / csn.unsqueeze(0), cs, ea
+
+
+def ema_update_f32(embed, cluster_size, embed_avg, counts, embed_sum, decay, eps, n_codes=None):
+    """Mutant: `n_codes`, only the first `n_codes` codes enter the total n."""
+    decay, eps = torch.tensor(decay, dtype=torch.float32), torch.tensor(eps, dtype=torch.float32)
+    cs = cluster_size.float() * decay + (1.0 - decay) * counts.float()
+    ea = embed_avg.float() * decay + (1.0 - decay) * embed_sum.float()
+    n = cs[:n_codes].sum()
+    csn = (cs + eps) / (n + float(cs.shape[0]) * eps) * n
+    return ea / csn.unsqueeze(0), cs, ea
+
+
+def embed_code_spec(idx, codes, K):
+    """out[n] = codes[clamp(idx[n], 0, K - 1)] for codes [K, D]: the documented clamp of an out-of-range index."""
+    return _f64(codes)[torch.as_tensor(idx).cpu().long().reshape(-1).clamp(0, K - 1)]
+
+
+def ema_state(D, K, gen, N=256):
+    """A calibrated codebook state and one batch's statistics, float32: (embed [D, K], cluster_size [K], embed_avg =
+    embed * cluster_size, counts [K], embed_sum [D, K]); both usage draws are peaked, so some codes are unused in
+    either (cluster_size 0 with counts 0 gives embed' = 0 / (eps ...) = 0).  N, the vectors per batch, is small on purpose:
+    embed' = ea / (cs + eps) * (1 + K eps / n) depends on the total n only through K eps / n, 8e-5 at K = 2048 and
+    n = 256 but 5e-6 at n = 4096 -- a wrong total would hide under the comparison's floor at a large batch."""
+    embed = torch.randn(D, K, generator=gen)
+    w = torch.exp(-torch.arange(K, dtype=torch.float32) * (6.0 / K))
+    w = w[torch.randperm(K, generator=gen)]
+    cluster_size = torch.bincount(torch.multinomial(w, N, replacement=True, generator=gen), minlength=K).float()
+    idx = torch.multinomial(w, N, replacement=True, generator=gen)
+    counts = torch.bincount(idx, minlength=K).float()
+    z = embed.t()[idx] + 0.1 * torch.randn(N, D, generator=gen)
+    embed_sum = torch.zeros(K, D).index_add_(0, idx, z).t().contiguous()
+    return embed, cluster_size, embed * cluster_size, counts, embed_sum
+
+
+def gate_data(n, gen):
+    """(dy, y) float32 [n] for a ReLU gate: y = randn with +0.0, -0.0, the smallest normal 2^-126 and negatives at the head,
+    at the tail and throughout (no denormals); dy = randn with NaN, +inf and -inf at masked places (y <= 0) only."""
+    y = torch.randn(n, generator=gen)
+    special = torch.tensor([0.0, -0.0, 2.0 ** -126, -1.5, 3.0])
+    where = torch.cat([torch.arange(min(n, 5)), torch.arange(5, max(n, 5), 13), torch.arange(max(n - 5, 0), n)])
+    y[where] = special[where % 5]
+    dy = torch.randn(n, generator=gen)
+    masked = (y <= 0).nonzero().reshape(-1)
+    for j, v in enumerate((float("nan"), float("inf"), float("-inf"))):
+        dy[masked[j::4]] = v
+    return dy, y
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Float64 specification, float32 yardstick and split-product models of the convolution weight gradients
 # (csrc/conv_wgrad_f32.hip), in the style of the row-ops block above: plain torch on the CPU, no autograd and none of the
 # project's kernels.  A weight gradient is an im2col contraction over pixels,

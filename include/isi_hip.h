@@ -658,7 +658,11 @@ int isi_set_dropout_seed_base(const void *device_u64);
  *              function of (seed, index): nothing is stored; a dropped element of a rectified output is 0 and gates its
  *              own gradient.  (`F.dropout` in train mode: same distribution, not torch's random stream.)
  * flags: ISI_CONV_RELU | one of ISI_CONV_BF16X3 / ISI_CONV_F16X3 | ISI_CONV_W16 as for isi_conv2d_f32.  Shapes the GEMM
- * kernel does not take (K % 32, K < 128, N <= 32, M < 256) return ISI_E_UNSUPPORTED: the caller keeps isi_conv2d_f32. */
+ * kernel does not take (K % 32, K < 128, N <= 32, M < 256) return ISI_E_UNSUPPORTED: the caller keeps isi_conv2d_f32.
+ * Refused before any launch: a row stride shorter than its row (ldx < K, ldo < N, a residual's ldr < N) and drop_p < 0 or
+ * NaN: ISI_E_INVALID; drop_p >= 1, a gate's ldg < N, and x, out, residual, gate or the weight spanning more than
+ * 2^30 - 4 elements ((M - 1) ld + width; the kernel's byte offsets are 32-bit and 2^32 - 16 marks "out of range"):
+ * ISI_E_UNSUPPORTED. */
 typedef struct isi_linear_args {
   const float *x;
   int64_t ldx;
@@ -674,6 +678,10 @@ typedef struct isi_linear_args {
   uint64_t drop_seed;
 } isi_linear_args;
 int isi_linear_f32(const isi_linear_args *args, void *stream);
+/* Which kernel isi_linear_f32 would launch for this shape on the current device, nothing launched:
+ * 0 = refused (outside the GEMM kernel); else tile | tail_rows << 8 with tile 1 = 128x64, 2 = 128x128,
+ * 3 = 256x128, 4 = 256x256.  Reads the device's CU count and ISI_GEMM_NARROW_BELOW / ISI_GEMM_NO_WIDE. */
+int isi_linear_route(int M, int N, int K, int flags);
 
 /* Backward of isi_layernorm_f32: dz = d loss / d (x + residual) (the gradient of both x and
  * residual), dgamma / dbeta [D] (overwritten; deterministic two-stage reduction).

@@ -691,7 +691,7 @@ int conv2d_batched_f32(const isi_src *s0, const isi_src *s1, const float *packed
   const int64_t e1 = two ? extent(B, s1->sn, s1->C, 1, H, s1->sh, W, s1->sw) : 1;
   const int64_t eo = extent(B, dst->sn, Cout, dst->sc, OH, dst->sh, OW, dst->sw);
   const int64_t er = (res && res->ptr) ? extent(B, res->sn, Cout, res->sc, OH, res->sh, OW, res->sw) : 1;
-  if (e0 > kMaxElems || e1 > kMaxElems || eo > kMaxElems || er > kMaxElems)
+  if (e0 >= kMaxElems || e1 >= kMaxElems || eo >= kMaxElems || er >= kMaxElems)   // (2^30 elements: the byte count wraps to 0)
     return unsupported("conv2d: a tensor spans 4 GiB or more");
   if ((!gate || (!(relu & (ISI_CONV_OUT_PAIR | ISI_CONV_GATE_PAIR)) && aligned16(gate))) && e0 <= kMaxElems && eo <= kMaxElems &&
       aligned16(packed_w) && conv_first_applicable(s0, s1, res, dst, Cout, KH, KW, stride, pad, OH, OW, nz)) {
@@ -766,7 +766,7 @@ int conv_transpose2d_k4s2_f32(const isi_src *s, const float *packed_w, const flo
   if ((int64_t)B * H * W > INT32_MAX) return unsupported("convT: more than 2^31 pixels per phase");
   const int64_t e0 = extent(B, s->sn, s->C, s->sc, H, s->sh, W, s->sw);
   const int64_t eo = extent(B, dst->sn, Cout, dst->sc, 2 * H, dst->sh, 2 * W, dst->sw);
-  if (e0 > kMaxElems || eo > kMaxElems) return unsupported("convT: a tensor spans 4 GiB or more");
+  if (e0 >= kMaxElems || eo >= kMaxElems) return unsupported("convT: a tensor spans 4 GiB or more");
   if (convT_small_applicable(s->C, Cout)) {
     if (relu & ISI_CONV_IN0_PAIR) {
       // pair-format input: the LDS-DMA form of the few-channel kernel (dense channels-last source, fp32 output)

@@ -368,19 +368,55 @@ bool gemm_split_applicable(int M, int N, int K, int split_mode) {
   return (split_mode == 1 || split_mode == 3) && K % 32 == 0 && K >= 128 && N > 32 && M >= 256;   // (K, N: where the convolution kernel uses split products too)
 }
 
-int gemm_split_f32(const float *a, int64_t lda, const float *w, const float *bias, const float *res, int64_t ldr, float *out,
-                   int64_t ldo, int M, int N, int K, int relu, int split_mode, hipStream_t stream, const float *w16,
-                   const GemmExtra *extra) {
+// The tile a launch runs and the rows it leaves to the fp32 dot products (isi_linear_route reports the same answer: the
+// launch code below has no other source for it).  `rows4`: the operand's row stride is a multiple of 4 floats (the tail
+// rows are read as float4); `plain`: one product, no band -- what the 256-row tiles take.
+GemmRoute gemm_split_route(int M, int N, bool rows4, bool plain) {
+  GemmRoute r;
+  r.tile = 1; r.tail = 0;
   // A few rows beyond a multiple of the tile height (the prior's B x (S + 1) = 8 x 1025 = 64 tiles + 8 rows) would add a
   // whole column of 128-row tiles: 520 instead of 512 for N = 512, and with two workgroups per CU the launch then
   // runs TWO rounds (28 vs 22 us at K = 512, 92 vs 66 us at K = 2048, measured).  The tiles cover the full tile rows
   // only and every workgroup finishes with its share of the remaining rows' dot products (fp32 FMA, exact operands;
   // the few-row kernel of the decode path as a second launch was measured too: 10 us, as much as it saved).
+  const int rem = M % BM;
+  if (rem > 0 && rem <= kGemmTailRows && M >= 8 * BM && rows4) { r.tail = rem; M -= rem; }
+  // 128 x 64 tiles when 128 x 128 ones would leave CUs without a second workgroup
+  const long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128);
+  // (from one workgroup per CU on: M = 8200, N = 512, K = 2048 72 -> 66 us with 128 x 128 tiles, K = 512 the same either way)
+  const int cus = current_device_cu_count();
+  const int narrow_below = knobs().gemm_narrow_below > 0 ? knobs().gemm_narrow_below : cus;
+  const bool narrow = tiles128 < narrow_below || N % 128 != 0;
+  if (narrow) return r;
+  r.tile = 2;
+  // 256 x 128 tiles (one workgroup per CU) where they come in whole rounds of the chip: the widest layers (measured at
+  // M = 8200, K = 512, tools/bench_linear.py with ISI_GEMM_NO_WIDE: N = 2048 (two rounds) 79 -> 70 us, N = 1024 (one round)
+  // 42 -> 40 us; N = 1536 (one and a half rounds) 63 -> 70 us: not taken)
+  const long tiles256 = (long)((M + 255) / 256) * ((N + 127) / 128);
+  const long tiles256x256 = (long)((M + 255) / 256) * ((N + 255) / 256);
+  if (plain && N % 256 == 0 && tiles256x256 == cus && !knobs().gemm_no_wide) r.tile = 4;
+  else if (plain && tiles256 % cus == 0 && knobs().gemm_no_wide != 1) r.tile = 3;
+  return r;
+}
+
+int gemm_split_linear_route(int M, int N, int K, int split_mode) {
+  if (M <= 0 || N <= 0 || K <= 0 || !gemm_split_applicable(M, N, K, split_mode) || knobs().no_gemm_kernel) return 0;
+  const GemmRoute r = gemm_split_route(M, N, true, true);      // (isi_linear_f32 takes rows of a multiple of 4 floats only)
+  return r.tile | r.tail << 8;
+}
+
+int gemm_split_f32(const float *a, int64_t lda, const float *w, const float *bias, const float *res, int64_t ldr, float *out,
+                   int64_t ldo, int M, int N, int K, int relu, int split_mode, hipStream_t stream, const float *w16,
+                   const GemmExtra *extra) {
   GemmArgs g;
   g.a = a; g.w = w16 ? w16 : w; g.bias = bias; g.res = res; g.out = out;
   g.M = M; g.N = N; g.K = K; g.lda = (int)lda; g.ldr = (int)ldr; g.ldo = (int)ldo; g.relu = relu;
   const int64_t ea = (int64_t)(M - 1) * lda + K, eo = (int64_t)(M - 1) * ldo + N, er = res ? (int64_t)(M - 1) * ldr + N : 1;
-  const int64_t lim = (int64_t)1 << 30;
+  // Spans of at most 2^30 - 4 elements: no byte count below wraps (2^30 elements = 2^32 bytes = 0 records: every store
+  // dropped), and every valid byte offset lies below the kernel's out-of-range offset OOB = 2^32 - 16.
+  const int64_t lim = ((int64_t)1 << 30) - 4;
+  static_assert((uint64_t)lim * 4 == OOB, "the largest span ends where the out-of-range offset begins");
+  if (lda < K || ldo < N || (res && ldr < N)) return invalid("gemm: a row stride is shorter than the row");
   if (ea > lim || eo > lim || er > lim || (int64_t)N * K > lim) return unsupported("gemm: a tensor spans 4 GiB or more");
   g.a_bytes = (unsigned)(ea * 4); g.w_bytes = (unsigned)((int64_t)N * K * 4); g.out_bytes = (unsigned)(eo * 4);
   g.res_bytes = (unsigned)(er * 4);
@@ -392,8 +428,9 @@ int gemm_split_f32(const float *a, int64_t lda, const float *w, const float *bia
   int nz = 1;
   if (extra) {
     nz = extra->nz;
+    if (!(extra->drop_p >= 0.f)) return invalid("gemm: dropout probability negative or NaN");
     if (extra->drop_p > 0.f) {
-      if (!(extra->drop_p < 1.f) || nz != 1 || eo > ((int64_t)1 << 30)) return unsupported("gemm: dropout needs 0 < p < 1 and a single product");
+      if (!(extra->drop_p < 1.f) || nz != 1) return unsupported("gemm: dropout needs 0 < p < 1 and a single product");
       const double t = (double)extra->drop_p * 4294967296.0;
       g.drop_thresh = t >= 4294967295.0 ? 0xFFFFFFFFu : (t < 1.0 ? 1u : (unsigned)t);
       g.drop_scale = 1.f / (1.f - extra->drop_p);
@@ -418,34 +455,31 @@ int gemm_split_f32(const float *a, int64_t lda, const float *w, const float *bia
     }
   }
   static_assert(BM <= kBandTileMax, "banded launches (win_rpu) run 128-row tiles: what kMargin of the attention backward covers");
-  const int rem = M % BM;
-  if (rem > 0 && rem <= kGemmTailRows && M >= 8 * BM && (lda & 3) == 0) { g.tail = rem; g.M = M - rem; M = g.M; }
-  // 128 x 64 tiles when 128 x 128 ones would leave CUs without a second workgroup
-  const long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128);
-  // (from one workgroup per CU on: M = 8200, N = 512, K = 2048 72 -> 66 us with 128 x 128 tiles, K = 512 the same either way)
-  const int narrow_below = knobs().gemm_narrow_below > 0 ? knobs().gemm_narrow_below : current_device_cu_count();
-  const bool narrow = tiles128 < narrow_below || N % 128 != 0;
-  // 256 x 128 tiles (one workgroup per CU) where they come in whole rounds of the chip: the widest layers (measured at
-  // M = 8200, K = 512, tools/bench_linear.py with ISI_GEMM_NO_WIDE: N = 2048 (two rounds) 79 -> 70 us, N = 1024 (one round)
-  // 42 -> 40 us; N = 1536 (one and a half rounds) 63 -> 70 us: not taken)
-  const long tiles256 = (long)((M + 255) / 256) * ((N + 127) / 128);
-  const long tiles256x256 = (long)((M + 255) / 256) * ((N + 255) / 256);
-  if (!narrow && nz == 1 && !g.win_rpu && N % 256 == 0 && tiles256x256 == current_device_cu_count() && !knobs().gemm_no_wide) {
-    if (split_mode == 3 && w16) return launch_gemm<true, 4, true, 2>(g, stream, nz);
-    if (split_mode == 3) return launch_gemm<true, 4, false, 2>(g, stream, nz);
-    if (w16) return launch_gemm<false, 4, true, 2>(g, stream, nz);
-    return launch_gemm<false, 4, false, 2>(g, stream, nz);
+  const GemmRoute route = gemm_split_route(M, N, (lda & 3) == 0, nz == 1 && !g.win_rpu);
+  if (route.tail) { g.tail = route.tail; g.M = M - route.tail; }
+  const bool f16 = split_mode == 3;
+  switch (route.tile) {
+    case 4:
+      if (f16 && w16) return launch_gemm<true, 4, true, 2>(g, stream, nz);
+      if (f16) return launch_gemm<true, 4, false, 2>(g, stream, nz);
+      if (w16) return launch_gemm<false, 4, true, 2>(g, stream, nz);
+      return launch_gemm<false, 4, false, 2>(g, stream, nz);
+    case 3:
+      if (f16 && w16) return launch_gemm<true, 2, true, 2>(g, stream, nz);
+      if (f16) return launch_gemm<true, 2, false, 2>(g, stream, nz);
+      if (w16) return launch_gemm<false, 2, true, 2>(g, stream, nz);
+      return launch_gemm<false, 2, false, 2>(g, stream, nz);
+    case 2:
+      if (f16 && w16) return launch_gemm<true, 2, true>(g, stream, nz);
+      if (f16) return launch_gemm<true, 2>(g, stream, nz);
+      if (w16) return launch_gemm<false, 2, true>(g, stream, nz);
+      return launch_gemm<false, 2>(g, stream, nz);
+    default:
+      if (f16 && w16) return launch_gemm<true, 1, true>(g, stream, nz);
+      if (f16) return launch_gemm<true, 1>(g, stream, nz);
+      if (w16) return launch_gemm<false, 1, true>(g, stream, nz);
+      return launch_gemm<false, 1>(g, stream, nz);
   }
-  if (!narrow && nz == 1 && !g.win_rpu && tiles256 % current_device_cu_count() == 0 && knobs().gemm_no_wide != 1) {
-    if (split_mode == 3 && w16) return launch_gemm<true, 2, true, 2>(g, stream, nz);
-    if (split_mode == 3) return launch_gemm<true, 2, false, 2>(g, stream, nz);
-    if (w16) return launch_gemm<false, 2, true, 2>(g, stream, nz);
-    return launch_gemm<false, 2, false, 2>(g, stream, nz);
-  }
-  if (split_mode == 3 && w16) return narrow ? launch_gemm<true, 1, true>(g, stream, nz) : launch_gemm<true, 2, true>(g, stream, nz);
-  if (split_mode == 3) return narrow ? launch_gemm<true, 1>(g, stream, nz) : launch_gemm<true, 2>(g, stream, nz);
-  if (w16) return narrow ? launch_gemm<false, 1, true>(g, stream, nz) : launch_gemm<false, 2, true>(g, stream, nz);
-  return narrow ? launch_gemm<false, 1>(g, stream, nz) : launch_gemm<false, 2>(g, stream, nz);
 }
 
 }  // namespace isi

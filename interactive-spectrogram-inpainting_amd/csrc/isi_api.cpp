@@ -227,6 +227,10 @@ int isi_linear_f32(const isi_linear_args *a, void *stream) {
                         ((mode == 3 && (a->flags & ISI_CONV_W16)) || (mode == 1 && (a->flags & ISI_CONV_W16_BF16))) ? a->packed_w + (size_t)a->N * kpad : nullptr,
                         &gx);
 }
+int isi_linear_route(int M, int N, int K, int flags) {
+  const int mode = (flags & ISI_CONV_BF16X6) ? 2 : (flags & ISI_CONV_F16X3) ? 3 : (flags & ISI_CONV_BF16X3) ? 1 : 0;
+  return gemm_split_linear_route(M, N, K, mode);
+}
 int isi_conv_transpose2d_k4s2_gated_f32(const isi_src *src, const float *packed_w, const float *bias,
                                         const float *gate, const isi_dst *dst, int B, int H, int W, int Cout,
                                         int flags, void *stream) {

@@ -204,6 +204,10 @@ int prior_sample_run_rows(const isi_prior_w *w, const isi_prior_state *s, const 
                           const isi_prior_code_bias *bias = nullptr);
 
 bool gemm_split_applicable(int M, int N, int K, int split_mode);
+// tile: 1 = 128 x 64, 2 = 128 x 128, 3 = 256 x 128, 4 = 256 x 256; tail: the last rows, left to fp32 dot products
+struct GemmRoute { int tile, tail; };
+GemmRoute gemm_split_route(int M, int N, bool rows4, bool plain);
+int gemm_split_linear_route(int M, int N, int K, int split_mode);   // isi_linear_route
 // Optional extras of gemm_split_f32: a batch of nz independent products (grid y; element strides between them) and a
 // band of the K range per 128-row tile -- rows [u win_rpu, (u + 1) win_rpu) only have non-zero A columns in
 // [lo_slope u + lo_base, hi_slope u + hi_base] (slopes >= 0), the K chunks outside the tile's band are skipped
@@ -232,8 +236,10 @@ __host__ __device__ inline bool dropout_keep(uint64_t seed, uint32_t idx, uint32
   uint32_t h = idx;
   h ^= h >> 16; h *= 0x7FEB352Du;
   h ^= (uint32_t)seed;                  // (behind the first round: seeds that differ in a low bit must not just swap neighbours)
-  h ^= h >> 15; h *= 0x846CA68Bu;
-  h ^= (uint32_t)(seed >> 32);
+  // (the high word in FRONT of the second multiply, which carries its bits upward: folded in behind it, a bit of it reached
+  // the hash's same bit and the one 16 below only, and `h >= thresh` reads the top bits -- seeds that differed in bits
+  // 32 .. 61 alone drew the same mask, tests/test_linear_gemm_host.py::test_dropout_keep_mask)
+  h ^= h >> 15; h ^= (uint32_t)(seed >> 32); h *= 0x846CA68Bu;
   h ^= h >> 16;
   return h >= thresh;
 }

@@ -334,7 +334,11 @@ def row_error(got, ref):
     """The metric of compare_rows.  A tensor with rows (two or more dimensions; rows = the last dimension): the largest
     over rows of max|err_row| / max|ref_row|, the scale clamped from below at 2^-100 (an all-zero reference row).  A
     vector: max|err| / max|ref|.  A non-finite value anywhere in `got` gives inf."""
-    got, ref = _f64(got), _f64(ref)
+    ref = torch.as_tensor(ref).detach()
+    if ref.is_cuda:                                       # (a reference kept on a device is compared there: 16 M outputs)
+        got, ref = torch.as_tensor(got).detach().to(ref.device).double(), ref.double()
+    else:
+        got, ref = _f64(got), _f64(ref)
     assert got.shape == ref.shape, f"shape {tuple(got.shape)} against {tuple(ref.shape)}"
     if not bool(torch.isfinite(got).all()):
         return float("inf")
@@ -926,3 +930,279 @@ def wgrad_case_refs(c):
 def rows2d(t):
     """A weight gradient as [rows, -1] (a row = one output channel's gradient); vectors stay vectors."""
     return t.reshape(t.shape[0], -1) if t.dim() > 1 else t
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Float64 specification, float32 yardstick and split-product models of the linear layers' GEMM (csrc/gemm_split_f32.hip,
+# through isi_linear_f32), in the style of the blocks above: plain torch, no autograd and none of the project's kernels.
+#     v = x W^T + bias + res;  ReLU;  gate > 0 ? v * gate_scale : 0;  keep ? v / (1 - p) : 0          (the epilogue's order)
+# with W [N, K] in torch's layout, `gate_scale` and `p` the float32 values the C-ABI receives, and `keep` the mask of
+# `dropout_keep_mask`.  Everything here computes on the device its operands live on (the CPU, except for the two shapes of
+# 8 M and 16 M outputs that tests/test_linear_gemm_gpu.py needs to reach the 256-row tiles: torch's matmuls, not the
+# project's).  tests/test_linear_gemm_host.py holds the spec to float64 autograd and shows what `linear_hold` rejects;
+# tests/test_linear_gemm_gpu.py holds the kernels to it on every tile route.
+LINEAR_TAIL_ROWS = 16          # kGemmTailRows: M % 128 up to this many rows (of M >= 1024) are fp32 dot products, no tile row
+LINEAR_TILES = {1: "128x64", 2: "128x128", 3: "256x128", 4: "256x256"}
+
+
+def linear_route(M, N, K, cus, narrow_below=0, no_wide=0):
+    """Mirror of gemm_split_route / isi_linear_route (csrc/gemm_split_f32.hip) for a device of `cus` compute units and the
+    knobs ISI_GEMM_NARROW_BELOW / ISI_GEMM_NO_WIDE: 0 = outside the GEMM kernel, else tile | tail_rows << 8 (LINEAR_TILES)."""
+    if K % 32 or K < 128 or N <= 32 or M < 256:
+        return 0
+    tail, rem = 0, M % 128
+    if 0 < rem <= LINEAR_TAIL_ROWS and M >= 8 * 128:
+        tail, M = rem, M - rem
+    cdiv = lambda a, b: (a + b - 1) // b
+    narrow = cdiv(M, 128) * cdiv(N, 128) < (narrow_below if narrow_below > 0 else cus) or N % 128 != 0
+    if narrow:
+        tile = 1
+    elif N % 256 == 0 and cdiv(M, 256) * cdiv(N, 256) == cus and not no_wide:
+        tile = 4
+    elif (cdiv(M, 256) * cdiv(N, 128)) % cus == 0 and no_wide != 1:
+        tile = 3
+    else:
+        tile = 2
+    return tile | tail << 8
+
+
+def dropout_thresh(p):
+    """The 32-bit threshold of gemm_split_f32: (double)(float)p * 2^32, truncated, clamped to [1, 0xFFFFFFFF]."""
+    t = float(np.float32(p)) * 4294967296.0
+    return 0xFFFFFFFF if t >= 4294967295.0 else 1 if t < 1.0 else int(t)
+
+
+def dropout_keep_mask(seed, M, N, ldo, p, high_word=True):
+    """Integer replica of `dropout_keep` (csrc/isi_internal.h) over an [M, N] output of row stride ldo, as a bool tensor: the
+    lowbias32 mixer over idx = m ldo + n (32 bits), the seed's low word folded in after round one and the high word inside
+    round two, in front of its multiply; keep iff h >= thresh.  `high_word` = False is a host-test mutant (the seed's high word ignored)."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    idx = np.arange(M, dtype=np.uint64)[:, None] * np.uint64(ldo) + np.arange(N, dtype=np.uint64)[None, :]
+    h = (idx & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    h ^= h >> np.uint32(16)
+    h *= np.uint32(0x7FEB352D)
+    h ^= np.uint32(seed & 0xFFFFFFFF)
+    h ^= h >> np.uint32(15)
+    if high_word:
+        h ^= np.uint32(seed >> 32)
+    h *= np.uint32(0x846CA68B)
+    h ^= h >> np.uint32(16)
+    return torch.from_numpy(h >= np.uint32(dropout_thresh(p)))
+
+
+def _linear_epilogue(v, bias, res, relu, gate, gate_scale, keep, p, gate_ge=False, gate_unscaled=False,
+                     keep_unscaled=False):
+    """The epilogue in v's dtype on v's device; returns (out, lin, live): `lin` the value without the ReLU (scaled like
+    `out`), `live` where neither the gate nor the mask forces a zero (None: everywhere)."""
+    to = lambda t: torch.as_tensor(t).detach().to(device=v.device, dtype=v.dtype)
+    if bias is not None:
+        v = v + to(bias)
+    if res is not None:
+        v = v + to(res)
+    lin, live = v, None
+    if gate is not None:
+        gs = torch.tensor(1.0 if gate_unscaled else float(np.float32(gate_scale)), dtype=v.dtype, device=v.device)
+        g = torch.as_tensor(gate).detach().to(v.device)
+        live = (g >= 0) if gate_ge else (g > 0)
+        lin = lin * gs
+    if keep is not None:
+        k = torch.as_tensor(keep).to(v.device)
+        live = k if live is None else live & k
+        if not keep_unscaled:
+            lin = lin / (1.0 - torch.tensor(float(np.float32(p)), dtype=v.dtype, device=v.device))
+    out = lin.clamp(min=0.0) if relu else lin
+    if live is not None:
+        out = torch.where(live, out, torch.zeros_like(out))
+    return out, lin, live
+
+
+def linear_spec(x, W, bias, res, relu, gate=None, gate_scale=1.0, keep=None, p=0.0, prod=None, parts=False):
+    """Float64 closed form of isi_linear_f32.  `prod`: the float64 product x W^T where the caller has it already (one per
+    case, every epilogue on top of it); `parts`: return (out, lin, live) of _linear_epilogue, not out alone."""
+    if prod is None:
+        prod = torch.as_tensor(x).detach().double() @ torch.as_tensor(W).detach().double().t()
+    r = _linear_epilogue(prod.double(), bias, res, relu, gate, gate_scale, keep, p)
+    return r if parts else r[0]
+
+
+def linear_f32(x, W, bias, res, relu, gate=None, gate_scale=1.0, keep=None, p=0.0, prod=None, skip_last_chunk=False,
+               repeat_chunk=False, x_dense=None, res_dense=None, tail_bf16=False, **epilogue_mutants):
+    """The same in float32 torch: the yardstick of the tail rows, half of the tile rows', and what the host tests apply
+    their mutants to.  `prod`: the float32 product where the caller has it.  Mutants: `skip_last_chunk`, the last 32 k
+    left out; `repeat_chunk`, the next-to-last 32 k of both operands in place of the last; `x_dense` = (flat buffer, first
+    element): rows of x read at stride K from there, not at their stride; `res_dense` likewise for the residual at stride N;
+    `tail_bf16`, single-term bf16 products (operands rounded to bf16); gate_ge / gate_unscaled / keep_unscaled: the epilogue's."""
+    if prod is None:
+        xf, Wf = torch.as_tensor(x).detach().float(), torch.as_tensor(W).detach().float()
+        M, K = xf.shape
+        if x_dense is not None:
+            buf, first = x_dense
+            xf = buf.reshape(-1)[first:first + M * K].reshape(M, K).float()
+        if tail_bf16:
+            xf, Wf = xf.bfloat16().float(), Wf.bfloat16().float()
+        if skip_last_chunk:
+            xf, Wf = xf[:, :K - 32], Wf[:, :K - 32]
+        elif repeat_chunk:
+            xf = torch.cat([xf[:, :K - 32], xf[:, K - 64:K - 32]], dim=1)
+            Wf = torch.cat([Wf[:, :K - 32], Wf[:, K - 64:K - 32]], dim=1)
+        prod = xf @ Wf.t()
+    if res_dense is not None:
+        buf, first = res_dense
+        res = buf.reshape(-1)[first:first + prod.numel()].reshape(prod.shape)
+    return _linear_epilogue(prod.float(), bias, res, relu, gate, gate_scale, keep, p, **epilogue_mutants)[0]
+
+
+def f16_pieces(v, scale):
+    """The split of csrc/split_f16.h on a float32 tensor, as float64 tensors: hi = f16(s v), lo = f16(s v - hi) (the product
+    by the power of two s and the subtraction are exact in float32)."""
+    sv = v.float() * scale
+    hi = sv.half().float()
+    return hi.double(), (sv - hi).half().double()
+
+
+def linear_split_model(x, W, mode, drop=None):
+    """Float64 evaluation of the three terms gemm_split_kernel keeps of x W^T -- mfma(al, bh); mfma(ah, bl); mfma(ah, bh):
+    lo.hi + hi.lo + hi.hi -- with the pieces of its product mode: "bf16" (ISI_CONV_BF16X3): bf16_pieces(v, 2) of both
+    operands; "f16" (ISI_CONV_F16X3): f16_pieces of 4 x and 1024 W, the sum divided by 4096.  Its distance from the exact
+    product is the truncation the mode accepts by design.  `drop` ("hi_lo" or "lo_hi": x piece, W piece) is a host-test
+    mutant: that cross term is left out."""
+    x, W = torch.as_tensor(x).detach(), torch.as_tensor(W).detach()
+    if mode == "bf16":
+        (xh, xl), (wh, wl), unscale = bf16_pieces(x, 2), bf16_pieces(W, 2), 1.0
+    else:
+        assert mode == "f16", mode
+        (xh, xl), (wh, wl), unscale = f16_pieces(x, 4.0), f16_pieces(W, 1024.0), 1.0 / 4096.0
+    s = xh @ wh.t()
+    if drop != "hi_lo":
+        s = s + xh @ wl.t()
+    if drop != "lo_hi":
+        s = s + xl @ wh.t()
+    assert drop in (None, "hi_lo", "lo_hi"), drop
+    return s * unscale
+
+
+def _larger_error_on(a, b, ref):
+    """larger_error on the device of ref."""
+    a, b = a.to(ref.device).double(), b.to(ref.device).double()
+    return torch.where((a - ref).abs() >= (b - ref).abs(), a, b)
+
+
+LinearExpect = collections.namedtuple("LinearExpect", "spec lin live yard relu tail")
+
+
+def linear_expect(prod64, prod32, model, tail, bias, res, relu, gate=None, gate_scale=1.0, keep=None, p=0.0):
+    """What one launch is held to: the spec on top of the float64 product, and the yardstick -- for the tile rows (all but
+    the last `tail`) per element the worse of the float32 evaluation and the mode's three-term model, for the tail rows
+    (plain fp32 dot products in the kernel) the float32 evaluation alone -- every one with the same epilogue."""
+    e = (bias, res, relu, gate, gate_scale, keep, p)
+    spec, lin, live = linear_spec(None, None, *e, prod=prod64, parts=True)
+    f32 = linear_f32(None, None, *e, prod=prod32)
+    yard = _larger_error_on(f32, _linear_epilogue(model.double(), *e)[0], spec)
+    if tail:
+        yard[-tail:] = f32[-tail:].to(yard.device).double()
+    return LinearExpect(spec, lin, live, yard, bool(relu), tail)
+
+
+def linear_hold(got, exp, what, margin=ROW_OPS_MARGIN):
+    """The comparison of the linear-GEMM tests, tile rows and tail rows as blocks of their own.  Per block:
+      * zeros: an element the gate or the mask removes is 0 exactly; with the ReLU, so is one whose float64 value lies more
+        than `tol` below 0; every other element further than `tol` from 0 is not 0 -- tol = what compare_rows allows that
+        row, margin x yardstick error x the row's largest |spec| (an element nearer 0 than the kernel may be wrong by can
+        fall on either side of a ReLU);
+      * values: compare_rows over the whole block, zeros included.
+    Returns the RowChecks; raises AssertionError at the first failure."""
+    M = exp.spec.shape[0]
+    got = torch.as_tensor(got).detach().to(exp.spec.device)
+    assert got.shape == exp.spec.shape, f"{what}: shape {tuple(got.shape)} against {tuple(exp.spec.shape)}"
+    checks = []
+    for name, rows in (("tile rows", slice(0, M - exp.tail)), ("tail rows", slice(M - exp.tail, M))):
+        if rows.start == rows.stop:
+            continue
+        g, spec, lin, yard = got[rows], exp.spec[rows], exp.lin[rows], exp.yard[rows]
+        live = torch.ones_like(spec, dtype=torch.bool) if exp.live is None else exp.live[rows]
+        yerr = max(row_error(yard, spec), ROW_OPS_FLOOR)
+        tol = margin * yerr * spec.abs().amax(dim=-1, keepdim=True).clamp(min=2.0 ** -100)
+        must_zero = ~live | (lin < -tol if exp.relu else torch.zeros_like(live))
+        must_not = live & ((lin > tol) if exp.relu else (lin.abs() > tol))
+        bad0, bad1 = int((g[must_zero] != 0).sum()), int((g[must_not] == 0).sum())
+        assert bad0 == 0, f"{what} {name}: {bad0} of {int(must_zero.sum())} elements the spec zeroes are not 0"
+        assert bad1 == 0, f"{what} {name}: {bad1} of {int(must_not.sum())} elements the spec keeps are 0"
+        checks.append(compare_rows(g, spec, yard, f"{what} {name}", margin))
+    return checks
+
+
+def linear_case_data(M, N, K, seed=None):
+    """(x [M, K], W [N, K] = randn / sqrt(K), bias [N], res [M, N], gate [M, N]) float32 on the CPU, seeded by the shape; the
+    gate is `gate_data`'s y: randn with +0.0, -0.0, 2^-126 and negatives at the head, at the tail and throughout."""
+    g = torch.Generator().manual_seed((M * 131 + N) * 131 + K if seed is None else seed)
+    x = torch.randn(M, K, generator=g)
+    W = torch.randn(N, K, generator=g) / K ** 0.5
+    bias = torch.randn(N, generator=g)
+    res = torch.randn(M, N, generator=g)
+    gate = gate_data(M * N, g)[1].reshape(M, N)
+    return x, W, bias, res, gate
+
+
+LinearCase = collections.namedtuple("LinearCase", "M N K tile tail knobs")      # knobs: ((name, value), ...)
+LINEAR_DROP_P = 0.25
+LINEAR_SEEDS = ((0x9E3779B9 << 32) | 0x7F4A7C15, (0x0000002A << 32) | 0x7F4A7C15)     # above 2^32; they share the low word
+LINEAR_EPILOGUES = ("bias", "bias+res+relu", "gate", "relu+dropout", "all")
+
+
+def linear_cases(cus):
+    """The cases of tests/test_linear_gemm_gpu.py for a device of `cus` compute units (the routes in the comments: 256), as
+    (small, wide): below 1 M outputs every epilogue of LINEAR_EPILOGUES runs, at the wide shapes -- the smallest that reach the
+    256-row tiles, which want a whole round of the chip -- the first and the last."""
+    nb = (("ISI_GEMM_NARROW_BELOW", 1),)
+    small = [
+        # 128 x 64, default knobs: ragged N below one tile, one row past a tile, K of 4 and of 5 chunks (both parities of the
+        # two-stage ring, the peeled last chunk)
+        LinearCase(256, 40, 128, 1, 0, ()), LinearCase(257, 72, 160, 1, 0, ()), LinearCase(300, 200, 128, 1, 0, ()),
+        # ... with tail rows: 6, the most (16), and one more (17 rows take a tile of their own)
+        LinearCase(1030, 192, 128, 1, 6, ()), LinearCase(1040, 64, 128, 1, 16, ()), LinearCase(1041, 64, 128, 1, 0, ()),
+        # 128 x 128
+        LinearCase(256, 128, 128, 2, 0, nb), LinearCase(385, 256, 160, 2, 0, nb), LinearCase(1027, 128, 128, 2, 3, nb),
+    ]
+    wide = [
+        # 256 x 128: whole tiles; a ragged last tile; 5 tail rows and a half-empty last 256-row tile
+        LinearCase(64 * cus, 512, 128, 3, 0, ()), LinearCase(64 * cus - 100, 512, 128, 3, 0, ()),
+        LinearCase(64 * cus - 123, 512, 160, 3, 5, ()),
+        # 256 x 256
+        LinearCase(128 * cus, 512, 128, 4, 0, ()), LinearCase(128 * cus - 100, 512, 128, 4, 0, ()),
+        LinearCase(128 * cus - 125, 512, 160, 4, 3, ()),
+        # the same rows on the narrower tiles: bit-identical tile rows
+        LinearCase(128 * cus, 512, 128, 3, 0, (("ISI_GEMM_NO_WIDE", 2),)), LinearCase(128 * cus, 512, 128, 2, 0, (("ISI_GEMM_NO_WIDE", 1),)),
+    ]
+    return small, wide
+
+
+def linear_epilogue_args(which, M, N, ldo, bias, res, gate, seed=LINEAR_SEEDS[0], keep=None):
+    """(bias, res, relu, gate, gate_scale, keep, p) of one of LINEAR_EPILOGUES: the arguments of linear_spec behind x and W.
+    The mask is that of an output of row stride ldo (`keep`: a mask the caller computed already)."""
+    p = LINEAR_DROP_P
+    gs = 1.0 / (1.0 - p)
+    mask = lambda: dropout_keep_mask(seed, M, N, ldo, p) if keep is None else keep
+    return {"bias": lambda: (bias, None, False, None, 1.0, None, 0.0),
+            "bias+res+relu": lambda: (bias, res, True, None, 1.0, None, 0.0),
+            "gate": lambda: (bias, None, False, gate, gs, None, 0.0),
+            "relu+dropout": lambda: (bias, None, True, None, 1.0, mask(), p),
+            "all": lambda: (bias, res, True, gate, gs, mask(), p)}[which]()
+
+
+LinearRefs = collections.namedtuple("LinearRefs", "x W bias res gate prod64 prod32 model")
+_linear_refs_cache = {}
+
+
+def linear_refs(M, N, K, device="cpu"):
+    """The data of a shape (linear_case_data), its float64 and float32 products and the two modes' three-term models, on
+    `device` (uncached; the wide shapes of the GPU test: torch's own matmuls there, 0.5 GB of references each)."""
+    x, W, bias, res, gate = (t.to(device) for t in linear_case_data(M, N, K))
+    model = {m: linear_split_model(x, W, m) for m in ("bf16", "f16")}
+    return LinearRefs(x, W, bias, res, gate, x.double() @ W.double().t(), x @ W.t(), model)
+
+
+def linear_case_refs(M, N, K):
+    """linear_refs on the CPU, computed once per process and left unchanged: every shape below 1 M outputs."""
+    if (M, N, K) not in _linear_refs_cache:
+        _linear_refs_cache[(M, N, K)] = linear_refs(M, N, K)
+    return _linear_refs_cache[(M, N, K)]

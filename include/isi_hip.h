@@ -125,6 +125,38 @@ int64_t isi_resample_out_len(int64_t L, int orig, int new_);
 int isi_resample_f32(const float *x, int64_t x_stride, float *y, int64_t y_stride, int B, int64_t L,
                      int orig, int new_, int width, const float *table, void *stream);
 
+/* ------------------------------------------------ pitch of an uploaded sound */
+/* Both priors are conditioned on the pitch; for an upload nobody knows it.  YIN (de Cheveigne & Kawahara 2002) on
+ * the sound brought to 48 kHz (specification tests/pitch_spec.py).  With T =
+ * (L - W - tau_max) / hop + 1 frames, frame t starting at s = t * hop:
+ *   d[b][t][tau] = sum_{j < W} (x[b][s + j] - x[b][s + j + tau])^2, tau = 0 .. tau_max;  e[b][t] = sum_{j < W} x[b][s + j]^2
+ *   cs(tau) = sum_{k = 1 .. tau} d(k), d'(0) = 1, d'(tau) = d(tau) * tau / cs(tau), 1 where cs = 0
+ *   tau* = the smallest tau in [tau_min, tau_max) with d'(tau) < threshold, then tau -> tau + 1 while tau + 1 < tau_max
+ *          and d'(tau + 1) < d'(tau); with no lag under the threshold the argmin of d' over [tau_min, tau_max), the
+ *          lowest tau on ties
+ *   period = tau* + (a - c) / (2 v), a, b, c = d(tau* - 1), d(tau*), d(tau* + 1), v = a - 2 b + c, if v > 0, else tau*
+ *   aperiodicity = d'(tau*)
+ * isi_pitch_frames (host only): T, or ISI_E_INVALID for W <= 0, hop <= 0, tau_max < 0 or L < W + tau_max.
+ * isi_pitch_difference_f32: x[b, 0:L], rows x_stride floats apart, any float-aligned base -> d [B][T][tau_max + 1] and
+ * energy [B][T], dense fp32.  The direct form, not E_a + E_tau - 2 corr: every term is one subtraction rounded to fp32
+ * and one fp32 fma into the lag's sum, j ascending, so d is relatively accurate at the dip, where it is orders below
+ * the frame energy: |d - d64| <= (W + 4) 2^-24 d64 against the float64 sum over the same fp32 samples.  The bits of
+ * d[b][t][tau] and energy[b][t] depend on that frame's samples, W and tau alone -- not on B, L, t, the alignment or the
+ * launch.  Checked before any launch: null pointers, B / L / W / hop <= 0, tau_max < 3, L < W + tau_max, a stride
+ * shorter than the row, a pointer not aligned to a float (ISI_E_INVALID); W + tau_max > 15360 -- one frame's samples
+ * are staged in LDS --, L >= 2^31, 2^31 workgroups (ISI_E_UNSUPPORTED).
+ * isi_pitch_pick_f32: d [n_frames][tau_max + 1] -> period [n_frames] (in samples), aperiodicity [n_frames].  The
+ * cumulative sum is an fp32 prefix sum: the choice equals the float64 one wherever every comparison it makes has a
+ * relative gap above (tau_max + 2) 2^-24.  Checked before any launch: null pointers, n_frames <= 0, tau_min < 1,
+ * tau_max < tau_min + 2, a threshold that is NaN or outside (0, 1] (ISI_E_INVALID); tau_max >= 15360, n_frames >= 2^31
+ * (ISI_E_UNSUPPORTED).
+ * Both: no atomics, no allocation, no host synchronisation; stream-ordered. */
+int64_t isi_pitch_frames(int64_t L, int W, int hop, int tau_max);
+int isi_pitch_difference_f32(const float *x, int64_t x_stride, float *d, float *energy, int B, int64_t L, int W,
+                             int hop, int tau_max, void *stream);
+int isi_pitch_pick_f32(const float *d, int64_t n_frames, int tau_min, int tau_max, float threshold, float *period,
+                       float *aperiodicity, void *stream);
+
 /* ------------------------------------------------ query-by-example search of a code database */
 /* "The stored sounds most like this one": weighted code-distance sums of Q query codemaps against N stored ones
  * (specification tests/code_search_spec.py).  For one layer with codebook E [K, D]:

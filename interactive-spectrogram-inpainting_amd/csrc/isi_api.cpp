@@ -315,6 +315,15 @@ int isi_resample_f32(const float *x, int64_t x_stride, float *y, int64_t y_strid
                      int width, const float *table, void *stream) {
   return resample_f32(x, x_stride, y, y_stride, B, L, orig, new_, width, table, S(stream));
 }
+int64_t isi_pitch_frames(int64_t L, int W, int hop, int tau_max) { return pitch_frames(L, W, hop, tau_max); }
+int isi_pitch_difference_f32(const float *x, int64_t x_stride, float *d, float *energy, int B, int64_t L, int W, int hop,
+                             int tau_max, void *stream) {
+  return pitch_difference_f32(x, x_stride, d, energy, B, L, W, hop, tau_max, S(stream));
+}
+int isi_pitch_pick_f32(const float *d, int64_t n_frames, int tau_min, int tau_max, float threshold, float *period,
+                       float *aperiodicity, void *stream) {
+  return pitch_pick_f32(d, n_frames, tau_min, tau_max, threshold, period, aperiodicity, S(stream));
+}
 int isi_code_distance_table_f32(const float *codebook, float *table, int K, int D, void *stream) {
   return code_distance_table_f32(codebook, table, K, D, S(stream));
 }

@@ -343,6 +343,12 @@ int resample_geometry(int fs_in, int fs_out, int *orig, int *new_, int *width, i
 int64_t resample_out_len(int64_t L, int orig, int new_);
 int resample_f32(const float *x, int64_t x_stride, float *y, int64_t y_stride, int B, int64_t L, int orig, int new_,
                  int width, const float *table, hipStream_t st);
+// pitch.hip
+int64_t pitch_frames(int64_t L, int W, int hop, int tau_max);
+int pitch_difference_f32(const float *x, int64_t x_stride, float *d, float *energy, int B, int64_t L, int W, int hop,
+                         int tau_max, hipStream_t st);
+int pitch_pick_f32(const float *d, int64_t n_frames, int tau_min, int tau_max, float threshold, float *period,
+                   float *aperiodicity, hipStream_t st);
 // code_search.hip
 int code_distance_table_f32(const float *codebook, float *table, int K, int D, hipStream_t st);
 size_t code_search_workspace_bytes(int64_t N, int64_t C, int K, int Q);

@@ -11,6 +11,8 @@ query arguments and JSON schema for the operations built on MI355X
   POST /analyze-audio?pitch=&instrument_family_str=   multipart file `audio` (RIFF / PCM 16-bit or float32, mono or
        averaged to mono, at any sampling rate the resampler takes -- 44.1 and 48 kHz recordings are converted to
        the models' rate on the GPU, GANsynth_pytorch/resample.py; read with the standard library)  (:557-568,624-667)
+       without `pitch`, or with `pitch=auto` (not in the reference): the pitch is estimated from the sound on the GPU
+       (GANsynth_pytorch/pitch.py) and fills the conditioning maps; 400 when the sound has none (noise, silence)
   POST /top-conditioned-sample?instrument_family_str=&min_pitch=&max_pitch=&temperature=&top_p=&top_k=
        body {top_code, bottom_code} -> application/zip of `{family}-{pitch}.wav`, one per pitch             (:1049-1115)
   GET/POST /sample-from-dataset?duration_top=&pitch=&pitch_class=&octave=&instrument_family_str=
@@ -161,6 +163,14 @@ def create_app(vqvae, transformer_top, transformer_bottom, label_encoders_per_mo
         res_n = inpainting.top_resolution_n(vqvae, transformer_top, transformer_bottom, spectrograms_helper, device)
         duration_n = inpainting.adapt_duration(audio.numel(), spectrograms_helper.fs_hz, max_sound_duration_s, res_n,
                                                transformer_top.shape[1])
+        if args.get('pitch') in (None, 'auto'):
+            # nobody knows the pitch of an upload: estimated from the samples about to be encoded (GANsynth_pytorch/pitch.py)
+            encoder = label_encoders_per_modality['pitch']
+            values['pitch'], _ = inpainting.estimate_pitch(
+                audio[:duration_n].to(device), spectrograms_helper,
+                pitch_range=getattr(encoder, 'classes_', getattr(encoder, 'classes', None)))
+            if values['pitch'] is None:
+                flask.abort(400, description="no pitch found in the sound (noise or silence): give the `pitch` argument")
         top_code, bottom_code = inpainting.analyze_audio(vqvae, spectrograms_helper, audio, duration_n, device)
         return respond(top_code, bottom_code, {k: matrix(transformer_top.shape, v) for k, v in values.items()},
                        {k: matrix(transformer_bottom.shape, v) for k, v in values.items()})

@@ -558,6 +558,26 @@ def analyze_audio(vqvae, spectrograms_helper, audio: torch.Tensor, duration_n: i
     return top_code, bottom_code
 
 
+@torch.no_grad()
+def estimate_pitch(audio: torch.Tensor, spectrograms_helper, fs_hz: Optional[int] = None, pitch_range=None):
+    """The `pitch` conditioning of a sound whose pitch nobody knows (an upload): (MIDI number or None, confidence).
+    Mono audio [samples] on the GPU at `fs_hz` (default: the models' rate); the estimate of
+    `GANsynth_pytorch.pitch.estimate_pitch` rounded to the nearest MIDI number and clamped to `pitch_range`, the values
+    the priors were trained with (callers pass the pitch label encoder's classes).  None when no frame is voiced
+    (noise, silence); the confidence is the voiced share of the frames."""
+    from GANsynth_pytorch.pitch import estimate_pitch as estimate
+    rate = int(spectrograms_helper.fs_hz if fs_hz is None else fs_hz)
+    midi, confidence = estimate(audio.to(torch.float32).reshape(-1), rate)
+    midi, confidence = float(midi), float(confidence)
+    if midi != midi:
+        return None, confidence
+    pitch = int(math.floor(midi + 0.5))
+    if pitch_range is not None:
+        values = [int(v) for v in pitch_range]
+        pitch = min(max(pitch, min(values)), max(values))
+    return pitch, confidence
+
+
 def resize_codemaps_repeat_last(top_code: torch.Tensor, bottom_code: torch.Tensor, duration_top: int):
     """flask_server.py:314-330: cut to `duration_top` columns of the top map (and the matching number of the bottom map);
     a shorter map is continued with its last column."""

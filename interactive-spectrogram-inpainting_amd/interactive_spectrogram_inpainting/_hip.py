@@ -237,6 +237,9 @@ SIGNATURES = {
     "isi_resample_geometry": (C.c_int, [C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4),
     "isi_resample_out_len": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
     "isi_resample_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "isi_pitch_frames": (C.c_int64, [C.c_int64, C.c_int, C.c_int, C.c_int]),
+    "isi_pitch_difference_f32": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _P]),
+    "isi_pitch_pick_f32": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_float, _P, _P, _P]),
     "isi_code_distance_table_f32": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "isi_code_search_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int]),
     "isi_code_search_f32": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P]),

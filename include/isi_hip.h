@@ -231,7 +231,8 @@ int isi_code_shift_best_f32(const float *dist, const uint8_t *allowed, float *be
 /* Execution switches (A/B comparisons in tests, measurements): each is read from the environment variable of the
  * same name once, at first use of the library; isi_knob_set changes it afterwards (process-wide, not thread-safe
  * against concurrent launches).  Names: ISI_CONV_FLUSH (accumulator flush period of the LDS-DMA convolution, default
- * 3, 0 = never), ISI_NO_PAIRS, ISI_NO_CONV_FIRST, ISI_NO_VQ_FUSION, ISI_NO_CONV_PAIR_KERNEL,
+ * 3, 0 = never), ISI_NO_PAIRS, ISI_NO_CONV_FIRST, ISI_NO_VQ_FUSION, ISI_NO_CODE_TABLES (dec_t's first convolution and
+ * upsample[0] as matrix work even where isi_vqvae_w carries their code tables), ISI_NO_CONV_PAIR_KERNEL,
  * ISI_NO_RESBLOCK_PAIR_KERNEL, ISI_NO_CONVT_PAIR_KERNEL, ISI_NO_TAIL_FUSION, ISI_NO_WGRAD_HALO (per-tap weight-gradient
  * kernel instead of the halo-staged one), ISI_NO_GEMM_KERNEL (linear layers and their weight gradients on the 1x1
  * convolution kernels instead of the GEMM kernels), ISI_CONV_PAIR_BM, ISI_CONV_PAIR_ALL,
@@ -1048,6 +1049,31 @@ int isi_vq_pack_fragments_f32(const float *packed_w16, float *frag_out, int Kpad
  * instead of by every workgroup of every launch (isi_codebook_w.planes).  D = 64. */
 size_t isi_vq_planes_bytes(int K);
 int isi_vq_pack_planes_f32(const float *codes_kd, const float *e2, void *planes_out, int D, int K, void *stream);
+/* Code tables: the two layers of the forward that read nothing but the quantised TOP map -- dec_t's first 3x3 convolution
+ * (encoder_decoder.py:138 through vqvae.py:265) and upsample_top_to_bottom[0] (ConvTranspose2d k4 s2 p1, vqvae.py:193-201,281)
+ * -- are linear in it, and each of its pixels is one of the K codebook rows: the per-pixel products W[tap] . E[id] are
+ * made once per version of the codebook and of the weight, and the layers become sums of gathered rows.
+ *   which = 0: T3 [tap = kh*3 + kw][K][Cout3],   T3[t][k][n]     = sum_c W3[n][t*D + c]      E[k][c]
+ *   which = 1: TU [phase = py*2 + px][tap = ty*2 + tx][K][CoutU], TU[ph][t][k][n] = sum_c Wph[ph][n][t*D + c] E[k][c]
+ * w3_packed / wT_packed: the fp32 sections of isi_pack_conv_weight_f32 ([Cout3][D][3][3]) / isi_pack_convT_k4s2_weight_f32
+ * ([D][CoutU][4][4], phase-matrix layout); codes_kd [K][D].  Every entry is accumulated in double and rounded to fp32
+ * once.  Behind its last block a table carries one pad row of Cout floats of -0.0, which a tap outside the map gathers
+ * (adding -0.0 changes no bit).  isi_vq_code_tables_bytes: size of one table with its pad row (0 for a bad argument); the
+ * gather needs (16 K + 1) Cout < 2^30.  isi_vq_pack_code_tables_f32: one launch per
+ * table given (either output may be NULL), no allocation, no synchronisation; tables 16-byte aligned, Cout multiples of 4.
+ * isi_vq_code_gather_f32: ONE launch that writes, from ids [B, H, W] (int64, low word read),
+ *   out3[b,y,x,:]        = [relu3]( bias3 + sum_{taps inside the map} T3[tap][ids[b, y+kh-1, x+kw-1]] )       [B, H, W, C3]
+ *   outU[b,2y+py,2x+px,:] = [reluU]( biasU + sum_{taps inside the map} TU[ph][t][ids[b, y-1+py+ty, x-1+px+tx]] ) [B, 2H, 2W, CU]
+ * dense channels-last, fp32 or (out*_pair != 0, C % 8 == 0) in the pair format of ISI_CONV_OUT_PAIR.  Either half may be
+ * left out (NULL table).  Taps are added in ascending tap order after the bias and a tap outside the map adds nothing: an
+ * output pixel's bits depend on its window's codes alone.  A code outside [0, K) -- the search's -1 -- is never used as
+ * an address: every output pixel whose window contains it is written as NaN.  The ReLU propagates NaN. */
+size_t isi_vq_code_tables_bytes(int which, int K, int Cout);
+int isi_vq_pack_code_tables_f32(const float *w3_packed, int Cout3, const float *wT_packed, int CoutU, const float *codes_kd, int D,
+                                int K, float *t3_out, float *tu_out, void *stream);
+int isi_vq_code_gather_f32(const int64_t *ids, const float *t3, const float *bias3, float *out3, int C3, int out3_pair, int relu3,
+                           const float *tu, const float *biasU, float *outU, int CU, int outU_pair, int reluU, int B, int H, int W,
+                           int K, void *stream);
 /* 1 when the fused launch covers the shape (D = 64, 32-channel multiples, C0 + C1 <= 256, both code planes in LDS) */
 int isi_vq_conv1x1_fusable(int C0, int C1, int D, int K);
 
@@ -1120,6 +1146,9 @@ typedef struct isi_vqvae_w { /* VQVAE.__init__, vqvae.py:126-216 */
   int no_quantize; /* 1: UnquantizedBottleneck (bottleneck.py:107-119, selected at vqvae.py:152-160): the two
                     * codebook searches are skipped, quant_t / quant_b receive the 1x1 convolutions' outputs,
                     * id_t / id_b are not written, scalars = {0, inf, 0, inf}; the codebooks may be null */
+  const float *code_table_conv3;    /* optional (NULL: the layer runs as a convolution): isi_vq_pack_code_tables_f32's table of
+                                     * dec_t.conv3 over quantize_t's codebook; must be re-made whenever either changes */
+  const float *code_table_upsample; /* the same for upsample[0]; used by calls that both encode and decode */
 } isi_vqvae_w;
 
 /* Outputs of VQVAE.encode / forward (vqvae.py:245-278).  Any pointer may be

@@ -26,6 +26,7 @@ const KnobEntry kKnobTable[] = {
     {"ISI_NO_CONV_FIRST", &Knobs::no_conv_first, 0, false},
     {"ISI_NO_VQ_FUSION", &Knobs::no_vq_fusion, 0, false},
     {"ISI_NO_SETUP_FUSION", &Knobs::no_setup_fusion, 0, false},
+    {"ISI_NO_CODE_TABLES", &Knobs::no_code_tables, 0, false},
     {"ISI_NO_CONV_PAIR_KERNEL", &Knobs::no_conv_pair_kernel, 0, false},
     {"ISI_NO_RESBLOCK_PAIR_KERNEL", &Knobs::no_resblock_pair_kernel, 0, false},
     {"ISI_NO_CONVT_PAIR_KERNEL", &Knobs::no_convt_pair_kernel, 0, false},
@@ -553,6 +554,16 @@ int isi_vq_conv1x1_nearest_tape_f32(const isi_src *src0, const isi_src *src1, co
 size_t isi_vq_conv1x1_workspace_floats(int C0, int C1, int D) { return vq_conv1x1_workspace_floats(C0, C1, D); }
 int isi_vq_pack_fragments_f32(const float *packed_w16, float *frag_out, int Kpad, void *stream) {
   return vq_pack_fragments_f32(packed_w16, frag_out, Kpad, S(stream));
+}
+size_t isi_vq_code_tables_bytes(int which, int K, int Cout) { return vq_code_tables_bytes(which, K, Cout); }
+int isi_vq_pack_code_tables_f32(const float *w3_packed, int Cout3, const float *wT_packed, int CoutU, const float *codes_kd, int D,
+                                int K, float *t3_out, float *tu_out, void *stream) {
+  return vq_pack_code_tables_f32(w3_packed, Cout3, wT_packed, CoutU, codes_kd, D, K, t3_out, tu_out, S(stream));
+}
+int isi_vq_code_gather_f32(const int64_t *ids, const float *t3, const float *bias3, float *out3, int C3, int out3_pair, int relu3,
+                           const float *tu, const float *biasU, float *outU, int CU, int outU_pair, int reluU, int B, int H, int W,
+                           int K, void *stream) {
+  return vq_code_gather_f32(ids, t3, bias3, out3, C3, out3_pair, relu3, tu, biasU, outU, CU, outU_pair, reluU, B, H, W, K, S(stream));
 }
 size_t isi_vq_planes_bytes(int K) { return vq_planes_bytes(K); }
 int isi_vq_pack_planes_f32(const float *codes_kd, const float *e2, void *planes_out, int D, int K, void *stream) {

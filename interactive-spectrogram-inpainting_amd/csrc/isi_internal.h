@@ -306,6 +306,13 @@ int vq_conv1x1_nearest_f32(const isi_src *s0, const isi_src *s1, const float *w1
 size_t vq_planes_bytes(int K);
 int vq_pack_planes_f32(const float *codes_kd, const float *e2, void *planes_out, int D, int K, hipStream_t stream);
 int vq_pack_fragments_f32(const float *packed_w16, float *frag_out, int Kpad, hipStream_t stream);
+// code_tables.hip: the two layers that read only the quantised top map, as sums of pack-time table rows
+size_t vq_code_tables_bytes(int which, int K, int Cout);
+int vq_pack_code_tables_f32(const float *w3_packed, int Cout3, const float *wT_packed, int CoutU, const float *codes_kd, int D,
+                            int K, float *t3_out, float *tu_out, hipStream_t stream);
+int vq_code_gather_f32(const int64_t *ids, const float *t3, const float *bias3, float *out3, int C3, int out3_pair, int relu3,
+                       const float *tu, const float *biasU, float *outU, int CU, int outU_pair, int reluU, int B, int H, int W,
+                       int K, hipStream_t stream);
 size_t vq_conv1x1_workspace_floats(int C0, int C1, int D);
 int vq_zero_counts(int32_t *counts, int K, hipStream_t stream);
 int vq_unquantized_scalars(float *scalars2, hipStream_t stream);

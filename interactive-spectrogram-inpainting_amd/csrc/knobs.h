@@ -14,6 +14,8 @@ struct Knobs {
   int no_vq_fusion;             // ISI_NO_VQ_FUSION: quantize_conv and search as two launches
   int no_setup_fusion;          // ISI_NO_SETUP_FUSION: the forward as before the pack-time set-up: codebook planes filled by every workgroup of the
                                 // searches, histogram zeroing and both levels' statistics as launches of their own
+  int no_code_tables;           // ISI_NO_CODE_TABLES: dec_t's first convolution and upsample[0] as matrix work even where the plan
+                                // carries their code tables (code_tables.hip)
   int no_conv_pair_kernel;      // ISI_NO_CONV_PAIR_KERNEL: register-staged kernel instead of the LDS-DMA one
   int no_resblock_pair_kernel;  // ISI_NO_RESBLOCK_PAIR_KERNEL
   int no_convt_pair_kernel;     // ISI_NO_CONVT_PAIR_KERNEL: four phase launches instead of the fused transposed conv

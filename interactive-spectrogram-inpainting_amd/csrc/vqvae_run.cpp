@@ -198,9 +198,20 @@ int run_encoder(const isi_encoder_w &e, isi_src in, int B, int H, int W, float *
 // `in0_pair` / `in1_pair`: formats of the two inputs; `pairs`: internal tensors are written in the pair format
 // wherever their consumer reads it (the few-channel transposed-convolution kernel reads fp32); `final_pair`: format
 // of the tensor written through `final_dst`.
+// `tab` (dec_t of a pair-pipeline call that carries code tables, code_tables.hip): the input is the quantised map of
+// the codes `tab->ids`; conv3 is then the table sum instead of a convolution, and the same launch writes the first
+// upsample layer where `tab->tu` is set.
+struct CodeTableJob {
+  const int64_t *ids;
+  int K;
+  const float *t3;                      // null: conv3 stays a convolution
+  const float *tu, *bias_u;             // null tu: no upsample half
+  float *out_u;
+  int C_u;
+};
 int run_decoder(const isi_decoder_w &d, const isi_src &in0, const isi_src *in1, int B, int H, int W,
                 float *s0, float *s1, float *hid, const isi_dst &final_dst, int pf, bool in0_pair, bool in1_pair,
-                bool pairs, bool final_pair, hipStream_t st) {
+                bool pairs, bool final_pair, hipStream_t st, const CodeTableJob *tab = nullptr) {
   Act cur{s0, d.conv3.Cout, H, W};
   bool stack_pairs = false;
   // format in which up[i] wants its input: pairs for the implicit-GEMM kernels and for the pair form of the
@@ -216,9 +227,12 @@ int run_decoder(const isi_decoder_w &d, const isi_src &in0, const isi_src *in1, 
     isi_dst dd = dst_nhwc(cur.p, cur.C, H, W);
     stack_pairs = res_stack_in_pairs(pairs, d.n_res, d.res3, B, H, W, cur.C);
     const bool op = d.n_res ? stack_pairs : (d.n_up ? up_reads_pair(0, cur.C) : final_pair);   // fp32 into a register-staged stack
-    int rc = conv2d_f32(&in0, in1, d.conv3.w, d.conv3.bias, nullptr, &dd, B, H, W, cur.C, 3, 3, 1,
-                        1, 1 | pf | (in0_pair ? ISI_CONV_IN0_PAIR : 0) | (in1_pair ? ISI_CONV_IN1_PAIR : 0) |
-                        (op ? ISI_CONV_OUT_PAIR : 0), st);
+    int rc = tab && tab->t3
+                 ? vq_code_gather_f32(tab->ids, tab->t3, d.conv3.bias, cur.p, cur.C, op, /*relu*/ 1, tab->tu, tab->bias_u,
+                                      tab->out_u, tab->C_u, /*pair*/ 1, /*relu*/ 0, B, H, W, tab->K, st)
+                 : conv2d_f32(&in0, in1, d.conv3.w, d.conv3.bias, nullptr, &dd, B, H, W, cur.C, 3, 3, 1,
+                              1, 1 | pf | (in0_pair ? ISI_CONV_IN0_PAIR : 0) | (in1_pair ? ISI_CONV_IN1_PAIR : 0) |
+                              (op ? ISI_CONV_OUT_PAIR : 0), st);
     if (rc) return rc;
   }
   bool cp = pairs;   // format of `cur` after the residual stack
@@ -395,6 +409,14 @@ int plan(const isi_vqvae_w &w, int mode, const float *x, int B, int H, int W,
   // quantize_conv_{t,b} fused into the codebook searches: the pair pipeline only (pair8 sources, blocked weights)
   const bool fuse_vq = pairs && !w.no_quantize && !knobs().no_vq_fusion;
   const bool frag_packed = fuse_vq && w.w16 == 2 && (mode & ISI_MODE_ENCODE);
+  // dec_t's first convolution and upsample[0] as sums of pack-time table rows (code_tables.hip): the pair pipeline of a
+  // call that produces the top codes itself.  encode() and forward() take the same route to id_b; the choice does not
+  // depend on the fusion or flush switches (ids exist on all of those paths).
+  const bool tab_ok = pairs && !w.no_quantize && w.precision == 4 && !knobs().no_code_tables && (mode & ISI_MODE_ENCODE) && D % 4 == 0;
+  const bool tab3 = tab_ok && w.code_table_conv3 && w.dec_t.conv3.Cin == D && w.dec_t.conv3.Cout % 8 == 0;
+  const bool tabU = tab_ok && (mode & ISI_MODE_DECODE) && w.code_table_upsample && w.n_upsample >= 1 && w.upsample[0].Cin == D &&
+                    w.upsample[0].Cout % 8 == 0;
+  const bool q_t_pair_read = !tab3 || ((mode & ISI_MODE_DECODE) && !tabU);   // by dec_t.conv3 / by upsample[0]
   // Both histograms are zeroed by the first encoder launch (its workgroup 0: conv_first_f32.hip) instead of a launch of
   // their own.  The workspace is the caller's and arrives with any content: zeroed per call.
   // (ISI_NO_SETUP_FUSION: the zeroing launch, for the tests' A/B.)
@@ -438,7 +460,7 @@ int plan(const isi_vqvae_w &w, int mode, const float *x, int B, int H, int W,
                          : run_quantizer(w.quantize_t, zbuf, (int64_t)B * et.H * et.W, id_t, quant_t, counts_top,
                                          sse_part, scal + 0, pf_enc & ISI_CONV_F16X3, st);
       if (rc) return rc;
-      if (pairs) {
+      if (pairs && q_t_pair_read) {
         rc = pair_encode_f32(quant_t, q_t_pair, (int64_t)B * et.H * et.W * D, st);
         if (rc) return rc;
       }
@@ -450,7 +472,16 @@ int plan(const isi_vqvae_w &w, int mode, const float *x, int B, int H, int W,
     {
       isi_src s = src_nhwc(pairs ? q_t_pair : quant_t, D, et.H, et.W);
       isi_dst d = dst_nhwc(dec_t, w.dec_t.up[w.dec_t.n_up - 1].Cout, sh.Hb, Wd);
-      rc = run_decoder(w.dec_t, s, nullptr, B, et.H, et.W, s0, s1, hid, d, pf_enc, pairs, false, pairs, pairs, st);
+      // one gather launch right behind the top search: the conv3 items, then the upsample items (both read only id_t)
+      const CodeTableJob job{id_t, w.quantize_t.K, tab3 ? w.code_table_conv3 : nullptr, tabU ? w.code_table_upsample : nullptr,
+                             w.upsample[0].bias, up, w.upsample[0].Cout};
+      if (tabU && !tab3) {
+        rc = vq_code_gather_f32(id_t, nullptr, nullptr, nullptr, 0, 0, 0, job.tu, job.bias_u, job.out_u, job.C_u, 1, 0, B, et.H,
+                                et.W, job.K, st);
+        if (rc) return rc;
+      }
+      rc = run_decoder(w.dec_t, s, nullptr, B, et.H, et.W, s0, s1, hid, d, pf_enc, pairs, false, pairs, pairs, st,
+                       tab3 ? &job : nullptr);
       if (rc) return rc;
     }
     // quantize_conv_b on cat([dec_t, enc_b]) cropped to Wq (vqvae.py:266-273)
@@ -515,6 +546,10 @@ int plan(const isi_vqvae_w &w, int mode, const float *x, int B, int H, int W,
     int h = sh.Ht, ww = sh.Wt;
     for (int i = 0; i < w.n_upsample; ++i) {
       float *o = (i % 2 == 0) ? up : up2;
+      if (i == 0 && tabU) {       // written by the gather launch of the ENCODE block
+        cur = o; h *= 2; ww *= 2;
+        continue;
+      }
       isi_src s = src_nhwc(cur, w.upsample[i].Cin, h, ww);
       isi_dst d = dst_nhwc(o, w.upsample[i].Cout, 2 * h, 2 * ww);
       rc = conv_transpose2d_k4s2_f32(&s, w.upsample[i].w, w.upsample[i].bias, &d, B, h, ww,

@@ -61,7 +61,8 @@ class isi_vqvae_w(C.Structure):
                 ("quantize_t", isi_codebook_w), ("quantize_b", isi_codebook_w),
                 ("dec_t", isi_decoder_w), ("dec", isi_decoder_w),
                 ("n_upsample", C.c_int), ("upsample", isi_conv_w * ISI_MAX_STAGES), ("w16", C.c_int),
-                ("precision", C.c_int), ("no_quantize", C.c_int)]
+                ("precision", C.c_int), ("no_quantize", C.c_int),
+                ("code_table_conv3", C.c_void_p), ("code_table_upsample", C.c_void_p)]
 
 
 class isi_vqvae_out(C.Structure):
@@ -196,6 +197,10 @@ SIGNATURES = {
     "isi_pair_decode_f32": (C.c_int, [_P, _P, C.c_int64, _P]),
     "isi_packed_convT_k4s2_weight_floats": (C.c_size_t, [C.c_int, C.c_int]),
     "isi_pack_codebook_f32": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
+    "isi_vq_code_tables_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "isi_vq_pack_code_tables_f32": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "isi_vq_code_gather_f32": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "isi_vq_planes_bytes": (C.c_size_t, [C.c_int]),
     "isi_vq_pack_planes_f32": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
     "isi_conv2d_f32": (C.c_int, [C.POINTER(isi_src), C.POINTER(isi_src), _P, _P, C.POINTER(isi_src),

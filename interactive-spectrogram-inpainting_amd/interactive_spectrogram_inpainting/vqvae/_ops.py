@@ -307,6 +307,47 @@ def embed_code(idx: torch.Tensor, codes: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def pack_code_tables(packed_w3: Optional[torch.Tensor], cout3: int, packed_wT: Optional[torch.Tensor], coutU: int,
+                     codes: torch.Tensor):
+    """Per-code product tables of a 3x3 convolution and of a ConvTranspose2d(k4,s2,p1) over the codebook `codes` [K,D]
+    (csrc/code_tables.hip), from the layers' packed weights: (T3 [9 K + 1, cout3] or None, TU [16 K + 1, coutU] or None),
+    rows ordered [tap][code] / [phase][tap][code], the last row the pad row of -0.0 a tap outside the map gathers."""
+    _hip.require_gpu(codes, "codes")
+    K, D = codes.shape
+    t3 = torch.empty(9 * K + 1, cout3, dtype=torch.float32, device=codes.device) if packed_w3 is not None else None
+    tu = torch.empty(16 * K + 1, coutU, dtype=torch.float32, device=codes.device) if packed_wT is not None else None
+    _hip.check(_hip.lib().isi_vq_pack_code_tables_f32(
+        packed_w3.data_ptr() if t3 is not None else None, cout3, packed_wT.data_ptr() if tu is not None else None, coutU,
+        codes.data_ptr(), D, K, t3.data_ptr() if t3 is not None else None, tu.data_ptr() if tu is not None else None,
+        _s(codes)), "isi_vq_pack_code_tables_f32")
+    return t3, tu
+
+
+def code_gather(ids: torch.Tensor, K: int, t3: Optional[torch.Tensor] = None, bias3: Optional[torch.Tensor] = None,
+                tu: Optional[torch.Tensor] = None, biasU: Optional[torch.Tensor] = None, pair3: bool = False,
+                pairU: bool = False, relu3: bool = True, reluU: bool = False):
+    """ids int64 [B,H,W] -> (relu(bias3 + sum of T3 rows) [B,H,W,C3] or None, biasU + sum of TU rows [B,2H,2W,CU] or
+    None) in ONE launch; `pair*`: that output in the split-f16 pair format."""
+    _hip.require_gpu(ids, "code indices")
+    if ids.dtype != torch.int64 or ids.dim() != 3:
+        raise TypeError("code indices must be int64 [B, H, W]")
+    for t, rows in ((t3, 9 * K + 1), (tu, 16 * K + 1)):
+        if t is not None and (t.dim() != 2 or t.shape[0] != rows or not t.is_contiguous()):
+            raise ValueError(f"a code table of pack_code_tables has {rows} rows (the pad row included)")
+    ids = ids.contiguous()
+    B, H, W = ids.shape
+    out3 = torch.empty(B, H, W, t3.shape[-1], dtype=torch.float32, device=ids.device) if t3 is not None else None
+    outU = torch.empty(B, 2 * H, 2 * W, tu.shape[-1], dtype=torch.float32, device=ids.device) if tu is not None else None
+
+    def p(t):
+        return t.data_ptr() if t is not None else None
+    _hip.check(_hip.lib().isi_vq_code_gather_f32(
+        ids.data_ptr(), p(t3), p(bias3), p(out3), t3.shape[-1] if t3 is not None else 0, int(pair3), int(relu3),
+        p(tu), p(biasU), p(outU), tu.shape[-1] if tu is not None else 0, int(pairU), int(reluU), B, H, W, K, _s(ids)),
+        "isi_vq_code_gather_f32")
+    return out3, outU
+
+
 def relu_(x: torch.Tensor) -> torch.Tensor:
     """In-place ReLU on a dense tensor (any memory format that is non-overlapping and dense)."""
     _hip.require_gpu(x, "relu input")

@@ -281,8 +281,29 @@ class VQVAE(nn.Module):
             warnings.warn(f"a convolution weight reaches {_F16_WEIGHT_LIMIT:g} in magnitude (or a weight / code vector is not finite): "
                           "beyond the operand range of conv_precision='split_f16', running this model in 'split_bf16'")
             w.precision = 3
+        self._pack_code_tables(w, keep)
         self._plan, self._plan_key = (w, keep), key
         return w
+
+    def _pack_code_tables(self, w: _hip.isi_vqvae_w, keep: list) -> None:
+        """The two layers that read nothing but the quantised top map -- `dec_t`'s first convolution and
+        `upsample_top_to_bottom[0]` -- as tables of their per-code products (csrc/code_tables.hip).  The tables are made
+        from this plan's codebook and packed weights and live and die with it, i.e. with the versions of all three."""
+        L = _hip.lib()
+        if w.no_quantize or w.precision != 4 or not w.n_upsample:    # (the library reads them in the pair pipeline only)
+            return
+        conv3, up = self.dec_t.blocks[0], self.upsample_top_to_bottom[0]
+        K, D = self.quantize_t.n_embed, self.quantize_t.dim
+        if conv3.in_channels != D or up.in_channels != D or conv3.out_channels % 8 or up.out_channels % 8:
+            return
+        dev = self.quantize_t.embed.device
+        t3 = torch.empty(L.isi_vq_code_tables_bytes(0, K, conv3.out_channels) // 4, dtype=torch.float32, device=dev)
+        tu = torch.empty(L.isi_vq_code_tables_bytes(1, K, up.out_channels) // 4, dtype=torch.float32, device=dev)
+        _hip.check(L.isi_vq_pack_code_tables_f32(w.dec_t.conv3.w, conv3.out_channels, w.upsample[0].w, up.out_channels,
+                                                 w.quantize_t.codes_kd, D, K, t3.data_ptr(), tu.data_ptr(),
+                                                 C.c_void_p(_hip.stream_ptr(dev))), "isi_vq_pack_code_tables_f32")
+        keep.extend([t3, tu])
+        w.code_table_conv3, w.code_table_upsample = t3.data_ptr(), tu.data_ptr()
 
     def _total_factor(self) -> Tuple[int, int]:
         return self.resolution_factors['bottom'], self.resolution_factors['top']

@@ -1089,6 +1089,25 @@ int isi_vq_finalize_f32(const float *sse_part, int n_part, const int32_t *counts
 int isi_embed_code_f32(const int64_t *idx, const float *codes_kd, float *out,
                        int64_t N, int D, int K, void *stream);
 
+/* embed_mix: per-cell weighted mixtures of codebook rows, the step in front of VQVAE.decode that renders "70 % of this
+ * sound, 30 % of that one".  For N cells, M sources (1 <= M <= 8), codes_kd [K][D], ids [M][N] int64 and weights [M][N]
+ * fp32 (source m starts ids_stride / w_stride ELEMENTS behind source m - 1), out [N][D] with ldo FLOATS between two cells:
+ *   out[n, :] = sum over m ascending, of the terms with w[m, n] != 0, of  w[m, n] * codes_kd[id[m, n], :]
+ * A term whose weight compares equal to zero (+0.0 or -0.0) does not exist: its id is never looked at (it may be -1, K,
+ * the priors' mask token, 2^40) and its codebook row may hold NaN.  A term with a non-zero weight (NaN included) and an id
+ * outside [0, K) makes all D channels of that cell NaN, and only that cell's; such an id is never used as an address (the
+ * rule of isi_vq_code_gather_f32).  One lane's arithmetic is acc = -0.0f, then acc = fmaf(w, e, acc) for each existing
+ * term, m ascending.  Hence: a cell whose only existing term has weight 1 equals the codebook row bit for bit, -0.0 entries
+ * included; a cell with no existing term is -0.0; the bits of a cell depend on that cell's ids and weights alone, not on
+ * N, the batch or the launch geometry.  Against the float64 sum the error is at most T 2^-24 sum_m |w_m e_m| (1 + 2^-20),
+ * T the number of existing terms: one rounding per fma, each bounded by 2^-24 of a partial sum the absolute sum dominates.
+ * Refused on the host before any launch (ISI_E_INVALID): a null pointer; N <= 0; M outside 1..8; D <= 0 or not a multiple
+ * of 4; K <= 0; codes_kd or out not 16-byte aligned, or ldo not a multiple of 4; ldo < D; ids_stride < N or w_stride < N.
+ * Index range (ISI_E_UNSUPPORTED at or beyond it): N D / 4 < 2^31 (the launch's lanes are numbered in 32 bits),
+ * ids_stride and w_stride < 2^56, ldo < 2^31 (addresses are formed in 64 bits from these).  One launch, no workspace. */
+int isi_embed_mix_f32(const int64_t *ids, int64_t ids_stride, const float *weights, int64_t w_stride,
+                      const float *codes_kd, float *out, int64_t ldo, int64_t N, int M, int D, int K, void *stream);
+
 /* ------------------------------------------------- whole VQ-VAE-2 forward */
 
 #define ISI_MAX_STAGES 4

@@ -584,6 +584,10 @@ int isi_embed_code_f32(const int64_t *idx, const float *codes_kd, float *out, in
                        int K, void *stream) {
   return embed_code_f32(idx, codes_kd, out, N, D, K, S(stream));
 }
+int isi_embed_mix_f32(const int64_t *ids, int64_t ids_stride, const float *weights, int64_t w_stride, const float *codes_kd,
+                      float *out, int64_t ldo, int64_t N, int M, int D, int K, void *stream) {
+  return embed_mix_f32(ids, ids_stride, weights, w_stride, codes_kd, out, ldo, N, M, D, K, S(stream));
+}
 
 int isi_vqvae_pair_activations(const isi_vqvae_w *w) { return vqvae_pair_activations(w); }
 size_t isi_vqvae_workspace_bytes(const isi_vqvae_w *w, int B, int H, int W) {

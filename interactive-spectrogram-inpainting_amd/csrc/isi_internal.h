@@ -327,6 +327,9 @@ int vq_finalize2_f32(const float *sse_t, int np_t, const int32_t *counts_t, int 
 int vq_scalars_sum_f32(float *out5, hipStream_t stream);
 int embed_code_f32(const int64_t *idx, const float *codes, float *out, int64_t N, int D, int K,
                    hipStream_t stream);
+// code_mix.hip: per-cell weighted mixtures of codebook rows (the spec: isi_embed_mix_f32 in isi_hip.h)
+int embed_mix_f32(const int64_t *ids, int64_t ids_stride, const float *weights, int64_t w_stride, const float *codes, float *out,
+                  int64_t ldo, int64_t N, int M, int D, int K, hipStream_t stream);
 
 int relu_inplace_f32(float *x, int64_t n, hipStream_t stream);
 

@@ -15,6 +15,9 @@ routes (flask_server.py), free of HTTP so that they can be called, tested and ti
                       cut / padded to the requested duration (:314-372, 446-514); optionally the one nearest to a sound
   similar_sounds      the stored sounds most like a given one, optionally outside a masked region (not in the
                       reference: utils/datasets/code_index.py, csrc/code_search.hip)
+  morph / morph_sweep / crossfade   decode per-cell weighted mixtures of several sounds' codes: timbre interpolation,
+                      a sweep between two sounds in one batch, a splice whose seam is a ramp in the latent (not in the
+                      reference: csrc/code_mix.hip, VQVAE.decode_code_mix)
   spectrogram_png     the decoded log-mel magnitude as a viridis PNG (:103-143, 1024-1046)
 
 The heavy work is `sample.sample_model` (encoder pass + KV-cached native decoding loop),
@@ -772,6 +775,145 @@ def patch_from_database(index, top_code: torch.Tensor, bottom_code: torch.Tensor
         patched = paste_fragment(top_code, bottom_code, item_top, item_bottom, window_mask, layer, start, shift)
         out.append((patched, attributes, distance, shift))
     return out
+
+
+MORPH_MAX_SOURCES = 8          # sources of one mixture (isi_embed_mix_f32)
+MORPH_SWEEP_MAX_STEPS = 256    # rows of one sweep: the batch cap of native sampling (priors/_decode.py)
+
+
+def _morph_codes(sounds) -> Tuple[torch.Tensor, torch.Tensor]:
+    """M (top_code, bottom_code) pairs of equal shapes -> int64 stacks ([M, B, F_t, T_t], [M, B, F_b, T_b])."""
+    sounds = list(sounds)
+    if not 1 <= len(sounds) <= MORPH_MAX_SOURCES:
+        raise ValueError(f"morph mixes 1 to {MORPH_MAX_SOURCES} sounds, got {len(sounds)}")
+    tops, bottoms = [], []
+    for top, bottom in sounds:
+        if top.dim() < 2 or bottom.dim() < 2:
+            raise ValueError("a sound is a (top_code [B, F_t, T_t], bottom_code [B, F_b, T_b]) pair")
+        tops.append(top.reshape(-1, *top.shape[-2:]))
+        bottoms.append(bottom.reshape(-1, *bottom.shape[-2:]))
+    for name, maps in (("top", tops), ("bottom", bottoms)):
+        if any(m.shape != maps[0].shape or m.dtype != torch.int64 or m.device != maps[0].device for m in maps):
+            raise ValueError(f"the sounds' {name} codemaps must be int64 maps of one shape on one device")
+    top, bottom = torch.stack(tops), torch.stack(bottoms)
+    if top.shape[1] != bottom.shape[1] or bottom.shape[2] % top.shape[2] or bottom.shape[3] % top.shape[3]:
+        raise ValueError(f"bottom maps {tuple(bottom.shape[1:])} are not a refinement of the top maps {tuple(top.shape[1:])}")
+    return top, bottom
+
+
+def _morph_weights(weights, M: int, F: int, T: int, name: str) -> torch.Tensor:
+    """M scalars, [M, T] or [M, F, T] -> fp32 [M, F, T] on the host, checked as the kernel will see it: finite,
+    non-negative, summing to 1 over the sources within 1e-6 in every cell."""
+    w = weights.detach().cpu() if isinstance(weights, torch.Tensor) else torch.as_tensor(weights)
+    w = w.to(torch.float64)
+    if w.dim() == 1 and w.shape[0] == M:
+        w = w.reshape(M, 1, 1)
+    elif w.dim() == 2 and tuple(w.shape) == (M, T):
+        w = w.reshape(M, 1, T)
+    elif not (w.dim() == 3 and tuple(w.shape) == (M, F, T)):
+        raise ValueError(f"{name}: expected {M} scalars, [{M}, {T}] or [{M}, {F}, {T}], got {tuple(w.shape)}")
+    w = w.expand(M, F, T).to(torch.float32)
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError(f"{name}: weights must be finite")
+    if bool((w < 0).any()):
+        raise ValueError(f"{name}: weights must be non-negative")
+    if bool(((w.double().sum(0) - 1).abs() > 1e-6).any()):
+        raise ValueError(f"{name}: the weights of every cell must sum to 1 (within 1e-6)")
+    return w.contiguous()
+
+
+def _check_mixed_codes(codes: torch.Tensor, weights: torch.Tensor, n_embed: int, name: str) -> None:
+    # one device sync, skipped while a HIP graph is being captured (like QuantizedBottleneck.embed_code)
+    if codes.is_cuda and torch.cuda.is_current_stream_capturing():
+        return
+    if bool((((codes < 0) | (codes >= n_embed)) & (weights != 0)).any()):
+        raise IndexError(f"{name} code out of range under a non-zero weight")
+
+
+def _snap_to_codes(bottleneck, quant: torch.Tensor) -> torch.Tensor:
+    """quant [B, H, W, D] -> ids [B, H, W] by the bottleneck's eval-mode nearest-code search (no codebook update)."""
+    was_training = bottleneck.training
+    bottleneck.eval()
+    try:
+        return bottleneck(quant)[2]
+    finally:
+        bottleneck.train(was_training)
+
+
+def _mix(vqvae, codes_t, weights_t, codes_b, weights_b, snap: bool):
+    """codes / weights [M, B, F, T] per level, the weights already checked: the spectrogram, or the snapped codemaps."""
+    weights_t, weights_b = weights_t.to(codes_t.device), weights_b.to(codes_b.device)
+    _check_mixed_codes(codes_t, weights_t, vqvae.quantize_t.n_embed, "top")
+    _check_mixed_codes(codes_b, weights_b, vqvae.quantize_b.n_embed, "bottom")
+    if not snap:
+        return vqvae.decode_code_mix(codes_t, weights_t, codes_b, weights_b)
+    return (_snap_to_codes(vqvae.quantize_t, vqvae.quantize_t.embed_mix(codes_t, weights_t)),
+            _snap_to_codes(vqvae.quantize_b, vqvae.quantize_b.embed_mix(codes_b, weights_b)))
+
+
+@torch.no_grad()
+def morph(vqvae, sounds, weights, weights_bottom=None, snap: bool = False):
+    """Render a mixture of sounds: in every cell of both codemaps the decoder receives sum_m w[m] * E[code_m] instead of one
+    codebook row (`VQVAE.decode_code_mix`, csrc/code_mix.hip).
+
+    `sounds`: M <= 8 (top_code [B, F_t, T_t], bottom_code [B, F_b, T_b]) pairs of equal shapes.  `weights`, in top
+    resolution: M scalars ("70 % of this, 30 % of that"), [M, T_t] -- one weight per source and top column, a morph that
+    moves in time -- or [M, F_t, T_t].  Every top cell's weight is repeated over the bottom cells under it unless
+    `weights_bottom` gives the bottom map its own (the same three forms in bottom resolution).  The weights are host
+    values: finite, non-negative and summing to 1 per cell within 1e-6, anything else raises ValueError -- a convex mix
+    stays inside the codebook's hull and therefore inside the decoder's operand range.  A zero weight hides its code (the
+    priors' mask token may sit under it); a code outside the codebook under a non-zero weight raises IndexError (one
+    device sync, skipped during stream capture, where the cell decodes to NaN instead).
+
+    Returns the spectrogram, as `decode_code` does.  `snap`: instead the (top_code, bottom_code) nearest to the mixed maps
+    (each bottleneck's eval-mode search): a sound the priors, the search and the UI can go on editing."""
+    codes_t, codes_b = _morph_codes(sounds)
+    M, B = codes_t.shape[:2]
+    w_t = _morph_weights(weights, M, *codes_t.shape[2:], "weights")
+    if weights_bottom is None:
+        w_b = w_t.repeat_interleave(codes_b.shape[2] // codes_t.shape[2], 1).repeat_interleave(codes_b.shape[3] // codes_t.shape[3], 2)
+    else:
+        w_b = _morph_weights(weights_bottom, M, *codes_b.shape[2:], "weights_bottom")
+    w_t = w_t.unsqueeze(1).expand(M, B, *w_t.shape[1:]).contiguous()
+    w_b = w_b.unsqueeze(1).expand(M, B, *w_b.shape[1:]).contiguous()
+    return _mix(vqvae, codes_t, w_t, codes_b, w_b, snap)
+
+
+@torch.no_grad()
+def morph_sweep(vqvae, a, b, steps: int) -> torch.Tensor:
+    """`steps` spectrograms [steps, C, H, W] from sound `a` to sound `b` ((top_code [1, F_t, T_t], bottom_code
+    [1, F_b, T_b]) each): row s mixes (1 - alpha_s) a + alpha_s b at alpha = linspace(0, 1, steps), as `morph` with those
+    two scalars would.  One batch, one decode call; at most 256 steps."""
+    steps = int(steps)
+    if not 1 <= steps <= MORPH_SWEEP_MAX_STEPS:
+        raise ValueError(f"morph_sweep: steps must be 1..{MORPH_SWEEP_MAX_STEPS}, got {steps}")
+    codes_t, codes_b = _morph_codes([a, b])
+    if codes_t.shape[1] != 1:
+        raise ValueError("morph_sweep: a and b are single sounds (batch 1)")
+    alpha = torch.linspace(0, 1, steps, dtype=torch.float32)
+    w = torch.stack([1 - alpha, alpha]).reshape(2, steps, 1, 1)          # (1 - alpha) + alpha = 1 within one rounding
+    codes_t, codes_b = (c.expand(2, steps, *c.shape[2:]).contiguous() for c in (codes_t, codes_b))
+    return _mix(vqvae, codes_t, w.expand(codes_t.shape).contiguous(), codes_b, w.expand(codes_b.shape).contiguous(), False)
+
+
+@torch.no_grad()
+def crossfade(vqvae, a, b, start_index_top: int, width_top: int, snap: bool = False):
+    """Sound `a` before top column `start_index_top`, sound `b` from column `start_index_top + width_top` on, and between
+    them a linear ramp in the latent: ramp column j of n carries (j + 1) / (n + 1) of `b`, with n = `width_top` columns in
+    the top map and, finer, n = ratio * `width_top` columns in the bottom map.  `width_top` = 0 is the hard cut: the decode
+    of the spliced codemaps, bit for bit.  Returns what `morph` returns."""
+    codes_t, codes_b = _morph_codes([a, b])
+    start, width = int(start_index_top), int(width_top)
+    T = codes_t.shape[3]
+    if start < 0 or width < 0 or start + width > T:
+        raise ValueError(f"crossfade: window [{start}, {start + width}) does not lie inside the {T} top columns")
+
+    def ramp(columns: int, scale: int) -> torch.Tensor:
+        j = torch.arange(columns, dtype=torch.float64) - scale * start
+        wb = ((j + 1) / (scale * width + 1)).clamp(0, 1)
+        return torch.stack([1 - wb, wb])
+
+    return morph(vqvae, [a, b], ramp(T, 1), ramp(codes_b.shape[3], codes_b.shape[3] // T), snap=snap)
 
 
 def sample_from_database(codes_dataset, label_encoders_per_modality: Mapping[str, object], duration_top: int,

@@ -307,6 +307,33 @@ def embed_code(idx: torch.Tensor, codes: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def embed_mix(ids: torch.Tensor, weights: torch.Tensor, codes: torch.Tensor) -> torch.Tensor:
+    """ids int64 [M, ...], weights fp32 [M, ...] (same shape, 1 <= M <= 8), codes [K, D] -> [..., D]: per cell the sum, m
+    ascending, of weights[m] * codes[ids[m]] over the terms with a non-zero weight (csrc/code_mix.hip; the specification
+    is isi_embed_mix_f32's comment in include/isi_hip.h).  A zero weight hides its id; a non-zero weight over an id
+    outside [0, K) makes that cell NaN."""
+    _hip.require_gpu(ids, "code indices")
+    _hip.require_gpu(weights, "mixing weights")
+    if ids.dtype != torch.int64:
+        raise TypeError(f"code indices must be int64, got {ids.dtype}")
+    if weights.dtype != torch.float32:
+        raise TypeError(f"mixing weights must be float32, got {weights.dtype}")
+    if ids.dim() < 1 or ids.shape != weights.shape or ids.device != weights.device:
+        raise ValueError(f"ids {tuple(ids.shape)} and weights {tuple(weights.shape)} must have the same shape [M, ...] on one device")
+    M = ids.shape[0]
+    if not 1 <= M <= 8:
+        raise ValueError(f"embed_mix takes 1 to 8 sources, got {M}")
+    ids, weights = ids.contiguous(), weights.contiguous()
+    K, D = codes.shape
+    out = torch.empty(*ids.shape[1:], D, dtype=torch.float32, device=ids.device)
+    N = ids.numel() // M
+    if N == 0:
+        return out
+    _hip.check(_hip.lib().isi_embed_mix_f32(ids.data_ptr(), N, weights.data_ptr(), N, codes.data_ptr(), out.data_ptr(), D,
+                                            N, M, D, K, _s(ids)), "isi_embed_mix_f32")
+    return out
+
+
 def pack_code_tables(packed_w3: Optional[torch.Tensor], cout3: int, packed_wT: Optional[torch.Tensor], coutU: int,
                      codes: torch.Tensor):
     """Per-code product tables of a 3x3 convolution and of a ConvTranspose2d(k4,s2,p1) over the codebook `codes` [K,D]

@@ -70,6 +70,13 @@ class QuantizedBottleneck(nn.Module):
         codes, _ = self.packed()
         return _ops.embed_code(embed_id, codes)
 
+    def embed_mix(self, embed_ids: Tensor, weights: Tensor) -> Tensor:
+        """embed_ids int64 [M, ...], weights fp32 [M, ...] -> [..., D]: per cell the weighted sum of M codebook rows
+        (`_ops.embed_mix`).  No range check on the host: a zero weight hides its id, and a non-zero weight over an id
+        outside the codebook makes that cell NaN on the device."""
+        codes, _ = self.packed()
+        return _ops.embed_mix(embed_ids, weights, codes)
+
 
 class QuantizedBottleneckWithRestarts(QuantizedBottleneck):
     """EMA codebook with random restarts of dead codes (the reference's `bottleneck.py:122-166`, whose arithmetic sits in
@@ -119,4 +126,7 @@ class UnquantizedBottleneck(QuantizedBottleneck):
         return output, diff, embed_ind, code_assignation_perplexity
 
     def embed_code(self, embed_ind):
+        raise NotImplementedError
+
+    def embed_mix(self, embed_ids, weights):
         raise NotImplementedError

@@ -434,6 +434,19 @@ class VQVAE(nn.Module):
         quant_b = self.quantize_b.embed_code(code_b).permute(0, 3, 1, 2)
         return self.decode(quant_t, quant_b)
 
+    def decode_code_mix(self, codes_t: Tensor, weights_t: Tensor, codes_b: Tensor, weights_b: Tensor) -> Tensor:
+        """Decode per-cell weighted mixtures of codes: codes_* int64 and weights_* fp32, each [M, B, H, W] in its level's
+        resolution (1 <= M <= 8 sources).  quant[b, :, y, x] = sum_m weights[m, b, y, x] * E[codes[m, b, y, x]] on both
+        levels (`QuantizedBottleneck.embed_mix`), then the decoder of `decode`, which reads the two maps in the
+        channels-last storage they are written in; returns what `decode_code` returns.  With M = 1 and weight 1 it is
+        `decode_code` bit for bit.  Any weights are accepted -- negative, not summing to 1, NaN: a mixture outside the
+        codebook's convex hull may leave the decoder's split-f16 operand range, which is the caller's business
+        (`inpainting.morph` admits convex weights only).  A zero weight hides its code (the priors' mask token may sit
+        under it); a non-zero weight over a code outside [0, K) makes that cell NaN."""
+        quant_t = self.quantize_t.embed_mix(codes_t, weights_t).permute(0, 3, 1, 2)
+        quant_b = self.quantize_b.embed_mix(codes_b, weights_b).permute(0, 3, 1, 2)
+        return self.decode(quant_t, quant_b)
+
     def post_process(self, dec: Tensor) -> Tensor:
         """vqvae.py:297-302: de-normalise, then zero the phase of bins at or below the magnitude floor
         (one fused pass when both are configured)."""

@@ -10,9 +10,11 @@
 //   * torch.cat (vqvae.py:270,282) is replaced by two-source convolutions;
 //   * NCHW<->NHWC permutes (vqvae.py:260-262,272-274) vanish: internal
 //     activations are channels-last, strides describe the API tensors.
+// A call is: check_shapes, carve (the workspace), check_call -- every refusal, before the first launch --, make_route
+// (which kernels, which formats: derived once), then the launches.  tests/forward_plan_tracer.cpp turns the launch
+// sequence of a few thousand calls into text on the host; run it before and after an edit of this file.
 #include <algorithm>
 
-#include <cstdlib>
 #include "isi_common.h"
 #include "isi_internal.h"
 #include "knobs.h"
@@ -24,7 +26,6 @@ namespace {
 struct Act {  // dense channels-last activation
   float *p;
   int C, H, W;
-  size_t elems(int B) const { return (size_t)B * H * W * C; }
 };
 
 isi_src src_nhwc(const float *p, int C, int H, int W, int Wstride = -1) {
@@ -50,6 +51,20 @@ isi_dst dst_nchw(float *p, int C, int H, int W) {
 }
 
 inline int down_dim(int x) { return (x + 2 - 4) / 2 + 1; }
+inline int up_dim(int x, int n_up) { return x << n_up; }   // behind n_up transposed convolutions (k4 s2 p1)
+// the scratch buffer a layer writes: the one of s0 / s1 its input is not in
+inline float *other(const float *cur, float *s0, float *s1) { return cur == s0 ? s1 : s0; }
+// split-f16 products with pack-time weight pieces: what every kernel that reads or writes the pair format runs on
+inline bool f16_pieces(int pf) { return (pf & ISI_CONV_F16X3) && (pf & ISI_CONV_W16); }
+inline int dec_t_channels(const isi_vqvae_w &w) { return w.dec_t.n_up ? w.dec_t.up[w.dec_t.n_up - 1].Cout : w.dec_t.conv3.Cout; }
+// precision: 0 all fp32 | 1 decoder split-bf16 (x3) | 2 everything x3 | 3 index-feeding layers six-term
+// split (x6: fp32-grade products), decoder x3 | 4 split-f16 everywhere (fp32-grade products, f16 range)
+// `feeds_codes`: the encoders, quantize_conv_*, dec_t; else the final decoder and upsample
+int product_flags(const isi_vqvae_w &w, bool feeds_codes) {
+  if (w.precision == 4) return ISI_CONV_F16X3 | (w.w16 ? ISI_CONV_W16 : 0);
+  if (feeds_codes) return w.precision == 3 ? ISI_CONV_BF16X6 : w.precision == 2 ? ISI_CONV_BF16X3 : 0;
+  return w.precision >= 1 ? ISI_CONV_BF16X3 : 0;
+}
 
 struct Bump {
   char *base;
@@ -96,36 +111,47 @@ bool compute_shapes(const isi_vqvae_w &w, int B, int H, int W, Shapes &s) {
   s.Hb = h; s.Wb = ww; s.Cb = w.enc_b.conv3.Cout;
   if (!encoder_out_dims(w.enc_t, h, ww, B, s.max_act)) return false;
   s.Ht = h; s.Wt = ww;
-  int up = 1;
-  for (int i = 0; i < w.dec_t.n_up; ++i) up *= 2;
-  if (s.Ht * up != s.Hb) return false;  // torch.cat would fail in the reference
-  s.Wq = std::min(s.Wt * up, s.Wb);
+  if (up_dim(s.Ht, w.dec_t.n_up) != s.Hb) return false;  // torch.cat would fail in the reference
+  s.Wq = std::min(up_dim(s.Wt, w.dec_t.n_up), s.Wb);
   decoder_max_act(w.dec_t, s.Ht, s.Wt, B, s.max_act);
   decoder_max_act(w.dec, s.Hb, s.Wq, B, s.max_act);
   return true;
 }
 
-// Rosinality residual stack shared by encoder and decoder: `cur` holds the
-// rectified input r; each block writes relu(r + conv1(relu(conv3(r)))).
-// The last block writes to `final_out` when that is non-null.
-// `in_pair` / `out_pair`: the stack's input / output tensors are in the split-f16 pair format (isi_hip.h,
-// ISI_CONV_*_PAIR; only set when every block is fusable, see pairs_eligible); tensors between blocks follow `in_pair`
-// (the callers pass fp32 in: see run_encoder).
-// Will the residual stack that follows a convolution run in the pair format (resblock_pair_f16.hip: every block reads
-// and writes pairs)?  Otherwise its blocks read fp32 and only the last one writes pairs.
+// ---- the pair format (isi_hip.h, ISI_CONV_*_PAIR): who reads what.  One definition per fact: the predictors
+// (*_pairs_ok, pairs_eligible) and the launchers (run_encoder, run_decoder) both ask these.
+
+// Does the residual stack behind a convolution run in the pair format (resblock_pair_f16.hip: every block reads and
+// writes pairs)?  Otherwise its blocks read fp32 and only the last one writes pairs.
 bool res_stack_in_pairs(bool pairs, int n_res, const isi_conv_w *res3, int B, int H, int W, int C) {
   if (!pairs || n_res == 0) return false;
   for (int i = 0; i < n_res; ++i)
     if (!resblock_pair_preferred(B, H, W, C, res3[i].Cout)) return false;
   return true;
 }
+// Layer i of an encoder (i = n_down: conv3) reads its input's format if it is the first, else the pipeline's.
+inline bool enc_reads_pair(int i, bool in_pair, bool pairs) { return i ? pairs : in_pair; }
+// What up[i] of a decoder in the pair pipeline reads: pairs for the implicit-GEMM kernels and for the pair form of the
+// few-channel kernel (64 input channels, <= 2 outputs, fp32 result: the last layer of the default model); fp32 for its
+// exact-fp32 form.  `final_pair`: the format of the decoder's result.
+enum UpRead { UP_F32_SMALL, UP_PAIR_SMALL, UP_PAIR_IGEMM };
+inline int up_cin(const isi_decoder_w &d, int i) { return i ? d.up[i - 1].Cout : d.conv3.Cout; }
+UpRead up_read(const isi_decoder_w &d, int i, bool final_pair, int pf) {
+  if (!convT_small_applicable(up_cin(d, i), d.up[i].Cout)) return UP_PAIR_IGEMM;
+  const bool pair_form = convT_small_pair_ok(up_cin(d, i), d.up[i].Cout) && i == d.n_up - 1 && !final_pair && f16_pieces(pf);
+  return pair_form ? UP_PAIR_SMALL : UP_F32_SMALL;
+}
 
+// Rosinality residual stack shared by encoder and decoder: `cur` holds the rectified input r; each block writes
+// relu(r + conv1(relu(conv3(r)))).  The last block writes to `final_out` when that is non-null.
+// `in_pair` / `out_pair`: the stack's input / output tensors are in the pair format (only set when every block is
+// fusable, see pairs_eligible); tensors between blocks follow `in_pair` (res_stack_in_pairs).
 int run_res_stack(int n_res, const isi_conv_w *res3, const isi_conv_w *res1, Act &cur, int B,
                   float *s0, float *s1, float *hid, float *final_out, int pf, bool in_pair, bool out_pair,
                   hipStream_t st) {
   for (int i = 0; i < n_res; ++i) {
     const int R = res3[i].Cout;
-    float *outp = (i == n_res - 1 && final_out) ? final_out : (cur.p == s0 ? s1 : s0);
+    float *outp = (i == n_res - 1 && final_out) ? final_out : other(cur.p, s0, s1);
     if (resblock_fusable(cur.C, R)) {
       const bool op = (i == n_res - 1) ? out_pair : in_pair;
       int rc = resblock_f32(cur.p, res3[i].w, res3[i].bias, res1[i].w, res1[i].bias, outp, B, cur.H,
@@ -150,47 +176,39 @@ int run_res_stack(int n_res, const isi_conv_w *res3, const isi_conv_w *res1, Act
   return ISI_OK;
 }
 
-// RosinalityEncoder (encoder_decoder.py:38-126).  `in` may be NCHW.
+// RosinalityEncoder (encoder_decoder.py:38-126).  `in` may be NCHW; the result lands in `final_out`.
 // `in_pair`: the input is in the pair format; `pairs`: every tensor this encoder writes (including its output) is.
 // `zero` / `zero_words`: int32 words the encoder's FIRST launch clears for later launches of the stream (conv2d_f32).
 int run_encoder(const isi_encoder_w &e, isi_src in, int B, int H, int W, float *s0, float *s1,
-                float *hid, float *final_out, Act &out, int pf, bool in_pair, bool pairs, hipStream_t st,
+                float *hid, float *final_out, int pf, bool in_pair, bool pairs, hipStream_t st,
                 int32_t *zero = nullptr, int zero_words = 0) {
   Act cur{nullptr, in.C, H, W};
   isi_src cs = in;
-  bool stack_pairs = false;
   const int op = pairs ? ISI_CONV_OUT_PAIR : 0;
-  bool cp = in_pair;   // format of the current tensor
   for (int i = 0; i < e.n_down; ++i) {
     const int OH = down_dim(cur.H), OW = down_dim(cur.W);
-    float *o = (cur.p == s0) ? s1 : s0;
+    float *o = other(cur.p, s0, s1);
     isi_dst d = dst_nhwc(o, e.down[i].Cout, OH, OW);
-    int rc = conv2d_f32(&cs, nullptr, e.down[i].w, e.down[i].bias, nullptr, &d, B, cur.H, cur.W,
-                        e.down[i].Cout, 4, 4, 2, 1, 1 | pf | (cp ? ISI_CONV_IN0_PAIR : 0) | op, st, nullptr, nullptr,
+    int rc = conv2d_f32(&cs, nullptr, e.down[i].w, e.down[i].bias, nullptr, &d, B, cur.H, cur.W, e.down[i].Cout, 4, 4, 2, 1,
+                        1 | pf | (enc_reads_pair(i, in_pair, pairs) ? ISI_CONV_IN0_PAIR : 0) | op, st, nullptr, nullptr,
                         zero, zero_words);
     if (rc) return rc;
     zero = nullptr;
     cur = Act{o, e.down[i].Cout, OH, OW};
     cs = src_nhwc(cur.p, cur.C, cur.H, cur.W);
-    cp = pairs;
-  }
-  {
-    float *o = (e.n_res == 0) ? final_out : ((cur.p == s0) ? s1 : s0);
-    isi_dst d = dst_nhwc(o, e.conv3.Cout, cur.H, cur.W);
-    stack_pairs = res_stack_in_pairs(pairs, e.n_res, e.res3, B, cur.H, cur.W, e.conv3.Cout);
-    int rc = conv2d_f32(&cs, nullptr, e.conv3.w, e.conv3.bias, nullptr, &d, B, cur.H, cur.W,
-                        e.conv3.Cout, 3, 3, 1, 1, 1 | pf | (cp ? ISI_CONV_IN0_PAIR : 0) | ((e.n_res && !stack_pairs) ? 0 : op), st,
-                        nullptr, nullptr, zero, zero_words);
-    if (rc) return rc;
-    cur = Act{o, e.conv3.Cout, cur.H, cur.W};
   }
   // the fused residual block stages its input once per slice (not once per tap): it reads and writes fp32 between
   // blocks -- decoding the skip connection from pairs cost more than the conversion saved, 64 -> 72 us per block --
   // and only the stack's last block writes pairs, for the implicit-GEMM consumers of the encoder's output
-  int rc = run_res_stack(e.n_res, e.res3, e.res1, cur, B, s0, s1, hid, final_out, pf, stack_pairs, pairs, st);
+  const bool stack_pairs = res_stack_in_pairs(pairs, e.n_res, e.res3, B, cur.H, cur.W, e.conv3.Cout);
+  float *o = (e.n_res == 0) ? final_out : other(cur.p, s0, s1);
+  isi_dst d = dst_nhwc(o, e.conv3.Cout, cur.H, cur.W);
+  int rc = conv2d_f32(&cs, nullptr, e.conv3.w, e.conv3.bias, nullptr, &d, B, cur.H, cur.W, e.conv3.Cout, 3, 3, 1, 1,
+                      1 | pf | (enc_reads_pair(e.n_down, in_pair, pairs) ? ISI_CONV_IN0_PAIR : 0) |
+                      ((e.n_res && !stack_pairs) ? 0 : op), st, nullptr, nullptr, zero, zero_words);
   if (rc) return rc;
-  out = cur;
-  return ISI_OK;
+  cur = Act{o, e.conv3.Cout, cur.H, cur.W};
+  return run_res_stack(e.n_res, e.res3, e.res1, cur, B, s0, s1, hid, final_out, pf, stack_pairs, pairs, st);
 }
 
 // RosinalityDecoder (encoder_decoder.py:129-227).  Input = cat(in0, in1) on
@@ -213,52 +231,33 @@ int run_decoder(const isi_decoder_w &d, const isi_src &in0, const isi_src *in1, 
                 float *s0, float *s1, float *hid, const isi_dst &final_dst, int pf, bool in0_pair, bool in1_pair,
                 bool pairs, bool final_pair, hipStream_t st, const CodeTableJob *tab = nullptr) {
   Act cur{s0, d.conv3.Cout, H, W};
-  bool stack_pairs = false;
-  // format in which up[i] wants its input: pairs for the implicit-GEMM kernels and for the pair form of the
-  // few-channel kernel (64 input channels, <= 2 outputs, fp32 result: the last layer of the default model); fp32 for
-  // its exact-fp32 form
-  auto up_reads_pair = [&](int i, int Cin) {
-    if (!pairs) return false;
-    if (!convT_small_applicable(Cin, d.up[i].Cout)) return true;
-    const bool last = (i == d.n_up - 1);
-    return convT_small_pair_ok(Cin, d.up[i].Cout) && last && !final_pair && (pf & ISI_CONV_F16X3) && (pf & ISI_CONV_W16);
-  };
-  {
-    isi_dst dd = dst_nhwc(cur.p, cur.C, H, W);
-    stack_pairs = res_stack_in_pairs(pairs, d.n_res, d.res3, B, H, W, cur.C);
-    const bool op = d.n_res ? stack_pairs : (d.n_up ? up_reads_pair(0, cur.C) : final_pair);   // fp32 into a register-staged stack
-    int rc = tab && tab->t3
-                 ? vq_code_gather_f32(tab->ids, tab->t3, d.conv3.bias, cur.p, cur.C, op, /*relu*/ 1, tab->tu, tab->bias_u,
-                                      tab->out_u, tab->C_u, /*pair*/ 1, /*relu*/ 0, B, H, W, tab->K, st)
-                 : conv2d_f32(&in0, in1, d.conv3.w, d.conv3.bias, nullptr, &dd, B, H, W, cur.C, 3, 3, 1,
-                              1, 1 | pf | (in0_pair ? ISI_CONV_IN0_PAIR : 0) | (in1_pair ? ISI_CONV_IN1_PAIR : 0) |
-                              (op ? ISI_CONV_OUT_PAIR : 0), st);
-    if (rc) return rc;
-  }
-  bool cp = pairs;   // format of `cur` after the residual stack
-  {
-    cp = d.n_up ? up_reads_pair(0, cur.C) : final_pair;
-    int rc = run_res_stack(d.n_res, d.res3, d.res1, cur, B, s0, s1, hid, nullptr, pf, stack_pairs, cp, st);
-    if (rc) return rc;
-  }
+  auto reads_pair = [&](int i) { return i == d.n_up ? final_pair : pairs && up_read(d, i, final_pair, pf) != UP_F32_SMALL; };
+  const bool stack_pairs = res_stack_in_pairs(pairs, d.n_res, d.res3, B, H, W, cur.C);
+  bool cp = reads_pair(0);   // format of `cur` behind the residual stack
+  const isi_dst d3 = dst_nhwc(cur.p, cur.C, H, W);
+  const bool op3 = d.n_res ? stack_pairs : cp;   // fp32 into a register-staged stack
+  int rc = tab && tab->t3
+               ? vq_code_gather_f32(tab->ids, tab->t3, d.conv3.bias, cur.p, cur.C, op3, /*relu*/ 1, tab->tu, tab->bias_u,
+                                    tab->out_u, tab->C_u, /*pair*/ 1, /*relu*/ 0, B, H, W, tab->K, st)
+               : conv2d_f32(&in0, in1, d.conv3.w, d.conv3.bias, nullptr, &d3, B, H, W, cur.C, 3, 3, 1,
+                            1, 1 | pf | (in0_pair ? ISI_CONV_IN0_PAIR : 0) | (in1_pair ? ISI_CONV_IN1_PAIR : 0) |
+                            (op3 ? ISI_CONV_OUT_PAIR : 0), st);
+  if (rc) return rc;
+  rc = run_res_stack(d.n_res, d.res3, d.res1, cur, B, s0, s1, hid, nullptr, pf, stack_pairs, cp, st);
+  if (rc) return rc;
   for (int i = 0; i < d.n_up; ++i) {
     const bool last = (i == d.n_up - 1);
     isi_src s = src_nhwc(cur.p, cur.C, cur.H, cur.W);
-    float *o = (cur.p == s0) ? s1 : s0;
+    float *o = other(cur.p, s0, s1);
     // the last two transposed convolutions as one producer / consumer pair (convT_pair_f16.hip, YP mode): the
     // [B, 2H, 2W, 64] activation between them is never written
-    if (i == d.n_up - 2 && cp && !final_pair && (pf & ISI_CONV_F16X3) && (pf & ISI_CONV_W16) &&
-        decoder_tail_ok(cur.C, d.up[i].Cout, d.up[i + 1].Cout)) {
-      int rc = decoder_tail_f32(cur.p, d.up[i].w, d.up[i].bias, d.up[i + 1].w, d.up[i + 1].bias, o, &final_dst, B, cur.H,
-                                cur.W, cur.C, d.up[i].Cout, d.up[i + 1].Cout, st);
-      if (rc) return rc;
-      return ISI_OK;
-    }
+    if (i == d.n_up - 2 && cp && !final_pair && f16_pieces(pf) && decoder_tail_ok(cur.C, d.up[i].Cout, d.up[i + 1].Cout))
+      return decoder_tail_f32(cur.p, d.up[i].w, d.up[i].bias, d.up[i + 1].w, d.up[i + 1].bias, o, &final_dst, B, cur.H,
+                              cur.W, cur.C, d.up[i].Cout, d.up[i + 1].Cout, st);
     isi_dst dd = last ? final_dst : dst_nhwc(o, d.up[i].Cout, 2 * cur.H, 2 * cur.W);
-    const bool op = last ? final_pair : up_reads_pair(i + 1, d.up[i].Cout);
-    int rc = conv_transpose2d_k4s2_f32(&s, d.up[i].w, d.up[i].bias, &dd, B, cur.H, cur.W,
-                                       d.up[i].Cout, (last ? 0 : 1) | pf | (cp ? ISI_CONV_IN0_PAIR : 0) |
-                                       (op ? ISI_CONV_OUT_PAIR : 0), st);
+    const bool op = reads_pair(i + 1);
+    rc = conv_transpose2d_k4s2_f32(&s, d.up[i].w, d.up[i].bias, &dd, B, cur.H, cur.W, d.up[i].Cout,
+                                   (last ? 0 : 1) | pf | (cp ? ISI_CONV_IN0_PAIR : 0) | (op ? ISI_CONV_OUT_PAIR : 0), st);
     if (rc) return rc;
     cp = op;
     cur = Act{o, d.up[i].Cout, 2 * cur.H, 2 * cur.W};
@@ -277,24 +276,18 @@ bool stack_fusable(int C, int n_res, const isi_conv_w *res3) {
 }
 bool encoder_pairs_ok(const isi_encoder_w &e, int Cin, bool in_pair) {
   int C = Cin;
-  bool cp = in_pair;
   for (int i = 0; i < e.n_down; ++i) {
-    if (cp && !conv_pair_sources_ok(C, 0, e.down[i].Cout, 16)) return false;
+    if (enc_reads_pair(i, in_pair, true) && !conv_pair_sources_ok(C, 0, e.down[i].Cout, 16)) return false;
     C = e.down[i].Cout;
-    cp = true;
   }
-  if (cp && !conv_pair_sources_ok(C, 0, e.conv3.Cout, 9)) return false;
+  if (enc_reads_pair(e.n_down, in_pair, true) && !conv_pair_sources_ok(C, 0, e.conv3.Cout, 9)) return false;
   return stack_fusable(e.conv3.Cout, e.n_res, e.res3);
 }
-bool decoder_pairs_ok(const isi_decoder_w &d, int C0, int C1, bool in0_pair, bool in1_pair) {
+bool decoder_pairs_ok(const isi_decoder_w &d, int C0, int C1, bool in0_pair, bool in1_pair, bool final_pair, int pf) {
   if ((in0_pair || in1_pair) && !conv_pair_sources_ok(C0, C1, d.conv3.Cout, 9)) return false;
   if (!stack_fusable(d.conv3.Cout, d.n_res, d.res3)) return false;
-  int C = d.conv3.Cout;
-  for (int i = 0; i < d.n_up; ++i) {
-    // the few-channel kernel is handed fp32; the implicit-GEMM phases read pairs
-    if (!convT_small_applicable(C, d.up[i].Cout) && !conv_pair_sources_ok(C, 0, d.up[i].Cout, 4)) return false;
-    C = d.up[i].Cout;
-  }
+  for (int i = 0; i < d.n_up; ++i)   // (the few-channel kernel takes either format as it comes)
+    if (up_read(d, i, final_pair, pf) == UP_PAIR_IGEMM && !conv_pair_sources_ok(up_cin(d, i), 0, d.up[i].Cout, 4)) return false;
   return d.n_up >= 1;
 }
 bool pairs_eligible(const isi_vqvae_w &w) {
@@ -304,269 +297,250 @@ bool pairs_eligible(const isi_vqvae_w &w) {
   // kernel does not
   if (knobs().no_conv_first || w.in_channel != 2 || w.enc_b.n_down < 1 ||
       (w.enc_b.down[0].Cout != 32 && w.enc_b.down[0].Cout != 64)) return false;
-  const int D = w.quantize_t.D;
+  const int D = w.quantize_t.D, pf = product_flags(w, true);
   if (w.quantize_b.D != D) return false;
   if (!encoder_pairs_ok(w.enc_b, w.in_channel, false)) return false;
   if (!encoder_pairs_ok(w.enc_t, w.enc_b.conv3.Cout, true)) return false;
   if (!conv_pair_sources_ok(w.enc_t.conv3.Cout, 0, D, 1)) return false;                 // quantize_conv_t
-  if (!decoder_pairs_ok(w.dec_t, D, 0, true, false)) return false;      // reads the pair copy of quant_t
-  if (convT_small_applicable(w.dec_t.n_up == 1 ? w.dec_t.conv3.Cout : w.dec_t.up[w.dec_t.n_up - 2].Cout,
-                             w.dec_t.up[w.dec_t.n_up - 1].Cout)) return false;         // its output is written as pairs
-  if (!conv_pair_sources_ok(w.dec_t.up[w.dec_t.n_up - 1].Cout, w.enc_b.conv3.Cout, D, 1)) return false;   // quantize_conv_b
+  if (!decoder_pairs_ok(w.dec_t, D, 0, true, false, true, pf)) return false;            // reads the pair copy of quant_t
+  if (up_read(w.dec_t, w.dec_t.n_up - 1, true, pf) != UP_PAIR_IGEMM) return false;      // its output is written as pairs
+  if (!conv_pair_sources_ok(dec_t_channels(w), w.enc_b.conv3.Cout, D, 1)) return false; // quantize_conv_b
   for (int i = 0; i < w.n_upsample; ++i) {
     if (convT_small_applicable(w.upsample[i].Cin, w.upsample[i].Cout)) return false;
     if (!conv_pair_sources_ok(w.upsample[i].Cin, 0, w.upsample[i].Cout, 4)) return false;
   }
   if (w.no_quantize) return false;   // the pair copies of quant_t / quant_b are made behind the codebook searches
-  return decoder_pairs_ok(w.dec, D, D, true, true);
+  return decoder_pairs_ok(w.dec, D, D, true, true, false, pf);
 }
 
-int run_quantizer(const isi_codebook_w &cb, const float *z, int64_t N, int64_t *idx, float *q,
-                  int32_t *counts, float *sse_part, float *scalars2, int flags, hipStream_t st) {
-  if (int rc0 = vq_zero_counts(counts, cb.K, st)) return rc0;
-  // With ISI_CONV_F16X3 (the split-f16 mode) the K distances are computed on the f16 matrix pipe only to pick two
-  // candidates; the decision between them is taken in fp32 (vq_nearest.hip) -- the same search as the fused kernel's.
-  int rc = vq_nearest_f32(z, cb.codes_kd, cb.e2, idx, q, counts, sse_part, N, cb.D, cb.K, flags, st);
-  if (rc) return rc;
-  return vq_finalize_f32(sse_part, vq_num_partials(N), counts, cb.K, N, cb.D, scalars2, st);
-}
-
-// UnquantizedBottleneck.forward (bottleneck.py:107-119): diff = 0, perplexity = inf
-int unquantized_scalars(float *scalars2, hipStream_t st) { return vq_unquantized_scalars(scalars2, st); }   // (a kernel: no memset nodes)
-
-// quantize_conv (1x1) + codebook search in ONE launch (vq_nearest.hip: z stays in registers), with the pair-format
-// copy of q written alongside.  `w1x1` = the 1x1 layer (its packed weight is followed by the blocked pair copy).
-int run_quantizer_fused(const isi_codebook_w &cb, const isi_conv_w &w1x1, const isi_src &a, const isi_src *b, int B, int H,
-                        int W, int64_t *idx, float *q, float *q_pair, int32_t *counts, float *sse_part, float *scalars2,
-                        float *wfrag_ws, hipStream_t st, bool finalize = true, bool frag_packed = false) {
-  const int Kpad = (int)round_up((size_t)w1x1.Cin, kBK);
-  // frag_packed (isi_vqvae_w.w16 == 2): the weight's third section is its fragment-major copy and the caller has zeroed
-  // both levels' histograms with one launch -- no pre-kernel in front of the search
-  int rc = vq_conv1x1_nearest_f32(&a, b, w1x1.w + (size_t)w1x1.Cout * Kpad, w1x1.bias, cb.codes_kd, cb.e2, idx, q, q_pair,
-                                  counts, sse_part, wfrag_ws, B, H, W, cb.D, cb.K, st, /*zero_counts*/ !frag_packed, nullptr,
-                                  frag_packed ? w1x1.w + (size_t)2 * w1x1.Cout * Kpad : nullptr,
-                                  knobs().no_setup_fusion ? nullptr : cb.planes);
-  if (rc || !finalize) return rc;     // (finalize = false: the caller finishes both levels with one launch, vq_finalize2_f32)
-  const int64_t N = (int64_t)B * H * W;
-  return vq_finalize_f32(sse_part, vq_num_partials(N), counts, cb.K, N, cb.D, scalars2, st);
-}
-
-int plan(const isi_vqvae_w &w, int mode, const float *x, int B, int H, int W,
-         const isi_vqvae_out *out, Bump &ws, hipStream_t st) {
-  Shapes sh;
-  if (!compute_shapes(w, B, H, W, sh)) return invalid("vqvae: input too small or odd top/bottom grid");
+// ---- which kernels a call runs: derived once, read by the launch code below
+struct Route {
+  int pf_enc, pf_dec;    // product flags of the layers that feed the quantisers / of the final decoder and upsample
+  bool pairs;            // internal activations as split-f16 pairs (isi_hip.h: ISI_CONV_*_PAIR)
+  bool fuse_t, fuse_b;   // quantize_conv_{t,b} fused into its codebook search (vq_nearest.hip: z stays in registers)
+  bool frag_packed;      // the 1x1 weights carry their fragment-major copy: no pre-kernel in front of a fused search
+  bool fuse_zero;        // both histograms zeroed by the first encoder launch instead of a launch of their own
+  bool tab3, tabU;       // dec_t.conv3 / upsample[0] as sums of pack-time table rows (code_tables.hip)
+  bool q_t_pair_read;    // somebody reads the pair copy of quant_t: dec_t.conv3 or upsample[0]
+};
+Route make_route(const isi_vqvae_w &w, int mode) {
+  const bool enc = mode & ISI_MODE_ENCODE, dec = mode & ISI_MODE_DECODE;
   const int D = w.quantize_t.D;
-  const bool dry = ws.dry;
-  if (w.n_upsample != w.dec_t.n_up) return invalid("vqvae: upsample depth must equal dec_t depth");
+  Route r;
+  r.pf_enc = product_flags(w, true); r.pf_dec = product_flags(w, false);
+  r.pairs = pairs_eligible(w);
+  // the pair pipeline only (pair8 sources, blocked weights); a level whose shape the fused kernel does not take runs
+  // as two launches beside a fused one
+  const bool fuse_vq = r.pairs && !w.no_quantize && !knobs().no_vq_fusion;
+  r.fuse_t = fuse_vq && vq_conv1x1_fusable(w.enc_t.conv3.Cout, 0, D, w.quantize_t.K);
+  r.fuse_b = fuse_vq && vq_conv1x1_fusable(dec_t_channels(w), w.enc_b.conv3.Cout, D, w.quantize_b.K);
+  r.frag_packed = fuse_vq && w.w16 == 2 && enc;
+  // (the workspace is the caller's and arrives with any content: zeroed per call.  ISI_NO_SETUP_FUSION: the zeroing
+  // launch, for the tests' A/B)
+  r.fuse_zero = r.frag_packed && !knobs().no_setup_fusion;
+  // The tables serve the pair pipeline of a call that produces the top codes itself.  encode() and forward() take the
+  // same route to id_b; the choice does not depend on the fusion or flush switches (ids exist on all of those paths).
+  const bool tab_ok = r.pairs && !w.no_quantize && w.precision == 4 && !knobs().no_code_tables && enc && D % 4 == 0;
+  r.tab3 = tab_ok && w.code_table_conv3 && w.dec_t.conv3.Cin == D && w.dec_t.conv3.Cout % 8 == 0;
+  r.tabU = tab_ok && dec && w.code_table_upsample && w.n_upsample >= 1 && w.upsample[0].Cin == D && w.upsample[0].Cout % 8 == 0;
+  r.q_t_pair_read = !r.tab3 || (dec && !r.tabU);
+  return r;
+}
 
-  float *s0 = ws.floats(sh.max_act);
-  float *s1 = ws.floats(sh.max_act);
+// ---- the workspace
+struct Buffers {
+  float *s0, *s1, *hid;          // ping-pong activations, hidden tensor of an unfused residual block
+  float *enc_b, *enc_t, *dec_t, *zbuf, *up, *up2;
+  float *q_t, *q_b;              // the quantised maps where the caller takes none
+  float *q_t_pair, *q_b_pair;    // their pair-format copies: what the pair pipeline's convolutions read
+  int64_t *id_t, *id_b;
+  int32_t *counts;               // [2][Kmax]: bottom, top (side by side: one launch zeroes both)
+  int Kmax;
+  float *sse_part, *sse_top;     // sse_top: the top level's partial sums where its finish waits for the bottom search
+  float *wfrag, *scal;
+  int32_t *counts_top() const { return counts + Kmax; }
+};
+Buffers carve(const isi_vqvae_w &w, const Shapes &sh, int B, Bump &ws) {
+  const int D = w.quantize_t.D;
+  const size_t top = (size_t)B * sh.Ht * sh.Wt, bottom = (size_t)B * sh.Hb * sh.Wb, cropped = (size_t)B * sh.Hb * sh.Wq;
+  Buffers b;
+  b.s0 = ws.floats(sh.max_act); b.s1 = ws.floats(sh.max_act);
   const int Rmax = std::max({w.enc_b.n_res ? w.enc_b.res3[0].Cout : 0, w.enc_t.n_res ? w.enc_t.res3[0].Cout : 0,
                              w.dec_t.n_res ? w.dec_t.res3[0].Cout : 0, w.dec.n_res ? w.dec.res3[0].Cout : 0, 1});
-  float *hid = ws.floats((size_t)B * sh.Hb * sh.Wb * Rmax);
-  float *enc_b = ws.floats((size_t)B * sh.Hb * sh.Wb * sh.Cb);
-  float *enc_t = ws.floats((size_t)B * sh.Ht * sh.Wt * w.enc_t.conv3.Cout);
-  float *dec_t = ws.floats((size_t)B * sh.Hb * sh.Wb * D);
-  float *zbuf = ws.floats((size_t)B * sh.Hb * sh.Wb * D);
-  float *up = ws.floats((size_t)B * sh.Hb * sh.Wb * D);
-  float *up2 = ws.floats((size_t)B * sh.Hb * sh.Wb * D);
-  float *q_t_ws = ws.floats((size_t)B * sh.Ht * sh.Wt * D);
-  float *q_b_ws = ws.floats((size_t)B * sh.Hb * sh.Wq * D);
-  // pair-format copies of the quantised maps: what the pair pipeline's convolutions read (the API tensors stay fp32)
-  float *q_t_pair = ws.floats((size_t)B * sh.Ht * sh.Wt * D);
-  float *q_b_pair = ws.floats((size_t)B * sh.Hb * sh.Wq * D);
-  int64_t *id_t_ws = static_cast<int64_t *>(ws.take((size_t)B * sh.Ht * sh.Wt * sizeof(int64_t)));
-  int64_t *id_b_ws = static_cast<int64_t *>(ws.take((size_t)B * sh.Hb * sh.Wq * sizeof(int64_t)));
-  const int Kmax = std::max(w.quantize_t.K, w.quantize_b.K);
-  // (the two histograms side by side: one launch zeroes both when the searches bring no pre-kernel of their own)
-  int32_t *counts = static_cast<int32_t *>(ws.take((size_t)2 * Kmax * sizeof(int32_t)));
-  float *sse_part = ws.floats(256);
-  // the top level's statistics stay alive until the bottom search is done: one launch finishes both (fused path)
-  int32_t *counts_top = counts + Kmax;
-  float *sse_top = ws.floats(256);
-  float *wfrag_ws = ws.floats((size_t)D * round_up((size_t)(w.quantize_conv_b.Cin > w.quantize_conv_t.Cin ? w.quantize_conv_b.Cin
-                                                                                                            : w.quantize_conv_t.Cin), kBK));
-  float *scal_ws = ws.floats(8);
-  if (dry) return ISI_OK;
-  if (ws.off > ws.cap) {
-    set_last_error("vqvae: workspace too small");
-    return ISI_E_WORKSPACE;
-  }
+  b.hid = ws.floats(bottom * Rmax);
+  b.enc_b = ws.floats(bottom * sh.Cb);
+  b.enc_t = ws.floats(top * w.enc_t.conv3.Cout);
+  b.dec_t = ws.floats(bottom * D);
+  b.zbuf = ws.floats(bottom * D);
+  b.up = ws.floats(bottom * D); b.up2 = ws.floats(bottom * D);
+  b.q_t = ws.floats(top * D); b.q_b = ws.floats(cropped * D);
+  b.q_t_pair = ws.floats(top * D); b.q_b_pair = ws.floats(cropped * D);
+  b.id_t = static_cast<int64_t *>(ws.take(top * sizeof(int64_t)));
+  b.id_b = static_cast<int64_t *>(ws.take(cropped * sizeof(int64_t)));
+  b.Kmax = std::max(w.quantize_t.K, w.quantize_b.K);
+  b.counts = static_cast<int32_t *>(ws.take((size_t)2 * b.Kmax * sizeof(int32_t)));
+  b.sse_part = ws.floats(256); b.sse_top = ws.floats(256);
+  b.wfrag = ws.floats((size_t)D * round_up((size_t)std::max(w.quantize_conv_b.Cin, w.quantize_conv_t.Cin), kBK));
+  b.scal = ws.floats(8);
+  return b;
+}
 
-  float *quant_t = out->quant_t ? out->quant_t : q_t_ws;
-  float *quant_b = out->quant_b ? out->quant_b : q_b_ws;
-  int64_t *id_t = out->id_t ? out->id_t : id_t_ws;
-  int64_t *id_b = out->id_b ? out->id_b : id_b_ws;
-  float *scal = out->scalars ? out->scalars : scal_ws;
-  int rc;
-  // precision: 0 all fp32 | 1 decoder split-bf16 (x3) | 2 everything x3 | 3 index-feeding layers six-term
-  // split (x6: fp32-grade products), decoder x3 | 4 split-f16 everywhere (fp32-grade products, f16 range)
-  const int f16 = ISI_CONV_F16X3 | (w.w16 ? ISI_CONV_W16 : 0);
-  const int pf_enc = w.precision == 4 ? f16 : w.precision == 3 ? ISI_CONV_BF16X6
-                   : w.precision == 2 ? ISI_CONV_BF16X3 : 0;   // feeds the quantisers
-  const bool pairs = pairs_eligible(w);   // internal activations as split-f16 pairs (isi_hip.h: ISI_CONV_*_PAIR)
-  const int pf_dec = w.precision == 4 ? f16 : w.precision >= 1 ? ISI_CONV_BF16X3 : 0;   // final decoder + upsample
-  // quantize_conv_{t,b} fused into the codebook searches: the pair pipeline only (pair8 sources, blocked weights)
-  const bool fuse_vq = pairs && !w.no_quantize && !knobs().no_vq_fusion;
-  const bool frag_packed = fuse_vq && w.w16 == 2 && (mode & ISI_MODE_ENCODE);
-  // dec_t's first convolution and upsample[0] as sums of pack-time table rows (code_tables.hip): the pair pipeline of a
-  // call that produces the top codes itself.  encode() and forward() take the same route to id_b; the choice does not
-  // depend on the fusion or flush switches (ids exist on all of those paths).
-  const bool tab_ok = pairs && !w.no_quantize && w.precision == 4 && !knobs().no_code_tables && (mode & ISI_MODE_ENCODE) && D % 4 == 0;
-  const bool tab3 = tab_ok && w.code_table_conv3 && w.dec_t.conv3.Cin == D && w.dec_t.conv3.Cout % 8 == 0;
-  const bool tabU = tab_ok && (mode & ISI_MODE_DECODE) && w.code_table_upsample && w.n_upsample >= 1 && w.upsample[0].Cin == D &&
-                    w.upsample[0].Cout % 8 == 0;
-  const bool q_t_pair_read = !tab3 || ((mode & ISI_MODE_DECODE) && !tabU);   // by dec_t.conv3 / by upsample[0]
-  // Both histograms are zeroed by the first encoder launch (its workgroup 0: conv_first_f32.hip) instead of a launch of
-  // their own.  The workspace is the caller's and arrives with any content: zeroed per call.
-  // (ISI_NO_SETUP_FUSION: the zeroing launch, for the tests' A/B.)
-  const bool fuse_zero = frag_packed && !knobs().no_setup_fusion;
-  if (frag_packed && !fuse_zero) {
-    rc = vq_zero_counts(counts, 2 * Kmax, st);
-    if (rc) return rc;
-  }
-  bool bottom_pair_done = false;
-  bool top_deferred = false;      // top-level scalars not written yet (fused path)
-  int64_t N_top = 0;
+// ---- refusals: all of them before the first launch.  check_shapes: what model and shape decide (the size query's too)
+int check_shapes(const isi_vqvae_w &w, int B, int H, int W, Shapes &sh) {
+  if (!compute_shapes(w, B, H, W, sh)) return invalid("vqvae: input too small or odd top/bottom grid");
+  if (w.n_upsample != w.dec_t.n_up) return invalid("vqvae: upsample depth must equal dec_t depth");
+  return ISI_OK;
+}
+int check_call(const isi_vqvae_w &w, int mode, const float *x, const isi_vqvae_out &out, const Shapes &sh, const Bump &ws) {
+  if (ws.off > ws.cap) return set_last_error("vqvae: workspace too small"), ISI_E_WORKSPACE;
+  if ((mode & ISI_MODE_ENCODE) && !x) return invalid("vqvae: x is null");
+  if (!(mode & ISI_MODE_DECODE)) return ISI_OK;
+  if (!out.dec) return invalid("vqvae: dec output is null");
+  if (!(mode & ISI_MODE_ENCODE) && (!out.quant_t || !out.quant_b)) return invalid("vqvae: decode needs quant_t and quant_b");
+  // (a one-column bottom grid under a top grid that up-samples to two)
+  if (up_dim(sh.Ht, w.n_upsample) != sh.Hb || up_dim(sh.Wt, w.n_upsample) != sh.Wq)
+    return invalid("vqvae: upsampled top grid != bottom grid");
+  return ISI_OK;
+}
 
-  if (mode & ISI_MODE_ENCODE) {
-    if (!x) return invalid("vqvae: x is null");
-    Act eb, et;
-    rc = run_encoder(w.enc_b, src_nchw(x, w.in_channel, H, W), B, H, W, s0, s1, hid, enc_b, eb, pf_enc, false, pairs, st,
-                     fuse_zero ? counts : nullptr, 2 * Kmax);
-    if (rc) return rc;
-    rc = run_encoder(w.enc_t, src_nhwc(eb.p, eb.C, eb.H, eb.W), B, eb.H, eb.W, s0, s1, hid, enc_t, et, pf_enc, pairs,
-                     pairs, st);
-    if (rc) return rc;
-    // quantize_conv_t + quantize_t (vqvae.py:260-263)
-    {
-      isi_src s = src_nhwc(et.p, et.C, et.H, et.W);
-      if (fuse_vq && vq_conv1x1_fusable(et.C, 0, D, w.quantize_t.K)) {
-        // (no fp32 map where the caller takes none and this call decodes from the pair copies)
-        rc = run_quantizer_fused(w.quantize_t, w.quantize_conv_t, s, nullptr, B, et.H, et.W, id_t,
-                                 (out->quant_t || !(mode & ISI_MODE_DECODE)) ? quant_t : nullptr, q_t_pair,
-                                 counts_top, sse_top, scal + 0, wfrag_ws, st, /*finalize*/ false, frag_packed);
-        if (rc) return rc;
-        top_deferred = true;
-        N_top = (int64_t)B * et.H * et.W;
-        goto top_done;
-      }
-      // UnquantizedBottleneck (bottleneck.py:107-119): the 1x1 convolution's output IS quant_t
-      isi_dst d = dst_nhwc(w.no_quantize ? quant_t : zbuf, D, et.H, et.W);
-      rc = conv2d_f32(&s, nullptr, w.quantize_conv_t.w, w.quantize_conv_t.bias, nullptr, &d, B, et.H,
-                      et.W, D, 1, 1, 1, 0, pf_enc | (pairs ? ISI_CONV_IN0_PAIR : 0), st);
-      if (rc) return rc;
-      rc = w.no_quantize ? unquantized_scalars(scal + 0, st)
-                         : run_quantizer(w.quantize_t, zbuf, (int64_t)B * et.H * et.W, id_t, quant_t, counts_top,
-                                         sse_part, scal + 0, pf_enc & ISI_CONV_F16X3, st);
-      if (rc) return rc;
-      if (pairs && q_t_pair_read) {
-        rc = pair_encode_f32(quant_t, q_t_pair, (int64_t)B * et.H * et.W * D, st);
-        if (rc) return rc;
-      }
-    }
-  top_done:;
-    // dec_t (vqvae.py:265): [B,Ht,Wt,D] -> [B,Hb,2^n Wt,D]
-    int Wd = et.W;
-    for (int i = 0; i < w.dec_t.n_up; ++i) Wd *= 2;
-    {
-      isi_src s = src_nhwc(pairs ? q_t_pair : quant_t, D, et.H, et.W);
-      isi_dst d = dst_nhwc(dec_t, w.dec_t.up[w.dec_t.n_up - 1].Cout, sh.Hb, Wd);
-      // one gather launch right behind the top search: the conv3 items, then the upsample items (both read only id_t)
-      const CodeTableJob job{id_t, w.quantize_t.K, tab3 ? w.code_table_conv3 : nullptr, tabU ? w.code_table_upsample : nullptr,
-                             w.upsample[0].bias, up, w.upsample[0].Cout};
-      if (tabU && !tab3) {
-        rc = vq_code_gather_f32(id_t, nullptr, nullptr, nullptr, 0, 0, 0, job.tu, job.bias_u, job.out_u, job.C_u, 1, 0, B, et.H,
-                                et.W, job.K, st);
-        if (rc) return rc;
-      }
-      rc = run_decoder(w.dec_t, s, nullptr, B, et.H, et.W, s0, s1, hid, d, pf_enc, pairs, false, pairs, pairs, st,
-                       tab3 ? &job : nullptr);
-      if (rc) return rc;
-    }
-    // quantize_conv_b on cat([dec_t, enc_b]) cropped to Wq (vqvae.py:266-273)
-    {
-      const int Cd = w.dec_t.up[w.dec_t.n_up - 1].Cout;
-      isi_src a = src_nhwc(dec_t, Cd, sh.Hb, sh.Wq, Wd);
-      isi_src b = src_nhwc(eb.p, eb.C, sh.Hb, sh.Wq, eb.W);
-      if (fuse_vq && vq_conv1x1_fusable(Cd, eb.C, D, w.quantize_b.K)) {
-        rc = run_quantizer_fused(w.quantize_b, w.quantize_conv_b, a, &b, B, sh.Hb, sh.Wq, id_b,
-                                 (out->quant_b || !(mode & ISI_MODE_DECODE)) ? quant_b : nullptr, q_b_pair, counts,
-                                 sse_part, scal + 2, wfrag_ws, st, /*finalize*/ !top_deferred, frag_packed);
-        if (rc) return rc;
-        if (top_deferred) {
-          const int64_t N_b = (int64_t)B * sh.Hb * sh.Wq;
-          rc = vq_finalize2_f32(sse_top, vq_num_partials(N_top), counts_top, w.quantize_t.K, N_top, sse_part,
-                                vq_num_partials(N_b), counts, w.quantize_b.K, N_b, D, scal, st);
-          if (rc) return rc;
-          top_deferred = false;
-          bottom_pair_done = true;
-          goto scalars_done;
-        }
-        bottom_pair_done = true;
-        goto bottom_done;
-      }
-      if (top_deferred) {      // (the bottom level takes the two-launch path: finish the top level on its own)
-        rc = vq_finalize_f32(sse_top, vq_num_partials(N_top), counts_top, w.quantize_t.K, N_top, D, scal + 0, st);
-        if (rc) return rc;
-        top_deferred = false;
-      }
-      isi_dst d = dst_nhwc(w.no_quantize ? quant_b : zbuf, D, sh.Hb, sh.Wq);
-      rc = conv2d_f32(&a, &b, w.quantize_conv_b.w, w.quantize_conv_b.bias, nullptr, &d, B, sh.Hb,
-                      sh.Wq, D, 1, 1, 1, 0, pf_enc | (pairs ? ISI_CONV_IN0_PAIR | ISI_CONV_IN1_PAIR : 0), st);
-      if (rc) return rc;
-      rc = w.no_quantize ? unquantized_scalars(scal + 2, st)
-                         : run_quantizer(w.quantize_b, zbuf, (int64_t)B * sh.Hb * sh.Wq, id_b, quant_b, counts,
-                                         sse_part, scal + 2, pf_enc & ISI_CONV_F16X3, st);
-      if (rc) return rc;
-    }
-  bottom_done:;
-    rc = vq_scalars_sum_f32(scal, st);       // scalars[4] = diff_t + diff_b
-    if (rc) return rc;
-  scalars_done:;
+// ---- one quantisation level: quantize_conv (1x1) over cat(a, b) and the codebook search (vqvae.py:260-263, 266-275)
+struct Level {
+  const isi_codebook_w &cb;
+  const isi_conv_w &w1x1;          // (its packed weight is followed by the blocked pair copy, then by the fragments)
+  isi_src a;
+  const isi_src *b;                // optional second source
+  int H, W;
+  int64_t *ids;
+  float *q;                        // the fp32 map: the caller's or the workspace's
+  bool q_unread;                   // nobody reads it: a fused search, which writes the pair copy itself, skips it
+  float *q_pair;
+  int32_t *counts;
+  float *sse;                      // partial sums of the squared error
+  float *scalars2;                 // diff, perplexity
+};
+int finish_level(const Level &l, int B, hipStream_t st) {
+  const int64_t N = (int64_t)B * l.H * l.W;
+  return vq_finalize_f32(l.sse, vq_num_partials(N), l.counts, l.cb.K, N, l.cb.D, l.scalars2, st);
+}
+// `fused`: one launch, with the pair-format copy of q written alongside; `finish` = false then leaves the statistics to
+// the caller (one launch finishes both levels, vq_finalize2_f32).  Not fused: 1x1 convolution, then the search, finished
+// at once; UnquantizedBottleneck (bottleneck.py:107-119): the convolution's output IS q, diff = 0, perplexity = inf.
+int quantize_level(const isi_vqvae_w &w, const Route &r, const Level &l, int B, bool fused, bool finish, const Buffers &bf,
+                   hipStream_t st) {
+  const int D = l.cb.D;
+  if (fused) {
+    const int Kpad = (int)round_up((size_t)l.w1x1.Cin, kBK);
+    // frag_packed: the caller has zeroed both levels' histograms -- no pre-kernel in front of the search
+    int rc = vq_conv1x1_nearest_f32(&l.a, l.b, l.w1x1.w + (size_t)l.w1x1.Cout * Kpad, l.w1x1.bias, l.cb.codes_kd, l.cb.e2, l.ids,
+                                    l.q_unread ? nullptr : l.q, l.q_pair, l.counts, l.sse, bf.wfrag, B, l.H, l.W, D, l.cb.K, st,
+                                    /*zero_counts*/ !r.frag_packed, nullptr,
+                                    r.frag_packed ? l.w1x1.w + (size_t)2 * l.w1x1.Cout * Kpad : nullptr,
+                                    knobs().no_setup_fusion ? nullptr : l.cb.planes);
+    return (rc || !finish) ? rc : finish_level(l, B, st);
   }
-  if (pairs && (mode & ISI_MODE_DECODE)) {
-    // forward: quant_t was encoded behind its search (dec_t reads it); decode: both maps arrive as fp32
-    if (!(mode & ISI_MODE_ENCODE)) {
-      rc = pair_encode_f32(quant_t, q_t_pair, (int64_t)B * sh.Ht * sh.Wt * D, st);
-      if (rc) return rc;
-    }
-    if (!bottom_pair_done) {
-      rc = pair_encode_f32(quant_b, q_b_pair, (int64_t)B * sh.Hb * sh.Wq * D, st);
-      if (rc) return rc;
-    }
-  }
+  isi_dst d = dst_nhwc(w.no_quantize ? l.q : bf.zbuf, D, l.H, l.W);
+  int rc = conv2d_f32(&l.a, l.b, l.w1x1.w, l.w1x1.bias, nullptr, &d, B, l.H, l.W, D, 1, 1, 1, 0,
+                      r.pf_enc | (r.pairs ? ISI_CONV_IN0_PAIR | (l.b ? ISI_CONV_IN1_PAIR : 0) : 0), st);
+  if (rc) return rc;
+  if (w.no_quantize) return vq_unquantized_scalars(l.scalars2, st);   // (a kernel: no memset nodes)
+  if ((rc = vq_zero_counts(l.counts, l.cb.K, st))) return rc;
+  // With ISI_CONV_F16X3 (the split-f16 mode) the K distances are computed on the f16 matrix pipe only to pick two
+  // candidates; the decision between them is taken in fp32 (vq_nearest.hip) -- the same search as the fused kernel's.
+  rc = vq_nearest_f32(bf.zbuf, l.cb.codes_kd, l.cb.e2, l.ids, l.q, l.counts, l.sse, (int64_t)B * l.H * l.W, D, l.cb.K,
+                      r.pf_enc & ISI_CONV_F16X3, st);
+  return rc ? rc : finish_level(l, B, st);
+}
 
-  if (mode & ISI_MODE_DECODE) {
-    if (!out->dec) return invalid("vqvae: dec output is null");
-    if (!(mode & ISI_MODE_ENCODE) && (!out->quant_t || !out->quant_b))
-      return invalid("vqvae: decode needs quant_t and quant_b");
-    // upsample_top_to_bottom: plain transposed convs, no ReLU (vqvae.py:183-201,281)
-    const float *cur = pairs ? q_t_pair : quant_t;
-    int h = sh.Ht, ww = sh.Wt;
-    for (int i = 0; i < w.n_upsample; ++i) {
-      float *o = (i % 2 == 0) ? up : up2;
-      if (i == 0 && tabU) {       // written by the gather launch of the ENCODE block
-        cur = o; h *= 2; ww *= 2;
-        continue;
-      }
+struct Call {   // what the launch code of one call shares
+  const isi_vqvae_w &w;
+  int mode, B;
+  Shapes sh;
+  Route r;
+  Buffers b;
+  float *quant_t, *quant_b, *scal;   // the caller's tensors, or the workspace's where it takes none
+  int64_t *id_t, *id_b;
+  hipStream_t st;
+};
+
+// VQVAE.encode (vqvae.py:251-278)
+int run_encode(const Call &c, const float *x, int H, int W, const isi_vqvae_out &out) {
+  const isi_vqvae_w &w = c.w;
+  const Route &r = c.r;
+  const Buffers &b = c.b;
+  const Shapes &sh = c.sh;
+  const int D = w.quantize_t.D, B = c.B, Cd = dec_t_channels(w), Wd = up_dim(sh.Wt, w.dec_t.n_up);
+  const bool decodes = c.mode & ISI_MODE_DECODE, both_fused = r.fuse_t && r.fuse_b;
+  int rc = run_encoder(w.enc_b, src_nchw(x, w.in_channel, H, W), B, H, W, b.s0, b.s1, b.hid, b.enc_b, r.pf_enc, false, r.pairs,
+                       c.st, r.fuse_zero ? b.counts : nullptr, 2 * b.Kmax);
+  if (rc) return rc;
+  rc = run_encoder(w.enc_t, src_nhwc(b.enc_b, sh.Cb, sh.Hb, sh.Wb), B, sh.Hb, sh.Wb, b.s0, b.s1, b.hid, b.enc_t, r.pf_enc,
+                   r.pairs, r.pairs, c.st);
+  if (rc) return rc;
+  // the top level.  Fused, its statistics wait in sse_top until the bottom search is done; in two launches they go
+  // through the slot both levels share
+  const Level top{w.quantize_t, w.quantize_conv_t, src_nhwc(b.enc_t, w.enc_t.conv3.Cout, sh.Ht, sh.Wt), nullptr, sh.Ht, sh.Wt,
+                  c.id_t, c.quant_t, !out.quant_t && decodes, b.q_t_pair, b.counts_top(), r.fuse_t ? b.sse_top : b.sse_part,
+                  c.scal + 0};
+  rc = quantize_level(w, r, top, B, r.fuse_t, /*finish*/ false, b, c.st);
+  if (rc) return rc;
+  if (!r.fuse_t && r.pairs && r.q_t_pair_read) {
+    rc = pair_encode_f32(c.quant_t, b.q_t_pair, (int64_t)B * sh.Ht * sh.Wt * D, c.st);
+    if (rc) return rc;
+  }
+  // dec_t (vqvae.py:265): [B,Ht,Wt,D] -> [B,Hb,2^n Wt,D]
+  const isi_src qs = src_nhwc(r.pairs ? b.q_t_pair : c.quant_t, D, sh.Ht, sh.Wt);
+  const isi_dst dd = dst_nhwc(b.dec_t, Cd, sh.Hb, Wd);
+  // one gather launch right behind the top search: the conv3 items, then the upsample items (both read only id_t)
+  const CodeTableJob job{c.id_t, w.quantize_t.K, r.tab3 ? w.code_table_conv3 : nullptr, r.tabU ? w.code_table_upsample : nullptr,
+                         w.upsample[0].bias, b.up, w.upsample[0].Cout};
+  if (r.tabU && !r.tab3) {
+    rc = vq_code_gather_f32(c.id_t, nullptr, nullptr, nullptr, 0, 0, 0, job.tu, job.bias_u, job.out_u, job.C_u, 1, 0, B, sh.Ht,
+                            sh.Wt, job.K, c.st);
+    if (rc) return rc;
+  }
+  rc = run_decoder(w.dec_t, qs, nullptr, B, sh.Ht, sh.Wt, b.s0, b.s1, b.hid, dd, r.pf_enc, r.pairs, false, r.pairs, r.pairs, c.st,
+                   r.tab3 ? &job : nullptr);
+  if (rc) return rc;
+  if (r.fuse_t && !r.fuse_b) {   // (the bottom level takes the two-launch path: finish the top level on its own)
+    rc = finish_level(top, B, c.st);
+    if (rc) return rc;
+  }
+  // the bottom level, on cat([dec_t, enc_b]) cropped to Wq (vqvae.py:266-273)
+  const isi_src eb = src_nhwc(b.enc_b, sh.Cb, sh.Hb, sh.Wq, sh.Wb);
+  const Level bottom{w.quantize_b, w.quantize_conv_b, src_nhwc(b.dec_t, Cd, sh.Hb, sh.Wq, Wd), &eb, sh.Hb, sh.Wq,
+                     c.id_b, c.quant_b, !out.quant_b && decodes, b.q_b_pair, b.counts, b.sse_part, c.scal + 2};
+  rc = quantize_level(w, r, bottom, B, r.fuse_b, /*finish*/ !both_fused, b, c.st);
+  if (rc) return rc;
+  if (!both_fused) return vq_scalars_sum_f32(c.scal, c.st);       // scalars[4] = diff_t + diff_b
+  const int64_t N_t = (int64_t)B * sh.Ht * sh.Wt, N_b = (int64_t)B * sh.Hb * sh.Wq;
+  return vq_finalize2_f32(top.sse, vq_num_partials(N_t), top.counts, w.quantize_t.K, N_t, bottom.sse, vq_num_partials(N_b),
+                          bottom.counts, w.quantize_b.K, N_b, D, c.scal, c.st);
+}
+
+// VQVAE.decode (vqvae.py:280-286); `q_t` / `q_b`: the quantised maps in the pipeline's format
+int run_decode(const Call &c, const float *q_t, const float *q_b, float *dec_out) {
+  const isi_vqvae_w &w = c.w;
+  const Shapes &sh = c.sh;
+  const bool pairs = c.r.pairs;
+  const int D = w.quantize_t.D;
+  // upsample_top_to_bottom: plain transposed convs, no ReLU (vqvae.py:183-201,281)
+  const float *cur = q_t;
+  int h = sh.Ht, ww = sh.Wt;
+  for (int i = 0; i < w.n_upsample; ++i, h *= 2, ww *= 2) {
+    float *o = (i % 2 == 0) ? c.b.up : c.b.up2;
+    if (i || !c.r.tabU) {      // (else: written by the gather launch of run_encode)
       isi_src s = src_nhwc(cur, w.upsample[i].Cin, h, ww);
       isi_dst d = dst_nhwc(o, w.upsample[i].Cout, 2 * h, 2 * ww);
-      rc = conv_transpose2d_k4s2_f32(&s, w.upsample[i].w, w.upsample[i].bias, &d, B, h, ww,
-                                     w.upsample[i].Cout, pf_dec | (pairs ? ISI_CONV_IN0_PAIR | ISI_CONV_OUT_PAIR : 0), st);
+      int rc = conv_transpose2d_k4s2_f32(&s, w.upsample[i].w, w.upsample[i].bias, &d, c.B, h, ww, w.upsample[i].Cout,
+                                         c.r.pf_dec | (pairs ? ISI_CONV_IN0_PAIR | ISI_CONV_OUT_PAIR : 0), c.st);
       if (rc) return rc;
-      cur = o; h *= 2; ww *= 2;
     }
-    if (h != sh.Hb || ww != sh.Wq) return invalid("vqvae: upsampled top grid != bottom grid");
-    isi_src a = src_nhwc(cur, D, h, ww);
-    isi_src b = src_nhwc(pairs ? q_b_pair : quant_b, D, sh.Hb, sh.Wq);
-    int OHf = sh.Hb, OWf = sh.Wq;
-    for (int i = 0; i < w.dec.n_up; ++i) { OHf *= 2; OWf *= 2; }
-    isi_dst d = dst_nchw(out->dec, w.in_channel, OHf, OWf);
-    rc = run_decoder(w.dec, a, &b, B, sh.Hb, sh.Wq, s0, s1, hid, d, pf_dec, pairs, pairs, pairs, false, st);
-    if (rc) return rc;
+    cur = o;
   }
-  return ISI_OK;
+  isi_src a = src_nhwc(cur, D, sh.Hb, sh.Wq);
+  isi_src b = src_nhwc(q_b, D, sh.Hb, sh.Wq);
+  isi_dst d = dst_nchw(dec_out, w.in_channel, up_dim(sh.Hb, w.dec.n_up), up_dim(sh.Wq, w.dec.n_up));
+  return run_decoder(w.dec, a, &b, c.B, sh.Hb, sh.Wq, c.b.s0, c.b.s1, c.b.hid, d, c.r.pf_dec, pairs, pairs, pairs, false, c.st);
 }
 
 }  // namespace
@@ -576,7 +550,9 @@ int vqvae_pair_activations(const isi_vqvae_w *w) { return (w && pairs_eligible(*
 size_t vqvae_workspace_bytes(const isi_vqvae_w *w, int B, int H, int W) {
   if (!w || B <= 0 || H <= 0 || W <= 0) return 0;
   Bump ws{nullptr, 0, 0, true};
-  if (plan(*w, ISI_MODE_FORWARD, nullptr, B, H, W, nullptr, ws, nullptr) != ISI_OK) return 0;
+  Shapes sh;
+  if (check_shapes(*w, B, H, W, sh) != ISI_OK) return 0;
+  carve(*w, sh, B, ws);
   return round_up(ws.off, 256);
 }
 
@@ -588,7 +564,30 @@ int vqvae_run(const isi_vqvae_w *w, int mode, const float *x, int B, int H, int 
   if (B <= 0 || H <= 0 || W <= 0) return invalid("vqvae_run: bad shape");
   if (reinterpret_cast<uintptr_t>(workspace) & 255) return invalid("vqvae_run: workspace must be 256-byte aligned");
   Bump ws{static_cast<char *>(workspace), workspace_bytes, 0, false};
-  return plan(*w, mode, x, B, H, W, out, ws, stream);
+  Shapes sh;
+  if (int rc = check_shapes(*w, B, H, W, sh)) return rc;
+  const Buffers b = carve(*w, sh, B, ws);
+  if (int rc = check_call(*w, mode, x, *out, sh, ws)) return rc;
+
+  const Route r = make_route(*w, mode);
+  const Call c{*w, mode, B, sh, r, b, out->quant_t ? out->quant_t : b.q_t, out->quant_b ? out->quant_b : b.q_b,
+               out->scalars ? out->scalars : b.scal, out->id_t ? out->id_t : b.id_t, out->id_b ? out->id_b : b.id_b, stream};
+  const int64_t D = w->quantize_t.D;
+  const bool enc = mode & ISI_MODE_ENCODE, dec = mode & ISI_MODE_DECODE;
+  if (r.frag_packed && !r.fuse_zero)
+    if (int rc = vq_zero_counts(b.counts, 2 * b.Kmax, stream)) return rc;
+  if (enc)
+    if (int rc = run_encode(c, x, H, W, *out)) return rc;
+  if (!dec) return ISI_OK;
+  if (r.pairs) {
+    // forward: quant_t was encoded behind its search (dec_t reads it), quant_b too where its search was fused;
+    // decode: both maps arrive as fp32
+    if (!enc)
+      if (int rc = pair_encode_f32(c.quant_t, b.q_t_pair, (int64_t)B * sh.Ht * sh.Wt * D, stream)) return rc;
+    if (!(enc && r.fuse_b))
+      if (int rc = pair_encode_f32(c.quant_b, b.q_b_pair, (int64_t)B * sh.Hb * sh.Wq * D, stream)) return rc;
+  }
+  return run_decode(c, r.pairs ? b.q_t_pair : c.quant_t, r.pairs ? b.q_b_pair : c.quant_b, out->dec);
 }
 
 }  // namespace isi

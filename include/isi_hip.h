@@ -1108,6 +1108,36 @@ int isi_embed_code_f32(const int64_t *idx, const float *codes_kd, float *out,
 int isi_embed_mix_f32(const int64_t *ids, int64_t ids_stride, const float *weights, int64_t w_stride,
                       const float *codes_kd, float *out, int64_t ldo, int64_t N, int M, int D, int K, void *stream);
 
+/* vq_nearest_topm: the M nearest codes of each vector (1 <= M <= 8), in order, among the codes its palette allows, with
+ * their distances -- "render this sound with that sound's codes", a sound as per-cell mixtures, the codebook's own
+ * alternatives for a cell.  z [N][D], codes_kd [K][D], e2 [K] as for isi_vq_nearest_f32 (isi_pack_codebook_f32).
+ * Palettes: allowed is [P][ceil(K / 32)] 32-bit words, bit k & 31 of word k >> 5 in row p says that code k is in palette
+ * p; allowed_row [N] names each vector's row (NULL: row 0 for every vector).  allowed == NULL: every code is allowed, and
+ * then P must be 0 and allowed_row NULL.  (The prior's code_bias / code_bias_map shape: a small table and a per-cell map.)
+ * Outputs, in the [M][N] layout with a stride in ELEMENTS that isi_embed_mix_f32 reads: ids_out[m * ids_stride + n] is the
+ * code of rank m of vector n, dist_out[m * dist_stride + n] its distance.  Nothing else of the two buffers is written.
+ *   d[n,k] = (|z_n|^2 - 2 z_n.e_k) + e2[k]   in fp32, with the products, their order and the |z|^2 sum of
+ *            isi_vq_nearest_f32's exact kernel (fp32 matrix pipe: no operand range beyond fp32's own)
+ *   rank m = the m-th smallest (d, k) pair in lexicographic order over the allowed codes k < K with d < +inf
+ * Ties -- duplicate code vectors included -- go to the lower code first.  Hence: without a palette rank 0 equals
+ * isi_vq_nearest_f32's idx_out, index for index, on any data; and a vector's results depend on that vector, its palette
+ * row and the codebook alone, not on N, the batch or the launch geometry.
+ * A palette with fewer than M such codes fills the missing ranks with id -1 and distance +inf (an empty row: all of them).
+ * An allowed_row value outside [0, P) is never used as an address: that vector is answered like an empty palette.
+ * A vector with a non-finite component (its fp32 |z|^2 is not finite) gets id -1 and distance NaN at every rank.
+ * A non-finite code vector is never returned: e2 already carries it (+inf or NaN), so its distance is not < +inf, and the
+ * matrix pipe confines it to its own row -- other codes' ranks are what they would be without it.  (A finite code whose
+ * |e|^2 overflows fp32 counts as non-finite.)  Padding codes of the last 32-code tile and palette bits at positions >= K
+ * are ignored.
+ * Refused on the host before any launch (ISI_E_INVALID): a null z, codes_kd, e2, ids_out or dist_out; N <= 0; M outside
+ * 1..8; D not 8, 16, 32 or 64; K <= 0; ids_stride < N or dist_stride < N; allowed_row without allowed; P != 0 without
+ * allowed; P <= 0 with allowed; z or codes_kd not 16-byte aligned.  ISI_E_UNSUPPORTED: P > 64 (the palette rows live in
+ * LDS); a codebook beyond isi_vq_nearest_f32's LDS budget, (Kp (D + 4) + 2 Kp + 8) floats with Kp = K rounded up to 32,
+ * plus P Kp / 32 words, above 150 KiB; N >= 2^40 or a stride >= 2^56.  One launch, no workspace. */
+int isi_vq_nearest_topm_f32(const float *z, const float *codes_kd, const float *e2, const uint32_t *allowed, int P,
+                            const int32_t *allowed_row, int64_t *ids_out, int64_t ids_stride, float *dist_out,
+                            int64_t dist_stride, int64_t N, int D, int K, int M, void *stream);
+
 /* ------------------------------------------------- whole VQ-VAE-2 forward */
 
 #define ISI_MAX_STAGES 4

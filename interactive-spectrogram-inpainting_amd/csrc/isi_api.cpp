@@ -588,6 +588,12 @@ int isi_embed_mix_f32(const int64_t *ids, int64_t ids_stride, const float *weigh
                       float *out, int64_t ldo, int64_t N, int M, int D, int K, void *stream) {
   return embed_mix_f32(ids, ids_stride, weights, w_stride, codes_kd, out, ldo, N, M, D, K, S(stream));
 }
+int isi_vq_nearest_topm_f32(const float *z, const float *codes_kd, const float *e2, const uint32_t *allowed, int P,
+                            const int32_t *allowed_row, int64_t *ids_out, int64_t ids_stride, float *dist_out,
+                            int64_t dist_stride, int64_t N, int D, int K, int M, void *stream) {
+  return vq_nearest_topm_f32(z, codes_kd, e2, allowed, P, allowed_row, ids_out, ids_stride, dist_out, dist_stride, N, D, K, M,
+                             S(stream));
+}
 
 int isi_vqvae_pair_activations(const isi_vqvae_w *w) { return vqvae_pair_activations(w); }
 size_t isi_vqvae_workspace_bytes(const isi_vqvae_w *w, int B, int H, int W) {

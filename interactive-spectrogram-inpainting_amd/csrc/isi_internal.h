@@ -330,6 +330,10 @@ int embed_code_f32(const int64_t *idx, const float *codes, float *out, int64_t N
 // code_mix.hip: per-cell weighted mixtures of codebook rows (the spec: isi_embed_mix_f32 in isi_hip.h)
 int embed_mix_f32(const int64_t *ids, int64_t ids_stride, const float *weights, int64_t w_stride, const float *codes, float *out,
                   int64_t ldo, int64_t N, int M, int D, int K, hipStream_t stream);
+// vq_topm.hip: the M nearest codes of each vector among its palette's (the spec: isi_vq_nearest_topm_f32 in isi_hip.h)
+int vq_nearest_topm_f32(const float *z, const float *codes, const float *e2, const uint32_t *allowed, int P,
+                        const int32_t *allowed_row, int64_t *ids, int64_t ids_stride, float *dist, int64_t dist_stride,
+                        int64_t N, int D, int K, int M, hipStream_t stream);
 
 int relu_inplace_f32(float *x, int64_t n, hipStream_t stream);
 

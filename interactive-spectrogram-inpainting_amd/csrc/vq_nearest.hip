@@ -22,17 +22,12 @@
 #include "knobs.h"
 #include "prof.h"
 #include "split_f16.h"
+#include "vq_dist.h"   // the workgroup shape, the LDS rows and the distance stage of the exact kernel (shared with vq_topm.hip)
 
 namespace isi {
 
 typedef short s16x8v __attribute__((ext_vector_type(8)));
 typedef int i32x4v __attribute__((ext_vector_type(4)));
-
-#ifndef ISI_VQ_WAVES
-#define ISI_VQ_WAVES 8
-#endif
-constexpr int VQ_BLOCK = 64 * ISI_VQ_WAVES;
-constexpr int VQ_VEC_PER_BLOCK_ITER = 32 * ISI_VQ_WAVES;  // each wave owns 32 vectors per pass
 
 template <int D>
 __global__ __launch_bounds__(VQ_BLOCK) void vq_nearest_kernel(
@@ -57,11 +52,7 @@ __global__ __launch_bounds__(VQ_BLOCK) void vq_nearest_kernel(
   const int half = lane >> 5;
 
   // ---- codebook -> LDS (once per persistent workgroup)
-  for (int i = tid; i < Kp * (D / 4); i += VQ_BLOCK) {
-    const int k = i / (D / 4), qd = i - k * (D / 4);
-    *reinterpret_cast<float4 *>(cb + (size_t)k * LDD + qd * 4) =
-        k < K ? *reinterpret_cast<const float4 *>(codes + (size_t)k * D + qd * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
+  vq_fill_rows_f32<D>(cb, codes, K, Kp, tid);
   for (int i = tid; i < Kp; i += VQ_BLOCK) { e2[i] = i < K ? e2g[i] : INFINITY; hist[i] = 0; }
   __syncthreads();
 
@@ -75,10 +66,9 @@ __global__ __launch_bounds__(VQ_BLOCK) void vq_nearest_kernel(
     float x2p = 0.f;
 #pragma unroll
     for (int j = 0; j < NQ; ++j) {
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (valid) v = *reinterpret_cast<const float4 *>(z + n * D + (2 * j + half) * 4);
+      const float4 v = vq_load_quad_f32(z, n, valid, 2 * j + half, D);
       zq[j] = v;
-      x2p += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+      x2p += vq_quad_norm2_f32(v.x, v.y, v.z, v.w);
     }
     const float x2 = x2p + __shfl_xor(x2p, 32);
 
@@ -88,20 +78,12 @@ __global__ __launch_bounds__(VQ_BLOCK) void vq_nearest_kernel(
       f32x16 acc;
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-      const float *arow = cb + (size_t)(kt + col) * LDD + half * 4;
-#pragma unroll
-      for (int j = 0; j < NQ; ++j) {
-        const float4 a = *reinterpret_cast<const float4 *>(arow + j * 8);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, zq[j].x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, zq[j].y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, zq[j].z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, zq[j].w, acc, 0, 0, 0);
-      }
+      vq_tile_dots_f32<D>(acc, cb + (size_t)(kt + col) * LDD + half * 4, zq);
       // rows (codes) of this lane, ascending: (r&3) + 8*(r>>2) + 4*half
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int code = kt + (r & 3) + 8 * (r >> 2) + 4 * half;
-        const float d = (x2 - 2.f * acc[r]) + e2[code];
+        const float d = vq_distance_f32(x2, acc[r], e2[code]);
         if (d < best) { best = d; besti = code; }
       }
     }
@@ -938,8 +920,8 @@ template <int D>
 static int launch_vq(const float *z, const float *codes, const float *e2, int64_t *idx, float *q,
                      int32_t *counts, float *sse_part, int64_t N, int K, hipStream_t stream) {
   const int Kp = (K + 31) & ~31;
-  const size_t smem = ((size_t)Kp * (D + 4) + 2 * Kp + ISI_VQ_WAVES) * sizeof(float);
-  if (smem > 150 * 1024) return unsupported("vq: codebook does not fit in LDS");
+  const size_t smem = vq_exact_lds_bytes<D>(Kp);
+  if (smem > kVqLdsBudget) return unsupported("vq: codebook does not fit in LDS");
   auto kern = vq_nearest_kernel<D>;
   if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)

@@ -916,6 +916,59 @@ def crossfade(vqvae, a, b, start_index_top: int, width_top: int, snap: bool = Fa
     return morph(vqvae, [a, b], ramp(T, 1), ramp(codes_b.shape[3], codes_b.shape[3] // T), snap=snap)
 
 
+@torch.no_grad()
+def render_with_palette(vqvae, spectrogram: torch.Tensor, palette_top, palette_bottom=None):
+    """Quantise `spectrogram` [B, C, H, W] with another sound's codes: (top_code [B, F_t, T_t], bottom_code [B, F_b, T_b]),
+    in every cell the nearest code of the level's palette -- typically `sample.codes_in_use(other_top, K)` and
+    `sample.codes_in_use(other_bottom, K)`, bool rows [K]; any single palette `VQVAE.encode_topm` takes will do.
+    `palette_bottom` None leaves the bottom level unrestricted.  The bottom level is searched under the top map the
+    palette produced.  The results are ordinary codemaps for the priors, the search and `decode_code`.  An empty palette
+    raises ValueError (a cell would have no code)."""
+    K_t, K_b = vqvae.quantize_t.n_embed, vqvae.quantize_b.n_embed
+
+    def one_palette(p, K, name):
+        if p is None:
+            return None
+        t = torch.as_tensor(p)
+        row = t.reshape(-1).cpu() if t.dtype == torch.bool else None
+        if row is None:                                       # code indices
+            idx = t.reshape(-1).long().cpu()
+            if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= K):
+                raise ValueError(f"render_with_palette: {name} holds a code outside [0, {K})")
+            row = torch.zeros(K, dtype=torch.bool)
+            row[idx] = True
+        if row.shape[0] != K:
+            raise ValueError(f"render_with_palette: {name} must be a bool row [{K}] or a tensor of code indices")
+        if not bool(row.any()):
+            raise ValueError(f"render_with_palette: {name} allows no code")
+        return row
+
+    codes_t, _, codes_b, _ = vqvae.encode_topm(spectrogram, m=1, allowed_codes_top=one_palette(palette_top, K_t, "palette_top"),
+                                               allowed_codes_bottom=one_palette(palette_bottom, K_b, "palette_bottom"))
+    return codes_t[0], codes_b[0]
+
+
+@torch.no_grad()
+def encode_soft(vqvae, spectrogram: torch.Tensor, m: int, temperature: float):
+    """One sound as per-cell mixtures of its `m` nearest codes: (codes_t, weights_t, codes_b, weights_b), each
+    [m, B, F, T] of its level, ready for `VQVAE.decode_code_mix` (and, a source at a time, for `morph`).  The weights are
+    `VQVAE.soft_weights` of the codebook distances: softmax of -(d_m - d_0) / temperature; temperature 0 puts weight 1 on
+    the nearest code, and the decode is then `decode_code` of the hard codemaps bit for bit."""
+    codes_t, dist_t, codes_b, dist_b = vqvae.encode_topm(spectrogram, m=m)
+    return codes_t, vqvae.soft_weights(dist_t, temperature), codes_b, vqvae.soft_weights(dist_b, temperature)
+
+
+@torch.no_grad()
+def code_alternatives(vqvae, spectrogram: torch.Tensor, m: int, layer: str):
+    """"What else could stand here?" by the VQ-VAE's own metric: (ids int64 [m, B, F, T], distances fp32 [m, B, F, T]) of
+    `layer` ('top' or 'bottom'), nearest first -- rank 0 is the cell's own code, the others are the swaps that stay closest
+    to the recorded sound.  (`sample.codemap_statistics` gives the prior's alternatives.)"""
+    if layer not in ('top', 'bottom'):
+        raise ValueError(f"layer must be 'top' or 'bottom', got {layer!r}")
+    codes_t, dist_t, codes_b, dist_b = vqvae.encode_topm(spectrogram, m=m)
+    return (codes_t, dist_t) if layer == 'top' else (codes_b, dist_b)
+
+
 def sample_from_database(codes_dataset, label_encoders_per_modality: Mapping[str, object], duration_top: int,
                          attribute_constraints: Mapping[str, object], generator: Optional[torch.Generator] = None, *,
                          similar_to: Optional[Tuple[torch.Tensor, Optional[torch.Tensor]]] = None, index=None):

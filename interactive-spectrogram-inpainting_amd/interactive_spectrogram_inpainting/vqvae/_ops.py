@@ -334,6 +334,110 @@ def embed_mix(ids: torch.Tensor, weights: torch.Tensor, codes: torch.Tensor) -> 
     return out
 
 
+TOPM_MAX = 8             # ranks of one search (isi_vq_nearest_topm_f32)
+TOPM_MAX_PALETTES = 64   # palette rows of one search
+
+
+def pack_palettes(allowed_codes, K: int, device=None) -> torch.Tensor:
+    """Palettes -> the word table int32 [P, ceil(K / 32)] of isi_vq_nearest_topm_f32 on `device`: bit k & 31 of word k >> 5
+    in row p says that code k is in palette p.  `allowed_codes`: a bool table [P, K] or one bool row [K] (what
+    `sample.codes_in_use` returns), or a list with one entry per palette, each a bool row [K] or a tensor / sequence of
+    code indices.  Indices outside [0, K) raise; a row may be empty."""
+    K = int(K)
+    if K <= 0:
+        raise ValueError("pack_palettes: K must be positive")
+    if torch.is_tensor(allowed_codes):
+        table = allowed_codes.detach().cpu()
+        if table.dtype != torch.bool or table.dim() not in (1, 2) or table.shape[-1] != K:
+            raise ValueError(f"pack_palettes: a tensor must be a bool table [P, {K}] or one bool row [{K}], got "
+                             f"{table.dtype} {tuple(table.shape)}")
+        table = table.reshape(-1, K)
+    else:
+        rows = []
+        for entry in list(allowed_codes):
+            e = torch.as_tensor(entry).detach().cpu()
+            if e.dtype == torch.bool:
+                if e.dim() != 1 or e.shape[0] != K:
+                    raise ValueError(f"pack_palettes: a bool row must have {K} entries, got {tuple(e.shape)}")
+                rows.append(e)
+                continue
+            if e.numel() and (e.is_floating_point() or e.is_complex()):
+                raise ValueError("pack_palettes: code indices must be integers")
+            e = e.reshape(-1).long()
+            if e.numel() and (int(e.min()) < 0 or int(e.max()) >= K):
+                raise ValueError(f"pack_palettes: code index outside [0, {K})")
+            row = torch.zeros(K, dtype=torch.bool)
+            row[e] = True
+            rows.append(row)
+        if not rows:
+            raise ValueError("pack_palettes: no palette given")
+        table = torch.stack(rows)
+    P = table.shape[0]
+    if P < 1:
+        raise ValueError("pack_palettes: no palette given")
+    W = (K + 31) // 32
+    bits = torch.zeros(P, W * 32, dtype=torch.int64)
+    bits[:, :K] = table.long()
+    words = (bits.reshape(P, W, 32) << torch.arange(32, dtype=torch.int64)).sum(-1)         # 0 .. 2^32 - 1
+    words = torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)           # the same 32 bits, signed
+    return words.to(device) if device is not None else words
+
+
+def unpack_palettes(words: torch.Tensor, K: int) -> torch.Tensor:
+    """The bool table [P, K] of a word table made by `pack_palettes`."""
+    w = words.detach().cpu().long() & 0xFFFFFFFF
+    bits = (w.unsqueeze(-1) >> torch.arange(32, dtype=torch.int64)) & 1
+    return bits.reshape(w.shape[0], -1)[:, :int(K)].bool()
+
+
+def vq_nearest_topm(z: torch.Tensor, codes: torch.Tensor, e2: torch.Tensor, m: int, allowed: Optional[torch.Tensor] = None,
+                    allowed_row: Optional[torch.Tensor] = None):
+    """z [..., D] dense channels-last -> (ids int64 [M, ...], dist fp32 [M, ...]): the `m` nearest codes of every vector, in
+    (distance, index) order, among the codes of the vector's palette (csrc/vq_topm.hip; the specification is
+    isi_vq_nearest_topm_f32's comment in include/isi_hip.h).  `allowed`: the word table of `pack_palettes` on z's device
+    (None: every code); `allowed_row` [...] integer: each vector's row of it (None: row 0).  Missing ranks are id -1 /
+    distance +inf; a vector with a non-finite component is id -1 / distance NaN.  The outputs are laid out as
+    `embed_mix` reads them."""
+    _hip.require_gpu(z, "top-m search input")
+    m = int(m)
+    if not 1 <= m <= TOPM_MAX:
+        raise ValueError(f"vq_nearest_topm returns 1 to {TOPM_MAX} ranks, got {m}")
+    if z.dtype != torch.float32:
+        raise TypeError(f"vectors must be float32, got {z.dtype}")
+    z = z.contiguous()
+    K, D = codes.shape
+    if z.dim() < 1 or z.shape[-1] != D:
+        raise ValueError(f"vectors {tuple(z.shape)} do not end in the codebook's dimension {D}")
+    cells = z.shape[:-1]
+    N = z.numel() // D
+    P = 0
+    if allowed is None:
+        if allowed_row is not None:
+            raise ValueError("allowed_row selects rows of `allowed`, which is not given")
+    else:
+        W = (K + 31) // 32
+        if allowed.dtype != torch.int32 or allowed.dim() != 2 or allowed.shape[1] != W or allowed.device != z.device:
+            raise ValueError(f"allowed must be the int32 word table [P, {W}] of pack_palettes on the vectors' device")
+        allowed = allowed.contiguous()
+        P = allowed.shape[0]
+        if not 1 <= P <= TOPM_MAX_PALETTES:
+            raise ValueError(f"1 to {TOPM_MAX_PALETTES} palettes per search, got {P}")
+        if allowed_row is not None:
+            if allowed_row.is_floating_point() or allowed_row.shape != cells:
+                raise ValueError(f"allowed_row must be an integer map {tuple(cells)}, got {allowed_row.dtype} {tuple(allowed_row.shape)}")
+            # out-of-range rows stay out of range in 32 bits: the kernel answers them like an empty palette
+            allowed_row = allowed_row.to(z.device).clamp(-1, P).to(torch.int32).contiguous()
+    ids = torch.empty(m, *cells, dtype=torch.int64, device=z.device)
+    dist = torch.empty(m, *cells, dtype=torch.float32, device=z.device)
+    if N == 0:
+        return ids, dist
+    _hip.check(_hip.lib().isi_vq_nearest_topm_f32(
+        z.data_ptr(), codes.data_ptr(), e2.data_ptr(), allowed.data_ptr() if allowed is not None else None, P,
+        allowed_row.data_ptr() if allowed_row is not None else None, ids.data_ptr(), N, dist.data_ptr(), N, N, D, K, m, _s(z)),
+        "isi_vq_nearest_topm_f32")
+    return ids, dist
+
+
 def pack_code_tables(packed_w3: Optional[torch.Tensor], cout3: int, packed_wT: Optional[torch.Tensor], coutU: int,
                      codes: torch.Tensor):
     """Per-code product tables of a 3x3 convolution and of a ConvTranspose2d(k4,s2,p1) over the codebook `codes` [K,D]

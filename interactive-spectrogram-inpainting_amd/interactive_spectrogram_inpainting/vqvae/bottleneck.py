@@ -77,6 +77,24 @@ class QuantizedBottleneck(nn.Module):
         codes, _ = self.packed()
         return _ops.embed_mix(embed_ids, weights, codes)
 
+    def nearest_codes(self, z_nhwc: Tensor, m: int = 1, allowed_codes=None, allowed_map: Optional[Tensor] = None
+                      ) -> Tuple[Tensor, Tensor]:
+        """z_nhwc [B, H, W, D] -> (ids int64 [M, B, H, W], dist fp32 [M, B, H, W]): the `m` nearest codes of every cell by
+        the bottleneck's own metric, nearest first, ties to the lower code (`_ops.vq_nearest_topm`).  `allowed_codes`: the
+        palettes the search is restricted to, in any form `_ops.pack_palettes` takes (a bool row [K] as
+        `sample.codes_in_use` returns it, a bool table [P, K], a list of index tensors) or an already packed word table;
+        `allowed_map` [B, H, W] names each cell's palette (None: the first).  A palette with fewer than `m` codes leaves
+        id -1 / distance +inf in the missing ranks.  The codebook is not updated, in any mode."""
+        codes, e2 = self.packed()
+        allowed = None
+        if allowed_codes is not None:
+            packed = (torch.is_tensor(allowed_codes) and allowed_codes.dtype == torch.int32 and allowed_codes.dim() == 2
+                      and allowed_codes.shape[1] == (self.n_embed + 31) // 32)
+            allowed = allowed_codes.to(z_nhwc.device) if packed else _ops.pack_palettes(allowed_codes, self.n_embed, z_nhwc.device)
+        elif allowed_map is not None:
+            raise ValueError("allowed_map selects rows of allowed_codes, which is not given")
+        return _ops.vq_nearest_topm(z_nhwc, codes, e2, m, allowed, allowed_map)
+
 
 class QuantizedBottleneckWithRestarts(QuantizedBottleneck):
     """EMA codebook with random restarts of dead codes (the reference's `bottleneck.py:122-166`, whose arithmetic sits in
@@ -129,4 +147,7 @@ class UnquantizedBottleneck(QuantizedBottleneck):
         raise NotImplementedError
 
     def embed_mix(self, embed_ids, weights):
+        raise NotImplementedError
+
+    def nearest_codes(self, z_nhwc, m=1, allowed_codes=None, allowed_map=None):
         raise NotImplementedError

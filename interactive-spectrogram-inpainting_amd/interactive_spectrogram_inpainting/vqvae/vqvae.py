@@ -447,6 +447,73 @@ class VQVAE(nn.Module):
         quant_b = self.quantize_b.embed_mix(codes_b, weights_b).permute(0, 3, 1, 2)
         return self.decode(quant_t, quant_b)
 
+    @torch.no_grad()
+    def encode_topm(self, input: Tensor, m: int = 1, allowed_codes_top=None, allowed_codes_bottom=None,
+                    allowed_map_top: Optional[Tensor] = None, allowed_map_bottom: Optional[Tensor] = None):
+        """The `m` nearest codes of every cell of both levels, optionally restricted to palettes: returns
+        (codes_t [M, B, Ht, Wt] int64, dist_t fp32, codes_b [M, B, Hb, Wq] int64, dist_b fp32), nearest first, in the layout
+        `decode_code_mix` reads (`QuantizedBottleneck.nearest_codes`, csrc/vq_topm.hip).  `allowed_codes_*`: palettes of
+        that level (a bool row [K] as `sample.codes_in_use` returns it, a bool table [P, K], a list of index tensors);
+        `allowed_map_*` [B, H, W]: each cell's palette (None: the first).  Missing ranks of a short palette are id -1 /
+        distance +inf.
+
+        The layer sequence is `encode`'s: enc_b, enc_t, quantize_conv_t, the search on the top level, then the top's
+        RANK-0 code through embed_code and dec_t (cropped to the bottom width under `adapt_quantized_durations`),
+        quantize_conv_b on cat(dec_t, enc_b), the search on the bottom level -- so the bottom level sees the top
+        quantisation the palette produced, as `encode` sees its own.  (A top cell whose palette is empty has no rank-0
+        code: IndexError.)  This is the interactive path of one upload, run layer by layer with the modules' own forwards:
+        every convolution on the exact-fp32 matrix pipe, whatever `conv_precision` says -- not the batch path of
+        `isi_vqvae_run` that `encode` and `forward` take.  With m = 1 and no palette the ids are `encode`'s except where two
+        codes are a rounding error apart.  Eval mode only: no codebook is updated."""
+        if self.training:
+            raise RuntimeError("encode_topm is an eval-mode call (model.eval()): it never updates the codebooks")
+        if self.disable_quantization:
+            raise NotImplementedError("encode_topm: this model has no codebooks (disable_quantization)")
+        _hip.require_gpu(input, "input")
+        if input.dim() != 4 or input.shape[1] != self.in_channel:
+            raise RuntimeError(f"expected input [B, {self.in_channel}, H, W], got {tuple(input.shape)}")
+        x = input.contiguous()
+        if self.data_normalizer is not None:
+            x = self.data_normalizer.normalize(x)
+
+        def nhwc(t):
+            p = t.permute(0, 2, 3, 1)
+            return p if p.is_contiguous() else p.contiguous()
+        enc_b = self.enc_b(x)
+        enc_t = self.enc_t(enc_b)
+        z_t = nhwc(self.quantize_conv_t.run(enc_t, relu=False))
+        codes_t, dist_t = self.quantize_t.nearest_codes(z_t, m, allowed_codes_top, allowed_map_top)
+        quant_t = self.quantize_t.embed_code(codes_t[0]).permute(0, 3, 1, 2)
+        dec_t = self.dec_t(quant_t)
+        if dec_t.shape[-1] != enc_b.shape[-1]:
+            if not self.adapt_quantized_durations:
+                raise RuntimeError("Sizes of tensors must match except in dimension 1")
+            w = min(dec_t.shape[-1], enc_b.shape[-1])
+            dec_t, enc_b = dec_t[..., :w], enc_b[..., :w]
+        z_b = nhwc(self.quantize_conv_b.run(dec_t, relu=False, x2=enc_b))
+        codes_b, dist_b = self.quantize_b.nearest_codes(z_b, m, allowed_codes_bottom, allowed_map_bottom)
+        return codes_t, dist_t, codes_b, dist_b
+
+    @staticmethod
+    def soft_weights(dist: Tensor, temperature: float) -> Tensor:
+        """dist fp32 [M, ...] as `encode_topm` returns it (non-decreasing along M; +inf or NaN where a rank does not
+        exist) -> mixing weights fp32 [M, ...]: w_m = softmax over the existing ranks of -(d_m - d_0) / temperature.  A
+        rank that does not exist gets 0 -- `decode_code_mix` skips a zero weight, so its id -1 is never looked at; a cell
+        without any rank gets all zeros.  temperature 0: weight 1 at rank 0.  A negative or NaN temperature raises."""
+        t = float(temperature)
+        if not t >= 0:
+            raise ValueError(f"soft_weights: temperature must be >= 0, got {temperature}")
+        d = dist.to(torch.float32)
+        exists = torch.isfinite(d)
+        if t == 0:
+            e = torch.zeros_like(d)
+            e[0] = exists[0].to(torch.float32)
+        else:
+            gap = torch.where(exists, d - d[:1], torch.zeros_like(d))        # >= 0: the exponentials lie in (0, 1]
+            e = torch.where(exists, torch.exp(-gap / t), torch.zeros_like(d))
+        total = e.sum(0, keepdim=True)
+        return torch.where(total > 0, e / total.clamp(min=1e-30), torch.zeros_like(e))
+
     def post_process(self, dec: Tensor) -> Tensor:
         """vqvae.py:297-302: de-normalise, then zero the phase of bins at or below the magnitude floor
         (one fused pass when both are configured)."""

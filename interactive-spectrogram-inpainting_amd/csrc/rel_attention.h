@@ -1,17 +1,20 @@
-// What the relative-attention translation units share: the kernel-side arguments of the forward kernels
-// (rel_attention_f32.hip: exact fp32 and the one-row tail kernel; rel_attention_fwd2.hip: the 64-key-tile kernels;
-// rel_attention_fwd3.hip: the plane-staged kernel) and the launchers the dispatcher hands over to; the host checks and
-// the argument fill common to the forward and the backward entry point (rel_attention_bwd_f32.hip); the constants and
-// the 16-bit operand trait of the two 16-bit forward files.
+// What the training-side relative attention's host plan (rel_attention_run.cpp) and its kernels share: the kernels' argument
+// blocks, the constants the plan sizes things by, the host checks and the argument fill common to the forward and the
+// backward entry point, and one launcher per kernel family.  The plan never names a kernel; a launcher picks the template
+// instantiation from its arguments and owns that kernel's one-time set-up.  The kernels:
+//   rel_attention_f32.hip      forward: exact fp32 and the one-row tail kernel
+//   rel_attention_fwd2.hip     forward: the 64-key-tile 16-bit kernels
+//   rel_attention_fwd3.hip     forward: the plane-staged 16-bit kernel and its pack launch
+//   rel_attention_bwd_f32.hip  backward: every kernel of it
+// This header compiles as plain C++ with the HIP headers; what only device code reads is rel_attention_dev.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "device_prims.h"
 #include "isi_common.h"
-#include "split_bf16.h"
 
 namespace isi {
 
+// The argument block of the forward kernels.  A KERNEL ARGUMENT: its layout is part of the device code.
 struct AttnKArgs {
   const float *q, *k, *v, *e, *mask;
   float *out, *lse;
@@ -26,22 +29,72 @@ struct AttnKArgs {
   float *logits;  // optional [B,H,Sq,ldl]: base-2 logits of the allowed pairs, kept for the backward (rel_attention_fwd2.hip)
   int ldl;
 };
+static_assert(sizeof(AttnKArgs) == 184, "AttnKArgs is a kernel argument block: its layout must not change");
 
-// rel_attention_fwd2.hip: any Cq, Ck >= 1, head_dim 16 / 32 / 64.  precision: 1 three-term split-bf16, 2 single-term bf16,
-// 3 single-term f16.
-int rel_attention_fwd2(const AttnKArgs &a, int head_dim, int precision, hipStream_t stream);
+// The argument block of the backward kernels.  A kernel argument like AttnKArgs.
+struct AttnBwdKArgs {
+  const float *q, *k, *v, *e, *mask, *dout, *out, *lse;
+  float *dsum;            // [B,H,Sq]
+  float *dq, *dk, *dv;
+  float *g;               // [H][Sq][B][Rp]: rows query-major, so that the rows of a GEMM tile share their band of columns
+  unsigned q_bytes, k_bytes, v_bytes, e_bytes, o_bytes;
+  int Sq, Sk, H, B;
+  int nqb, nkb;           // stationary query / key blocks the split kernels run (all, or only the full ones)
+  int q_ss, q_sb, q_sh, k_ss, k_sb, k_sh, v_ss, v_sb, v_sh, o_ss, o_sb, o_sh;  // element strides
+  int Cq, Ck, Ek, R, Rp;
+  int rho_lo;             // G column c holds table row rho_lo + c (causal modes only touch half of the table)
+  int g_band_only;        // G is zeroed only around its band: EVERY (query, key) pair the mask allows is stored (zeros too)
+  int mask_mode;
+  float scale;
+  const float *logits;    // optional [B,H,Sq,ldl]: the forward's base-2 logits of the allowed pairs (isi_attn_args.logits):
+  int ldl;                // the split kernels read them instead of forming Q K^T and the skewed band product again
+  int g_from_kv;          // (kept logits, Cq = Ck = 1, band-only G) the KEY-stationary kernel stores dS into G -- lanes run
+                          // along keys: 128-byte runs of a query's row -- and the query-stationary kernel only reads it back
+                          // for dQ += dS K: no second exp / dO V^T / dS pass, no V tiles, no scatter
+};
+static_assert(sizeof(AttnBwdKArgs) == 248, "AttnBwdKArgs is a kernel argument block: its layout must not change");
+
+constexpr int QB = 128;        // queries (in the backward's key-stationary kernels: keys) per workgroup
+constexpr int BAND = 160;      // rows of e a 128 x 32 tile can touch (>= 127/Cq + 31/Ck + 1, and the same with Cq, Ck swapped)
+
+// Where the plane-staged forward keeps its 16-bit operand planes in the caller's workspace (rel_attention_run.cpp computes
+// it, the launchers of rel_attention_fwd3.hip read it): plane element counts and byte offsets
+struct PlaneLayout { int Skp, npl; size_t kv_plane, e_plane, k_off, v_off, e_off, total; };
+
+// ---- launchers.  head_dim is 16, 32 or 64 (the plane-staged kernel: 32 or 64); anything else is refused
+// rel_attention_f32.hip: exact fp32, all query blocks
+int launch_attn_fwd_exact(const AttnKArgs &a, int head_dim, hipStream_t st);
+// the query rows [row0, row0 + rows) in exact fp32, one workgroup per (batch, head) and row
+int launch_attn_fwd_tail_rows(const AttnKArgs &a, int head_dim, int row0, int rows, hipStream_t st);
+// rel_attention_fwd2.hip: any Cq, Ck >= 1.  precision: 1 three-term split-bf16, 2 single-term bf16, 3 single-term f16;
+// nW persistent workgroups per (batch, head) pair
+int launch_attn_fwd2(const AttnKArgs &a, int head_dim, int precision, int nW, hipStream_t st);
 int rel_attention_fwd2_debug_stamps(long long *host, int n);
-
-// rel_attention_fwd3.hip: one channel per event (Cq = Ck = 1), head_dim 32 / 64, precision 1 .. 3; K, V and e are split into
-// 16-bit planes in `workspace` (rel_attention_fwd3_workspace_bytes, 256-byte aligned) by a pack launch in front of the kernel.
-bool rel_attention_fwd3_ok(const AttnKArgs &a, int head_dim, int precision);
-size_t rel_attention_fwd3_workspace_bytes(const AttnKArgs &a, int head_dim, int precision);
-int rel_attention_fwd3(const AttnKArgs &a, int head_dim, int precision, void *workspace, size_t workspace_bytes, hipStream_t stream);
+// rel_attention_fwd3.hip: one channel per event (Cq = Ck = 1), head_dim 32 / 64, precision 1 .. 3.  TWO launches: K, V and
+// e are split into 16-bit planes in `workspace` (L.total bytes, 256-byte aligned) by a pack launch, then the kernel
+int launch_attn_fwd3(const AttnKArgs &a, int head_dim, int precision, const PlaneLayout &L, void *workspace, int nW,
+                     hipStream_t st);
 int rel_attention_fwd3_debug_stamps(long long *host, int n);
+// rel_attention_bwd_f32.hip.  D[b,h,i] = dO_i . O_i into a.dsum
+int launch_attn_dsum(const AttnBwdKArgs &a, int head_dim, hipStream_t st);
+// G zeroed: all n4 float4 of it, or, on `rows` = (head, query, batch) rows of Rp columns, the margins of each row's band
+// [lo_slope i + lo_base, hi_slope i + hi_base]
+int launch_attn_zero_g(float *g, size_t n4, hipStream_t st);
+int launch_attn_zero_g_margins(float *g, long rows, int Sq, int B, int Rp, int lo_slope, int lo_base, int hi_slope, int hi_base,
+                               hipStream_t st);
+// the split-bf16 pair.  one: single-term products; saved: the kept logits a.logits are read; which: 1 = the key-stationary
+// kernel (dK, dV), 2 = the query-stationary one (dQ, G), 3 = both, in that order
+int launch_attn_bwd_split(const AttnBwdKArgs &a, int head_dim, bool one, bool saved, int which, hipStream_t st);
+// the last tail_q query rows and tail_k keys in exact fp32, one launch for both
+int launch_attn_bwd_tails(const AttnBwdKArgs &a, int head_dim, int tail_q, int tail_k, hipStream_t st);
+// the exact-fp32 pair: key-stationary (dK, dV), then query-stationary (dQ, G)
+int launch_attn_bwd_exact(const AttnBwdKArgs &a, int head_dim, hipStream_t st);
+// packed GEMM operand of every head's table rows [lo, lo + n), transposed and zero padded to Kpad; and back:
+// d_rel[h][r][d] = dw[h][r - lo][d] on those rows, 0 elsewhere (dw rows padded to Rp, columns to Kp)
+int launch_pack_rel_T(const float *e, float *out, int H, int R, int HD, int Kpad, int lo, int n, hipStream_t st);
+int launch_unpack_drel(const float *dw, float *out, int H, int R, int HD, int Rp, int Kp, int lo, int n, hipStream_t st);
 
 // ---- host: what rel_attention_f32() and rel_attention_bwd_f32() check and fill alike
-
-constexpr int BAND = 160;      // rows of e a 128 x 32 tile can touch (>= 127/Cq + 31/Ck + 1, and the same with Cq, Ck swapped)
 
 // elements from a [S, B, H, hd] tensor's first to one past its last
 inline int64_t span(int64_t S, int64_t ss, int64_t B, int64_t sb, int64_t H, int64_t sh, int64_t hd) {
@@ -94,44 +147,5 @@ inline void attn_fill_common(KArgs &a, const isi_attn_args *g, const AttnSpans &
   a.Cq = g->Cq; a.Ck = g->Ck; a.Ek = g->Ek;
   a.mask_mode = g->mask_mode; a.scale = g->scale;
 }
-
-// ---- device: constants of all the attention kernels; LD and the operand trait Prec are the 16-bit forward kernels'
-// (rel_attention_fwd2.hip, rel_attention_fwd3.hip)
-
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-
-constexpr unsigned OOB = 0xFFFFFFF0u;   // a buffer offset beyond every descriptor: the load returns zeros
-constexpr float NEG = -1e30f;
-constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
-constexpr int QB = 128;    // queries (in the backward's key-stationary kernels: keys) per workgroup
-constexpr int LD = 68;     // floats per query row of the skew buffer (64 band rows + 4)
-
-// the 16-bit operand type of a mode: conversions (round to nearest even) and the matrix instruction
-template <bool F16> struct Prec;
-template <> struct Prec<false> {
-  static __device__ __forceinline__ unsigned pack2(const float a, const float b) {
-    const f32x2_t v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-  }
-  static __device__ __forceinline__ void split2(const float a, const float b, unsigned &hi, unsigned &lo) { isi::split2(a, b, hi, lo); }
-  static __device__ __forceinline__ f32x16 mfma(const s16x8_t a, const s16x8_t b, const f32x16 c) { return ISI_MFB(a, b, c); }
-};
-template <> struct Prec<true> {
-  static __device__ __forceinline__ unsigned pack2(const float a, const float b) {
-    const f32x2_t v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2_t));
-  }
-  static __device__ __forceinline__ void split2(const float a, const float b, unsigned &hi, unsigned &lo) {
-    const f32x2_t v = {a, b};
-    const f16x2_t h = __builtin_convertvector(v, f16x2_t);
-    const f16x2_t l = __builtin_convertvector(v - __builtin_convertvector(h, f32x2_t), f16x2_t);
-    hi = __builtin_bit_cast(unsigned, h);
-    lo = __builtin_bit_cast(unsigned, l);
-  }
-  static __device__ __forceinline__ f32x16 mfma(const s16x8_t a, const s16x8_t b, const f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-  }
-};
 
 }  // namespace isi

@@ -1,22 +1,38 @@
-// Backward of the relative-position attention of rel_attention_f32.hip, gfx950
-// exact-fp32 matrix pipe.  Nothing of size Sq x Sk is stored by the forward: both
-// kernels recompute the probabilities P = exp(logit - LSE) tile by tile from q, k,
-// e and the per-query log-sum-exp the forward kernel wrote.
+// Backward of the relative-position attention for gfx950: every kernel of it and their launchers (rel_attention.h).  Which
+// of them a call runs, in which order and on which workspace is the host plan's business (rel_attention_run.cpp).
 //
 //   dP = dO V^T                      D_i = sum_d dO[i,d] O[i,d]
 //   dS = P o (dP - D) * scale
 //   dV = P^T dO      dK = dS^T Q      dQ = dS K + G E      dE = G^T Q
 //   G[i, r] = sum over keys j with r(i,j) = r of dS[i,j]      (the "un-skew" of dS)
 //
-//   rel_attention_bwd_kv_kernel   key-stationary: a wave owns 32 keys (K, V rows in
-//       registers, dK^T / dV^T in accumulators), query tiles stream through LDS.  No
-//       atomics: every dK / dV element is produced by exactly one wave.
-//   rel_attention_bwd_q_kernel    query-stationary (the forward's loop): dQ^T in
-//       accumulators; dS is transposed through LDS so that one query's 32 keys land
-//       on consecutive columns of G (row-coalesced float atomics; a G row is only
-//       ever touched by the one wave that owns the query, in program order).
-//   then two plain GEMMs on the existing kernels:  dQ += G E  (1x1 "convolution",
-//       residual = dQ) and dE = G^T Q (the pixel-reduction GEMM of conv_wgrad_f32).
+// Nothing of size Sq x Sk has to be stored by the forward: the kernels recompute the probabilities P = exp(logit - LSE)
+// tile by tile from q, k, e and the per-query log-sum-exp the forward wrote -- or, where the forward kept its logits
+// (isi_attn_args.logits, the SAVED instantiations of the split pair), read those instead of forming Q K^T and the skewed
+// band product again.  In the order of the file:
+//
+//   attn_dsum_kernel              D, one lane group per (batch, head, query) row.
+//   rel_attention_bwd_q_kernel,   the exact-fp32 pair (precision 0; 256 threads, fp32 matrix pipe).  Query-stationary
+//   rel_attention_bwd_kv_kernel   (the forward's loop): dQ^T in accumulators; dS is transposed through LDS so that one
+//       query's 32 keys land on consecutive columns of G, which is ADDED to with row-coalesced float atomics (G zeroed in
+//       full beforehand; a G row is only ever touched by the one wave that owns the query, in program order).
+//       Key-stationary: a wave owns 32 keys (K, V rows in registers, dK^T / dV^T in accumulators), query tiles stream
+//       through LDS; no atomics: every dK / dV element is produced by exactly one wave.
+//   rel_attention_bwd_q_split_kernel,   the split-bf16 pair (precision >= 1; 512 threads, bf16 matrix pipe, three-term
+//   rel_attention_bwd_kv_split_kernel   products or ONE single-term product, persistent over XCD-ordered blocks).  With one
+//       channel per event every (query, key) pair has its own element of G: the query-stationary kernel STORES the whole
+//       band of a row, zeros included (AttnBwdKArgs.g_band_only: only the band's margins are zeroed beforehand; without
+//       it G is added to with the exact pair's atomics).  With
+//       kept logits and such a G the key-stationary kernel stores dS into G itself (g_from_kv) and the query-stationary
+//       one, launched last, only reads it back for dQ += dS K.
+//   pack_rel_T_kernel,            the table rows G covers as the transposed, zero-padded operand of dQ += G E, and dE back
+//   unpack_drel_kernel            from the weight-gradient GEMM's padded layout into d_rel.  The two products themselves run on
+//       the banded GEMM (gemm_split_f32.hip: GemmExtra's window) or the batched 1x1 convolution, and on the batched
+//       weight-gradient GEMM (conv_wgrad_f32.hip: WgradBand).
+//   attn_bwd_tail_kernel          one or two query rows / keys beyond the last full 128-row block (attention_tail_rows) in exact
+//       fp32, one workgroup per (batch, head) and row, both roles in one launch; behind the split pair only.
+//   attn_zero_f4_kernel,          G zeroed in full, or only the kMargin columns on either side of each row's band.
+//   attn_zero_margins_kernel
 //
 // Replaces autograd through the attention of the absent package
 // VQCPCB.transformer.transformer_custom behind `loss.backward()`
@@ -27,33 +43,11 @@
 #include "device_prims.h"
 #include "isi_common.h"
 #include "isi_internal.h"
-#include "knobs.h"
 #include "prof.h"
-#include "rel_attention.h"
+#include "rel_attention_dev.h"
 #include "split_bf16.h"
 
 namespace isi {
-
-struct AttnBwdKArgs {
-  const float *q, *k, *v, *e, *mask, *dout, *out, *lse;
-  float *dsum;            // [B,H,Sq]
-  float *dq, *dk, *dv;
-  float *g;               // [H][Sq][B][Rp]: rows query-major, so that the rows of a GEMM tile share their band of columns
-  unsigned q_bytes, k_bytes, v_bytes, e_bytes, o_bytes;
-  int Sq, Sk, H, B;
-  int nqb, nkb;           // stationary query / key blocks the split kernels run (all, or only the full ones)
-  int q_ss, q_sb, q_sh, k_ss, k_sb, k_sh, v_ss, v_sb, v_sh, o_ss, o_sb, o_sh;  // element strides
-  int Cq, Ck, Ek, R, Rp;
-  int rho_lo;             // G column c holds table row rho_lo + c (causal modes only touch half of the table)
-  int g_band_only;        // G is zeroed only around its band: EVERY (query, key) pair the mask allows is stored (zeros too)
-  int mask_mode;
-  float scale;
-  const float *logits;    // optional [B,H,Sq,ldl]: the forward's base-2 logits of the allowed pairs (isi_attn_args.logits):
-  int ldl;                // the split kernels read them instead of forming Q K^T and the skewed band product again
-  int g_from_kv;          // (kept logits, Cq = Ck = 1, band-only G) the KEY-stationary kernel stores dS into G -- lanes run
-                          // along keys: 128-byte runs of a query's row -- and the query-stationary kernel only reads it back
-                          // for dQ += dS K: no second exp / dO V^T / dS pass, no V tiles, no scatter
-};
 
 namespace {
 constexpr int RING = 256;      // rows of the band ring (power of two, >= BAND + 32)
@@ -1501,40 +1495,6 @@ __global__ void unpack_drel_kernel(const float *__restrict__ dw, float *__restri
 }
 
 namespace {
-struct BwdLayout {
-  int Rp, Kp;                                // padded table rows (x4) / GEMM K of the table (x32) ; Kp: head dim x32
-  size_t dsum, g, wT, dw, wg, total;         // float offsets into the workspace
-  size_t wg_floats;
-};
-// Table rows a (query, key) pair can select: causal / anti-causal self-attention (Cq == Ck) only ever
-// reaches the upper / lower half of the table, which halves G and the two GEMMs over it.
-void rho_range(const isi_attn_args *g, int *lo, int *n) {
-  const int R = g->rel_rows;
-  *lo = 0; *n = R;
-  if (g->Cq == g->Ck && !g->dense_mask) {
-    if (g->mask_mode == 1) { *lo = std::min(std::max(g->Ek - 1, 0), R - 1); *n = R - *lo; }   // j <= i: rho >= Ek - 1
-    if (g->mask_mode == 2) { *n = std::max(1, std::min(R, g->Ek)); }                           // j >= i: rho <= Ek - 1
-  }
-}
-BwdLayout bwd_layout(int B, int H, int Sq, int R, int HD) {   // R = number of table rows G covers
-  BwdLayout L;
-  L.Rp = (int)round_up((size_t)std::max(R, 1), kBK);      // (a whole number of K chunks: G is a GEMM operand as it stands)
-  L.Kp = (int)round_up((size_t)HD, kBK);
-  size_t off = 0;
-  auto take = [&](size_t n) { const size_t o = off; off += round_up(n, 64); return o; };
-  L.dsum = take((size_t)B * H * Sq);
-  if (R > 0) {
-    L.g = take((size_t)H * B * Sq * L.Rp);
-    L.wT = take((size_t)H * HD * round_up((size_t)L.Rp, kBK));
-    L.dw = take((size_t)H * L.Rp * L.Kp);
-    L.wg_floats = conv_wgrad_batched_workspace_floats(L.Rp, HD, B * Sq, 1, H);
-    L.wg = take(L.wg_floats);
-  } else {
-    L.g = L.wT = L.dw = L.wg = 0; L.wg_floats = 0;
-  }
-  L.total = off;
-  return L;
-}
 // ---- the one or two rows / keys beyond the last full 128-row block (attention_tail_rows: the prior's sequences are
 // 1024 codes + a start row).  As a stationary block of the kernels above such a row costs as much as 128 of them -- a
 // third round of workgroups on the 256 CUs for one row per (batch, head): 1252 vs 1007 us for the dense 1025 x 1025
@@ -1704,26 +1664,9 @@ __global__ __launch_bounds__(TAIL_THREADS) void attn_bwd_tail_kernel(const AttnB
   else attn_bwd_tail_key<HD>(p, part, p.Sk - tail_k + (z - tail_q));
 }
 
-template <int HD>
-int launch_bwd_tails(const AttnBwdKArgs &a, int tail_q, int tail_k, hipStream_t stream) {
-  hipLaunchKernelGGL(attn_bwd_tail_kernel<HD>, dim3(a.H, a.B, tail_q + tail_k), dim3(TAIL_THREADS), 0, stream, a, tail_q, tail_k);
-  return check_launch("attn_bwd_tail");
-}
-}  // namespace
-
-size_t rel_attention_bwd_workspace_floats(const isi_attn_args *g) {
-  if (!g || g->B <= 0 || g->H <= 0 || g->Sq <= 0) return 0;
-  int lo = 0, n = 0;
-  if (g->rel_embeddings && g->rel_rows > 0) rho_range(g, &lo, &n);
-  return bwd_layout(g->B, g->H, g->Sq, n, g->head_dim).total;
-}
-
-// which: 1 = the key-stationary kernel (dK, dV), 2 = the query-stationary one (dQ, G), 3 = both
-template <int HD, bool ONE, bool SAVED = false>
-static int launch_bwd_split(const AttnBwdKArgs &a, hipStream_t stream, int which = 3) {
-  if constexpr (!SAVED) {
-    if (a.logits) return launch_bwd_split<HD, ONE, true>(a, stream, which);
-  }
+// ------------------------------------------------------------------ launchers (rel_attention.h)
+template <int HD, bool ONE, bool SAVED>
+int launch_bwd_split(const AttnBwdKArgs &a, int which, hipStream_t stream) {
   auto kq = rel_attention_bwd_q_split_kernel<HD, ONE, SAVED>;
   auto kkv = rel_attention_bwd_kv_split_kernel<HD, ONE, SAVED>;
   constexpr int VR = ((HD + 31) / 32) * 32;
@@ -1754,9 +1697,14 @@ static int launch_bwd_split(const AttnBwdKArgs &a, hipStream_t stream, int which
   }
   return ISI_OK;
 }
+template <int HD>
+int launch_bwd_split_hd(const AttnBwdKArgs &a, bool one, bool saved, int which, hipStream_t stream) {
+  if (one) return saved ? launch_bwd_split<HD, true, true>(a, which, stream) : launch_bwd_split<HD, true, false>(a, which, stream);
+  return saved ? launch_bwd_split<HD, false, true>(a, which, stream) : launch_bwd_split<HD, false, false>(a, which, stream);
+}
 
 template <int HD>
-static int launch_bwd(const AttnBwdKArgs &a, hipStream_t stream) {
+int launch_bwd(const AttnBwdKArgs &a, hipStream_t stream) {
   auto kq = rel_attention_bwd_q_kernel<HD>;
   auto kkv = rel_attention_bwd_kv_kernel<HD>;
   constexpr size_t smem = (size_t)((128 + RING) * (HD + 4) + 4 * 32 * SRLD + 192) * sizeof(float);
@@ -1783,169 +1731,70 @@ static int launch_bwd(const AttnBwdKArgs &a, hipStream_t stream) {
   return check_launch("rel_attention_bwd_q");
 }
 
-int rel_attention_bwd_f32(const isi_attn_bwd_args *ga, hipStream_t stream) {
-  if (!ga) return invalid("rel_attention_bwd: null pointer");
-  const isi_attn_args *g = &ga->fwd;
-  if (!g->lse || !ga->d_out || !ga->dq || !ga->dk || !ga->dv || !ga->workspace) return invalid("rel_attention_bwd: null pointer");
-  AttnSpans sp;
-  const uintptr_t own_ptrs = reinterpret_cast<uintptr_t>(ga->d_out) | reinterpret_cast<uintptr_t>(ga->dq) |
-                             reinterpret_cast<uintptr_t>(ga->dk) | reinterpret_cast<uintptr_t>(ga->dv) |
-                             reinterpret_cast<uintptr_t>(ga->workspace);
-  if (const int rc = attn_check_common(g, "rel_attention_bwd", own_ptrs, &sp)) return rc;
-  if (g->head_dim != 16 && g->head_dim != 32 && g->head_dim != 64)
-    return unsupported("rel_attention_bwd: head_dim must be 16, 32 or 64");
-  if (31 / g->Cq + 127 / g->Ck + 1 > BAND) return unsupported("rel_attention_bwd: band too wide");   // the key-stationary tiles
-  const bool has_e = g->rel_embeddings != nullptr;
-  if (has_e && (g->rel_rows <= 0 || !ga->d_rel)) return invalid("rel_attention_bwd: rel_rows / d_rel missing");
-  const int64_t lim = (int64_t)1 << 30;
-  const int HD = g->head_dim;
-  int rho_lo = 0, rho_n = 0;
-  if (has_e) rho_range(g, &rho_lo, &rho_n);
-  const BwdLayout L = bwd_layout(g->B, g->H, g->Sq, rho_n, HD);
-  if (ga->workspace_floats < L.total) { set_last_error("rel_attention_bwd: workspace too small"); return ISI_E_WORKSPACE; }
-  if (has_e && (int64_t)g->H * g->B * g->Sq * L.Rp > lim) return unsupported("rel_attention_bwd: G spans 4 GiB or more");
+template <int HD>
+int launch_bwd_tails(const AttnBwdKArgs &a, int tail_q, int tail_k, hipStream_t stream) {
+  hipLaunchKernelGGL(attn_bwd_tail_kernel<HD>, dim3(a.H, a.B, tail_q + tail_k), dim3(TAIL_THREADS), 0, stream, a, tail_q, tail_k);
+  return check_launch("attn_bwd_tail");
+}
+}  // namespace
 
-  AttnBwdKArgs a;
-  memset(&a, 0, sizeof a);
-  attn_fill_common(a, g, sp);
-  a.dout = ga->d_out;
-  a.dsum = ga->workspace + L.dsum;
-  a.dq = ga->dq; a.dk = ga->dk; a.dv = ga->dv;
-  a.g = has_e ? ga->workspace + L.g : nullptr;
-  a.o_bytes = (unsigned)(sp.o * 4);
-  a.Rp = L.Rp; a.rho_lo = rho_lo;
-  if (g->logits) {      // the forward's logits (isi_attn_args.logits): read by the split kernels
-    if (g->precision < 1) return unsupported("rel_attention_bwd: kept logits go with the 16-bit modes (precision >= 1)");
-    if (g->logits_ld < ((g->Sk + 31) & ~31) || (g->logits_ld & 3) || (reinterpret_cast<uintptr_t>(g->logits) & 15) ||
-        g->logits_ld > ((int64_t)1 << 30))
-      return invalid("rel_attention_bwd: logits_ld must be a multiple of 4, at least Sk rounded up to 32; logits 16-byte aligned");
-    a.logits = g->logits; a.ldl = (int)g->logits_ld;
-  }
+int launch_attn_dsum(const AttnBwdKArgs &a, int head_dim, hipStream_t st) {
+  const int nstat = a.B * a.H * a.Sq;
+  hipLaunchKernelGGL(attn_dsum_kernel, dim3((unsigned)(((int64_t)nstat * (head_dim / 4) + 255) / 256)), dim3(256), 0, st, a, head_dim);
+  return check_launch("attn_dsum");
+}
 
-  const int nstat = g->B * g->H * g->Sq;
-  hipLaunchKernelGGL(attn_dsum_kernel, dim3((unsigned)(((int64_t)nstat * (HD / 4) + 255) / 256)), dim3(256), 0, stream, a, HD);
-  int rc = check_launch("attn_dsum");
-  if (rc) return rc;
-  const bool split = g->precision >= 1;
-  // G's band per query (columns rho - rho_lo; Cq = Ck = 1): [i + bot, i + top] unmasked, [top, i + top] causal,
-  // [i + bot, top] anti-causal -- the two products over G skip what lies outside it
-  const int KpT = (int)round_up((size_t)L.Rp, kBK);
-  const int Mg = g->Sq * g->B;
-  const bool unique = has_e && g->Cq == 1 && g->Ck == 1;
-  const int top = g->Ek - 1 - rho_lo, bot = g->Ek - g->Sk - rho_lo;
-  const int lo_slope = g->mask_mode == 1 ? 0 : 1, lo_base = g->mask_mode == 1 ? top : bot;
-  const int hi_slope = g->mask_mode == 2 ? 0 : 1, hi_base = top;
-  const bool gemm_path = has_e && split && KpT == L.Rp && g->q_ss == (int64_t)g->B * g->q_sb && gemm_split_applicable(Mg, HD, L.Rp, 1) &&
-                         !knobs().no_gemm_kernel;
-  // ... and then only the margins of the band have to be zeroed (attn_zero_margins_kernel)
-  const bool band_only = unique && gemm_path && !knobs().attn_full_zero;
-  a.g_band_only = band_only ? 1 : 0;
-  if (has_e) {
-    if (band_only) {
-      const long rows = (long)g->H * g->Sq * g->B;
-      hipLaunchKernelGGL(attn_zero_margins_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, a.g, rows, g->Sq, g->B,
-                         L.Rp, lo_slope, lo_base, hi_slope, hi_base);
-      if ((rc = check_launch("attn_zero_margins"))) return rc;
-    } else {
-      // (a kernel, not hipMemsetAsync: a memset node inside a recorded training step -- a replayed HIP graph -- was followed by
-      // reductions that read unwritten partial sums in ~3 % of the replays on ROCm 7.2 with graph packet capture)
-      const size_t n4 = (size_t)g->H * g->B * g->Sq * L.Rp / 4;       // Rp is a multiple of 4
-      hipLaunchKernelGGL(attn_zero_f4_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 4096)), dim3(256), 0, stream,
-                         reinterpret_cast<float4 *>(a.g), n4);
-      if ((rc = check_launch("attn_zero(G)"))) return rc;
-    }
-  }
-  const bool one = g->precision == 2;     // single-term bf16 products, like the forward of that mode
-  // rows / keys beyond the last full block that go through the one-row kernels (the G row of such a query is written
-  // with one key per column, which needs Ck = 1)
-  const int tail_q = (split && (!has_e || g->Ck == 1)) ? attention_tail_rows(g->Sq, g->mask_mode, g->dense_mask != nullptr) : 0;
-  const int tail_k = split ? attention_tail_rows(g->Sk, g->mask_mode, g->dense_mask != nullptr) : 0;
-  a.nqb = tail_q ? g->Sq / QB : (g->Sq + QB - 1) / QB;
-  a.nkb = tail_k ? g->Sk / QB : (g->Sk + QB - 1) / QB;
-  // kept logits and a band-only G: the key-stationary kernel (and the one-key kernel) store dS into G, the query-stationary
-  // kernel runs last and reads it back (AttnBwdKArgs.g_from_kv; ISI_ATTN_G_FROM_KV=0: every kernel forms its own dS)
-  a.g_from_kv = (split && band_only && a.logits && knobs().attn_g_from_kv) ? 1 : 0;
-  auto run_split = [&](int which) {
-    switch (HD) {
-      case 16: return one ? launch_bwd_split<16, true>(a, stream, which) : launch_bwd_split<16, false>(a, stream, which);
-      case 32: return one ? launch_bwd_split<32, true>(a, stream, which) : launch_bwd_split<32, false>(a, stream, which);
-      default: return one ? launch_bwd_split<64, true>(a, stream, which) : launch_bwd_split<64, false>(a, stream, which);
-    }
-  };
-  auto run_tails = [&]() {
-    return HD == 16 ? launch_bwd_tails<16>(a, tail_q, tail_k, stream) : HD == 32 ? launch_bwd_tails<32>(a, tail_q, tail_k, stream)
-                                                                               : launch_bwd_tails<64>(a, tail_q, tail_k, stream);
-  };
-  if (!split) {
-    rc = HD == 16 ? launch_bwd<16>(a, stream) : HD == 32 ? launch_bwd<32>(a, stream) : launch_bwd<64>(a, stream);
-    if (!rc && (tail_q || tail_k)) rc = run_tails();
-  } else if (a.g_from_kv) {
-    rc = run_split(1);
-    if (!rc && (tail_q || tail_k)) rc = run_tails();      // (the one-key kernel stores its column of G)
-    if (!rc) rc = run_split(2);
-  } else {
-    rc = run_split(3);
-    if (!rc && (tail_q || tail_k)) rc = run_tails();
-  }
-  if (rc || !has_e) return rc;
+// (a kernel, not hipMemsetAsync: a memset node inside a recorded training step -- a replayed HIP graph -- was followed by
+// reductions that read unwritten partial sums in ~3 % of the replays on ROCm 7.2 with graph packet capture)
+int launch_attn_zero_g(float *g, size_t n4, hipStream_t st) {
+  hipLaunchKernelGGL(attn_zero_f4_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 4096)), dim3(256), 0, st,
+                     reinterpret_cast<float4 *>(g), n4);
+  return check_launch("attn_zero(G)");
+}
 
-  // ---- dQ += G E  and  dE = G^T Q, head by head, on the GEMM kernels
-  const int R = g->rel_rows;
-  float *wT = ga->workspace + L.wT;
-  {
-    const int64_t total = (int64_t)g->H * HD * KpT;
-    hipLaunchKernelGGL(pack_rel_T_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
-                       g->rel_embeddings, wT, g->H, R, HD, KpT, rho_lo, rho_n);
-    if ((rc = check_launch("pack_rel_T"))) return rc;
+int launch_attn_zero_g_margins(float *g, long rows, int Sq, int B, int Rp, int lo_slope, int lo_base, int hi_slope, int hi_base,
+                               hipStream_t st) {
+  hipLaunchKernelGGL(attn_zero_margins_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, g, rows, Sq, B, Rp, lo_slope,
+                     lo_base, hi_slope, hi_base);
+  return check_launch("attn_zero_margins");
+}
+
+int launch_attn_bwd_split(const AttnBwdKArgs &a, int head_dim, bool one, bool saved, int which, hipStream_t st) {
+  switch (head_dim) {
+    case 16: return launch_bwd_split_hd<16>(a, one, saved, which, st);
+    case 32: return launch_bwd_split_hd<32>(a, one, saved, which, st);
+    case 64: return launch_bwd_split_hd<64>(a, one, saved, which, st);
+    default: return unsupported("rel_attention_bwd: head_dim must be 16, 32 or 64");
   }
-  const int gemm_flags = g->precision >= 1 ? ISI_CONV_BF16X3 : 0;   // same product mode as the attention kernels
-  {
-    // all heads in one launch each (grid z = head): G_h [B*Sq, Rp] x E_h^T, accumulated into dq's head slice ...
-    isi_src sg;
-    memset(&sg, 0, sizeof sg);
-    sg.ptr = a.g; sg.C = L.Rp; sg.sn = (int64_t)g->B * L.Rp; sg.sc = 1; sg.sh = L.Rp; sg.sw = L.Rp;   // "image" = [Sq][B][1]
-    isi_src res;
-    memset(&res, 0, sizeof res);
-    res.ptr = ga->dq; res.C = HD; res.sn = g->q_ss; res.sc = 1; res.sh = g->q_sb; res.sw = g->q_sb;
-    isi_dst dst;
-    memset(&dst, 0, sizeof dst);
-    dst.ptr = ga->dq; dst.sn = g->q_ss; dst.sc = 1; dst.sh = g->q_sb; dst.sw = g->q_sb;
-    const int64_t zs_g = (int64_t)g->B * g->Sq * L.Rp;
-    // Rows of G are (query, batch): with one channel per event on both sides the non-zero columns of query i are the
-    // band [i + Ek - Sk, i + Ek - 1] - rho_lo (unmasked), [Ek - 1, i + Ek - 1] - rho_lo (causal) ... -- a 128-row
-    // tile holds 128 / B queries, its band is about half of the table: the GEMM kernel skips the other K chunks
-    GemmExtra gx;
-    memset(&gx, 0, sizeof gx);
-    gx.nz = g->H; gx.zs_a = zs_g; gx.zs_w = (int64_t)HD * KpT; gx.zs_res = g->q_sh; gx.zs_out = g->q_sh;
-    if (g->Cq == 1 && g->Ck == 1) {
-      gx.win_rpu = g->B;
-      gx.lo_slope = lo_slope; gx.lo_base = lo_base; gx.hi_slope = hi_slope; gx.hi_base = hi_base;
-    }
-    if (gemm_path)
-      rc = gemm_split_f32(a.g, L.Rp, wT, nullptr, ga->dq, g->q_sb, ga->dq, g->q_sb, Mg, HD, L.Rp, 0, 1, stream, nullptr, &gx);
-    else
-    rc = conv2d_batched_f32(&sg, nullptr, wT, nullptr, &res, &dst, g->Sq, g->B, 1, HD, 1, 1, 1, 0, gemm_flags, g->H,
-                            zs_g, (int64_t)HD * KpT, g->q_sh, g->q_sh, stream);
-    if (rc) return rc;
-    // ... and dE_h = G_h^T Q_h, the pixel-reduction GEMM; column c of G is non-zero on the queries [c - top, c - bot]
-    // (unmasked), from c - top on (causal), up to c - bot (anti-causal): the kernel reads only those rows
-    const WgradBand wb{g->B, g->mask_mode == 2 ? 0 : 1, g->mask_mode == 2 ? 0 : -top,
-                       g->mask_mode == 1 ? 0 : 1, g->mask_mode == 1 ? g->Sq - 1 : -bot, band_only ? 1 : 0};
-    isi_src sq;
-    memset(&sq, 0, sizeof sq);
-    sq.ptr = g->q; sq.C = HD; sq.sn = g->q_ss; sq.sc = 1; sq.sh = g->q_sb; sq.sw = g->q_sb;
-    rc = conv_wgrad_batched_f32(&sq, nullptr, a.g, ga->workspace + L.dw, nullptr, ga->workspace + L.wg, L.wg_floats,
-                                g->Sq, g->B, 1, L.Rp, 1, 1, 1, 0, gemm_flags, g->H, g->q_sh, zs_g,
-                                (int64_t)L.Rp * L.Kp, stream, 0, gx.win_rpu ? &wb : nullptr);
-    if (rc) return rc;
+}
+
+int launch_attn_bwd_tails(const AttnBwdKArgs &a, int head_dim, int tail_q, int tail_k, hipStream_t st) {
+  switch (head_dim) {
+    case 16: return launch_bwd_tails<16>(a, tail_q, tail_k, st);
+    case 32: return launch_bwd_tails<32>(a, tail_q, tail_k, st);
+    case 64: return launch_bwd_tails<64>(a, tail_q, tail_k, st);
+    default: return unsupported("rel_attention_bwd: head_dim must be 16, 32 or 64");
   }
-  {
-    const int64_t total = (int64_t)g->H * R * HD;
-    hipLaunchKernelGGL(unpack_drel_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
-                       ga->workspace + L.dw, ga->d_rel, g->H, R, HD, L.Rp, L.Kp, rho_lo, rho_n);
-    rc = check_launch("unpack_drel");
+}
+int launch_attn_bwd_exact(const AttnBwdKArgs &a, int head_dim, hipStream_t st) {
+  switch (head_dim) {
+    case 16: return launch_bwd<16>(a, st);
+    case 32: return launch_bwd<32>(a, st);
+    case 64: return launch_bwd<64>(a, st);
+    default: return unsupported("rel_attention_bwd: head_dim must be 16, 32 or 64");
   }
-  return rc;
+}
+
+int launch_pack_rel_T(const float *e, float *out, int H, int R, int HD, int Kpad, int lo, int n, hipStream_t st) {
+  const int64_t total = (int64_t)H * HD * Kpad;
+  hipLaunchKernelGGL(pack_rel_T_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, e, out, H, R, HD, Kpad, lo, n);
+  return check_launch("pack_rel_T");
+}
+
+int launch_unpack_drel(const float *dw, float *out, int H, int R, int HD, int Rp, int Kp, int lo, int n, hipStream_t st) {
+  const int64_t total = (int64_t)H * R * HD;
+  hipLaunchKernelGGL(unpack_drel_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, dw, out, H, R, HD, Rp, Kp, lo, n);
+  return check_launch("unpack_drel");
 }
 
 int rel_attention_bwd_debug_stamps(long long *host, int n) {

@@ -23,15 +23,14 @@
 //   O^T  += V^T P^T          (P^T is already the B fragment: accumulator r of a
 //                             lane is the k-slot of MFMA step r)
 //
-// This file holds the exact-fp32 kernel (precision 0), the one-row tail kernel and the public dispatcher
-// rel_attention_f32(); the 16-bit precisions run the kernels of rel_attention_fwd2.hip / rel_attention_fwd3.hip
-// (attn_fwd_route below decides which).
+// This file holds the exact-fp32 kernel (precision 0), the one-row tail kernel and their launchers (rel_attention.h); the
+// 16-bit precisions run the kernels of rel_attention_fwd2.hip / rel_attention_fwd3.hip.  Which kernel a call runs is
+// the host plan's decision (rel_attention_run.cpp: attn_fwd_route).
 #include "device_prims.h"
 #include "isi_common.h"
 #include "isi_internal.h"
-#include "knobs.h"
 #include "prof.h"
-#include "rel_attention.h"
+#include "rel_attention_dev.h"
 
 namespace isi {
 
@@ -417,8 +416,9 @@ __global__ __launch_bounds__(512) void attn_fwd_tail_row_kernel(const AttnKArgs 
   }
 }
 
+namespace {
 template <int HD>
-static int launch_attn(const AttnKArgs &a, int B, hipStream_t stream) {
+int launch_attn(const AttnKArgs &a, hipStream_t stream) {
   auto kern = rel_attention_f32_kernel<HD>;
   constexpr size_t smem = (size_t)((128 + RING) * (HD + 4) + 8 * 32 * SRLD) * sizeof(float) + 64 * sizeof(int);
   static DeviceOnce attr_set;
@@ -428,91 +428,32 @@ static int launch_attn(const AttnKArgs &a, int B, hipStream_t stream) {
       return check_launch("hipFuncSetAttribute(rel_attention)");
     attr_set.mark();
   }
-  const double pairs = (double)a.Sq * a.Sk * (a.mask_mode ? 0.5 : 1.0) * a.H * B;
+  const double pairs = (double)a.Sq * a.Sk * (a.mask_mode ? 0.5 : 1.0) * a.H * a.B;
   prof::Scope scope(prof::K_REL_ATTENTION, 2.0 * pairs * HD * (a.e ? 3 : 2),
-                    4.0 * B * a.H * HD * (2.0 * a.Sq + 2.0 * a.Sk), stream);
-  ISI_PROF_LAUNCH(scope, kern, dim3((a.Sq + QB - 1) / QB, a.H, B), dim3(512), smem, stream, a);
+                    4.0 * a.B * a.H * HD * (2.0 * a.Sq + 2.0 * a.Sk), stream);
+  ISI_PROF_LAUNCH(scope, kern, dim3((a.Sq + QB - 1) / QB, a.H, a.B), dim3(512), smem, stream, a);
   return check_launch("rel_attention_f32");
 }
+}  // namespace
 
-// The one routing decision of the forward.  Exact fp32 has its own kernel; the 16-bit precisions run the 64-key-tile
-// kernels (rel_attention_fwd2.hip) or, with a workspace for its operand planes, the plane-staged kernel
-// (rel_attention_fwd3.hip) where that one takes the shape.
-enum class AttnFwd { F32, Tiles64, Planes };
-enum class AttnWs { None, Given, Query };   // Query: no workspace yet, the caller asks whether to bring one
-static AttnFwd attn_fwd_route(const AttnKArgs &a, int head_dim, int precision, AttnWs ws) {
-  if (precision == 0) return AttnFwd::F32;
-  // the plane-staged kernel pays a pack launch (10-13 us at B 8 x H 8 x S 1025): measured, it wins with three-term products
-  // (causal 91 vs 96 us, unmasked 127 vs 141) and loses 3-4 us with single-term ones -- those ask for no workspace unless
-  // ISI_ATTN_FWD3_ALL is set (a caller that hands one over anyway gets the plane-staged kernel)
-  if (ws == AttnWs::Query && precision != 1 && !knobs().attn_fwd3_all) return AttnFwd::Tiles64;
-  if (ws == AttnWs::None || knobs().attn_no_fwd3 || !rel_attention_fwd3_ok(a, head_dim, precision)) return AttnFwd::Tiles64;
-  return AttnFwd::Planes;
-}
-
-int rel_attention_f32(const isi_attn_args *g, hipStream_t stream) {
-  AttnSpans sp;
-  if (const int rc = attn_check_common(g, "rel_attention", 0, &sp)) return rc;
-  AttnKArgs a;
-  attn_fill_common(a, g, sp);
-  if (g->precision < 0 || g->precision > 3) return invalid("rel_attention: precision must be 0 .. 3");
-  // 0 fp32 pipe | 1 three-term split-bf16 | 2 single-term bf16 | 3 single-term f16
-  a.split = g->precision == 1 ? 1 : g->precision >= 2 ? 2 : 0;
-  const AttnFwd route = attn_fwd_route(a, g->head_dim, g->precision, g->workspace ? AttnWs::Given : AttnWs::None);
-  a.logits = g->logits; a.ldl = (int)g->logits_ld;
-  if (a.logits) {
-    if (g->logits_ld < ((g->Sk + 31) & ~31) || (g->logits_ld & 3) || (reinterpret_cast<uintptr_t>(a.logits) & 15))
-      return invalid("rel_attention: logits_ld must be a multiple of 4, at least Sk rounded up to 32; logits 16-byte aligned");
-    if ((int64_t)g->B * g->H * g->Sq * g->logits_ld > ((int64_t)1 << 40)) return unsupported("rel_attention: logits buffer too large");
-    if (route == AttnFwd::F32)
-      return unsupported("rel_attention: the logits are stored by the 64-key-tile kernels only (precision >= 1)");
-  }
-  if (a.e && a.R <= 0) return invalid("rel_attention: rel_rows must be positive");
-  // One or two rows beyond the last full query block (the prior's sequences are 1024 codes + a start row) would be a
-  // block of their own that runs as long as a full one: 576 instead of 512 workgroups on 256 CUs -- a third round
-  // for one row per (batch, head) (244 vs 165 us, dense, B 8 x H 8 x 1025 x 1025).  They go through a one-row kernel
-  // instead (attn_fwd_tail_row_kernel: exact fp32, one workgroup per (batch, head) and row).
-  const int tail = attention_tail_rows(g->Sq, g->mask_mode, g->dense_mask != nullptr);
-  const bool split_tail = a.split && tail > 0;
-  a.nblk = split_tail ? g->Sq / QB : (g->Sq + QB - 1) / QB;
-  int rc;
-  if (route == AttnFwd::Planes) {
-    // operands as 16-bit planes in the caller's workspace, staged by LDS-DMA
-    rc = rel_attention_fwd3(a, g->head_dim, g->precision, g->workspace, g->workspace_bytes, stream);
-  } else if (route == AttnFwd::Tiles64) {
-    rc = rel_attention_fwd2(a, g->head_dim, g->precision, stream);
-  } else
-  switch (g->head_dim) {
-    case 16: rc = launch_attn<16>(a, g->B, stream); break;
-    case 32: rc = launch_attn<32>(a, g->B, stream); break;
-    case 64: rc = launch_attn<64>(a, g->B, stream); break;
+int launch_attn_fwd_exact(const AttnKArgs &a, int head_dim, hipStream_t st) {
+  switch (head_dim) {
+    case 16: return launch_attn<16>(a, st);
+    case 32: return launch_attn<32>(a, st);
+    case 64: return launch_attn<64>(a, st);
     default: return unsupported("rel_attention: head_dim must be 16, 32 or 64");
   }
-  if (rc || !split_tail) return rc;
-  const dim3 tgrid(g->H, g->B, tail);
-  switch (g->head_dim) {
-    case 16: hipLaunchKernelGGL(attn_fwd_tail_row_kernel<16>, tgrid, dim3(512), 0, stream, a, g->Sq - tail); break;
-    case 32: hipLaunchKernelGGL(attn_fwd_tail_row_kernel<32>, tgrid, dim3(512), 0, stream, a, g->Sq - tail); break;
-    default: hipLaunchKernelGGL(attn_fwd_tail_row_kernel<64>, tgrid, dim3(512), 0, stream, a, g->Sq - tail); break;
+}
+
+int launch_attn_fwd_tail_rows(const AttnKArgs &a, int head_dim, int row0, int rows, hipStream_t st) {
+  const dim3 tgrid(a.H, a.B, rows);
+  switch (head_dim) {
+    case 16: hipLaunchKernelGGL(attn_fwd_tail_row_kernel<16>, tgrid, dim3(512), 0, st, a, row0); break;
+    case 32: hipLaunchKernelGGL(attn_fwd_tail_row_kernel<32>, tgrid, dim3(512), 0, st, a, row0); break;
+    case 64: hipLaunchKernelGGL(attn_fwd_tail_row_kernel<64>, tgrid, dim3(512), 0, st, a, row0); break;
+    default: return unsupported("rel_attention: head_dim must be 16, 32 or 64");
   }
   return check_launch("attn_fwd_tail_row");
-}
-
-// bytes of isi_attn_args.workspace that let the forward run its plane-staged kernel (0: that kernel does not take the call)
-size_t rel_attention_workspace_bytes(const isi_attn_args *g) {
-  if (!g || g->Sq <= 0 || g->Sk <= 0 || g->B <= 0 || g->H <= 0 || g->precision < 1 || g->precision > 3) return 0;
-  AttnKArgs a{};
-  a.e = g->rel_embeddings; a.R = g->rel_rows; a.Sq = g->Sq; a.Sk = g->Sk; a.H = g->H; a.B = g->B; a.Cq = g->Cq; a.Ck = g->Ck;
-  if (attn_fwd_route(a, g->head_dim, g->precision, AttnWs::Query) != AttnFwd::Planes) return 0;
-  return rel_attention_fwd3_workspace_bytes(a, g->head_dim, g->precision);
-}
-
-// Rows (keys, in the backward's key-stationary kernel) beyond the last full 128-row block that are NOT given a block of
-// their own: 1 or 2 of them behind at least two full blocks, unmasked attention only (under a causal mask the ragged
-// block is made the cheapest one instead, see the kernels: measured better than the extra launch).
-int attention_tail_rows(int S, int mask_mode, bool dense_mask) {
-  const int tail = S % QB;
-  return (tail >= 1 && tail <= 2 && S >= 2 * QB && !dense_mask && mask_mode == 0) ? tail : 0;
 }
 
 }  // namespace isi

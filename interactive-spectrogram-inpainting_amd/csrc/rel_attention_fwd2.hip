@@ -27,7 +27,7 @@
 #include "isi_common.h"
 #include "isi_internal.h"
 #include "prof.h"
-#include "rel_attention.h"
+#include "rel_attention_dev.h"
 #include "split_bf16.h"
 
 namespace isi {
@@ -583,7 +583,7 @@ int rel_attention_fwd2_debug_stamps(long long *host, int n) {
 
 namespace {
 template <int HD, int TERMS, bool F16, bool UNIT>
-int launch_fwd2_t(const AttnKArgs &a, hipStream_t stream) {
+int launch_fwd2_t(const AttnKArgs &a, int nW, hipStream_t stream) {
   auto kern = rel_attn_fwd2_kernel<HD, TERMS, F16, UNIT>;
   constexpr size_t smem = Tile<HD, TERMS>::smem;
   static_assert(smem <= 160 * 1024, "LDS budget");
@@ -593,12 +593,7 @@ int launch_fwd2_t(const AttnKArgs &a, hipStream_t stream) {
       return check_launch("hipFuncSetAttribute(rel_attn_fwd2)");
     attr_set.mark();
   }
-  // workgroups per (batch, head) pair: one block each while the chip is not full; otherwise as many as give every CU one
-  // persistent workgroup, at most one per two blocks under a mask (a heavy and a light block each)
-  const int pairs = a.H * a.B, cus = current_device_cu_count();
-  int nW = a.nblk;
-  if ((int64_t)pairs * a.nblk > cus)
-    nW = std::max(1, std::min(a.mask_mode ? (a.nblk + 1) / 2 : a.nblk, cus / pairs));
+  const int pairs = a.H * a.B;
   const double npairs = (double)a.Sq * a.Sk * (a.mask_mode ? 0.5 : 1.0) * pairs;
   prof::Scope scope(prof::K_REL_ATTENTION, 2.0 * npairs * HD * (a.e ? 3 : 2),
                     4.0 * pairs * HD * (2.0 * a.Sq + 2.0 * a.Sk), stream);
@@ -606,22 +601,22 @@ int launch_fwd2_t(const AttnKArgs &a, hipStream_t stream) {
   return check_launch("rel_attn_fwd2");
 }
 template <int HD>
-int launch_fwd2_hd(const AttnKArgs &a, int precision, hipStream_t stream) {
+int launch_fwd2_hd(const AttnKArgs &a, int precision, int nW, hipStream_t stream) {
   const bool unit = a.Cq == 1 && a.Ck == 1;
   switch (precision) {
-    case 1: return unit ? launch_fwd2_t<HD, 3, false, true>(a, stream) : launch_fwd2_t<HD, 3, false, false>(a, stream);
-    case 2: return unit ? launch_fwd2_t<HD, 1, false, true>(a, stream) : launch_fwd2_t<HD, 1, false, false>(a, stream);
-    case 3: return unit ? launch_fwd2_t<HD, 1, true, true>(a, stream) : launch_fwd2_t<HD, 1, true, false>(a, stream);
+    case 1: return unit ? launch_fwd2_t<HD, 3, false, true>(a, nW, stream) : launch_fwd2_t<HD, 3, false, false>(a, nW, stream);
+    case 2: return unit ? launch_fwd2_t<HD, 1, false, true>(a, nW, stream) : launch_fwd2_t<HD, 1, false, false>(a, nW, stream);
+    case 3: return unit ? launch_fwd2_t<HD, 1, true, true>(a, nW, stream) : launch_fwd2_t<HD, 1, true, false>(a, nW, stream);
     default: return unsupported("rel_attention: precision");
   }
 }
 }  // namespace
 
-int rel_attention_fwd2(const AttnKArgs &a, int head_dim, int precision, hipStream_t stream) {
+int launch_attn_fwd2(const AttnKArgs &a, int head_dim, int precision, int nW, hipStream_t st) {
   switch (head_dim) {
-    case 16: return launch_fwd2_hd<16>(a, precision, stream);
-    case 32: return launch_fwd2_hd<32>(a, precision, stream);
-    case 64: return launch_fwd2_hd<64>(a, precision, stream);
+    case 16: return launch_fwd2_hd<16>(a, precision, nW, st);
+    case 32: return launch_fwd2_hd<32>(a, precision, nW, st);
+    case 64: return launch_fwd2_hd<64>(a, precision, nW, st);
     default: return unsupported("rel_attention: head_dim must be 16, 32 or 64");
   }
 }

@@ -35,7 +35,7 @@
 #include "isi_common.h"
 #include "isi_internal.h"
 #include "prof.h"
-#include "rel_attention.h"
+#include "rel_attention_dev.h"
 #include "split_bf16.h"
 
 namespace isi {
@@ -762,35 +762,9 @@ int rel_attention_fwd3_debug_stamps(long long *host, int n) {
 }
 
 namespace {
-struct PlaneLayout { int Skp, npl; size_t kv_plane, e_plane, k_off, v_off, e_off, total; };   // element counts / byte offsets
-PlaneLayout plane_layout(const AttnKArgs &a, int head_dim, int precision) {
-  PlaneLayout L;
-  L.Skp = (a.Sk + 31) & ~31;
-  L.npl = precision == 1 ? 2 : 1;
-  L.kv_plane = (size_t)a.H * a.B * L.Skp * head_dim;
-  L.e_plane = a.e ? (size_t)a.H * a.R * head_dim : 0;
-  L.k_off = 0;
-  L.v_off = round_up(L.k_off + L.npl * L.kv_plane * 2, 256);
-  L.e_off = round_up(L.v_off + L.npl * L.kv_plane * 2, 256);
-  L.total = round_up(L.e_off + L.npl * L.e_plane * 2, 256);
-  return L;
-}
-}  // namespace
-
-bool rel_attention_fwd3_ok(const AttnKArgs &a, int head_dim, int precision) {
-  if (!(a.Cq == 1 && a.Ck == 1) || !(head_dim == 64 || head_dim == 32) || precision < 1 || precision > 3 || !a.e) return false;
-  const PlaneLayout L = plane_layout(a, head_dim, precision);
-  // one buffer descriptor per operand over all its planes (32-bit offsets)
-  return L.npl * L.kv_plane * 2 < ((size_t)1 << 31) && L.npl * L.e_plane * 2 < ((size_t)1 << 31);
-}
-
-size_t rel_attention_fwd3_workspace_bytes(const AttnKArgs &a, int head_dim, int precision) {
-  return rel_attention_fwd3_ok(a, head_dim, precision) ? plane_layout(a, head_dim, precision).total : 0;
-}
-
-namespace {
+// the pack launch, then the kernel on the planes it wrote
 template <int HD, int TERMS, bool F16>
-int launch_fwd3_t(const AttnKArgs &a, const PlaneLayout &L, void *ws, hipStream_t stream) {
+int launch_fwd3_t(const AttnKArgs &a, const PlaneLayout &L, void *ws, int nW, hipStream_t stream) {
   constexpr int NPL = TERMS == 1 ? 1 : 2;
   unsigned char *base = static_cast<unsigned char *>(ws);
   PackArgs pk;
@@ -825,10 +799,7 @@ int launch_fwd3_t(const AttnKArgs &a, const PlaneLayout &L, void *ws, hipStream_
       return check_launch("hipFuncSetAttribute(rel_attn_fwd3)");
     attr_set.mark();
   }
-  const int pairs = a.H * a.B, cus = current_device_cu_count();
-  int nW = a.nblk;
-  if ((int64_t)pairs * a.nblk > cus)
-    nW = std::max(1, std::min(a.mask_mode ? (a.nblk + 1) / 2 : a.nblk, cus / pairs));
+  const int pairs = a.H * a.B;
   const double npairs = (double)a.Sq * a.Sk * (a.mask_mode ? 0.5 : 1.0) * pairs;
   prof::Scope scope(prof::K_REL_ATTENTION, 2.0 * npairs * HD * (a.e ? 3 : 2),
                     4.0 * pairs * HD * (2.0 * a.Sq + 2.0 * a.Sk), stream);
@@ -836,22 +807,23 @@ int launch_fwd3_t(const AttnKArgs &a, const PlaneLayout &L, void *ws, hipStream_
   return check_launch("rel_attn_fwd3");
 }
 template <int HD>
-int launch_fwd3_hd(const AttnKArgs &a, const PlaneLayout &L, int precision, void *ws, hipStream_t stream) {
+int launch_fwd3_hd(const AttnKArgs &a, const PlaneLayout &L, int precision, void *ws, int nW, hipStream_t stream) {
   switch (precision) {
-    case 1: return launch_fwd3_t<HD, 3, false>(a, L, ws, stream);
-    case 2: return launch_fwd3_t<HD, 1, false>(a, L, ws, stream);
-    case 3: return launch_fwd3_t<HD, 1, true>(a, L, ws, stream);
+    case 1: return launch_fwd3_t<HD, 3, false>(a, L, ws, nW, stream);
+    case 2: return launch_fwd3_t<HD, 1, false>(a, L, ws, nW, stream);
+    case 3: return launch_fwd3_t<HD, 1, true>(a, L, ws, nW, stream);
     default: return unsupported("rel_attention: precision");
   }
 }
 }  // namespace
 
-int rel_attention_fwd3(const AttnKArgs &a, int head_dim, int precision, void *workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (!rel_attention_fwd3_ok(a, head_dim, precision)) return unsupported("rel_attention_fwd3: shape");
-  const PlaneLayout L = plane_layout(a, head_dim, precision);
-  if (!workspace || workspace_bytes < L.total || (reinterpret_cast<uintptr_t>(workspace) & 255))
-    return invalid("rel_attention: workspace too small or not 256-byte aligned (isi_rel_attention_workspace_bytes)");
-  return head_dim == 64 ? launch_fwd3_hd<64>(a, L, precision, workspace, stream) : launch_fwd3_hd<32>(a, L, precision, workspace, stream);
+int launch_attn_fwd3(const AttnKArgs &a, int head_dim, int precision, const PlaneLayout &L, void *workspace, int nW,
+                     hipStream_t st) {
+  switch (head_dim) {
+    case 64: return launch_fwd3_hd<64>(a, L, precision, workspace, nW, st);
+    case 32: return launch_fwd3_hd<32>(a, L, precision, workspace, nW, st);
+    default: return unsupported("rel_attention_fwd3: shape");
+  }
 }
 
 }  // namespace isi

@@ -1025,7 +1025,9 @@ int isi_vq_num_partials(int64_t N);
  * memory.  Pair pipeline only: sources in the pair format (ISI_CONV_*_PAIR, channels-last, 32-channel multiples),
  * `packed_w16` = the packed 1x1 weight's blocked pair copy (ISI_CONV_W16: packed weight + D * Kpad floats), D = 64.
  * Pixel n = (b H + y) W + x reads src0 / src1 through their strides.  Outputs as isi_vq_nearest_f32 (bit-identical
- * to isi_conv2d_f32(ISI_CONV_F16X3 | ISI_CONV_W16) followed by it); `q_pair_out` (nullable): pair-format copy of q.
+ * to isi_conv2d_f32(ISI_CONV_F16X3 | ISI_CONV_W16) followed by it from C0 + C1 = 128 on, where that convolution runs the
+ * split products; below it runs exact-fp32 products and its z is another rounding of the same sum -- idx and counts
+ * still agree away from near-ties); `q_pair_out` (nullable): pair-format copy of q.
  * `workspace`: isi_vq_conv1x1_workspace_floats(C0, C1, D) floats, 16-byte aligned (a fragment-major copy of the
  * weight is written there by a small pre-kernel). */
 int isi_vq_conv1x1_nearest_f32(const isi_src *src0, const isi_src *src1, const float *packed_w16, const float *bias,

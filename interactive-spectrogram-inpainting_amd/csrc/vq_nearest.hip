@@ -816,35 +816,39 @@ __global__ __launch_bounds__(VQ_BLOCK) void vq_conv1x1_nearest_kernel(const VqFu
   }
 }
 
+// One term p log(max(p, 1e-7)) of the entropy H, p = counts / N (bottleneck.py:97-100), in double; the terms are summed and
+// exponentiated in double as well.  perplexity = exp(H) turns the ABSOLUTE error of H into its relative error.  In fp32 the
+// sum over 256 threads and a tree left about 2 ulp(H) of it -- 1.0e-6 of the perplexity at H = 5.25 (257 vectors on 576 codes:
+// tests/test_vq_fused_gpu.py), past what the fp32 evaluation of the same formula is allowed (8 x 2^-23); and in a flat
+// histogram every term is the SAME number, so the rounding of an fp32 p = 1 / N (weighted by log p + 1: 3e-7) and that of
+// logf (one ulp of |log p| = 5.5: 4e-7) do not average out over the terms, they add up to themselves.
+__device__ __forceinline__ double vq_entropy_term(const int32_t count, const double inv_n) {
+  const double pr = (double)count * inv_n;
+  return pr * log(fmax(pr, 1e-7));
+}
+
 __global__ void vq_finalize_kernel(const float *__restrict__ sse_part, int n_part,
                                    const int32_t *__restrict__ counts, int K, int64_t N, int D,
                                    float *__restrict__ out2) {
   __shared__ float red[256];
+  __shared__ double redh[256];
   const int tid = threadIdx.x;
   float s = 0.f;
   for (int i = tid; i < n_part; i += 256) s += sse_part[i];
+  double h = 0.0;
+  const double inv_n = 1.0 / (double)N;
+  for (int i = tid; i < K; i += 256) h += vq_entropy_term(counts[i], inv_n);
   red[tid] = s;
+  redh[tid] = h;
   __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
+  for (int o = 128; o > 0; o >>= 1) {      // both sums down one tree (the double one costs no barrier of its own)
+    if (tid < o) { red[tid] += red[tid + o]; redh[tid] += redh[tid + o]; }
     __syncthreads();
   }
   const float sse = red[0];
-  __syncthreads();
-  float h = 0.f;
-  for (int i = tid; i < K; i += 256) {
-    const float pr = (float)counts[i] / (float)N;
-    h += pr * logf(fmaxf(pr, 1e-7f));
-  }
-  red[tid] = h;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
   if (tid == 0) {
     out2[0] = sse / ((float)N * (float)D);
-    out2[1] = expf(-red[0]);
+    out2[1] = (float)exp(-redh[0]);
   }
 }
 
@@ -856,6 +860,7 @@ __global__ __launch_bounds__(512) void vq_finalize2_kernel(const float *__restri
                                                            const int32_t *__restrict__ counts_b, int K_b, int64_t N_b,
                                                            int D, float *__restrict__ out5) {
   __shared__ float red[2][256];
+  __shared__ double redh[2][256];
   __shared__ float diff[2];
   const int lvl = threadIdx.x >> 8, tid = threadIdx.x & 255;
   const float *sse_part = lvl ? sse_b : sse_t;
@@ -864,29 +869,21 @@ __global__ __launch_bounds__(512) void vq_finalize2_kernel(const float *__restri
   const int64_t N = lvl ? N_b : N_t;
   float s = 0.f;
   for (int i = tid; i < n_part; i += 256) s += sse_part[i];
+  double h = 0.0;                                    // (as vq_finalize_kernel: the same bits)
+  const double inv_n = 1.0 / (double)N;
+  for (int i = tid; i < K; i += 256) h += vq_entropy_term(counts[i], inv_n);
   red[lvl][tid] = s;
+  redh[lvl][tid] = h;
   __syncthreads();
   for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) red[lvl][tid] += red[lvl][tid + o];
+    if (tid < o) { red[lvl][tid] += red[lvl][tid + o]; redh[lvl][tid] += redh[lvl][tid + o]; }
     __syncthreads();
   }
   const float sse = red[lvl][0];
-  __syncthreads();
-  float h = 0.f;
-  for (int i = tid; i < K; i += 256) {
-    const float pr = (float)counts[i] / (float)N;
-    h += pr * logf(fmaxf(pr, 1e-7f));
-  }
-  red[lvl][tid] = h;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) red[lvl][tid] += red[lvl][tid + o];
-    __syncthreads();
-  }
   if (tid == 0) {
     const float dd = sse / ((float)N * (float)D);
     out5[2 * lvl] = dd;
-    out5[2 * lvl + 1] = expf(-red[lvl][0]);
+    out5[2 * lvl + 1] = (float)exp(-redh[lvl][0]);
     diff[lvl] = dd;
   }
   __syncthreads();

@@ -1,5 +1,6 @@
 """Helpers shared by CPU and GPU tests (test infrastructure)."""
 import collections
+import functools
 import math
 
 import numpy as np
@@ -1206,3 +1207,350 @@ def linear_case_refs(M, N, K):
     if (M, N, K) not in _linear_refs_cache:
         _linear_refs_cache[(M, N, K)] = linear_refs(M, N, K)
     return _linear_refs_cache[(M, N, K)]
+
+
+# Float64 specification of the fused quantize_conv + codebook search (vq_conv1x1_nearest_kernel of csrc/vq_nearest.hip, through
+# isi_vq_conv1x1_nearest_f32 / isi_vq_conv1x1_nearest_tape_f32), its float32 yardstick, seeded case data that is free of
+# near-ties by construction, and the comparisons of tests/test_vq_fused_gpu.py -- tests/test_vq_fused_host.py shows, without
+# a GPU, what they reject.  Activations [N, C] channels-last (N = B H W pixels), W [64, C0 + C1], embed [D = 64, K].
+VQ_FUSED_D = 64
+VQ_FUSED_TILE = 256            # VQ_VEC_PER_BLOCK_ITER: pixels of one workgroup pass (8 waves of 32)
+VQ_FUSED_GRID = 256            # vq_grid's cap: beyond 256 tiles a workgroup runs its tile loop again
+VQ_FUSED_MIN_GAP = 1e-4        # ten times quantizer_large.npz's: z is computed here and carries the convolution's rounding
+VQ_FUSED_ACT_LIMIT = 16384.0   # range of the pair format (include/isi_hip.h, ISI_CONV_F16X3): beyond it a pixel is loud
+VQ_FUSED_SSE_RTOL = 1e-5       # tolerance of `diff` throughout tests/test_hip_parity.py
+VqFusedSpec = collections.namedtuple("VqFusedSpec", "z idx q counts sse sse_rows diff perplexity")
+VqFusedCase = collections.namedtuple("VqFusedCase", "C0 C1 K B H W strided")
+
+
+def _vq_fused_top2(z, e):
+    """(two smallest distances [n, 2], their codes [n, 2]) of d[n, k] = sum_d (z[n, d] - e[k, d])^2, written out as a difference
+    (no cancelling three-term formula) in the dtype of z, in blocks of pixels.  A smaller distance first, the lower code first
+    on exact equality.  One code only: the second distance is +inf."""
+    n, K = z.shape[0], e.shape[0]
+    step = max(1, 2 ** 22 // (K * z.shape[1]))
+    best, code = [], []
+    for lo in range(0, n, step):
+        d = (z[lo:lo + step, None, :] - e[None, :, :]).pow(2).sum(dim=-1)
+        if K == 1:
+            d = torch.cat([d, torch.full_like(d, float("inf"))], dim=1)
+        # (sorting by (distance, code): a stable sort of the distances keeps the lower code in front of its equals)
+        ds, order = torch.sort(d, dim=1, stable=True)
+        best.append(ds[:, :2])
+        code.append(order[:, :2])
+    return torch.cat(best), torch.cat(code)
+
+
+def _vq_fused_eval(a0, a1, W, bias, embed, dtype):
+    a = torch.as_tensor(a0).detach().cpu() if a1 is None else torch.cat([torch.as_tensor(a0).detach().cpu(), torch.as_tensor(a1).detach().cpu()], dim=1)
+    W, embed = torch.as_tensor(W).detach().cpu(), torch.as_tensor(embed).detach().cpu()
+    N, (D, K) = a.shape[0], embed.shape
+    lost = ~torch.isfinite(a).all(dim=1) | (a.abs() >= VQ_FUSED_ACT_LIMIT).any(dim=1)
+    if not bool(torch.isfinite(embed).all()):
+        lost[:] = True
+    live = ~lost
+    z = torch.where(lost[:, None], torch.zeros_like(a), a).to(dtype) @ W.to(dtype).t()
+    if bias is not None:
+        z = z + torch.as_tensor(bias).detach().cpu().to(dtype)
+    e = embed.to(dtype).t().contiguous()
+    idx = torch.full((N,), -1, dtype=torch.int64)
+    q = torch.full((N, D), float("nan"), dtype=dtype)
+    sse_rows = torch.full((N,), float("nan"), dtype=dtype)
+    if bool(live.any()):
+        idx[live] = _vq_fused_top2(z[live], e)[1][:, 0]
+        q[live] = e[idx[live]]
+        sse_rows[live] = (q[live] - z[live]).pow(2).sum(dim=1)
+    z[lost] = float("nan")
+    counts = torch.bincount(idx[live], minlength=K)
+    sse = sse_rows.sum()
+    diff, perplexity = vq_finalize_spec(sse.reshape(1), counts, N, D)
+    return VqFusedSpec(z, idx, q, counts, sse, sse_rows, diff, perplexity)
+
+
+def vq_fused_spec(a0, a1, W, bias, embed):
+    """VqFusedSpec of the fused launch, everything float64: z = cat(a0, a1) W^T + bias; d = |z - e_k|^2 as a difference;
+    idx = argmin, the lowest index on exact equality; q = e_idx; counts = bincount(idx, K); sse = sum (e_idx - z)^2 (sse_rows:
+    per pixel); diff and perplexity through vq_finalize_spec.  A pixel with a non-finite activation, or one beyond the pair
+    format's range (|a| >= 16384), has idx = -1, q = NaN (z likewise), is not counted and makes sse NaN; so does every pixel
+    when a code is not finite (include/isi_hip.h, "quantization")."""
+    return _vq_fused_eval(a0, a1, W, bias, embed, torch.float64)
+
+
+def vq_fused_f32(a0, a1, W, bias, embed):
+    """The same in float32 torch: the yardstick of z, and what the host tests apply their simulated defects to."""
+    return _vq_fused_eval(a0, a1, W, bias, embed, torch.float32)
+
+
+def vq_fused_split_z(a0, a1, W, bias):
+    """Float64 evaluation of the three split-f16 terms the kernel keeps of the 1x1 convolution (linear_split_model, "f16"), plus
+    the bias: the other half of the yardstick of z."""
+    a = a0 if a1 is None else torch.cat([a0, a1], dim=1)
+    return linear_split_model(a, W, "f16") + (0.0 if bias is None else _f64(bias))
+
+
+def vq_fused_gaps(z, embed, alias=None):
+    """Per pixel, the float64 gap between the best and the second-best code, normalised by |z|^2 + |e_best|^2 (the metric of
+    oracle.near_tie_free_vectors).  `alias` [K] (code -> the lowest index holding the same vector): duplicates of a code take no
+    part, so a pixel that ties between duplicates is measured against every OTHER code."""
+    z, e = _f64(z), _f64(embed).t().contiguous()
+    if alias is not None:
+        e = e.clone()
+        e[alias != torch.arange(e.shape[0])] = float("inf")      # (inf - z)^2 = inf: never among the two best
+    best, code = _vq_fused_top2(z, e)
+    return (best[:, 1] - best[:, 0]) / (z.pow(2).sum(dim=1) + e[code[:, 0]].pow(2).sum(dim=1))
+
+
+def _vq_fused_draw(n, C, gen):
+    """Rectified Gaussian activations, as the models' are, rounded so that the pair format holds them exactly."""
+    return pair_round_f16(torch.randn(n, C, generator=gen).clamp(min=0.0))
+
+
+def vq_fused_settle(a, W, bias, embed, gen, alias=None, frozen=None, min_gap=VQ_FUSED_MIN_GAP):
+    """Redraws every pixel (row of a [N, C]) whose gap is below min_gap until none remains; `frozen` [N] bool: pixels a test
+    placed by hand, never redrawn (the caller checks their gaps).  Returns the settled copy."""
+    a = a.clone()
+    Wd, bd = _f64(W), _f64(bias)
+    rows = torch.arange(a.shape[0]) if frozen is None else (~frozen).nonzero().reshape(-1)
+    for _ in range(64):
+        if rows.numel() == 0:
+            return a
+        low = vq_fused_gaps(a[rows].double() @ Wd.t() + bd, embed, alias) < min_gap
+        rows = rows[low]
+        a[rows] = _vq_fused_draw(rows.numel(), a.shape[1], gen)
+    raise AssertionError("vq_fused_settle: near-ties remain after 64 redraws")
+
+
+VQ_FUSED_DUP_SOURCES = (3, 70, 141)           # where the three most-used codes are moved to, and per source its two copies:
+VQ_FUSED_DUP_COPIES = ((7, 68), (74, 167), (145, 270))   # the other lane half of the same 32-row tile (bit 2 of the row), another tile
+
+
+def vq_fused_duplicate_codes(a, W, bias, embed):
+    """(embed', alias): the three most-used codes of the data moved to VQ_FUSED_DUP_SOURCES and copied to VQ_FUSED_DUP_COPIES,
+    all at higher indices; alias as vq_fused_gaps takes it."""
+    K = embed.shape[1]
+    z = a.double() @ _f64(W).t() + _f64(bias)
+    idx = _vq_fused_top2(z, _f64(embed).t().contiguous())[1][:, 0]
+    top = torch.bincount(idx, minlength=K).argsort(descending=True, stable=True)[:3].tolist()
+    embed = embed.clone()
+    for src, k in zip(VQ_FUSED_DUP_SOURCES, top):
+        cur = k
+        for s2, k2 in zip(VQ_FUSED_DUP_SOURCES, top):     # (an earlier swap may have moved this code)
+            if s2 == src:
+                break
+            cur = k2 if cur == s2 else (s2 if cur == k2 else cur)
+        tmp = embed[:, src].clone()
+        embed[:, src] = embed[:, cur]
+        embed[:, cur] = tmp
+    alias = torch.arange(K)
+    for src, copies in zip(VQ_FUSED_DUP_SOURCES, VQ_FUSED_DUP_COPIES):
+        for c in copies:
+            assert c > src and c < K
+            embed[:, c] = embed[:, src]
+            alias[c] = src
+    return embed, alias
+
+
+def vq_fused_case_seed(case):
+    return ((case.C0 * 263 + case.C1) * 4099 + case.K) * 70001 + case.B * case.H * case.W
+
+
+def vq_fused_case_data(case, seed=None, dups=False, W=None, bias=None):
+    """(a0 [N, C0], a1 [N, C1] or None, W [64, C], bias [64], embed [64, K], alias or None) float32 on the CPU, seeded.  The
+    activations are rectified and rounded by pair_round_f16; W ~ N(0, 1 / C), bias ~ 0.1 N(0, 1); the codebook is K of the spec's
+    own z vectors (of max(N, 2 K) drawn pixels, the first N being the data: at N < 2 K some pixels have a code of their own and
+    the others do not, as at N >> K) plus 0.05 N(0, 1) jitter, so the codes lie where the data is; then every pixel with a gap (vq_fused_gaps) below VQ_FUSED_MIN_GAP is redrawn until none remains.  Measured for
+    C in {32, 192, 256}, K = 512, N = 66 603: 0.3 % of the draws fall below 1e-4 and a float32 evaluation of the whole formula
+    flips an index only at gaps of about 1e-7 -- three decades of room, so the indices of a correct kernel equal the spec's,
+    all of them.  `dups`: vq_fused_duplicate_codes first; the pixels that tie between duplicates are exempt from the gap
+    against their duplicates, and only against those.  `W`, `bias`: given ones in place of the drawn."""
+    C, N, K = case.C0 + case.C1, case.B * case.H * case.W, case.K
+    gen = torch.Generator().manual_seed(vq_fused_case_seed(case) if seed is None else seed)
+    pool = _vq_fused_draw(max(N, 2 * K), C, gen)
+    Wr = torch.randn(VQ_FUSED_D, C, generator=gen) / C ** 0.5
+    br = 0.1 * torch.randn(VQ_FUSED_D, generator=gen)
+    W, bias = Wr if W is None else W, br if bias is None else bias
+    z = pool.double() @ W.double().t() + bias.double()
+    pick = torch.randperm(pool.shape[0], generator=gen)[:K]
+    embed = (z[pick] + 0.05 * torch.randn(K, VQ_FUSED_D, generator=gen).double()).float().t().contiguous()
+    a, alias = pool[:N], None
+    if dups:
+        embed, alias = vq_fused_duplicate_codes(a, W, bias, embed)
+    a = vq_fused_settle(a, W, bias, embed, gen, alias)
+    return a[:, :case.C0].contiguous(), (a[:, case.C0:].contiguous() if case.C1 else None), W, bias, embed, alias
+
+
+VQ_FUSED_FAR_PIXELS = {5: 200, 11: 320}       # hand-placed pixel -> the far code that is its nearest
+
+
+def vq_fused_far_case_data(case):
+    """The constructions of test_codebook_beyond_f16_range for the fused launch (C0 + C1 >= 96, K = 512): W is an identity block
+    on channels 32 .. 95 (both sources at (64, 128)) and zero elsewhere, the bias zero, so z is those 64 activations.  40 dead
+    codes scaled by 3e4; one code at 1e5 times its neighbour; pixel 5, whose nearest code (200) has a component of 70; a far
+    code of moderate norm (320: 200 in one component) with pixel 11 next to it, which no certificate covers -- the fp32 scan
+    decides.  Every other pixel is settled against the edited codebook.  Returns vq_fused_case_data's tuple."""
+    C = case.C0 + case.C1
+    assert C >= 96 and case.K == 512
+    W = torch.zeros(VQ_FUSED_D, C)
+    W[:, 32:96] = torch.eye(VQ_FUSED_D)
+    bias = torch.zeros(VQ_FUSED_D)
+    a0, a1, _, _, embed, _ = vq_fused_case_data(case, seed=vq_fused_case_seed(case) + 1, W=W, bias=bias)
+    a = a0 if a1 is None else torch.cat([a0, a1], dim=1)
+    a[5], a[11] = 0.0, 0.0
+    a[5, 32 + 7], a[11, 32 + 3] = 70.0, 198.0
+    embed[:, 300:340] *= 3.0e4
+    embed[:, 17] = embed[:, 16] * 1.0e5
+    embed[:, 200] = a[5, 32:96]
+    embed[:, 320] = 0.0
+    embed[3, 320] = 200.0
+    frozen = torch.zeros(a.shape[0], dtype=torch.bool)
+    frozen[list(VQ_FUSED_FAR_PIXELS)] = True
+    a = vq_fused_settle(a, W, bias, embed, torch.Generator().manual_seed(vq_fused_case_seed(case) + 2), frozen=frozen)
+    return a[:, :case.C0].contiguous(), (a[:, case.C0:].contiguous() if case.C1 else None), W, bias, embed, None
+
+
+VqFusedRefs = collections.namedtuple("VqFusedRefs", "a0 a1 W bias embed alias spec f32 z_yard")
+
+def vq_fused_refs(a0, a1, W, bias, embed, alias=None):
+    """Spec, float32 evaluation and the yardstick of z -- per element the worse of the float32 evaluation and the three-term
+    split-f16 model -- of given operands."""
+    spec, f32 = vq_fused_spec(a0, a1, W, bias, embed), vq_fused_f32(a0, a1, W, bias, embed)
+    live = spec.idx >= 0
+    yard = torch.full_like(spec.z, float("nan"))
+    if bool(live.any()):
+        a1l = None if a1 is None else a1[live]
+        yard[live] = larger_error(f32.z[live], vq_fused_split_z(a0[live], a1l, W, bias), spec.z[live])
+    return VqFusedRefs(a0, a1, W, bias, embed, alias, spec, f32, yard)
+
+
+@functools.lru_cache(maxsize=None)
+def vq_fused_case_refs(case, dups=False):
+    """vq_fused_refs of vq_fused_case_data, computed once per process and left unchanged."""
+    return vq_fused_refs(*vq_fused_case_data(case, dups=dups))
+
+
+def _vfc(C0, C1, K, shape, strided=False):
+    return VqFusedCase(C0, C1, K, *shape, strided)
+
+
+# (B, H, W) per pixel count: 257 and 31 are prime; 255, 256 and 66 603 decompose in all three dimensions of pixel_offsets
+VQ_FUSED_SHAPES = {1: (1, 1, 1), 31: (1, 31, 1), 33: (3, 1, 11), 255: (3, 5, 17), 256: (4, 8, 8), 257: (1, 1, 257),
+                   66603: (3, 149, 149)}
+# channel routes (C0, C1) -> the chunk-count template NCH: 32 and 96 leave a dead chunk, (96, 160) starts the second source
+# on an odd chunk
+VQ_FUSED_ROUTES = {(32, 0): 2, (64, 0): 2, (96, 0): 4, (128, 0): 4, (256, 0): 8, (32, 32): 2, (64, 128): 6, (96, 160): 8}
+VQ_FUSED_ROUTE_CASES = [_vfc(c0, c1, 512, VQ_FUSED_SHAPES[257]) for c0, c1 in VQ_FUSED_ROUTES]
+# pixel counts: below one wave's 32 vectors, one past it, around one tile, and 260 full tiles + 43 vectors (workgroups 0..4 run
+# a second pass, the last tile is ragged; K = 64 there: its float64 reference takes about a second)
+VQ_FUSED_PIXEL_CASES = ([_vfc(64, 128, 512, VQ_FUSED_SHAPES[n]) for n in (1, 31, 33, 255, 256, 257)]
+                        + [_vfc(32, 0, 64, VQ_FUSED_SHAPES[n]) for n in (1, 31, 33, 255, 256, 257, 66603)])
+VQ_FUSED_K_SIZES = (16, 40, 500, 512)         # ... and K_max, which the tests ask isi_vq_conv1x1_fusable for
+# cropped channel slices of wider maps (VQ_FUSED_PARENTS); 255 = 3 x 5 x 17 moves through every stride at a small size
+VQ_FUSED_STRIDED_CASES = [_vfc(64, 128, 512, (1, 257, 1), True), _vfc(64, 128, 512, VQ_FUSED_SHAPES[255], True),
+                          _vfc(64, 128, 64, VQ_FUSED_SHAPES[66603], True)]
+# per source: (channels the parent map has beyond the slice, first channel of the slice, rows above, below, columns left, right
+# of the crop):
+# different parents, different strides, and a nonzero pointer offset for both
+VQ_FUSED_PARENTS = ((64, 32, 1, 1, 2, 1), (96, 64, 2, 1, 1, 0))
+
+
+def vq_fused_k_cases(k_max):
+    return [_vfc(64, 0, K, VQ_FUSED_SHAPES[257]) for K in VQ_FUSED_K_SIZES + (k_max,)]
+
+
+def vq_fused_k_max(L):
+    """The largest K isi_vq_conv1x1_fusable(64, 0, 64, K) accepts (the library's answer; it is monotone in K)."""
+    ks = [K for K in range(1, 4097) if L.isi_vq_conv1x1_fusable(64, 0, VQ_FUSED_D, K) == 1]
+    assert ks and ks == list(range(1, ks[-1] + 1)), "isi_vq_conv1x1_fusable is not monotone in K"
+    return ks[-1]
+
+
+def vq_fused_case_id(c):
+    return f"C{c.C0}+{c.C1}-K{c.K}-{c.B}x{c.H}x{c.W}" + ("-strided" if c.strided else "")
+
+
+def vq_num_partials(N):
+    """isi_vq_num_partials: one partial per workgroup of vq_grid."""
+    return min(VQ_FUSED_GRID, max(1, -(-N // VQ_FUSED_TILE)))
+
+
+def vq_fused_partials(sse_rows):
+    """sse_part as the kernel's workgroups own it: workgroup g sums the tiles g, g + 256, ... of 256 pixels."""
+    N = sse_rows.shape[0]
+    n_part = vq_num_partials(N)
+    tile = torch.arange(N) // VQ_FUSED_TILE
+    return torch.zeros(n_part, dtype=sse_rows.dtype).index_add_(0, tile % n_part, sse_rows)
+
+
+def pair_encode_host(x):
+    """The pair format of csrc/split_f16.h on the CPU: per group of 8 consecutive floats {hi[8] | lo[8]}, the f16 pieces of
+    4 x, in a float32-typed tensor of x's shape (its bits are what matters)."""
+    xs = x.float().contiguous() * 4.0
+    hi = xs.half()
+    lo = (xs - hi.float()).half()
+    g = torch.stack([hi.reshape(-1, 8), lo.reshape(-1, 8)], dim=1)
+    return g.reshape(-1).view(torch.float32).reshape(x.shape)
+
+
+def pair_decode_host(p):
+    """(hi + lo) / 4 of every element of a pair-format tensor."""
+    h = p.detach().cpu().contiguous().reshape(-1).view(torch.float16).reshape(-1, 2, 8).float()
+    return ((h[:, 0] + h[:, 1]) / 4.0).reshape(p.shape)
+
+
+# The comparisons.  Each takes a launch's output as a CPU tensor and raises AssertionError with `what` in front.
+def vq_fused_hold_idx(idx, spec, what):
+    """Every index equals the spec's: the data has no near-tie, so the cap on differing indices is zero."""
+    idx = torch.as_tensor(idx).cpu().reshape(-1)
+    assert idx.dtype == torch.int64 and idx.shape == spec.idx.shape, f"{what}: idx {idx.dtype} {tuple(idx.shape)}"
+    bad = (idx != spec.idx).nonzero().reshape(-1)
+    assert bad.numel() == 0, (f"{what}: {bad.numel()} of {idx.numel()} indices differ from the float64 spec's, first at pixel "
+                              f"{int(bad[0])}: {int(idx[bad[0]])} against {int(spec.idx[bad[0]])}")
+
+
+def vq_fused_hold_counts(counts, spec, what):
+    counts = torch.as_tensor(counts).cpu().reshape(-1).long()
+    assert counts.shape == spec.counts.shape and torch.equal(counts, spec.counts), \
+        f"{what}: counts differ from the spec's histogram (sum {int(counts.sum())} against {int(spec.counts.sum())})"
+
+
+def vq_fused_hold_z(z, refs, what, margin=ROW_OPS_MARGIN):
+    """z of the pixels the spec keeps through compare_rows against refs.z_yard; returns the RowCheck."""
+    live = refs.spec.idx >= 0
+    return compare_rows(torch.as_tensor(z).cpu()[live], refs.spec.z[live], refs.z_yard[live], f"{what} z", margin)
+
+
+def vq_fused_hold_q(q, refs, what):
+    """q = z + (e_idx - z) in float32: every element within one float32 ulp of max(|z|, |e|), 2^-23 of it, from e_idx; a pixel
+    without a code is NaN throughout."""
+    q, spec = torch.as_tensor(q).cpu(), refs.spec
+    live = spec.idx >= 0
+    assert q.shape == spec.q.shape and bool(torch.isnan(q[~live]).all()), f"{what}: q of a pixel without a code is not NaN"
+    e, z = spec.q[live], spec.z[live]
+    err = (q[live].double() - e).abs()
+    assert bool(torch.isfinite(q[live]).all()), f"{what}: q is not finite"
+    over = err - 2.0 ** -23 * torch.maximum(z.abs(), e.abs())
+    assert float(over.max() if over.numel() else 0.0) <= 0.0, \
+        f"{what}: q is further than one float32 ulp of max(|z|, |e|) from e_idx (largest error {float(err.max()):.3e})"
+
+
+def vq_fused_hold_q_pair(q_pair, q, refs, what):
+    """pair_decode(q_pair) within 2^-23 max|q| of q; NaN pieces where q is NaN."""
+    dec, q = pair_decode_host(torch.as_tensor(q_pair).cpu()), torch.as_tensor(q).cpu()
+    live = refs.spec.idx >= 0
+    assert bool(torch.isnan(dec[~live]).all()), f"{what}: q_pair of a pixel without a code does not decode to NaN"
+    if bool(live.any()):
+        err, scale = float((dec[live] - q[live]).abs().max()), float(q[live].abs().max())
+        assert math.isfinite(err) and err <= 2.0 ** -23 * scale, f"{what}: pair_decode(q_pair) is {err:.3e} from q (max|q| {scale:.3e})"
+
+
+def vq_fused_hold_sse(sse_part, spec, what):
+    """Every partial written (the buffer starts as NaN), their float64 sum within 1e-5 of the spec's; NaN where the spec's is."""
+    sse_part = torch.as_tensor(sse_part).cpu().reshape(-1)
+    assert sse_part.numel() == vq_num_partials(spec.idx.numel()), f"{what}: {sse_part.numel()} partials"
+    total = float(sse_part.double().sum())
+    if math.isnan(float(spec.sse)):
+        assert math.isnan(total), f"{what}: the squared error of a launch with a lost pixel is {total}, not NaN"
+        return
+    assert not bool(torch.isnan(sse_part).any()), f"{what}: {int(torch.isnan(sse_part).sum())} partials were not written"
+    assert abs(total - float(spec.sse)) <= VQ_FUSED_SSE_RTOL * float(spec.sse), \
+        f"{what}: summed squared error {total!r} against the spec's {float(spec.sse)!r}"

@@ -42,7 +42,8 @@ const char *isi_last_error(void);
  * 2 isi_conv_w, 3 isi_encoder_w, 4 isi_decoder_w, 5 isi_codebook_w,
  * 6 isi_vqvae_w, 7 isi_vqvae_out, 8 isi_attn_args, 9 isi_prior_w,
  * 10 isi_prior_state, 11 isi_attn_bwd_args, 12 isi_reduce_job, 13 isi_prior_rows,
- * 14 isi_prior_code_bias, 15 isi_adam_tensor, 16 isi_adam_hyper.
+ * 14 isi_prior_code_bias, 15 isi_adam_tensor, 16 isi_adam_hyper, 17 isi_decode_stage_args,
+ * 18 isi_decode_single_source_args.
  * Returns 0 for an unknown id. */
 size_t isi_abi_struct_bytes(int which);
 
@@ -760,6 +761,70 @@ size_t isi_decode_stage_workspace_floats(int M, int N, int K);
 int isi_decode_stage_f32(const float *x, int x_stride, const float *ln_g, const float *ln_b, const float *W, const float *bias,
                          const float *res, int res_stride, const float *res_g, const float *res_b, float *out, int out_stride,
                          int M, int N, int K, int relu, float eps, float *workspace, size_t workspace_floats, void *stream);
+
+/* The same stage as the decoding loop describes it (isi_abi_struct_bytes(17) = sizeof(isi_decode_stage_args)): everything
+ * isi_prior_sample_run puts into a stage's launch, so that every route of the loop's stage kernels can be run alone.
+ *   columns [0, split) of the result go to `out` (row stride out_stride), columns [split, N) to `out2` (nullable: split == N),
+ *   an fp32 array (out2_format = ISI_KV_F32) or a bf16 array (ISI_KV_BF16: rounded to nearest-even; 16-byte aligned);
+ *   out2_stride and out2_pos count elements of that format.
+ * The position: x, res and out2 move on by x_pos, res_pos, out2_pos elements per sequence position.  `p` is the position by
+ * value: the host advances the pointers.  With `counter` (a device int) the kernels read the position there; `p` is then not
+ * used.  With `row_pos` (device, [steps][M]) row m stands at row_pos[t * M + m], t = p (the launch gets row_pos + p * M) or
+ * t = *counter (the whole array beside the counter), and moves by that position; only the batched kernels address rows so.
+ * A stage none of whose addresses moves takes neither counter nor row_pos (ISI_E_INVALID).
+ * The hand-off: with ln_g, stat_out ([M][2], 8-byte aligned) receives the input rows' (mean, 1 / sqrt(var + eps)); with res_g,
+ * res_stat gives the residual rows' statistics, which are then not formed from the rows.
+ * part (one row, K <= 512, no ln_g): the input row is the merge of an attention's key-split partials
+ * [K / part_hd heads][part_ns <= 8][part_hd + 4], each (o[part_hd], max, sum, -, -); x is then not read.
+ * The kernel is the loop's own choice from M, N, K, the fields and ISI_DECODE_MFMA_ROWS; `kernel` reports it (ISI_STAGE_*).
+ * (The tiles take a LayerNorm over K <= 2048, and a normalised residual of more than 512 features only with res_stat.)
+ * A field the chosen kernel would not read is refused (ISI_E_UNSUPPORTED, the message names it): stat_out, res_stat or part on
+ * the groups-of-8 kernel, part beyond one row of K <= 512, row_pos where K > 2048.  Refusals precede every launch and
+ * write nothing but `kernel`.  workspace as for isi_decode_stage_f32. */
+#define ISI_STAGE_ONE_ROW 0
+#define ISI_STAGE_TILES 1
+#define ISI_STAGE_ROWS_IN_REGISTERS 2
+#define ISI_STAGE_GROUPS_OF_8 3
+#define ISI_STAGE_REFUSED 4
+typedef struct isi_decode_stage_args {
+  const float *x; int x_stride;
+  const float *ln_g, *ln_b;
+  const float *W, *bias;
+  const float *res; int res_stride;
+  const float *res_g, *res_b;
+  float *out; int out_stride;
+  void *out2; int out2_stride, out2_format;
+  int split, M, N, K, relu;
+  float eps;
+  int p;
+  const int *counter;
+  const int *row_pos;
+  int64_t x_pos, res_pos, out2_pos;
+  float *stat_out;
+  const float *res_stat;
+  const float *part; int part_ns, part_hd;
+  float *workspace; size_t workspace_floats;
+  int kernel;              /* out */
+} isi_decode_stage_args;
+int isi_decode_stage_ex_f32(isi_decode_stage_args *args, void *stream);
+
+/* The single-source cross-attention block of the loop alone (isi_prior_state.cross_out; isi_abi_struct_bytes(18)):
+ *   y2[m] = LN1(y1[m]) + table[(pos_m / Cd) * table_B + m * table_sb],  stat_out[m] = (mean, 1 / sqrt(var + eps)) of y2[m]
+ * for B rows of d <= 1024 features; table_B, table_sb = (B, 1), or (1, 0) for a table all rows share; stat_out nullable.
+ * pos_m = p, or *counter (p then holds the same value for the host's check), or with row_pos ([steps][B], device) row m's
+ * own row_pos[t * B + m], t = p or *counter; row_pos_host is its host copy.  Cd >= 1 and every pos_m / Cd < S_src, checked
+ * on the host before the launch. */
+typedef struct isi_decode_single_source_args {
+  const float *y1, *ln_g, *ln_b, *table;
+  float *y2, *stat_out;
+  int p;
+  const int *counter;
+  const int *row_pos, *row_pos_host;
+  int Cd, S_src, B, d;
+  float eps;
+  int table_B, table_sb;
+} isi_decode_single_source_args;
+int isi_decode_single_source_f32(const isi_decode_single_source_args *args, void *stream);
 
 /* Decoding step: ONE query row per (batch, head) at sequence position q_pos
  * against args->Sk cached keys/values (same logits as isi_rel_attention_f32;

@@ -110,6 +110,8 @@ size_t isi_abi_struct_bytes(int which) {
     case 14: return sizeof(isi_prior_code_bias);
     case 15: return sizeof(isi_adam_tensor);
     case 16: return sizeof(isi_adam_hyper);
+    case 17: return sizeof(isi_decode_stage_args);
+    case 18: return sizeof(isi_decode_single_source_args);
     default: return 0;
   }
 }
@@ -386,6 +388,10 @@ int isi_decode_stage_f32(const float *x, int x_stride, const float *ln_g, const 
                          int M, int N, int K, int relu, float eps, float *workspace, size_t workspace_floats, void *stream) {
   return decode_stage_f32(x, x_stride, ln_g, ln_b, W, bias, res, res_stride, res_g, res_b, out, out_stride, M, N, K, relu, eps,
                           workspace, workspace_floats, S(stream));
+}
+int isi_decode_stage_ex_f32(isi_decode_stage_args *args, void *stream) { return decode_stage_ex_f32(args, S(stream)); }
+int isi_decode_single_source_f32(const isi_decode_single_source_args *args, void *stream) {
+  return decode_single_source_f32(args, S(stream));
 }
 int isi_rel_attention_decode_f32(const isi_attn_args *args, int q_pos, float *workspace, void *stream) {
   return rel_attention_decode_f32(args, q_pos, workspace, S(stream));

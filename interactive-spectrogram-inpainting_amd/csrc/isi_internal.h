@@ -195,6 +195,9 @@ size_t decode_stage_workspace_floats(int M, int N, int K);
 int decode_stage_f32(const float *x, int x_stride, const float *ln_g, const float *ln_b, const float *W, const float *bias,
                      const float *res, int res_stride, const float *res_g, const float *res_b, float *out, int out_stride,
                      int M, int N, int K, int relu, float eps, float *workspace, size_t workspace_floats, hipStream_t st);
+// isi_decode_stage_ex_f32 / isi_decode_single_source_f32: a stage / the single-source block as the loop launches them
+int decode_stage_ex_f32(isi_decode_stage_args *args, hipStream_t st);
+int decode_single_source_f32(const isi_decode_single_source_args *args, hipStream_t st);
 size_t prior_decode_scratch_floats(const isi_prior_w *w, int B);
 // bias: isi_prior_sample_run_bias / isi_prior_sample_run_rows_bias; nullptr or a zeroed struct: off
 int prior_sample_run(const isi_prior_w *w, const isi_prior_state *s, int p_begin, int p_end, float temperature,

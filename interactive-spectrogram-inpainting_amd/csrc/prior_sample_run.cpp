@@ -44,6 +44,10 @@ namespace {
 
 // ---------------------------------------------------------------- which kernel runs a stage
 bool row_mfma_supported(const RowLinArgs &a) {
+  // what the tile kernel holds per lane of a row while it forms LayerNorm statistics: 8 float4 of an input row, 8 floats of a
+  // residual row.  Wider residual rows run on the tiles with their statistics handed (res_stat), as the loop hands them
+  if (a.ln_g && a.K > 2048) return false;
+  if (a.res && a.res_g && !a.res_stat && a.N > 512) return false;
   return a.M >= 2 && (a.K & 7) == 0 && (a.x_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0 &&
          (reinterpret_cast<uintptr_t>(a.W) & 15) == 0 && (!a.ln_g || ((reinterpret_cast<uintptr_t>(a.ln_g) | reinterpret_cast<uintptr_t>(a.ln_b)) & 15) == 0);
 }
@@ -91,7 +95,8 @@ RowLinArgs row_group(const RowLinArgs &a, int m0) {
 
 // what the kernel of a stage cannot run: the same answer before anything is launched (check_stages) and at the launch
 int stage_refusal(const RowLinArgs &a, StageKernel k) {
-  if (k == StageKernel::kRefused) return unsupported("decode stage: ragged rows need the batched kernels (K <= 2048)");
+  if (k == StageKernel::kRefused) return unsupported("decode stage: ragged rows need the batched kernels (K <= 2048; a normalised residual of more than 512 features "
+                       "on the tiles, with its statistics handed)");
   if (k == StageKernel::kGroupsOf8 && row_linear_lds_bytes(a.M, a.K) > kRowLinearLdsMax)
     return unsupported("row_linear: rows do not fit in LDS");
   return ISI_OK;
@@ -296,7 +301,9 @@ int run_stage(const Call &c, const RowLinArgs &a, Queue q, const float *part = n
 void hand_stats(const Call &c, RowLinArgs &producer, RowLinArgs &consumer, bool consumer_merges = false) {
   if (!c.r.handoff || !producer.ln_g || !consumer.res_g) return;
   const StageKernel k = stage_kernel(producer, false);
-  if (k != stage_kernel(consumer, consumer_merges)) return;
+  RowLinArgs handed = consumer;        // (the consumer as it would be launched: the tiles take wide residual rows only so)
+  handed.res_stat = c.sc.rowstat;
+  if (k != stage_kernel(handed, consumer_merges)) return;
   const bool on = k == StageKernel::kTiles || (k == StageKernel::kOneRow && !c.r.rag) ||
                   (k == StageKernel::kRowsInRegisters && producer.M > 1 && producer.M <= knobs().decode_mfma_rows);
   if (!on) return;
@@ -674,6 +681,85 @@ int decode_stage_f32(const float *x, int x_stride, const float *ln_g, const floa
                           .with_residual(res, res_stride, res_g, res_b).with_relu(relu != 0);
   float *ws = (workspace && !(reinterpret_cast<uintptr_t>(workspace) & 15)) ? workspace : nullptr;
   return launch_stage_rows(stage.a, nullptr, 1, 64, ws, ws ? workspace_floats : 0, Queue{st, false});
+}
+
+// A stage as the loop describes it (isi_decode_stage_ex_f32): the argument block through Stage and placed(), the kernel by
+// stage_kernel(), the launch by launch_stage_rows() -- the loop's own plan with nothing forced.  What is checked here is what
+// check_call guarantees the loop's stages (alignment, pairs), and every field the chosen kernel would not read.
+int decode_stage_ex_f32(isi_decode_stage_args *g, hipStream_t st) {
+  if (!g) return invalid("decode_stage_ex: null argument");
+  g->kernel = ISI_STAGE_REFUSED;
+  auto misaligned = [](const void *p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) != 0; };
+  if (!g->x || !g->W || !g->out || g->M <= 0 || g->M > 256 || g->N <= 0 || g->K <= 0) return invalid("decode_stage_ex: bad argument");
+  if ((g->K & 3) || (g->x_stride & 3) || (g->x_pos & 3) || misaligned(g->x, 16) || misaligned(g->W, 16))
+    return invalid("decode_stage_ex: K, x_stride and x_pos must be multiples of 4, x and W 16-byte aligned");
+  if ((g->ln_g == nullptr) != (g->ln_b == nullptr) || (g->res_g == nullptr) != (g->res_b == nullptr) || (g->res_g && !g->res))
+    return invalid("decode_stage_ex: LayerNorm weight and bias come together (and the residual's with a residual)");
+  if (g->ln_g && (misaligned(g->ln_g, 16) || misaligned(g->ln_b, 16))) return invalid("decode_stage_ex: ln_g and ln_b must be 16-byte aligned");
+  if (g->out2 ? (g->split <= 0 || g->split >= g->N) : g->split != g->N)
+    return invalid("decode_stage_ex: out2 takes the columns [split, N), 0 < split < N; without out2 split == N");
+  if (g->out2_format != ISI_KV_F32 && g->out2_format != ISI_KV_BF16)
+    return invalid("decode_stage_ex: out2_format must be ISI_KV_F32 (0) or ISI_KV_BF16 (1)");
+  if (g->out2 && misaligned(g->out2, g->out2_format == ISI_KV_BF16 ? 16 : 4))
+    return invalid("decode_stage_ex: a bf16 out2 must be 16-byte aligned");
+  const bool moves = g->x_pos || g->res_pos || g->out2_pos;
+  if (!moves && g->counter) return invalid("decode_stage_ex: counter on a stage none of whose addresses moves (x_pos, res_pos, out2_pos)");
+  if (!moves && g->row_pos) return invalid("decode_stage_ex: row_pos on a stage none of whose addresses moves (x_pos, res_pos, out2_pos)");
+  if (moves && !g->counter && g->p < 0) return invalid("decode_stage_ex: p < 0");
+  if ((g->res_pos && !g->res) || (g->out2_pos && !g->out2)) return invalid("decode_stage_ex: res_pos / out2_pos without res / out2");
+  if (g->stat_out && (!g->ln_g || misaligned(g->stat_out, 8))) return invalid("decode_stage_ex: stat_out needs ln_g and 8-byte alignment");
+  if (g->res_stat && (!g->res_g || misaligned(g->res_stat, 8))) return invalid("decode_stage_ex: res_stat needs res_g and 8-byte alignment");
+  if (g->part) {
+    if (g->part_ns < 1 || g->part_ns > 8 || g->part_hd < 4 || (g->part_hd & 3) || g->K % g->part_hd || misaligned(g->part, 16))
+      return invalid("decode_stage_ex: part needs 1 <= part_ns <= 8, part_hd a multiple of 4 that divides K, 16-byte alignment");
+    if (g->ln_g || g->stat_out) return invalid("decode_stage_ex: part replaces the input row: no ln_g, no stat_out");
+  }
+  Stage stage = Stage(g->x, g->K, g->W, g->bias, g->out, g->N, g->M).with_strides(g->x_stride, g->out_stride).with_eps(g->eps)
+                    .with_ln(g->ln_g, g->ln_b).with_residual(g->res, g->res_stride, g->res_g, g->res_b).with_relu(g->relu != 0);
+  if (g->out2) {
+    stage.with_out2(static_cast<float *>(g->out2), g->out2_stride, g->split, g->out2_format == ISI_KV_BF16);
+    stage.a.out_stride = g->out_stride;
+  }
+  stage.advancing((long)g->x_pos, (long)g->res_pos, (long)g->out2_pos);
+  stage.a.stat_out = g->stat_out;
+  stage.a.res_stat = g->res_stat;
+  const int p = g->counter ? -1 : g->p;
+  const Where at{p, g->counter, g->row_pos ? g->row_pos + (p < 0 ? 0 : (size_t)p * g->M) : nullptr, nullptr};
+  const RowLinArgs a = placed(stage.a, at);
+  const StageKernel k = stage_kernel(a, g->part != nullptr);
+  g->kernel = k == StageKernel::kOneRow ? ISI_STAGE_ONE_ROW : k == StageKernel::kTiles ? ISI_STAGE_TILES
+              : k == StageKernel::kRowsInRegisters ? ISI_STAGE_ROWS_IN_REGISTERS
+              : k == StageKernel::kGroupsOf8 ? ISI_STAGE_GROUPS_OF_8 : ISI_STAGE_REFUSED;
+  if (int rc = stage_refusal(a, k)) return rc;
+  if (g->part && k != StageKernel::kOneRow) return unsupported("decode_stage_ex: part is merged by the one-row kernel only (M == 1, K <= 512)");
+  if (k == StageKernel::kGroupsOf8) {
+    if (g->stat_out) return unsupported("decode_stage_ex: stat_out is not written by the groups-of-8 kernel");
+    if (g->res_stat) return unsupported("decode_stage_ex: res_stat is not read by the groups-of-8 kernel");
+  }
+  float *ws = (g->workspace && !misaligned(g->workspace, 16)) ? g->workspace : nullptr;
+  return launch_stage_rows(a, g->part, g->part_ns, g->part_hd, ws, ws ? g->workspace_floats : 0, Queue{st, false});
+}
+
+// The single-source cross-attention block alone (isi_decode_single_source_f32): SingleSourceArgs as single_source_block fills it
+int decode_single_source_f32(const isi_decode_single_source_args *g, hipStream_t st) {
+  if (!g || !g->y1 || !g->ln_g || !g->ln_b || !g->table || !g->y2) return invalid("decode_single_source: null pointer");
+  if (g->B <= 0 || g->B > 256 || g->d <= 0) return invalid("decode_single_source: bad B or d");
+  if (g->d > 64 * SS_RS) return unsupported("decode_single_source: d <= 1024");
+  if (g->Cd < 1 || g->S_src < 1 || g->p < 0) return invalid("decode_single_source: Cd >= 1, S_src >= 1, p >= 0");
+  if (!((g->table_B == g->B && g->table_sb == 1) || (g->table_B == 1 && g->table_sb == 0)))
+    return invalid("decode_single_source: (table_B, table_sb) is (B, 1), or (1, 0) for a shared table");
+  if (g->stat_out && (reinterpret_cast<uintptr_t>(g->stat_out) & 7)) return invalid("decode_single_source: stat_out must be 8-byte aligned");
+  if (g->row_pos && !g->row_pos_host) return invalid("decode_single_source: row_pos comes with its host copy row_pos_host");
+  for (int m = 0; m < (g->row_pos ? g->B : 1); ++m) {
+    const int pm = g->row_pos ? g->row_pos_host[(size_t)g->p * g->B + m] : g->p;
+    if (pm < 0 || pm / g->Cd >= g->S_src) return invalid("decode_single_source: a position without a source row (p / Cd >= S_src)");
+  }
+  SingleSourceArgs ss{};
+  ss.y1 = g->y1; ss.ln_g = g->ln_g; ss.ln_b = g->ln_b; ss.table = g->table; ss.y2 = g->y2; ss.stat_out = g->stat_out;
+  ss.pos = g->counter; ss.p = g->counter ? 0 : g->p; ss.Cd = g->Cd; ss.S_src = g->S_src; ss.B = g->B; ss.d = g->d; ss.eps = g->eps;
+  ss.row_pos = g->row_pos ? (g->counter ? g->row_pos : g->row_pos + (size_t)g->p * g->B) : nullptr;
+  ss.table_B = g->table_B; ss.table_sb = g->table_sb;
+  return launch_single_source_cross(ss, st);
 }
 
 size_t prior_decode_scratch_floats(const isi_prior_w *w, int B) {

@@ -168,6 +168,27 @@ class isi_adam_hyper(C.Structure):
                 ("eps", C.c_double), ("step_size", C.c_double), ("inv_sqrt_bc2", C.c_double), ("reserved", C.c_double)]
 
 
+ISI_STAGE_ONE_ROW, ISI_STAGE_TILES, ISI_STAGE_ROWS_IN_REGISTERS, ISI_STAGE_GROUPS_OF_8, ISI_STAGE_REFUSED = range(5)
+
+
+class isi_decode_stage_args(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("x_stride", C.c_int), ("ln_g", C.c_void_p), ("ln_b", C.c_void_p), ("W", C.c_void_p),
+                ("bias", C.c_void_p), ("res", C.c_void_p), ("res_stride", C.c_int), ("res_g", C.c_void_p), ("res_b", C.c_void_p),
+                ("out", C.c_void_p), ("out_stride", C.c_int), ("out2", C.c_void_p), ("out2_stride", C.c_int),
+                ("out2_format", C.c_int), ("split", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("relu", C.c_int),
+                ("eps", C.c_float), ("p", C.c_int), ("counter", C.c_void_p), ("row_pos", C.c_void_p),
+                ("x_pos", C.c_int64), ("res_pos", C.c_int64), ("out2_pos", C.c_int64), ("stat_out", C.c_void_p),
+                ("res_stat", C.c_void_p), ("part", C.c_void_p), ("part_ns", C.c_int), ("part_hd", C.c_int),
+                ("workspace", C.c_void_p), ("workspace_floats", C.c_size_t), ("kernel", C.c_int)]
+
+
+class isi_decode_single_source_args(C.Structure):
+    _fields_ = [("y1", C.c_void_p), ("ln_g", C.c_void_p), ("ln_b", C.c_void_p), ("table", C.c_void_p), ("y2", C.c_void_p),
+                ("stat_out", C.c_void_p), ("p", C.c_int), ("counter", C.c_void_p), ("row_pos", C.c_void_p),
+                ("row_pos_host", C.c_void_p), ("Cd", C.c_int), ("S_src", C.c_int), ("B", C.c_int), ("d", C.c_int),
+                ("eps", C.c_float), ("table_B", C.c_int), ("table_sb", C.c_int)]
+
+
 # name -> (restype, argtypes); must list every symbol include/isi_hip.h declares
 _P = C.c_void_p
 SIGNATURES = {
@@ -331,6 +352,8 @@ SIGNATURES = {
     "isi_decode_stage_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "isi_decode_stage_f32": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_int, C.c_float, _P, C.c_size_t, _P]),
+    "isi_decode_stage_ex_f32": (C.c_int, [C.POINTER(isi_decode_stage_args), _P]),
+    "isi_decode_single_source_f32": (C.c_int, [C.POINTER(isi_decode_single_source_args), _P]),
     "isi_mse_loss_num_partials": (C.c_int, [C.c_int64]),
     "isi_mse_loss_f32": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P]),
     "isi_mse_loss_bwd_f32": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P]),
@@ -372,7 +395,8 @@ def lib() -> C.CDLL:
                     fn.argtypes = args
                 structs = [isi_src, isi_dst, isi_conv_w, isi_encoder_w, isi_decoder_w, isi_codebook_w,
                            isi_vqvae_w, isi_vqvae_out, isi_attn_args, isi_prior_w, isi_prior_state, isi_attn_bwd_args,
-                           isi_reduce_job, isi_prior_rows, isi_prior_code_bias, isi_adam_tensor, isi_adam_hyper]
+                           isi_reduce_job, isi_prior_rows, isi_prior_code_bias, isi_adam_tensor, isi_adam_hyper,
+                           isi_decode_stage_args, isi_decode_single_source_args]
                 for i, st in enumerate(structs):
                     if handle.isi_abi_struct_bytes(i) != C.sizeof(st):
                         raise HipLibraryError(f"ABI mismatch for {st.__name__}: library "

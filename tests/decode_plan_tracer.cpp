@@ -31,6 +31,11 @@
 //   r: 0 none, else kRefusals[r - 1] (printed in the header)
 // stage/m<M>/n<N>/k<K>/f<flags>/w<workspace>/r<refusal>: isi_decode_stage_f32 alone
 //   f: 1 LayerNorm on the input | 2 residual | 4 LayerNorm on the residual | 8 ReLU;  w: 0 none | 1 given | 2 misaligned
+// stagex/m<M>/n<N>/k<K>/s<split>/f<flags>/v<out2>/a<addressing>/w<workspace>/q<decode_mfma_rows>.<decode_stats_global>/
+//        g<heads>.<head_dim>.<splits>.<kind>/h<hand-off>: isi_decode_stage_ex_f32, the route table of tests/tests_support.py
+//   (DECODE_STAGE_CASES, the cases of tests/test_decode_stage_gpu.py; tests/test_decode_stage_host.py holds the two lists together)
+//   v: 0 no out2 | 1 fp32 | 2 bf16;  a: 0 position by value | 1 device counter | 2 row_pos offset to its step | 3 row_pos beside
+//   the counter;  w: 0 none | 1 given | 2 one float short;  g: merged attention partials (0.0.0.0: none);  h: 1 stat_out | 2 res_stat
 #include <sys/wait.h>
 #include <unistd.h>
 
@@ -279,7 +284,9 @@ hipError_t hipDeviceSynchronize() { runtime_call("hipDeviceSynchronize"); return
 namespace {
 
 struct Case {
-  bool stage = false;
+  bool stage = false, stagex = false;
+  // stagex
+  int split = 0, kv = 0, addr = 0, stats_global = 0, ph = 0, hd = 0, ns = 0, kind = 0, handoff = 0;
   // run
   int B = 1, d = 64, heads = 4, ff = 128, layers = 2, S_t = 64, S_src = 16, opts = 0, bias = 0;
   int graph = 8, mfma_rows = 16, no_handoff = 0, range = 3, mask = 0, scenario = 0, refuse = 0;
@@ -289,7 +296,10 @@ struct Case {
 
 std::string case_id(const Case &c) {
   char b[200];
-  if (c.stage) snprintf(b, sizeof b, "stage/m%d/n%d/k%d/f%d/w%d/r%d", c.M, c.N, c.K, c.flags, c.ws, c.refuse);
+  if (c.stagex)
+    snprintf(b, sizeof b, "stagex/m%d/n%d/k%d/s%d/f%d/v%d/a%d/w%d/q%d.%d/g%d.%d.%d.%d/h%d", c.M, c.N, c.K, c.split, c.flags, c.kv, c.addr,
+             c.ws, c.mfma_rows, c.stats_global, c.ph, c.hd, c.ns, c.kind, c.handoff);
+  else if (c.stage) snprintf(b, sizeof b, "stage/m%d/n%d/k%d/f%d/w%d/r%d", c.M, c.N, c.K, c.flags, c.ws, c.refuse);
   else
     snprintf(b, sizeof b, "run/b%d/d%d.%d.%d/l%d/t%d.%d/o%d/c%d/k%d.%d.%d/p%d/m%d/x%d/r%d", c.B, c.d, c.heads, c.ff, c.layers, c.S_t,
              c.S_src, c.opts, c.bias, c.graph, c.mfma_rows, c.no_handoff, c.range, c.mask, c.scenario, c.refuse);
@@ -306,6 +316,7 @@ void set_knobs(const Case &c) {
   memset(&g_knobs, 0, sizeof g_knobs);
   g_knobs.decode_nt = 1;
   g_knobs.prior_graph = c.graph; g_knobs.decode_mfma_rows = c.mfma_rows; g_knobs.decode_no_stat_handoff = c.no_handoff;
+  g_knobs.decode_stats_global = c.stats_global;
 }
 
 struct CallResult { int rc, launches; };
@@ -429,6 +440,32 @@ CallResult run_stage(const Case &c) {
   return {rc, g_launches};
 }
 
+// isi_decode_stage_ex_f32 on a case of the route table: three positions of every position-addressed array, position / step 1
+CallResult run_stagex(const Case &c) {
+  g_regions.clear(); g_trace.clear(); g_launches = 0;
+  isi_decode_stage_args g;
+  memset(&g, 0, sizeof g);
+  const int n2 = c.N - c.split;
+  g.x = fregion("x"); g.x_stride = c.K; g.W = fregion("W"); g.bias = fregion("bias");
+  if (c.flags & 1) { g.ln_g = fregion("ln_g"); g.ln_b = fregion("ln_b"); }
+  if (c.flags & 2) { g.res = fregion("res"); g.res_stride = c.N; g.res_pos = (int64_t)c.M * c.N; }
+  if (c.flags & 4) { g.res_g = fregion("res_g"); g.res_b = fregion("res_b"); }
+  g.out = static_cast<float *>(region("out")); g.out_stride = c.split;
+  if (c.kv) { g.out2 = region("out2"); g.out2_stride = n2; g.out2_format = c.kv == 2 ? ISI_KV_BF16 : ISI_KV_F32; g.out2_pos = (int64_t)c.M * n2; }
+  g.split = c.split; g.M = c.M; g.N = c.N; g.K = c.K; g.relu = (c.flags & 8) ? 1 : 0; g.eps = 1e-5f;
+  g.p = 1; g.x_pos = (int64_t)c.M * c.K;
+  if (c.addr == 1 || c.addr == 3) g.counter = static_cast<const int *>(region("counter"));
+  if (c.addr >= 2) g.row_pos = static_cast<const int *>(region("row_pos"));
+  if (c.handoff & 1) g.stat_out = static_cast<float *>(region("stat_out"));
+  if (c.handoff & 2) g.res_stat = fregion("res_stat");
+  if (c.ph) { g.part = fregion("part"); g.part_ns = c.ns; g.part_hd = c.hd; }
+  const size_t chunks = (size_t)c.M * ((c.K + 511) / 512) * c.N;
+  if (c.ws) { g.workspace = static_cast<float *>(region("workspace")); g.workspace_floats = c.ws == 2 ? chunks - 1 : chunks + 4; }
+  const int rc = isi::decode_stage_ex_f32(&g, kCaller);
+  g_trace += "kernel " + std::to_string(g.kernel) + "\nreturn " + std::to_string(rc) + "\n";
+  return {rc, g_launches};
+}
+
 // the whole case: its calls' traces, return codes and launch counts
 struct CaseResult { std::string trace, rcs, ns; };
 CaseResult run_case(const Case &c) {
@@ -441,7 +478,7 @@ CaseResult run_case(const Case &c) {
   if (c.scenario == 2) variants = {0, 1, 2, 3, 4, 5, 6, 7, 8, 0};
   CaseResult res;
   for (size_t i = 0; i < variants.size(); ++i) {
-    const CallResult cr = c.stage ? run_stage(c) : run_call(c, variants[i]);
+    const CallResult cr = c.stagex ? run_stagex(c) : c.stage ? run_stage(c) : run_call(c, variants[i]);
     res.trace += "call " + std::to_string(i) + ": " + g_trace;
     res.rcs += (i ? "," : "") + std::to_string(cr.rc);
     res.ns += (i ? "," : "") + std::to_string(cr.launches);
@@ -461,6 +498,79 @@ const int kBatches[] = {1, 2, 8, 9, 16, 17, 47, 48, 256};
 struct Dims { int d, heads, ff; };
 const Dims kDims[] = {{64, 4, 128}, {512, 8, 1024}, {544, 17, 128}, {64, 4, 2048}, {64, 4, 2052}, {64, 4, 2056}, {1024, 16, 128},
                       {1056, 33, 128}, {64, 4, 5120}};
+
+// isi_decode_stage_ex_f32: DECODE_STAGE_CASES of tests/tests_support.py (_decode_stage_table), loop for loop
+Case xcase(int M, int N, int K, int split, int flags, int kv = 0, int addr = 0, int ws = 0, int handoff = 0) {
+  Case c;
+  c.stagex = true; c.M = M; c.N = N; c.K = K; c.split = kv ? split : N; c.flags = flags; c.kv = kv; c.addr = addr; c.ws = ws;
+  c.handoff = handoff;
+  return c;
+}
+void enumerate_stagex() {
+  const int ALL = 15, cyc[6] = {15, 1, 7, 11, 0, 2};
+  // the one-row kernel
+  { const int Ks[] = {64, 256, 260, 512, 516, 1024, 1028, 2048};
+    for (int i = 0; i < 8; ++i)
+      for (int kv : {1, 2}) add(xcase(1, 40, Ks[i], 7, cyc[i % 6] | 1, kv, ((i + kv) & 1) ? 1 : 0)); }
+  for (int K : {64, 1028})
+    for (int N : {1, 7, 8, 9}) {
+      add(xcase(1, N, K, N, N != 8 ? ALL : 2, 0, N == 9 ? 1 : 0));
+      if (N > 1) add(xcase(1, N, K, 3, 1, N == 8 ? 2 : 1));
+    }
+  for (int K : {256, 1024}) {
+    add(xcase(1, 40, K, 40, 1 | 8, 0, 0, 0, 1));
+    add(xcase(1, 40, K, 40, 2 | 4, 0, 1, 0, 2));
+  }
+  { const int parts[7][4] = {{4, 16, 1, 0}, {2, 32, 3, 0}, {8, 32, 2, 1}, {4, 64, 8, 2}, {8, 64, 3, 1}, {16, 32, 8, 0}, {8, 64, 2, 2}};
+    for (int j = 0; j < 7; ++j) {
+      Case c = xcase(1, 40, parts[j][0] * parts[j][1], 40, 2 | 4, 0, j & 1, 0, j % 3 == 2 ? 2 : 0);
+      c.ph = parts[j][0]; c.hd = parts[j][1]; c.ns = parts[j][2]; c.kind = parts[j][3];
+      add(c);
+    } }
+  // rows in registers
+  { const int KM[16][2] = {{256, 2}, {256, 3}, {256, 8}, {256, 9}, {260, 4}, {260, 5}, {260, 17}, {512, 2}, {512, 5}, {516, 2}, {516, 3},
+                           {516, 9}, {1024, 4}, {1028, 2}, {1028, 3}, {2048, 5}};
+    for (int i = 0; i < 16; ++i)
+      for (int addr : {(i & 1) ? 1 : 0, (i & 1) ? 3 : 2})
+        for (int kv : {1, 2}) add(xcase(KM[i][1], 24, KM[i][0], 7, cyc[i % 6] | 1, kv, addr)); }
+  for (int j = 0; j < 2; ++j) {
+    const int M = j ? 9 : 3, addr = j ? 2 : 0;
+    add(xcase(M, 24, 512, 24, 1, 0, addr, 0, 1));
+    add(xcase(M, 24, 512, 24, ALL & ~1, 0, addr, 0, 2));
+  }
+  // 32-row tiles
+  for (int M : {2, 31, 32, 33, 40}) { Case c = xcase(M, 33, 512, 16, ALL, 1, 0, 1); c.mfma_rows = M == 2 ? 1 : 16; add(c); }
+  for (int N : {31, 32, 48}) add(xcase(33, N, 512, 16, 1 | 2, 2, 0, 1));
+  for (int K : {8, 520, 2048})
+    for (int ws : {1, 0, 2}) add(xcase(33, 48, K, 16, ALL, ws == 1 ? 2 : 1, ws == 1 ? 1 : 0, ws));
+  for (int K : {8, 512}) { Case c = xcase(33, 48, K, 16, ALL, 1); c.stats_global = 1; add(c); }
+  { const int Kw[3][2] = {{512, 0}, {2048, 1}, {2048, 0}};
+    for (int i = 0; i < 3; ++i)
+      for (int kv : {1, 2}) add(xcase(33, 48, Kw[i][0], 16, ALL, kv, kv == 1 ? 2 : 3, Kw[i][1])); }
+  { const int Kws[4][3] = {{512, 0, 0}, {512, 0, 1}, {2048, 1, 0}, {2048, 0, 0}};
+    for (int i = 0; i < 4; ++i) {
+      { Case c = xcase(33, 48, Kws[i][0], 48, 1, 0, 0, Kws[i][1], 1); c.stats_global = Kws[i][2]; add(c); }
+      add(xcase(33, 48, Kws[i][0], 48, 2 | 4, 0, Kws[i][2] ? 2 : 0, Kws[i][1], 2));
+    } }
+  { const int Kw[2][2] = {{512, 0}, {2048, 1}};
+    for (int i = 0; i < 2; ++i) {
+      add(xcase(33, 516, Kw[i][0], 516, 2 | 4, 0, 0, Kw[i][1], 2));
+      add(xcase(33, 516, Kw[i][0], 516, 2 | 4, 0, 0, Kw[i][1]));
+    } }
+  add(xcase(33, 516, 512, 516, 2 | 4, 0, 2, 0, 2));
+  add(xcase(33, 516, 512, 516, 2 | 4, 0, 2));
+  // groups of 8 rows in LDS
+  { const int Ms[] = {1, 2, 3, 4, 5, 8, 9};
+    for (int i = 0; i < 7; ++i)
+      for (int K : {2052, 2560}) add(xcase(Ms[i], 24, K, 7, cyc[i % 6] | 1, ((i + K / 4) & 1) ? 2 : 1, i % 3 == 0 ? 1 : 0)); }
+  { const int NM[4][2] = {{516, 1}, {516, 3}, {1024, 1}, {1024, 9}};
+    for (int i = 0; i < 4; ++i) add(xcase(NM[i][1], NM[i][0], 512, NM[i][0], ALL, 0, NM[i][1] == 3 ? 1 : 0)); }
+  add(xcase(17, 24, 2056, 24, 2 | 8));
+  add(xcase(17, 24, 2056, 24, 1 | 2));
+  add(xcase(8, 24, 5116, 24, 1));
+  add(xcase(8, 24, 5120, 24, 1));
+  add(xcase(3, 24, 2052, 7, 1, 1, 2));
+}
 
 // One axis varies while the others stay at their defaults (Case's initialisers), plus the combinations the routes depend on.
 void enumerate() {
@@ -549,6 +659,11 @@ void enumerate() {
   { Case c; c.stage = true; c.M = 2; c.flags = 4; add(c); }                    // a residual's LayerNorm without a residual
   { Case c; c.stage = true; c.M = 2; c.N = 544; c.flags = 6; add(c); }         // a normalised residual of more than 512 features
   { Case c; c.stage = true; c.M = 2; c.K = 2052; add(c); }                     // K > 2048
+  // no statistics hand-off at d_model > 512 on the tiles: the out-projections and linear2 (a normalised residual of 1024 features,
+  // which the tile kernel does not reduce itself) leave the tiles -- groups of 8, in a ragged plan too (no stage with a normalised
+  // residual moves with the position)
+  for (int o : {0, (int)O_RAGGED}) { Case c; c.d = 1024; c.heads = 16; c.B = 17; c.no_handoff = 1; c.opts = o; add(c); }
+  enumerate_stagex();
 }
 
 }  // namespace

@@ -37,6 +37,9 @@ def test_struct_layouts_match():
                _hip.isi_codebook_w, _hip.isi_vqvae_w, _hip.isi_vqvae_out]
     for i, st in enumerate(structs):
         assert lib.isi_abi_struct_bytes(i) == ctypes.sizeof(st)
+    # the arguments of a decoding-loop stage / the single-source block on their own (isi_decode_stage_ex_f32)
+    assert lib.isi_abi_struct_bytes(17) == ctypes.sizeof(_hip.isi_decode_stage_args)
+    assert lib.isi_abi_struct_bytes(18) == ctypes.sizeof(_hip.isi_decode_single_source_args)
     assert lib.isi_abi_struct_bytes(99) == 0
 
 

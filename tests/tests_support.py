@@ -1554,3 +1554,343 @@ def vq_fused_hold_sse(sse_part, spec, what):
     assert not bool(torch.isnan(sse_part).any()), f"{what}: {int(torch.isnan(sse_part).sum())} partials were not written"
     assert abs(total - float(spec.sse)) <= VQ_FUSED_SSE_RTOL * float(spec.sse), \
         f"{what}: summed squared error {total!r} against the spec's {float(spec.sse)!r}"
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The stage kernels of the key/value-cached decoding loop (csrc/prior_decode.hip through isi_decode_stage_ex_f32 and
+# isi_decode_single_source_f32): float64 specifications, their float32 evaluations (the yardsticks of compare_rows and
+# what the host tests apply their mutants to), and the route table -- one case per route of the host plan `stage_kernel()`
+# and of the launchers' template instantiations.  tests/test_decode_stage_host.py holds the specs to float64 torch and shows
+# that every mutant falls outside the bound; tests/test_decode_stage_gpu.py holds the kernels to the specs;
+# tests/decode_plan_tracer.cpp runs the same cases (`stagex/...`, kStageExCases) through the host plan without a GPU.
+DECODE_STAGE_POSITIONS = 3       # slots of every position-addressed array of a case (x, res, the k|v cache)
+DECODE_STAGE_P = 1               # the position (or step of row_pos) a case addresses, by value or in the device counter
+DECODE_STAGE_ROW_INVARIANCE = 4e-6   # a row of a batch against the row alone, GEMV families (tests/test_prior_gpu.py's allowance)
+STAGE_ONE_ROW, STAGE_TILES, STAGE_ROWS_IN_REGISTERS, STAGE_GROUPS_OF_8, STAGE_REFUSED = range(5)
+STAGE_FAMILY = {STAGE_ONE_ROW: "one_row", STAGE_TILES: "tiles", STAGE_ROWS_IN_REGISTERS: "rows_in_registers",
+                STAGE_GROUPS_OF_8: "groups_of_8", STAGE_REFUSED: "refused"}
+STAGE_LAUNCHER = {STAGE_ONE_ROW: "row_gemv1", STAGE_TILES: "row_mfma", STAGE_ROWS_IN_REGISTERS: "row_gemvm",
+                  STAGE_GROUPS_OF_8: "row_linear_8"}
+F_LN, F_RES, F_RES_LN, F_RELU = 1, 2, 4, 8                    # DecodeStageCase.flags
+KV_NONE, KV_F32, KV_BF16 = 0, 1, 2                            # .kv: no out2 (split == N) | fp32 out2 | bf16 out2
+AT_VALUE, AT_COUNTER, AT_ROWS, AT_ROWS_COUNTER = 0, 1, 2, 3   # .addr: by value | device counter | row_pos direct | beside the counter
+WS_NONE, WS_GIVEN, WS_SHORT = 0, 1, 2                         # .ws: the tile workspace: none | given | one float short
+H_NONE, H_STAT_OUT, H_RES_STAT = 0, 1, 2                      # .handoff bits
+# part = (heads, head_dim, splits, kind): kind 0 plain | 1 split 1 of every head is neutral | 2 split 0 lies 60 below the others
+DecodeStageCase = collections.namedtuple("DecodeStageCase", "M N K split flags kv addr ws mfma_rows stats_global part handoff kernel")
+
+
+def _dsc(kernel, M, N, K, split=None, flags=F_LN, kv=KV_NONE, addr=AT_VALUE, ws=WS_NONE, mfma_rows=16, stats_global=0, part=None,
+         handoff=H_NONE):
+    split = N if kv == KV_NONE else split
+    return DecodeStageCase(M, N, K, split, flags, kv, addr, ws, mfma_rows, stats_global, part, handoff, kernel)
+
+
+def decode_stage_case_id(c):
+    h, hd, ns, kind = c.part or (0, 0, 0, 0)
+    return (f"stagex/m{c.M}/n{c.N}/k{c.K}/s{c.split}/f{c.flags}/v{c.kv}/a{c.addr}/w{c.ws}/q{c.mfma_rows}.{c.stats_global}/"
+            f"g{h}.{hd}.{ns}.{kind}/h{c.handoff}")
+
+
+def _decode_stage_table():
+    t = []
+    ALL = F_LN | F_RES | F_RES_LN | F_RELU
+    flag_cycle = (ALL, F_LN, F_LN | F_RES | F_RES_LN, F_LN | F_RES | F_RELU, 0, F_RES)
+    # ---- the one-row kernel: the four KQ on both sides of each threshold; k|v with an odd split, fp32 and bf16; N around the
+    # 8 (KQ <= 2) / 4 (KQ >= 4) features of a workgroup; position by value and by the counter; the hand-off both ways
+    for i, K in enumerate((64, 256, 260, 512, 516, 1024, 1028, 2048)):
+        for kv in (KV_F32, KV_BF16):
+            t.append(_dsc(STAGE_ONE_ROW, 1, 40, K, 7, flag_cycle[i % 6] | F_LN, kv, AT_COUNTER if (i + kv) & 1 else AT_VALUE))
+    for K in (64, 1028):
+        for N in (1, 7, 8, 9):
+            t.append(_dsc(STAGE_ONE_ROW, 1, N, K, flags=ALL if N != 8 else F_RES, addr=AT_COUNTER if N == 9 else AT_VALUE))
+            if N > 1:
+                t.append(_dsc(STAGE_ONE_ROW, 1, N, K, 3, F_LN, KV_BF16 if N == 8 else KV_F32))
+    for K in (256, 1024):
+        t.append(_dsc(STAGE_ONE_ROW, 1, 40, K, flags=F_LN | F_RELU, handoff=H_STAT_OUT))
+        t.append(_dsc(STAGE_ONE_ROW, 1, 40, K, flags=F_RES | F_RES_LN, handoff=H_RES_STAT, addr=AT_COUNTER))
+    # merged input: the out-projection of a batch-1 step (normalised residual, on and off the hand-off)
+    for j, part in enumerate(((4, 16, 1, 0), (2, 32, 3, 0), (8, 32, 2, 1), (4, 64, 8, 2), (8, 64, 3, 1), (16, 32, 8, 0), (8, 64, 2, 2))):
+        t.append(_dsc(STAGE_ONE_ROW, 1, 40, part[0] * part[1], flags=F_RES | F_RES_LN, part=part, addr=AT_COUNTER if j & 1 else AT_VALUE,
+                      handoff=H_RES_STAT if j % 3 == 2 else H_NONE))
+    # ---- rows in registers: the nine (KQ, MR), a ragged last group, row_pos on and off, fp32 and bf16 k|v
+    for i, (K, M) in enumerate(((256, 2), (256, 3), (256, 8), (256, 9), (260, 4), (260, 5), (260, 17), (512, 2), (512, 5), (516, 2),
+                                (516, 3), (516, 9), (1024, 4), (1028, 2), (1028, 3), (2048, 5))):
+        for addr in (AT_COUNTER if i & 1 else AT_VALUE, AT_ROWS_COUNTER if i & 1 else AT_ROWS):
+            for kv in (KV_F32, KV_BF16):
+                t.append(_dsc(STAGE_ROWS_IN_REGISTERS, M, 24, K, 7, flag_cycle[i % 6] | F_LN, kv, addr))
+    for M, addr in ((3, AT_VALUE), (9, AT_ROWS)):
+        t.append(_dsc(STAGE_ROWS_IN_REGISTERS, M, 24, 512, flags=F_LN, handoff=H_STAT_OUT, addr=addr))
+        t.append(_dsc(STAGE_ROWS_IN_REGISTERS, M, 24, 512, flags=ALL & ~F_LN, handoff=H_RES_STAT, addr=addr))
+    # ---- 32-row tiles: M around a tile, N around a tile with the k|v boundary inside it, K in one chunk / a short last chunk /
+    # four chunks; the chunks side by side (workspace), one after the other (none), a workspace one float short
+    for M in (2, 31, 32, 33, 40):
+        t.append(_dsc(STAGE_TILES, M, 33, 512, 16, ALL, KV_F32, mfma_rows=1 if M == 2 else 16, ws=WS_GIVEN))
+    for N in (31, 32, 48):
+        t.append(_dsc(STAGE_TILES, 33, N, 512, 16, F_LN | F_RES, KV_BF16, ws=WS_GIVEN))
+    for K in (8, 520, 2048):
+        for ws in (WS_GIVEN, WS_NONE, WS_SHORT):
+            t.append(_dsc(STAGE_TILES, 33, 48, K, 16, ALL, KV_BF16 if ws == WS_GIVEN else KV_F32, ws=ws,
+                          addr=AT_COUNTER if ws == WS_GIVEN else AT_VALUE))
+    for K in (8, 512):                                   # the statistics from memory where the staged tile would give them
+        t.append(_dsc(STAGE_TILES, 33, 48, K, 16, ALL, KV_F32, stats_global=1))
+    for K, ws in ((512, WS_NONE), (2048, WS_GIVEN), (2048, WS_NONE)):
+        for kv in (KV_F32, KV_BF16):
+            t.append(_dsc(STAGE_TILES, 33, 48, K, 16, ALL, kv, AT_ROWS if kv == KV_F32 else AT_ROWS_COUNTER, ws))
+    for K, ws, sg in ((512, WS_NONE, 0), (512, WS_NONE, 1), (2048, WS_GIVEN, 0), (2048, WS_NONE, 0)):
+        t.append(_dsc(STAGE_TILES, 33, 48, K, flags=F_LN, handoff=H_STAT_OUT, ws=ws, stats_global=sg))
+        t.append(_dsc(STAGE_TILES, 33, 48, K, flags=F_RES | F_RES_LN, handoff=H_RES_STAT, ws=ws, addr=AT_ROWS if sg else AT_VALUE))
+    # a normalised residual of 516 features: on the tiles with its statistics handed (8 residual floats per lane and row are what
+    # the tile kernel reduces itself); without them the plan leaves the tiles -- five groups of 8, or refused with row_pos
+    for K, ws in ((512, WS_NONE), (2048, WS_GIVEN)):
+        t.append(_dsc(STAGE_TILES, 33, 516, K, flags=F_RES | F_RES_LN, ws=ws, handoff=H_RES_STAT))
+        t.append(_dsc(STAGE_GROUPS_OF_8, 33, 516, K, flags=F_RES | F_RES_LN, ws=ws))
+    t.append(_dsc(STAGE_TILES, 33, 516, 512, flags=F_RES | F_RES_LN, addr=AT_ROWS, handoff=H_RES_STAT))
+    t.append(_dsc(STAGE_REFUSED, 33, 516, 512, flags=F_RES | F_RES_LN, addr=AT_ROWS))
+    # ---- groups of 8 rows in LDS: the four row capacities, two launches at 9 rows, the K tail beyond 8 float4 per lane
+    for i, M in enumerate((1, 2, 3, 4, 5, 8, 9)):
+        for K in (2052, 2560):
+            t.append(_dsc(STAGE_GROUPS_OF_8, M, 24, K, 7, flag_cycle[i % 6] | F_LN, KV_BF16 if (i + K // 4) & 1 else KV_F32,
+                          AT_COUNTER if i % 3 == 0 else AT_VALUE))
+    for N, M in ((516, 1), (516, 3), (1024, 1), (1024, 9)):
+        t.append(_dsc(STAGE_GROUPS_OF_8, M, N, 512, flags=ALL, addr=AT_COUNTER if M == 3 else AT_VALUE))
+    # 17 rows of K = 2056: on the tiles (a short fifth chunk) without a LayerNorm; with one, whose statistics the tiles form for
+    # K <= 2048 only, in three groups of 8
+    t.append(_dsc(STAGE_TILES, 17, 24, 2056, flags=F_RES | F_RELU))
+    t.append(_dsc(STAGE_GROUPS_OF_8, 17, 24, 2056, flags=F_LN | F_RES))
+    t.append(_dsc(STAGE_GROUPS_OF_8, 8, 24, 5116, flags=F_LN))        # 8 rows of 5116 floats: the last that fit in 160 KiB with
+    t.append(_dsc(STAGE_REFUSED, 8, 24, 5120, flags=F_LN))            # ... their statistics; beyond the LDS bound: refused
+    t.append(_dsc(STAGE_REFUSED, 3, 24, 2052, 7, F_LN, KV_F32, AT_ROWS))   # per-row positions where no batched kernel takes K
+    return t
+
+
+DECODE_STAGE_CASES = _decode_stage_table()
+
+
+def decode_stage_instance(c):
+    """The template instantiation(s) the launchers of csrc/prior_decode.hip pick for a case, from its shape alone."""
+    kq = 1 if c.K <= 256 else 2 if c.K <= 512 else 4 if c.K <= 1024 else 8
+    kv16, rag = c.kv == KV_BF16, c.addr in (AT_ROWS, AT_ROWS_COUNTER)
+    if c.kernel == STAGE_ONE_ROW:
+        return ("row_gemv1", kq, kv16, c.part is not None)
+    if c.kernel == STAGE_ROWS_IN_REGISTERS:
+        mr = 2 if c.M <= 2 else 4 if c.M <= 4 else 8
+        while kq * mr > 16:
+            mr //= 2
+        return ("row_gemvm", kq, mr, rag, kv16)
+    if c.kernel == STAGE_TILES:
+        nz, tiles = -(-c.K // 512), -(-c.N // 32) * -(-c.M // 32)
+        side_by_side = nz > 1 and tiles < 128 and c.ws == WS_GIVEN
+        stats = "none" if not c.flags & F_LN else "staged" if c.K <= 512 and not c.stats_global else "memory"
+        return ("row_mfma32", rag, kv16, side_by_side, stats)
+    if c.kernel == STAGE_GROUPS_OF_8:
+        groups = [min(8, c.M - m0) for m0 in range(0, c.M, 8)]
+        return ("row_linear_ln", tuple(1 if g <= 1 else 2 if g <= 2 else 4 if g <= 4 else 8 for g in groups), kv16)
+    return ("refused",)
+
+
+def decode_stage_coverage_gaps(cases):
+    """What `cases` leave out of the template instantiations the launchers of csrc/prior_decode.hip can pick: [] when every
+    KQ x KV16 of the one-row kernel (and the merged input at both KQ it exists for), every (KQ, MR) x RAG x KV16 of the
+    rows-in-registers kernel, RAG x KV16 x (chunks side by side with the finishing launch | not) and the three forms of the
+    input statistics of the tiles, and every MR x KV16 of the LDS kernel (two launches at 9 rows) occur."""
+    inst = collections.Counter(decode_stage_instance(c) for c in cases)
+    want = [("row_gemv1", kq, kv16, False) for kq in (1, 2, 4, 8) for kv16 in (False, True)]
+    want += [("row_gemv1", 1, False, True), ("row_gemv1", 2, False, True)]
+    want += [("row_gemvm", kq, mr, rag, kv16) for kq, mr in ((1, 2), (1, 4), (1, 8), (2, 2), (2, 4), (2, 8), (4, 2), (4, 4), (8, 2))
+             for rag in (False, True) for kv16 in (False, True)]
+    gaps = [w for w in want if not inst[w]]
+    gaps += [("row_mfma32", rag, kv16, side) for rag in (False, True) for kv16 in (False, True) for side in (False, True)
+             if not any(k[:4] == ("row_mfma32", rag, kv16, side) for k in inst)]
+    gaps += [("row_mfma32 statistics", f) for f in ("none", "staged", "memory") if not any(k[0] == "row_mfma32" and k[4] == f for k in inst)]
+    gaps += [("row_linear_ln", mr, kv16) for mr in (1, 2, 4, 8) for kv16 in (False, True)
+             if not any(k[0] == "row_linear_ln" and k[2] == kv16 and mr in k[1] for k in inst)]
+    gaps += [("row_linear_ln", "two launches")] if not any(k[0] == "row_linear_ln" and len(k[1]) == 2 for k in inst) else []
+    return gaps
+
+
+def decode_stage_row_positions(M, own=True):
+    """row_pos [2 steps][M]: at step DECODE_STAGE_P row m stands at its own position (own) or every row at DECODE_STAGE_P; the
+    other step holds other valid positions, so a kernel reading the wrong step reads rows that hold NaN."""
+    P = DECODE_STAGE_POSITIONS
+    at = [(2 * m + 1) % P if own else DECODE_STAGE_P for m in range(M)]
+    other = [(a + 1) % P for a in at]
+    rows = [other, at] if DECODE_STAGE_P == 1 else [at, other]
+    return torch.tensor(rows, dtype=torch.int32)
+
+
+def decode_stage_data(c, seed=None):
+    """The tensors of a case on the CPU, float32: x [P][M][K] and res [P][M][N] at every position (rows differ in scale and
+    offset, so a neighbour's statistics do not fit), W [N][K], bias, the LayerNorm parameters, the attention partials."""
+    g = torch.Generator().manual_seed(seed if seed is not None else 1000003 * c.M + 1009 * c.N + c.K + 17 * c.flags + c.addr)
+    P, M, N, K = DECODE_STAGE_POSITIONS, c.M, c.N, c.K
+    rnd = lambda *s: torch.randn(*s, generator=g)
+    d = {}
+    scale = 0.5 + 1.5 * torch.rand(P, M, 1, generator=g)
+    d["x"] = rnd(P, M, K) * scale + (2.0 * torch.rand(P, M, 1, generator=g) - 1.0)
+    d["W"] = rnd(N, K) / math.sqrt(K)
+    d["bias"] = rnd(N)
+    d["ln_g"], d["ln_b"] = 1 + 0.1 * rnd(K), 0.1 * rnd(K)
+    d["res"] = rnd(P, M, N) * (0.5 + 1.5 * torch.rand(P, M, 1, generator=g)) + (2.0 * torch.rand(P, M, 1, generator=g) - 1.0)
+    d["res_g"], d["res_b"] = 1 + 0.1 * rnd(N), 0.1 * rnd(N)
+    if c.part:
+        H, HD, NS, kind = c.part
+        part = torch.zeros(H, NS, HD + 4)
+        part[:, :, :HD] = rnd(H, NS, HD)
+        part[:, :, HD] = 3.0 * rnd(H, NS)                                   # the split's maximum logit
+        part[:, :, HD + 1] = 0.5 + 1.5 * torch.rand(H, NS, generator=g)     # its sum of exp(logit - maximum)
+        if kind == 1:                        # what the attention kernel writes for a split without keys
+            part[:, 1, :HD], part[:, 1, HD], part[:, 1, HD + 1] = 0.0, -1e30, 0.0
+        if kind == 2:
+            part[:, 0, HD] = part[:, 1:, HD].amax(dim=1) - 60.0
+        d["part"] = part
+    return d
+
+
+def decode_stage_rows(c, d, row_pos=None):
+    """(x rows [M][K], residual rows [M][N]) the case addresses: position DECODE_STAGE_P, or row m at row_pos[DECODE_STAGE_P][m]."""
+    at = [DECODE_STAGE_P] * c.M if row_pos is None else [int(v) for v in row_pos[DECODE_STAGE_P]]
+    m = torch.arange(c.M)
+    return d["x"][at, m], d["res"][at, m]
+
+
+def row_stats(rows, eps, dtype=torch.float64, pad_to=None):
+    """[M][2]: (mean, 1 / sqrt(biased variance + eps)) per row.  Mutants: `pad_to`, the variance also sums (0 - mean)^2 over the
+    lanes between the width and its next multiple of pad_to (a missing bounds check in the second pass)."""
+    z = rows.to(dtype)
+    D = z.shape[-1]
+    mean = z.sum(dim=-1, keepdim=True) / D
+    sq = (z - mean).pow(2).sum(dim=-1, keepdim=True)
+    if pad_to:
+        sq = sq + (-(-D // pad_to) * pad_to - D) * mean * mean
+    return torch.cat([mean, 1.0 / torch.sqrt(sq / D + eps)], dim=-1)
+
+
+def _normalise(rows, stats, gamma, beta):
+    return (rows - stats[:, :1]) * stats[:, 1:] * gamma + beta
+
+
+def decode_stage_eval(dtype, x, W, bias=None, ln=None, res=None, res_ln=None, relu=False, eps=1e-5, split=None, res_stats=None,
+                      stat_perm=None, res_stat_perm=None, pad_to=None, k_keep=None, out2_shift=0):
+    """(out [M][split], out2 [M][N - split] or None, the input rows' statistics [M][2] or None) of a stage in `dtype`:
+    act(LN(x) W^T + bias + LN_res(res)), LayerNorm statistics (mean, 1 / sqrt(var + eps)) per row; `res_stats` [M][2]: the
+    residual's statistics as given.  The mutants of the host tests: stat_perm / res_stat_perm, row m is normalised with the
+    statistics of row perm[m]; pad_to (row_stats); k_keep, the products beyond k_keep are dropped; out2_shift, out2's columns
+    rolled by that many."""
+    t = lambda v: None if v is None else torch.as_tensor(v).detach().cpu().to(dtype)
+    x, W, bias, res = t(x), t(W), t(bias), t(res)
+    stats = None
+    if ln is not None:
+        stats = row_stats(x, eps, dtype, pad_to=pad_to)
+        x = _normalise(x, stats if stat_perm is None else stats[stat_perm], t(ln[0]), t(ln[1]))
+    y = x @ W.t() if k_keep is None else x[:, :k_keep] @ W[:, :k_keep].t()
+    if bias is not None:
+        y = y + bias
+    if res is not None:
+        if res_ln is not None:
+            rs = row_stats(res, eps, dtype, pad_to=pad_to) if res_stats is None else t(res_stats)
+            res = _normalise(res, rs if res_stat_perm is None else rs[res_stat_perm], t(res_ln[0]), t(res_ln[1]))
+        y = y + res
+    if relu:
+        y = y.clamp(min=0.0)
+    split = y.shape[1] if split is None else split
+    out2 = y[:, split:] if split < y.shape[1] else None
+    if out2 is not None and out2_shift:
+        out2 = out2.roll(out2_shift, dims=1)
+    return y[:, :split], out2, stats
+
+
+def decode_stage_spec(*a, **kw):
+    return decode_stage_eval(torch.float64, *a, **kw)
+
+
+def decode_stage_f32(*a, **kw):
+    return decode_stage_eval(torch.float32, *a, **kw)
+
+
+def merge_partials_eval(dtype, part, splits=None, subtract_max=True):
+    """The input row [H * HD] from an attention's key-split partials [H][NS][HD + 4] = (o[HD], max, sum, -, -):
+    M = max_s max_s, w_s = exp(max_s - M), x = sum_s w_s o_s / sum_s w_s sum_s.  Mutants: `splits`, only the first that many
+    are merged; subtract_max=False, w_s = exp(max_s)."""
+    p = torch.as_tensor(part).detach().cpu().to(dtype)
+    HD = p.shape[2] - 4
+    p = p[:, :splits] if splits else p
+    mx = p[:, :, HD]
+    w = torch.exp(mx - mx.amax(dim=1, keepdim=True)) if subtract_max else torch.exp(mx)
+    num = (w.unsqueeze(-1) * p[:, :, :HD]).sum(dim=1)
+    den = (w * p[:, :, HD + 1]).sum(dim=1, keepdim=True)
+    return (num / den).reshape(1, -1)
+
+
+def merge_partials_spec(part):
+    return merge_partials_eval(torch.float64, part)
+
+
+def merge_partials_f32(part, **kw):
+    return merge_partials_eval(torch.float32, part, **kw)
+
+
+def single_source_eval(dtype, y1, gamma, beta, table, pos, Cd, eps=1e-5, with_stats=True):
+    """(y2 [B][d], its statistics [B][2]) of the single-source cross-attention block: y2[m] = LN1(y1[m]) + table[pos[m] // Cd][m]
+    for a table [S_src][B or 1][d] (one row per source position: shared by all rows)."""
+    t = lambda v: torch.as_tensor(v).detach().cpu().to(dtype)
+    y1, table = t(y1), t(table)
+    B = y1.shape[0]
+    src = torch.stack([table[int(pos[m]) // Cd, m if table.shape[1] > 1 else 0] for m in range(B)])
+    y2 = _normalise(y1, row_stats(y1, eps, dtype), t(gamma), t(beta)) + src
+    return y2, (row_stats(y2, eps, dtype) if with_stats else None)
+
+
+def single_source_spec(*a, **kw):
+    return single_source_eval(torch.float64, *a, **kw)
+
+
+def single_source_f32(*a, **kw):
+    return single_source_eval(torch.float32, *a, **kw)
+
+
+def bf16_widen(bits):
+    """int16 bf16 patterns -> float32."""
+    return (torch.as_tensor(bits).cpu().to(torch.int32) << 16).view(torch.float32)
+
+
+def bf16_bits(v, truncate=False):
+    """float32 -> int16 bf16 patterns, rounded to nearest-even (the mutant: truncated)."""
+    v = torch.as_tensor(v).detach().cpu().float().contiguous()
+    if truncate:
+        return (v.view(torch.int32) >> 16).to(torch.int16)
+    return v.to(torch.bfloat16).view(torch.int16)
+
+
+def compare_rows_bf16(got, ref, yardstick, what, margin=ROW_OPS_MARGIN):
+    """compare_rows for values stored as bf16 (`got`: widened): every element within the fp32 bound of its row --
+    margin * max(row_error(yardstick, ref), 2^-23) * max|ref_row| -- plus half a bf16 ulp of the spec value (8 bits of
+    significand: 2^(exponent - 8)).  ratio: the part of the error beyond the half ulp against the yardstick."""
+    got, ref = _f64(got), _f64(ref)
+    assert got.shape == ref.shape and bool(torch.isfinite(got).all()), f"{what}: shape or a non-finite value"
+    yard = max(row_error(yardstick, ref), ROW_OPS_FLOOR)
+    assert math.isfinite(yard), f"{what}: the float32 yardstick itself is not finite"
+    half_ulp = torch.exp2(torch.floor(torch.log2(ref.abs().clamp(min=2.0 ** -126))) - 8.0)
+    scale = ref.abs().amax(dim=-1, keepdim=True).clamp(min=2.0 ** -100)
+    beyond = (((got - ref).abs() - half_ulp).clamp(min=0.0) / scale).max()
+    err, ratio = float(((got - ref).abs() / scale).max()), float(beyond) / yard
+    assert ratio <= margin, (f"{what}: {float(beyond):.3e} beyond half a bf16 ulp is {ratio:.1f} times the float32 yardstick "
+                             f"{yard:.3e} (margin {margin:g})")
+    return RowCheck(what, err, yard, ratio)
+
+
+# isi_decode_single_source_f32: (d, B, Cd, shared table, addressing, stat_out)
+SingleSourceCase = collections.namedtuple("SingleSourceCase", "d B Cd shared addr stats")
+SINGLE_SOURCE_CASES = [SingleSourceCase(*v) for v in (
+    (64, 1, 1, False, AT_VALUE, True), (64, 3, 4, True, AT_COUNTER, True), (64, 4, 4, False, AT_ROWS, True),
+    (64, 5, 1, False, AT_ROWS_COUNTER, False), (100, 1, 4, True, AT_COUNTER, False), (100, 3, 1, False, AT_ROWS, False),
+    (100, 4, 4, True, AT_VALUE, True), (100, 5, 4, False, AT_ROWS_COUNTER, True), (1024, 1, 4, False, AT_COUNTER, True),
+    (1024, 3, 4, False, AT_VALUE, False), (1024, 4, 1, True, AT_ROWS_COUNTER, True), (1024, 5, 4, True, AT_ROWS, True))]
+SINGLE_SOURCE_P = 5              # the position / step addressed; rows of a ragged launch stand at SINGLE_SOURCE_P - (m % 3) * 2
+SINGLE_SOURCE_S_SRC = 6
+
+
+def single_source_positions(c, own=True):
+    """[steps = SINGLE_SOURCE_P + 1][B] positions; the step addressed is the last."""
+    at = [SINGLE_SOURCE_P - ((m % 3) * 2 if own else 0) for m in range(c.B)]
+    return torch.tensor([[(a + 1 + t) % (SINGLE_SOURCE_P + 1) for a in at] for t in range(SINGLE_SOURCE_P)] + [at], dtype=torch.int32)

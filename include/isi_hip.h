@@ -188,6 +188,32 @@ int isi_code_search_f32(const uint16_t *codes, const uint16_t *query, const floa
                         const uint8_t *allowed, float *dist, int64_t N, int64_t C, int K, int Q, int accumulate,
                         void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------ search of a code database by encoder vectors */
+/* The asymmetric distance (specification tests/code_soft_search_spec.py): the query is not a
+ * codemap but one vector per cell -- an encoder's output before it is snapped to a code, or a blend of codes -- and is
+ * compared with the stored codes' vectors, dist(z, x) = sum_c w[c] |z[c] - E[x[c]]|^2.  The searches take it as per-cell
+ * ROWS of K floats, so any other per-cell cost can be searched the same way:
+ *   R[c][k]    = sum_d (z[c][d] - E[k][d])^2                      d ascending, fp32 fma (the table's expression)
+ *   dist[j][n] = sum_c w[j][c] * R[j][c][codes[n][c]]
+ * isi_code_query_rows_f32: z fp32 [cells, D] with a row stride of z_stride >= D floats (an NHWC activation is read in
+ * place), codebook [K, D] row-major -> rows fp32 [cells, K].  Where z[c] equals codebook row a bit for bit, rows[c][:]
+ * equals isi_code_distance_table_f32's T[a][:] bit for bit; |R - R64| <= (D + 4) 2^-24 R64; a non-finite vector gives a
+ * non-finite row by IEEE rules and touches no other row.  ISI_E_INVALID for a null or float-misaligned pointer, cells,
+ * K or D <= 0, z_stride < D; ISI_E_UNSUPPORTED for K > 65535 and cells * K >= 2^39.
+ * isi_code_search_rows_f32: isi_code_search_f32 with rows fp32 [Q, C, K] in place of query and table.  A cell whose
+ * weight is exactly 0 contributes +0 whatever its row holds, NaN and inf included: that is this search's mask (there is no
+ * mask token).  Everything else is isi_code_search_f32's contract word for word -- weights >= 0 or NULL, one rounding per
+ * product, runs of 256 cells in cell order and the run sums in run order, no atomics, stored codes >= K clamped to K - 1,
+ * allowed, accumulate, item-local and deterministic results, |dist - spec| <= (C + 2) 2^-24 sum_c |w R| -- and with
+ * rows[j][c] = T[query[j][c]] gathered by the caller (mask-token cells under weight 0) dist equals isi_code_search_f32's
+ * bit for bit.  The workspace is isi_code_search_workspace_bytes's; the refusals are isi_code_search_f32's, with `rows`
+ * where it names query and table. */
+int isi_code_query_rows_f32(const float *z, int64_t z_stride, const float *codebook, float *rows, int64_t cells, int K, int D,
+                            void *stream);
+int isi_code_search_rows_f32(const uint16_t *codes, const float *rows, const float *weights, const uint8_t *allowed,
+                             float *dist, int64_t N, int64_t C, int K, int Q, int accumulate, void *workspace,
+                             size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------ shift-invariant search of a code database */
 /* "Which stored sound contains something like this fragment, wherever it sits in time" (DESIGN.md section 6c;
  * specification tests/code_shift_search_spec.py).  codes uint16 [N, F, T], query uint16 [Q, F, W] with 1 <= W <= T,
@@ -214,11 +240,21 @@ int isi_code_search_f32(const uint16_t *codes, const uint16_t *query, const floa
  * F * T >= 2^31, Q * S * N >= 2^39, more than 2^31 - 1 workgroups (ISI_E_UNSUPPORTED).
  * isi_code_shift_best_f32: best[j][n] = min_s dist[j][s][n] and best_shift[j][n] = the smallest s that attains it
  * (int32); where allowed[n] == 0 (allowed uint8 [N] or NULL) best is +inf and best_shift -1.  ISI_E_INVALID for a null
- * or misaligned dist / best / best_shift, N or S <= 0, Q outside 1..64; ISI_E_UNSUPPORTED for Q * S * N >= 2^39. */
+ * or misaligned dist / best / best_shift, N or S <= 0, Q outside 1..64; ISI_E_UNSUPPORTED for Q * S * N >= 2^39.
+ * isi_code_shift_search_rows_f32: the same search by encoder vectors (section above): window rows fp32 [Q, F * W, K],
+ * cell c = f * W + t, in place of query and table,
+ *   dist[j][s][n] = sum_f sum_t w[j][f][t] * R[j][f * W + t][codes[n][f][t + o_s]]
+ * with isi_code_shift_search_f32's summation order, workspace and refusals (`rows` where it names query and table) and
+ * isi_code_search_rows_f32's zero-weight rule.  With gathered table rows it equals isi_code_shift_search_f32 bit for
+ * bit; at W == T, S == 1, shift0 == 0 it equals isi_code_search_rows_f32 bit for bit.  isi_code_shift_best_f32 serves
+ * both. */
 size_t isi_code_shift_search_workspace_bytes(int64_t N, int F, int T, int W, int S, int K, int Q);
 int isi_code_shift_search_f32(const uint16_t *codes, const uint16_t *query, const float *weights, const float *table,
                               float *dist, int64_t N, int F, int T, int W, int shift0, int step, int S, int K, int Q,
                               int accumulate, void *workspace, size_t workspace_bytes, void *stream);
+int isi_code_shift_search_rows_f32(const uint16_t *codes, const float *rows, const float *weights, float *dist, int64_t N,
+                                   int F, int T, int W, int shift0, int step, int S, int K, int Q, int accumulate,
+                                   void *workspace, size_t workspace_bytes, void *stream);
 int isi_code_shift_best_f32(const float *dist, const uint8_t *allowed, float *best, int32_t *best_shift, int64_t N, int S,
                             int Q, void *stream);
 

@@ -20,6 +20,12 @@
 // Q <= 64 (grid.z).  Codes are read as 16-byte vectors when C % 8 == 0, the base is 16-byte aligned and K <= 2048 (a
 // chunk then holds a multiple of 8 cells), one by one otherwise; table rows as float4 when K % 4 == 0 and the base is
 // 16-byte aligned.  A stored code >= K is clamped to K - 1: nothing is read outside the stage.
+//
+// Search by encoder vectors (specification tests/code_soft_search_spec.py).  Nothing in the look-up
+// cares where a staged row came from: isi_code_search_rows_f32 runs the same kernel with the stage fed from per-cell rows
+// R [Q][C][K] (template argument ROWS; a zero weight stages zeros), and isi_code_query_rows_f32 builds such rows from
+// vectors, R[c][k] = sum_d (z[c][d] - E[k][d])^2 -- the table's expression, so vectors that are codebook rows give the
+// table's rows and the hard search's distances bit for bit.
 #include "isi_common.h"
 #include "isi_internal.h"
 #include "device_prims.h"
@@ -51,9 +57,74 @@ __global__ __launch_bounds__(256) void code_distance_table_kernel(const float *_
   T[(size_t)a * K + b] = acc;
 }
 
+// Rows of a query given as vectors: R[c][k] = sum_d (z[c][d] - E[k][d])^2 -- the table kernel's expression with the query
+// on the `a` side, d ascending, one fma per d, so a vector that IS codebook row a gives T[a][:] bit for bit.  One workgroup
+// (256 threads) owns QR_CELLS cells x 256 codes: lane k keeps one accumulator per cell and walks d in chunks of QR_D.  A
+// chunk of the codebook tile is staged transposed, Et[d][k] with a row stride of 257 floats (the transposing writes and the
+// lane-per-code reads are both conflict-free); the cells' vectors are staged as they lie and read back as uniform 16-byte
+// broadcasts.  d beyond D is staged as 0 on both sides: fma(0, 0, acc) == acc for every acc this sum can hold (never -0).
+// The stores of one cell are 256 consecutive floats of its row.
+constexpr int QR_THREADS = 256;
+constexpr int QR_CELLS = 32;
+constexpr int QR_D = 32;
+constexpr int QR_ESTRIDE = QR_THREADS + 1;
+
+__global__ __launch_bounds__(QR_THREADS) void code_query_rows_kernel(const float *__restrict__ z, int64_t z_stride,
+                                                                     const float *__restrict__ E, float *__restrict__ R,
+                                                                     int64_t cells, int K, int D) {
+  __shared__ float Et[QR_D * QR_ESTRIDE];
+  __shared__ float4 zs[QR_CELLS * (QR_D / 4)];
+  const int tid = (int)threadIdx.x;
+  const int64_t c0 = (int64_t)blockIdx.x * QR_CELLS;
+  const int k0 = (int)blockIdx.y * QR_THREADS;
+  float acc[QR_CELLS];
+#pragma unroll
+  for (int cl = 0; cl < QR_CELLS; ++cl) acc[cl] = 0.f;
+  for (int d0 = 0; d0 < D; d0 += QR_D) {
+#pragma unroll 4
+    for (int i = 0; i < QR_D; ++i) {                 // 256 codes x 32 d: a wave reads two 128-byte pieces of two codes
+      const int idx = i * QR_THREADS + tid, kk = idx / QR_D, dd = idx % QR_D;
+      float v = 0.f;
+      if (k0 + kk < K && d0 + dd < D) v = E[(size_t)(k0 + kk) * D + d0 + dd];
+      Et[dd * QR_ESTRIDE + kk] = v;
+    }
+#pragma unroll
+    for (int i = 0; i < QR_CELLS * QR_D / QR_THREADS; ++i) {
+      const int idx = i * QR_THREADS + tid, cl = idx / QR_D, dd = idx % QR_D;
+      float v = 0.f;
+      if (c0 + cl < cells && d0 + dd < D) v = z[(size_t)(c0 + cl) * (size_t)z_stride + d0 + dd];
+      reinterpret_cast<float *>(zs)[cl * QR_D + dd] = v;
+    }
+    __syncthreads();
+    for (int d4 = 0; d4 < QR_D / 4; ++d4) {
+      const float e0 = Et[(4 * d4 + 0) * QR_ESTRIDE + tid], e1 = Et[(4 * d4 + 1) * QR_ESTRIDE + tid];
+      const float e2 = Et[(4 * d4 + 2) * QR_ESTRIDE + tid], e3 = Et[(4 * d4 + 3) * QR_ESTRIDE + tid];
+#pragma unroll
+      for (int cl = 0; cl < QR_CELLS; ++cl) {
+        const float4 zv = zs[cl * (QR_D / 4) + d4];
+        float diff = zv.x - e0;
+        acc[cl] = fmaf(diff, diff, acc[cl]);
+        diff = zv.y - e1;
+        acc[cl] = fmaf(diff, diff, acc[cl]);
+        diff = zv.z - e2;
+        acc[cl] = fmaf(diff, diff, acc[cl]);
+        diff = zv.w - e3;
+        acc[cl] = fmaf(diff, diff, acc[cl]);
+      }
+    }
+    __syncthreads();
+  }
+  if (k0 + tid < K) {
+#pragma unroll
+    for (int cl = 0; cl < QR_CELLS; ++cl)
+      if (c0 + cl < cells) R[(size_t)(c0 + cl) * (size_t)K + k0 + tid] = acc[cl];
+  }
+}
+
 // G > 0: chunks of 8 G cells, an item's codes read as 16-byte vectors, SUB chunks' worth at a time (SUB = 2 at G = 4: the
 // 128 bytes of a whole cache line per item); G == 0: chunks of cc cells, codes read one by one inside the look-up loop.
-template <int G, int IPT, int SUB>
+// ROWS: `table` holds per-cell rows R [Q][C][K] (isi_code_search_rows_f32) and `query` is unused; only the stage differs.
+template <int G, int IPT, int SUB, bool ROWS>
 __global__ __launch_bounds__(CS_THREADS) void code_search_kernel(const uint16_t *__restrict__ codes,
                                                                  const uint16_t *__restrict__ query,
                                                                  const float *__restrict__ weights,
@@ -66,7 +137,7 @@ __global__ __launch_bounds__(CS_THREADS) void code_search_kernel(const uint16_t 
   const int64_t n0 = (int64_t)blockIdx.x * (CS_THREADS * IPT) + tid;
   const int c_begin = split * CS_SPLIT;
   const int c_end = C - c_begin < CS_SPLIT ? C : c_begin + CS_SPLIT;
-  const uint16_t *__restrict__ qj = query + (size_t)j * C;
+  const uint16_t *__restrict__ qj = ROWS ? nullptr : query + (size_t)j * C;   // (no query on the rows route)
   const float *__restrict__ wj = weights ? weights + (size_t)j * C : nullptr;
   const unsigned kmax = (unsigned)K - 1u;
   if (G > 0) cc = 8 * G;
@@ -91,7 +162,8 @@ __global__ __launch_bounds__(CS_THREADS) void code_search_kernel(const uint16_t 
       const int c0 = cb + sub * cc;
       if (c0 >= c_end) break;
       const int ncell = c_end - c0 < cc ? c_end - c0 : cc;
-      stage_code_rows<CS_THREADS>(rows, qj, wj, table, c0, ncell, K, vec_table);
+      if constexpr (ROWS) stage_query_rows<CS_THREADS>(rows, table, wj, j, C, c0, ncell, K, vec_table);
+      else stage_code_rows<CS_THREADS>(rows, qj, wj, table, c0, ncell, K, vec_table);
       __syncthreads();
       if (G > 0) {
 #pragma unroll
@@ -162,48 +234,77 @@ int code_distance_table_f32(const float *codebook, float *table, int K, int D, h
   return check_launch("code_distance_table");
 }
 
+int code_query_rows_f32(const float *z, int64_t z_stride, const float *codebook, float *rows, int64_t cells, int K, int D,
+                        hipStream_t st) {
+  if (!z) return invalid("code_query_rows: z is a null pointer");
+  if (!codebook) return invalid("code_query_rows: codebook is a null pointer");
+  if (!rows) return invalid("code_query_rows: rows is a null pointer");
+  if (cells <= 0) return invalid("code_query_rows: cells must be positive");
+  if (K <= 0) return invalid("code_query_rows: K must be positive");
+  if (D <= 0) return invalid("code_query_rows: D must be positive");
+  if (z_stride < D) return invalid("code_query_rows: z_stride must be at least D");
+  if (reinterpret_cast<uintptr_t>(z) & 3) return invalid("code_query_rows: z must be aligned to a float");
+  if (reinterpret_cast<uintptr_t>(codebook) & 3) return invalid("code_query_rows: codebook must be aligned to a float");
+  if (reinterpret_cast<uintptr_t>(rows) & 3) return invalid("code_query_rows: rows must be aligned to a float");
+  if (K > 65535) return unsupported("code_query_rows: K beyond 65535 (stored codes are 16-bit)");
+  if ((unsigned __int128)cells * (unsigned)K >= ((unsigned __int128)1 << 39))
+    return unsupported("code_query_rows: cells * K beyond 2^39");
+  if ((cells + QR_CELLS - 1) / QR_CELLS >= ((int64_t)1 << 31))
+    return unsupported("code_query_rows: cells beyond 2^31 - 1 workgroups of 32");
+  if ((unsigned __int128)cells * (unsigned __int128)z_stride >= ((unsigned __int128)1 << 62))
+    return unsupported("code_query_rows: cells * z_stride beyond 2^62");
+  const dim3 grid((unsigned)((cells + QR_CELLS - 1) / QR_CELLS), (unsigned)((K + QR_THREADS - 1) / QR_THREADS)), block(QR_THREADS);
+  hipLaunchKernelGGL(code_query_rows_kernel, grid, block, 0, st, z, z_stride, codebook, rows, cells, K, D);
+  return check_launch("code_query_rows");
+}
+
 size_t code_search_workspace_bytes(int64_t N, int64_t C, int K, int Q) {
   if (N <= 0 || C <= 0 || K <= 0 || Q <= 0 || Q > CS_MAX_Q || C > CS_MAX_C) return 0;
   const unsigned __int128 b = (unsigned __int128)num_splits(C) * (unsigned)Q * (unsigned __int128)N * sizeof(float);
   return b > (unsigned __int128)SIZE_MAX ? 0 : (size_t)b;
 }
 
-int code_search_f32(const uint16_t *codes, const uint16_t *query, const float *weights, const float *table,
-                    const uint8_t *allowed, float *dist, int64_t N, int64_t C, int K, int Q, int accumulate, void *workspace,
-                    size_t workspace_bytes, hipStream_t st) {
-  if (!codes) return invalid("code_search: codes is a null pointer");
-  if (!query) return invalid("code_search: query is a null pointer");
-  if (!table) return invalid("code_search: table is a null pointer");
-  if (!dist) return invalid("code_search: dist is a null pointer");
-  if (!workspace) return invalid("code_search: workspace is a null pointer");
-  if (N <= 0) return invalid("code_search: N must be positive");
-  if (C <= 0) return invalid("code_search: C must be positive");
-  if (K <= 0) return invalid("code_search: K must be positive");
-  if (Q < 1 || Q > CS_MAX_Q) return invalid("code_search: Q must lie in 1..64");
-  if (accumulate != 0 && accumulate != 1) return invalid("code_search: accumulate must be 0 or 1");
-  if (reinterpret_cast<uintptr_t>(codes) & 1) return invalid("code_search: codes must be aligned to 2 bytes");
-  if (reinterpret_cast<uintptr_t>(query) & 1) return invalid("code_search: query must be aligned to 2 bytes");
-  if (reinterpret_cast<uintptr_t>(weights) & 3) return invalid("code_search: weights must be aligned to a float");
-  if (reinterpret_cast<uintptr_t>(table) & 3) return invalid("code_search: table must be aligned to a float");
-  if (reinterpret_cast<uintptr_t>(dist) & 3) return invalid("code_search: dist must be aligned to a float");
-  if (reinterpret_cast<uintptr_t>(workspace) & 3) return invalid("code_search: workspace must be aligned to a float");
-  if (K > 65535) return unsupported("code_search: K beyond 65535 (stored codes are 16-bit)");
-  if (K > CS_MAX_K) return unsupported("code_search: K beyond 16384 (one table row per staged cell must fit 64 KB of LDS)");
-  if (C > CS_MAX_C) return unsupported("code_search: C beyond 256 * 65535 cells");
+namespace {
+// What isi_code_search_f32 and isi_code_search_rows_f32 share: every refusal, the route and the two launches.  by_rows:
+// `source` is rows [Q, C, K] and there is no query; otherwise it is the table [K, K].
+int code_search_any(const char *fn, bool by_rows, const uint16_t *codes, const uint16_t *query, const float *weights,
+                    const float *source, const uint8_t *allowed, float *dist, int64_t N, int64_t C, int K, int Q,
+                    int accumulate, void *workspace, size_t workspace_bytes, hipStream_t st) {
+  if (!codes) return refuse(ISI_E_INVALID, fn, "codes is a null pointer");
+  if (!by_rows && !query) return refuse(ISI_E_INVALID, fn, "query is a null pointer");
+  if (!source) return refuse(ISI_E_INVALID, fn, by_rows ? "rows is a null pointer" : "table is a null pointer");
+  if (!dist) return refuse(ISI_E_INVALID, fn, "dist is a null pointer");
+  if (!workspace) return refuse(ISI_E_INVALID, fn, "workspace is a null pointer");
+  if (N <= 0) return refuse(ISI_E_INVALID, fn, "N must be positive");
+  if (C <= 0) return refuse(ISI_E_INVALID, fn, "C must be positive");
+  if (K <= 0) return refuse(ISI_E_INVALID, fn, "K must be positive");
+  if (Q < 1 || Q > CS_MAX_Q) return refuse(ISI_E_INVALID, fn, "Q must lie in 1..64");
+  if (accumulate != 0 && accumulate != 1) return refuse(ISI_E_INVALID, fn, "accumulate must be 0 or 1");
+  if (reinterpret_cast<uintptr_t>(codes) & 1) return refuse(ISI_E_INVALID, fn, "codes must be aligned to 2 bytes");
+  if (reinterpret_cast<uintptr_t>(query) & 1) return refuse(ISI_E_INVALID, fn, "query must be aligned to 2 bytes");
+  if (reinterpret_cast<uintptr_t>(weights) & 3) return refuse(ISI_E_INVALID, fn, "weights must be aligned to a float");
+  if (reinterpret_cast<uintptr_t>(source) & 3)
+    return refuse(ISI_E_INVALID, fn, by_rows ? "rows must be aligned to a float" : "table must be aligned to a float");
+  if (reinterpret_cast<uintptr_t>(dist) & 3) return refuse(ISI_E_INVALID, fn, "dist must be aligned to a float");
+  if (reinterpret_cast<uintptr_t>(workspace) & 3) return refuse(ISI_E_INVALID, fn, "workspace must be aligned to a float");
+  if (K > 65535) return refuse(ISI_E_UNSUPPORTED, fn, "K beyond 65535 (stored codes are 16-bit)");
+  if (K > CS_MAX_K)
+    return refuse(ISI_E_UNSUPPORTED, fn, by_rows ? "K beyond 16384 (one row per staged cell must fit 64 KB of LDS)"
+                                                 : "K beyond 16384 (one table row per staged cell must fit 64 KB of LDS)");
+  if (C > CS_MAX_C) return refuse(ISI_E_UNSUPPORTED, fn, "C beyond 256 * 65535 cells");
   if ((N + CS_THREADS - 1) / CS_THREADS >= ((int64_t)1 << 31) || (unsigned __int128)N * (unsigned)Q >= ((unsigned __int128)1 << 39))
-    return unsupported("code_search: N beyond 2^31 workgroups of items or Q * N beyond 2^39");
+    return refuse(ISI_E_UNSUPPORTED, fn, "N beyond 2^31 workgroups of items or Q * N beyond 2^39");
   const size_t need = code_search_workspace_bytes(N, C, K, Q);
-  if (need == 0) return unsupported("code_search: the workspace size overflows size_t");
+  if (need == 0) return refuse(ISI_E_UNSUPPORTED, fn, "the workspace size overflows size_t");
   if (workspace_bytes < need) {
     char buf[160];
-    snprintf(buf, sizeof buf, "code_search: workspace_bytes %zu < %zu (isi_code_search_workspace_bytes)", workspace_bytes, need);
-    set_last_error(buf);
-    return ISI_E_WORKSPACE;
+    snprintf(buf, sizeof buf, "workspace_bytes %zu < %zu (isi_code_search_workspace_bytes)", workspace_bytes, need);
+    return refuse(ISI_E_WORKSPACE, fn, buf);
   }
   const int splits = (int)num_splits(C);
   const int cc = code_chunk_cells(K);
   const bool vec_codes = cc >= 8 && (C % 8) == 0 && !(reinterpret_cast<uintptr_t>(codes) & 15);
-  const int vec_table = (K % 4) == 0 && !(reinterpret_cast<uintptr_t>(table) & 15);
+  const int vec_table = (K % 4) == 0 && !(reinterpret_cast<uintptr_t>(source) & 15);
   const size_t lds = (size_t)cc * K * sizeof(float);
   const bool lines = vec_codes && cc == CS_MAX_CHUNK;                  // two chunks = the 128 bytes of a whole line per item
   const int ipt = lines ? 2 : CS_IPT;
@@ -211,19 +312,41 @@ int code_search_f32(const uint16_t *codes, const uint16_t *query, const float *w
   const dim3 grid((unsigned)blocks, (unsigned)splits, (unsigned)Q), block(CS_THREADS);
   float *partial = static_cast<float *>(workspace);
   const int Ci = (int)C;
-#define ISI_CS_LAUNCH(G, IPT, SUB) \
-  hipLaunchKernelGGL((code_search_kernel<G, IPT, SUB>), grid, block, lds, st, codes, query, weights, table, partial, N, Ci, K, cc, vec_table)
+#define ISI_CS_LAUNCH(G, IPT, SUB)                                                                                         \
+  do {                                                                                                                     \
+    if (by_rows)                                                                                                           \
+      hipLaunchKernelGGL((code_search_kernel<G, IPT, SUB, true>), grid, block, lds, st, codes, query, weights, source,     \
+                         partial, N, Ci, K, cc, vec_table);                                                                \
+    else                                                                                                                   \
+      hipLaunchKernelGGL((code_search_kernel<G, IPT, SUB, false>), grid, block, lds, st, codes, query, weights, source,    \
+                         partial, N, Ci, K, cc, vec_table);                                                                \
+  } while (0)
   if (!vec_codes) ISI_CS_LAUNCH(0, CS_IPT, 1);
   else if (lines) ISI_CS_LAUNCH(4, 2, 2);
   else if (cc == 24) ISI_CS_LAUNCH(3, CS_IPT, 1);
   else if (cc == 16) ISI_CS_LAUNCH(2, CS_IPT, 1);
   else ISI_CS_LAUNCH(1, CS_IPT, 1);
 #undef ISI_CS_LAUNCH
-  if (const int rc = check_launch("code_search")) return rc;
+  if (const int rc = check_launch(fn)) return rc;
   const int64_t QN = (int64_t)Q * N;
   hipLaunchKernelGGL(code_search_reduce_kernel, dim3((unsigned)((QN + 255) / 256)), dim3(256), 0, st, partial, allowed, dist,
                      N, QN, splits, accumulate);
-  return check_launch("code_search (reduce)");
+  return check_launch(by_rows ? "code_search_rows (reduce)" : "code_search (reduce)");
+}
+}  // namespace
+
+int code_search_f32(const uint16_t *codes, const uint16_t *query, const float *weights, const float *table,
+                    const uint8_t *allowed, float *dist, int64_t N, int64_t C, int K, int Q, int accumulate, void *workspace,
+                    size_t workspace_bytes, hipStream_t st) {
+  return code_search_any("code_search", false, codes, query, weights, table, allowed, dist, N, C, K, Q, accumulate, workspace,
+                         workspace_bytes, st);
+}
+
+int code_search_rows_f32(const uint16_t *codes, const float *rows, const float *weights, const uint8_t *allowed, float *dist,
+                         int64_t N, int64_t C, int K, int Q, int accumulate, void *workspace, size_t workspace_bytes,
+                         hipStream_t st) {
+  return code_search_any("code_search_rows", true, codes, nullptr, weights, rows, allowed, dist, N, C, K, Q, accumulate,
+                         workspace, workspace_bytes, st);
 }
 
 }  // namespace isi

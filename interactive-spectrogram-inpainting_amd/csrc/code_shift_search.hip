@@ -28,6 +28,9 @@
 // since x + 0-th partial is all the second launch would compute.
 //
 // Limits: K <= 16384, F * W <= 256 * 65535 (runs ride grid.y), Q <= 64 (grid.z), F * T < 2^31, Q * S * N < 2^39.
+//
+// isi_code_shift_search_rows_f32 is the same search with the stage fed from per-cell window rows
+// R [Q][F * W][K] instead of table rows (template argument ROWS): everything after the stage is shared.
 #include "isi_common.h"
 #include "isi_internal.h"
 #include "device_prims.h"
@@ -51,7 +54,9 @@ __device__ __forceinline__ void store_sum(float *__restrict__ out, size_t at, fl
 }  // namespace
 
 // The vector route.  blockIdx.x = item block * passes + pass; a pass covers the offsets s_base .. s_base + 8 NB - 1.
-template <int STEP, int NB>
+// ROWS (both routes): `table` holds per-cell window rows R [Q][F * W][K] (isi_code_shift_search_rows_f32) and `query` is
+// unused; only the stage differs.
+template <int STEP, int NB, bool ROWS>
 __global__ __launch_bounds__(SS_THREADS) void code_shift_search_vec_kernel(
     const uint16_t *__restrict__ codes, const uint16_t *__restrict__ query, const float *__restrict__ weights,
     const float *__restrict__ table, float *__restrict__ out, int64_t N, int F, int T, int W, int shift0, int S, int K, int cc,
@@ -67,7 +72,7 @@ __global__ __launch_bounds__(SS_THREADS) void code_shift_search_vec_kernel(
   const int s_base = pass * (SS_OB * NB);
   const int v_base = (shift0 + s_base * STEP) >> 3;   // (shift0 % 8 == 0 on this route)
   const int v_row = T >> 3;
-  const uint16_t *__restrict__ qj = query + (size_t)j * C;
+  const uint16_t *__restrict__ qj = ROWS ? nullptr : query + (size_t)j * C;   // (no query on the rows route)
   const float *__restrict__ wj = weights ? weights + (size_t)j * C : nullptr;
   const uint16_t *__restrict__ item = codes + (size_t)(valid ? n : 0) * ((size_t)F * T);
   const unsigned kmax = (unsigned)K - 1u;
@@ -77,7 +82,8 @@ __global__ __launch_bounds__(SS_THREADS) void code_shift_search_vec_kernel(
   for (int a = 0; a < SS_OB * NB; ++a) acc[a] = 0.f;
   for (int c0 = c_begin; c0 < c_end; c0 += cc) {
     const int ncell = c_end - c0 < cc ? c_end - c0 : cc;          // a multiple of 8: W % 8 == 0 and cc % 8 == 0
-    stage_code_rows<SS_THREADS>(rows, qj, wj, table, c0, ncell, K, vec_table);
+    if constexpr (ROWS) stage_query_rows<SS_THREADS>(rows, table, wj, j, C, c0, ncell, K, vec_table);
+    else stage_code_rows<SS_THREADS>(rows, qj, wj, table, c0, ncell, K, vec_table);
     __syncthreads();
     for (int g = 0; g < ncell; g += 8) {
       const int c = c0 + g, f = c / W, t0 = c - f * W;           // 8 columns t0 .. t0 + 7 of row f
@@ -123,6 +129,7 @@ __global__ __launch_bounds__(SS_THREADS) void code_shift_search_vec_kernel(
 }
 
 // The scalar route: any W, step, shift0, alignment and K.  A pass is 8 offsets; every look-up fetches its own code.
+template <bool ROWS>
 __global__ __launch_bounds__(SS_THREADS) void code_shift_search_scalar_kernel(
     const uint16_t *__restrict__ codes, const uint16_t *__restrict__ query, const float *__restrict__ weights,
     const float *__restrict__ table, float *__restrict__ out, int64_t N, int F, int T, int W, int shift0, int step, int S, int K,
@@ -135,7 +142,7 @@ __global__ __launch_bounds__(SS_THREADS) void code_shift_search_scalar_kernel(
   const int C = F * W, c_begin = run * SS_RUN;
   const int c_end = C - c_begin < SS_RUN ? C : c_begin + SS_RUN;
   const int s_base = pass * SS_OB;
-  const uint16_t *__restrict__ qj = query + (size_t)j * C;
+  const uint16_t *__restrict__ qj = ROWS ? nullptr : query + (size_t)j * C;   // (no query on the rows route)
   const float *__restrict__ wj = weights ? weights + (size_t)j * C : nullptr;
   const uint16_t *__restrict__ item = codes + (size_t)(valid ? n : 0) * ((size_t)F * T) + shift0 + (size_t)s_base * step;
   const unsigned kmax = (unsigned)K - 1u;
@@ -144,7 +151,8 @@ __global__ __launch_bounds__(SS_THREADS) void code_shift_search_scalar_kernel(
   for (int e = 0; e < SS_OB; ++e) acc[e] = 0.f;
   for (int c0 = c_begin; c0 < c_end; c0 += cc) {
     const int ncell = c_end - c0 < cc ? c_end - c0 : cc;
-    stage_code_rows<SS_THREADS>(rows, qj, wj, table, c0, ncell, K, vec_table);
+    if constexpr (ROWS) stage_query_rows<SS_THREADS>(rows, table, wj, j, C, c0, ncell, K, vec_table);
+    else stage_code_rows<SS_THREADS>(rows, qj, wj, table, c0, ncell, K, vec_table);
     __syncthreads();
     if (valid) {
       for (int cl = 0; cl < ncell; ++cl) {
@@ -217,51 +225,55 @@ size_t code_shift_search_workspace_bytes(int64_t N, int F, int T, int W, int S, 
   return b > (unsigned __int128)SIZE_MAX ? 0 : (size_t)b;
 }
 
-int code_shift_search_f32(const uint16_t *codes, const uint16_t *query, const float *weights, const float *table, float *dist,
-                          int64_t N, int F, int T, int W, int shift0, int step, int S, int K, int Q, int accumulate,
-                          void *workspace, size_t workspace_bytes, hipStream_t st) {
-  if (!codes) return invalid("code_shift_search: codes is a null pointer");
-  if (!query) return invalid("code_shift_search: query is a null pointer");
-  if (!table) return invalid("code_shift_search: table is a null pointer");
-  if (!dist) return invalid("code_shift_search: dist is a null pointer");
-  if (!workspace) return invalid("code_shift_search: workspace is a null pointer");
-  if (N <= 0) return invalid("code_shift_search: N must be positive");
-  if (F <= 0) return invalid("code_shift_search: F must be positive");
-  if (T <= 0) return invalid("code_shift_search: T must be positive");
-  if (W <= 0) return invalid("code_shift_search: W must be positive");
-  if (S <= 0) return invalid("code_shift_search: S must be positive");
-  if (K <= 0) return invalid("code_shift_search: K must be positive");
-  if (step <= 0) return invalid("code_shift_search: step must be positive");
-  if (shift0 < 0) return invalid("code_shift_search: shift0 must not be negative");
-  if (W > T) return invalid("code_shift_search: W must not exceed T");
+namespace {
+// What isi_code_shift_search_f32 and isi_code_shift_search_rows_f32 share: every refusal, the route and the launches.
+// by_rows: `source` is window rows [Q, F * W, K] and there is no query; otherwise it is the table [K, K].
+int code_shift_search_any(const char *fn, bool by_rows, const uint16_t *codes, const uint16_t *query, const float *weights,
+                          const float *source, float *dist, int64_t N, int F, int T, int W, int shift0, int step, int S, int K,
+                          int Q, int accumulate, void *workspace, size_t workspace_bytes, hipStream_t st) {
+  if (!codes) return refuse(ISI_E_INVALID, fn, "codes is a null pointer");
+  if (!by_rows && !query) return refuse(ISI_E_INVALID, fn, "query is a null pointer");
+  if (!source) return refuse(ISI_E_INVALID, fn, by_rows ? "rows is a null pointer" : "table is a null pointer");
+  if (!dist) return refuse(ISI_E_INVALID, fn, "dist is a null pointer");
+  if (!workspace) return refuse(ISI_E_INVALID, fn, "workspace is a null pointer");
+  if (N <= 0) return refuse(ISI_E_INVALID, fn, "N must be positive");
+  if (F <= 0) return refuse(ISI_E_INVALID, fn, "F must be positive");
+  if (T <= 0) return refuse(ISI_E_INVALID, fn, "T must be positive");
+  if (W <= 0) return refuse(ISI_E_INVALID, fn, "W must be positive");
+  if (S <= 0) return refuse(ISI_E_INVALID, fn, "S must be positive");
+  if (K <= 0) return refuse(ISI_E_INVALID, fn, "K must be positive");
+  if (step <= 0) return refuse(ISI_E_INVALID, fn, "step must be positive");
+  if (shift0 < 0) return refuse(ISI_E_INVALID, fn, "shift0 must not be negative");
+  if (W > T) return refuse(ISI_E_INVALID, fn, "W must not exceed T");
   if ((int64_t)shift0 + (int64_t)(S - 1) * step + W > T)
-    return invalid("code_shift_search: shift0 + (S - 1) * step + W must not exceed T (the last offset leaves the stored map)");
-  if (Q < 1 || Q > SS_MAX_Q) return invalid("code_shift_search: Q must lie in 1..64");
-  if (accumulate != 0 && accumulate != 1) return invalid("code_shift_search: accumulate must be 0 or 1");
-  if (reinterpret_cast<uintptr_t>(codes) & 1) return invalid("code_shift_search: codes must be aligned to 2 bytes");
-  if (reinterpret_cast<uintptr_t>(query) & 1) return invalid("code_shift_search: query must be aligned to 2 bytes");
-  if (reinterpret_cast<uintptr_t>(weights) & 3) return invalid("code_shift_search: weights must be aligned to a float");
-  if (reinterpret_cast<uintptr_t>(table) & 3) return invalid("code_shift_search: table must be aligned to a float");
-  if (reinterpret_cast<uintptr_t>(dist) & 3) return invalid("code_shift_search: dist must be aligned to a float");
-  if (reinterpret_cast<uintptr_t>(workspace) & 3) return invalid("code_shift_search: workspace must be aligned to a float");
-  if (K > 65535) return unsupported("code_shift_search: K beyond 65535 (stored codes are 16-bit)");
-  if (K > SS_MAX_K) return unsupported("code_shift_search: K beyond 16384 (one table row per staged cell must fit 64 KB of LDS)");
-  if ((int64_t)F * W > SS_MAX_C) return unsupported("code_shift_search: F * W beyond 256 * 65535 cells");
-  if ((int64_t)F * T >= ((int64_t)1 << 31)) return unsupported("code_shift_search: F * T beyond 2^31 - 1 codes per stored map");
+    return refuse(ISI_E_INVALID, fn, "shift0 + (S - 1) * step + W must not exceed T (the last offset leaves the stored map)");
+  if (Q < 1 || Q > SS_MAX_Q) return refuse(ISI_E_INVALID, fn, "Q must lie in 1..64");
+  if (accumulate != 0 && accumulate != 1) return refuse(ISI_E_INVALID, fn, "accumulate must be 0 or 1");
+  if (reinterpret_cast<uintptr_t>(codes) & 1) return refuse(ISI_E_INVALID, fn, "codes must be aligned to 2 bytes");
+  if (reinterpret_cast<uintptr_t>(query) & 1) return refuse(ISI_E_INVALID, fn, "query must be aligned to 2 bytes");
+  if (reinterpret_cast<uintptr_t>(weights) & 3) return refuse(ISI_E_INVALID, fn, "weights must be aligned to a float");
+  if (reinterpret_cast<uintptr_t>(source) & 3)
+    return refuse(ISI_E_INVALID, fn, by_rows ? "rows must be aligned to a float" : "table must be aligned to a float");
+  if (reinterpret_cast<uintptr_t>(dist) & 3) return refuse(ISI_E_INVALID, fn, "dist must be aligned to a float");
+  if (reinterpret_cast<uintptr_t>(workspace) & 3) return refuse(ISI_E_INVALID, fn, "workspace must be aligned to a float");
+  if (K > 65535) return refuse(ISI_E_UNSUPPORTED, fn, "K beyond 65535 (stored codes are 16-bit)");
+  if (K > SS_MAX_K)
+    return refuse(ISI_E_UNSUPPORTED, fn, by_rows ? "K beyond 16384 (one row per staged cell must fit 64 KB of LDS)"
+                                                 : "K beyond 16384 (one table row per staged cell must fit 64 KB of LDS)");
+  if ((int64_t)F * W > SS_MAX_C) return refuse(ISI_E_UNSUPPORTED, fn, "F * W beyond 256 * 65535 cells");
+  if ((int64_t)F * T >= ((int64_t)1 << 31)) return refuse(ISI_E_UNSUPPORTED, fn, "F * T beyond 2^31 - 1 codes per stored map");
   if ((unsigned __int128)N * (unsigned)Q * (unsigned)S >= ((unsigned __int128)1 << 39))
-    return unsupported("code_shift_search: Q * S * N beyond 2^39");
+    return refuse(ISI_E_UNSUPPORTED, fn, "Q * S * N beyond 2^39");
   const size_t need = code_shift_search_workspace_bytes(N, F, T, W, S, K, Q);
-  if (need == 0) return unsupported("code_shift_search: the workspace size overflows size_t");
+  if (need == 0) return refuse(ISI_E_UNSUPPORTED, fn, "the workspace size overflows size_t");
   if (workspace_bytes < need) {
     char buf[176];
-    snprintf(buf, sizeof buf, "code_shift_search: workspace_bytes %zu < %zu (isi_code_shift_search_workspace_bytes)",
-             workspace_bytes, need);
-    set_last_error(buf);
-    return ISI_E_WORKSPACE;
+    snprintf(buf, sizeof buf, "workspace_bytes %zu < %zu (isi_code_shift_search_workspace_bytes)", workspace_bytes, need);
+    return refuse(ISI_E_WORKSPACE, fn, buf);
   }
   const int runs = (int)shift_runs((int64_t)F * W);
   const int cc = code_chunk_cells(K);
-  const int vec_table = (K % 4) == 0 && !(reinterpret_cast<uintptr_t>(table) & 15);
+  const int vec_table = (K % 4) == 0 && !(reinterpret_cast<uintptr_t>(source) & 15);
   const bool vec = (step == 1 || step == 2) && cc >= 8 && (W % 8) == 0 && (T % 8) == 0 && (shift0 % 8) == 0 &&
                    !(reinterpret_cast<uintptr_t>(codes) & 15);
   const int nblk = (S + SS_OB - 1) / SS_OB;
@@ -273,19 +285,30 @@ int code_shift_search_f32(const uint16_t *codes, const uint16_t *query, const fl
     passes = (nblk + nb - 1) / nb;
   }
   const int64_t gx = (N + SS_THREADS - 1) / SS_THREADS * passes;
-  if (gx >= ((int64_t)1 << 31)) return unsupported("code_shift_search: N beyond 2^31 - 1 workgroups of items and offsets along x");
+  if (gx >= ((int64_t)1 << 31)) return refuse(ISI_E_UNSUPPORTED, fn, "N beyond 2^31 - 1 workgroups of items and offsets along x");
   const size_t lds = (size_t)cc * K * sizeof(float);
   const dim3 grid((unsigned)gx, (unsigned)runs, (unsigned)Q), block(SS_THREADS);
   const bool direct = runs == 1;
   float *out = direct ? dist : static_cast<float *>(workspace);
   const int acc_now = direct ? accumulate : 0;
+#define ISI_SS_ARGS codes, query, weights, source, out, N, F, T, W, shift0
 #define ISI_SS_LAUNCH(STEP, NB)                                                                                              \
-  hipLaunchKernelGGL((code_shift_search_vec_kernel<STEP, NB>), grid, block, lds, st, codes, query, weights, table, out, N, F, \
-                     T, W, shift0, S, K, cc, vec_table, passes, acc_now)
-  if (!vec)
-    hipLaunchKernelGGL(code_shift_search_scalar_kernel, grid, block, lds, st, codes, query, weights, table, out, N, F, T, W,
-                       shift0, step, S, K, cc, vec_table, passes, acc_now);
-  else if (step == 1) {
+  do {                                                                                                                       \
+    if (by_rows)                                                                                                             \
+      hipLaunchKernelGGL((code_shift_search_vec_kernel<STEP, NB, true>), grid, block, lds, st, ISI_SS_ARGS, S, K, cc,        \
+                         vec_table, passes, acc_now);                                                                        \
+    else                                                                                                                     \
+      hipLaunchKernelGGL((code_shift_search_vec_kernel<STEP, NB, false>), grid, block, lds, st, ISI_SS_ARGS, S, K, cc,       \
+                         vec_table, passes, acc_now);                                                                        \
+  } while (0)
+  if (!vec) {
+    if (by_rows)
+      hipLaunchKernelGGL(code_shift_search_scalar_kernel<true>, grid, block, lds, st, ISI_SS_ARGS, step, S, K, cc, vec_table,
+                         passes, acc_now);
+    else
+      hipLaunchKernelGGL(code_shift_search_scalar_kernel<false>, grid, block, lds, st, ISI_SS_ARGS, step, S, K, cc, vec_table,
+                         passes, acc_now);
+  } else if (step == 1) {
     if (nb == 1) ISI_SS_LAUNCH(1, 1);
     else if (nb == 2) ISI_SS_LAUNCH(1, 2);
     else if (nb == 4) ISI_SS_LAUNCH(1, 4);
@@ -296,13 +319,29 @@ int code_shift_search_f32(const uint16_t *codes, const uint16_t *query, const fl
     else if (nb == 4) ISI_SS_LAUNCH(2, 4);
     else ISI_SS_LAUNCH(2, 7);
   }
+#undef ISI_SS_ARGS
 #undef ISI_SS_LAUNCH
-  if (const int rc = check_launch("code_shift_search")) return rc;
+  if (const int rc = check_launch(fn)) return rc;
   if (direct) return ISI_OK;
   const int64_t QSN = (int64_t)Q * S * N;
   hipLaunchKernelGGL(code_shift_reduce_kernel, dim3((unsigned)((QSN + 255) / 256)), dim3(256), 0, st,
                      static_cast<const float *>(workspace), dist, QSN, runs, accumulate);
-  return check_launch("code_shift_search (reduce)");
+  return check_launch(by_rows ? "code_shift_search_rows (reduce)" : "code_shift_search (reduce)");
+}
+}  // namespace
+
+int code_shift_search_f32(const uint16_t *codes, const uint16_t *query, const float *weights, const float *table, float *dist,
+                          int64_t N, int F, int T, int W, int shift0, int step, int S, int K, int Q, int accumulate,
+                          void *workspace, size_t workspace_bytes, hipStream_t st) {
+  return code_shift_search_any("code_shift_search", false, codes, query, weights, table, dist, N, F, T, W, shift0, step, S, K,
+                               Q, accumulate, workspace, workspace_bytes, st);
+}
+
+int code_shift_search_rows_f32(const uint16_t *codes, const float *rows, const float *weights, float *dist, int64_t N, int F,
+                               int T, int W, int shift0, int step, int S, int K, int Q, int accumulate, void *workspace,
+                               size_t workspace_bytes, hipStream_t st) {
+  return code_shift_search_any("code_shift_search_rows", true, codes, nullptr, weights, rows, dist, N, F, T, W, shift0, step,
+                               S, K, Q, accumulate, workspace, workspace_bytes, st);
 }
 
 int code_shift_best_f32(const float *dist, const uint8_t *allowed, float *best, int32_t *best_shift, int64_t N, int S, int Q,

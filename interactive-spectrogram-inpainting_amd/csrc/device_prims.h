@@ -1,6 +1,6 @@
 // Device primitives the MFMA kernels rest on, each defined ONCE: buffer loads, buffer descriptors, the LDS-DMA, the
-// 32x32 accumulator layout and the swizzle of the bf16 LDS planes -- and the table-row stage the two code-database
-// searches share.  All of them are __forceinline__: a kernel's machine code does not depend on where they are written
+// 32x32 accumulator layout and the swizzle of the bf16 LDS planes -- and the two row stages (table-fed, rows-fed) the
+// code-database searches share.  All of them are __forceinline__: a kernel's machine code does not depend on where they are written
 // down.  Helpers with a single user stay in that user's file.
 #pragma once
 #ifndef __HIPCC__
@@ -59,6 +59,35 @@ __device__ __forceinline__ void stage_code_rows(float *rows, const uint16_t *__r
     const float *__restrict__ src = table + (size_t)(live ? r : 0u) * K;
     float *dst = rows + cl * K;
     if (vec_table) {
+      for (int k4 = lane; k4 < (K >> 2); k4 += 64) {
+        float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (live) {
+          t = reinterpret_cast<const float4 *>(src)[k4];
+          t.x *= wv; t.y *= wv; t.z *= wv; t.w *= wv;
+        }
+        reinterpret_cast<float4 *>(dst)[k4] = t;
+      }
+    } else {
+      for (int k = lane; k < K; k += 64) dst[k] = live ? src[k] * wv : 0.f;
+    }
+  }
+}
+
+// The same stage fed with per-cell rows instead of table rows (the searches by encoder vectors): query j's rows R[j][c][:]
+// lie at R + (j * cells + c) * K (a size_t offset: Q * cells * K floats pass 2^31), rows[cl][k] = w[c0 + cl] * R[j][c0 + cl][k],
+// one rounding.  A cell whose weight is exactly 0 -- the vector query's mask -- is written as zeros whatever its row holds
+// (0 * NaN would not be 0); nothing of its row is read.  wj may be null (weight 1); vec_rows: K % 4 == 0 and a
+// 16-byte-aligned R, so every row is.
+template <int THREADS>
+__device__ __forceinline__ void stage_query_rows(float *rows, const float *__restrict__ R, const float *__restrict__ wj, int j,
+                                                 int cells, int c0, int ncell, int K, int vec_rows) {
+  const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+  for (int cl = wave; cl < ncell; cl += THREADS / 64) {
+    const float wv = wj ? wj[c0 + cl] : 1.f;
+    const bool live = wv != 0.f;
+    const float *__restrict__ src = R + ((size_t)j * (size_t)cells + (size_t)(c0 + cl)) * (size_t)K;
+    float *dst = rows + cl * K;
+    if (vec_rows) {
       for (int k4 = lane; k4 < (K >> 2); k4 += 64) {
         float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
         if (live) {

@@ -337,6 +337,16 @@ int isi_code_search_f32(const uint16_t *codes, const uint16_t *query, const floa
   return code_search_f32(codes, query, weights, table, allowed, dist, N, C, K, Q, accumulate, workspace, workspace_bytes,
                          S(stream));
 }
+int isi_code_query_rows_f32(const float *z, int64_t z_stride, const float *codebook, float *rows, int64_t cells, int K, int D,
+                            void *stream) {
+  return code_query_rows_f32(z, z_stride, codebook, rows, cells, K, D, S(stream));
+}
+int isi_code_search_rows_f32(const uint16_t *codes, const float *rows, const float *weights, const uint8_t *allowed,
+                             float *dist, int64_t N, int64_t C, int K, int Q, int accumulate, void *workspace,
+                             size_t workspace_bytes, void *stream) {
+  return code_search_rows_f32(codes, rows, weights, allowed, dist, N, C, K, Q, accumulate, workspace, workspace_bytes,
+                              S(stream));
+}
 size_t isi_code_shift_search_workspace_bytes(int64_t N, int F, int T, int W, int S_, int K, int Q) {
   return code_shift_search_workspace_bytes(N, F, T, W, S_, K, Q);
 }
@@ -345,6 +355,12 @@ int isi_code_shift_search_f32(const uint16_t *codes, const uint16_t *query, cons
                               int accumulate, void *workspace, size_t workspace_bytes, void *stream) {
   return code_shift_search_f32(codes, query, weights, table, dist, N, F, T, W, shift0, step, S_, K, Q, accumulate, workspace,
                                workspace_bytes, S(stream));
+}
+int isi_code_shift_search_rows_f32(const uint16_t *codes, const float *rows, const float *weights, float *dist, int64_t N,
+                                   int F, int T, int W, int shift0, int step, int S_, int K, int Q, int accumulate,
+                                   void *workspace, size_t workspace_bytes, void *stream) {
+  return code_shift_search_rows_f32(codes, rows, weights, dist, N, F, T, W, shift0, step, S_, K, Q, accumulate, workspace,
+                                    workspace_bytes, S(stream));
 }
 int isi_code_shift_best_f32(const float *dist, const uint8_t *allowed, float *best, int32_t *best_shift, int64_t N, int S_,
                             int Q, void *stream) {

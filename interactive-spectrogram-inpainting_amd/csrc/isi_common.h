@@ -33,6 +33,14 @@ inline int unsupported(const char *msg) {
   return ISI_E_UNSUPPORTED;
 }
 
+// `code` with the message "<fn>: <what>": for refusals that several entry points share
+inline int refuse(int code, const char *fn, const char *what) {
+  char buf[256];
+  snprintf(buf, sizeof buf, "%s: %s", fn, what);
+  set_last_error(buf);
+  return code;
+}
+
 inline size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; }
 
 // hipFuncSetAttribute and the CU count are PER DEVICE: a process that drives a second GPU (tests on cuda:1, one

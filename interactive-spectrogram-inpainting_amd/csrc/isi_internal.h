@@ -372,7 +372,12 @@ size_t code_search_workspace_bytes(int64_t N, int64_t C, int K, int Q);
 int code_search_f32(const uint16_t *codes, const uint16_t *query, const float *weights, const float *table,
                     const uint8_t *allowed, float *dist, int64_t N, int64_t C, int K, int Q, int accumulate, void *workspace,
                     size_t workspace_bytes, hipStream_t st);
-// the stage both searches share (device_prims.h: stage_code_rows): 64 KB of LDS hold `cc` table rows of K floats, at most 32,
+int code_query_rows_f32(const float *z, int64_t z_stride, const float *codebook, float *rows, int64_t cells, int K, int D,
+                        hipStream_t st);
+int code_search_rows_f32(const uint16_t *codes, const float *rows, const float *weights, const uint8_t *allowed, float *dist,
+                         int64_t N, int64_t C, int K, int Q, int accumulate, void *workspace, size_t workspace_bytes,
+                         hipStream_t st);
+// the stage both searches share (device_prims.h: stage_code_rows, stage_query_rows): 64 KB of LDS hold `cc` table rows of K floats, at most 32,
 // a multiple of 8 from 8 cells on (code vectors hold 8 cells)
 constexpr int kCodeStageFloats = 16384;
 inline int code_chunk_cells(int K) {
@@ -386,6 +391,9 @@ size_t code_shift_search_workspace_bytes(int64_t N, int F, int T, int W, int S, 
 int code_shift_search_f32(const uint16_t *codes, const uint16_t *query, const float *weights, const float *table, float *dist,
                           int64_t N, int F, int T, int W, int shift0, int step, int S, int K, int Q, int accumulate,
                           void *workspace, size_t workspace_bytes, hipStream_t st);
+int code_shift_search_rows_f32(const uint16_t *codes, const float *rows, const float *weights, float *dist, int64_t N, int F,
+                               int T, int W, int shift0, int step, int S, int K, int Q, int accumulate, void *workspace,
+                               size_t workspace_bytes, hipStream_t st);
 int code_shift_best_f32(const float *dist, const uint8_t *allowed, float *best, int32_t *best_shift, int64_t N, int S, int Q,
                         hipStream_t st);
 

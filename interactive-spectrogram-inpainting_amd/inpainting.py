@@ -15,6 +15,9 @@ routes (flask_server.py), free of HTTP so that they can be called, tested and ti
                       cut / padded to the requested duration (:314-372, 446-514); optionally the one nearest to a sound
   similar_sounds      the stored sounds most like a given one, optionally outside a masked region (not in the
                       reference: utils/datasets/code_index.py, csrc/code_search.hip)
+  similar_sounds_to_spectrogram / similar_fragments_to_spectrogram / similar_to_mixture   the same questions for a sound
+                      that is no codemap -- an upload's encoder vectors, a morph's blends -- compared with the stored
+                      codes' vectors without snapping it to codes first (CodeIndex.search_soft)
   morph / morph_sweep / crossfade   decode per-cell weighted mixtures of several sounds' codes: timbre interpolation,
                       a sweep between two sounds in one batch, a splice whose seam is a ramp in the latent (not in the
                       reference: csrc/code_mix.hip, VQVAE.decode_code_mix)
@@ -594,24 +597,27 @@ def resize_codemaps_repeat_last(top_code: torch.Tensor, bottom_code: torch.Tenso
     return resize(top_code, duration_top), resize(bottom_code, ratio * duration_top)
 
 
-def similar_sounds(index, top_code: torch.Tensor, bottom_code: Optional[torch.Tensor], mask: Optional[torch.Tensor] = None,
-                   layer: str = 'top', start_index_top: int = 0, k: int = 8,
-                   attribute_constraints: Optional[Mapping[str, object]] = None):
-    """The k items of a `utils.datasets.code_index.CodeIndex` nearest to a sound, as a list of
-    ((top [1,F_t,T_t], bottom [1,F_b,T_b]), attributes, distance), nearest first (equal distances by item index).
-    top_code [1,F_t,T], bottom_code [1,F_b,T_b] or None (the top layer alone is compared): the query is the window of the
-    stored duration starting at `start_index_top`, cut as `timerange_change` cuts its model window; a map shorter than the
-    stored duration is continued with its last column (`resize_codemaps_repeat_last`) and the added columns weigh nothing.
-    mask bool [1,F,W] in the resolution of `layer` over the window: True = do not compare here ("the sounds that agree
-    with everything outside my hole"); a top-layer mask extends to the bottom layer as `timerange_change` extends it.
-    attribute_constraints: `sample_from_database`'s.  The comparison runs on the device (csrc/code_search.hip)."""
+def _found_items(index, indices, distances, shifts=None):
+    """The searches' answers as the lists `similar_sounds` / `similar_fragments` return: ((top, bottom), attributes,
+    distance[, shift_top]) per item."""
+    out = []
+    for n, (i, d) in enumerate(zip(indices.tolist(), distances.tolist())):
+        top, bottom, _ = index[i]
+        found = ((top.unsqueeze(0), None if bottom is None else bottom.unsqueeze(0)), index.decoded_attributes(i), d)
+        out.append(found if shifts is None else found + (int(shifts[n]),))
+    return out
+
+
+def _similar_window(index, top_code, bottom_code, mask, layer: str, start_index_top: int):
+    """What `similar_sounds` compares, for maps whose last two dimensions are [F, T] (codes [1, F, T]; vectors laid out
+    [1, D, F, T]): (top_frame, bottom_frame, mask_top, mask_bottom, two) -- the window of the stored duration from
+    `start_index_top` on, a shorter map continued with its last column under a mask, the caller's mask merged in."""
     if layer not in ('top', 'bottom'):
         raise ValueError(f"unknown layer {layer}")
     two = bottom_code is not None and index.bottom_shape is not None
     shape_top = index.top_shape
     shape_bottom = index.bottom_shape if two else (shape_top[0], shape_top[1])
-    top_code = top_code.reshape(1, *top_code.shape[-2:])
-    bottom_ref = bottom_code.reshape(1, *bottom_code.shape[-2:]) if two else top_code
+    bottom_ref = bottom_code if two else top_code
     window = _windows(top_code, bottom_ref, SimpleNamespace(shape=shape_top), SimpleNamespace(shape=shape_bottom),
                       start_index_top)
     (s_top, e_top), (s_bot, e_bot), ratio_t = window
@@ -643,30 +649,37 @@ def similar_sounds(index, top_code: torch.Tensor, bottom_code: Optional[torch.Te
             mask_bottom[..., :mask.shape[-1]] |= mask[..., :shape_bottom[1]]
         else:
             raise ValueError("a bottom-layer mask needs bottom_code and an index that holds bottom maps")
+    return top_frame, bottom_frame, mask_top, mask_bottom, two
+
+
+def similar_sounds(index, top_code: torch.Tensor, bottom_code: Optional[torch.Tensor], mask: Optional[torch.Tensor] = None,
+                   layer: str = 'top', start_index_top: int = 0, k: int = 8,
+                   attribute_constraints: Optional[Mapping[str, object]] = None):
+    """The k items of a `utils.datasets.code_index.CodeIndex` nearest to a sound, as a list of
+    ((top [1,F_t,T_t], bottom [1,F_b,T_b]), attributes, distance), nearest first (equal distances by item index).
+    top_code [1,F_t,T], bottom_code [1,F_b,T_b] or None (the top layer alone is compared): the query is the window of the
+    stored duration starting at `start_index_top`, cut as `timerange_change` cuts its model window; a map shorter than the
+    stored duration is continued with its last column (`resize_codemaps_repeat_last`) and the added columns weigh nothing.
+    mask bool [1,F,W] in the resolution of `layer` over the window: True = do not compare here ("the sounds that agree
+    with everything outside my hole"); a top-layer mask extends to the bottom layer as `timerange_change` extends it.
+    attribute_constraints: `sample_from_database`'s.  The comparison runs on the device (csrc/code_search.hip)."""
+    top_code = top_code.reshape(1, *top_code.shape[-2:])
+    if bottom_code is not None:
+        bottom_code = bottom_code.reshape(1, *bottom_code.shape[-2:])
+    top_frame, bottom_frame, mask_top, mask_bottom, two = _similar_window(index, top_code, bottom_code, mask, layer,
+                                                                          start_index_top)
+    device = index.device
     indices, distances = index.search(top_frame.to(device), bottom_frame.to(device) if two else None, mask_top=mask_top,
                                       mask_bottom=mask_bottom, k=k, attribute_constraints=attribute_constraints)
-    out = []
-    for i, d in zip(indices.tolist(), distances.tolist()):
-        top, bottom, _ = index[i]
-        out.append(((top.unsqueeze(0), None if bottom is None else bottom.unsqueeze(0)), index.decoded_attributes(i), d))
-    return out
+    return _found_items(index, indices, distances)
 
 
-def similar_fragments(index, top_code: torch.Tensor, bottom_code: Optional[torch.Tensor], start_index_top: int, width_top: int,
-                      mask: Optional[torch.Tensor] = None, layer: str = 'top', k: int = 8,
-                      shift_range: Optional[Tuple[int, int]] = None,
-                      attribute_constraints: Optional[Mapping[str, object]] = None):
-    """The k items of a `CodeIndex` that contain something nearest to a FRAGMENT of a sound, wherever it sits in time, as a
-    list of ((top [1,F_t,T_t], bottom [1,F_b,T_b]), attributes, distance, shift_top), nearest first (equal distances by
-    item index).  The query is the `width_top` top columns of the sound starting at `start_index_top` (and the matching
-    bottom columns, cut with the ratio `similar_sounds` uses); shift_top is the item's column under the window's first one.
-    mask bool [1,F,W] in the resolution of `layer` over that window: True = do not compare here; a top-layer mask extends to
-    the bottom layer as `timerange_change` extends it.  shift_range=(lo, hi): only offsets lo <= o < hi of the stored
-    maps.  The comparison runs on the device (`CodeIndex.search_shifted`, csrc/code_shift_search.hip)."""
+def _fragment_window(index, top_code, bottom_code, start_index_top, width_top, mask, layer: str):
+    """What `similar_fragments` compares, for maps whose last two dimensions are [F, T]:
+    (query_top, query_bottom or None, mask_top, mask_bottom, two)."""
     if layer not in ('top', 'bottom'):
         raise ValueError(f"unknown layer {layer}")
     two = bottom_code is not None and index.bottom_shape is not None
-    top_code = top_code.reshape(1, *top_code.shape[-2:])
     start, width = int(start_index_top), int(width_top)
     if start < 0 or width < 1 or start + width > top_code.shape[-1]:
         raise ValueError(f"the window [{start}, {start + width}) lies outside the top map's {top_code.shape[-1]} columns")
@@ -674,7 +687,7 @@ def similar_fragments(index, top_code: torch.Tensor, bottom_code: Optional[torch
     ratio_t = index.bottom_shape[1] // index.top_shape[1] if two else 1
     ratio_f = index.bottom_shape[0] // index.top_shape[0] if two else 1
     query_top = top_code[..., start:start + width]
-    query_bottom = bottom_code.reshape(1, *bottom_code.shape[-2:])[..., ratio_t * start:ratio_t * (start + width)] if two else None
+    query_bottom = bottom_code[..., ratio_t * start:ratio_t * (start + width)] if two else None
     mask_top = mask_bottom = None
     if mask is not None:
         mask = mask.to(device).reshape(1, *mask.shape[-2:])
@@ -690,14 +703,99 @@ def similar_fragments(index, top_code: torch.Tensor, bottom_code: Optional[torch
                 mask_bottom = mask.repeat_interleave(ratio_f, -2).repeat_interleave(ratio_t, -1)
         else:
             mask_bottom = mask
+    return query_top, query_bottom, mask_top, mask_bottom, two
+
+
+def similar_fragments(index, top_code: torch.Tensor, bottom_code: Optional[torch.Tensor], start_index_top: int, width_top: int,
+                      mask: Optional[torch.Tensor] = None, layer: str = 'top', k: int = 8,
+                      shift_range: Optional[Tuple[int, int]] = None,
+                      attribute_constraints: Optional[Mapping[str, object]] = None):
+    """The k items of a `CodeIndex` that contain something nearest to a FRAGMENT of a sound, wherever it sits in time, as a
+    list of ((top [1,F_t,T_t], bottom [1,F_b,T_b]), attributes, distance, shift_top), nearest first (equal distances by
+    item index).  The query is the `width_top` top columns of the sound starting at `start_index_top` (and the matching
+    bottom columns, cut with the ratio `similar_sounds` uses); shift_top is the item's column under the window's first one.
+    mask bool [1,F,W] in the resolution of `layer` over that window: True = do not compare here; a top-layer mask extends to
+    the bottom layer as `timerange_change` extends it.  shift_range=(lo, hi): only offsets lo <= o < hi of the stored
+    maps.  The comparison runs on the device (`CodeIndex.search_shifted`, csrc/code_shift_search.hip)."""
+    top_code = top_code.reshape(1, *top_code.shape[-2:])
+    if bottom_code is not None:
+        bottom_code = bottom_code.reshape(1, *bottom_code.shape[-2:])
+    query_top, query_bottom, mask_top, mask_bottom, two = _fragment_window(index, top_code, bottom_code, start_index_top,
+                                                                           width_top, mask, layer)
+    device = index.device
     indices, shifts, distances = index.search_shifted(query_top.to(device), query_bottom.to(device) if two else None,
                                                       mask_top=mask_top, mask_bottom=mask_bottom, k=k, shift_range=shift_range,
                                                       attribute_constraints=attribute_constraints)
-    out = []
-    for i, o, d in zip(indices.tolist(), shifts.tolist(), distances.tolist()):
-        top, bottom, _ = index[i]
-        out.append(((top.unsqueeze(0), None if bottom is None else bottom.unsqueeze(0)), index.decoded_attributes(i), d, o))
-    return out
+    return _found_items(index, indices, distances, shifts.tolist())
+
+
+def _similar_to_vectors(index, z_top: torch.Tensor, z_bottom: Optional[torch.Tensor], mask, layer: str, start_index_top: int,
+                        k: int, attribute_constraints):
+    """`similar_sounds` for per-cell vectors z_top [1, F_t, T, D], z_bottom [1, F_b, T_b, D] or None: the same window, the
+    same masks, `CodeIndex.search_soft` in place of `search`."""
+    as_maps = lambda z: z.reshape(1, *z.shape[-3:]).permute(0, 3, 1, 2)                 # noqa: E731  [1, D, F, T]
+    top_frame, bottom_frame, mask_top, mask_bottom, two = _similar_window(
+        index, as_maps(z_top), None if z_bottom is None else as_maps(z_bottom), mask, layer, start_index_top)
+    as_vectors = lambda m: m.permute(0, 2, 3, 1).to(index.device)                      # noqa: E731
+    indices, distances = index.search_soft(top_vectors=as_vectors(top_frame),
+                                           bottom_vectors=as_vectors(bottom_frame) if two else None, mask_top=mask_top,
+                                           mask_bottom=mask_bottom, k=k, attribute_constraints=attribute_constraints)
+    return _found_items(index, indices, distances)
+
+
+@torch.no_grad()
+def similar_sounds_to_spectrogram(index, vqvae, spectrogram: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                                  layer: str = 'top', k: int = 8, start_index_top: int = 0, two_layers: bool = True,
+                                  attribute_constraints: Optional[Mapping[str, object]] = None):
+    """`similar_sounds` for a sound that is not in the database -- an upload: spectrogram [1, C, H, W] on the GPU is
+    encoded to the vectors the codebook search sees (`VQVAE.encode_vectors`) and those, NOT the codes they would snap to,
+    are compared with the stored codes' vectors: dist = sum_c w[c] |z[c] - E[x[c]]|^2 (`CodeIndex.search_soft`, DESIGN.md
+    section 6c.2), so the upload's quantisation error is not counted as signal.  mask, layer, start_index_top, k,
+    attribute_constraints and the returned list are `similar_sounds`'s; two_layers=False compares the top layer alone."""
+    z_top, z_bottom, _, _ = vqvae.encode_vectors(spectrogram)
+    if z_top.shape[0] != 1:
+        raise ValueError(f"one sound per call: the spectrogram holds {z_top.shape[0]}")
+    return _similar_to_vectors(index, z_top, z_bottom if two_layers else None, mask, layer, start_index_top, k,
+                               attribute_constraints)
+
+
+@torch.no_grad()
+def similar_to_mixture(index, vqvae, codes_t: torch.Tensor, weights_t: torch.Tensor, codes_b: Optional[torch.Tensor] = None,
+                       weights_b: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, layer: str = 'top',
+                       k: int = 8, start_index_top: int = 0, attribute_constraints: Optional[Mapping[str, object]] = None):
+    """The stored sounds nearest to a MORPH, without snapping it to codes: codes_* int64 and weights_* fp32 [M, 1, F, T] as
+    `decode_code_mix` takes them (`morph`, `crossfade`, `VQVAE.encode_topm` with `soft_weights`); each cell's vector is
+    the mixture sum_m weights[m] E[codes[m]] (`QuantizedBottleneck.embed_mix`) and is compared with the stored codes'
+    vectors (`CodeIndex.search_soft`).  codes_b None: the top layer alone.  One-hot weights give `similar_sounds` on the
+    codes they select, bit for bit.  mask, layer, start_index_top, k, attribute_constraints and the returned list are
+    `similar_sounds`'s."""
+    z_top = vqvae.quantize_t.embed_mix(codes_t, weights_t)
+    z_bottom = None if codes_b is None else vqvae.quantize_b.embed_mix(codes_b, weights_b)
+    if z_top.shape[0] != 1:
+        raise ValueError(f"one sound per call: the mixture holds {z_top.shape[0]}")
+    return _similar_to_vectors(index, z_top, z_bottom, mask, layer, start_index_top, k, attribute_constraints)
+
+
+@torch.no_grad()
+def similar_fragments_to_spectrogram(index, vqvae, spectrogram: torch.Tensor, start_index_top: int, width_top: int,
+                                     mask: Optional[torch.Tensor] = None, layer: str = 'top', k: int = 8,
+                                     shift_range: Optional[Tuple[int, int]] = None, two_layers: bool = True,
+                                     attribute_constraints: Optional[Mapping[str, object]] = None):
+    """`similar_fragments` for an upload: the window of `width_top` top columns from `start_index_top` on is cut from the
+    encoder's vectors (`VQVAE.encode_vectors`) and laid over every stored sound at every offset that fits
+    (`CodeIndex.search_shifted_soft`).  The other arguments and the returned list -- ((top, bottom), attributes, distance,
+    shift_top) -- are `similar_fragments`'s."""
+    z_top, z_bottom, _, _ = vqvae.encode_vectors(spectrogram)
+    if z_top.shape[0] != 1:
+        raise ValueError(f"one sound per call: the spectrogram holds {z_top.shape[0]}")
+    as_maps = lambda z: z.permute(0, 3, 1, 2)                                          # noqa: E731  [1, D, F, T]
+    query_top, query_bottom, mask_top, mask_bottom, two = _fragment_window(
+        index, as_maps(z_top), as_maps(z_bottom) if two_layers else None, start_index_top, width_top, mask, layer)
+    as_vectors = lambda m: m.permute(0, 2, 3, 1).to(index.device)                      # noqa: E731
+    indices, shifts, distances = index.search_shifted_soft(
+        top_vectors=as_vectors(query_top), bottom_vectors=as_vectors(query_bottom) if two else None, mask_top=mask_top,
+        mask_bottom=mask_bottom, k=k, shift_range=shift_range, attribute_constraints=attribute_constraints)
+    return _found_items(index, indices, distances, shifts.tolist())
 
 
 def _paste_columns(sound: torch.Tensor, item: torch.Tensor, mask: torch.Tensor, start: int, shift: int) -> torch.Tensor:

@@ -269,8 +269,11 @@ SIGNATURES = {
     "isi_code_distance_table_f32": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "isi_code_search_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int]),
     "isi_code_search_f32": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P]),
+    "isi_code_query_rows_f32": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, C.c_int, C.c_int, _P]),
+    "isi_code_search_rows_f32": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P]),
     "isi_code_shift_search_workspace_bytes": (C.c_size_t, [C.c_int64] + [C.c_int] * 6),
     "isi_code_shift_search_f32": (C.c_int, [_P] * 5 + [C.c_int64] + [C.c_int] * 9 + [_P, C.c_size_t, _P]),
+    "isi_code_shift_search_rows_f32": (C.c_int, [_P] * 4 + [C.c_int64] + [C.c_int] * 9 + [_P, C.c_size_t, _P]),
     "isi_code_shift_best_f32": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, _P]),
     "isi_rel_attention_f32": (C.c_int, [C.POINTER(isi_attn_args), _P]),
     "isi_rel_attention_workspace_bytes": (C.c_size_t, [C.POINTER(isi_attn_args)]),

@@ -12,8 +12,19 @@ and a two-layer distance is alpha dist_top + beta dist_bottom.  The bits of an i
 weights, the item and the table only, so equal sounds stay tied and a ranking never flickers: results are ordered by
 (distance ascending, item index ascending).  `search_shifted` answers the fragment question -- "which stored sound contains
 something like this window, wherever it sits in time" -- with the same metric at every offset that fits
-(csrc/code_shift_search.hip, specification tests/code_shift_search_spec.py).  No CPU path: the index, the VQ-VAE and the
-queries must live on the GPU."""
+(csrc/code_shift_search.hip, specification tests/code_shift_search_spec.py).
+
+That metric compares CODES with codes -- the product quantiser's symmetric distance, right for a query that is a codemap.
+A query that is not -- an upload's encoder output before it is snapped to codes, a morph's per-cell blend of codes -- is
+compared by the asymmetric distance instead (`search_soft`, `search_shifted_soft`; DESIGN.md section 6c.2, specification
+tests/code_soft_search_spec.py): per cell a ROW of K floats takes the place of the table row,
+
+    R[c][k]    = sum_d (z[c][d] - E[k][d])^2             built on the device from the vectors z (isi_code_query_rows_f32)
+    dist(z, x) = sum_c w[c] R[c][x[c]]                   = sum_c w[c] |z[c] - E[x[c]]|^2; a cell of weight 0 counts nothing
+
+through the same kernels with another stage, so a vector that is a codebook row gives the hard search's bits; any other
+per-cell cost can be handed over as ready rows.  No CPU path: the index, the VQ-VAE and the queries must live on the
+GPU."""
 from __future__ import annotations
 
 import ctypes as C
@@ -27,6 +38,8 @@ from ... import _hip
 
 MAX_QUERIES = 64          # isi_code_search_f32: 1 <= Q <= 64 per launch
 SHIFT_BUDGET_BYTES = 1 << 30      # search_shifted / distances_shifted: workspace + dist [Q, S, N] of one group of queries
+ROWS_BUDGET_BYTES = 1 << 28       # search_soft / search_shifted_soft: rows [Q, C, K] built from vectors, one group of queries
+                                  # (a flagship bottom map is 8 MB of rows per query: 32 queries at a time)
 
 
 def _as_codes(codes, name: str, n_embed: int) -> torch.Tensor:
@@ -271,22 +284,9 @@ class CodeIndex:
                                                      ('bottom', bottom_code, mask_bottom, layer_weights[1])) if code is not None]
         if len({c[2].shape[0] for c in checked}) != 1:
             raise ValueError("top_code and bottom_code hold different numbers of queries")
-        jobs = [(layer,) + self._query(layer, code, mask, weight) + (single,) for layer, weight, code, mask, single in checked]
-        Q, N = jobs[0][1].shape[0], len(self)
-        lib, stream = _hip.lib(), C.c_void_p(_hip.stream_ptr(self.device))
-        dist = torch.empty(Q, N, dtype=torch.float32, device=self.device)
-        for n_done, (layer, query, weights, _) in enumerate(jobs):
-            stored = self.top if layer == 'top' else self.bottom
-            table = self.table(layer)
-            cells, K = query.shape[1], table.shape[0]
-            need = lib.isi_code_search_workspace_bytes(N, cells, K, Q)
-            if self._workspace is None or self._workspace.numel() * 4 < need:
-                self._workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=self.device)
-            _hip.check(lib.isi_code_search_f32(
-                stored.data_ptr(), query.data_ptr(), None if weights is None else weights.data_ptr(), table.data_ptr(),
-                None if allowed is None else allowed.data_ptr(), dist.data_ptr(), N, cells, K, Q, int(n_done > 0),
-                self._workspace.data_ptr(), self._workspace.numel() * 4, stream), "isi_code_search_f32")
-        return dist, all(job[3] for job in jobs)
+        jobs = [(layer, 'code') + self._query(layer, code, mask, weight) + (int(code.shape[2]), single)
+                for layer, weight, code, mask, single in checked]
+        return self._aligned_distances(jobs, allowed)
 
     def search(self, top_code=None, bottom_code=None, *, mask_top=None, mask_bottom=None,
                layer_weights: Tuple[float, float] = (1., 1.), k: int = 8,
@@ -302,15 +302,68 @@ class CodeIndex:
         allowed = self.allowed(attribute_constraints, exclude)
         dist, single = self.distances(top_code, bottom_code, mask_top=mask_top, mask_bottom=mask_bottom,
                                       layer_weights=layer_weights, allowed=allowed)
+        values, order = self._nearest(dist, k, self._admitted(allowed, attribute_constraints, exclude))
+        return (order[0], values[0]) if single else (order, values)
+
+    def _aligned_distances(self, jobs, allowed: Optional[torch.Tensor]):
+        """(dist fp32 [Q, N], single) of jobs (layer, kind, payload, weights, W, single): a code layer (payload = the uint16
+        query [Q, C]) through isi_code_search_f32, a vectors or rows layer through isi_code_search_rows_f32, the layers
+        after the first accumulated; the queries in groups that keep the rows built from vectors under ROWS_BUDGET_BYTES."""
+        Q, N = jobs[0][2].shape[0], len(self)
+        lib, stream = _hip.lib(), C.c_void_p(_hip.stream_ptr(self.device))
+        dist = torch.empty(Q, N, dtype=torch.float32, device=self.device)
+        group = self._rows_group_size(jobs)
+        for q0 in range(0, Q, group):
+            q1 = min(Q, q0 + group)
+            for n_done, job in enumerate(jobs):
+                layer, kind, payload, weights = job[:4]
+                stored = self.top if layer == 'top' else self.bottom
+                cells = payload.shape[1]
+                K = int((self.vqvae.quantize_t if layer == 'top' else self.vqvae.quantize_b).n_embed)
+                self._grow_workspace(lib.isi_code_search_workspace_bytes(N, cells, K, q1 - q0))
+                common = (None if allowed is None else allowed.data_ptr(), dist[q0:q1].data_ptr(), N, cells, K, q1 - q0,
+                          int(n_done > 0), self._workspace.data_ptr(), self._workspace.numel() * 4, stream)
+                w_ptr = None if weights is None else weights[q0:q1].data_ptr()
+                if kind == 'code':
+                    _hip.check(lib.isi_code_search_f32(stored.data_ptr(), payload[q0:q1].data_ptr(), w_ptr,
+                                                       self.table(layer).data_ptr(), *common), "isi_code_search_f32")
+                else:
+                    rows = self._rows_of(job, q0, q1)
+                    _hip.check(lib.isi_code_search_rows_f32(stored.data_ptr(), rows.data_ptr(), w_ptr, *common),
+                               "isi_code_search_rows_f32")
+        return dist, all(job[5] for job in jobs)
+
+    # ---- what the searches share after the distances: who is admitted, the ranking, the best offset
+    def _admitted(self, allowed: Optional[torch.Tensor], attribute_constraints, exclude) -> int:
+        """How many items `allowed` admits (LookupError when none)."""
         count = len(self) if allowed is None else int(allowed.sum())
         if count < 1:
             raise LookupError(f"no item of the index meets {dict(attribute_constraints or {})}"
                               + (f" outside {list(exclude)}" if exclude is not None and len(exclude) else ""))
-        # a stable sort: equal distances keep the order of the item indices (torch.topk promises nothing for ties)
+        return count
+
+    @staticmethod
+    def _nearest(dist: torch.Tensor, k: int, count: int):
+        """(values, order) [Q, min(k, count)] of dist [Q, N], by (distance, item index) ascending.  A stable sort: equal
+        distances keep the order of the item indices (torch.topk promises nothing for ties)."""
         values, order = torch.sort(dist, dim=1, stable=True)
         k = min(int(k), count)
-        values, order = values[:, :k].contiguous(), order[:, :k].contiguous()
-        return (order[0], values[0]) if single else (order, values)
+        return values[:, :k].contiguous(), order[:, :k].contiguous()
+
+    def _best_over_shifts(self, groups, Q: int, lo: int, count: int, allowed, n_allowed: int, k: int, single: bool):
+        """The result of a shifted search from its groups (q0, q1, dist [q1 - q0, count, N]): every item at its best offset
+        (isi_code_shift_best_f32), ranked, the offsets made absolute."""
+        lib, stream = _hip.lib(), C.c_void_p(_hip.stream_ptr(self.device))
+        N = len(self)
+        best = torch.empty(Q, N, dtype=torch.float32, device=self.device)
+        best_shift = torch.empty(Q, N, dtype=torch.int32, device=self.device)
+        for q0, q1, dist in groups:
+            _hip.check(lib.isi_code_shift_best_f32(dist.data_ptr(), None if allowed is None else allowed.data_ptr(),
+                                                   best[q0:q1].data_ptr(), best_shift[q0:q1].data_ptr(), N, count, q1 - q0,
+                                                   stream), "isi_code_shift_best_f32")
+        values, order = self._nearest(best, k, n_allowed)
+        shifts = torch.gather(best_shift, 1, order).to(torch.int64) + lo
+        return (order[0], shifts[0], values[0]) if single else (order, shifts, values)
 
     # ---- shift-invariant search (csrc/code_shift_search.hip)
     def _shift_plan(self, top_code, bottom_code, mask_top, mask_bottom, layer_weights, shift_range):
@@ -328,13 +381,23 @@ class CodeIndex:
         stored = self.top if checked[0][0] == 'top' else self.bottom
         T, W = int(stored.shape[2]), int(checked[0][2].shape[2])
         if len(checked) == 2:
-            ratio = self.bottom.shape[2] // self.top.shape[2]
-            if ratio < 1 or ratio * self.top.shape[2] != self.bottom.shape[2]:
-                raise ValueError(f"the bottom maps' {self.bottom.shape[2]} columns are no multiple of the top maps' "
-                                 f"{self.top.shape[2]}: a two-layer shifted search has no common offset")
-            if checked[1][2].shape[2] != ratio * W:
-                raise ValueError(f"bottom_code: {checked[1][2].shape[2]} columns, but the top window's {W} columns span "
-                                 f"{ratio * W} of the bottom layer")
+            self._check_two_layer_windows(W, int(checked[1][2].shape[2]), "bottom_code")
+        return (checked,) + self._shift_offsets(T, W, shift_range)
+
+    def _check_two_layer_windows(self, W: int, W_bottom: int, name: str) -> None:
+        """A two-layer shifted search needs a common offset: T_b = r T_t and a bottom window of r W columns (ValueError)."""
+        ratio = self.bottom.shape[2] // self.top.shape[2]
+        if ratio < 1 or ratio * self.top.shape[2] != self.bottom.shape[2]:
+            raise ValueError(f"the bottom maps' {self.bottom.shape[2]} columns are no multiple of the top maps' "
+                             f"{self.top.shape[2]}: a two-layer shifted search has no common offset")
+        if W_bottom != ratio * W:
+            raise ValueError(f"{name}: {W_bottom} columns, but the top window's {W} columns span {ratio * W} of the bottom "
+                             "layer")
+
+    @staticmethod
+    def _shift_offsets(T: int, W: int, shift_range):
+        """(lo, count): the offsets lo .. lo + count - 1 at which a window of W columns fits the stored T, inside
+        shift_range (ValueError when there is none)."""
         lo, hi = 0, T - W + 1
         if shift_range is not None:
             if len(shift_range) != 2:
@@ -343,51 +406,22 @@ class CodeIndex:
             if lo >= hi:
                 raise ValueError(f"shift_range {tuple(shift_range)} holds no offset at which a window of {W} columns fits "
                                  f"the stored {T}")
-        return checked, lo, hi - lo
+        return lo, hi - lo
 
     def _shifted_jobs(self, checked):
+        """The layers of a hard shifted search as the jobs `_shifted_groups` runs: (layer, 'code', query, weights, W, single)."""
         jobs = []
         for layer, weight, code, mask, single in checked:
             query, weights = self._query(layer, code, mask, weight)
-            jobs.append((layer, query, weights, int(code.shape[2]), single))
+            jobs.append((layer, 'code', query, weights, int(code.shape[2]), single))
         return jobs
 
     def _shifted_group_size(self, jobs, count) -> int:
         """Queries per launch so that workspace + dist [g, S, N] stay under SHIFT_BUDGET_BYTES (at least 1)."""
         N = len(self)
-        runs = max(-(-(self.top if layer == 'top' else self.bottom).shape[1] * W // 256) for layer, _, _, W, _ in jobs)
+        runs = max(-(-(self.top if job[0] == 'top' else self.bottom).shape[1] * job[4] // 256) for job in jobs)
         per_query = (1 + (runs if runs > 1 else 0)) * count * N * 4
         return max(1, min(MAX_QUERIES, SHIFT_BUDGET_BYTES // per_query))
-
-    def _shifted_into(self, jobs, q0: int, q1: int, first: int, count: int, dist: torch.Tensor) -> None:
-        """dist [q1 - q0, count, N] (contiguous) of the queries q0 .. q1 - 1 at the offsets first .. first + count - 1."""
-        lib, stream = _hip.lib(), C.c_void_p(_hip.stream_ptr(self.device))
-        N, Q = len(self), q1 - q0
-        ratio = 1 if len(jobs) == 1 else self.bottom.shape[2] // self.top.shape[2]
-        for n_done, (layer, query, weights, W, _) in enumerate(jobs):
-            stored = self.top if layer == 'top' else self.bottom
-            table = self.table(layer)
-            F, T, K = int(stored.shape[1]), int(stored.shape[2]), table.shape[0]
-            step = ratio if n_done > 0 else 1
-            need = lib.isi_code_shift_search_workspace_bytes(N, F, T, W, count, K, Q)
-            if self._workspace is None or self._workspace.numel() * 4 < need:
-                self._workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=self.device)
-            _hip.check(lib.isi_code_shift_search_f32(
-                stored.data_ptr(), query[q0:q1].data_ptr(), None if weights is None else weights[q0:q1].data_ptr(),
-                table.data_ptr(), dist.data_ptr(), N, F, T, W, step * first, step, count, K, Q, int(n_done > 0),
-                self._workspace.data_ptr(), self._workspace.numel() * 4, stream), "isi_code_shift_search_f32")
-
-    def _shifted_groups(self, jobs, lo: int, count: int):
-        """Yields (q0, q1, dist [q1 - q0, count, N]) group by group.  The launch starts at a multiple of 8 columns (the
-        kernel reads aligned vectors from there); the offsets below `lo` are computed and dropped."""
-        Q, N = jobs[0][1].shape[0], len(self)
-        first = lo - lo % 8
-        group = self._shifted_group_size(jobs, count + lo - first)
-        for q0 in range(0, Q, group):
-            q1 = min(Q, q0 + group)
-            dist = torch.empty(q1 - q0, count + lo - first, N, dtype=torch.float32, device=self.device)
-            self._shifted_into(jobs, q0, q1, first, count + lo - first, dist)
-            yield q0, q1, (dist if first == lo else dist[:, lo - first:].contiguous())
 
     def distances_shifted(self, top_code=None, bottom_code=None, *, mask_top=None, mask_bottom=None,
                           layer_weights: Tuple[float, float] = (1., 1.), shift_range: Optional[Tuple[int, int]] = None):
@@ -415,22 +449,206 @@ class CodeIndex:
             raise ValueError(f"k must be at least 1, not {k}")
         checked, lo, count = self._shift_plan(top_code, bottom_code, mask_top, mask_bottom, layer_weights, shift_range)
         allowed = self.allowed(attribute_constraints, exclude)
-        n_allowed = len(self) if allowed is None else int(allowed.sum())
-        if n_allowed < 1:
-            raise LookupError(f"no item of the index meets {dict(attribute_constraints or {})}"
-                              + (f" outside {list(exclude)}" if exclude is not None and len(exclude) else ""))
+        n_allowed = self._admitted(allowed, attribute_constraints, exclude)
         jobs = self._shifted_jobs(checked)
+        return self._best_over_shifts(self._shifted_groups(jobs, lo, count), jobs[0][2].shape[0], lo, count, allowed, n_allowed,
+                                      k, all(job[5] for job in jobs))
+
+    # ---- search by encoder vectors: per-cell distance rows
+    def _checked_soft(self, layer: str, code, vectors, rows, mask, window: bool = False):
+        """One layer of a soft query, given as exactly one of code / vectors / rows, checked before any device work:
+        (kind, data, mask or None, single) with data [Q, F, W] for kind 'code' (as `_checked`), [Q, F, W, D] for
+        'vectors', [Q, F, W, K] for 'rows'; W == T unless `window`."""
+        given = [kind for kind, value in (('code', code), ('vectors', vectors), ('rows', rows)) if value is not None]
+        if len(given) != 1:
+            raise ValueError(f"the {layer} layer takes one of {layer}_code, {layer}_vectors and {layer}_rows, got "
+                             + " and ".join(f"{layer}_{kind}" for kind in given))
+        kind = given[0]
+        if kind == 'code':
+            return ('code',) + self._checked(layer, code, mask, window)
+        name = f"{layer}_{kind}"
+        stored = self.top if layer == 'top' else self.bottom
+        if stored is None:
+            raise ValueError(f"{name} given, but the index holds no {layer} maps")
+        quantizer = self.vqvae.quantize_t if layer == 'top' else self.vqvae.quantize_b
+        last = int(quantizer.dim) if kind == 'vectors' else int(quantizer.n_embed)
+        F, T = int(stored.shape[1]), int(stored.shape[2])
+        data = torch.as_tensor(vectors if kind == 'vectors' else rows)
+        columns = f"W, {last}] with 1 <= W <= {T}" if window else f"{T}, {last}]"
+        if data.dim() not in (3, 4) or not data.dtype.is_floating_point or data.shape[-1] != last or data.shape[-3] != F \
+                or not (1 <= data.shape[-2] <= T if window else data.shape[-2] == T):
+            raise ValueError(f"{name}: expected floating-point [{F}, {columns} (or [Q, ...]) -- the stored maps' cells and "
+                             f"the layer's {'embedding dimension' if kind == 'vectors' else 'number of codes'} -- got "
+                             f"{data.dtype} {tuple(data.shape)}")
+        single = data.dim() == 3 or data.shape[0] == 1
+        W = int(data.shape[-2])
+        data = data.reshape(-1, F, W, last)
+        Q = data.shape[0]
+        if not 1 <= Q <= MAX_QUERIES:
+            raise ValueError(f"{name}: {Q} queries, a search takes 1..{MAX_QUERIES}")
+        if mask is not None:
+            mask = torch.as_tensor(mask)
+            if mask.dtype != torch.bool or mask.dim() not in (2, 3) or tuple(mask.shape[-2:]) != (F, W) \
+                    or (mask.dim() == 3 and mask.shape[0] not in (1, Q)):
+                raise ValueError(f"mask_{layer}: expected bool [{F}, {W}] (or [Q, ...]), got {mask.dtype} {tuple(mask.shape)}")
+        return kind, data, mask, single
+
+    def _soft_layers(self, what: str, forms, masks, layer_weights, window: bool):
+        """[(layer, weight, kind, data, mask, single)] of the layers given, validated (ValueError)."""
+        if all(value is None for form in forms for value in form):
+            raise ValueError(f"{what}: give a top layer, a bottom layer or both (as *_code, *_vectors or *_rows)")
+        if any(float(w) < 0 for w in layer_weights):
+            raise ValueError(f"layer_weights must be >= 0, got {tuple(layer_weights)}")
+        checked = [(layer, weight) + self._checked_soft(layer, *form, mask, window)
+                   for layer, form, mask, weight in zip(('top', 'bottom'), forms, masks, layer_weights)
+                   if any(value is not None for value in form)]
+        if len({c[3].shape[0] for c in checked}) != 1:
+            raise ValueError("the top and the bottom layer hold different numbers of queries")
+        return checked
+
+    def _soft_job(self, layer: str, weight: float, kind: str, data: torch.Tensor, mask, single: bool):
+        """(layer, kind, payload, weights fp32 [Q, C] or None, W, single) on the device: payload is the uint16 query [Q, C]
+        of a code layer, fp32 [Q, C, D] vectors or fp32 [Q, C, K] rows otherwise."""
+        if kind == 'code':
+            query, weights = self._query(layer, data, mask, weight)
+            return layer, kind, query, weights, int(data.shape[2]), single
+        stored = self.top if layer == 'top' else self.bottom
+        if not data.is_cuda or (mask is not None and not mask.is_cuda) or not stored.is_cuda:
+            raise _hip.HipLibraryError(f"{layer}_{kind} / mask_{layer} / the index live on "
+                                       f"{data.device} / {None if mask is None else mask.device} / {stored.device}: this "
+                                       "package computes only on an MI355X (HIP kernels, no CPU fallback)")
+        Q, F, W, last = data.shape
+        payload = data.to(self.device, torch.float32).reshape(Q, F * W, last).contiguous()
+        weights = None
+        if mask is not None or float(weight) != 1.0:
+            keep = torch.ones(Q, F, W, dtype=torch.bool, device=self.device) if mask is None \
+                else ~mask.to(self.device).reshape(-1, F, W).expand(Q, F, W)
+            weights = (keep.to(torch.float32) * float(weight)).reshape(Q, -1).contiguous()
+        return layer, kind, payload, weights, W, single
+
+    def _rows_group_size(self, jobs) -> int:
+        """Queries per launch so that the rows built from vectors, [g, C, K] fp32 per layer, stay under ROWS_BUDGET_BYTES
+        (at least 1).  Rows the caller hands over exist already and are not counted."""
+        per_query = max([job[2].shape[1] * int((self.vqvae.quantize_t if job[0] == 'top' else self.vqvae.quantize_b).n_embed) * 4
+                         for job in jobs if job[1] == 'vectors'] or [0])
+        return MAX_QUERIES if per_query == 0 else max(1, min(MAX_QUERIES, ROWS_BUDGET_BYTES // per_query))
+
+    def _rows_of(self, job, q0: int, q1: int) -> torch.Tensor:
+        """rows fp32 [q1 - q0, C, K] of a vectors or rows layer, built on the device for a vectors layer."""
+        layer, kind, payload = job[0], job[1], job[2]
+        if kind == 'rows':
+            return payload[q0:q1]
+        quantizer = self.vqvae.quantize_t if layer == 'top' else self.vqvae.quantize_b
+        _hip.require_gpu(quantizer.embed, f"quantize_{layer[0]}.embed")
+        if quantizer.embed.device != self.device:
+            raise _hip.HipLibraryError(f"the VQ-VAE lives on {quantizer.embed.device}, the index on {self.device}")
+        return quantizer.distance_rows(payload[q0:q1])
+
+    def _grow_workspace(self, need: int) -> None:
+        if self._workspace is None or self._workspace.numel() * 4 < need:
+            self._workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=self.device)
+
+    def distances_soft(self, top_code=None, bottom_code=None, *, top_vectors=None, bottom_vectors=None, top_rows=None,
+                       bottom_rows=None, mask_top=None, mask_bottom=None, layer_weights: Tuple[float, float] = (1., 1.),
+                       allowed: Optional[torch.Tensor] = None):
+        """(dist fp32 [Q, N], single) as `distances`, each layer given as exactly one of codes (`distances`' launch), vectors
+        [Q, F, T, D] (or [F, T, D]) -- dist = sum_c w[c] |z[c] - E[x[c]]|^2, the rows built on the device -- or ready rows
+        [Q, F, T, K] of any per-cell cost."""
+        checked = self._soft_layers("search_soft", ((top_code, top_vectors, top_rows), (bottom_code, bottom_vectors, bottom_rows)),
+                                    (mask_top, mask_bottom), layer_weights, window=False)
+        return self._aligned_distances([self._soft_job(*c) for c in checked], allowed)
+
+    def search_soft(self, top_code=None, bottom_code=None, *, top_vectors=None, bottom_vectors=None, top_rows=None,
+                    bottom_rows=None, mask_top=None, mask_bottom=None, layer_weights: Tuple[float, float] = (1., 1.), k: int = 8,
+                    attribute_constraints: Optional[Mapping[str, object]] = None, exclude: Optional[Sequence[int]] = None):
+        """`search` for queries that are no codemaps: the k stored items nearest to per-cell VECTORS -- an encoder's output
+        before it is snapped to codes (`VQVAE.encode_vectors`), or a blend of codes (`embed_mix`) -- by
+        dist(z, x) = sum_c w[c] |z[c] - E[x[c]]|^2.  Per layer give exactly one of `*_code` (compared through the code
+        distance table, as `search` does), `*_vectors` [F, T, D] (or [Q, F, T, D]; D the layer's embedding dimension) or
+        `*_rows` [Q, F, T, K], ready per-cell costs of every code; the layers add up as in `search`, so an upload's top
+        vectors can be searched beside hard bottom codes.  There is no mask token in a vector: mask_* (True = weight 0) is
+        the only mask, and a masked cell counts nothing whatever its vector holds.  Vectors that are codebook rows bit for
+        bit give `search`'s distances bit for bit.  Everything else -- layer_weights, k, attribute_constraints, exclude,
+        the (distance, index) order, LookupError / ValueError / HipLibraryError -- is `search`'s.  Rows are built for at
+        most ROWS_BUDGET_BYTES of queries at a time; distances are query-local, so the grouping changes no bit."""
+        if int(k) < 1:
+            raise ValueError(f"k must be at least 1, not {k}")
+        allowed = self.allowed(attribute_constraints, exclude)
+        dist, single = self.distances_soft(top_code, bottom_code, top_vectors=top_vectors, bottom_vectors=bottom_vectors,
+                                           top_rows=top_rows, bottom_rows=bottom_rows, mask_top=mask_top,
+                                           mask_bottom=mask_bottom, layer_weights=layer_weights, allowed=allowed)
+        values, order = self._nearest(dist, k, self._admitted(allowed, attribute_constraints, exclude))
+        return (order[0], values[0]) if single else (order, values)
+
+    def _soft_shift_plan(self, forms, masks, layer_weights, shift_range):
+        """`_shift_plan` for soft layers: (checked layers, lo, count)."""
+        checked = self._soft_layers("search_shifted_soft", forms, masks, layer_weights, window=True)
+        stored = self.top if checked[0][0] == 'top' else self.bottom
+        T, W = int(stored.shape[2]), int(checked[0][3].shape[2])
+        if len(checked) == 2:
+            self._check_two_layer_windows(W, int(checked[1][3].shape[2]), "the bottom window")
+        return (checked,) + self._shift_offsets(T, W, shift_range)
+
+    def _shifted_groups(self, jobs, lo: int, count: int):
+        """Yields (q0, q1, dist [q1 - q0, count, N]) group by group, for the hard and the soft shifted searches: a code layer
+        through isi_code_shift_search_f32, a vectors or rows layer through isi_code_shift_search_rows_f32.  The launch
+        starts at a multiple of 8 columns (the kernel reads aligned vectors from there); the offsets below `lo` are computed
+        and dropped."""
         lib, stream = _hip.lib(), C.c_void_p(_hip.stream_ptr(self.device))
-        Q, N = jobs[0][1].shape[0], len(self)
-        best = torch.empty(Q, N, dtype=torch.float32, device=self.device)
-        best_shift = torch.empty(Q, N, dtype=torch.int32, device=self.device)
-        for q0, q1, dist in self._shifted_groups(jobs, lo, count):
-            _hip.check(lib.isi_code_shift_best_f32(dist.data_ptr(), None if allowed is None else allowed.data_ptr(),
-                                                   best[q0:q1].data_ptr(), best_shift[q0:q1].data_ptr(), N, count, q1 - q0,
-                                                   stream), "isi_code_shift_best_f32")
-        values, order = torch.sort(best, dim=1, stable=True)
-        k = min(int(k), n_allowed)
-        values, order = values[:, :k].contiguous(), order[:, :k].contiguous()
-        shifts = torch.gather(best_shift, 1, order).to(torch.int64) + lo
-        single = all(job[4] for job in jobs)
-        return (order[0], shifts[0], values[0]) if single else (order, shifts, values)
+        Q, N = jobs[0][2].shape[0], len(self)
+        first = lo - lo % 8
+        S = count + lo - first
+        group = min(self._shifted_group_size(jobs, S), self._rows_group_size(jobs))
+        ratio = 1 if len(jobs) == 1 else self.bottom.shape[2] // self.top.shape[2]
+        for q0 in range(0, Q, group):
+            q1 = min(Q, q0 + group)
+            dist = torch.empty(q1 - q0, S, N, dtype=torch.float32, device=self.device)
+            for n_done, job in enumerate(jobs):
+                layer, kind, payload, weights, W = job[:5]
+                stored = self.top if layer == 'top' else self.bottom
+                F, T = int(stored.shape[1]), int(stored.shape[2])
+                K = int((self.vqvae.quantize_t if layer == 'top' else self.vqvae.quantize_b).n_embed)
+                step = ratio if n_done > 0 else 1
+                self._grow_workspace(lib.isi_code_shift_search_workspace_bytes(N, F, T, W, S, K, q1 - q0))
+                common = (dist.data_ptr(), N, F, T, W, step * first, step, S, K, q1 - q0, int(n_done > 0),
+                          self._workspace.data_ptr(), self._workspace.numel() * 4, stream)
+                w_ptr = None if weights is None else weights[q0:q1].data_ptr()
+                if kind == 'code':
+                    _hip.check(lib.isi_code_shift_search_f32(stored.data_ptr(), payload[q0:q1].data_ptr(), w_ptr,
+                                                             self.table(layer).data_ptr(), *common), "isi_code_shift_search_f32")
+                else:
+                    rows = self._rows_of(job, q0, q1)
+                    _hip.check(lib.isi_code_shift_search_rows_f32(stored.data_ptr(), rows.data_ptr(), w_ptr, *common),
+                               "isi_code_shift_search_rows_f32")
+            yield q0, q1, (dist if first == lo else dist[:, lo - first:].contiguous())
+
+    def distances_shifted_soft(self, top_code=None, bottom_code=None, *, top_vectors=None, bottom_vectors=None, top_rows=None,
+                               bottom_rows=None, mask_top=None, mask_bottom=None,
+                               layer_weights: Tuple[float, float] = (1., 1.), shift_range: Optional[Tuple[int, int]] = None):
+        """dist fp32 [Q, S, N] as `distances_shifted`, for windows given per layer as codes, vectors [Q, F, W, D] or rows
+        [Q, F, W, K] (`search_shifted_soft`)."""
+        checked, lo, count = self._soft_shift_plan(((top_code, top_vectors, top_rows), (bottom_code, bottom_vectors, bottom_rows)),
+                                                   (mask_top, mask_bottom), layer_weights, shift_range)
+        jobs = [self._soft_job(*c) for c in checked]
+        return torch.cat([dist for _, _, dist in self._shifted_groups(jobs, lo, count)], 0)
+
+    def search_shifted_soft(self, top_code=None, bottom_code=None, *, top_vectors=None, bottom_vectors=None, top_rows=None,
+                            bottom_rows=None, mask_top=None, mask_bottom=None, layer_weights: Tuple[float, float] = (1., 1.),
+                            k: int = 8, shift_range: Optional[Tuple[int, int]] = None,
+                            attribute_constraints: Optional[Mapping[str, object]] = None,
+                            exclude: Optional[Sequence[int]] = None):
+        """`search_shifted` for windows that are no codemaps: per layer exactly one of `*_code` [F, W], `*_vectors`
+        [F, W, D] or `*_rows` [Q, F, W, K] (a leading Q as in `search_soft`), the bottom window r = T_b / T_t times as
+        wide as the top one.  Returns (indices, shifts, distances) as `search_shifted` does, with its offsets, shift_range,
+        masks, constraints, ordering and errors; the zero-weight rule and the bitwise agreement with the hard search on
+        vectors that are codebook rows are `search_soft`'s.  The groups of queries respect both SHIFT_BUDGET_BYTES and
+        ROWS_BUDGET_BYTES."""
+        if int(k) < 1:
+            raise ValueError(f"k must be at least 1, not {k}")
+        checked, lo, count = self._soft_shift_plan(((top_code, top_vectors, top_rows), (bottom_code, bottom_vectors, bottom_rows)),
+                                                   (mask_top, mask_bottom), layer_weights, shift_range)
+        allowed = self.allowed(attribute_constraints, exclude)
+        n_allowed = self._admitted(allowed, attribute_constraints, exclude)
+        jobs = [self._soft_job(*c) for c in checked]
+        return self._best_over_shifts(self._shifted_groups(jobs, lo, count), jobs[0][2].shape[0], lo, count, allowed,
+                                      n_allowed, k, all(job[5] for job in jobs))

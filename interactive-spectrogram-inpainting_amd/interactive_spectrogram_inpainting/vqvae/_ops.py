@@ -438,6 +438,30 @@ def vq_nearest_topm(z: torch.Tensor, codes: torch.Tensor, e2: torch.Tensor, m: i
     return ids, dist
 
 
+def code_distance_rows(z: torch.Tensor, codes: torch.Tensor) -> torch.Tensor:
+    """z [..., D] fp32 -> rows fp32 [..., K]: R[..., k] = sum_d (z[..., d] - codes[k][d])^2, the code distance table's
+    expression with the vector in the row's place (csrc/code_search.hip: isi_code_query_rows_f32).
+    A vector that is a codebook row bit for bit gives that row of the table bit for bit.  Vectors that lie at one stride
+    in memory -- a channel slice of a channels-last activation -- are read in place."""
+    _hip.require_gpu(z, "distance rows input")
+    if z.dtype != torch.float32:
+        raise TypeError(f"vectors must be float32, got {z.dtype}")
+    K, D = codes.shape
+    if z.dim() < 1 or z.shape[-1] != D:
+        raise ValueError(f"vectors {tuple(z.shape)} do not end in the codebook's dimension {D}")
+    cells = z.shape[:-1]
+    rows = torch.empty(*cells, K, dtype=torch.float32, device=z.device)
+    if rows.numel() == 0:
+        return rows
+    flat = z.reshape(-1, D)                              # a view where the vectors lie at one stride
+    if flat.stride(1) != 1 or (flat.shape[0] > 1 and flat.stride(0) < D):
+        flat = flat.contiguous()
+    stride = flat.stride(0) if flat.shape[0] > 1 else D
+    _hip.check(_hip.lib().isi_code_query_rows_f32(flat.data_ptr(), stride, codes.data_ptr(), rows.data_ptr(), flat.shape[0],
+                                                  K, D, _s(z)), "isi_code_query_rows_f32")
+    return rows
+
+
 def pack_code_tables(packed_w3: Optional[torch.Tensor], cout3: int, packed_wT: Optional[torch.Tensor], coutU: int,
                      codes: torch.Tensor):
     """Per-code product tables of a 3x3 convolution and of a ConvTranspose2d(k4,s2,p1) over the codebook `codes` [K,D]

@@ -95,6 +95,13 @@ class QuantizedBottleneck(nn.Module):
             raise ValueError("allowed_map selects rows of allowed_codes, which is not given")
         return _ops.vq_nearest_topm(z_nhwc, codes, e2, m, allowed, allowed_map)
 
+    def distance_rows(self, z: Tensor) -> Tensor:
+        """z [..., D] -> fp32 [..., K]: every vector's squared distance to every code, |z - E[k]|^2 -- the per-cell rows
+        `CodeIndex.search_soft` compares stored codes with (`_ops.code_distance_rows`).  A vector that is codebook row `a`
+        bit for bit gives row `a` of the code distance table bit for bit.  The codebook is not updated, in any mode."""
+        codes, _ = self.packed()
+        return _ops.code_distance_rows(z, codes)
+
 
 class QuantizedBottleneckWithRestarts(QuantizedBottleneck):
     """EMA codebook with random restarts of dead codes (the reference's `bottleneck.py:122-166`, whose arithmetic sits in
@@ -150,4 +157,7 @@ class UnquantizedBottleneck(QuantizedBottleneck):
         raise NotImplementedError
 
     def nearest_codes(self, z_nhwc, m=1, allowed_codes=None, allowed_map=None):
+        raise NotImplementedError
+
+    def distance_rows(self, z):
         raise NotImplementedError

@@ -465,10 +465,18 @@ class VQVAE(nn.Module):
         every convolution on the exact-fp32 matrix pipe, whatever `conv_precision` says -- not the batch path of
         `isi_vqvae_run` that `encode` and `forward` take.  With m = 1 and no palette the ids are `encode`'s except where two
         codes are a rounding error apart.  Eval mode only: no codebook is updated."""
+        return self._encode_layers("encode_topm", input, m, allowed_codes_top, allowed_codes_bottom, allowed_map_top,
+                                   allowed_map_bottom)[:4]
+
+    def _encode_layers(self, what: str, input: Tensor, m: int, allowed_codes_top=None, allowed_codes_bottom=None,
+                       allowed_map_top: Optional[Tensor] = None, allowed_map_bottom: Optional[Tensor] = None):
+        """The layer sequence `encode_topm` documents, for it and for `encode_vectors`:
+        (codes_t, dist_t, codes_b, dist_b, z_t [B, Ht, Wt, D], z_b [B, Hb, Wb, D]) -- the searches' results and the
+        vectors they searched with."""
         if self.training:
-            raise RuntimeError("encode_topm is an eval-mode call (model.eval()): it never updates the codebooks")
+            raise RuntimeError(f"{what} is an eval-mode call (model.eval()): it never updates the codebooks")
         if self.disable_quantization:
-            raise NotImplementedError("encode_topm: this model has no codebooks (disable_quantization)")
+            raise NotImplementedError(f"{what}: this model has no codebooks (disable_quantization)")
         _hip.require_gpu(input, "input")
         if input.dim() != 4 or input.shape[1] != self.in_channel:
             raise RuntimeError(f"expected input [B, {self.in_channel}, H, W], got {tuple(input.shape)}")
@@ -492,7 +500,17 @@ class VQVAE(nn.Module):
             dec_t, enc_b = dec_t[..., :w], enc_b[..., :w]
         z_b = nhwc(self.quantize_conv_b.run(dec_t, relu=False, x2=enc_b))
         codes_b, dist_b = self.quantize_b.nearest_codes(z_b, m, allowed_codes_bottom, allowed_map_bottom)
-        return codes_t, dist_t, codes_b, dist_b
+        return codes_t, dist_t, codes_b, dist_b, z_t, z_b
+
+    @torch.no_grad()
+    def encode_vectors(self, input: Tensor):
+        """The encoder's output BEFORE it is snapped to codes: (z_t [B, Ht, Wt, D], z_b [B, Hb, Wb, D], id_t [B, Ht, Wt],
+        id_b [B, Hb, Wb]) -- per cell the vector the codebook search sees, channels-last, and its nearest code.  This is
+        `encode_topm`'s layer sequence with m = 1 (the bottom level sees the top's quantisation, as in `encode`), so the
+        ids are `encode_topm(input, 1)`'s; the vectors are what `CodeIndex.search_soft` takes as `*_vectors`: an upload
+        compared with the stored sounds without throwing its quantisation error away.  Eval mode only."""
+        codes_t, _, codes_b, _, z_t, z_b = self._encode_layers("encode_vectors", input, 1)
+        return z_t, z_b, codes_t[0], codes_b[0]
 
     @staticmethod
     def soft_weights(dist: Tensor, temperature: float) -> Tensor:

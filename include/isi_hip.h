@@ -258,6 +258,56 @@ int isi_code_shift_search_rows_f32(const uint16_t *codes, const float *rows, con
 int isi_code_shift_best_f32(const float *dist, const uint8_t *allowed, float *best, int32_t *best_shift, int64_t N, int S,
                             int Q, void *stream);
 
+/* ------------------------------------------------ time-warped search of a code database */
+/* "Which stored sound is like this one, played a little faster or slower" (specification
+ * tests/code_warp_search_spec.py).  A grid has W query columns and T item columns.  The query is n_parts in {1, 2} parts
+ * (a top layer, a bottom layer, or both); part p has F rows, r >= 1 columns of its own per grid column (top: 1; bottom
+ * beside a top part: T_b / T_t), a codebook size K, stored codes uint16 [N, F, T r], per-cell cost rows fp32
+ * [Q, F * W r, K] with cell c = f * (W r) + (i r + u) -- the rows of isi_code_search_rows_f32; a codemap query is rows
+ * gathered from the code distance table by the caller, mask-token cells under weight 0 -- and weights fp32 [Q, F, W r] >= 0
+ * or NULL (1 on every cell).
+ *   cost[i][t] = sum_p sum_f sum_u fl(w_p[f][i r + u] * rows_p[c][min(codes_p[n][f][t r + u], K - 1)])
+ * in fp32 from +0, each product rounded once, added in the order parts, f ascending, u ascending; a cell whose weight is
+ * exactly 0 adds +0 whatever its row holds, NaN and inf included.  Query column i is matched to one item column p(i) with
+ * p(i+1) - p(i) in {0, 1, 2} (hold, step, skip), lo <= p(i) - i <= hi and 0 <= p(i) <= T - 1; every query column counts
+ * once, so the distances of different paths and items compare.  With lo == hi == o the only path is p(i) = o + i.
+ *   D[0][t] = cost[0][t];   D[i][t] = fl(cost[i][t] + min(D[i-1][t-1], D[i-1][t], D[i-1][t-2]))   (+inf off the band)
+ *   dist = min_t D[W-1][t],  end = the smallest t that attains it;  +inf and -1 without a path or where allowed[n] == 0
+ * The minimum is taken by strict comparisons in the order t-1, t, t-2: that is the path's tie rule; it never changes dist,
+ * which is the minimum over all admissible paths of the path's left-to-right fp32 sum.
+ * isi_code_warp_search_f32: dist fp32 [Q, N], end int32 [Q, N] or NULL, allowed uint8 [N] or NULL.  Deterministic and
+ * item-local: the bits of dist[j][n] depend on the query's rows and weights, the item's codes, T, W, lo and hi only -- not
+ * on N, Q, the item's position, alignment, the launch geometry or the run; no atomics.  Widening the band never increases
+ * a distance.  Exact when the rows hold small non-negative integers, the weights are 0 or 1 and the sums stay below 2^24.
+ * For rows >= 0 under non-zero weight |dist - dist64| <= (V + W + 2) 2^-24 dist64, V = sum_p F_p r_p, dist64 the same
+ * recurrence in float64 on the same fp32 factors.  Negative or non-finite rows under a non-zero weight follow IEEE rules
+ * through the expressions above and touch nothing outside the buffers.  A stored code >= K is clamped to K - 1.  A fetched
+ * code serves every (query column, band position) pair of a group of columns that reaches it.  W may exceed T (lo < 0).
+ * isi_code_warp_path_f32: the same recurrence for M chosen items per query, items int64 [Q, M] -> path int32 [Q, M, W]
+ * (p(i), backtracked on the device from `end`) and dist fp32 [Q, M], bit for bit the search's (allowed is not applied).
+ * An item outside [0, N) gets +inf and a path of -1 throughout, as does an item without a path.  The workspace
+ * (isi_code_warp_path_workspace_bytes, host only: Q M W (hi - lo + 1) bytes of back-pointers rounded up to 16; 0 for
+ * sizes the call refuses) is scratch.  Not tuned: one wavefront per (query, item).
+ * No allocation, no host synchronisation; stream-ordered.  Checked before any launch, isi_last_error() names the
+ * argument: a null parts / codes / rows / dist (path: items / path / dist / workspace), a misaligned pointer (2 bytes for
+ * codes, 8 for items, 4 for the others), N, T, W, F, r or K <= 0, n_parts outside 1..2, Q outside 1..64, M outside 1..64,
+ * lo > hi, a band that leaves the first or the last query column without an admissible cell (hi < 0, lo > T - 1,
+ * W - 1 + hi < 0 or W - 1 + lo > T - 1) (ISI_E_INVALID); hi - lo + 1 > 64, K > 16384, W > 4096, Q * N >= 2^39,
+ * F * max(W, T) * r >= 2^31 (ISI_E_UNSUPPORTED); a workspace smaller than isi_code_warp_path_workspace_bytes
+ * (ISI_E_WORKSPACE). */
+typedef struct isi_warp_part {
+  const uint16_t *codes;   /* [N, F, T r]                 */
+  const float *rows;       /* [Q, F * W r, K]             */
+  const float *weights;    /* [Q, F, W r] or NULL         */
+  int F, r, K;
+} isi_warp_part;
+int isi_code_warp_search_f32(const isi_warp_part *parts, int n_parts, const uint8_t *allowed, float *dist, int32_t *end,
+                             int64_t N, int T, int W, int lo, int hi, int Q, void *stream);
+size_t isi_code_warp_path_workspace_bytes(int M, int W, int lo, int hi, int Q);
+int isi_code_warp_path_f32(const isi_warp_part *parts, int n_parts, const int64_t *items, int M, int32_t *path, float *dist,
+                           void *workspace, size_t workspace_bytes, int64_t N, int T, int W, int lo, int hi, int Q,
+                           void *stream);
+
 /* ------------------------------------------------- measurement (bench.py) */
 /* Per-launch timing with HIP events recorded on the launch stream.  State is
  * per calling thread; `on` = 1 starts (earlier records cleared), 0 pauses, 2 resumes without

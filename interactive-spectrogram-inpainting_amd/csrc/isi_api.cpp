@@ -366,6 +366,18 @@ int isi_code_shift_best_f32(const float *dist, const uint8_t *allowed, float *be
                             int Q, void *stream) {
   return code_shift_best_f32(dist, allowed, best, best_shift, N, S_, Q, S(stream));
 }
+int isi_code_warp_search_f32(const isi_warp_part *parts, int n_parts, const uint8_t *allowed, float *dist, int32_t *end,
+                             int64_t N, int T, int W, int lo, int hi, int Q, void *stream) {
+  return code_warp_search_f32(parts, n_parts, allowed, dist, end, N, T, W, lo, hi, Q, S(stream));
+}
+size_t isi_code_warp_path_workspace_bytes(int M, int W, int lo, int hi, int Q) {
+  return code_warp_path_workspace_bytes(M, W, lo, hi, Q);
+}
+int isi_code_warp_path_f32(const isi_warp_part *parts, int n_parts, const int64_t *items, int M, int32_t *path, float *dist,
+                           void *workspace, size_t workspace_bytes, int64_t N, int T, int W, int lo, int hi, int Q,
+                           void *stream) {
+  return code_warp_path_f32(parts, n_parts, items, M, path, dist, workspace, workspace_bytes, N, T, W, lo, hi, Q, S(stream));
+}
 int isi_rel_attention_f32(const isi_attn_args *args, void *stream) { return rel_attention_f32(args, S(stream)); }
 size_t isi_rel_attention_workspace_bytes(const isi_attn_args *args) { return rel_attention_workspace_bytes(args); }
 size_t isi_rel_attention_bwd_workspace_floats(const isi_attn_args *fwd) { return rel_attention_bwd_workspace_floats(fwd); }

@@ -396,6 +396,12 @@ int code_shift_search_rows_f32(const uint16_t *codes, const float *rows, const f
                                size_t workspace_bytes, hipStream_t st);
 int code_shift_best_f32(const float *dist, const uint8_t *allowed, float *best, int32_t *best_shift, int64_t N, int S, int Q,
                         hipStream_t st);
+// code_warp_search.hip
+int code_warp_search_f32(const isi_warp_part *parts, int n_parts, const uint8_t *allowed, float *dist, int32_t *end, int64_t N,
+                         int T, int W, int lo, int hi, int Q, hipStream_t st);
+size_t code_warp_path_workspace_bytes(int M, int W, int lo, int hi, int Q);
+int code_warp_path_f32(const isi_warp_part *parts, int n_parts, const int64_t *items, int M, int32_t *path, float *dist,
+                       void *workspace, size_t workspace_bytes, int64_t N, int T, int W, int lo, int hi, int Q, hipStream_t st);
 
 size_t packed_conv_weight_floats(int Cout, int Cin, int KH, int KW);
 size_t packed_convT_k4s2_weight_floats(int Cin, int Cout);

@@ -838,6 +838,68 @@ def paste_fragment(top_code: torch.Tensor, bottom_code: torch.Tensor, item_top: 
     return top_code, _paste_columns(bottom_code, item_bottom, mask, ratio_t * start, ratio_t * shift)
 
 
+def similar_sounds_warped(index, top_code: torch.Tensor, bottom_code: Optional[torch.Tensor], mask: Optional[torch.Tensor] = None,
+                          layer: str = 'top', start_index_top: int = 0, k: int = 8, drift: Tuple[int, int] = (-4, 4),
+                          attribute_constraints: Optional[Mapping[str, object]] = None):
+    """`similar_sounds` for sounds that unfold a little faster or slower than the query: the same window, masks and returned
+    list, compared by `CodeIndex.search_warped` -- every query column is matched to one item column, the item's time may
+    hold, step or skip from one query column to the next, and its drift against the query stays in drift=(lo, hi) top
+    columns.  `CodeIndex.warp_paths` gives the alignment of a returned item, `paste_warped` copies
+    codes along it."""
+    top_code = top_code.reshape(1, *top_code.shape[-2:])
+    if bottom_code is not None:
+        bottom_code = bottom_code.reshape(1, *bottom_code.shape[-2:])
+    top_frame, bottom_frame, mask_top, mask_bottom, two = _similar_window(index, top_code, bottom_code, mask, layer,
+                                                                          start_index_top)
+    device = index.device
+    indices, distances = index.search_warped(top_frame.to(device), bottom_frame.to(device) if two else None, mask_top=mask_top,
+                                             mask_bottom=mask_bottom, k=k, drift=drift,
+                                             attribute_constraints=attribute_constraints)
+    return _found_items(index, indices, distances)
+
+
+def _paste_indexed(sound: torch.Tensor, item: torch.Tensor, mask: torch.Tensor, columns: torch.Tensor,
+                   source: torch.Tensor) -> torch.Tensor:
+    """sound [1,F,T] with the cells under mask [1,F,len(columns)] taken from item [1,F,T_i]: sound column columns[c] from
+    item column source[c]; columns outside the sound or the item stay as they are."""
+    sound = sound.clone()
+    inside = (columns >= 0) & (columns < sound.shape[-1]) & (source >= 0) & (source < item.shape[-1])
+    chosen = mask.to(sound.device)[..., inside.to(sound.device)]
+    columns, source = columns[inside].to(sound.device), source[inside].to(sound.device)
+    sound[..., columns] = torch.where(chosen, item.to(sound.device, sound.dtype)[..., source], sound[..., columns])
+    return sound
+
+
+def paste_warped(top_code: torch.Tensor, bottom_code: torch.Tensor, item_top: torch.Tensor, item_bottom: torch.Tensor,
+                 mask: torch.Tensor, start_index_top: int, path, layer: str = 'top'):
+    """`paste_fragment` along a warped alignment: path [W] (`CodeIndex.warp_paths`) names, for the query column i that sits
+    at top column `start_index_top` + i of the sound, the item's top column p(i).  The cells under mask bool [1,F,W] (in
+    the resolution of `layer`; r W columns for the bottom layer) take the item's codes: top column start + i from item
+    column p(i), bottom columns r (start + i) + u from r p(i) + u, u < r.  A top-layer mask extends to the bottom layer as
+    in `paste_fragment`; columns outside the sound or the item stay as they are.  With path[i] = o + i this is
+    `paste_fragment` at shift_top = o, bit for bit.  Pure indexing: works on CPU tensors.  Returns the new (top, bottom)."""
+    if layer not in ('top', 'bottom'):
+        raise ValueError(f"unknown layer {layer}")
+    top_code, bottom_code = top_code.reshape(1, *top_code.shape[-2:]), bottom_code.reshape(1, *bottom_code.shape[-2:])
+    item_top, item_bottom = item_top.reshape(1, *item_top.shape[-2:]), item_bottom.reshape(1, *item_bottom.shape[-2:])
+    mask = mask.reshape(1, *mask.shape[-2:])
+    path = torch.as_tensor(path).reshape(-1).to('cpu', torch.int64)
+    ratio_t, ratio_f = bottom_code.shape[-1] // top_code.shape[-1], bottom_code.shape[-2] // top_code.shape[-2]
+    rows, width = (top_code.shape[-2], len(path)) if layer == 'top' else (bottom_code.shape[-2], ratio_t * len(path))
+    if mask.dtype != torch.bool or tuple(mask.shape[-2:]) != (rows, width):
+        raise ValueError(f"mask: expected bool [1, {rows}, {width}] over the path's {len(path)} columns in the {layer} "
+                         f"layer's resolution, got {mask.dtype} {tuple(mask.shape)}")
+    columns = torch.arange(len(path)) + int(start_index_top)
+    if layer == 'top':
+        top_code = _paste_indexed(top_code, item_top, mask, columns, path)
+        mask = mask.repeat_interleave(ratio_f, -2).repeat_interleave(ratio_t, -1)
+    else:
+        top_code = top_code.clone()
+    fine = torch.arange(ratio_t)
+    wide = lambda c: (ratio_t * c[:, None] + fine[None, :]).reshape(-1)               # noqa: E731
+    return top_code, _paste_indexed(bottom_code, item_bottom, mask, wide(columns), wide(path))
+
+
 def patch_from_database(index, top_code: torch.Tensor, bottom_code: torch.Tensor, mask: torch.Tensor, layer: str = 'top',
                         context_top: int = 4, k: int = 1, attribute_constraints: Optional[Mapping[str, object]] = None):
     """Fill a hole from the code database instead of sampling it: mask bool [1,F,T] in the resolution of `layer` over the

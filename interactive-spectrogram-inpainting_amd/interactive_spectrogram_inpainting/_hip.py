@@ -70,6 +70,11 @@ class isi_vqvae_out(C.Structure):
                 ("id_t", C.c_void_p), ("id_b", C.c_void_p), ("scalars", C.c_void_p)]
 
 
+class isi_warp_part(C.Structure):
+    _fields_ = [("codes", C.c_void_p), ("rows", C.c_void_p), ("weights", C.c_void_p),
+                ("F", C.c_int), ("r", C.c_int), ("K", C.c_int)]
+
+
 class isi_attn_args(C.Structure):
     _fields_ = [("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("rel_embeddings", C.c_void_p),
                 ("dense_mask", C.c_void_p), ("out", C.c_void_p),
@@ -275,6 +280,10 @@ SIGNATURES = {
     "isi_code_shift_search_f32": (C.c_int, [_P] * 5 + [C.c_int64] + [C.c_int] * 9 + [_P, C.c_size_t, _P]),
     "isi_code_shift_search_rows_f32": (C.c_int, [_P] * 4 + [C.c_int64] + [C.c_int] * 9 + [_P, C.c_size_t, _P]),
     "isi_code_shift_best_f32": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, _P]),
+    "isi_code_warp_search_f32": (C.c_int, [C.POINTER(isi_warp_part), C.c_int, _P, _P, _P, C.c_int64] + [C.c_int] * 5 + [_P]),
+    "isi_code_warp_path_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    "isi_code_warp_path_f32": (C.c_int, [C.POINTER(isi_warp_part), C.c_int, _P, C.c_int, _P, _P, _P, C.c_size_t, C.c_int64]
+                               + [C.c_int] * 5 + [_P]),
     "isi_rel_attention_f32": (C.c_int, [C.POINTER(isi_attn_args), _P]),
     "isi_rel_attention_workspace_bytes": (C.c_size_t, [C.POINTER(isi_attn_args)]),
     "isi_rel_attention_bwd_workspace_floats": (C.c_size_t, [C.POINTER(isi_attn_args)]),

@@ -24,7 +24,12 @@ tests/code_soft_search_spec.py): per cell a ROW of K floats takes the place of t
 
 through the same kernels with another stage, so a vector that is a codebook row gives the hard search's bits; any other
 per-cell cost can be handed over as ready rows.  No CPU path: the index, the VQ-VAE and the queries must live on the
-GPU."""
+GPU.
+
+All of the above compare column i of the query with column o + i of the item.  `search_warped` lets a sound unfold a
+little faster or slower (csrc/code_warp_search.hip; DESIGN.md section 6c.3, specification tests/code_warp_search_spec.py):
+query column i is matched to item column p(i), p(i+1) - p(i) in {0, 1, 2}, the drift p(i) - i inside a band, and the
+distance is the least sum of `search_soft`'s column costs over all such paths; `warp_paths` returns the paths."""
 from __future__ import annotations
 
 import ctypes as C
@@ -38,6 +43,8 @@ from ... import _hip
 
 MAX_QUERIES = 64          # isi_code_search_f32: 1 <= Q <= 64 per launch
 SHIFT_BUDGET_BYTES = 1 << 30      # search_shifted / distances_shifted: workspace + dist [Q, S, N] of one group of queries
+MAX_DRIFTS = 64           # isi_code_warp_search_f32: hi - lo + 1 <= 64
+MAX_PATH_ITEMS = 64       # isi_code_warp_path_f32: 1 <= M <= 64 per launch
 ROWS_BUDGET_BYTES = 1 << 28       # search_soft / search_shifted_soft: rows [Q, C, K] built from vectors, one group of queries
                                   # (a flagship bottom map is 8 MB of rows per query: 32 queries at a time)
 
@@ -652,3 +659,151 @@ class CodeIndex:
         jobs = [self._soft_job(*c) for c in checked]
         return self._best_over_shifts(self._shifted_groups(jobs, lo, count), jobs[0][2].shape[0], lo, count, allowed,
                                       n_allowed, k, all(job[5] for job in jobs))
+
+    # ---- time-warped search (csrc/code_warp_search.hip)
+    def _warp_plan(self, what: str, forms, masks, layer_weights, drift):
+        """Validation and geometry of a warped search, before any device work: (checked layers, lo, hi), the drift in the
+        columns of the first layer given."""
+        checked = self._soft_layers(what, forms, masks, layer_weights, window=True)
+        stored = self.top if checked[0][0] == 'top' else self.bottom
+        T, W = int(stored.shape[2]), int(checked[0][3].shape[2])
+        if len(checked) == 2:
+            self._check_two_layer_windows(W, int(checked[1][3].shape[2]), "the bottom window")
+        try:
+            lo, hi = (int(d) for d in drift)
+        except (TypeError, ValueError):
+            raise ValueError(f"drift: expected (lo, hi), got {drift}") from None
+        if lo > hi:
+            raise ValueError(f"drift {(lo, hi)}: lo must not exceed hi")
+        if hi - lo + 1 > MAX_DRIFTS:
+            raise ValueError(f"drift {(lo, hi)} holds {hi - lo + 1} drifts, a warped search takes at most {MAX_DRIFTS}")
+        if hi < 0 or lo > T - 1 or W - 1 + hi < 0 or W - 1 + lo > T - 1:
+            raise ValueError(f"drift {(lo, hi)} leaves the first or the last of {W} query columns without a column of the "
+                             f"stored {T}")
+        return checked, lo, hi
+
+    def _warp_rows(self, job, q0: int, q1: int):
+        """(rows fp32 [g, C, K], weights fp32 [g, C] or None) of one layer of a warped query: a code layer as rows gathered
+        from the code distance table, its mask-token cells under weight 0."""
+        layer, kind, payload, weights = job[:4]
+        w = None if weights is None else weights[q0:q1]
+        if kind != 'code':
+            return self._rows_of(job, q0, q1), w
+        table = self.table(layer)
+        K = table.shape[0]
+        query = payload[q0:q1].view(torch.int16).to(torch.int64).bitwise_and(0xFFFF)
+        token = query >= K
+        rows = table[torch.where(token, 0, query)].contiguous()
+        if w is None:
+            w = torch.ones(query.shape, dtype=torch.float32, device=self.device)
+        return rows, torch.where(token, 0.0, w).contiguous()
+
+    def _warp_group_size(self, jobs) -> int:
+        """Queries per launch so that the rows built or gathered for them stay under ROWS_BUDGET_BYTES (at least 1)."""
+        per_query = max([job[2].shape[1] * int((self.vqvae.quantize_t if job[0] == 'top' else self.vqvae.quantize_b).n_embed) * 4
+                         for job in jobs if job[1] != 'rows'] or [0])
+        return MAX_QUERIES if per_query == 0 else max(1, min(MAX_QUERIES, ROWS_BUDGET_BYTES // per_query))
+
+    def _warp_parts(self, jobs, q0: int, q1: int):
+        """(isi_warp_part array, T, W, the tensors it points into) of the queries q0 .. q1 - 1."""
+        ratio = 1 if len(jobs) == 1 else self.bottom.shape[2] // self.top.shape[2]
+        parts = (_hip.isi_warp_part * len(jobs))()
+        keep = []
+        for p, job in enumerate(jobs):
+            stored = self.top if job[0] == 'top' else self.bottom
+            rows, w = self._warp_rows(job, q0, q1)
+            keep += [rows, w]
+            parts[p].codes, parts[p].rows = stored.data_ptr(), rows.data_ptr()
+            parts[p].weights = None if w is None else w.data_ptr()
+            parts[p].F, parts[p].r, parts[p].K = int(stored.shape[1]), (ratio if p > 0 else 1), int(rows.shape[2])
+        first = self.top if jobs[0][0] == 'top' else self.bottom
+        return parts, int(first.shape[2]), int(jobs[0][4]), keep
+
+    def _warp_forms(self, top_code, bottom_code, top_vectors, bottom_vectors, top_rows, bottom_rows):
+        return (top_code, top_vectors, top_rows), (bottom_code, bottom_vectors, bottom_rows)
+
+    def distances_warped(self, top_code=None, bottom_code=None, *, top_vectors=None, bottom_vectors=None, top_rows=None,
+                         bottom_rows=None, mask_top=None, mask_bottom=None, layer_weights: Tuple[float, float] = (1., 1.),
+                         drift: Tuple[int, int] = (-4, 4), allowed: Optional[torch.Tensor] = None):
+        """(dist fp32 [Q, N], single): the warped distance of `search_warped` of every query to every item; +inf where
+        allowed[n] == 0."""
+        checked, lo, hi = self._warp_plan("search_warped", self._warp_forms(top_code, bottom_code, top_vectors, bottom_vectors,
+                                                                            top_rows, bottom_rows),
+                                          (mask_top, mask_bottom), layer_weights, drift)
+        jobs = [self._soft_job(*c) for c in checked]
+        lib, stream = _hip.lib(), C.c_void_p(_hip.stream_ptr(self.device))
+        Q, N = jobs[0][2].shape[0], len(self)
+        dist = torch.empty(Q, N, dtype=torch.float32, device=self.device)
+        group = self._warp_group_size(jobs)
+        for q0 in range(0, Q, group):
+            q1 = min(Q, q0 + group)
+            parts, T, W, keep = self._warp_parts(jobs, q0, q1)
+            _hip.check(lib.isi_code_warp_search_f32(parts, len(jobs), None if allowed is None else allowed.data_ptr(),
+                                                    dist[q0:q1].data_ptr(), None, N, T, W, lo, hi, q1 - q0, stream),
+                       "isi_code_warp_search_f32")
+            del keep
+        return dist, all(job[5] for job in jobs)
+
+    def search_warped(self, top_code=None, bottom_code=None, *, top_vectors=None, bottom_vectors=None, top_rows=None,
+                      bottom_rows=None, mask_top=None, mask_bottom=None, layer_weights: Tuple[float, float] = (1., 1.),
+                      k: int = 8, drift: Tuple[int, int] = (-4, 4),
+                      attribute_constraints: Optional[Mapping[str, object]] = None, exclude: Optional[Sequence[int]] = None):
+        """The k stored items nearest to a sound that may unfold a little faster or slower than the query:
+        (indices int64 [k], distances float32 [k]); [Q, k] each for Q > 1 queries.  Query column i is matched to one item
+        column p(i) with p(i+1) - p(i) in {0, 1, 2} and lo <= p(i) - i <= hi for drift=(lo, hi); every query column counts
+        once, and the distance is the least sum of column costs over all such paths (specification
+        tests/code_warp_search_spec.py).  A column's cost is `search_soft`'s sum over its cells.  Per layer give exactly one
+        of `*_code`, `*_vectors` or `*_rows`, as a whole map or as a window [F, W] of 1 <= W <= T columns (the bottom
+        window r = T_b / T_t times as wide as the top one); drift is measured in top columns whenever a top layer is
+        given, and hi - lo + 1 <= 64.  drift=(o, o) is the shifted search's alignment at offset o.  Masks, layer_weights,
+        the (distance, index) order, attribute_constraints, exclude, LookupError / ValueError / HipLibraryError and the
+        grouping of the queries under ROWS_BUDGET_BYTES are `search_soft`'s."""
+        if int(k) < 1:
+            raise ValueError(f"k must be at least 1, not {k}")
+        allowed = self.allowed(attribute_constraints, exclude)
+        dist, single = self.distances_warped(top_code, bottom_code, top_vectors=top_vectors, bottom_vectors=bottom_vectors,
+                                             top_rows=top_rows, bottom_rows=bottom_rows, mask_top=mask_top,
+                                             mask_bottom=mask_bottom, layer_weights=layer_weights, drift=drift, allowed=allowed)
+        values, order = self._nearest(dist, k, self._admitted(allowed, attribute_constraints, exclude))
+        return (order[0], values[0]) if single else (order, values)
+
+    def warp_paths(self, indices, top_code=None, bottom_code=None, *, top_vectors=None, bottom_vectors=None, top_rows=None,
+                   bottom_rows=None, mask_top=None, mask_bottom=None, layer_weights: Tuple[float, float] = (1., 1.),
+                   drift: Tuple[int, int] = (-4, 4)):
+        """The alignments behind `search_warped`'s distances: for items `indices` [k] (or [Q, k]) and the same query, the
+        item column p(i) matched to every query column, int64 [k, W] (or [Q, k, W]).  Among paths of equal cost the one
+        that prefers step over hold over skip, backtracked from the smallest end column."""
+        checked, lo, hi = self._warp_plan("warp_paths", self._warp_forms(top_code, bottom_code, top_vectors, bottom_vectors,
+                                                                         top_rows, bottom_rows),
+                                          (mask_top, mask_bottom), layer_weights, drift)
+        jobs = [self._soft_job(*c) for c in checked]
+        Q, N, single = jobs[0][2].shape[0], len(self), all(job[5] for job in jobs)
+        items = torch.as_tensor(indices)
+        if items.dtype.is_floating_point or items.dtype == torch.bool or items.dim() not in (1, 2) or items.numel() == 0 \
+                or (items.dim() == 2 and items.shape[0] != Q) or (items.dim() == 1 and Q != 1):
+            raise ValueError(f"indices: expected item indices [k] (or [{Q}, k] for {Q} queries), got "
+                             f"{items.dtype} {tuple(items.shape)}")
+        items = items.reshape(Q, -1).to(self.device, torch.int64)
+        if int(items.min()) < -N or int(items.max()) >= N:
+            raise IndexError(f"indices outside an index of {N} items")
+        items = items % N
+        lib, stream = _hip.lib(), C.c_void_p(_hip.stream_ptr(self.device))
+        W = int(jobs[0][4])
+        path = torch.empty(Q, items.shape[1], W, dtype=torch.int32, device=self.device)
+        group = self._warp_group_size(jobs)
+        for q0 in range(0, Q, group):
+            q1 = min(Q, q0 + group)
+            parts, T, _, keep = self._warp_parts(jobs, q0, q1)
+            for m0 in range(0, items.shape[1], MAX_PATH_ITEMS):
+                chosen = items[q0:q1, m0:m0 + MAX_PATH_ITEMS].contiguous()
+                M = chosen.shape[1]
+                out = torch.empty(q1 - q0, M, W, dtype=torch.int32, device=self.device)
+                dist = torch.empty(q1 - q0, M, dtype=torch.float32, device=self.device)
+                self._grow_workspace(lib.isi_code_warp_path_workspace_bytes(M, W, lo, hi, q1 - q0))
+                _hip.check(lib.isi_code_warp_path_f32(parts, len(jobs), chosen.data_ptr(), M, out.data_ptr(), dist.data_ptr(),
+                                                      self._workspace.data_ptr(), self._workspace.numel() * 4, N, T, W, lo, hi,
+                                                      q1 - q0, stream), "isi_code_warp_path_f32")
+                path[q0:q1, m0:m0 + M] = out
+            del keep
+        path = path.to(torch.int64)
+        return path[0] if single and torch.as_tensor(indices).dim() == 1 else path

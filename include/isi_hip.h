@@ -1155,15 +1155,23 @@ int isi_prior_sample_run_rows_bias(const isi_prior_w *w, const isi_prior_state *
  *   counts   [K] int32  histogram of idx (caller zeroes; accumulated)
  *   sse_part [isi_vq_num_partials(N)] fp32 per-workgroup sum (e_idx - z)^2
  * Requirements: D in {8,16,32,64}; with Kp = K rounded up to 32: Kp*(D+4)*4 + Kp*8 <= 150 KiB
- * (the LDS image is padded with rows that can never win). */
+ * (the LDS image is padded with rows that can never win).
+ * A vector with a non-finite component gets idx -1 and q = NaN, is not counted, and makes its workgroup's partial NaN.
+ * A code vector with a non-finite component (its e2 is +inf or NaN) never wins: its distance is not below +inf, and the
+ * matrix pipe confines it to its own row, so every other code ranks as if it were absent (what isi_vq_nearest_topm_f32
+ * documents for the same stage); a codebook of such codes alone answers every vector with -1.
+ * Refused on the host before any launch: a null pointer, N <= 0, K <= 0, z, codes_kd or q_out not 16-byte aligned
+ * (ISI_E_INVALID); another D, or a codebook beyond the LDS bound above (ISI_E_UNSUPPORTED). */
 int isi_vq_nearest_f32(const float *z, const float *codes_kd, const float *e2,
                        int64_t *idx_out, float *q_out, int32_t *counts,
                        float *sse_part, int64_t N, int D, int K, void *stream);
 /* Same, with a flag word: ISI_CONV_F16X3 computes z.e_k with split-f16 products (three f16 MFMA terms, per-product
- * error ~2^-23; |z| < 16384, |e| < 64) when D == 64 and the codebook's two f16 planes fit in LDS (K <= 512), five
- * times fewer matrix-pipe cycles than the exact-fp32 products that bound isi_vq_nearest_f32.  0 = exact.
- * A vector with a non-finite component (or distances) gets idx -1, q = NaN, and makes the squared error NaN; so does
- * every vector when a code vector is not finite.  FINITE code vectors beyond the range (|e| >= 64: the unused codes of a
+ * error ~2^-23; |z| < 16384, |e| < 64) when D == 64 and the codebook's two f16 planes fit in LDS -- with Kp = K rounded
+ * up to 32: Kp*264 + Kp/8 + 48 bytes <= 150 KiB, that is K <= 576 --, five times fewer matrix-pipe cycles than the
+ * exact-fp32 products that bound isi_vq_nearest_f32.  0 = exact; so is the flag at another D or a larger K, which the
+ * exact kernel's own bound then refuses (K > 544 at D = 64).
+ * On the split-f16 route a vector with a non-finite component or one beyond the range (|z| >= 16384) gets idx -1,
+ * q = NaN, and makes the squared error NaN; so does every vector when a code vector is not finite.  FINITE code vectors beyond the range (|e| >= 64: the unused codes of a
  * trained codebook) are exact: they are kept out of the f16 search and the fp32 decision proves per vector that none of
  * them can win ((min |e_far| - |z|)^2 > winner's distance) or compares the winner with each of them in fp32. */
 int isi_vq_nearest_flags_f32(const float *z, const float *codes_kd, const float *e2,

@@ -26,7 +26,7 @@ import vq_topm_spec as S
 pytestmark = pytest.mark.gpu
 
 RECORD = []
-SHAPES = [(64, 512), (64, 77), (8, 40)]
+SHAPES = [(64, 512), (64, 77), (8, 40), (32, 77), (16, 200)]
 SIZES = [1, 33, 257, 20011]
 RANKS = [1, 2, 5, 8]
 

@@ -1248,18 +1248,37 @@ def _vq_fused_eval(a0, a1, W, bias, embed, dtype):
     lost = ~torch.isfinite(a).all(dim=1) | (a.abs() >= VQ_FUSED_ACT_LIMIT).any(dim=1)
     if not bool(torch.isfinite(embed).all()):
         lost[:] = True
-    live = ~lost
     z = torch.where(lost[:, None], torch.zeros_like(a), a).to(dtype) @ W.to(dtype).t()
     if bias is not None:
         z = z + torch.as_tensor(bias).detach().cpu().to(dtype)
+    return _vq_search_eval(z, embed, lost, dtype)
+
+
+def _vq_search_eval(z, embed, lost, dtype):
+    """The search half of both specifications: VqFusedSpec of vectors z [N, D] (already of `dtype`) on embed [D, K]; `lost`
+    [N] bool are the vectors the route gives up before it searches.  A code with a non-finite component takes no part (its
+    distance is never below +inf) and the other codes rank as if it were absent; a vector left without a finite distance is
+    lost as well.  Lost vectors: idx -1, q and z NaN, not counted, sse NaN."""
+    N, (D, K) = z.shape[0], embed.shape
     e = embed.to(dtype).t().contiguous()
+    absent = ~torch.isfinite(e).all(dim=1)
+    if bool(absent.any()):
+        e_rank = e.clone()
+        e_rank[absent] = float("inf")                       # (inf - z)^2 = inf: behind every finite distance
+        lost = lost | ~torch.isfinite(z).all(dim=1)
+        if bool(absent.all()):
+            lost = torch.ones_like(lost)
+    else:
+        e_rank = e
+    live = ~lost
     idx = torch.full((N,), -1, dtype=torch.int64)
     q = torch.full((N, D), float("nan"), dtype=dtype)
     sse_rows = torch.full((N,), float("nan"), dtype=dtype)
     if bool(live.any()):
-        idx[live] = _vq_fused_top2(z[live], e)[1][:, 0]
+        idx[live] = _vq_fused_top2(z[live], e_rank)[1][:, 0]
         q[live] = e[idx[live]]
         sse_rows[live] = (q[live] - z[live]).pow(2).sum(dim=1)
+    z = z.clone()
     z[lost] = float("nan")
     counts = torch.bincount(idx[live], minlength=K)
     sse = sse_rows.sum()
@@ -1554,6 +1573,298 @@ def vq_fused_hold_sse(sse_part, spec, what):
     assert not bool(torch.isnan(sse_part).any()), f"{what}: {int(torch.isnan(sse_part).sum())} partials were not written"
     assert abs(total - float(spec.sse)) <= VQ_FUSED_SSE_RTOL * float(spec.sse), \
         f"{what}: summed squared error {total!r} against the spec's {float(spec.sse)!r}"
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The stand-alone codebook searches (vq_nearest_kernel<D> and vq_nearest_f16x3_kernel of csrc/vq_nearest.hip with the shared
+# distance stage of csrc/vq_dist.h, through isi_vq_nearest_f32 / isi_vq_nearest_flags_f32) and pack_codebook_kernel of
+# csrc/pack.hip: the search half of the fused specification applied to a GIVEN z, the loss rules of each route, K_max from
+# the two LDS formulas, seeded case data free of near-ties, and the case table of tests/test_vq_search_gpu.py --
+# tests/test_vq_search_host.py shows, without a GPU, what it relies on.  z [N, D], embed [D, K].
+VQ_EXACT, VQ_F16X3 = "exact", "f16x3"
+VQ_SEARCH_DIMS = (8, 16, 32, 64)
+VQ_SEARCH_ROUTES = tuple((VQ_EXACT, D) for D in VQ_SEARCH_DIMS) + ((VQ_F16X3, 64),)
+VQ_LDS_BUDGET = 150 * 1024     # kVqLdsBudget
+VQ_SEARCH_WAVES = 8            # ISI_VQ_WAVES
+VQ_SEARCH_SECOND_PASS_N = VQ_FUSED_GRID * VQ_FUSED_TILE + 257     # workgroups 0 and 1 run a second pass, the second one ragged
+VqSearchCase = collections.namedtuple("VqSearchCase", "route D K N kind")
+VqSearchRefs = collections.namedtuple("VqSearchRefs", "z embed alias frozen spec f32")
+
+
+def vq_search_lost(z, embed, route):
+    """[N] bool, the vectors a route gives up (include/isi_hip.h, "quantization").  Exact: a non-finite component.  f16x3:
+    also a component beyond the pieces' range (|z| >= 16384), and every vector when a code is not finite."""
+    z, embed = torch.as_tensor(z).detach().cpu(), torch.as_tensor(embed).detach().cpu()
+    lost = ~torch.isfinite(z).all(dim=1)
+    if route == VQ_F16X3:
+        lost = lost | (z.abs() >= VQ_FUSED_ACT_LIMIT).any(dim=1)
+        if not bool(torch.isfinite(embed).all()):
+            lost = torch.ones_like(lost)
+    else:
+        assert route == VQ_EXACT, route
+    return lost
+
+
+def _vq_search(z, embed, route, dtype):
+    z, embed = torch.as_tensor(z).detach().cpu(), torch.as_tensor(embed).detach().cpu()
+    return _vq_search_eval(z.to(dtype), embed, vq_search_lost(z, embed, route), dtype)
+
+
+def vq_search_spec(z, embed, route=VQ_EXACT):
+    """VqFusedSpec of a stand-alone search, everything float64: the search half of vq_fused_spec (_vq_search_eval) on the
+    given z, with the route's loss rules (vq_search_lost).  On the exact route a non-finite code never wins and the other
+    codes rank as if it were absent."""
+    return _vq_search(z, embed, route, torch.float64)
+
+
+def vq_search_f32(z, embed, route=VQ_EXACT):
+    """The same in float32 torch: what the host tests apply their simulated defects to."""
+    return _vq_search(z, embed, route, torch.float32)
+
+
+def vq_search_lds_bytes(D, Kp, split):
+    """vq_exact_lds_bytes<D> (csrc/vq_dist.h) or, `split`, vq_planes_lds_bytes (csrc/vq_nearest.hip) of Kp padded codes."""
+    if split:
+        assert D == 64
+        return Kp * 64 * 2 * 2 + (2 * Kp + VQ_SEARCH_WAVES + 1 + Kp // 32 + 3) * 4
+    return (Kp * (D + 4) + 2 * Kp + VQ_SEARCH_WAVES) * 4
+
+
+def vq_search_k_max(D, split=False):
+    """The largest K whose LDS image (K rounded up to the 32-code tile) stays within the 150 KiB budget: 2720, 1728, 992 and
+    544 for the exact route at D = 8, 16, 32, 64; 576 for the split-f16 route.  The GPU test holds the library to it."""
+    Kp = 32
+    assert vq_search_lds_bytes(D, Kp, split) <= VQ_LDS_BUDGET
+    while vq_search_lds_bytes(D, Kp + 32, split) <= VQ_LDS_BUDGET:
+        Kp += 32
+    return Kp
+
+
+def vq_search_gaps(z, embed, alias=None):
+    """vq_fused_gaps of given vectors, for data with non-finite entries: a non-finite code takes no part (as in the spec), a
+    non-finite vector has the gap NaN."""
+    z, embed = _f64(z), _f64(embed).clone()
+    embed[:, ~torch.isfinite(embed).all(dim=0)] = float("inf")
+    bad = ~torch.isfinite(z).all(dim=1)
+    gaps = vq_fused_gaps(torch.where(bad[:, None], torch.zeros_like(z), z), embed, alias)
+    gaps[bad] = float("nan")
+    return gaps
+
+
+def _vq_search_draw(n, D, gen):
+    return 0.8 * torch.randn(n, D, generator=gen)
+
+
+def vq_search_settle(z, embed, gen, alias=None, frozen=None, min_gap=VQ_FUSED_MIN_GAP):
+    """Redraws every vector whose gap (vq_search_gaps) is below min_gap until none remains; `frozen` [N] bool: rows a case
+    placed by hand, never redrawn (tests/test_vq_search_host.py asserts their gaps).  Returns the settled copy.
+    Why 1e-4 suffices on the split-f16 route as well: its ranking truncates 2^-19 of a distance and adds a margin of 2^-20
+    |z|^2, a distance is at most 2 (|z|^2 + |e|^2), so the ranking moves a distance by less than 2^-18 + 2^-20 = 4.8e-6 of
+    |z|^2 + |e|^2 -- a gap of 1e-4 of that keeps the true best code among the two candidates, and strictly first in the
+    fp32 decision (rounding ~2^-22), with more than twenty times to spare.  No index may differ."""
+    z = z.clone()
+    rows = torch.arange(z.shape[0]) if frozen is None else (~frozen).nonzero().reshape(-1)
+    for _ in range(64):
+        if rows.numel() == 0:
+            return z
+        rows = rows[vq_search_gaps(z[rows], embed, alias) < min_gap]
+        z[rows] = _vq_search_draw(rows.numel(), z.shape[1], gen)
+    raise AssertionError("vq_search_settle: near-ties remain after 64 redraws")
+
+
+VQ_SEARCH_KINDS = ("plain", "edges", "dups", "lost", "badcode", "far_certified", "far_scan", "far_pad", "far_all")
+VQ_SEARCH_EDGE_ROWS = {"code": 2, "zero": 9, "tiny": 20}      # a row equal to code K // 2, the zero vector, a row of norm 1e-3
+VQ_SEARCH_DUP_ROWS = (1, 34, 256)                             # rows laid exactly on the duplicated codes (256: the ragged tile)
+VQ_SEARCH_LOST_ROWS = {3: float("nan"), 40: float("inf"), 599: float("-inf")}   # row -> the value of one of its components
+VQ_SEARCH_LOUD_ROW, VQ_SEARCH_LOUD_CODE = 70, 17              # a finite row with a component of 3e4, and its nearest code
+VQ_SEARCH_BAD_CODES = {10: float("inf"), 37: float("nan"), -1: float("-inf")}   # code -> one component (-1: the last code)
+VQ_SEARCH_FAR_ROWS = {"far_scan": VQ_FUSED_FAR_PIXELS, "far_pad": {11: 98}}     # hand-placed row -> the far code nearest to it
+
+
+def vq_search_dup_layout(K):
+    """(sources, copies per source): VQ_FUSED_DUP_* where K allows, else an analogue of the same structure -- per source a
+    copy in the other lane half of the same 32-row tile (bit 2 of the row differs) and one in another tile, both at higher
+    indices."""
+    if K > max(max(c) for c in VQ_FUSED_DUP_COPIES):
+        return VQ_FUSED_DUP_SOURCES, VQ_FUSED_DUP_COPIES
+    if K >= 96:
+        return (3, 40), ((7, 68), (44, 75))
+    assert K >= 64, K
+    return (3, 9), ((7, 35), (13, 41))
+
+
+def vq_search_case_seed(c):
+    """(Not a function of the route: the two routes of D = 64 search the same data.)"""
+    return ((c.D * 4099 + c.K) * 70001 + c.N) * 16 + VQ_SEARCH_KINDS.index(c.kind)
+
+
+def vq_search_case_data(c):
+    """(z [N, D], embed [D, K], alias or None, frozen [N] bool) float32 on the CPU, seeded: codes ~ N(0, 0.7^2), vectors
+    ~ N(0, 0.8^2) (at most 0.3 % of such rows have a gap below 1e-4 at any (D, K) of the table), the kind's hand-placed rows
+    and codes, then every other row settled (vq_search_settle).
+      plain          nothing placed
+      edges          a row equal to a code bit for bit, the zero vector, a row of norm 1e-3 (the LDS image's padding rows are
+                     zero vectors: with anything but a losing |e|^2 they would win the last two); the code of the smallest
+                     norm is shrunk by 0.9 so that the origin has no near-tie
+      dups           vq_search_dup_layout; VQ_SEARCH_DUP_ROWS lie exactly on the duplicated codes
+      lost           VQ_SEARCH_LOST_ROWS hold NaN, +Inf, -Inf; row VQ_SEARCH_LOUD_ROW is finite with a component of 3e4, beyond
+                     the split-f16 route's range -- the exact route answers it: code VQ_SEARCH_LOUD_CODE has 6.0 there, which
+                     puts it 6e4 (6 - 1.8) / 9e8 = 2.8e-4 of |z|^2 in front of every other code
+      badcode        VQ_SEARCH_BAD_CODES: three codes with a non-finite component, one of them in the padded last tile
+      far_certified  ten codes scaled by 3e4: the certificate of vq_decide_f32 holds for every row
+      far_scan       the constructions of vq_fused_far_case_data: 40 dead codes, a code at 1e5 times its neighbour, and the
+                     two rows of VQ_FUSED_FAR_PIXELS, which the fp32 scan decides
+      far_pad        a far code of moderate norm in the padded last tile (K = 100: code 98) with row 11 next to it, code 99 dead
+      far_all        every code is far (scaled by 1e3): no candidate at all, the scan answers every row"""
+    D, K, N, kind = c.D, c.K, c.N, c.kind
+    gen = torch.Generator().manual_seed(vq_search_case_seed(c))
+    embed = 0.7 * torch.randn(D, K, generator=gen)
+    z = _vq_search_draw(N, D, gen)
+    frozen, alias = torch.zeros(N, dtype=torch.bool), None
+
+    def far_pair(row, code, comp=3):       # a far code of moderate norm and a row next to it
+        embed[:, code] = 0.0
+        embed[comp, code] = 200.0
+        z[row] = 0.0
+        z[row, comp] = 198.0
+        frozen[row] = True
+
+    if kind == "edges":
+        assert N >= 33 and K >= 2
+        embed[:, embed.pow(2).sum(dim=0).argmin()] *= 0.9
+        v = torch.randn(D, generator=gen)
+        z[VQ_SEARCH_EDGE_ROWS["code"]] = embed[:, K // 2]
+        z[VQ_SEARCH_EDGE_ROWS["zero"]] = 0.0
+        z[VQ_SEARCH_EDGE_ROWS["tiny"]] = 1e-3 * v / v.norm()
+        frozen[list(VQ_SEARCH_EDGE_ROWS.values())] = True
+    elif kind == "dups":
+        sources, copies = vq_search_dup_layout(K)
+        alias = torch.arange(K)
+        for src, cs, row in zip(sources, copies, VQ_SEARCH_DUP_ROWS):
+            for k in cs:
+                assert src < k < K
+                embed[:, k] = embed[:, src]
+                alias[k] = src
+            z[row] = embed[:, src]
+            frozen[row] = True
+    elif kind == "lost":
+        assert N > max(VQ_SEARCH_LOST_ROWS) and K > VQ_SEARCH_LOUD_CODE and D >= 8
+        embed[5, VQ_SEARCH_LOUD_CODE] = 6.0
+        for comp, (row, value) in zip((1, D - 1, 0), VQ_SEARCH_LOST_ROWS.items()):
+            z[row, comp] = value
+            frozen[row] = True
+        z[VQ_SEARCH_LOUD_ROW, 5] = 3.0e4
+        frozen[VQ_SEARCH_LOUD_ROW] = True
+    elif kind == "badcode":
+        for comp, (code, value) in zip((2, 0, 1), VQ_SEARCH_BAD_CODES.items()):
+            embed[comp, code] = value
+    elif kind == "far_certified":
+        embed[:, 130:140] *= 3.0e4
+    elif kind == "far_scan":
+        assert D == 64 and K == 512
+        embed[:, 300:340] *= 3.0e4
+        embed[:, 17] = embed[:, 16] * 1.0e5
+        z[5] = 0.0
+        z[5, 7] = 70.0
+        embed[:, 200] = z[5]
+        frozen[5] = True
+        far_pair(11, 320)
+    elif kind == "far_pad":
+        assert D == 64 and K == 100
+        far_pair(11, 98)
+        embed[:, 99] *= 3.0e4
+    elif kind == "far_all":
+        embed *= 1.0e3
+    else:
+        assert kind == "plain", kind
+    return vq_search_settle(z, embed, gen, alias, frozen), embed, alias, frozen
+
+
+@functools.lru_cache(maxsize=None)
+def vq_search_case_refs(c):
+    """VqSearchRefs of a case -- its data, the float64 spec and the float32 evaluation on the case's route -- computed once
+    per process and left unchanged."""
+    z, embed, alias, frozen = vq_search_case_data(c)
+    return VqSearchRefs(z, embed, alias, frozen, vq_search_spec(z, embed, c.route), vq_search_f32(z, embed, c.route))
+
+
+def _vq_search_table():
+    cases = []
+    for route, D in VQ_SEARCH_ROUTES:
+        split = route == VQ_F16X3
+        # K: one code, one ragged tile, around one tile, 2 tiles (an even count), 3 tiles (odd), 4 tiles with a ragged last
+        # one, 5 tiles, (f16x3: 545, beyond what the exact route accepts at D = 64,) and the route's K_max
+        ks = (1, 5, 31, 32, 33, 64, 96, 100, 160) + ((545,) if split else ()) + (vq_search_k_max(D, split),)
+        cases += [VqSearchCase(route, D, K, 257, "plain") for K in ks]
+        cases += [VqSearchCase(route, D, 100, N, "plain") for N in (1, 31, 32, 33, 255, 256)]
+        cases += [VqSearchCase(route, D, 100, 257, "edges"), VqSearchCase(route, D, 96, 257, "dups"),
+                  VqSearchCase(route, D, 100, 600, "lost"), VqSearchCase(route, D, 100, 257, "badcode")]
+        if D == 64:
+            cases += [VqSearchCase(route, D, 64, 257, "dups"), VqSearchCase(route, D, 512, 257, "dups")]
+    # the second grid-stride pass, one per route (their float64 specs take seconds on the CPU)
+    cases += [VqSearchCase(VQ_EXACT, 8, 33, VQ_SEARCH_SECOND_PASS_N, "plain"), VqSearchCase(VQ_F16X3, 64, 96, VQ_SEARCH_SECOND_PASS_N, "plain")]
+    cases += [VqSearchCase(VQ_F16X3, 64, 160, 257, "far_certified"), VqSearchCase(VQ_F16X3, 64, 512, 257, "far_scan"),
+              VqSearchCase(VQ_F16X3, 64, 100, 257, "far_pad"), VqSearchCase(VQ_F16X3, 64, 5, 257, "far_all")]
+    return cases
+
+
+VQ_SEARCH_CASES = _vq_search_table()
+
+
+def vq_search_case_id(c):
+    return f"{c.route}-D{c.D}-K{c.K}-N{c.N}-{c.kind}"
+
+
+def vq_search_coverage_gaps(cases):
+    """What a case table lacks of the corners the stand-alone searches have (an empty list: nothing): per route and D tile
+    counts 1 to 5 (3 and 5: the odd exit of the split-f16 tile pipeline and the prefetch behind an odd last tile), the
+    route's K_max, a ragged last tile, vector counts on both sides of a wave's 32 and a workgroup's 256, every data kind
+    the route has; per route a second grid-stride pass; on the split-f16 route 545 codes and the four far-code kinds."""
+    lack = []
+    for route, D in VQ_SEARCH_ROUTES:
+        mine = [c for c in cases if (c.route, c.D) == (route, D)]
+        name = f"{route} D={D}"
+        tiles = {(c.K + 31) // 32 for c in mine}
+        lack += [f"{name}: no codebook of {t} tiles" for t in (1, 2, 3, 4, 5) if t not in tiles]
+        ks, ns = {c.K for c in mine}, {c.N for c in mine}
+        if vq_search_k_max(D, route == VQ_F16X3) not in ks:
+            lack.append(f"{name}: K_max is missing")
+        if not any(K % 32 and K > 32 for K in ks):
+            lack.append(f"{name}: no ragged last tile behind a full one")
+        lack += [f"{name}: no launch of {n} vectors" for n in (1, 31, 32, 33, 255, 256, 257) if n not in ns]
+        kinds = {c.kind for c in mine}
+        lack += [f"{name}: no case of kind {k}" for k in ("plain", "edges", "dups", "lost", "badcode") if k not in kinds]
+    for route in (VQ_EXACT, VQ_F16X3):
+        if not any(c.route == route and -(-c.N // VQ_FUSED_TILE) > VQ_FUSED_GRID and c.N % VQ_FUSED_TILE for c in cases):
+            lack.append(f"{route}: no second grid-stride pass with a ragged tile")
+    split = [c for c in cases if c.route == VQ_F16X3]
+    if not any(c.K > vq_search_k_max(64) for c in split):
+        lack.append("f16x3: no codebook beyond the exact route's K_max")
+    lack += [f"f16x3: no case of kind {k}" for k in ("far_certified", "far_scan", "far_pad", "far_all") if k not in {c.kind for c in split}]
+    for c in cases:
+        if c.kind in ("dups",) and c.N != 257 or c.kind == "edges" and c.N < 33 or c.kind == "lost" and c.N <= max(VQ_SEARCH_LOST_ROWS):
+            lack.append(f"{vq_search_case_id(c)}: too few vectors for its hand-placed rows")
+    return lack
+
+
+def vq_pack_codebook_spec(embed):
+    """(codes [K, D]: the transpose, bit for bit; e2 [K, 1] float64: |e_k|^2) of isi_pack_codebook_f32 on embed [D, K]."""
+    e = torch.as_tensor(embed).detach().cpu()
+    return e.t().contiguous(), _f64(e).pow(2).sum(dim=0).reshape(-1, 1)
+
+
+def vq_pack_codebook_f32(embed, exchanged=False):
+    """|e_k|^2 [K, 1] as a float32 sum over d in sequence, the yardstick of e2.  Mutant `exchanged`: element (d, k) read at
+    d * D + k -- D and K exchanged in the index (K >= D keeps it inside the array)."""
+    e = torch.as_tensor(embed).detach().cpu().float()
+    D, K = e.shape
+    if exchanged:
+        assert K >= D
+        e = e.reshape(-1)[(torch.arange(D)[:, None] * D + torch.arange(K)[None, :])]
+    s = torch.zeros(K)
+    for d in range(D):
+        s = s + e[d] * e[d]
+    return s.reshape(-1, 1)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

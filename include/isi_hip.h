@@ -83,6 +83,28 @@ int isi_spec_to_stft_bwd_f32(const float *a, const float *ph, const float *dx, f
                              int64_t rows, int F, int mel, void *stream);
 int isi_spec_inverse_prepare_bwd_f32(const float *spec, const float *da, const float *dph,
                                      float *dspec, int B, int T, int F, void *stream);
+/* Phase-locked splice (not in the reference): keep an original sound's own STFT frames where w == 0 and, inside every
+ * run of frames with w > 0, continue the original's phase with the decoded phase increments.  Per (b, k) row, with
+ * phi_o = angle and Ao = modulus of the original's bin, psi = ph, As = isi_spec_to_stft's magnitude of `a` under `mel`,
+ * a run = a maximal range [t0, t1) of frames with w > 0, wrap = principal value in (-pi, pi]:
+ *   w == 0:            out = the original's two floats, bit for bit
+ *   both neighbours:   c = wrap(phi_o[t1] - phi_o[t0-1] - (psi[t1] - psi[t0-1])) / (t1 - t0 + 1)
+ *                      phi[t] = phi_o[t0-1] + (psi[t] - psi[t0-1]) + (t - t0 + 1) c
+ *   t0 == 0 only:      phi[t] = phi_o[t1] - (psi[t1] - psi[t])
+ *   t1 == T only:      phi[t] = phi_o[t0-1] + (psi[t] - psi[t0-1])
+ *   the whole row:     phi[t] = psi[t]; with w == 1 the bits isi_spec_to_stft_f32 writes
+ *   magnitude:         As where w == 1, else exp((1 - w) log Ao + w log As); 0 when Ao or As is not positive
+ *   out = magnitude (cos phi | sin phi)
+ * stft_orig, stft_out [B,T,2F]; a, ph [B,T,F]; w [w_batch,T,F], w_batch 1 or B, weights in [0, 1] (anything not > 0
+ * counts as 0).  Inputs and output must not overlap.
+ * isi_spec_splice_blend: g[n] = share of the squared periodic-Hann analysis window, over the frames t of [0, T_frames)
+ * that reach sample n with a non-zero window value (0 < n + n_fft - hop - t hop < n_fft), that belongs to frames with
+ * touched[b,t] != 0; out[n] = orig[n] bit for bit where g == 0, else orig[n] + g (ola[n] - orig[n]).  g is exactly 1
+ * where every such frame is touched.  audio_* [B,L], touched [B,T_frames] bytes; hop must divide n_fft. */
+int isi_spec_splice_f32(const float *stft_orig, const float *a, const float *ph, const float *w, int w_batch,
+                        float *stft_out, int B, int T, int F, int mel, void *stream);
+int isi_spec_splice_blend_f32(const float *audio_orig, const float *audio_ola, const unsigned char *touched,
+                              float *audio_out, int B, int T_frames, int n_fft, int hop, int64_t L, void *stream);
 /* One scale of the multi-scale spectral loss (reference utils/losses/spectral.py:78-118, where the STFTs come
  * from torch.stft): xp / xt = STFT rows [B*T][RS] (re block | im block of F bins, RS >= 2F) of the predicted and
  * the target audio.  fwd: per (sample, chunk of rows_per_block frames) the sums

@@ -9,6 +9,8 @@ flask_server.py:242-244,596,1016):
                           mel_break_frequency_hertz, mel_bin_width_threshold_factor)
         .to(device)  .to_spectrogram(audio [B, L]) -> [B, 2, n_fft/2, T]
         .to_audio(spec [B, 2, n_fft/2, T]) -> [B, T * hop]        .fs_hz
+        .to_audio_spliced(spec, original_audio [B, T * hop], weights [1 or B, T, n_fft/2]) -> [B, T * hop]
+            (not in the reference: the original's own samples outside an edited region, csrc/spec_splice.hip)
 
 Arithmetic = the published GANSynth representation (specification and parity status:
 oracle/spectrogram_oracle.py — the original package is absent, parity unpinned).
@@ -175,6 +177,62 @@ class SpectrogramsHelper:
         _hip.check(L.isi_overlap_add_f32(frames.data_ptr(), audio.data_ptr(), B, T, self.n_fft, self.hop_length,
                                          self.n_fft - self.hop_length, n_out, _s(spec)), "isi_overlap_add_f32")
         return audio, ((spec, a, ph) if keep else None)
+
+    @torch.no_grad()
+    def to_audio_spliced(self, spec: torch.Tensor, original_audio: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
+        """`to_audio(spec)` inside an edited region, the original's own samples outside it, coherent at both seams.
+
+        spec [B, 2, F, T], original_audio [B, T * hop], weights [1 or B, T, n_fft / 2] in [0, 1] over LINEAR bins (0: the
+        original, above 0: regenerated) -> [B, T * hop].  The original's STFT keeps its frames where the weight is 0; inside
+        every run of frames with a positive weight the phase continues the original's with the decoded phase increments and
+        meets it again at the run's far end (isi_spec_splice_f32, csrc/spec_splice.hip).  The STFT carries the
+        n_fft / hop - 1 frames past T that the last samples' overlap sums need: they come from the zero-padded original,
+        so a hole near the end meets complete sums.  The representation drops the DC bin, so the samples no regenerated
+        frame reaches are copied from the original, and the others are blended by the regenerated frames' share of the
+        squared window (isi_spec_splice_blend_f32).  No gradient."""
+        _hip.require_gpu(spec, "spectrogram")
+        _hip.require_gpu(original_audio, "original_audio")
+        _hip.require_gpu(weights, "weights")
+        c = self._build(spec.device)
+        spec = spec.float().contiguous()
+        B, two, F, T = spec.shape
+        N, hop = self.n_fft, self.hop_length
+        if two != 2 or F != self.n_bins:
+            raise ValueError(f"expected [B, 2, {self.n_bins}, T], got {tuple(spec.shape)}")
+        n_out = T * hop
+        if original_audio.dtype != torch.float32 or tuple(original_audio.shape) != (B, n_out):
+            raise ValueError(f"original_audio: expected float32 [{B}, {n_out}], got {original_audio.dtype} "
+                             f"{tuple(original_audio.shape)}")
+        if weights.dtype != torch.float32 or weights.dim() != 3 or weights.shape[0] not in (1, B) \
+                or tuple(weights.shape[1:]) != (T, F):
+            raise ValueError(f"weights: expected float32 [1 or {B}, {T}, {F}], got {weights.dtype} {tuple(weights.shape)}")
+        original_audio, weights = original_audio.contiguous(), weights.contiguous()
+        L = _hip.lib()
+        extra = N // hop - 1
+        X_all, T_all = self._stft(torch.nn.functional.pad(original_audio, (0, extra * hop)))   # [B, T + extra, 2F]
+        assert T_all == T + extra
+        X_orig = X_all[:, :T].contiguous()
+        a = torch.empty(B, T, F, dtype=torch.float32, device=spec.device)
+        ph = torch.empty_like(a)
+        _hip.check(L.isi_spec_inverse_prepare_f32(spec.data_ptr(), a.data_ptr(), ph.data_ptr(), B, T, F, _s(spec)),
+                   "isi_spec_inverse_prepare_f32")
+        a, ph = self._unproject(a, ph)
+        X = torch.empty(B, T, 2 * F, dtype=torch.float32, device=spec.device)
+        _hip.check(L.isi_spec_splice_f32(X_orig.data_ptr(), a.data_ptr(), ph.data_ptr(), weights.data_ptr(),
+                                         weights.shape[0], X.data_ptr(), B, T, F, int(self.mel), _s(spec)),
+                   "isi_spec_splice_f32")
+        X_all = torch.cat([X, X_all[:, T:]], 1)
+        frames = _gemm.linear(X_all, c["istft_w"], None, N)                 # [B, T + extra, n_fft]
+        ola = torch.empty(B, n_out, dtype=torch.float32, device=spec.device)
+        _hip.check(L.isi_overlap_add_f32(frames.data_ptr(), ola.data_ptr(), B, T_all, N, hop, N - hop, n_out, _s(spec)),
+                   "isi_overlap_add_f32")
+        touched = torch.zeros(B, T_all, dtype=torch.uint8, device=spec.device)
+        touched[:, :T] = (weights > 0).any(-1)
+        audio = torch.empty_like(ola)
+        _hip.check(L.isi_spec_splice_blend_f32(original_audio.data_ptr(), ola.data_ptr(), touched.data_ptr(),
+                                               audio.data_ptr(), B, T_all, N, hop, n_out, _s(spec)),
+                   "isi_spec_splice_blend_f32")
+        return audio
 
     def _to_audio_backward(self, saved, d_audio: torch.Tensor) -> torch.Tensor:
         spec, a, ph = saved

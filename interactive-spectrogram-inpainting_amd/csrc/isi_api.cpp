@@ -310,6 +310,14 @@ int isi_overlap_add_f32(const float *frames, float *audio, int B, int T, int n_f
                         void *stream) {
   return overlap_add_f32(frames, audio, B, T, n_fft, hop, left, L, S(stream));
 }
+int isi_spec_splice_f32(const float *stft_orig, const float *a, const float *ph, const float *w, int w_batch, float *stft_out,
+                        int B, int T, int F, int mel, void *stream) {
+  return spec_splice_f32(stft_orig, a, ph, w, w_batch, stft_out, B, T, F, mel, S(stream));
+}
+int isi_spec_splice_blend_f32(const float *audio_orig, const float *audio_ola, const uint8_t *touched, float *audio_out, int B,
+                              int T_frames, int n_fft, int hop, int64_t L, void *stream) {
+  return spec_splice_blend_f32(audio_orig, audio_ola, touched, audio_out, B, T_frames, n_fft, hop, L, S(stream));
+}
 int isi_resample_geometry(int fs_in, int fs_out, int *orig, int *new_, int *width, int *taps) {
   return resample_geometry(fs_in, fs_out, orig, new_, width, taps);
 }

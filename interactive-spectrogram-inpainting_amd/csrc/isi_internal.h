@@ -356,6 +356,11 @@ int spec_inverse_prepare_bwd_f32(const float *spec, const float *da, const float
                                  hipStream_t st);
 int overlap_add_f32(const float *frames, float *audio, int B, int T, int n_fft, int hop, int left, int64_t L,
                     hipStream_t st);
+// spec_splice.hip: phase-locked splice of regenerated frames into an original's STFT, and the sample blend behind it
+int spec_splice_f32(const float *stft_orig, const float *a, const float *ph, const float *w, int w_batch, float *stft_out,
+                    int B, int T, int F, int mel, hipStream_t st);
+int spec_splice_blend_f32(const float *audio_orig, const float *audio_ola, const uint8_t *touched, float *audio_out, int B,
+                          int T_frames, int n_fft, int hop, int64_t L, hipStream_t st);
 int resample_geometry(int fs_in, int fs_out, int *orig, int *new_, int *width, int *taps);
 int64_t resample_out_len(int64_t L, int orig, int new_);
 int resample_f32(const float *x, int64_t x_stride, float *y, int64_t y_stride, int B, int64_t L, int orig, int new_,

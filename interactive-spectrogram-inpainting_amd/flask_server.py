@@ -8,6 +8,10 @@ query arguments and JSON schema for the operations built on MI355X
   POST /erase?eraser_amplitude=&start_index_top=                                        (:873-931)
   POST /get-audio[?fs_hz=]   -> audio/wav (16-bit PCM written with the standard library); `fs_hz` (not in the
        reference) asks for the audio resampled to that rate                               (:1003-1021)
+  POST /get-audio-spliced[?fs_hz=]   (not in the reference) multipart: file `audio`, the original upload (as
+       /analyze-audio takes it, converted to the models' rate), and `codes`, the JSON /get-audio takes (a form field or a
+       file part) -> audio/wav: the upload's own samples wherever the codes are those of the upload, the decoded codes
+       where they were edited, phase-locked to the upload at both seams (csrc/spec_splice.hip)
   POST /analyze-audio?pitch=&instrument_family_str=   multipart file `audio` (RIFF / PCM 16-bit or float32, mono or
        averaged to mono, at any sampling rate the resampler takes -- 44.1 and 48 kHz recordings are converted to
        the models' rate on the GPU, GANsynth_pytorch/resample.py; read with the standard library)  (:557-568,624-667)
@@ -31,6 +35,7 @@ Global (non-local) class conditioning only, like the reference's default deploym
 from __future__ import annotations
 
 import io
+import json
 import struct
 import zipfile
 from typing import Mapping, Optional
@@ -141,12 +146,8 @@ def create_app(vqvae, transformer_top, transformer_bottom, label_encoders_per_mo
                 flask.abort(400, description=str(e))
         return flask.send_file(io.BytesIO(_wav_bytes(audio, fs_hz)), mimetype="audio/wav", max_age=0)
 
-    @app.route('/analyze-audio', methods=['POST'])
-    def analyze_audio():
-        if spectrograms_helper is None:
-            flask.abort(501)
-        args = flask.request.args
-        values = {'pitch': args.get('pitch', type=int), 'instrument_family_str': str(args.get('instrument_family_str'))}
+    def uploaded_audio():
+        """the multipart file `audio` as mono samples at the models' rate; 400 when it is missing or unreadable"""
         try:
             audio, rate = _read_wav(flask.request.files['audio'].read())
         except (KeyError, ValueError, struct.error) as e:
@@ -160,6 +161,37 @@ def create_app(vqvae, transformer_top, transformer_bottom, label_encoders_per_mo
                 audio = _resample.resample(audio.to(device), rate, spectrograms_helper.fs_hz)
             except ValueError as e:
                 flask.abort(400, description=str(e))
+        return audio
+
+    @app.route('/get-audio-spliced', methods=['POST'])
+    def get_audio_spliced():
+        if spectrograms_helper is None:
+            flask.abort(501)
+        original = uploaded_audio()
+        try:
+            part = flask.request.files.get('codes')
+            text = part.read() if part is not None else flask.request.form['codes']
+            top_code, bottom_code = codes(json.loads(text))
+        except (KeyError, ValueError, TypeError) as e:
+            flask.abort(400, description=f"codes: {e}")
+        audio = inpainting.codes_to_audio_spliced(vqvae, spectrograms_helper, original, top_code, bottom_code)[0]
+        fs_hz = flask.request.args.get('fs_hz', type=int, default=None)
+        if fs_hz is None:
+            fs_hz = spectrograms_helper.fs_hz
+        else:
+            try:
+                audio = _resample.resample(audio, spectrograms_helper.fs_hz, fs_hz)
+            except ValueError as e:
+                flask.abort(400, description=str(e))
+        return flask.send_file(io.BytesIO(_wav_bytes(audio, fs_hz)), mimetype="audio/wav", max_age=0)
+
+    @app.route('/analyze-audio', methods=['POST'])
+    def analyze_audio():
+        if spectrograms_helper is None:
+            flask.abort(501)
+        args = flask.request.args
+        values = {'pitch': args.get('pitch', type=int), 'instrument_family_str': str(args.get('instrument_family_str'))}
+        audio = uploaded_audio()
         res_n = inpainting.top_resolution_n(vqvae, transformer_top, transformer_bottom, spectrograms_helper, device)
         duration_n = inpainting.adapt_duration(audio.numel(), spectrograms_helper.fs_hz, max_sound_duration_s, res_n,
                                                transformer_top.shape[1])

@@ -21,6 +21,9 @@ routes (flask_server.py), free of HTTP so that they can be called, tested and ti
   morph / morph_sweep / crossfade   decode per-cell weighted mixtures of several sounds' codes: timbre interpolation,
                       a sweep between two sounds in one batch, a splice whose seam is a ramp in the latent (not in the
                       reference: csrc/code_mix.hip, VQVAE.decode_code_mix)
+  codes_to_audio_spliced / splice_weights / changed_cells   `codes_to_audio` for an UPLOAD whose codes were edited: the
+                      upload's own samples outside the edit, the decoded codes inside it, phase-locked at both seams
+                      (not in the reference: csrc/spec_splice.hip, SpectrogramsHelper.to_audio_spliced)
   spectrogram_png     the decoded log-mel magnitude as a viridis PNG (:103-143, 1024-1046)
 
 The heavy work is `sample.sample_model` (encoder pass + KV-cached native decoding loop),
@@ -508,6 +511,87 @@ def erase(vqvae, top_code: torch.Tensor, bottom_code: torch.Tensor, mask: torch.
 @torch.no_grad()
 def codes_to_audio(vqvae, spectrograms_helper, top_code: torch.Tensor, bottom_code: torch.Tensor) -> torch.Tensor:
     return spectrograms_helper.to_audio(vqvae.decode_code(top_code, bottom_code))
+
+
+def changed_cells(top0: torch.Tensor, bottom0: torch.Tensor, top1: torch.Tensor, bottom1: torch.Tensor) -> torch.Tensor:
+    """Which cells of the top codemap an edit touched: bool [F_top, T_top] ([B, F_top, T_top] for batches of more than one
+    sound), true where the top code differs or any bottom cell under it does.  Codemaps [F, T] or [B, F, T]."""
+    maps = [torch.as_tensor(c).cpu() for c in (top0, bottom0, top1, bottom1)]
+    maps = [c.unsqueeze(0) if c.dim() == 2 else c for c in maps]
+    t0, b0, t1, b1 = maps
+    if t0.shape != t1.shape or b0.shape != b1.shape or t0.dim() != 3 or b0.dim() != 3 or t0.shape[0] != b0.shape[0]:
+        raise ValueError("changed_cells: the two sounds' codemaps must have equal shapes")
+    (B, Ft, Tt), (_, Fb, Tb) = t0.shape, b0.shape
+    if Fb % Ft or Tb % Tt:
+        raise ValueError(f"changed_cells: bottom map {Fb} x {Tb} is no multiple of top map {Ft} x {Tt}")
+    under = (b0 != b1).reshape(B, Ft, Fb // Ft, Tt, Tb // Tt).any(4).any(2)
+    changed = (t0 != t1) | under
+    return changed[0] if B == 1 else changed
+
+
+def splice_weights(spectrograms_helper, mask_top: torch.Tensor, n_frames: int, feather_frames: int, halo_top: int = 1) -> torch.Tensor:
+    """The weights `SpectrogramsHelper.to_audio_spliced` takes, from a mask over the top codemap: float32
+    [1 or B, n_frames, n_fft / 2] on the CPU, 0 where the original is kept, above 0 where the sound is regenerated.
+
+    mask_top bool [F_top, T_top] (or [B, F_top, T_top]; `changed_cells` makes one).  The mask is grown by `halo_top` cells
+    in both directions (the decoder's receptive field changes the neighbours of a changed code too), repeated to
+    spectrogram rows and frames (mask row i covers spectrogram rows [i up, (i + 1) up), lowest frequency first: the order
+    of `erase` and, bottom-up, of `spectrogram_png`), and given linear ramps of `feather_frames` frames in time on both
+    sides (1 - d / (feather_frames + 1) at distance d).  For a mel helper the rows are mel bands: a linear bin gets the
+    mean of the bands it feeds, weighted with `_mel_matrix`; a bin that feeds none keeps the original.  Host, float64."""
+    m = torch.as_tensor(mask_top).cpu()
+    if m.dim() == 2:
+        m = m.unsqueeze(0)
+    if m.dim() != 3:
+        raise ValueError("splice_weights: mask_top must be [F_top, T_top] or [B, F_top, T_top]")
+    _, Ft, Tt = m.shape
+    rows, feather, halo = int(spectrograms_helper.n_bins), int(feather_frames), int(halo_top)
+    if feather < 0 or halo < 0 or n_frames < 1 or n_frames % Tt or rows % Ft:
+        raise ValueError(f"splice_weights: {n_frames} frames x {rows} rows is no multiple of the mask's {Tt} x {Ft}, "
+                         "or a negative feather / halo")
+    w = (m != 0).to(torch.float64)
+    if halo:
+        w = torch.nn.functional.max_pool2d(w.unsqueeze(1), 2 * halo + 1, stride=1, padding=halo).squeeze(1)
+    w = w.repeat_interleave(rows // Ft, 1).repeat_interleave(n_frames // Tt, 2)          # [B, rows, frames]
+    hard, w = w, w.clone()
+    for d in range(1, min(feather, n_frames - 1) + 1):
+        level = 1.0 - d / (feather + 1.0)
+        w[..., d:] = torch.maximum(w[..., d:], level * hard[..., :-d])
+        w[..., :-d] = torch.maximum(w[..., :-d], level * hard[..., d:])
+    w = w.transpose(1, 2)                                                               # [B, frames, rows]
+    if getattr(spectrograms_helper, 'mel', False):
+        M = spectrograms_helper._mel_matrix().to(torch.float64)                          # [linear, mel]
+        fed = M.sum(1)
+        w = (w @ M.t()) / torch.where(fed > 0, fed, torch.ones_like(fed))
+    return w.clamp(0.0, 1.0).to(torch.float32).contiguous()
+
+
+@torch.no_grad()
+def codes_to_audio_spliced(vqvae, spectrograms_helper, original_audio: torch.Tensor, top_code: torch.Tensor,
+                           bottom_code: torch.Tensor, mask_top: Optional[torch.Tensor] = None,
+                           feather_frames: Optional[int] = None, halo_top: int = 1) -> torch.Tensor:
+    """`codes_to_audio` for an uploaded sound whose codes were edited: the upload's own samples wherever the edit does
+    not reach, the decoded codes inside it, phase-locked to the upload at both seams (`to_audio_spliced`).
+
+    original_audio: mono [samples] (or [B, samples]) at the models' rate, trimmed / zero-padded to the codes' duration as
+    `analyze_audio` does.  mask_top bool [F_top, T_top]: the edited cells of the top map; None: the upload is encoded
+    again and the cells whose codes differ are taken (`changed_cells`).  The mask is grown by `halo_top` cells and
+    feathered over `feather_frames` frames (default: one top column's) -- `splice_weights`.  Unchanged codes return the
+    upload itself.  Returns [B, samples]."""
+    spec = vqvae.decode_code(top_code, bottom_code)
+    B, n_frames = spec.shape[0], spec.shape[-1]
+    duration_n = n_frames * spectrograms_helper.hop_length
+    x = original_audio.to(device=spec.device, dtype=torch.float32).reshape(B, -1)[:, :duration_n]
+    if x.shape[1] < duration_n:
+        x = torch.nn.functional.pad(x, (0, duration_n - x.shape[1]))
+    x = x.contiguous()
+    if mask_top is None:
+        _, _, _, top0, bottom0, *_ = vqvae.encode(spectrograms_helper.to_spectrogram(x))
+        mask_top = changed_cells(top0, bottom0, top_code, bottom_code)
+    if feather_frames is None:
+        feather_frames = n_frames // top_code.shape[-1]
+    weights = splice_weights(spectrograms_helper, mask_top, n_frames, feather_frames, halo_top)
+    return spectrograms_helper.to_audio_spliced(spec, x, weights.to(spec.device))
 
 
 @torch.no_grad()

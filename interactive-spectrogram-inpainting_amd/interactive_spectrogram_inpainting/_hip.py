@@ -265,6 +265,8 @@ SIGNATURES = {
     "isi_spec_to_stft_bwd_f32": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, _P]),
     "isi_spec_inverse_prepare_bwd_f32": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "isi_overlap_add_f32": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _P]),
+    "isi_spec_splice_f32": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "isi_spec_splice_blend_f32": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _P]),
     "isi_resample_geometry": (C.c_int, [C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4),
     "isi_resample_out_len": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
     "isi_resample_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P]),

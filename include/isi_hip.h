@@ -105,6 +105,34 @@ int isi_spec_splice_f32(const float *stft_orig, const float *a, const float *ph,
                         float *stft_out, int B, int T, int F, int mel, void *stream);
 int isi_spec_splice_blend_f32(const float *audio_orig, const float *audio_ola, const unsigned char *touched,
                               float *audio_out, int B, int T_frames, int n_fft, int hop, int64_t L, void *stream);
+/* Re-timing of an STFT with identity phase locking (not in the reference): the step that turns the analysis STFT, or
+ * isi_spec_to_stft_f32's output, into a time stretch and, with isi_resample_f32 behind the inverse, a transposition.
+ * X [B,T,2F] (real block | imaginary block, DC dropped: bin j is DFT bin j + 1 of n_fft = 2F), pos [pos_batch,T_out]
+ * (pos_batch 1 or B): the source position of every output frame, in frames, on the device; out [B,T_out,2F].
+ * Source, per (b, t, j): P = fl(fl(re re) + fl(im im)) in float32 without FMA, A = sqrt P, phi = atan2(im, re),
+ * Omega_j = 2 pi ((j + 1) hop mod n_fft) / n_fft, dev[t] = wrap(phi[t+1] - phi[t] - Omega_j) for t <= T - 2, wrap =
+ * principal value in (-pi, pi].  Bin j is a peak of frame t iff P > 0 and for d = 1, 2: P[j] > P[j-d] and
+ * P[j] >= P[j+d] (neighbours outside [0, F) do not object); near[t,j] = the peak nearest to j, the lower one on a tie,
+ * j itself in a frame without a peak.
+ * Output frame u: p = pos[u] clamped to [0, T-1] (a NaN counts as 0; no content of pos leads to an access outside the
+ * arrays), t = min(floor p, T - 2), f = p - t, ta = f < 0.5 ? t : t + 1,
+ *   M[j] = (1 - f) A[t,j] + f A[t+1,j],   D[j] = Omega_j + ((1 - f) dev[max(t-1,0),j] + f dev[t,j]),
+ *   u == 0:  Phi[j] = phi[t,j] + f (2 pi (j + 1) hop / n_fft + dev[t,j])
+ *   u > 0:   n = near[ta,j], Phi[j] = wrap((Phi_before[n] + D[n]) + (phi[ta,j] - phi[ta,n]))
+ *   out = M (cos Phi | sin Phi).
+ * The leading copy run: with c the largest count such that pos[0] is an integer in [0, T-1] and pos[u] == pos[0] + u
+ * <= T - 1 for every u < c, frames u < c are the source's two floats of frame pos[u], bit for bit, and Phi of frame
+ * c - 1 is that frame's phi: pos = 0, 1, ..., T - 1 returns X.
+ * workspace: isi_stft_stretch_workspace_bytes(B, T, F) bytes (host only; 0 for sizes the call refuses), four [B,T,F]
+ * planes the call fills: A, phi, dev (float32; dev of frame T - 1 is 0) and near (int32) -- readable afterwards.
+ * Refused before any launch: a null or misaligned pointer, B, F or T_out < 1, T < 2, pos_batch outside {1, B}, hop < 1 or
+ * not dividing 2F (ISI_E_INVALID); F > ISI_STFT_STRETCH_MAX_F, T > 2^24 (positions are float32 frame numbers), X or
+ * out above 2^30 - 4 elements (ISI_E_UNSUPPORTED); a workspace too small (ISI_E_WORKSPACE).  Inputs, output and
+ * workspace must not overlap. */
+#define ISI_STFT_STRETCH_MAX_F 2048
+size_t isi_stft_stretch_workspace_bytes(int B, int T, int F);
+int isi_stft_stretch_f32(const float *X, const float *pos, int pos_batch, float *out, void *workspace,
+                         size_t workspace_bytes, int B, int T, int T_out, int F, int hop, void *stream);
 /* One scale of the multi-scale spectral loss (reference utils/losses/spectral.py:78-118, where the STFTs come
  * from torch.stft): xp / xt = STFT rows [B*T][RS] (re block | im block of F bins, RS >= 2F) of the predicted and
  * the target audio.  fwd: per (sample, chunk of rows_per_block frames) the sums

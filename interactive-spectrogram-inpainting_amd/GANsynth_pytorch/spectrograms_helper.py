@@ -11,6 +11,8 @@ flask_server.py:242-244,596,1016):
         .to_audio(spec [B, 2, n_fft/2, T]) -> [B, T * hop]        .fs_hz
         .to_audio_spliced(spec, original_audio [B, T * hop], weights [1 or B, T, n_fft/2]) -> [B, T * hop]
             (not in the reference: the original's own samples outside an edited region, csrc/spec_splice.hip)
+        .to_audio_stretched(spec, positions [T_out] or [1 or B, T_out]) -> [B, T_out * hop]
+            (not in the reference: the decoded sound at another length, csrc/stft_stretch.hip)
 
 Arithmetic = the published GANSynth representation (specification and parity status:
 oracle/spectrogram_oracle.py — the original package is absent, parity unpinned).
@@ -232,6 +234,38 @@ class SpectrogramsHelper:
         _hip.check(L.isi_spec_splice_blend_f32(original_audio.data_ptr(), ola.data_ptr(), touched.data_ptr(),
                                                audio.data_ptr(), B, T_all, N, hop, n_out, _s(spec)),
                    "isi_spec_splice_blend_f32")
+        return audio
+
+    @torch.no_grad()
+    def to_audio_stretched(self, spec: torch.Tensor, positions: torch.Tensor) -> torch.Tensor:
+        """`to_audio(spec)` at another length: spec [B, 2, F, T], positions float32 [T_out] or [1 or B, T_out] on the GPU, the
+        source position (in frames of the spectrogram) of every output frame -> [B, T_out * hop].  The decoded STFT
+        (isi_spec_to_stft_f32's, as in `to_audio`) is re-timed with its phases locked to the spectral peaks
+        (isi_stft_stretch_f32, csrc/stft_stretch.hip; `GANsynth_pytorch.stretch.stretch_positions` makes positions); the
+        positions 0 .. T - 1 give `to_audio`'s STFT bit for bit.  No gradient."""
+        from GANsynth_pytorch import stretch as _stretch
+        _hip.require_gpu(spec, "spectrogram")
+        c = self._build(spec.device)
+        spec = spec.float().contiguous()
+        B, two, F, T = spec.shape
+        if two != 2 or F != self.n_bins:
+            raise ValueError(f"expected [B, 2, {self.n_bins}, T], got {tuple(spec.shape)}")
+        L = _hip.lib()
+        a = torch.empty(B, T, F, dtype=torch.float32, device=spec.device)
+        ph = torch.empty_like(a)
+        _hip.check(L.isi_spec_inverse_prepare_f32(spec.data_ptr(), a.data_ptr(), ph.data_ptr(), B, T, F, _s(spec)),
+                   "isi_spec_inverse_prepare_f32")
+        a, ph = self._unproject(a, ph)
+        X = torch.empty(B, T, 2 * F, dtype=torch.float32, device=spec.device)
+        _hip.check(L.isi_spec_to_stft_f32(a.data_ptr(), ph.data_ptr(), X.data_ptr(), B * T, F, int(self.mel), _s(spec)),
+                   "isi_spec_to_stft_f32")
+        Y = _stretch.stft_stretch(X, positions, self.hop_length)
+        T_out = Y.shape[1]
+        frames = _gemm.linear(Y, c["istft_w"], None, self.n_fft)
+        n_out = T_out * self.hop_length
+        audio = torch.empty(B, n_out, dtype=torch.float32, device=spec.device)
+        _hip.check(L.isi_overlap_add_f32(frames.data_ptr(), audio.data_ptr(), B, T_out, self.n_fft, self.hop_length,
+                                         self.n_fft - self.hop_length, n_out, _s(spec)), "isi_overlap_add_f32")
         return audio
 
     def _to_audio_backward(self, saved, d_audio: torch.Tensor) -> torch.Tensor:

@@ -318,6 +318,11 @@ int isi_spec_splice_blend_f32(const float *audio_orig, const float *audio_ola, c
                               int T_frames, int n_fft, int hop, int64_t L, void *stream) {
   return spec_splice_blend_f32(audio_orig, audio_ola, touched, audio_out, B, T_frames, n_fft, hop, L, S(stream));
 }
+size_t isi_stft_stretch_workspace_bytes(int B, int T, int F) { return stft_stretch_workspace_bytes(B, T, F); }
+int isi_stft_stretch_f32(const float *X, const float *pos, int pos_batch, float *out, void *workspace, size_t workspace_bytes,
+                         int B, int T, int T_out, int F, int hop, void *stream) {
+  return stft_stretch_f32(X, pos, pos_batch, out, workspace, workspace_bytes, B, T, T_out, F, hop, S(stream));
+}
 int isi_resample_geometry(int fs_in, int fs_out, int *orig, int *new_, int *width, int *taps) {
   return resample_geometry(fs_in, fs_out, orig, new_, width, taps);
 }

@@ -361,6 +361,10 @@ int spec_splice_f32(const float *stft_orig, const float *a, const float *ph, con
                     int B, int T, int F, int mel, hipStream_t st);
 int spec_splice_blend_f32(const float *audio_orig, const float *audio_ola, const uint8_t *touched, float *audio_out, int B,
                           int T_frames, int n_fft, int hop, int64_t L, hipStream_t st);
+// stft_stretch.hip: an STFT re-timed along a list of source positions, identity phase locking
+size_t stft_stretch_workspace_bytes(int B, int T, int F);
+int stft_stretch_f32(const float *X, const float *pos, int pos_batch, float *out, void *workspace, size_t workspace_bytes,
+                     int B, int T, int T_out, int F, int hop, hipStream_t st);
 int resample_geometry(int fs_in, int fs_out, int *orig, int *new_, int *width, int *taps);
 int64_t resample_out_len(int64_t L, int orig, int new_);
 int resample_f32(const float *x, int64_t x_stride, float *y, int64_t y_stride, int B, int64_t L, int orig, int new_,

@@ -12,6 +12,12 @@ query arguments and JSON schema for the operations built on MI355X
        /analyze-audio takes it, converted to the models' rate), and `codes`, the JSON /get-audio takes (a form field or a
        file part) -> audio/wav: the upload's own samples wherever the codes are those of the upload, the decoded codes
        where they were edited, phase-locked to the upload at both seams (csrc/spec_splice.hip)
+  POST /transpose-audio?semitones= | ?to_pitch=   (not in the reference) multipart: file `audio` (as /analyze-audio takes
+       it) -> audio/wav at the models' rate: the sound `semitones` higher (fractional and negative values too), or at
+       the MIDI pitch `to_pitch` (its own pitch is estimated; 400 when it is unvoiced), at its own length
+  POST /stretch-audio?factor=&keep_attack_s=&keep_release_s=   (not in the reference) multipart: file `audio` ->
+       audio/wav: the sound `factor` times as long at its own pitch; the first / last seconds named keep their own rate
+       (both: GANsynth_pytorch/stretch.py, csrc/stft_stretch.hip; the arguments may also be form fields)
   POST /analyze-audio?pitch=&instrument_family_str=   multipart file `audio` (RIFF / PCM 16-bit or float32, mono or
        averaged to mono, at any sampling rate the resampler takes -- 44.1 and 48 kHz recordings are converted to
        the models' rate on the GPU, GANsynth_pytorch/resample.py; read with the standard library)  (:557-568,624-667)
@@ -184,6 +190,49 @@ def create_app(vqvae, transformer_top, transformer_bottom, label_encoders_per_mo
             except ValueError as e:
                 flask.abort(400, description=str(e))
         return flask.send_file(io.BytesIO(_wav_bytes(audio, fs_hz)), mimetype="audio/wav", max_age=0)
+
+    def number(name, default=None):
+        """a numeric argument from the query string or the form; 400 when it is not a number"""
+        text = flask.request.values.get(name)
+        if text is None:
+            return default
+        try:
+            return float(text)
+        except ValueError:
+            flask.abort(400, description=f"{name}: not a number: {text!r}")
+
+    @app.route('/transpose-audio', methods=['POST'])
+    def transpose_audio():
+        if spectrograms_helper is None:
+            flask.abort(501)
+        semitones, to_pitch = number('semitones'), number('to_pitch')
+        if (semitones is None) == (to_pitch is None):
+            flask.abort(400, description="give exactly one of semitones and to_pitch")
+        original = uploaded_audio()
+        try:
+            audio, _, _ = inpainting.transpose_sound(vqvae, spectrograms_helper, original.to(device), semitones=semitones,
+                                                     to_pitch=to_pitch, re_encode=False)
+        except ValueError as e:
+            flask.abort(400, description=str(e))
+        return flask.send_file(io.BytesIO(_wav_bytes(audio.reshape(-1), spectrograms_helper.fs_hz)), mimetype="audio/wav",
+                               max_age=0)
+
+    @app.route('/stretch-audio', methods=['POST'])
+    def stretch_audio():
+        if spectrograms_helper is None:
+            flask.abort(501)
+        factor = number('factor')
+        if factor is None:
+            flask.abort(400, description="factor is missing")
+        keep_attack_s, keep_release_s = number('keep_attack_s', 0.0), number('keep_release_s', 0.0)
+        original = uploaded_audio()
+        try:
+            audio = inpainting.stretch_sound(vqvae, spectrograms_helper, audio=original.to(device), factor=factor,
+                                             keep_attack_s=keep_attack_s, keep_release_s=keep_release_s)
+        except ValueError as e:
+            flask.abort(400, description=str(e))
+        return flask.send_file(io.BytesIO(_wav_bytes(audio.reshape(-1), spectrograms_helper.fs_hz)), mimetype="audio/wav",
+                               max_age=0)
 
     @app.route('/analyze-audio', methods=['POST'])
     def analyze_audio():

@@ -24,6 +24,10 @@ routes (flask_server.py), free of HTTP so that they can be called, tested and ti
   codes_to_audio_spliced / splice_weights / changed_cells   `codes_to_audio` for an UPLOAD whose codes were edited: the
                       upload's own samples outside the edit, the decoded codes inside it, phase-locked at both seams
                       (not in the reference: csrc/spec_splice.hip, SpectrogramsHelper.to_audio_spliced)
+  stretch_sound / transpose_sound   a sound (or decoded codes) at another length, a sound at another pitch -- by a number
+                      of semitones, to a MIDI pitch, or to the estimated pitch of another sound -- with its codes, so that
+                      morphs and searches can compare sounds at equal pitch (not in the reference: csrc/stft_stretch.hip,
+                      GANsynth_pytorch/stretch.py)
   spectrogram_png     the decoded log-mel magnitude as a viridis PNG (:103-143, 1024-1046)
 
 The heavy work is `sample.sample_model` (encoder pass + KV-cached native decoding loop),
@@ -592,6 +596,71 @@ def codes_to_audio_spliced(vqvae, spectrograms_helper, original_audio: torch.Ten
         feather_frames = n_frames // top_code.shape[-1]
     weights = splice_weights(spectrograms_helper, mask_top, n_frames, feather_frames, halo_top)
     return spectrograms_helper.to_audio_spliced(spec, x, weights.to(spec.device))
+
+
+def _sound_device(audio, vqvae, spectrograms_helper) -> torch.device:
+    """where a sound is worked on: its own GPU, else the helper's device, else the model's"""
+    if audio.is_cuda:
+        return audio.device
+    if getattr(spectrograms_helper, 'device', None) is not None:
+        return spectrograms_helper.device
+    return next(vqvae.parameters()).device if vqvae is not None else audio.device
+
+
+@torch.no_grad()
+def stretch_sound(vqvae, spectrograms_helper, audio: Optional[torch.Tensor] = None, codes=None, factor: float = 1.0,
+                  keep_attack_s: float = 0.0, keep_release_s: float = 0.0) -> torch.Tensor:
+    """A sound `factor` times as long at its own pitch; the first `keep_attack_s` and the last `keep_release_s` seconds keep
+    their own rate ("hold this note longer but keep its attack").  Either `audio`, mono [samples] or [B, samples] at the
+    models' rate (`GANsynth_pytorch.stretch.time_stretch` of its own STFT), or `codes` = (top_code, bottom_code), decoded at
+    the other length (`SpectrogramsHelper.to_audio_stretched`: no second analysis).  Returns audio [.., samples].
+    ValueError for a factor that is not positive and finite or kept seconds that do not fit."""
+    from GANsynth_pytorch import stretch
+    if (audio is None) == (codes is None):
+        raise ValueError("stretch_sound: give exactly one of audio and codes")
+    if audio is not None:
+        x = audio.to(device=_sound_device(audio, vqvae, spectrograms_helper), dtype=torch.float32)
+        return stretch.time_stretch(spectrograms_helper, x, factor, keep_attack_s, keep_release_s)
+    top_code, bottom_code = codes
+    spec = vqvae.decode_code(top_code, bottom_code)
+    head = stretch._seconds_to_frames(spectrograms_helper, keep_attack_s, "keep_attack_s")
+    tail = stretch._seconds_to_frames(spectrograms_helper, keep_release_s, "keep_release_s")
+    positions = stretch.stretch_positions(spec.shape[-1], factor=factor, keep_head=head, keep_tail=tail)
+    return spectrograms_helper.to_audio_stretched(spec, positions.to(spec.device))
+
+
+@torch.no_grad()
+def transpose_sound(vqvae, spectrograms_helper, audio: torch.Tensor, semitones: Optional[float] = None,
+                    to_pitch: Optional[float] = None, like: Optional[torch.Tensor] = None, re_encode: bool = True):
+    """A sound at another pitch and its own length: (audio, top_code, bottom_code).  Exactly one of `semitones` (may be
+    fractional), `to_pitch` (a MIDI number) and `like` (another sound, whose estimated pitch is the target).  The last two
+    take the source's pitch from `GANsynth_pytorch.pitch.estimate_pitch`, unrounded; ValueError when a sound they need the
+    pitch of is unvoiced.  Mono audio [samples] at the models' rate.  The codes come from `analyze_audio` of the result
+    (None, None with re_encode=False), so that it can be morphed, searched and inpainted like any other sound."""
+    from GANsynth_pytorch import stretch
+    from GANsynth_pytorch.pitch import estimate_pitch as estimate
+    if sum(v is not None for v in (semitones, to_pitch, like)) != 1:
+        raise ValueError("transpose_sound: give exactly one of semitones, to_pitch and like")
+    device = _sound_device(audio, vqvae, spectrograms_helper)
+    x = audio.to(device=device, dtype=torch.float32).reshape(-1)
+
+    def pitch_of(sound, name):
+        midi = float(estimate(sound, int(spectrograms_helper.fs_hz))[0])
+        if midi != midi:
+            raise ValueError(f"transpose_sound: {name} is unvoiced, it has no pitch to transpose from or to")
+        return midi
+
+    if semitones is None:
+        target = float(to_pitch) if to_pitch is not None else \
+            pitch_of(like.to(device=device, dtype=torch.float32).reshape(-1), "the sound to be like")
+        if not math.isfinite(target):
+            raise ValueError(f"transpose_sound: to_pitch must be finite, got {target}")
+        semitones = target - pitch_of(x, "the sound")
+    y = stretch.transpose(spectrograms_helper, x, float(semitones))
+    if not re_encode:
+        return y, None, None
+    top_code, bottom_code = analyze_audio(vqvae, spectrograms_helper, y, y.numel(), device)
+    return y, top_code, bottom_code
 
 
 @torch.no_grad()

@@ -267,6 +267,8 @@ SIGNATURES = {
     "isi_overlap_add_f32": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _P]),
     "isi_spec_splice_f32": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "isi_spec_splice_blend_f32": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _P]),
+    "isi_stft_stretch_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "isi_stft_stretch_f32": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "isi_resample_geometry": (C.c_int, [C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4),
     "isi_resample_out_len": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
     "isi_resample_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P]),

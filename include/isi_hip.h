@@ -176,6 +176,27 @@ int64_t isi_resample_out_len(int64_t L, int orig, int new_);
 int isi_resample_f32(const float *x, int64_t x_stride, float *y, int64_t y_stride, int B, int64_t L,
                      int orig, int new_, int width, const float *table, void *stream);
 
+/* Time-warped read (not in the reference): the same windowed sinc with a position and a cutoff PER OUTPUT SAMPLE, for
+ * reading a sound along an arbitrary time map -- vibrato, glides, pitch flattening (GANsynth_pytorch/bend.py; DESIGN.md
+ * section 6i; specification tests/warp_resample_spec.py):
+ *   y[b, n] = sum_m c h(c (p - m)) x[b, m]  over the integers m in [0, L) with |c (p - m)| < 64, m ascending, fp32 fma
+ *   p = pos[b or 0, n] in source samples, c = min(max(cut[b or 0, n], ISI_WARP_CUT_MIN), 1), a NaN cut counts as the minimum
+ *   h(t) = sinc(t) I0(beta sqrt(1 - (t / 64)^2)) / I0(beta), the constants of isi_resample_f32 ("kaiser best")
+ * x is 0 outside [0, L).  A position that is NaN or infinite, or whose support does not meet [0, L), gives +0.0; no
+ * content of pos or cut leads to an access outside the arrays, |p| beyond 2^31 included.  pos is DOUBLE: a float32
+ * position near sample 60 000 is good to 2^-8 sample only, a -38 dB phase error at 8 kHz; floor(p) and the fraction are
+ * taken once per output in double, every tap distance is then an exact small integer plus that fraction in fp32.  The
+ * weights are evaluated in the kernel (no table): within 4.02 x 2^-24 c of the float64 weight, the tap products are
+ * summed by fma.  At most 2 * 64 / ISI_WARP_CUT_MIN + 1 = 641 taps per output.
+ * x[b, 0:L] and y[b, 0:N_out], rows x_stride / y_stride floats apart, any float-aligned bases; pos (8-byte aligned) and
+ * cut [pos_batch, N_out] dense, pos_batch 1 or B.  No atomics, no allocation, no host synchronisation; stream-ordered;
+ * the bits of an output depend on its own p, c and the samples under its support -- not on B, the row or the launch.
+ * Checked before any launch: null or misaligned pointers, B / L / N_out < 1, pos_batch outside {1, B}, a stride shorter
+ * than the row (ISI_E_INVALID); L or N_out >= 2^31, 2^31 workgroups (ISI_E_UNSUPPORTED). */
+#define ISI_WARP_CUT_MIN 0.2f
+int isi_warp_resample_f32(const float *x, int64_t x_stride, const double *pos, const float *cut, int pos_batch,
+                          float *y, int64_t y_stride, int B, int64_t L, int64_t N_out, void *stream);
+
 /* ------------------------------------------------ pitch of an uploaded sound */
 /* Both priors are conditioned on the pitch; for an upload nobody knows it.  YIN (de Cheveigne & Kawahara 2002) on
  * the sound brought to 48 kHz (specification tests/pitch_spec.py).  With T =

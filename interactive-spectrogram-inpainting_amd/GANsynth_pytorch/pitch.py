@@ -11,10 +11,14 @@ first lag under the threshold is then a multiple of the period (specification: t
     a frame is voiced if d'(tau*) < VOICED_AP and its energy exceeds VOICED_E of the clip's largest; the clip's pitch is
     the lower median of the voiced frames' 69 + 12 log2(FS_A / (440 period)), its confidence the voiced share.
 
+`pitch_contour` runs the same two kernels again on windows of about four periods, for a contour fine enough to act on
+(GANsynth_pytorch/bend.py).
+
 No CPU path: the audio must live on the GPU."""
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import NamedTuple, Tuple, Union
 
 import torch
@@ -98,3 +102,34 @@ def estimate_pitch(audio: torch.Tensor, fs_hz: int, return_track: bool = False
         return midi, confidence
     times = (torch.arange(voiced.shape[1], device=x.device, dtype=torch.float32) * HOP + W / 2) / FS_A
     return midi, confidence, PitchTrack(midi_t, aperiodicity, energy, voiced, times)
+
+
+def pitch_contour(audio: torch.Tensor, fs_hz: int, periods: float = 4.0) -> PitchTrack:
+    """The pitch of ONE voiced clip frame by frame, finely enough to act on (GANsynth_pytorch/bend.py): audio [L] or [1, L].
+    `estimate_pitch`'s 64 ms frames average a 6 Hz vibrato away; here the clip's pitch gives the period and the same two
+    kernels run again on windows of about `periods` periods:
+        W = 64 ceil(periods period / 64) clamped to [256, 3072], hop = W / 4,
+        lags limited to floor(0.7 period) .. ceil(1.45 period) + 2 (no octave to fall into),
+        frame t is timed (t hop + (W + period) / 2) / 48000: the centre of the samples its chosen lag compares.
+    The voiced flags follow `estimate_pitch`'s rule.  ValueError when the clip is unvoiced (it has no period)."""
+    if audio.dim() == 2 and audio.shape[0] != 1 or audio.dim() not in (1, 2):
+        raise ValueError(f"pitch_contour takes one clip, [L] or [1, L]; got {tuple(audio.shape)}")
+    midi, _ = estimate_pitch(audio, fs_hz)
+    clip = float(midi.reshape(-1)[0])
+    if clip != clip:
+        raise ValueError("pitch_contour: the clip is unvoiced, it has no period to size the window by")
+    period = FS_A / (440.0 * 2.0 ** ((clip - 69.0) / 12.0))
+    w = min(max(64 * int(math.ceil(float(periods) * period / 64.0)), 256), 3072)
+    hop, tau_min, tau_max = w // 4, max(int(math.floor(0.7 * period)), 1), int(math.ceil(1.45 * period)) + 2
+    x = resample(audio, fs_hz, FS_A)
+    x = x.unsqueeze(0) if x.dim() == 1 else x
+    if x.shape[1] < w + tau_max:
+        x = torch.nn.functional.pad(x, (0, w + tau_max - x.shape[1]))
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    d, energy = difference(x, w, hop, tau_max)
+    period_t, aperiodicity = pick(d, tau_min)
+    voiced = (aperiodicity < VOICED_AP) & (energy > VOICED_E * energy.amax(1, keepdim=True))
+    midi_t = 69.0 + 12.0 * torch.log2(FS_A / (440.0 * period_t))
+    times = (torch.arange(voiced.shape[1], device=x.device, dtype=torch.float32) * hop + (w + period) / 2.0) / FS_A
+    return PitchTrack(midi_t, aperiodicity, energy, voiced, times)

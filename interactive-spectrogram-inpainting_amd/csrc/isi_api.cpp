@@ -331,6 +331,10 @@ int isi_resample_f32(const float *x, int64_t x_stride, float *y, int64_t y_strid
                      int width, const float *table, void *stream) {
   return resample_f32(x, x_stride, y, y_stride, B, L, orig, new_, width, table, S(stream));
 }
+int isi_warp_resample_f32(const float *x, int64_t x_stride, const double *pos, const float *cut, int pos_batch, float *y,
+                          int64_t y_stride, int B, int64_t L, int64_t N_out, void *stream) {
+  return warp_resample_f32(x, x_stride, pos, cut, pos_batch, y, y_stride, B, L, N_out, S(stream));
+}
 int64_t isi_pitch_frames(int64_t L, int W, int hop, int tau_max) { return pitch_frames(L, W, hop, tau_max); }
 int isi_pitch_difference_f32(const float *x, int64_t x_stride, float *d, float *energy, int B, int64_t L, int W, int hop,
                              int tau_max, void *stream) {

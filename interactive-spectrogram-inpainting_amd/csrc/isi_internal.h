@@ -369,6 +369,9 @@ int resample_geometry(int fs_in, int fs_out, int *orig, int *new_, int *width, i
 int64_t resample_out_len(int64_t L, int orig, int new_);
 int resample_f32(const float *x, int64_t x_stride, float *y, int64_t y_stride, int B, int64_t L, int orig, int new_,
                  int width, const float *table, hipStream_t st);
+// warp_resample.hip: the same windowed sinc read along a per-sample position and cutoff
+int warp_resample_f32(const float *x, int64_t x_stride, const double *pos, const float *cut, int pos_batch, float *y,
+                      int64_t y_stride, int B, int64_t L, int64_t n_out, hipStream_t st);
 // pitch.hip
 int64_t pitch_frames(int64_t L, int W, int hop, int tau_max);
 int pitch_difference_f32(const float *x, int64_t x_stride, float *d, float *energy, int B, int64_t L, int W, int hop,

@@ -18,6 +18,10 @@ query arguments and JSON schema for the operations built on MI355X
   POST /stretch-audio?factor=&keep_attack_s=&keep_release_s=   (not in the reference) multipart: file `audio` ->
        audio/wav: the sound `factor` times as long at its own pitch; the first / last seconds named keep their own rate
        (both: GANsynth_pytorch/stretch.py, csrc/stft_stretch.hip; the arguments may also be form fields)
+  POST /bend-audio?vibrato_hz=&vibrato_cents= | ?glide_from=&glide_to= | ?flatten=1[&to_pitch=]   (not in the reference)
+       multipart: file `audio` -> audio/wav at its own length: a vibrato added, a glide between two transpositions in
+       semitones, or the sound's own vibrato and drift removed and the sound tuned to the MIDI pitch `to_pitch` (its own
+       rounded pitch by default; 400 when it is unvoiced)   (GANsynth_pytorch/bend.py, csrc/warp_resample.hip)
   POST /analyze-audio?pitch=&instrument_family_str=   multipart file `audio` (RIFF / PCM 16-bit or float32, mono or
        averaged to mono, at any sampling rate the resampler takes -- 44.1 and 48 kHz recordings are converted to
        the models' rate on the GPU, GANsynth_pytorch/resample.py; read with the standard library)  (:557-568,624-667)
@@ -212,6 +216,30 @@ def create_app(vqvae, transformer_top, transformer_bottom, label_encoders_per_mo
         try:
             audio, _, _ = inpainting.transpose_sound(vqvae, spectrograms_helper, original.to(device), semitones=semitones,
                                                      to_pitch=to_pitch, re_encode=False)
+        except ValueError as e:
+            flask.abort(400, description=str(e))
+        return flask.send_file(io.BytesIO(_wav_bytes(audio.reshape(-1), spectrograms_helper.fs_hz)), mimetype="audio/wav",
+                               max_age=0)
+
+    @app.route('/bend-audio', methods=['POST'])
+    def bend_audio():
+        if spectrograms_helper is None:
+            flask.abort(501)
+        vib, gl = (number('vibrato_hz'), number('vibrato_cents')), (number('glide_from'), number('glide_to'))
+        flatten, to_pitch = number('flatten', 0.0) != 0.0, number('to_pitch')
+        for pair, names in ((vib, "vibrato_hz and vibrato_cents"), (gl, "glide_from and glide_to")):
+            if (pair[0] is None) != (pair[1] is None):
+                flask.abort(400, description=f"{names} come together")
+        if (vib[0] is not None) + (gl[0] is not None) + flatten != 1:
+            flask.abort(400, description="give exactly one of vibrato_hz + vibrato_cents, glide_from + glide_to and flatten=1")
+        if to_pitch is not None and not flatten:
+            flask.abort(400, description="to_pitch belongs to flatten=1")
+        original = uploaded_audio()
+        try:
+            audio, _, _ = inpainting.bend_sound(vqvae, spectrograms_helper, original.to(device),
+                                                vibrato=vib if vib[0] is not None else None,
+                                                glide=gl if gl[0] is not None else None, flatten=flatten, to_pitch=to_pitch,
+                                                re_encode=False)
         except ValueError as e:
             flask.abort(400, description=str(e))
         return flask.send_file(io.BytesIO(_wav_bytes(audio.reshape(-1), spectrograms_helper.fs_hz)), mimetype="audio/wav",

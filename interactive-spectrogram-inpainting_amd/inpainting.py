@@ -663,6 +663,77 @@ def transpose_sound(vqvae, spectrograms_helper, audio: torch.Tensor, semitones: 
     return y, top_code, bottom_code
 
 
+def contour_curve(track, clip_pitch: float, n_samples: int, fs_hz: int, max_correction: float = 1.5) -> torch.Tensor:
+    """A `PitchTrack` of one clip -> its pitch per sample, float64 [n_samples] on the host, in MIDI numbers: linear between
+    the frame times, held outside.  Frames that are unvoiced, or further than `max_correction` semitones from the clip's
+    pitch (an octave error would otherwise become a 12-semitone jump), take the nearest accepted frame's value.
+    ValueError when no frame is accepted."""
+    import numpy as np
+    midi = track.midi.reshape(-1).double().cpu().numpy()
+    ok = track.voiced.reshape(-1).cpu().numpy() & (np.abs(midi - clip_pitch) <= float(max_correction))
+    idx = np.flatnonzero(ok)
+    if idx.size == 0:
+        raise ValueError("no frame of the sound has a pitch near the clip's: nothing to follow")
+    nearest = idx[np.abs(np.arange(midi.size)[:, None] - idx[None, :]).argmin(1)]
+    times = track.times_s.double().cpu().numpy()
+    return torch.from_numpy(np.interp(np.arange(int(n_samples)) / float(fs_hz), times, midi[nearest]))
+
+
+@torch.no_grad()
+def bend_sound(vqvae, spectrograms_helper, audio: torch.Tensor, curve=None, vibrato=None, glide=None, flatten: bool = False,
+               to_pitch: Optional[float] = None, contour_of: Optional[torch.Tensor] = None, times_s=None,
+               max_correction: float = 1.5, re_encode: bool = True):
+    """A sound with its pitch contour redrawn, at its own length: (audio, top_code, bottom_code), like `transpose_sound`.
+    Exactly one of
+      curve       semitones over time: control points at `times_s` (seconds; linear between, held outside), or one value per sample
+      vibrato     (rate_hz, depth_cents): added from the start, faded in over 0.1 s
+      glide       (from_semitones, to_semitones) over the whole sound
+      flatten     bend by target - contour(t): the sound's own vibrato and drift removed.  The target is `to_pitch` (a MIDI
+                  number: "tune this upload to the class the prior is told"), else the clip's own pitch rounded
+      contour_of  another sound, whose deviation from its own median pitch is added ("sing it like that one")
+    The contours come from `GANsynth_pytorch.pitch.pitch_contour` (`contour_curve`: frames that are unvoiced or further than
+    `max_correction` semitones from their clip's pitch take the nearest accepted frame's value).  ValueError for an unvoiced
+    sound where a contour is needed and for curves `GANsynth_pytorch.bend.curve` refuses.  Mono audio [samples] at the
+    models' rate; the codes come from `analyze_audio` of the result (None, None with re_encode=False)."""
+    from GANsynth_pytorch import bend as _bend
+    from GANsynth_pytorch.pitch import estimate_pitch as estimate, pitch_contour
+    chosen = sum([curve is not None, vibrato is not None, glide is not None, bool(flatten), contour_of is not None])
+    if chosen != 1:
+        raise ValueError("bend_sound: give exactly one of curve, vibrato, glide, flatten and contour_of")
+    if to_pitch is not None and not flatten:
+        raise ValueError("bend_sound: to_pitch belongs to flatten")
+    device = _sound_device(audio, vqvae, spectrograms_helper)
+    x = audio.to(device=device, dtype=torch.float32).reshape(-1)
+    fs_hz = int(spectrograms_helper.fs_hz)
+
+    def contour(sound, name):
+        midi = float(estimate(sound, fs_hz)[0])
+        if midi != midi:
+            raise ValueError(f"bend_sound: {name} is unvoiced, it has no pitch contour")
+        return contour_curve(pitch_contour(sound, fs_hz), midi, x.numel(), fs_hz, max_correction), midi
+
+    if vibrato is not None:
+        rate_hz, depth_cents = vibrato
+        y = _bend.vibrato(spectrograms_helper, x, rate_hz, depth_cents)
+    elif glide is not None:
+        y = _bend.glide(spectrograms_helper, x, glide[0], glide[1])
+    elif curve is not None:
+        y = _bend.bend(spectrograms_helper, x, curve, times_s)
+    elif flatten:
+        own, clip = contour(x, "the sound")
+        target = float(to_pitch) if to_pitch is not None else float(round(clip))
+        if not math.isfinite(target):
+            raise ValueError(f"bend_sound: to_pitch must be finite, got {target}")
+        y = _bend.bend(spectrograms_helper, x, target - own)
+    else:
+        other, _ = contour(contour_of.to(device=device, dtype=torch.float32).reshape(-1), "the sound whose contour is taken")
+        y = _bend.bend(spectrograms_helper, x, other - other.median())
+    if not re_encode:
+        return y, None, None
+    top_code, bottom_code = analyze_audio(vqvae, spectrograms_helper, y, y.numel(), device)
+    return y, top_code, bottom_code
+
+
 @torch.no_grad()
 def top_conditioned_sample(vqvae, transformer_bottom, spectrograms_helper, top_code: torch.Tensor, temperature: float,
                            class_conditioning_bottom, device, top_k_sampling_k: int = 0, top_p_sampling_p: float = 0.0,

@@ -272,6 +272,7 @@ SIGNATURES = {
     "isi_resample_geometry": (C.c_int, [C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4),
     "isi_resample_out_len": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
     "isi_resample_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "isi_warp_resample_f32": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, _P, C.c_int64, C.c_int, C.c_int64, C.c_int64, _P]),
     "isi_pitch_frames": (C.c_int64, [C.c_int64, C.c_int, C.c_int, C.c_int]),
     "isi_pitch_difference_f32": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _P]),
     "isi_pitch_pick_f32": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_float, _P, _P, _P]),

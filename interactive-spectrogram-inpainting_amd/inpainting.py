@@ -821,14 +821,35 @@ def resize_codemaps_repeat_last(top_code: torch.Tensor, bottom_code: torch.Tenso
     return resize(top_code, duration_top), resize(bottom_code, ratio * duration_top)
 
 
-def _found_items(index, indices, distances, shifts=None):
-    """The searches' answers as the lists `similar_sounds` / `similar_fragments` return: ((top, bottom), attributes,
-    distance[, shift_top]) per item."""
+def _check_layer(layer: str) -> None:
+    if layer not in ('top', 'bottom'):
+        raise ValueError(f"unknown layer {layer}")
+
+
+def _one_map(m: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """A codemap or a mask [F, T] (or [1, F, T], [1, 1, F, T]) as [1, F, T]."""
+    return None if m is None else m.reshape(1, *m.shape[-2:])
+
+
+def _bottom_mask(mask: torch.Tensor, ratio_f: int, ratio_t: int) -> torch.Tensor:
+    """A top-layer mask in the bottom layer's resolution, as `timerange_change` extends it."""
+    return mask.repeat_interleave(ratio_f, -2).repeat_interleave(ratio_t, -1)
+
+
+def _search_window(index, search, window, vectors: bool = False, **options):
+    """The body of the `similar_*` functions: `window` -- what `_similar_window` or `_fragment_window` returns -- through
+    `search`, one of the index's `search_*` methods, and its answer as the list they return: ((top, bottom), attributes,
+    distance[, shift_top]) per item.  vectors: the maps are laid out [1, D, F, T] and go in as `*_vectors`."""
+    top, bottom, mask_top, mask_bottom, two = window
+    on_device = (lambda m: m.permute(0, 2, 3, 1).to(index.device)) if vectors else (lambda m: m.to(index.device))
+    form = 'vectors' if vectors else 'code'
+    indices, *shifts, distances = search(**{f'top_{form}': on_device(top), f'bottom_{form}': on_device(bottom) if two else None},
+                                         mask_top=mask_top, mask_bottom=mask_bottom, **options)
     out = []
-    for n, (i, d) in enumerate(zip(indices.tolist(), distances.tolist())):
-        top, bottom, _ = index[i]
-        found = ((top.unsqueeze(0), None if bottom is None else bottom.unsqueeze(0)), index.decoded_attributes(i), d)
-        out.append(found if shifts is None else found + (int(shifts[n]),))
+    for i, d, *shift in zip(indices.tolist(), distances.tolist(), *(s.tolist() for s in shifts)):
+        item_top, item_bottom, _ = index[i]
+        out.append(((item_top.unsqueeze(0), None if item_bottom is None else item_bottom.unsqueeze(0)),
+                    index.decoded_attributes(i), d, *shift))
     return out
 
 
@@ -836,8 +857,7 @@ def _similar_window(index, top_code, bottom_code, mask, layer: str, start_index_
     """What `similar_sounds` compares, for maps whose last two dimensions are [F, T] (codes [1, F, T]; vectors laid out
     [1, D, F, T]): (top_frame, bottom_frame, mask_top, mask_bottom, two) -- the window of the stored duration from
     `start_index_top` on, a shorter map continued with its last column under a mask, the caller's mask merged in."""
-    if layer not in ('top', 'bottom'):
-        raise ValueError(f"unknown layer {layer}")
+    _check_layer(layer)
     two = bottom_code is not None and index.bottom_shape is not None
     shape_top = index.top_shape
     shape_bottom = index.bottom_shape if two else (shape_top[0], shape_top[1])
@@ -866,8 +886,7 @@ def _similar_window(index, top_code, bottom_code, mask, layer: str, start_index_
         if layer == 'top':
             mask_top[..., :mask.shape[-1]] |= mask[..., :shape_top[1]]
             if two:
-                ratio_f = shape_bottom[0] // shape_top[0]
-                up = mask.repeat_interleave(ratio_f, -2).repeat_interleave(ratio_t, -1)
+                up = _bottom_mask(mask, shape_bottom[0] // shape_top[0], ratio_t)
                 mask_bottom[..., :up.shape[-1]] |= up[..., :shape_bottom[1]]
         elif two:
             mask_bottom[..., :mask.shape[-1]] |= mask[..., :shape_bottom[1]]
@@ -887,22 +906,14 @@ def similar_sounds(index, top_code: torch.Tensor, bottom_code: Optional[torch.Te
     mask bool [1,F,W] in the resolution of `layer` over the window: True = do not compare here ("the sounds that agree
     with everything outside my hole"); a top-layer mask extends to the bottom layer as `timerange_change` extends it.
     attribute_constraints: `sample_from_database`'s.  The comparison runs on the device (csrc/code_search.hip)."""
-    top_code = top_code.reshape(1, *top_code.shape[-2:])
-    if bottom_code is not None:
-        bottom_code = bottom_code.reshape(1, *bottom_code.shape[-2:])
-    top_frame, bottom_frame, mask_top, mask_bottom, two = _similar_window(index, top_code, bottom_code, mask, layer,
-                                                                          start_index_top)
-    device = index.device
-    indices, distances = index.search(top_frame.to(device), bottom_frame.to(device) if two else None, mask_top=mask_top,
-                                      mask_bottom=mask_bottom, k=k, attribute_constraints=attribute_constraints)
-    return _found_items(index, indices, distances)
+    window = _similar_window(index, _one_map(top_code), _one_map(bottom_code), mask, layer, start_index_top)
+    return _search_window(index, index.search, window, k=k, attribute_constraints=attribute_constraints)
 
 
 def _fragment_window(index, top_code, bottom_code, start_index_top, width_top, mask, layer: str):
     """What `similar_fragments` compares, for maps whose last two dimensions are [F, T]:
     (query_top, query_bottom or None, mask_top, mask_bottom, two)."""
-    if layer not in ('top', 'bottom'):
-        raise ValueError(f"unknown layer {layer}")
+    _check_layer(layer)
     two = bottom_code is not None and index.bottom_shape is not None
     start, width = int(start_index_top), int(width_top)
     if start < 0 or width < 1 or start + width > top_code.shape[-1]:
@@ -924,7 +935,7 @@ def _fragment_window(index, top_code, bottom_code, start_index_top, width_top, m
         if layer == 'top':
             mask_top = mask
             if two:
-                mask_bottom = mask.repeat_interleave(ratio_f, -2).repeat_interleave(ratio_t, -1)
+                mask_bottom = _bottom_mask(mask, ratio_f, ratio_t)
         else:
             mask_bottom = mask
     return query_top, query_bottom, mask_top, mask_bottom, two
@@ -941,30 +952,22 @@ def similar_fragments(index, top_code: torch.Tensor, bottom_code: Optional[torch
     mask bool [1,F,W] in the resolution of `layer` over that window: True = do not compare here; a top-layer mask extends to
     the bottom layer as `timerange_change` extends it.  shift_range=(lo, hi): only offsets lo <= o < hi of the stored
     maps.  The comparison runs on the device (`CodeIndex.search_shifted`, csrc/code_shift_search.hip)."""
-    top_code = top_code.reshape(1, *top_code.shape[-2:])
-    if bottom_code is not None:
-        bottom_code = bottom_code.reshape(1, *bottom_code.shape[-2:])
-    query_top, query_bottom, mask_top, mask_bottom, two = _fragment_window(index, top_code, bottom_code, start_index_top,
-                                                                           width_top, mask, layer)
-    device = index.device
-    indices, shifts, distances = index.search_shifted(query_top.to(device), query_bottom.to(device) if two else None,
-                                                      mask_top=mask_top, mask_bottom=mask_bottom, k=k, shift_range=shift_range,
-                                                      attribute_constraints=attribute_constraints)
-    return _found_items(index, indices, distances, shifts.tolist())
+    window = _fragment_window(index, _one_map(top_code), _one_map(bottom_code), start_index_top, width_top, mask, layer)
+    return _search_window(index, index.search_shifted, window, k=k, shift_range=shift_range,
+                          attribute_constraints=attribute_constraints)
+
+
+def _vector_maps(z: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """Per-cell vectors [1, F, T, D] laid out as the windows cut them: [1, D, F, T]."""
+    return None if z is None else z.reshape(1, *z.shape[-3:]).permute(0, 3, 1, 2)
 
 
 def _similar_to_vectors(index, z_top: torch.Tensor, z_bottom: Optional[torch.Tensor], mask, layer: str, start_index_top: int,
                         k: int, attribute_constraints):
     """`similar_sounds` for per-cell vectors z_top [1, F_t, T, D], z_bottom [1, F_b, T_b, D] or None: the same window, the
     same masks, `CodeIndex.search_soft` in place of `search`."""
-    as_maps = lambda z: z.reshape(1, *z.shape[-3:]).permute(0, 3, 1, 2)                 # noqa: E731  [1, D, F, T]
-    top_frame, bottom_frame, mask_top, mask_bottom, two = _similar_window(
-        index, as_maps(z_top), None if z_bottom is None else as_maps(z_bottom), mask, layer, start_index_top)
-    as_vectors = lambda m: m.permute(0, 2, 3, 1).to(index.device)                      # noqa: E731
-    indices, distances = index.search_soft(top_vectors=as_vectors(top_frame),
-                                           bottom_vectors=as_vectors(bottom_frame) if two else None, mask_top=mask_top,
-                                           mask_bottom=mask_bottom, k=k, attribute_constraints=attribute_constraints)
-    return _found_items(index, indices, distances)
+    window = _similar_window(index, _vector_maps(z_top), _vector_maps(z_bottom), mask, layer, start_index_top)
+    return _search_window(index, index.search_soft, window, vectors=True, k=k, attribute_constraints=attribute_constraints)
 
 
 @torch.no_grad()
@@ -1012,74 +1015,10 @@ def similar_fragments_to_spectrogram(index, vqvae, spectrogram: torch.Tensor, st
     z_top, z_bottom, _, _ = vqvae.encode_vectors(spectrogram)
     if z_top.shape[0] != 1:
         raise ValueError(f"one sound per call: the spectrogram holds {z_top.shape[0]}")
-    as_maps = lambda z: z.permute(0, 3, 1, 2)                                          # noqa: E731  [1, D, F, T]
-    query_top, query_bottom, mask_top, mask_bottom, two = _fragment_window(
-        index, as_maps(z_top), as_maps(z_bottom) if two_layers else None, start_index_top, width_top, mask, layer)
-    as_vectors = lambda m: m.permute(0, 2, 3, 1).to(index.device)                      # noqa: E731
-    indices, shifts, distances = index.search_shifted_soft(
-        top_vectors=as_vectors(query_top), bottom_vectors=as_vectors(query_bottom) if two else None, mask_top=mask_top,
-        mask_bottom=mask_bottom, k=k, shift_range=shift_range, attribute_constraints=attribute_constraints)
-    return _found_items(index, indices, distances, shifts.tolist())
-
-
-def _paste_columns(sound: torch.Tensor, item: torch.Tensor, mask: torch.Tensor, start: int, shift: int) -> torch.Tensor:
-    """sound [1,F,T] with the cells under mask [1,F,W] (over the columns start .. start + W - 1) taken from item [1,F,T_i]:
-    column col from item column col - start + shift; columns outside the sound or the item stay as they are."""
-    sound = sound.clone()
-    columns = torch.arange(mask.shape[-1]) + int(start)
-    source = columns - int(start) + int(shift)
-    inside = (columns >= 0) & (columns < sound.shape[-1]) & (source >= 0) & (source < item.shape[-1])
-    chosen = mask.to(sound.device)[..., inside.to(sound.device)]
-    columns, source = columns[inside].to(sound.device), source[inside].to(sound.device)
-    sound[..., columns] = torch.where(chosen, item.to(sound.device, sound.dtype)[..., source], sound[..., columns])
-    return sound
-
-
-def paste_fragment(top_code: torch.Tensor, bottom_code: torch.Tensor, item_top: torch.Tensor, item_bottom: torch.Tensor,
-                   mask: torch.Tensor, layer: str, window_start_top: int, shift_top: int):
-    """Fill a hole with a retrieved sound's codes: the cells of (top_code [1,F_t,T], bottom_code [1,F_b,T_b]) under
-    mask bool [1,F,W] -- in the resolution of `layer`, over the window that starts at top column `window_start_top` -- take
-    the codes of (item_top, item_bottom), sound column `col` from item column `col - window_start_top + shift_top` (in
-    bottom columns: both scaled by the time ratio).  A top-layer mask extends to the bottom layer as `timerange_change`
-    extends it; a bottom-layer mask leaves the top map alone.  Cells whose source column falls outside the item stay
-    unchanged.  Pure indexing: works on CPU tensors.  Returns the new (top, bottom)."""
-    if layer not in ('top', 'bottom'):
-        raise ValueError(f"unknown layer {layer}")
-    top_code, bottom_code = top_code.reshape(1, *top_code.shape[-2:]), bottom_code.reshape(1, *bottom_code.shape[-2:])
-    item_top, item_bottom = item_top.reshape(1, *item_top.shape[-2:]), item_bottom.reshape(1, *item_bottom.shape[-2:])
-    mask = mask.reshape(1, *mask.shape[-2:])
-    ratio_t, ratio_f = bottom_code.shape[-1] // top_code.shape[-1], bottom_code.shape[-2] // top_code.shape[-2]
-    rows = top_code.shape[-2] if layer == 'top' else bottom_code.shape[-2]
-    if mask.dtype != torch.bool or mask.shape[-2] != rows:
-        raise ValueError(f"mask: expected bool [1, {rows}, W] in the {layer} layer's resolution, got "
-                         f"{mask.dtype} {tuple(mask.shape)}")
-    start, shift = int(window_start_top), int(shift_top)
-    if layer == 'top':
-        top_code = _paste_columns(top_code, item_top, mask, start, shift)
-        mask = mask.repeat_interleave(ratio_f, -2).repeat_interleave(ratio_t, -1)
-    else:
-        top_code = top_code.clone()
-    return top_code, _paste_columns(bottom_code, item_bottom, mask, ratio_t * start, ratio_t * shift)
-
-
-def similar_sounds_warped(index, top_code: torch.Tensor, bottom_code: Optional[torch.Tensor], mask: Optional[torch.Tensor] = None,
-                          layer: str = 'top', start_index_top: int = 0, k: int = 8, drift: Tuple[int, int] = (-4, 4),
-                          attribute_constraints: Optional[Mapping[str, object]] = None):
-    """`similar_sounds` for sounds that unfold a little faster or slower than the query: the same window, masks and returned
-    list, compared by `CodeIndex.search_warped` -- every query column is matched to one item column, the item's time may
-    hold, step or skip from one query column to the next, and its drift against the query stays in drift=(lo, hi) top
-    columns (DESIGN.md section 6c.3).  `CodeIndex.warp_paths` gives the alignment of a returned item, `paste_warped` copies
-    codes along it."""
-    top_code = top_code.reshape(1, *top_code.shape[-2:])
-    if bottom_code is not None:
-        bottom_code = bottom_code.reshape(1, *bottom_code.shape[-2:])
-    top_frame, bottom_frame, mask_top, mask_bottom, two = _similar_window(index, top_code, bottom_code, mask, layer,
-                                                                          start_index_top)
-    device = index.device
-    indices, distances = index.search_warped(top_frame.to(device), bottom_frame.to(device) if two else None, mask_top=mask_top,
-                                             mask_bottom=mask_bottom, k=k, drift=drift,
-                                             attribute_constraints=attribute_constraints)
-    return _found_items(index, indices, distances)
+    window = _fragment_window(index, _vector_maps(z_top), _vector_maps(z_bottom if two_layers else None), start_index_top,
+                              width_top, mask, layer)
+    return _search_window(index, index.search_shifted_soft, window, vectors=True, k=k, shift_range=shift_range,
+                          attribute_constraints=attribute_constraints)
 
 
 def _paste_indexed(sound: torch.Tensor, item: torch.Tensor, mask: torch.Tensor, columns: torch.Tensor,
@@ -1094,6 +1033,56 @@ def _paste_indexed(sound: torch.Tensor, item: torch.Tensor, mask: torch.Tensor, 
     return sound
 
 
+def _paste_layers(top_code, bottom_code, item_top, item_bottom, mask, layer: str, columns_of, width_top: Optional[int] = None):
+    """What `paste_fragment` and `paste_warped` share: the maps and the mask as [1,F,T]; `layer`, the mask's type, its rows
+    and -- where the window's width in top columns is known -- its columns checked (ValueError); then the paste of both
+    layers for a top-layer mask, which extends to the bottom layer as `timerange_change` extends it, and of the bottom
+    layer alone for a bottom-layer mask.  columns_of(W, scale) -> (sound columns, item columns) under a mask of W columns
+    of a layer that has `scale` columns per top column."""
+    _check_layer(layer)
+    top_code, bottom_code, item_top, item_bottom, mask = (_one_map(m) for m in (top_code, bottom_code, item_top, item_bottom,
+                                                                                mask))
+    ratio_t, ratio_f = bottom_code.shape[-1] // top_code.shape[-1], bottom_code.shape[-2] // top_code.shape[-2]
+    rows = top_code.shape[-2] if layer == 'top' else bottom_code.shape[-2]
+    width = None if width_top is None else width_top * (1 if layer == 'top' else ratio_t)
+    if mask.dtype != torch.bool or mask.shape[-2] != rows or width not in (None, mask.shape[-1]):
+        raise ValueError(f"mask: expected bool [1, {rows}, {'W' if width is None else width}] in the {layer} layer's "
+                         f"resolution, got {mask.dtype} {tuple(mask.shape)}")
+    if layer == 'top':
+        top_code = _paste_indexed(top_code, item_top, mask, *columns_of(mask.shape[-1], 1))
+        mask = _bottom_mask(mask, ratio_f, ratio_t)
+    else:
+        top_code = top_code.clone()
+    return top_code, _paste_indexed(bottom_code, item_bottom, mask, *columns_of(mask.shape[-1], ratio_t))
+
+
+def paste_fragment(top_code: torch.Tensor, bottom_code: torch.Tensor, item_top: torch.Tensor, item_bottom: torch.Tensor,
+                   mask: torch.Tensor, layer: str, window_start_top: int, shift_top: int):
+    """Fill a hole with a retrieved sound's codes: the cells of (top_code [1,F_t,T], bottom_code [1,F_b,T_b]) under
+    mask bool [1,F,W] -- in the resolution of `layer`, over the window that starts at top column `window_start_top` -- take
+    the codes of (item_top, item_bottom), sound column `col` from item column `col - window_start_top + shift_top` (in
+    bottom columns: both scaled by the time ratio).  A top-layer mask extends to the bottom layer as `timerange_change`
+    extends it; a bottom-layer mask leaves the top map alone.  Cells whose source column falls outside the item stay
+    unchanged.  Pure indexing: works on CPU tensors.  Returns the new (top, bottom)."""
+    def columns_of(W, scale):                        # the mask's own width: any number of bottom columns for a bottom mask
+        start, shift = int(window_start_top), int(shift_top)
+        columns = torch.arange(W) + scale * start
+        return columns, columns + scale * (shift - start)
+    return _paste_layers(top_code, bottom_code, item_top, item_bottom, mask, layer, columns_of)
+
+
+def similar_sounds_warped(index, top_code: torch.Tensor, bottom_code: Optional[torch.Tensor], mask: Optional[torch.Tensor] = None,
+                          layer: str = 'top', start_index_top: int = 0, k: int = 8, drift: Tuple[int, int] = (-4, 4),
+                          attribute_constraints: Optional[Mapping[str, object]] = None):
+    """`similar_sounds` for sounds that unfold a little faster or slower than the query: the same window, masks and returned
+    list, compared by `CodeIndex.search_warped` -- every query column is matched to one item column, the item's time may
+    hold, step or skip from one query column to the next, and its drift against the query stays in drift=(lo, hi) top
+    columns (DESIGN.md section 6c.3).  `CodeIndex.warp_paths` gives the alignment of a returned item, `paste_warped` copies
+    codes along it."""
+    window = _similar_window(index, _one_map(top_code), _one_map(bottom_code), mask, layer, start_index_top)
+    return _search_window(index, index.search_warped, window, k=k, drift=drift, attribute_constraints=attribute_constraints)
+
+
 def paste_warped(top_code: torch.Tensor, bottom_code: torch.Tensor, item_top: torch.Tensor, item_bottom: torch.Tensor,
                  mask: torch.Tensor, start_index_top: int, path, layer: str = 'top'):
     """`paste_fragment` along a warped alignment: path [W] (`CodeIndex.warp_paths`) names, for the query column i that sits
@@ -1102,26 +1091,13 @@ def paste_warped(top_code: torch.Tensor, bottom_code: torch.Tensor, item_top: to
     column p(i), bottom columns r (start + i) + u from r p(i) + u, u < r.  A top-layer mask extends to the bottom layer as
     in `paste_fragment`; columns outside the sound or the item stay as they are.  With path[i] = o + i this is
     `paste_fragment` at shift_top = o, bit for bit.  Pure indexing: works on CPU tensors.  Returns the new (top, bottom)."""
-    if layer not in ('top', 'bottom'):
-        raise ValueError(f"unknown layer {layer}")
-    top_code, bottom_code = top_code.reshape(1, *top_code.shape[-2:]), bottom_code.reshape(1, *bottom_code.shape[-2:])
-    item_top, item_bottom = item_top.reshape(1, *item_top.shape[-2:]), item_bottom.reshape(1, *item_bottom.shape[-2:])
-    mask = mask.reshape(1, *mask.shape[-2:])
+    _check_layer(layer)
     path = torch.as_tensor(path).reshape(-1).to('cpu', torch.int64)
-    ratio_t, ratio_f = bottom_code.shape[-1] // top_code.shape[-1], bottom_code.shape[-2] // top_code.shape[-2]
-    rows, width = (top_code.shape[-2], len(path)) if layer == 'top' else (bottom_code.shape[-2], ratio_t * len(path))
-    if mask.dtype != torch.bool or tuple(mask.shape[-2:]) != (rows, width):
-        raise ValueError(f"mask: expected bool [1, {rows}, {width}] over the path's {len(path)} columns in the {layer} "
-                         f"layer's resolution, got {mask.dtype} {tuple(mask.shape)}")
-    columns = torch.arange(len(path)) + int(start_index_top)
-    if layer == 'top':
-        top_code = _paste_indexed(top_code, item_top, mask, columns, path)
-        mask = mask.repeat_interleave(ratio_f, -2).repeat_interleave(ratio_t, -1)
-    else:
-        top_code = top_code.clone()
-    fine = torch.arange(ratio_t)
-    wide = lambda c: (ratio_t * c[:, None] + fine[None, :]).reshape(-1)               # noqa: E731
-    return top_code, _paste_indexed(bottom_code, item_bottom, mask, wide(columns), wide(path))
+
+    def columns_of(W, scale):                        # every top column of the path as its `scale` columns of the layer
+        columns, fine = torch.arange(len(path)) + int(start_index_top), torch.arange(scale)
+        return tuple((scale * c[:, None] + fine[None, :]).reshape(-1) for c in (columns, path))
+    return _paste_layers(top_code, bottom_code, item_top, item_bottom, mask, layer, columns_of, width_top=len(path))
 
 
 def patch_from_database(index, top_code: torch.Tensor, bottom_code: torch.Tensor, mask: torch.Tensor, layer: str = 'top',
@@ -1131,10 +1107,8 @@ def patch_from_database(index, top_code: torch.Tensor, bottom_code: torch.Tensor
     `context_top` after it, clipped to the sound, with the hole masked -- "agree with what surrounds my hole, anywhere in
     time" (`similar_fragments`); each of the k nearest items is pasted into the hole at its best offset (`paste_fragment`).
     Returns a list of ((top [1,F_t,T], bottom [1,F_b,T_b]), attributes, distance, shift_top), nearest first."""
-    if layer not in ('top', 'bottom'):
-        raise ValueError(f"unknown layer {layer}")
-    top_code, bottom_code = top_code.reshape(1, *top_code.shape[-2:]), bottom_code.reshape(1, *bottom_code.shape[-2:])
-    mask = mask.reshape(1, *mask.shape[-2:])
+    _check_layer(layer)
+    top_code, bottom_code, mask = _one_map(top_code), _one_map(bottom_code), _one_map(mask)
     whole = top_code if layer == 'top' else bottom_code
     if mask.dtype != torch.bool or tuple(mask.shape[-2:]) != tuple(whole.shape[-2:]):
         raise ValueError(f"mask: expected bool [1, {whole.shape[-2]}, {whole.shape[-1]}] over the whole {layer} map, got "

@@ -33,8 +33,9 @@ distance is the least sum of `search_soft`'s column costs over all such paths; `
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 from collections import OrderedDict
-from typing import Mapping, Optional, Sequence, Tuple
+from typing import Mapping, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -68,6 +69,32 @@ def _as_codes(codes, name: str, n_embed: int) -> torch.Tensor:
     if hi >= n_embed:
         raise ValueError(f"{name}: codes must lie in [0, {n_embed}), found {hi}")
     return codes
+
+
+class _Stored(NamedTuple):
+    """One layer of the index: the stored maps [N, F, T] and the layer's quantiser, K codes of D dimensions."""
+    maps: torch.Tensor
+    F: int
+    T: int
+    quantizer: object
+    K: int
+    D: int
+
+
+@dataclasses.dataclass
+class _QueryLayer:
+    """One layer of a query, checked against the stored maps: data integer [Q, F, W] for kind 'code', floating
+    [Q, F, W, D] for 'vectors', [Q, F, W, K] for 'rows'; mask bool [F, W] / [1 or Q, F, W] or None; W == T unless the
+    search takes windows.  `_upload` adds what the kernels read."""
+    layer: str
+    kind: str
+    data: torch.Tensor
+    mask: Optional[torch.Tensor]
+    weight: float
+    single: bool
+    W: int
+    payload: Optional[torch.Tensor] = None            # uint16 [Q, C] codes, fp32 [Q, C, D] vectors or fp32 [Q, C, K] rows
+    weights: Optional[torch.Tensor] = None            # fp32 [Q, C]; None: every cell weighs 1
 
 
 class CodeIndex:
@@ -208,14 +235,25 @@ class CodeIndex:
             ok[torch.as_tensor([self._check_item(i) for i in exclude], dtype=torch.int64, device=self.device)] = False
         return ok.to(torch.uint8)
 
-    # ---- tables
-    def table(self, layer: str) -> torch.Tensor:
-        """The layer's code distance table [K, K] fp32, rebuilt when the codebook buffer changes."""
-        quantizer = self.vqvae.quantize_t if layer == 'top' else self.vqvae.quantize_b
-        embed = quantizer.embed
+    # ---- layers and tables
+    def _layer(self, layer: str, given: Optional[str] = None) -> _Stored:
+        """The 'top' or the 'bottom' layer of the index (ValueError, naming the argument `given`, when it holds none)."""
+        maps, quantizer = (self.top, self.vqvae.quantize_t) if layer == 'top' else (self.bottom, self.vqvae.quantize_b)
+        if maps is None:
+            raise ValueError(f"{given or 'a ' + layer + ' layer'} given, but the index holds no {layer} maps")
+        return _Stored(maps, int(maps.shape[1]), int(maps.shape[2]), quantizer, int(quantizer.n_embed), int(quantizer.dim))
+
+    def _embed(self, layer: str) -> torch.Tensor:
+        """The layer's codebook buffer [D, K], on the index's device (HipLibraryError otherwise)."""
+        embed = self._layer(layer).quantizer.embed
         _hip.require_gpu(embed, f"quantize_{layer[0]}.embed")
         if embed.device != self.device:
             raise _hip.HipLibraryError(f"the VQ-VAE lives on {embed.device}, the index on {self.device}")
+        return embed
+
+    def table(self, layer: str) -> torch.Tensor:
+        """The layer's code distance table [K, K] fp32, rebuilt when the codebook buffer changes."""
+        embed = self._embed(layer)
         key = (_hip.version_of(embed), embed.data_ptr(), embed.device)
         cached = self._tables.get(layer)
         if cached is None or cached[0] != key:
@@ -229,118 +267,130 @@ class CodeIndex:
             self._tables[layer] = cached
         return cached[1]
 
-    # ---- search
-    def _checked(self, layer: str, code, mask, window: bool = False):
-        """(code [Q, F, T], mask or None, single) of one layer, shapes checked against the stored maps (ValueError).
-        window: the query may be narrower than the stored maps, [Q, F, W] with 1 <= W <= T."""
-        stored = self.top if layer == 'top' else self.bottom
-        if stored is None:
-            raise ValueError(f"{layer}_code given, but the index holds no {layer} maps")
-        shape = tuple(stored.shape[1:])
-        code = torch.as_tensor(code)
-        if window:
-            if code.dim() not in (2, 3) or code.shape[-2] != shape[0] or not 1 <= code.shape[-1] <= shape[1] \
-                    or code.dtype.is_floating_point:
-                raise ValueError(f"{layer}_code: expected integer windows [{shape[0]}, W] (or [Q, ...]) with 1 <= W <= "
-                                 f"{shape[1]}, got {code.dtype} {tuple(code.shape)}")
-            shape = (shape[0], int(code.shape[-1]))
-        if code.dim() not in (2, 3) or tuple(code.shape[-2:]) != shape or code.dtype.is_floating_point:
-            raise ValueError(f"{layer}_code: expected integer codemaps [{shape[0]}, {shape[1]}] (or [Q, ...]) like the "
-                             f"stored ones, got {code.dtype} {tuple(code.shape)}")
-        single = code.dim() == 2 or code.shape[0] == 1
-        code = code.reshape(-1, *shape)
-        Q = code.shape[0]
+    # ---- a query: validation on the host (wherever the tensors live), then the upload
+    def _checked_layer(self, layer: str, code, vectors, rows, mask, weight: float, window: bool) -> _QueryLayer:
+        """One layer of a query, given as exactly one of code / vectors / rows, checked against the stored maps
+        (ValueError).  window: the query may be narrower than the stored maps, W columns with 1 <= W <= T."""
+        given = [kind for kind, value in (('code', code), ('vectors', vectors), ('rows', rows)) if value is not None]
+        if len(given) != 1:
+            raise ValueError(f"the {layer} layer takes one of {layer}_code, {layer}_vectors and {layer}_rows, got "
+                             + " and ".join(f"{layer}_{kind}" for kind in given))
+        kind, name = given[0], f"{layer}_{given[0]}"
+        stored = self._layer(layer, name)
+        F, T = stored.F, stored.T
+        data = torch.as_tensor({'code': code, 'vectors': vectors, 'rows': rows}[kind])
+        tail = {'code': (), 'vectors': (stored.D,), 'rows': (stored.K,)}[kind]       # what follows [F, W] in a query's shape
+        lead = data.dim() - 2 - len(tail)                                            # 1: a leading Q
+        if lead not in (0, 1) or data.dtype.is_floating_point != (kind != 'code') or tuple(data.shape[lead + 2:]) != tail \
+                or data.shape[lead] != F or not (1 <= data.shape[lead + 1] <= T if window else data.shape[lead + 1] == T):
+            wanted = [str(F), f"W (1 <= W <= {T})" if window else str(T)] + [str(n) for n in tail]
+            last = {'code': "", 'vectors': " and the layer's embedding dimension", 'rows': " and the layer's number of codes"}
+            raise ValueError(f"{name}: expected {'integer' if kind == 'code' else 'floating-point'} [{', '.join(wanted)}] "
+                             f"(or [Q, ...]) -- the stored maps' cells{last[kind]} -- got {data.dtype} {tuple(data.shape)}")
+        single = lead == 0 or data.shape[0] == 1
+        W = int(data.shape[lead + 1])
+        data = data.reshape(-1, F, W, *tail)
+        Q = data.shape[0]
         if not 1 <= Q <= MAX_QUERIES:
-            raise ValueError(f"{layer}_code: {Q} queries, a search takes 1..{MAX_QUERIES}")
+            raise ValueError(f"{name}: {Q} queries, a search takes 1..{MAX_QUERIES}")
         if mask is not None:
             mask = torch.as_tensor(mask)
-            if mask.dtype != torch.bool or mask.dim() not in (2, 3) or tuple(mask.shape[-2:]) != shape \
+            if mask.dtype != torch.bool or mask.dim() not in (2, 3) or tuple(mask.shape[-2:]) != (F, W) \
                     or (mask.dim() == 3 and mask.shape[0] not in (1, Q)):
-                raise ValueError(f"mask_{layer}: expected bool [{shape[0]}, {shape[1]}] (or [Q, ...]), got "
-                                 f"{mask.dtype} {tuple(mask.shape)}")
-        return code, mask, single
+                raise ValueError(f"mask_{layer}: expected bool [{F}, {W}] (or [Q, ...]), got {mask.dtype} {tuple(mask.shape)}")
+        return _QueryLayer(layer, kind, data, mask, float(weight), single, W)
 
-    def _query(self, layer: str, code: torch.Tensor, mask: Optional[torch.Tensor], weight: float):
-        """(query uint16 [Q, C], weights fp32 [Q, C] or None) of one checked layer, on the device."""
-        stored = self.top if layer == 'top' else self.bottom
-        if not code.is_cuda or (mask is not None and not mask.is_cuda) or not stored.is_cuda:
-            raise _hip.HipLibraryError(f"{layer}_code / mask_{layer} / the index live on "
-                                       f"{code.device} / {None if mask is None else mask.device} / {stored.device}: this "
-                                       "package computes only on an MI355X (HIP kernels, no CPU fallback)")
-        Q, shape = code.shape[0], tuple(code.shape[1:])
-        K = int(self.vqvae.n_embed_t if layer == 'top' else self.vqvae.n_embed_b)
-        code = code.to(self.device, torch.int64)
-        query = torch.where((code < 0) | (code > K), K, code).to(torch.uint16).reshape(Q, -1).contiguous()
-        weights = None
-        if mask is not None or float(weight) != 1.0:
-            keep = torch.ones(Q, *shape, dtype=torch.bool, device=self.device) if mask is None \
-                else ~mask.to(self.device).reshape(-1, *shape).expand(Q, *shape)
-            weights = (keep.to(torch.float32) * float(weight)).reshape(Q, -1).contiguous()
-        return query, weights
-
-    def distances(self, top_code=None, bottom_code=None, *, mask_top=None, mask_bottom=None,
-                  layer_weights: Tuple[float, float] = (1., 1.), allowed: Optional[torch.Tensor] = None):
-        """(dist fp32 [Q, N], single): layer_weights[0] dist_top + layer_weights[1] dist_bottom of every query against
-        every item; +inf where allowed[n] == 0."""
-        if top_code is None and bottom_code is None:
-            raise ValueError("search: give top_code, bottom_code or both")
+    def _checked_query(self, what: str, forms, masks, layer_weights, window: bool = False):
+        """The layers given of a query for the method `what`, validated before any device work (ValueError): forms =
+        ((top_code, top_vectors, top_rows), (bottom_code, ...)), masks = (mask_top, mask_bottom).  The layers hold equally
+        many queries; two windows need a common offset: T_b = r T_t and a bottom window of r W columns."""
+        if all(value is None for form in forms for value in form):
+            raise ValueError(f"{what}: give a top layer, a bottom layer or both (as *_code, *_vectors or *_rows)")
         if any(float(w) < 0 for w in layer_weights):
             raise ValueError(f"layer_weights must be >= 0, got {tuple(layer_weights)}")
-        checked = [(layer, weight) + self._checked(layer, code, mask)
-                   for layer, code, mask, weight in (('top', top_code, mask_top, layer_weights[0]),
-                                                     ('bottom', bottom_code, mask_bottom, layer_weights[1])) if code is not None]
-        if len({c[2].shape[0] for c in checked}) != 1:
-            raise ValueError("top_code and bottom_code hold different numbers of queries")
-        jobs = [(layer, 'code') + self._query(layer, code, mask, weight) + (int(code.shape[2]), single)
-                for layer, weight, code, mask, single in checked]
-        return self._aligned_distances(jobs, allowed)
+        layers = [self._checked_layer(layer, *form, mask, weight, window)
+                  for layer, form, mask, weight in zip(('top', 'bottom'), forms, masks, layer_weights)
+                  if any(value is not None for value in form)]
+        if len({q.data.shape[0] for q in layers}) != 1:
+            raise ValueError("the top and the bottom layer hold different numbers of queries")
+        if window and len(layers) == 2:
+            T_top, T_bottom = self.top.shape[2], self.bottom.shape[2]
+            ratio = T_bottom // T_top
+            if ratio < 1 or ratio * T_top != T_bottom:
+                raise ValueError(f"the bottom maps' {T_bottom} columns are no multiple of the top maps' {T_top}: a two-layer "
+                                 "search of windows has no common offset")
+            if layers[1].W != ratio * layers[0].W:
+                raise ValueError(f"bottom_{layers[1].kind}: the bottom window holds {layers[1].W} columns, but the top "
+                                 f"window's {layers[0].W} columns span {ratio * layers[0].W} of the bottom layer")
+        return layers
 
-    def search(self, top_code=None, bottom_code=None, *, mask_top=None, mask_bottom=None,
-               layer_weights: Tuple[float, float] = (1., 1.), k: int = 8,
-               attribute_constraints: Optional[Mapping[str, object]] = None, exclude: Optional[Sequence[int]] = None):
-        """The k nearest stored items: (indices int64 [k], distances float32 [k]), ordered by (distance, index) ascending;
-        [Q, k] each for queries [Q, F, T] with Q > 1.  Codemaps are [F, T] or [1, F, T] in the stored shapes (ValueError
-        otherwise); mask_* bool, True = "do not compare here" (the region about to be regenerated: weight 0), as is every
-        query cell outside [0, n_embed) -- a query taken from an inpainting request carries the prior's mask token there.
-        attribute_constraints: `sample_from_database`'s equality on decoded attributes; exclude: item indices left out.
-        Fewer than k allowed items: as many as there are; none: LookupError.  CPU tensors: HipLibraryError."""
+    def _plan(self, what: str, forms, masks, layer_weights, extent=None):
+        """(checked layers, extent(T, W)) -- a search over windows hands in `extent`, which turns the stored T and the
+        window's W, in the columns of the first layer given, into its offsets or its drifts; () for whole maps."""
+        layers = self._checked_query(what, forms, masks, layer_weights, window=extent is not None)
+        return layers, (() if extent is None else extent(self._layer(layers[0].layer).T, layers[0].W))
+
+    def _upload(self, q: _QueryLayer) -> _QueryLayer:
+        """The checked layer with payload and weights on the device (HipLibraryError for CPU tensors): a code layer's
+        cells outside [0, K) become the mask token K."""
+        stored = self._layer(q.layer)
+        if not q.data.is_cuda or (q.mask is not None and not q.mask.is_cuda) or not stored.maps.is_cuda:
+            raise _hip.HipLibraryError(f"{q.layer}_{q.kind} / mask_{q.layer} / the index live on "
+                                       f"{q.data.device} / {None if q.mask is None else q.mask.device} / {stored.maps.device}: "
+                                       "this package computes only on an MI355X (HIP kernels, no CPU fallback)")
+        Q, shape = q.data.shape[0], (stored.F, q.W)
+        if q.kind == 'code':
+            code = q.data.to(self.device, torch.int64)
+            payload = torch.where((code < 0) | (code > stored.K), stored.K, code).to(torch.uint16).reshape(Q, -1).contiguous()
+        else:
+            payload = q.data.to(self.device, torch.float32).reshape(Q, stored.F * q.W, -1).contiguous()
+        weights = None
+        if q.mask is not None or q.weight != 1.0:
+            keep = torch.ones(Q, *shape, dtype=torch.bool, device=self.device) if q.mask is None \
+                else ~q.mask.to(self.device).reshape(-1, *shape).expand(Q, *shape)
+            weights = (keep.to(torch.float32) * q.weight).reshape(Q, -1).contiguous()
+        return dataclasses.replace(q, payload=payload, weights=weights)
+
+    def _rows_group_size(self, layers, counted=('vectors',)) -> int:
+        """Queries per launch so that the rows made for them, [g, C, K] fp32 per layer of a kind in `counted`, stay under
+        ROWS_BUDGET_BYTES (at least 1).  Rows the caller hands over exist already and are never counted."""
+        per_query = max([q.payload.shape[1] * self._layer(q.layer).K * 4 for q in layers if q.kind in counted] or [0])
+        return MAX_QUERIES if per_query == 0 else max(1, min(MAX_QUERIES, ROWS_BUDGET_BYTES // per_query))
+
+    def _rows_of(self, q: _QueryLayer, q0: int, q1: int) -> torch.Tensor:
+        """rows fp32 [q1 - q0, C, K] of a vectors or rows layer, built on the device for a vectors layer."""
+        if q.kind == 'rows':
+            return q.payload[q0:q1]
+        self._embed(q.layer)
+        return self._layer(q.layer).quantizer.distance_rows(q.payload[q0:q1])
+
+    def _grow_workspace(self, need: int) -> None:
+        if self._workspace is None or self._workspace.numel() * 4 < need:
+            self._workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=self.device)
+
+    # ---- what the searches share around the distances: the order of their steps, who is admitted, the ranking
+    def _distances(self, what: str, forms, masks, layer_weights, distances, allowed, extent=None):
+        """(dist fp32 [Q, N], single) of the aligned or the warped routine `distances`: plan, upload, launch."""
+        layers, extent = self._plan(what, forms, masks, layer_weights, extent)
+        return distances([self._upload(q) for q in layers], *extent, allowed), all(q.single for q in layers)
+
+    def _search(self, what: str, forms, masks, layer_weights, k: int, attribute_constraints, exclude, distances, extent=None,
+                rank=None):
+        """Every search, in one order: k and the query are checked (ValueError), then who is admitted (LookupError), and
+        only then anything is uploaded (HipLibraryError) and launched -- `distances(layers, *extent, allowed)` -- and
+        ranked: by `rank`, or the k nearest of dist [Q, N]."""
         if int(k) < 1:
             raise ValueError(f"k must be at least 1, not {k}")
+        layers, extent = self._plan(what, forms, masks, layer_weights, extent)
         allowed = self.allowed(attribute_constraints, exclude)
-        dist, single = self.distances(top_code, bottom_code, mask_top=mask_top, mask_bottom=mask_bottom,
-                                      layer_weights=layer_weights, allowed=allowed)
-        values, order = self._nearest(dist, k, self._admitted(allowed, attribute_constraints, exclude))
+        n_allowed = self._admitted(allowed, attribute_constraints, exclude)
+        found = distances([self._upload(q) for q in layers], *extent, allowed)
+        single = all(q.single for q in layers)
+        if rank is not None:
+            return rank(found, layers[0].data.shape[0], *extent, allowed, n_allowed, k, single)
+        values, order = self._nearest(found, k, n_allowed)
         return (order[0], values[0]) if single else (order, values)
 
-    def _aligned_distances(self, jobs, allowed: Optional[torch.Tensor]):
-        """(dist fp32 [Q, N], single) of jobs (layer, kind, payload, weights, W, single): a code layer (payload = the uint16
-        query [Q, C]) through isi_code_search_f32, a vectors or rows layer through isi_code_search_rows_f32, the layers
-        after the first accumulated; the queries in groups that keep the rows built from vectors under ROWS_BUDGET_BYTES."""
-        Q, N = jobs[0][2].shape[0], len(self)
-        lib, stream = _hip.lib(), C.c_void_p(_hip.stream_ptr(self.device))
-        dist = torch.empty(Q, N, dtype=torch.float32, device=self.device)
-        group = self._rows_group_size(jobs)
-        for q0 in range(0, Q, group):
-            q1 = min(Q, q0 + group)
-            for n_done, job in enumerate(jobs):
-                layer, kind, payload, weights = job[:4]
-                stored = self.top if layer == 'top' else self.bottom
-                cells = payload.shape[1]
-                K = int((self.vqvae.quantize_t if layer == 'top' else self.vqvae.quantize_b).n_embed)
-                self._grow_workspace(lib.isi_code_search_workspace_bytes(N, cells, K, q1 - q0))
-                common = (None if allowed is None else allowed.data_ptr(), dist[q0:q1].data_ptr(), N, cells, K, q1 - q0,
-                          int(n_done > 0), self._workspace.data_ptr(), self._workspace.numel() * 4, stream)
-                w_ptr = None if weights is None else weights[q0:q1].data_ptr()
-                if kind == 'code':
-                    _hip.check(lib.isi_code_search_f32(stored.data_ptr(), payload[q0:q1].data_ptr(), w_ptr,
-                                                       self.table(layer).data_ptr(), *common), "isi_code_search_f32")
-                else:
-                    rows = self._rows_of(job, q0, q1)
-                    _hip.check(lib.isi_code_search_rows_f32(stored.data_ptr(), rows.data_ptr(), w_ptr, *common),
-                               "isi_code_search_rows_f32")
-        return dist, all(job[5] for job in jobs)
-
-    # ---- what the searches share after the distances: who is admitted, the ranking, the best offset
     def _admitted(self, allowed: Optional[torch.Tensor], attribute_constraints, exclude) -> int:
         """How many items `allowed` admits (LookupError when none)."""
         count = len(self) if allowed is None else int(allowed.sum())
@@ -372,35 +422,53 @@ class CodeIndex:
         shifts = torch.gather(best_shift, 1, order).to(torch.int64) + lo
         return (order[0], shifts[0], values[0]) if single else (order, shifts, values)
 
+    # ---- aligned search (csrc/code_search.hip)
+    def _aligned_distances(self, layers, allowed: Optional[torch.Tensor]) -> torch.Tensor:
+        """dist fp32 [Q, N] of uploaded layers: a code layer through isi_code_search_f32, a vectors or rows layer through
+        isi_code_search_rows_f32, the layers after the first accumulated; the queries in groups that keep the rows built
+        from vectors under ROWS_BUDGET_BYTES."""
+        Q, N = layers[0].payload.shape[0], len(self)
+        lib, stream = _hip.lib(), C.c_void_p(_hip.stream_ptr(self.device))
+        dist = torch.empty(Q, N, dtype=torch.float32, device=self.device)
+        group = self._rows_group_size(layers)
+        for q0 in range(0, Q, group):
+            q1 = min(Q, q0 + group)
+            for n_done, q in enumerate(layers):
+                stored = self._layer(q.layer)
+                cells = q.payload.shape[1]
+                self._grow_workspace(lib.isi_code_search_workspace_bytes(N, cells, stored.K, q1 - q0))
+                common = (None if allowed is None else allowed.data_ptr(), dist[q0:q1].data_ptr(), N, cells, stored.K, q1 - q0,
+                          int(n_done > 0), self._workspace.data_ptr(), self._workspace.numel() * 4, stream)
+                w_ptr = None if q.weights is None else q.weights[q0:q1].data_ptr()
+                if q.kind == 'code':
+                    _hip.check(lib.isi_code_search_f32(stored.maps.data_ptr(), q.payload[q0:q1].data_ptr(), w_ptr,
+                                                       self.table(q.layer).data_ptr(), *common), "isi_code_search_f32")
+                else:
+                    rows = self._rows_of(q, q0, q1)
+                    _hip.check(lib.isi_code_search_rows_f32(stored.maps.data_ptr(), rows.data_ptr(), w_ptr, *common),
+                               "isi_code_search_rows_f32")
+        return dist
+
+    def distances(self, top_code=None, bottom_code=None, *, mask_top=None, mask_bottom=None,
+                  layer_weights: Tuple[float, float] = (1., 1.), allowed: Optional[torch.Tensor] = None):
+        """(dist fp32 [Q, N], single): layer_weights[0] dist_top + layer_weights[1] dist_bottom of every query against
+        every item; +inf where allowed[n] == 0."""
+        return self._distances("search", ((top_code, None, None), (bottom_code, None, None)), (mask_top, mask_bottom),
+                               layer_weights, self._aligned_distances, allowed)
+
+    def search(self, top_code=None, bottom_code=None, *, mask_top=None, mask_bottom=None,
+               layer_weights: Tuple[float, float] = (1., 1.), k: int = 8,
+               attribute_constraints: Optional[Mapping[str, object]] = None, exclude: Optional[Sequence[int]] = None):
+        """The k nearest stored items: (indices int64 [k], distances float32 [k]), ordered by (distance, index) ascending;
+        [Q, k] each for queries [Q, F, T] with Q > 1.  Codemaps are [F, T] or [1, F, T] in the stored shapes (ValueError
+        otherwise); mask_* bool, True = "do not compare here" (the region about to be regenerated: weight 0), as is every
+        query cell outside [0, n_embed) -- a query taken from an inpainting request carries the prior's mask token there.
+        attribute_constraints: `sample_from_database`'s equality on decoded attributes; exclude: item indices left out.
+        Fewer than k allowed items: as many as there are; none: LookupError.  CPU tensors: HipLibraryError."""
+        return self._search("search", ((top_code, None, None), (bottom_code, None, None)), (mask_top, mask_bottom),
+                            layer_weights, k, attribute_constraints, exclude, self._aligned_distances)
+
     # ---- shift-invariant search (csrc/code_shift_search.hip)
-    def _shift_plan(self, top_code, bottom_code, mask_top, mask_bottom, layer_weights, shift_range):
-        """Validation and geometry of a shifted search, before any device work: (checked layers, lo, count) with the
-        offsets lo .. lo + count - 1 in the columns of the first layer given."""
-        if top_code is None and bottom_code is None:
-            raise ValueError("search_shifted: give top_code, bottom_code or both")
-        if any(float(w) < 0 for w in layer_weights):
-            raise ValueError(f"layer_weights must be >= 0, got {tuple(layer_weights)}")
-        checked = [(layer, weight) + self._checked(layer, code, mask, window=True)
-                   for layer, code, mask, weight in (('top', top_code, mask_top, layer_weights[0]),
-                                                     ('bottom', bottom_code, mask_bottom, layer_weights[1])) if code is not None]
-        if len({c[2].shape[0] for c in checked}) != 1:
-            raise ValueError("top_code and bottom_code hold different numbers of queries")
-        stored = self.top if checked[0][0] == 'top' else self.bottom
-        T, W = int(stored.shape[2]), int(checked[0][2].shape[2])
-        if len(checked) == 2:
-            self._check_two_layer_windows(W, int(checked[1][2].shape[2]), "bottom_code")
-        return (checked,) + self._shift_offsets(T, W, shift_range)
-
-    def _check_two_layer_windows(self, W: int, W_bottom: int, name: str) -> None:
-        """A two-layer shifted search needs a common offset: T_b = r T_t and a bottom window of r W columns (ValueError)."""
-        ratio = self.bottom.shape[2] // self.top.shape[2]
-        if ratio < 1 or ratio * self.top.shape[2] != self.bottom.shape[2]:
-            raise ValueError(f"the bottom maps' {self.bottom.shape[2]} columns are no multiple of the top maps' "
-                             f"{self.top.shape[2]}: a two-layer shifted search has no common offset")
-        if W_bottom != ratio * W:
-            raise ValueError(f"{name}: {W_bottom} columns, but the top window's {W} columns span {ratio * W} of the bottom "
-                             "layer")
-
     @staticmethod
     def _shift_offsets(T: int, W: int, shift_range):
         """(lo, count): the offsets lo .. lo + count - 1 at which a window of W columns fits the stored T, inside
@@ -415,29 +483,55 @@ class CodeIndex:
                                  f"the stored {T}")
         return lo, hi - lo
 
-    def _shifted_jobs(self, checked):
-        """The layers of a hard shifted search as the jobs `_shifted_groups` runs: (layer, 'code', query, weights, W, single)."""
-        jobs = []
-        for layer, weight, code, mask, single in checked:
-            query, weights = self._query(layer, code, mask, weight)
-            jobs.append((layer, 'code', query, weights, int(code.shape[2]), single))
-        return jobs
-
-    def _shifted_group_size(self, jobs, count) -> int:
+    def _shifted_group_size(self, layers, count) -> int:
         """Queries per launch so that workspace + dist [g, S, N] stay under SHIFT_BUDGET_BYTES (at least 1)."""
         N = len(self)
-        runs = max(-(-(self.top if job[0] == 'top' else self.bottom).shape[1] * job[4] // 256) for job in jobs)
+        runs = max(-(-self._layer(q.layer).F * q.W // 256) for q in layers)
         per_query = (1 + (runs if runs > 1 else 0)) * count * N * 4
         return max(1, min(MAX_QUERIES, SHIFT_BUDGET_BYTES // per_query))
+
+    def _shifted_groups(self, layers, lo: int, count: int, allowed=None):
+        """Yields (q0, q1, dist [q1 - q0, count, N]) group by group, for the hard and the soft shifted searches: a code layer
+        through isi_code_shift_search_f32, a vectors or rows layer through isi_code_shift_search_rows_f32.  The launch
+        starts at a multiple of 8 columns (the kernel reads aligned vectors from there); the offsets below `lo` are computed
+        and dropped.  (`allowed` plays no part at a single offset: `_best_over_shifts` applies it.)"""
+        lib, stream = _hip.lib(), C.c_void_p(_hip.stream_ptr(self.device))
+        Q, N = layers[0].payload.shape[0], len(self)
+        first = lo - lo % 8
+        S = count + lo - first
+        group = min(self._shifted_group_size(layers, S), self._rows_group_size(layers))
+        ratio = 1 if len(layers) == 1 else self.bottom.shape[2] // self.top.shape[2]
+        for q0 in range(0, Q, group):
+            q1 = min(Q, q0 + group)
+            dist = torch.empty(q1 - q0, S, N, dtype=torch.float32, device=self.device)
+            for n_done, q in enumerate(layers):
+                stored = self._layer(q.layer)
+                step = ratio if n_done > 0 else 1
+                self._grow_workspace(lib.isi_code_shift_search_workspace_bytes(N, stored.F, stored.T, q.W, S, stored.K, q1 - q0))
+                common = (dist.data_ptr(), N, stored.F, stored.T, q.W, step * first, step, S, stored.K, q1 - q0, int(n_done > 0),
+                          self._workspace.data_ptr(), self._workspace.numel() * 4, stream)
+                w_ptr = None if q.weights is None else q.weights[q0:q1].data_ptr()
+                if q.kind == 'code':
+                    _hip.check(lib.isi_code_shift_search_f32(stored.maps.data_ptr(), q.payload[q0:q1].data_ptr(), w_ptr,
+                                                             self.table(q.layer).data_ptr(), *common), "isi_code_shift_search_f32")
+                else:
+                    rows = self._rows_of(q, q0, q1)
+                    _hip.check(lib.isi_code_shift_search_rows_f32(stored.maps.data_ptr(), rows.data_ptr(), w_ptr, *common),
+                               "isi_code_shift_search_rows_f32")
+            yield q0, q1, (dist if first == lo else dist[:, lo - first:].contiguous())
+
+    def _distances_shifted(self, what: str, forms, masks, layer_weights, shift_range) -> torch.Tensor:
+        """dist fp32 [Q, S, N] of every offset: plan, upload, launch, the groups joined."""
+        layers, (lo, count) = self._plan(what, forms, masks, layer_weights, lambda T, W: self._shift_offsets(T, W, shift_range))
+        return torch.cat([dist for _, _, dist in self._shifted_groups([self._upload(q) for q in layers], lo, count)], 0)
 
     def distances_shifted(self, top_code=None, bottom_code=None, *, mask_top=None, mask_bottom=None,
                           layer_weights: Tuple[float, float] = (1., 1.), shift_range: Optional[Tuple[int, int]] = None):
         """dist fp32 [Q, S, N]: the distance of every query window to every item at every offset of `search_shifted`
         (dist[:, s] belongs to the offset lo + s, lo = the first allowed one).  Q S N floats: for callers that want
         every offset, not for the whole of a large database at once."""
-        checked, lo, count = self._shift_plan(top_code, bottom_code, mask_top, mask_bottom, layer_weights, shift_range)
-        jobs = self._shifted_jobs(checked)
-        return torch.cat([dist for _, _, dist in self._shifted_groups(jobs, lo, count)], 0)
+        return self._distances_shifted("search_shifted", ((top_code, None, None), (bottom_code, None, None)),
+                                       (mask_top, mask_bottom), layer_weights, shift_range)
 
     def search_shifted(self, top_code=None, bottom_code=None, *, mask_top=None, mask_bottom=None,
                        layer_weights: Tuple[float, float] = (1., 1.), k: int = 8,
@@ -452,118 +546,19 @@ class CodeIndex:
         attribute_constraints, exclude, the (distance, item index) order, LookupError / ValueError / HipLibraryError: as
         `search`.  The queries run in groups whose workspace and dist [Q, S, N] stay under SHIFT_BUDGET_BYTES; distances
         are query- and item-local, so the grouping changes no bit."""
-        if int(k) < 1:
-            raise ValueError(f"k must be at least 1, not {k}")
-        checked, lo, count = self._shift_plan(top_code, bottom_code, mask_top, mask_bottom, layer_weights, shift_range)
-        allowed = self.allowed(attribute_constraints, exclude)
-        n_allowed = self._admitted(allowed, attribute_constraints, exclude)
-        jobs = self._shifted_jobs(checked)
-        return self._best_over_shifts(self._shifted_groups(jobs, lo, count), jobs[0][2].shape[0], lo, count, allowed, n_allowed,
-                                      k, all(job[5] for job in jobs))
+        return self._search("search_shifted", ((top_code, None, None), (bottom_code, None, None)), (mask_top, mask_bottom),
+                            layer_weights, k, attribute_constraints, exclude, self._shifted_groups,
+                            lambda T, W: self._shift_offsets(T, W, shift_range), self._best_over_shifts)
 
     # ---- search by encoder vectors: per-cell distance rows (DESIGN.md section 6c.2)
-    def _checked_soft(self, layer: str, code, vectors, rows, mask, window: bool = False):
-        """One layer of a soft query, given as exactly one of code / vectors / rows, checked before any device work:
-        (kind, data, mask or None, single) with data [Q, F, W] for kind 'code' (as `_checked`), [Q, F, W, D] for
-        'vectors', [Q, F, W, K] for 'rows'; W == T unless `window`."""
-        given = [kind for kind, value in (('code', code), ('vectors', vectors), ('rows', rows)) if value is not None]
-        if len(given) != 1:
-            raise ValueError(f"the {layer} layer takes one of {layer}_code, {layer}_vectors and {layer}_rows, got "
-                             + " and ".join(f"{layer}_{kind}" for kind in given))
-        kind = given[0]
-        if kind == 'code':
-            return ('code',) + self._checked(layer, code, mask, window)
-        name = f"{layer}_{kind}"
-        stored = self.top if layer == 'top' else self.bottom
-        if stored is None:
-            raise ValueError(f"{name} given, but the index holds no {layer} maps")
-        quantizer = self.vqvae.quantize_t if layer == 'top' else self.vqvae.quantize_b
-        last = int(quantizer.dim) if kind == 'vectors' else int(quantizer.n_embed)
-        F, T = int(stored.shape[1]), int(stored.shape[2])
-        data = torch.as_tensor(vectors if kind == 'vectors' else rows)
-        columns = f"W, {last}] with 1 <= W <= {T}" if window else f"{T}, {last}]"
-        if data.dim() not in (3, 4) or not data.dtype.is_floating_point or data.shape[-1] != last or data.shape[-3] != F \
-                or not (1 <= data.shape[-2] <= T if window else data.shape[-2] == T):
-            raise ValueError(f"{name}: expected floating-point [{F}, {columns} (or [Q, ...]) -- the stored maps' cells and "
-                             f"the layer's {'embedding dimension' if kind == 'vectors' else 'number of codes'} -- got "
-                             f"{data.dtype} {tuple(data.shape)}")
-        single = data.dim() == 3 or data.shape[0] == 1
-        W = int(data.shape[-2])
-        data = data.reshape(-1, F, W, last)
-        Q = data.shape[0]
-        if not 1 <= Q <= MAX_QUERIES:
-            raise ValueError(f"{name}: {Q} queries, a search takes 1..{MAX_QUERIES}")
-        if mask is not None:
-            mask = torch.as_tensor(mask)
-            if mask.dtype != torch.bool or mask.dim() not in (2, 3) or tuple(mask.shape[-2:]) != (F, W) \
-                    or (mask.dim() == 3 and mask.shape[0] not in (1, Q)):
-                raise ValueError(f"mask_{layer}: expected bool [{F}, {W}] (or [Q, ...]), got {mask.dtype} {tuple(mask.shape)}")
-        return kind, data, mask, single
-
-    def _soft_layers(self, what: str, forms, masks, layer_weights, window: bool):
-        """[(layer, weight, kind, data, mask, single)] of the layers given, validated (ValueError)."""
-        if all(value is None for form in forms for value in form):
-            raise ValueError(f"{what}: give a top layer, a bottom layer or both (as *_code, *_vectors or *_rows)")
-        if any(float(w) < 0 for w in layer_weights):
-            raise ValueError(f"layer_weights must be >= 0, got {tuple(layer_weights)}")
-        checked = [(layer, weight) + self._checked_soft(layer, *form, mask, window)
-                   for layer, form, mask, weight in zip(('top', 'bottom'), forms, masks, layer_weights)
-                   if any(value is not None for value in form)]
-        if len({c[3].shape[0] for c in checked}) != 1:
-            raise ValueError("the top and the bottom layer hold different numbers of queries")
-        return checked
-
-    def _soft_job(self, layer: str, weight: float, kind: str, data: torch.Tensor, mask, single: bool):
-        """(layer, kind, payload, weights fp32 [Q, C] or None, W, single) on the device: payload is the uint16 query [Q, C]
-        of a code layer, fp32 [Q, C, D] vectors or fp32 [Q, C, K] rows otherwise."""
-        if kind == 'code':
-            query, weights = self._query(layer, data, mask, weight)
-            return layer, kind, query, weights, int(data.shape[2]), single
-        stored = self.top if layer == 'top' else self.bottom
-        if not data.is_cuda or (mask is not None and not mask.is_cuda) or not stored.is_cuda:
-            raise _hip.HipLibraryError(f"{layer}_{kind} / mask_{layer} / the index live on "
-                                       f"{data.device} / {None if mask is None else mask.device} / {stored.device}: this "
-                                       "package computes only on an MI355X (HIP kernels, no CPU fallback)")
-        Q, F, W, last = data.shape
-        payload = data.to(self.device, torch.float32).reshape(Q, F * W, last).contiguous()
-        weights = None
-        if mask is not None or float(weight) != 1.0:
-            keep = torch.ones(Q, F, W, dtype=torch.bool, device=self.device) if mask is None \
-                else ~mask.to(self.device).reshape(-1, F, W).expand(Q, F, W)
-            weights = (keep.to(torch.float32) * float(weight)).reshape(Q, -1).contiguous()
-        return layer, kind, payload, weights, W, single
-
-    def _rows_group_size(self, jobs) -> int:
-        """Queries per launch so that the rows built from vectors, [g, C, K] fp32 per layer, stay under ROWS_BUDGET_BYTES
-        (at least 1).  Rows the caller hands over exist already and are not counted."""
-        per_query = max([job[2].shape[1] * int((self.vqvae.quantize_t if job[0] == 'top' else self.vqvae.quantize_b).n_embed) * 4
-                         for job in jobs if job[1] == 'vectors'] or [0])
-        return MAX_QUERIES if per_query == 0 else max(1, min(MAX_QUERIES, ROWS_BUDGET_BYTES // per_query))
-
-    def _rows_of(self, job, q0: int, q1: int) -> torch.Tensor:
-        """rows fp32 [q1 - q0, C, K] of a vectors or rows layer, built on the device for a vectors layer."""
-        layer, kind, payload = job[0], job[1], job[2]
-        if kind == 'rows':
-            return payload[q0:q1]
-        quantizer = self.vqvae.quantize_t if layer == 'top' else self.vqvae.quantize_b
-        _hip.require_gpu(quantizer.embed, f"quantize_{layer[0]}.embed")
-        if quantizer.embed.device != self.device:
-            raise _hip.HipLibraryError(f"the VQ-VAE lives on {quantizer.embed.device}, the index on {self.device}")
-        return quantizer.distance_rows(payload[q0:q1])
-
-    def _grow_workspace(self, need: int) -> None:
-        if self._workspace is None or self._workspace.numel() * 4 < need:
-            self._workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=self.device)
-
     def distances_soft(self, top_code=None, bottom_code=None, *, top_vectors=None, bottom_vectors=None, top_rows=None,
                        bottom_rows=None, mask_top=None, mask_bottom=None, layer_weights: Tuple[float, float] = (1., 1.),
                        allowed: Optional[torch.Tensor] = None):
         """(dist fp32 [Q, N], single) as `distances`, each layer given as exactly one of codes (`distances`' launch), vectors
         [Q, F, T, D] (or [F, T, D]) -- dist = sum_c w[c] |z[c] - E[x[c]]|^2, the rows built on the device -- or ready rows
         [Q, F, T, K] of any per-cell cost."""
-        checked = self._soft_layers("search_soft", ((top_code, top_vectors, top_rows), (bottom_code, bottom_vectors, bottom_rows)),
-                                    (mask_top, mask_bottom), layer_weights, window=False)
-        return self._aligned_distances([self._soft_job(*c) for c in checked], allowed)
+        return self._distances("search_soft", ((top_code, top_vectors, top_rows), (bottom_code, bottom_vectors, bottom_rows)),
+                               (mask_top, mask_bottom), layer_weights, self._aligned_distances, allowed)
 
     def search_soft(self, top_code=None, bottom_code=None, *, top_vectors=None, bottom_vectors=None, top_rows=None,
                     bottom_rows=None, mask_top=None, mask_bottom=None, layer_weights: Tuple[float, float] = (1., 1.), k: int = 8,
@@ -578,66 +573,17 @@ class CodeIndex:
         bit give `search`'s distances bit for bit.  Everything else -- layer_weights, k, attribute_constraints, exclude,
         the (distance, index) order, LookupError / ValueError / HipLibraryError -- is `search`'s.  Rows are built for at
         most ROWS_BUDGET_BYTES of queries at a time; distances are query-local, so the grouping changes no bit."""
-        if int(k) < 1:
-            raise ValueError(f"k must be at least 1, not {k}")
-        allowed = self.allowed(attribute_constraints, exclude)
-        dist, single = self.distances_soft(top_code, bottom_code, top_vectors=top_vectors, bottom_vectors=bottom_vectors,
-                                           top_rows=top_rows, bottom_rows=bottom_rows, mask_top=mask_top,
-                                           mask_bottom=mask_bottom, layer_weights=layer_weights, allowed=allowed)
-        values, order = self._nearest(dist, k, self._admitted(allowed, attribute_constraints, exclude))
-        return (order[0], values[0]) if single else (order, values)
-
-    def _soft_shift_plan(self, forms, masks, layer_weights, shift_range):
-        """`_shift_plan` for soft layers: (checked layers, lo, count)."""
-        checked = self._soft_layers("search_shifted_soft", forms, masks, layer_weights, window=True)
-        stored = self.top if checked[0][0] == 'top' else self.bottom
-        T, W = int(stored.shape[2]), int(checked[0][3].shape[2])
-        if len(checked) == 2:
-            self._check_two_layer_windows(W, int(checked[1][3].shape[2]), "the bottom window")
-        return (checked,) + self._shift_offsets(T, W, shift_range)
-
-    def _shifted_groups(self, jobs, lo: int, count: int):
-        """Yields (q0, q1, dist [q1 - q0, count, N]) group by group, for the hard and the soft shifted searches: a code layer
-        through isi_code_shift_search_f32, a vectors or rows layer through isi_code_shift_search_rows_f32.  The launch
-        starts at a multiple of 8 columns (the kernel reads aligned vectors from there); the offsets below `lo` are computed
-        and dropped."""
-        lib, stream = _hip.lib(), C.c_void_p(_hip.stream_ptr(self.device))
-        Q, N = jobs[0][2].shape[0], len(self)
-        first = lo - lo % 8
-        S = count + lo - first
-        group = min(self._shifted_group_size(jobs, S), self._rows_group_size(jobs))
-        ratio = 1 if len(jobs) == 1 else self.bottom.shape[2] // self.top.shape[2]
-        for q0 in range(0, Q, group):
-            q1 = min(Q, q0 + group)
-            dist = torch.empty(q1 - q0, S, N, dtype=torch.float32, device=self.device)
-            for n_done, job in enumerate(jobs):
-                layer, kind, payload, weights, W = job[:5]
-                stored = self.top if layer == 'top' else self.bottom
-                F, T = int(stored.shape[1]), int(stored.shape[2])
-                K = int((self.vqvae.quantize_t if layer == 'top' else self.vqvae.quantize_b).n_embed)
-                step = ratio if n_done > 0 else 1
-                self._grow_workspace(lib.isi_code_shift_search_workspace_bytes(N, F, T, W, S, K, q1 - q0))
-                common = (dist.data_ptr(), N, F, T, W, step * first, step, S, K, q1 - q0, int(n_done > 0),
-                          self._workspace.data_ptr(), self._workspace.numel() * 4, stream)
-                w_ptr = None if weights is None else weights[q0:q1].data_ptr()
-                if kind == 'code':
-                    _hip.check(lib.isi_code_shift_search_f32(stored.data_ptr(), payload[q0:q1].data_ptr(), w_ptr,
-                                                             self.table(layer).data_ptr(), *common), "isi_code_shift_search_f32")
-                else:
-                    rows = self._rows_of(job, q0, q1)
-                    _hip.check(lib.isi_code_shift_search_rows_f32(stored.data_ptr(), rows.data_ptr(), w_ptr, *common),
-                               "isi_code_shift_search_rows_f32")
-            yield q0, q1, (dist if first == lo else dist[:, lo - first:].contiguous())
+        return self._search("search_soft", ((top_code, top_vectors, top_rows), (bottom_code, bottom_vectors, bottom_rows)),
+                            (mask_top, mask_bottom), layer_weights, k, attribute_constraints, exclude, self._aligned_distances)
 
     def distances_shifted_soft(self, top_code=None, bottom_code=None, *, top_vectors=None, bottom_vectors=None, top_rows=None,
                                bottom_rows=None, mask_top=None, mask_bottom=None,
                                layer_weights: Tuple[float, float] = (1., 1.), shift_range: Optional[Tuple[int, int]] = None):
         """dist fp32 [Q, S, N] as `distances_shifted`, for windows given per layer as codes, vectors [Q, F, W, D] or rows
         [Q, F, W, K] (`search_shifted_soft`)."""
-        checked, lo, count = self._soft_shift_plan(((top_code, top_vectors, top_rows), (bottom_code, bottom_vectors, bottom_rows)),
-                                                   (mask_top, mask_bottom), layer_weights, shift_range)
-        jobs = [self._soft_job(*c) for c in checked]
-        return torch.cat([dist for _, _, dist in self._shifted_groups(jobs, lo, count)], 0)
+        return self._distances_shifted("search_shifted_soft", ((top_code, top_vectors, top_rows),
+                                                               (bottom_code, bottom_vectors, bottom_rows)),
+                                       (mask_top, mask_bottom), layer_weights, shift_range)
 
     def search_shifted_soft(self, top_code=None, bottom_code=None, *, top_vectors=None, bottom_vectors=None, top_rows=None,
                             bottom_rows=None, mask_top=None, mask_bottom=None, layer_weights: Tuple[float, float] = (1., 1.),
@@ -650,25 +596,14 @@ class CodeIndex:
         masks, constraints, ordering and errors; the zero-weight rule and the bitwise agreement with the hard search on
         vectors that are codebook rows are `search_soft`'s.  The groups of queries respect both SHIFT_BUDGET_BYTES and
         ROWS_BUDGET_BYTES."""
-        if int(k) < 1:
-            raise ValueError(f"k must be at least 1, not {k}")
-        checked, lo, count = self._soft_shift_plan(((top_code, top_vectors, top_rows), (bottom_code, bottom_vectors, bottom_rows)),
-                                                   (mask_top, mask_bottom), layer_weights, shift_range)
-        allowed = self.allowed(attribute_constraints, exclude)
-        n_allowed = self._admitted(allowed, attribute_constraints, exclude)
-        jobs = [self._soft_job(*c) for c in checked]
-        return self._best_over_shifts(self._shifted_groups(jobs, lo, count), jobs[0][2].shape[0], lo, count, allowed,
-                                      n_allowed, k, all(job[5] for job in jobs))
+        return self._search("search_shifted_soft", ((top_code, top_vectors, top_rows), (bottom_code, bottom_vectors, bottom_rows)),
+                            (mask_top, mask_bottom), layer_weights, k, attribute_constraints, exclude, self._shifted_groups,
+                            lambda T, W: self._shift_offsets(T, W, shift_range), self._best_over_shifts)
 
     # ---- time-warped search (csrc/code_warp_search.hip; DESIGN.md section 6c.3)
-    def _warp_plan(self, what: str, forms, masks, layer_weights, drift):
-        """Validation and geometry of a warped search, before any device work: (checked layers, lo, hi), the drift in the
-        columns of the first layer given."""
-        checked = self._soft_layers(what, forms, masks, layer_weights, window=True)
-        stored = self.top if checked[0][0] == 'top' else self.bottom
-        T, W = int(stored.shape[2]), int(checked[0][3].shape[2])
-        if len(checked) == 2:
-            self._check_two_layer_windows(W, int(checked[1][3].shape[2]), "the bottom window")
+    @staticmethod
+    def _drift_band(T: int, W: int, drift):
+        """(lo, hi): the drifts of a warped search of W query columns over the stored T (ValueError)."""
         try:
             lo, hi = (int(d) for d in drift)
         except (TypeError, ValueError):
@@ -680,69 +615,61 @@ class CodeIndex:
         if hi < 0 or lo > T - 1 or W - 1 + hi < 0 or W - 1 + lo > T - 1:
             raise ValueError(f"drift {(lo, hi)} leaves the first or the last of {W} query columns without a column of the "
                              f"stored {T}")
-        return checked, lo, hi
+        return lo, hi
 
-    def _warp_rows(self, job, q0: int, q1: int):
+    def _warp_rows(self, q: _QueryLayer, q0: int, q1: int):
         """(rows fp32 [g, C, K], weights fp32 [g, C] or None) of one layer of a warped query: a code layer as rows gathered
         from the code distance table, its mask-token cells under weight 0."""
-        layer, kind, payload, weights = job[:4]
-        w = None if weights is None else weights[q0:q1]
-        if kind != 'code':
-            return self._rows_of(job, q0, q1), w
-        table = self.table(layer)
+        w = None if q.weights is None else q.weights[q0:q1]
+        if q.kind != 'code':
+            return self._rows_of(q, q0, q1), w
+        table = self.table(q.layer)
         K = table.shape[0]
-        query = payload[q0:q1].view(torch.int16).to(torch.int64).bitwise_and(0xFFFF)
+        query = q.payload[q0:q1].view(torch.int16).to(torch.int64).bitwise_and(0xFFFF)
         token = query >= K
         rows = table[torch.where(token, 0, query)].contiguous()
         if w is None:
             w = torch.ones(query.shape, dtype=torch.float32, device=self.device)
         return rows, torch.where(token, 0.0, w).contiguous()
 
-    def _warp_group_size(self, jobs) -> int:
-        """Queries per launch so that the rows built or gathered for them stay under ROWS_BUDGET_BYTES (at least 1)."""
-        per_query = max([job[2].shape[1] * int((self.vqvae.quantize_t if job[0] == 'top' else self.vqvae.quantize_b).n_embed) * 4
-                         for job in jobs if job[1] != 'rows'] or [0])
-        return MAX_QUERIES if per_query == 0 else max(1, min(MAX_QUERIES, ROWS_BUDGET_BYTES // per_query))
-
-    def _warp_parts(self, jobs, q0: int, q1: int):
-        """(isi_warp_part array, T, W, the tensors it points into) of the queries q0 .. q1 - 1."""
-        ratio = 1 if len(jobs) == 1 else self.bottom.shape[2] // self.top.shape[2]
-        parts = (_hip.isi_warp_part * len(jobs))()
+    def _warp_parts(self, layers, q0: int, q1: int):
+        """(isi_warp_part array, T, the tensors it points into) of the queries q0 .. q1 - 1."""
+        ratio = 1 if len(layers) == 1 else self.bottom.shape[2] // self.top.shape[2]
+        parts = (_hip.isi_warp_part * len(layers))()
         keep = []
-        for p, job in enumerate(jobs):
-            stored = self.top if job[0] == 'top' else self.bottom
-            rows, w = self._warp_rows(job, q0, q1)
+        for p, q in enumerate(layers):
+            stored = self._layer(q.layer)
+            rows, w = self._warp_rows(q, q0, q1)
             keep += [rows, w]
-            parts[p].codes, parts[p].rows = stored.data_ptr(), rows.data_ptr()
+            parts[p].codes, parts[p].rows = stored.maps.data_ptr(), rows.data_ptr()
             parts[p].weights = None if w is None else w.data_ptr()
-            parts[p].F, parts[p].r, parts[p].K = int(stored.shape[1]), (ratio if p > 0 else 1), int(rows.shape[2])
-        first = self.top if jobs[0][0] == 'top' else self.bottom
-        return parts, int(first.shape[2]), int(jobs[0][4]), keep
+            parts[p].F, parts[p].r, parts[p].K = stored.F, (ratio if p > 0 else 1), int(rows.shape[2])
+        return parts, self._layer(layers[0].layer).T, keep
 
-    def _warp_forms(self, top_code, bottom_code, top_vectors, bottom_vectors, top_rows, bottom_rows):
-        return (top_code, top_vectors, top_rows), (bottom_code, bottom_vectors, bottom_rows)
+    def _warped_distances(self, layers, lo: int, hi: int, allowed: Optional[torch.Tensor]) -> torch.Tensor:
+        """dist fp32 [Q, N] of uploaded layers (isi_code_warp_search_f32), the queries in groups that keep the rows built
+        or gathered for them under ROWS_BUDGET_BYTES."""
+        lib, stream = _hip.lib(), C.c_void_p(_hip.stream_ptr(self.device))
+        Q, N = layers[0].payload.shape[0], len(self)
+        dist = torch.empty(Q, N, dtype=torch.float32, device=self.device)
+        group = self._rows_group_size(layers, ('code', 'vectors'))
+        for q0 in range(0, Q, group):
+            q1 = min(Q, q0 + group)
+            parts, T, keep = self._warp_parts(layers, q0, q1)
+            _hip.check(lib.isi_code_warp_search_f32(parts, len(layers), None if allowed is None else allowed.data_ptr(),
+                                                    dist[q0:q1].data_ptr(), None, N, T, layers[0].W, lo, hi, q1 - q0, stream),
+                       "isi_code_warp_search_f32")
+            del keep
+        return dist
 
     def distances_warped(self, top_code=None, bottom_code=None, *, top_vectors=None, bottom_vectors=None, top_rows=None,
                          bottom_rows=None, mask_top=None, mask_bottom=None, layer_weights: Tuple[float, float] = (1., 1.),
                          drift: Tuple[int, int] = (-4, 4), allowed: Optional[torch.Tensor] = None):
         """(dist fp32 [Q, N], single): the warped distance of `search_warped` of every query to every item; +inf where
         allowed[n] == 0."""
-        checked, lo, hi = self._warp_plan("search_warped", self._warp_forms(top_code, bottom_code, top_vectors, bottom_vectors,
-                                                                            top_rows, bottom_rows),
-                                          (mask_top, mask_bottom), layer_weights, drift)
-        jobs = [self._soft_job(*c) for c in checked]
-        lib, stream = _hip.lib(), C.c_void_p(_hip.stream_ptr(self.device))
-        Q, N = jobs[0][2].shape[0], len(self)
-        dist = torch.empty(Q, N, dtype=torch.float32, device=self.device)
-        group = self._warp_group_size(jobs)
-        for q0 in range(0, Q, group):
-            q1 = min(Q, q0 + group)
-            parts, T, W, keep = self._warp_parts(jobs, q0, q1)
-            _hip.check(lib.isi_code_warp_search_f32(parts, len(jobs), None if allowed is None else allowed.data_ptr(),
-                                                    dist[q0:q1].data_ptr(), None, N, T, W, lo, hi, q1 - q0, stream),
-                       "isi_code_warp_search_f32")
-            del keep
-        return dist, all(job[5] for job in jobs)
+        return self._distances("search_warped", ((top_code, top_vectors, top_rows), (bottom_code, bottom_vectors, bottom_rows)),
+                               (mask_top, mask_bottom), layer_weights, self._warped_distances, allowed,
+                               lambda T, W: self._drift_band(T, W, drift))
 
     def search_warped(self, top_code=None, bottom_code=None, *, top_vectors=None, bottom_vectors=None, top_rows=None,
                       bottom_rows=None, mask_top=None, mask_bottom=None, layer_weights: Tuple[float, float] = (1., 1.),
@@ -758,14 +685,9 @@ class CodeIndex:
         given, and hi - lo + 1 <= 64.  drift=(o, o) is the shifted search's alignment at offset o.  Masks, layer_weights,
         the (distance, index) order, attribute_constraints, exclude, LookupError / ValueError / HipLibraryError and the
         grouping of the queries under ROWS_BUDGET_BYTES are `search_soft`'s."""
-        if int(k) < 1:
-            raise ValueError(f"k must be at least 1, not {k}")
-        allowed = self.allowed(attribute_constraints, exclude)
-        dist, single = self.distances_warped(top_code, bottom_code, top_vectors=top_vectors, bottom_vectors=bottom_vectors,
-                                             top_rows=top_rows, bottom_rows=bottom_rows, mask_top=mask_top,
-                                             mask_bottom=mask_bottom, layer_weights=layer_weights, drift=drift, allowed=allowed)
-        values, order = self._nearest(dist, k, self._admitted(allowed, attribute_constraints, exclude))
-        return (order[0], values[0]) if single else (order, values)
+        return self._search("search_warped", ((top_code, top_vectors, top_rows), (bottom_code, bottom_vectors, bottom_rows)),
+                            (mask_top, mask_bottom), layer_weights, k, attribute_constraints, exclude, self._warped_distances,
+                            lambda T, W: self._drift_band(T, W, drift))
 
     def warp_paths(self, indices, top_code=None, bottom_code=None, *, top_vectors=None, bottom_vectors=None, top_rows=None,
                    bottom_rows=None, mask_top=None, mask_bottom=None, layer_weights: Tuple[float, float] = (1., 1.),
@@ -773,11 +695,11 @@ class CodeIndex:
         """The alignments behind `search_warped`'s distances: for items `indices` [k] (or [Q, k]) and the same query, the
         item column p(i) matched to every query column, int64 [k, W] (or [Q, k, W]).  Among paths of equal cost the one
         that prefers step over hold over skip, backtracked from the smallest end column."""
-        checked, lo, hi = self._warp_plan("warp_paths", self._warp_forms(top_code, bottom_code, top_vectors, bottom_vectors,
-                                                                         top_rows, bottom_rows),
-                                          (mask_top, mask_bottom), layer_weights, drift)
-        jobs = [self._soft_job(*c) for c in checked]
-        Q, N, single = jobs[0][2].shape[0], len(self), all(job[5] for job in jobs)
+        forms = (top_code, top_vectors, top_rows), (bottom_code, bottom_vectors, bottom_rows)
+        layers, (lo, hi) = self._plan("warp_paths", forms, (mask_top, mask_bottom), layer_weights,
+                                      lambda T, W: self._drift_band(T, W, drift))
+        layers = [self._upload(q) for q in layers]
+        Q, N, W, single = layers[0].payload.shape[0], len(self), layers[0].W, all(q.single for q in layers)
         items = torch.as_tensor(indices)
         if items.dtype.is_floating_point or items.dtype == torch.bool or items.dim() not in (1, 2) or items.numel() == 0 \
                 or (items.dim() == 2 and items.shape[0] != Q) or (items.dim() == 1 and Q != 1):
@@ -788,19 +710,18 @@ class CodeIndex:
             raise IndexError(f"indices outside an index of {N} items")
         items = items % N
         lib, stream = _hip.lib(), C.c_void_p(_hip.stream_ptr(self.device))
-        W = int(jobs[0][4])
         path = torch.empty(Q, items.shape[1], W, dtype=torch.int32, device=self.device)
-        group = self._warp_group_size(jobs)
+        group = self._rows_group_size(layers, ('code', 'vectors'))
         for q0 in range(0, Q, group):
             q1 = min(Q, q0 + group)
-            parts, T, _, keep = self._warp_parts(jobs, q0, q1)
+            parts, T, keep = self._warp_parts(layers, q0, q1)
             for m0 in range(0, items.shape[1], MAX_PATH_ITEMS):
                 chosen = items[q0:q1, m0:m0 + MAX_PATH_ITEMS].contiguous()
                 M = chosen.shape[1]
                 out = torch.empty(q1 - q0, M, W, dtype=torch.int32, device=self.device)
                 dist = torch.empty(q1 - q0, M, dtype=torch.float32, device=self.device)
                 self._grow_workspace(lib.isi_code_warp_path_workspace_bytes(M, W, lo, hi, q1 - q0))
-                _hip.check(lib.isi_code_warp_path_f32(parts, len(jobs), chosen.data_ptr(), M, out.data_ptr(), dist.data_ptr(),
+                _hip.check(lib.isi_code_warp_path_f32(parts, len(layers), chosen.data_ptr(), M, out.data_ptr(), dist.data_ptr(),
                                                       self._workspace.data_ptr(), self._workspace.numel() * 4, N, T, W, lo, hi,
                                                       q1 - q0, stream), "isi_code_warp_path_f32")
                 path[q0:q1, m0:m0 + M] = out

@@ -240,6 +240,8 @@ def test_code_index_validation_needs_no_device():
         index.search(top[0], k=0)
     with pytest.raises(ValueError):
         index.search(top[:3], bottom[:2])
+    with pytest.raises(LookupError):                                   # nobody admitted: said before any upload or launch
+        index.search(top[0], bottom[0], attribute_constraints={"pitch": 1000})
     with pytest.raises(_hip.HipLibraryError):
         index.search(top[0], bottom[0])
     with pytest.raises(_hip.HipLibraryError):

@@ -329,6 +329,10 @@ def test_code_index_validation_needs_no_device():
         index.search_shifted_soft(top_vectors=z_t[:, :2], bottom_vectors=z_b[:, :5])
     with pytest.raises(ValueError, match="shift_range"):
         index.search_shifted_soft(top_vectors=z_t[:, :2], shift_range=(3, 9))
+    with pytest.raises(LookupError):                                   # nobody admitted: said before any upload or launch
+        index.search_soft(top_vectors=z_t, bottom_vectors=z_b, attribute_constraints={"pitch": 1000})
+    with pytest.raises(LookupError):
+        index.search_shifted_soft(top_vectors=z_t[:, :2], bottom_vectors=z_b[:, :4], attribute_constraints={"pitch": 1000})
     no_bottom = CodeIndex.from_arrays(top, None, {}, vq, "cpu")
     with pytest.raises(ValueError, match="holds no bottom maps"):
         no_bottom.search_soft(top_vectors=z_t, bottom_vectors=z_b)

@@ -302,6 +302,25 @@ def test_paste_warped_is_paste_fragment_on_a_straight_path_and_follows_a_bent_on
         inpainting.paste_warped(top, bottom, item_top, item_bottom, full, start, path, layer="middle")
 
 
+def test_paste_fragment_takes_a_bottom_mask_of_odd_width():
+    """A bottom-layer window need not be a whole number of top columns: 3 bottom columns on maps of time ratio 2 (a width
+    `paste_warped`, whose mask spans r W columns, cannot express)."""
+    import inpainting
+    g = torch.Generator().manual_seed(5)
+    top, bottom = torch.randint(0, 32, (1, 4, 10), generator=g), torch.randint(0, 32, (1, 8, 20), generator=g)
+    item_top, item_bottom = torch.randint(0, 32, (1, 4, 12), generator=g), torch.randint(0, 32, (1, 8, 24), generator=g)
+    mask = torch.rand(1, 8, 3, generator=g) < 0.6
+    assert mask.any() and not mask.all()
+    for start, shift in ((3, 2), (0, 0), (9, 11), (2, -1)):            # bottom columns 2 start + c from item columns 2 shift + c
+        new_top, new_bottom = inpainting.paste_fragment(top, bottom, item_top, item_bottom, mask, "bottom", start, shift)
+        want = bottom.clone()
+        for c in range(3):
+            column, source = 2 * start + c, 2 * shift + c
+            if 0 <= column < 20 and 0 <= source < 24:
+                want[0, :, column] = torch.where(mask[0, :, c], item_bottom[0, :, source], bottom[0, :, column])
+        assert torch.equal(new_bottom, want) and torch.equal(new_top, top) and new_top is not top
+
+
 def _vqvae(n_embed=32):
     from interactive_spectrogram_inpainting.vqvae.vqvae import VQVAE
     return VQVAE(in_channel=2, num_hidden_channels=32, n_res_block=1, num_residual_channels=8, embed_dim=16,
@@ -363,6 +382,8 @@ def test_search_warped_validation_needs_no_device():
             search(top[0, :, :2], drift=(0, 2))
     with pytest.raises(ValueError):
         index.search_warped(top[0], k=0)
+    with pytest.raises(LookupError):                                   # nobody admitted: said before any upload or launch
+        index.search_warped(top[0], bottom[0], attribute_constraints={"pitch": 1000})
     no_bottom = CodeIndex.from_arrays(top, None, {}, vq, "cpu")
     with pytest.raises(ValueError, match="holds no bottom maps"):
         no_bottom.search_warped(top[0], bottom[0])

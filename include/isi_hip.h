@@ -772,7 +772,9 @@ int isi_vq_ema_update_restart_f32(float *embed, float *cluster_size, float *embe
  * q/k/v/out are addressed as [seq, batch, head, head_dim] with element strides
  * (ss, sb, sh) and contiguous head_dim (16, 32 or 64).  rel_embeddings
  * [H, rel_rows, head_dim] may be NULL (no bias).  mask_mode: 0 none, 1 causal
- * (j <= i), 2 anti-causal (j >= i); dense_mask [Sq,Sk] additive, may be NULL. */
+ * (j <= i), 2 anti-causal (j >= i); dense_mask [Sq,Sk] additive, may be NULL (an entry may be -inf: that pair has
+ * weight 0).  A query row with no allowed pair, or with only -inf logits (anti-causal rows beyond the last key, an all -inf
+ * row of dense_mask) is an EMPTY row: every kernel writes out = 0 and lse = 1e30f for it, no NaN. */
 typedef struct isi_attn_args {
   const float *q, *k, *v, *rel_embeddings, *dense_mask;
   float *out;
@@ -789,7 +791,7 @@ typedef struct isi_attn_args {
                   * ~4e-4 of the output's maximum where mode 2 gives ~3e-3; its backward runs three-term products) */
   float *logits; /* optional [B,H,Sq,logits_ld] (16-bit modes only, precision >= 1): the forward stores the logit of every
                   * (query, key) pair the mask allows -- (q.k + q.e[r]) * scale * log2(e) + mask * log2(e), i.e. in units
-                  * of exp2 -- and isi_rel_attention_bwd_f32, handed the same buffer, reads them instead of forming
+                  * of exp2; -inf where dense_mask is; the rows of the one-row tail kernel included -- and isi_rel_attention_bwd_f32, handed the same buffer, reads them instead of forming
                   * Q K^T, the band product Q E^T and its skew a second and a third time (60 % of the backward's time at
                   * S = 1025).  Entries of masked pairs are never read.  NULL: nothing is stored / everything is recomputed */
   int64_t logits_ld; /* row stride of `logits` in floats: a multiple of 4, >= Sk rounded up to a multiple of 32 */

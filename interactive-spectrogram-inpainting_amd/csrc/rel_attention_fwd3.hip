@@ -608,12 +608,14 @@ __global__ __launch_bounds__(512) void rel_attn_fwd3_kernel(const AttnKArgs p, c
         const int khi = min(p.Sk - 1, p.mask_mode == 1 ? qi : 0x7fffffff) - k0 - 4 * half;
         const int klo = (p.mask_mode == 2 ? qi : 0) - k0 - 4 * half;
         if (p.mask) {      // additive mask tensor (masks the wrapper does not recognise as causal / anti-causal)
-          const float *mrow = p.mask + (size_t)min(qi, p.Sq - 1) * p.Sk + k0 + 4 * half;
+          // (a pair the predicates leave out reads the row's FIRST entry: see rel_attention_fwd2.hip)
+          const float *mrow = p.mask + (size_t)min(qi, p.Sq - 1) * p.Sk;
+          const int mcol = k0 + 4 * half;
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int jj = (r & 3) + 8 * (r >> 2);
             const bool ok = jj <= khi && jj >= klo;
-            const float sc = ok ? sacc[r] + mrow[ok ? jj : 0] * LOG2E : NEG;
+            const float sc = ok ? sacc[r] + mrow[ok ? mcol + jj : 0] * LOG2E : NEG;
             sv[r] = sc;
             tmax = fmaxf(tmax, sc);
           }

@@ -2205,3 +2205,515 @@ def single_source_positions(c, own=True):
     """[steps = SINGLE_SOURCE_P + 1][B] positions; the step addressed is the last."""
     at = [SINGLE_SOURCE_P - ((m % 3) * 2 if own else 0) for m in range(c.B)]
     return torch.tensor([[(a + 1 + t) % (SINGLE_SOURCE_P + 1) for a in at] for t in range(SINGLE_SOURCE_P)] + [at], dtype=torch.int32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Float64 specification, float32 yardstick and 16-bit operand models of the training-side relative attention FORWARD
+# (isi_rel_attention_f32: csrc/rel_attention_f32.hip, rel_attention_fwd2.hip, rel_attention_fwd3.hip, routed by
+# attn_fwd_route in csrc/rel_attention_run.cpp), in the style of the blocks above: plain torch on the CPU, no autograd
+# and none of the project's kernels.  include/isi_hip.h (isi_attn_args) states the operation:
+#     logit[i,j] = (q_i.k_j + q_i.e[h, r(i,j)]) * scale + mask(i,j),   r(i,j) = floor(i/Cq) - floor(j/Ck) + Ek - 1
+#     out_i = softmax_j(logit) v_j over the pairs mask_mode allows;  lse_i = log sum_j exp(logit)   (natural log)
+#     kept logits (16-bit modes): logit * log2(e) of every allowed pair
+#     a row with no allowed pair, or with only -inf logits (an EMPTY row): out = 0, lse = 1e30f
+# Tensors here: q [Sq,B,H,hd] (or [Sq,B,H*hd]), k / v [Sk,B,H,hd], the table [H,rel_rows,hd] or None, the dense additive
+# mask [Sq,Sk] or None; results out [B,H,Sq,hd], lse [B,H,Sq], logits2 [B,H,Sq,Sk], allowed [Sq,Sk].
+# tests/test_attention_fwd_host.py holds the spec to oracle/prior_oracle.py and shows what the hold rejects;
+# tests/test_attention_fwd_gpu.py holds every kernel route to it.
+ATTN_QB = 128                                  # QB of csrc/rel_attention.h: query rows per block
+ATTN_LOG2E = 1.4426950408889634
+ATTN_EMPTY_LSE = float(np.float32(1e30))       # what the kernels store as the log-sum-exp of an empty row
+ATTN_FAMILIES = ("exact", "tiles64", "planes")
+ATTN_KNOB_NO_FWD3, ATTN_KNOB_FWD3_ALL = 1, 2   # bits of `knobs`, as in tests/attention_plan_tracer.cpp
+ATTN_KNOB_NAMES = {ATTN_KNOB_NO_FWD3: "ISI_ATTN_NO_FWD3", ATTN_KNOB_FWD3_ALL: "ISI_ATTN_FWD3_ALL"}
+AttnFwd = collections.namedtuple("AttnFwd", "out lse logits2 allowed")
+
+
+def attention_allowed(Sq, Sk, mask_mode, strict=False):
+    """The [Sq,Sk] predicate of mask_mode: 0 every pair, 1 causal (j <= i), 2 anti-causal (j >= i).  `strict` is a host-test
+    mutant (j < i, j > i)."""
+    i, j = torch.arange(Sq)[:, None], torch.arange(Sk)[None, :]
+    if mask_mode == 1:
+        return (j < i) if strict else (j <= i)
+    if mask_mode == 2:
+        return (j > i) if strict else (j >= i)
+    assert mask_mode == 0, mask_mode
+    return torch.ones(Sq, Sk, dtype=torch.bool)
+
+
+def attention_rel_index(Sq, Sk, Cq, Ck, Ek):
+    """r(i,j) = floor(i/Cq) - floor(j/Ck) + Ek - 1, [Sq,Sk]."""
+    return torch.arange(Sq)[:, None] // Cq - torch.arange(Sk)[None, :] // Ck + (Ek - 1)
+
+
+def _attn_heads(t, H):
+    """[S,B,H,hd] or [S,B,H*hd] -> [B,H,S,hd]"""
+    t = torch.as_tensor(t).detach().cpu()
+    if t.dim() == 3:
+        t = t.reshape(t.shape[0], t.shape[1], H, t.shape[2] // H)
+    return t.permute(1, 2, 0, 3)
+
+
+def _attn_softmax(l2, allowed, pv, dtype, lse_base2=False, drop_last_key=False, stale_max=False):
+    """Softmax over the allowed, finite base-2 logits of every row, the product with V through `pv(p)`, the log-sum-exp
+    and the empty-row convention.  The switches are the host tests' mutants: `drop_last_key` leaves the last key of a
+    ragged 32-key tile (Sk % 32 != 0) out of the softmax; `stale_max` is an online softmax over [the keys before the last
+    32-key tile | that tile] that forgets to rescale the first part's numerator when the last tile raises the maximum."""
+    Sk = l2.shape[-1]
+    ninf = torch.tensor(float("-inf"), dtype=dtype)
+    if drop_last_key and Sk % 32:
+        allowed = allowed.clone()
+        allowed[:, Sk - 1] = False
+    masked = torch.where(allowed, l2, ninf)
+    m = masked.amax(dim=-1, keepdim=True)
+    empty = m == float("-inf")
+    msafe = torch.where(empty, torch.zeros_like(m), m)
+    p = torch.exp2(masked - msafe)
+    l = p.sum(dim=-1, keepdim=True)
+    num = pv(p)
+    if stale_max and Sk > 32:
+        cut = (Sk - 1) // 32 * 32
+        m0 = masked[..., :cut].amax(dim=-1, keepdim=True)
+        has0 = m0 > float("-inf")
+        # the first part's numerator relative to ITS maximum, never rescaled by alpha = exp2(m0 - m)
+        first = torch.where(has0, torch.exp2(masked[..., :cut] - torch.where(has0, m0, torch.zeros_like(m0))), torch.zeros_like(p[..., :cut]))
+        num = pv(torch.cat([first, p[..., cut:]], dim=-1))
+    one = torch.ones_like(l)
+    out = torch.where(empty, torch.zeros_like(num), num / torch.where(empty, one, l))
+    lse = msafe + torch.log2(torch.where(empty, one, l))
+    if not lse_base2:
+        lse = lse * math.log(2.0)
+    lse = torch.where(empty, torch.full_like(lse, ATTN_EMPTY_LSE), lse)
+    return out, lse.squeeze(-1)
+
+
+def _attention_eval(dtype, q, k, v, rel, H, Cq, Ck, Ek, mask_mode, dense_mask, scale, rel_shift=0, swap_c=False, strict_causal=False,
+                    rel_unscaled=False, dense_on_disallowed=False, lse_base2=False, logits_no_mask=False, drop_last_key=False,
+                    stale_max=False):
+    """The operation in `dtype`; every keyword is a mutant of the host tests (off: the operation as specified)."""
+    hq, hk, hv = (_attn_heads(t, H).to(dtype) for t in (q, k, v))
+    Sq, Sk = hq.shape[2], hk.shape[2]
+    s = hq @ hk.transpose(-1, -2)
+    if rel is not None:
+        e = torch.as_tensor(rel).detach().cpu().to(dtype)
+        idx = attention_rel_index(Sq, Sk, *((Ck, Cq) if swap_c else (Cq, Ck)), Ek) + rel_shift
+        if rel_shift or swap_c:
+            idx = idx.clamp(0, e.shape[1] - 1)
+        assert int(idx.min()) >= 0 and int(idx.max()) < e.shape[1], "the table must cover every (query, key) pair"
+        srel = torch.einsum("bhid,hrd->bhir", hq, e).gather(3, idx.expand(hq.shape[0], H, Sq, Sk))
+        s = (s * scale + srel) if rel_unscaled else (s + srel) * scale
+    else:
+        s = s * scale
+    l2 = s * ATTN_LOG2E
+    allowed = attention_allowed(Sq, Sk, mask_mode)
+    used = attention_allowed(Sq, Sk, mask_mode, strict=True) if strict_causal else allowed
+    kept = l2
+    if dense_mask is not None:
+        dm = torch.as_tensor(dense_mask).detach().cpu().to(dtype) * ATTN_LOG2E
+        with_mask = l2 + (torch.where(used, torch.zeros_like(dm), dm) if dense_on_disallowed else dm)
+        kept = l2 if logits_no_mask else with_mask
+        l2 = with_mask
+    out, lse = _attn_softmax(l2, used, lambda p: p @ hv, dtype, lse_base2, drop_last_key, stale_max)
+    return AttnFwd(out, lse, kept, allowed)
+
+
+def attention_fwd_spec(q, k, v, rel, H, Cq, Ck, Ek, mask_mode, dense_mask, scale):
+    """The float64 specification: (out, lse, logits2, allowed).  logits2 = (q.k + q.e[r]) * scale * log2(e) + mask * log2(e)
+    for every pair (the entries `allowed` leaves out are unspecified in a kernel's buffer); a pair whose dense-mask entry is
+    -inf is allowed, has weight 0 and logit -inf; an empty row has out = 0 and lse = ATTN_EMPTY_LSE."""
+    return _attention_eval(torch.float64, q, k, v, rel, H, Cq, Ck, Ek, mask_mode, dense_mask, scale)
+
+
+def attention_fwd_f32(q, k, v, rel, H, Cq, Ck, Ek, mask_mode, dense_mask, scale, **mutant):
+    """The same evaluation in float32 torch on the CPU: the yardstick (and what the host tests mutate)."""
+    return _attention_eval(torch.float32, q, k, v, rel, H, Cq, Ck, Ek, mask_mode, dense_mask, scale, **mutant)
+
+
+def _attn_pieces(t, precision):
+    """The float64 values of the 16-bit pieces a kernel makes of the float32 tensor t: precision 1 (hi, lo) =
+    bf16_pieces(t, 2); 2 (rne_bf16(t),); 3 (rne_f16(t),)."""
+    t = t.float()
+    if precision == 1:
+        return bf16_pieces(t, 2)
+    if precision == 2:
+        return (t.bfloat16().double(),)
+    assert precision == 3, precision
+    assert float(t.abs().max()) < 65504.0, "outside f16's range (include/isi_hip.h: |q k v e| < 65504)"
+    return (t.half().double(),)
+
+
+def _attn_terms(A, Bp, contract, drop=None):
+    """The products a mode keeps of (pieces A of K / e / V) x (pieces Bp of Q / P): one term for the single-term modes,
+    A.lo B.hi + A.hi B.lo + A.hi B.hi for precision 1.  `drop` = "lo_hi" (the A.lo B.hi term) is a host-test mutant."""
+    if len(A) == 1:
+        return contract(A[0], Bp[0])
+    s = contract(A[0], Bp[0]) + contract(A[0], Bp[1])
+    return s if drop == "lo_hi" else s + contract(A[1], Bp[0])
+
+
+def attention_fwd_model(q, k, v, rel, H, Cq, Ck, Ek, mask_mode, dense_mask, scale, precision, drop=None):
+    """Float64 evaluation on the operands the 16-bit kernels multiply; its distance from the spec is the truncation the mode
+    accepts by design.  Read from csrc/rel_attention_fwd2.hip (rel_attention_fwd3.hip computes the same products from planes
+    attn_pack_kernel makes with the same conversions, lines 128-138):
+      * q is multiplied by qscale = scale * log2(e) in float32 and THEN converted (fwd2 lines 112, 263-276; fwd3 lines 210,
+        375-390): `PR::split2(a.x * qscale, ...)` for precision 1, `PR::pack2(a.x * qscale, ...)` for 2 and 3;
+      * K and the table rows are converted as they are (fwd2 `put_row`, lines 174-185; fwd3's pack kernel);
+      * S^T = K Q^T and the band product E Q^T keep `mfma(k_lo, q_hi); mfma(k_hi, q_lo); mfma(k_hi, q_hi)` (fwd2 lines
+        341-356, fwd3 lines 500-503 and 527-531), one product for the single-term modes; float32 accumulation;
+      * the dense mask is added in float32 as mask * log2(e) (fwd2 line 434), the softmax runs in float32 on base-2 logits;
+      * the row sum l adds the float32 probabilities BEFORE their conversion (fwd2 lines 419-420, 457-459), the numerator
+        multiplies converted probabilities with converted V (fwd2 lines 468-483: `PR::split2(sv[...])` / `PR::pack2`; V in
+        `commit`, lines 194-212) and keeps `mfma(v_lo, p_hi); mfma(v_hi, p_lo); mfma(v_hi, p_hi)` (lines 500-505).
+    Conversions round to nearest even (`__builtin_convertvector`); hi = rne(x), lo = rne(x - hi) (csrc/split_bf16.h).  The
+    model converts the probabilities relative to the row's FINAL maximum where the kernels convert them relative to the
+    running one and rescale afterwards: the same relative rounding, at another power of two.  `drop`: a host-test mutant."""
+    assert precision in (1, 2, 3), precision
+    hq, hk, hv = (_attn_heads(t, H).float() for t in (q, k, v))
+    Sq, Sk = hq.shape[2], hk.shape[2]
+    qscale = np.float32(scale) * np.float32(ATTN_LOG2E)
+    Q = _attn_pieces(hq * float(qscale), precision)
+    l2 = _attn_terms(_attn_pieces(hk, precision), Q, lambda a, b: b @ a.transpose(-1, -2), drop)
+    if rel is not None:
+        e = torch.as_tensor(rel).detach().cpu().float()
+        idx = attention_rel_index(Sq, Sk, Cq, Ck, Ek)
+        assert int(idx.min()) >= 0 and int(idx.max()) < e.shape[1]
+        band = _attn_terms(_attn_pieces(e, precision), Q, lambda a, b: torch.einsum("bhid,hrd->bhir", b, a), drop)
+        l2 = l2 + band.gather(3, idx.expand(hq.shape[0], H, Sq, Sk))
+    if dense_mask is not None:
+        l2 = l2 + torch.as_tensor(dense_mask).detach().cpu().double() * ATTN_LOG2E
+    allowed = attention_allowed(Sq, Sk, mask_mode)
+    V = _attn_pieces(hv, precision)
+    out, lse = _attn_softmax(l2, allowed, lambda p: _attn_terms(V, _attn_pieces(p, precision), lambda a, b: b @ a, drop), torch.float64)
+    return AttnFwd(out, lse, l2, allowed)
+
+
+def attention_tail_rows(S, mask_mode, dense):
+    """attention_tail_rows of csrc/rel_attention_run.cpp"""
+    tail = S % ATTN_QB
+    return tail if (1 <= tail <= 2 and S >= 2 * ATTN_QB and not dense and mask_mode == 0) else 0
+
+
+def attention_fwd_route(hd, precision, Cq, Ck, table, Sq, mask_mode, dense, workspace, knobs, cus, B, H, Sk=None, rel_rows=None):
+    """Restatement of attn_fwd_route, attention_tail_rows, blocks and persistent_workgroups (csrc/rel_attention_run.cpp):
+    (family, tail_rows, nW) of an accepted forward call.  workspace: "none" | "given" | "query" (the caller brings one iff
+    isi_rel_attention_workspace_bytes answers > 0); knobs: bits ATTN_KNOB_*; cus: the device's CU count.  family "exact"
+    (precision 0; nW = its grid's query blocks), "tiles64" (rel_attention_fwd2.hip) or "planes" (rel_attention_fwd3.hip);
+    tail_rows: rows the one-row kernel takes behind a 16-bit kernel; nW: persistent workgroups per (batch, head) pair.  With
+    Sk and rel_rows the planes' 2 GiB limit (planes_ok) is applied too."""
+    assert workspace in ("none", "given", "query"), workspace
+    cdiv = lambda a, b: (a + b - 1) // b
+    if precision == 0:
+        return "exact", 0, cdiv(Sq, ATTN_QB)
+    planes_ok = Cq == 1 and Ck == 1 and hd in (32, 64) and 1 <= precision <= 3 and bool(table)
+    if planes_ok and Sk is not None:
+        npl = 2 if precision == 1 else 1
+        planes_ok = (npl * H * B * cdiv(Sk, 32) * 32 * hd * 2 < 2 ** 31 and npl * H * (rel_rows or 0) * hd * 2 < 2 ** 31)
+    if workspace == "query" and precision != 1 and not knobs & ATTN_KNOB_FWD3_ALL:
+        family = "tiles64"
+    elif workspace == "none" or knobs & ATTN_KNOB_NO_FWD3 or not planes_ok:
+        family = "tiles64"
+    else:
+        family = "planes"
+    tail = attention_tail_rows(Sq, mask_mode, dense)
+    nblk = Sq // ATTN_QB if tail else cdiv(Sq, ATTN_QB)
+    pairs = H * B
+    nW = nblk if pairs * nblk <= cus else max(1, min((nblk + 1) // 2 if mask_mode else nblk, cus // pairs))
+    return family, tail, nW
+
+
+# ---- the cases.  B = H = 0 with `persistent` set: the pair count is derived from the device (attention_fwd_case_resolve)
+AttnFwdCase = collections.namedtuple(
+    "AttnFwdCase", "hd prec Sq Sk B H Cq Ck mask dense table ws knobs layout wide ld_extra kind outputs ek_extra persistent")
+ATTN_LAYOUTS = ("contig", "fused", "batch_first", "head2")
+ATTN_KINDS = ("plain", "peaked", "late_max", "flat", "shifted")
+ATTN_OUTPUTS = ("none", "lse", "lse+logits")
+ATTN_SQ = (1, 33, 127, 128, 129, 257, 258, 259)
+ATTN_SK = (1, 31, 32, 33, 63, 65, 97, 130, 257)
+ATTN_CHANNELS = ((4, 1), (1, 4), (4, 4), (2, 1), (3, 2))
+ATTN_DEFAULT_CUS = 256
+
+
+def attention_fwd_case_id(c):
+    return (f"hd{c.hd}-p{c.prec}-s{c.Sq}.{c.Sk}-b{c.B}h{c.H}-c{c.Cq}.{c.Ck}-m{c.mask}d{int(c.dense)}t{int(c.table)}-w{c.ws}k{c.knobs}-"
+            f"{c.layout}{'+wide' if c.wide else ''}-ld{c.ld_extra}-{c.kind}-{c.outputs}-e{c.ek_extra}" + (f"-{c.persistent}" if c.persistent else ""))
+
+
+def attention_fwd_case_resolve(c, cus=ATTN_DEFAULT_CUS):
+    """A persistent case with its (batch, head) pairs for a device of `cus` CUs: "one": one pair more than CUs (nW = 1, one
+    workgroup walks every block); "snake": cus // 2 pairs (pairs * blocks > cus >= 2 pairs: 1 < nW < blocks)."""
+    if not c.persistent:
+        return c
+    pairs = cus + 1 if c.persistent == "one" else max(cus // 2, 1)
+    H = 2 if pairs % 2 == 0 else 1
+    return c._replace(B=pairs // H, H=H)
+
+
+def attention_fwd_case_route(c, cus=ATTN_DEFAULT_CUS):
+    c = attention_fwd_case_resolve(c, cus)
+    Ek = -(-c.Sk // c.Ck) + c.ek_extra
+    return attention_fwd_route(c.hd, c.prec, c.Cq, c.Ck, c.table, c.Sq, c.mask, c.dense, c.ws, c.knobs, cus, c.B, c.H, Sk=c.Sk,
+                               rel_rows=-(-c.Sq // c.Cq) + Ek - 1)
+
+
+def _attention_fwd_table():
+    def ac(hd, prec, Sq, Sk, mask=0, dense=False, B=2, H=3, Cq=1, Ck=1, table=True, ws="none", knobs=0, layout="contig", wide=False,
+           ld_extra=0, kind="plain", outputs="lse", ek_extra=0, persistent=""):
+        if ws == "query" and prec in (2, 3):
+            knobs |= ATTN_KNOB_FWD3_ALL           # the size query answers for the single-term modes only under this knob
+        if prec == 0 and outputs == "lse+logits":
+            outputs = "lse"                       # (kept logits are refused with precision 0)
+        return AttnFwdCase(hd, prec, Sq, Sk, B, H, Cq, Ck, mask, dense, table, ws, knobs, layout, wide, ld_extra, kind, outputs, ek_extra,
+                           persistent)
+    # (Sq, Sk, mask, dense): every ragged length, mask and mask combination once per family
+    slots = [(1, 1, 0, False), (33, 31, 0, False), (127, 32, 1, False), (128, 33, 2, False), (129, 97, 0, True), (257, 65, 1, False),
+             (258, 130, 2, False), (259, 257, 0, False), (33, 63, 1, False), (129, 130, 1, True), (129, 129, 2, False),
+             (257, 130, 2, False), (258, 97, 1, False)]
+    insts = {"exact": [(hd, 0, None) for hd in (16, 32, 64)],
+             "tiles64": [(hd, p, u) for u in (True, False) for p in (1, 2, 3) for hd in (16, 32, 64)],
+             "planes": [(hd, p, True) for p in (1, 2, 3) for hd in (32, 64)]}
+    cases = []
+    for fam in ATTN_FAMILIES:
+        n = max(len(slots), len(insts[fam]))
+        general = 0
+        for i in range(n):
+            Sq, Sk, mask, dense = slots[i % len(slots)]
+            hd, prec, unit = insts[fam][i % len(insts[fam])]
+            Cq, Ck = 1, 1
+            if fam == "exact" and i % 2:
+                unit = False
+            if unit is False:
+                Cq, Ck = ATTN_CHANNELS[general % len(ATTN_CHANNELS)]
+                general += 1
+            layout = ATTN_LAYOUTS[i % 4]
+            if (Sq, Sk) == (129, 129):
+                layout = "fused"                 # q, k and v in ONE [S,B,3d] buffer
+            cases.append(ac(hd, prec, Sq, Sk, mask, dense, H=4 if i % 3 == 0 else 3, Cq=Cq, Ck=Ck,
+                            table=True if fam == "planes" else i % 4 != 3, ws="query" if fam == "planes" else "none", layout=layout,
+                            wide=i % 2 == 1, ld_extra=32 * (i // 2 % 2), kind=ATTN_KINDS[i % 5], outputs=ATTN_OUTPUTS[i % 3],
+                            ek_extra=3 if i == 6 else 0))
+    # the one-row tail kernel: every head dim behind the 64-key tiles, 32 / 64 behind the planes; Sk below its 512 / G key groups
+    for j, (hd, ws) in enumerate([(16, "none"), (32, "none"), (64, "none"), (32, "query"), (64, "query")]):
+        cases.append(ac(hd, 1 + j % 3, (257, 258)[j % 2], (5, 257, 130)[j % 3], ws=ws, kind=ATTN_KINDS[j % 5], outputs="lse+logits",
+                        layout=ATTN_LAYOUTS[j % 4], wide=j % 2 == 0, ld_extra=32 * (j % 2)))
+    cases.append(ac(64, 2, 385, 5, ws="none", outputs="lse+logits", kind="late_max"))
+    # causal, several channels per query event, ragged Sq: the kernels keep the ragged block last there (rel_attention_fwd2.hip:100)
+    cases.append(ac(32, 1, 161, 161, 1, Cq=4, Ck=4, outputs="lse+logits", layout="fused"))
+    cases.append(ac(32, 0, 161, 161, 1, Cq=2, Ck=1))
+    # a workspace without a table: the 64-key tiles
+    cases.append(ac(32, 1, 129, 65, 0, table=False, ws="given", outputs="lse+logits"))
+    # a workspace handed over with a single-term mode and no knob: the planes ("a caller that hands one over anyway")
+    cases.append(ac(64, 2, 130, 97, 1, ws="given", outputs="lse+logits", kind="peaked"))
+    # the persistent schedule: at least three query blocks under both masks, pairs from the CU count
+    for fam_ws, hd in (("none", 16), ("query", 32)):
+        for how in ("one", "snake"):
+            for mask in (1, 2):
+                cases.append(ac(hd, 1 if how == "one" else 2, 257, 257, mask, B=0, H=0, ws=fam_ws, persistent=how,
+                                outputs="lse+logits" if (how, mask) == ("snake", 1) else "lse", kind="plain" if mask == 1 else "late_max"))
+    return cases
+
+
+ATTENTION_FWD_CASES = _attention_fwd_table()
+ATTENTION_FWD_ENTRY_CASES = [c for c in ATTENTION_FWD_CASES if not c.persistent and c.layout in ("contig", "fused", "batch_first")
+                             and not c.wide and not c.ld_extra and c.ws != "given" and c.outputs == "lse+logits"][:6]
+
+
+def _attention_fwd_features(c, cus):
+    family, tail, nW = attention_fwd_case_route(c, cus)
+    r = attention_fwd_case_resolve(c, cus)
+    unit = c.Cq == 1 and c.Ck == 1
+    f = {f"{family}: Sq {c.Sq}", f"{family}: Sk {c.Sk}", f"{family}: mask {c.mask}", f"{family}: layout {c.layout}",
+         f"{family}: kind {c.kind}", f"{family}: outputs {c.outputs}", f"{family}: table {int(c.table)}",
+         f"pairs % 8 {'==' if r.B * r.H % 8 == 0 else '!='} 0"}
+    f.add({"exact": f"inst exact hd{c.hd}", "tiles64": f"inst tiles64 hd{c.hd} p{c.prec} {'unit' if unit else 'general'}",
+           "planes": f"inst planes hd{c.hd} p{c.prec}"}[family])
+    if tail:
+        f.add(f"inst tail hd{c.hd} behind {family}")
+        if c.Sk < 512 // (c.hd // 4):
+            f.add("tail: Sk below the key groups")
+    if c.Sq in (257, 258) and c.mask and not tail:
+        f.add(f"{family}: Sq {c.Sq} masked, no tail")
+    if c.dense:
+        f.add(f"{family}: dense mask")
+        if c.mask == 1:
+            f.add(f"{family}: dense mask + causal")
+    if c.mask == 1 and c.Sk != c.Sq:
+        f.add(f"{family}: causal Sk {'<' if c.Sk < c.Sq else '>'} Sq")
+    if c.mask == 2 and c.Sq > c.Sk:
+        f.add(f"{family}: anti-causal Sq > Sk")
+    if not unit:
+        f.add(f"{family}: channels {c.Cq}.{c.Ck}")
+    if c.mask == 1 and c.Cq != 1 and c.Sq % ATTN_QB:
+        f.add(f"{family}: causal Cq != 1 ragged")
+    if c.ek_extra:
+        f.add(f"{family}: Ek above the key events")
+    if c.wide:
+        f.add(f"{family}: out in a wider buffer")
+    if c.outputs == "lse+logits":
+        f.add(f"{family}: logits_ld +{c.ld_extra}")
+    if c.persistent and c.Sq > 2 * ATTN_QB:
+        pairs, blocks = r.B * r.H, -(-c.Sq // ATTN_QB)
+        if pairs > cus and nW == 1:
+            f.add(f"{family}: persistent one mask {c.mask}")
+        if pairs * blocks > cus >= 2 * pairs and 1 < nW < blocks:
+            f.add(f"{family}: persistent snake mask {c.mask}")
+    f.add(f"route: workspace {c.ws} p{c.prec} knobs {c.knobs} table {int(c.table)} -> {family}")
+    return f
+
+
+def attention_fwd_requirements():
+    req = [f"inst exact hd{hd}" for hd in (16, 32, 64)]
+    req += [f"inst tiles64 hd{hd} p{p} {u}" for hd in (16, 32, 64) for p in (1, 2, 3) for u in ("unit", "general")]
+    req += [f"inst planes hd{hd} p{p}" for hd in (32, 64) for p in (1, 2, 3)]
+    req += [f"inst tail hd{hd} behind tiles64" for hd in (16, 32, 64)] + [f"inst tail hd{hd} behind planes" for hd in (32, 64)]
+    req += ["tail: Sk below the key groups", "pairs % 8 == 0", "pairs % 8 != 0"]
+    req += ["route: workspace none p1 knobs 0 table 1 -> tiles64", "route: workspace query p1 knobs 0 table 1 -> planes",
+            "route: workspace query p2 knobs 2 table 1 -> planes", "route: workspace query p3 knobs 2 table 1 -> planes",
+            "route: workspace given p1 knobs 0 table 0 -> tiles64", "route: workspace given p2 knobs 0 table 1 -> planes"]
+    for fam in ATTN_FAMILIES:
+        req += [f"{fam}: Sq {s}" for s in ATTN_SQ] + [f"{fam}: Sk {s}" for s in ATTN_SK] + [f"{fam}: mask {m}" for m in (0, 1, 2)]
+        req += [f"{fam}: Sq {s} masked, no tail" for s in (257, 258)]
+        req += [f"{fam}: dense mask", f"{fam}: dense mask + causal", f"{fam}: causal Sk < Sq", f"{fam}: causal Sk > Sq",
+                f"{fam}: anti-causal Sq > Sk", f"{fam}: Ek above the key events", f"{fam}: out in a wider buffer", f"{fam}: table 1"]
+        req += [f"{fam}: layout {l}" for l in ATTN_LAYOUTS] + [f"{fam}: kind {k}" for k in ATTN_KINDS]
+        req += [f"{fam}: outputs {o}" for o in ATTN_OUTPUTS if fam != "exact" or o != "lse+logits"]
+        if fam != "planes":
+            req += [f"{fam}: channels {a}.{b}" for a, b in ATTN_CHANNELS] + [f"{fam}: causal Cq != 1 ragged", f"{fam}: table 0"]
+        if fam != "exact":
+            req += [f"{fam}: logits_ld +0", f"{fam}: logits_ld +32"]
+            req += [f"{fam}: persistent {how} mask {m}" for how in ("one", "snake") for m in (1, 2)]
+    return req
+
+
+def attention_fwd_coverage_gaps(cases, cus=ATTN_DEFAULT_CUS):
+    """The requirements of the case table (every instantiation; per family the ragged lengths, masks, channel layouts,
+    buffer layouts, data kinds, requested outputs and persistent schedules; the routes as the code offers them) that no
+    case of `cases` covers."""
+    have = set()
+    for c in cases:
+        have |= _attention_fwd_features(c, cus)
+    return [r for r in attention_fwd_requirements() if r not in have]
+
+
+AttnData = collections.namedtuple("AttnData", "q k v rel dense scale Ek rel_rows empty_rows")
+
+
+def attention_fwd_case_data(c):
+    """The inputs of a (resolved) case, seeded from its id: q [Sq,B,H,hd], k / v [Sk,B,H,hd], the table, the dense mask, scale,
+    Ek, rel_rows, and `empty_rows`: the query rows the case designs to be empty (anti-causal rows beyond the last key; the
+    all -inf row of a dense mask).  Kinds: plain: randn, table x 0.5; peaked: q x 6; late_max: the logits grow with the key
+    index, so the running maximum moves in every tile and arrives in the last; flat: k = 0 and table = 0 (uniform weights,
+    out = mean of v, lse = ln(allowed count)); shifted: every logit about -80 (natural units)."""
+    import zlib
+    assert c.B > 0 and c.H > 0, "resolve a persistent case first"
+    gen = torch.Generator().manual_seed(zlib.crc32(attention_fwd_case_id(c._replace(B=0, H=0) if c.persistent else c).encode()))
+    rn = lambda *s: torch.randn(*s, generator=gen)
+    Sq, Sk, B, H, hd = c.Sq, c.Sk, c.B, c.H, c.hd
+    scale = float(np.float32(1.0 / math.sqrt(hd)))
+    Ek = -(-Sk // c.Ck) + c.ek_extra
+    rel_rows = -(-Sq // c.Cq) + Ek - 1
+    q, k, v = rn(Sq, B, H, hd), rn(Sk, B, H, hd), rn(Sk, B, H, hd)
+    rel = rn(H, rel_rows, hd) * 0.5 if c.table else None
+    if c.kind == "peaked":
+        q = q * 6.0
+    elif c.kind == "late_max":
+        q = q.abs()
+        k = k * 0.2 + 2.0 * (torch.arange(Sk, dtype=torch.float32)[:, None, None, None] + 1.0) / Sk
+    elif c.kind == "flat":
+        k = torch.zeros_like(k)
+        rel = None if rel is None else torch.zeros_like(rel)
+    elif c.kind == "shifted":
+        u = torch.nn.functional.normalize(rn(1, B, H, hd), dim=-1)
+        q, k = 4.0 * u + 0.3 * q, -(20.0 / scale) * u + k
+    else:
+        assert c.kind == "plain", c.kind
+    dense, empty = None, set()
+    if c.mask == 2:
+        empty |= set(range(Sk, Sq))
+    if c.dense:
+        assert Sk > 64 and Sq > 66 and c.mask in (0, 1)
+        dense = rn(Sq, Sk)
+        dense[torch.rand(Sq, Sk, generator=gen) < 0.15] = float("-inf")
+        rows = torch.arange(Sq)
+        cols = rows.clamp(max=Sk - 1)
+        dense[rows, cols] = dense[rows, cols].nan_to_num(neginf=0.5)     # every row keeps a live pair both masks allow ...
+        r_all, r_late = Sq // 2, Sq - 1
+        dense[r_all] = float("-inf")                                     # ... but this one: an empty row
+        dense[r_late, :64] = float("-inf")                               # the online softmax sees two whole tiles of -inf first
+        empty.add(r_all)
+    return AttnData(q, k, v, rel, dense, scale, Ek, rel_rows, sorted(empty))
+
+
+AttnRefs = collections.namedtuple("AttnRefs", "spec f32 model yard tail empty")
+
+
+def _attn_finite(t):
+    return torch.where(torch.isfinite(t), t, torch.zeros_like(t))
+
+
+def attention_fwd_refs(c, d, tail, models=True):
+    """spec, float32 yardstick, the mode's model (None for precision 0) and the yardstick of the hold: per element the
+    worse of the float32 evaluation and the model on the tile rows of precisions 1 .. 3, the float32 evaluation alone for
+    precision 0 and for the last `tail` query rows (the one-row kernel is exact fp32); `empty`: [B,H,Sq] rows the spec finds
+    empty."""
+    a = (d.q, d.k, d.v, d.rel, c.H, c.Cq, c.Ck, d.Ek, c.mask, d.dense, d.scale)
+    spec, f32 = attention_fwd_spec(*a), attention_fwd_f32(*a)
+    f32 = AttnFwd(f32.out.double(), f32.lse.double(), f32.logits2.double(), f32.allowed)
+    assert bool(torch.isfinite(f32.out).all()) and bool(torch.isfinite(f32.lse).all()), "the float32 yardstick is not finite on this data"
+    model, yard = None, f32
+    if c.prec and models:
+        model = attention_fwd_model(*a, c.prec)
+        yo = larger_error(f32.out, model.out, spec.out)
+        yl = larger_error(f32.lse, model.lse, spec.lse)
+        yg = larger_error(_attn_finite(f32.logits2), _attn_finite(model.logits2), _attn_finite(spec.logits2))
+        if tail:
+            yo[:, :, -tail:], yl[:, :, -tail:], yg[:, :, -tail:] = f32.out[:, :, -tail:], f32.lse[:, :, -tail:], _attn_finite(f32.logits2[:, :, -tail:])
+        yard = AttnFwd(yo, yl, yg, spec.allowed)
+    return AttnRefs(spec, f32, model, yard, tail, spec.lse == ATTN_EMPTY_LSE)
+
+
+@functools.lru_cache(maxsize=2)
+def attention_fwd_case_refs(c, cus=ATTN_DEFAULT_CUS):
+    """(resolved case, data, refs) of a case on a device of `cus` CUs; computed once per case."""
+    r = attention_fwd_case_resolve(c, cus)
+    d = attention_fwd_case_data(r)
+    return r, d, attention_fwd_refs(r, d, attention_fwd_case_route(c, cus)[1])
+
+
+def attention_fwd_hold(got, refs, what, yard=None, margin=ROW_OPS_MARGIN):
+    """The hold of the attention forward: compare_rows with the project's margin and floor on
+      out     rows = the hd values of one (batch, head, query); an empty row is 0 exactly;
+      lse     (got.lse is not None) the vector without the empty rows, which equal ATTN_EMPTY_LSE exactly;
+      logits  (got.logits2 is not None: [B,H,Sq,>= Sk]) per query row over the allowed columns: disallowed entries and the
+              columns from Sk on are unspecified (0 on both sides), a -inf entry must be -inf exactly (then 0).
+    The tile rows and the last refs.tail query rows (the one-row kernel's, float32 yardstick) are blocks of their own, as in
+    linear_hold.  Returns {"out" | "lse" | "logits" | "tail out" | ...: RowCheck}; raises AssertionError at the first failure."""
+    spec, yard = refs.spec, yard or refs.yard
+    Sq, Sk = spec.logits2.shape[-2:]
+    out = torch.as_tensor(got.out).detach().cpu()
+    assert out.shape == spec.out.shape, f"{what}: out {tuple(out.shape)} against {tuple(spec.out.shape)}"
+    lse = None if got.lse is None else torch.as_tensor(got.lse).detach().cpu()
+    lg = None if got.logits2 is None else torch.as_tensor(got.logits2).detach().cpu()[..., :Sk].double()
+    assert lse is None or lse.shape == spec.lse.shape
+    assert lg is None or lg.shape == spec.logits2.shape, f"{what}: logits {tuple(lg.shape)} against {tuple(spec.logits2.shape)}"
+    checks = {}
+    for name, rows in (("", slice(0, Sq - refs.tail)), ("tail ", slice(Sq - refs.tail, Sq))):
+        if rows.start == rows.stop:
+            continue
+        empty = refs.empty[:, :, rows]
+        assert bool((out[:, :, rows][empty] == 0).all()), f"{what}: an empty row's out is not 0"
+        checks[name + "out"] = compare_rows(out[:, :, rows], spec.out[:, :, rows], yard.out[:, :, rows], f"{what} {name}out", margin)
+        if lse is not None:
+            assert bool((lse[:, :, rows][empty] == ATTN_EMPTY_LSE).all()), f"{what}: an empty row's lse is not 1e30"
+            if not bool(empty.all()):
+                checks[name + "lse"] = compare_rows(lse[:, :, rows][~empty], spec.lse[:, :, rows][~empty], yard.lse[:, :, rows][~empty],
+                                                    f"{what} {name}lse", margin)
+        if lg is not None:
+            sl = spec.logits2[:, :, rows]
+            allowed = spec.allowed[rows].expand_as(sl)
+            ninf = allowed & (sl == float("-inf"))
+            assert bool((lg[:, :, rows][ninf] == float("-inf")).all()), f"{what}: a -inf logit is not -inf"
+            keep, zero = allowed & ~ninf, torch.zeros_like(sl)
+            checks[name + "logits"] = compare_rows(torch.where(keep, lg[:, :, rows], zero), torch.where(keep, sl, zero),
+                                                   torch.where(keep, _attn_finite(yard.logits2[:, :, rows]), zero),
+                                                   f"{what} {name}logits", margin)
+    return checks

@@ -133,6 +133,34 @@ int isi_spec_splice_blend_f32(const float *audio_orig, const float *audio_ola, c
 size_t isi_stft_stretch_workspace_bytes(int B, int T, int F);
 int isi_stft_stretch_f32(const float *X, const float *pos, int pos_batch, float *out, void *workspace,
                          size_t workspace_bytes, int B, int T, int T_out, int F, int hop, void *stream);
+/* Formant correction of STFT frames by the true envelope (not in the reference; GANsynth_pytorch/stretch.py and bend.py;
+ * DESIGN.md section 6j; specification tests/formant_spec.py): `transpose` and `bend` move the pitch by reading the sound
+ * faster or slower, so a component at f in the stretched sound ends at rho f and should carry the envelope's value there.
+ * Y [B,T,2F] in isi_stft_stretch_f32's layout, ratio [ratio_batch,T] (ratio_batch 1 or B) on the device, cos_table [2F]:
+ * cos(pi i / F) made by the caller in float64 and rounded once; out [B,T,2F]; env [B,T,F+1] or NULL.  depth and max_gain
+ * are in nepers.  Per frame (b, t), with n = order, I = iterations:
+ *   P_j = fl(fl(re re) + fl(im im)) in float32 without FMA; Pmax = max_j P_j, NaN if any P_j is.
+ *   rho = ratio clamped to [1/4, 4]; a NaN counts as 1.
+ *   The frame is copied bit for bit unless 0 < Pmax < +inf, and when rho == 1.
+ *   L_j = max(1/2 ln P_j, 1/2 ln Pmax - depth); on k = 0 .. F: Lx_0 = L_0 (the dropped DC bin takes bin 1's value), Lx_k = L_{k-1}.
+ *   S(A): c_q = (1 / 2F) [A_0 + (-1)^q A_F + 2 sum_{k=1}^{F-1} A_k cos(pi q k / F)], q = 0 .. n - 1,
+ *         w_q = (1 + cos(pi q / n)) / 2,   V_k = w_0 c_0 + 2 sum_{q=1}^{n-1} w_q c_q cos(pi q k / F).
+ *   A(0) = Lx; for i = 1 .. I: V(i) = S(A(i-1)), A(i) = max(Lx, V(i)); V = V(I).  The count is fixed.
+ *   x = min(fl(rho k), F) in float32, i = min(floor x, F - 1), f = x - i, V_x = (1 - f) V_i + f V_{i+1},
+ *   out_j = exp(clamp(V_x - V_k, -max_gain, +max_gain)) (re_j, im_j), k = j + 1.  Phases are untouched.
+ * cos(pi q k / F) is cos_table[(q k) mod 2F]; the sums are float32 fma chains in a fixed order (a frame's bits depend on
+ * that frame and its ratio alone, not on B, T or the launch).  env receives V of every frame: a frame copied because
+ * rho == 1 still has its row computed; a frame copied because of Pmax has the row +0.0.
+ * No content of ratio leads to an access outside the arrays.  No atomics, no allocation, no host synchronisation;
+ * stream-ordered.  Refused before any launch: a null (env excepted) or misaligned pointer, B, T or F < 1, F < 2, order
+ * outside [2, min(F, ISI_FORMANT_MAX_ORDER)], iterations outside [1, ISI_FORMANT_MAX_ITERATIONS], ratio_batch outside
+ * {1, B}, a depth or max_gain that is NaN, negative or infinite, Y, out and env overlapping -- out == Y is not supported
+ * -- (ISI_E_INVALID); F > ISI_STFT_STRETCH_MAX_F, an array above 2^30 - 4 elements (ISI_E_UNSUPPORTED). */
+#define ISI_FORMANT_MAX_ORDER 256
+#define ISI_FORMANT_MAX_ITERATIONS 64
+int isi_formant_shift_f32(const float *Y, const float *ratio, int ratio_batch, const float *cos_table, float *out,
+                          float *env, int B, int T, int F, int order, int iterations, float depth, float max_gain,
+                          void *stream);
 /* One scale of the multi-scale spectral loss (reference utils/losses/spectral.py:78-118, where the STFTs come
  * from torch.stft): xp / xt = STFT rows [B*T][RS] (re block | im block of F bins, RS >= 2F) of the predicted and
  * the target audio.  fwd: per (sample, chunk of rows_per_block frames) the sums

@@ -8,13 +8,15 @@ tests/warp_resample_spec.py): every instant stays where it
 
     warp(audio [L] or [B, L], positions float64 [N] or [1 or B, N], cutoff=None) -> [.., N]
     bend_maps(L, semitones, times_s, fs_hz, hop) -> (r [L], phi [L], frame positions [J]), float64 (`bend` takes them on the host)
-    bend(helper, audio, semitones, times_s=None) -> the input's shape
+    bend(helper, audio, semitones, times_s=None, preserve_formants=False, formant_order=None, pitch=None) -> the input's shape
     vibrato(helper, audio, rate_hz, depth_cents, onset_s=0.0, ramp_s=0.1)
     glide(helper, audio, from_semitones, to_semitones, start_s=0.0, end_s=None)
 
-Not done: formants move with the pitch (a flattened voice keeps its vowel only for small corrections); a stretch of the
-curve at rate 1 still passes the vocoder and the ROLLOFF low-pass (the sound there is the re-synthesis, not the input's
-bits); no gradients.  One curve per call: the rows of a batch are bent alike.  No CPU path: the audio must live on the GPU."""
+With `preserve_formants` every stretched frame is corrected by the true envelope at the curve's local rate before the
+synthesis (isi_formant_shift_f32, csrc/formant.hip): the pitch follows the curve, the resonances stay.
+
+Not done: a stretch of the curve at rate 1 still passes the vocoder and the ROLLOFF low-pass (the sound there is the
+re-synthesis, not the input's bits); one envelope order per call, no envelope taken from another sound; no gradients.  One curve per call: the rows of a batch are bent alike.  No CPU path: the audio must live on the GPU."""
 from __future__ import annotations
 
 import ctypes as C
@@ -140,13 +142,26 @@ def bend_maps(L: int, semitones, times_s=None, fs_hz: int = 16000, hop: int = 64
     return r, phi, frames
 
 
+def frame_rates(r: torch.Tensor, frames: torch.Tensor, n_fft: int, hop: int) -> torch.Tensor:
+    """float32 [J]: the rate r at the centre of every stretched frame.  Frame j of the stretched sound sits at source frame
+    p = frames[j]; under the helper's framing a frame at p starts n_fft - hop samples before sample p hop, so its centre is
+    sample p hop + hop - n_fft / 2 -- rounded to the nearest sample and clamped to [0, L - 1]."""
+    centre = torch.round(frames * hop + (hop - n_fft / 2.0)).clamp(0, r.numel() - 1).to(torch.int64)
+    return r[centre].to(torch.float32)
+
+
 @torch.no_grad()
-def bend(helper, audio: torch.Tensor, semitones, times_s=None) -> torch.Tensor:
+def bend(helper, audio: torch.Tensor, semitones, times_s=None, preserve_formants: bool = False,
+         formant_order: Optional[int] = None, pitch: Optional[float] = None) -> torch.Tensor:
     """audio [L] or [B, L] (float32, on the GPU) -> the same shape, its pitch moved by the curve (`curve`: control points
     `semitones` at `times_s`, or one value per sample) at its own length and timing.  The sound, zero-padded so that the far
     side of the last output's support exists, goes through `helper._stft`, `stretch.stft_stretch` along phi^-1 followed by the
     trailing frames at rate 1, the helper's synthesis, and `warp` along phi.  A curve that is zero everywhere returns the
-    input itself."""
+    input itself.
+    preserve_formants: between the vocoder and the synthesis every stretched frame passes `stretch.formant_shift` with the
+    curve's rate at the frame's centre (`frame_rates`: sample p hop + hop - n_fft / 2 of the source for a frame at source
+    position p, clamped to the sound); the trailing frames behind phi(L) take 1 and are copied.  The envelope's order as
+    in `stretch.transpose`: `formant_order`, else from `pitch` (a MIDI number), else from `estimate_pitch` of the sound."""
     if audio.dim() not in (1, 2) or audio.shape[-1] == 0:
         raise ValueError(f"expected audio [L] or [B, L] with L > 0, got {tuple(audio.shape)}")
     L = audio.shape[-1]
@@ -154,6 +169,11 @@ def bend(helper, audio: torch.Tensor, semitones, times_s=None) -> torch.Tensor:
     s = curve(L, semitones, times_s, helper.fs_hz, "cpu")          # bad curves are refused before the GPU is asked for
     if not bool(s.any()):
         return audio
+    if not preserve_formants and (formant_order is not None or pitch is not None):
+        raise ValueError("bend: formant_order and pitch belong to preserve_formants=True")
+    order = None
+    if preserve_formants and (formant_order is not None or pitch is not None):
+        order = _stretch._envelope_order(helper, audio, formant_order, pitch)       # refused before the GPU is asked for
     _hip.require_gpu(audio, "audio")
     if audio.dtype != torch.float32:
         raise _hip.HipLibraryError(f"audio has dtype {audio.dtype}; expected float32")
@@ -170,6 +190,11 @@ def bend(helper, audio: torch.Tensor, semitones, times_s=None) -> torch.Tensor:
     assert got == T_all
     pos = torch.cat([frames.clamp(max=T_all - 1), torch.arange(T, T_all, dtype=torch.float64)]).to(torch.float32)
     Y = _stretch.stft_stretch(X, pos.to(dev), hop)
+    if preserve_formants:
+        if order is None:
+            order = _stretch._envelope_order(helper, audio, None, None)
+        rho = torch.cat([frame_rates(r, frames, N, hop), torch.ones(T_all - T, dtype=torch.float32)])
+        Y = _stretch.formant_shift(Y, rho.to(dev), order)
     z = _stretch._synthesise(helper, Y, (frames.numel() + tail) * hop)
     out = warp(z, phi.to(dev).unsqueeze(0), cut.to(dev).unsqueeze(0))
     return out[0] if audio.dim() == 1 else out
@@ -188,19 +213,22 @@ def vibrato_curve(L: int, fs_hz: int, rate_hz: float, depth_cents: float, onset_
     return depth_cents / 100.0 * ramp * torch.sin(2.0 * math.pi * rate_hz * t)
 
 
-def vibrato(helper, audio: torch.Tensor, rate_hz: float, depth_cents: float, onset_s: float = 0.0, ramp_s: float = 0.1
-            ) -> torch.Tensor:
-    """the sound with a vibrato of `rate_hz` and +-`depth_cents` from `onset_s` on, faded in over `ramp_s`"""
+def vibrato(helper, audio: torch.Tensor, rate_hz: float, depth_cents: float, onset_s: float = 0.0, ramp_s: float = 0.1,
+            preserve_formants: bool = False, formant_order: Optional[int] = None, pitch: Optional[float] = None) -> torch.Tensor:
+    """the sound with a vibrato of `rate_hz` and +-`depth_cents` from `onset_s` on, faded in over `ramp_s`; the formant
+    arguments are `bend`'s"""
     s = vibrato_curve(audio.shape[-1], helper.fs_hz, rate_hz, depth_cents, onset_s, ramp_s)
-    return bend(helper, audio, s)
+    return bend(helper, audio, s, None, preserve_formants, formant_order, pitch)
 
 
 def glide(helper, audio: torch.Tensor, from_semitones: float, to_semitones: float, start_s: float = 0.0,
-          end_s: Optional[float] = None) -> torch.Tensor:
+          end_s: Optional[float] = None, preserve_formants: bool = False, formant_order: Optional[int] = None,
+          pitch: Optional[float] = None) -> torch.Tensor:
     """the sound gliding from `from_semitones` to `to_semitones` (linear in semitones) between start_s and end_s (the end of
-    the sound by default), held before and after"""
+    the sound by default), held before and after; the formant arguments are `bend`'s"""
     end_s = audio.shape[-1] / float(helper.fs_hz) if end_s is None else float(end_s)
     start_s = float(start_s)
     if not (math.isfinite(start_s) and math.isfinite(end_s) and 0.0 <= start_s < end_s):
         raise ValueError(f"glide: need 0 <= start_s < end_s, got {start_s} and {end_s}")
-    return bend(helper, audio, [float(from_semitones), float(to_semitones)], [start_s, end_s])
+    return bend(helper, audio, [float(from_semitones), float(to_semitones)], [start_s, end_s], preserve_formants, formant_order,
+                pitch)

@@ -11,10 +11,20 @@ the partials of an attack stay aligned.  A transposition is a stretch by num / d
     stft_stretch(X [B, T, 2F], positions [T_out] or [1 or B, T_out], hop) -> [B, T_out, 2F]
     time_stretch(helper, audio [L] or [B, L], factor, keep_attack_s=0.0, keep_release_s=0.0) -> [.., T_out hop]
     transpose_ratio(semitones, max_denominator=512) -> (num, den, error in cents)
-    transpose(helper, audio, semitones) -> the input's shape
+    transpose(helper, audio, semitones, preserve_formants=False, formant_order=None, pitch=None) -> the input's shape
 
-Not done: transient detection (`keep_attack_s` is the caller's knowledge), formant preservation (a transposed voice moves
-its formants along), gradients.  No CPU path: the audio must live on the GPU."""
+A transposition reads the sound faster or slower, so the whole spectrum moves, resonances included.  With
+`preserve_formants` the stretched frames are corrected by the true envelope first (isi_formant_shift_f32, csrc/formant.hip;
+specification tests/formant_spec.py): a component that will end at rho f takes the envelope's value
+there, and the resonances stay where they were.
+
+    formant_order(fs_hz, f0_hz) -> int, half the pitch period in samples
+    formant_shift(Y [B, T, 2F], ratio [T] or [1 or B, T], order, iterations=16, floor_db=80, max_gain_db=40, return_envelope=False)
+    spectral_envelope(helper, audio, order=None, pitch=None) -> [.., T, F + 1] in nepers
+    shift_formants(helper, audio, semitones, order=None, pitch=None) -> the sound at its own pitch, its formants moved
+
+Not done: transient detection (`keep_attack_s` is the caller's knowledge), per-row envelope orders in a batch (one order
+per call), imposing one sound's envelope on another, gradients.  No CPU path: the audio must live on the GPU."""
 from __future__ import annotations
 
 import ctypes as C
@@ -102,14 +112,154 @@ def _seconds_to_frames(helper, seconds: float, what: str) -> int:
     return int(math.ceil(seconds * helper.fs_hz / helper.hop_length))
 
 
+DB = math.log(10.0) / 20.0              # nepers per dB
+UNVOICED_ORDER = 32
+_TABLES = {}
+
+
+def formant_order(fs_hz: float, f0_hz: float) -> int:
+    """round(0.5 fs / f0) clamped to [4, 256]: half the pitch period in samples, where the Hann lifter reaches zero -- the
+    envelope then follows what changes more slowly than the partials' spacing.  ValueError unless both are positive and finite."""
+    fs_hz, f0_hz = float(fs_hz), float(f0_hz)
+    if not (math.isfinite(fs_hz) and math.isfinite(f0_hz) and fs_hz > 0.0 and f0_hz > 0.0):
+        raise ValueError(f"formant_order: fs_hz and f0_hz must be positive and finite, got {fs_hz} and {f0_hz}")
+    return int(min(max(round(0.5 * fs_hz / f0_hz), 4), _hip.FORMANT_MAX_ORDER))
+
+
+def _cos_table(F: int, device) -> torch.Tensor:
+    """cos(pi i / F), i < 2F: float64 on the host, rounded once (the entries on the axes are exact)"""
+    key = (int(F), str(device))
+    if key not in _TABLES:
+        c = np.cos(math.pi * np.arange(2 * F) / F)
+        c[0], c[F] = 1.0, -1.0
+        if F % 2 == 0:
+            c[F // 2] = c[3 * F // 2] = 0.0
+        _TABLES[key] = torch.from_numpy(c.astype(np.float32)).to(device)
+    return _TABLES[key]
+
+
+def formant_shift(Y: torch.Tensor, ratio: torch.Tensor, order: int, iterations: int = 16, floor_db: float = 80.0,
+                  max_gain_db: float = 40.0, return_envelope: bool = False):
+    """Y float32 [B, T, 2F] (`stft_stretch`'s layout), ratio float32 [T] or [1 or B, T], both on the GPU -> [B, T, 2F]:
+    isi_formant_shift_f32.  Every frame is multiplied by exp(V(rho k) - V(k)), V its true envelope of `order` cepstral
+    coefficients after `iterations` passes, the log spectrum floored `floor_db` under the frame's peak and the gain held
+    within +-`max_gain_db`; rho is the frame's ratio clamped to [1/4, 4].  A frame whose ratio is 1 or NaN, and a frame that
+    is silent or holds a value that is not finite, is returned bit for bit.  return_envelope: also V [B, T, F + 1] in nepers.
+    ValueError for shapes and arguments the kernel refuses."""
+    _hip.require_gpu(Y, "Y")
+    _hip.require_gpu(ratio, "ratio")
+    if Y.dtype != torch.float32 or ratio.dtype != torch.float32:
+        raise _hip.HipLibraryError(f"Y and ratio must be float32, got {Y.dtype} and {ratio.dtype}")
+    if ratio.device != Y.device:
+        raise _hip.HipLibraryError(f"ratio lives on {ratio.device}, Y on {Y.device}")
+    if ratio.dim() == 1:
+        ratio = ratio.unsqueeze(0)
+    if Y.dim() != 3 or Y.shape[-1] % 2 or Y.shape[-1] < 4 or Y.shape[0] < 1 or Y.shape[1] < 1:
+        raise ValueError(f"Y: expected [B, T, 2F] with F >= 2, got {tuple(Y.shape)}")
+    B, T, F = Y.shape[0], Y.shape[1], Y.shape[2] // 2
+    if F > _hip.STFT_STRETCH_MAX_F:
+        raise ValueError(f"isi_formant_shift_f32 does not take F = {F} (at most {_hip.STFT_STRETCH_MAX_F})")
+    if ratio.dim() != 2 or ratio.shape[0] not in (1, B) or ratio.shape[1] != T:
+        raise ValueError(f"ratio: expected [T] or [1 or {B}, {T}], got {tuple(ratio.shape)}")
+    order, iterations = int(order), int(iterations)
+    if not 2 <= order <= min(F, _hip.FORMANT_MAX_ORDER):
+        raise ValueError(f"order must lie in 2 .. {min(F, _hip.FORMANT_MAX_ORDER)}, got {order}")
+    if not 1 <= iterations <= _hip.FORMANT_MAX_ITERATIONS:
+        raise ValueError(f"iterations must lie in 1 .. {_hip.FORMANT_MAX_ITERATIONS}, got {iterations}")
+    depth, max_gain = float(floor_db) * DB, float(max_gain_db) * DB
+    if not (math.isfinite(depth) and math.isfinite(max_gain) and depth >= 0.0 and max_gain >= 0.0):
+        raise ValueError(f"floor_db and max_gain_db must be finite and not negative, got {floor_db} and {max_gain_db}")
+    Y, ratio = Y.contiguous(), ratio.contiguous()
+    out = torch.empty_like(Y)
+    env = torch.empty(B, T, F + 1, dtype=torch.float32, device=Y.device) if return_envelope else None
+    _hip.check(_hip.lib().isi_formant_shift_f32(Y.data_ptr(), ratio.data_ptr(), ratio.shape[0], _cos_table(F, Y.device).data_ptr(),
+                                                out.data_ptr(), env.data_ptr() if return_envelope else None, B, T, F, order,
+                                                iterations, depth, max_gain, C.c_void_p(_hip.stream_ptr(Y.device))),
+               "isi_formant_shift_f32")
+    return (out, env) if return_envelope else out
+
+
+def _envelope_order(helper, audio: torch.Tensor, order: Optional[int], pitch: Optional[float]) -> int:
+    """the order in this precedence: `order`, `pitch` (a MIDI number), `estimate_pitch` of the sound (the first row of a
+    batch that is voiced); 32 for an unvoiced sound.  Never above F of the helper."""
+    F = helper.n_fft // 2
+    if order is not None:
+        order = int(order)
+        if not 2 <= order <= min(F, _hip.FORMANT_MAX_ORDER):
+            raise ValueError(f"formant order must lie in 2 .. {min(F, _hip.FORMANT_MAX_ORDER)}, got {order}")
+        return order
+    if pitch is None:
+        from GANsynth_pytorch.pitch import estimate_pitch
+        midi = estimate_pitch(audio, int(helper.fs_hz))[0].reshape(-1)
+        voiced = midi[~torch.isnan(midi)]
+        if voiced.numel() == 0:
+            return min(UNVOICED_ORDER, F)
+        pitch = float(voiced[0])
+    pitch = float(pitch)
+    if not math.isfinite(pitch):
+        raise ValueError(f"pitch must be a finite MIDI number, got {pitch}")
+    return min(formant_order(helper.fs_hz, 440.0 * 2.0 ** ((pitch - 69.0) / 12.0)), F)
+
+
+def _check_audio(audio: torch.Tensor) -> None:
+    if audio.dim() not in (1, 2) or audio.shape[-1] == 0:
+        raise ValueError(f"expected audio [L] or [B, L] with L > 0, got {tuple(audio.shape)}")
+    _hip.require_gpu(audio, "audio")
+    if audio.dtype != torch.float32:
+        raise _hip.HipLibraryError(f"audio has dtype {audio.dtype}; expected float32")
+
+
+def _analyse(helper, x: torch.Tensor):
+    """x [B, L] -> (X [B, T + extra, 2F], T): the helper's STFT of the sound zero-padded as `time_stretch` pads it"""
+    hop = helper.hop_length
+    extra, T = helper.n_fft // hop - 1, -(-x.shape[1] // hop)
+    X, T_all = helper._stft(torch.nn.functional.pad(x, (0, T * hop - x.shape[1] + extra * hop)))
+    assert T_all == T + extra
+    return X, T
+
+
 @torch.no_grad()
-def time_stretch(helper, audio: torch.Tensor, factor: float, keep_attack_s: float = 0.0, keep_release_s: float = 0.0
-                 ) -> torch.Tensor:
+def spectral_envelope(helper, audio: torch.Tensor, order: Optional[int] = None, pitch: Optional[float] = None) -> torch.Tensor:
+    """audio [L] or [B, L] -> [.., T, F + 1], T = ceil(L / hop): the true envelope of every frame of the helper's STFT in
+    nepers (ln of the magnitude), on DFT bins 0 .. F; a silent frame's row is 0.  The order as in `transpose`."""
+    _check_audio(audio)
+    x = audio.unsqueeze(0) if audio.dim() == 1 else audio
+    order = _envelope_order(helper, audio, order, pitch)
+    X, T = _analyse(helper, x)
+    X = X[:, :T].contiguous()
+    env = formant_shift(X, torch.ones(T, dtype=torch.float32, device=X.device), order, return_envelope=True)[1]
+    return env[0] if audio.dim() == 1 else env
+
+
+@torch.no_grad()
+def shift_formants(helper, audio: torch.Tensor, semitones: float, order: Optional[int] = None, pitch: Optional[float] = None
+                   ) -> torch.Tensor:
+    """audio [L] or [B, L] -> the same shape at its own pitch and length, its formants `semitones` higher (lower when
+    negative): the helper's STFT, isi_formant_shift_f32 with rho = 2^(-semitones / 12) (the value at f is then taken from
+    f / 2^(semitones / 12): the envelope moves up), the helper's synthesis.  0 returns the input itself."""
+    semitones = float(semitones)
+    if not math.isfinite(semitones):
+        raise ValueError(f"semitones must be finite, got {semitones}")
+    if semitones == 0.0:
+        return audio
+    _check_audio(audio)
+    x = audio.unsqueeze(0) if audio.dim() == 1 else audio
+    order = _envelope_order(helper, audio, order, pitch)
+    X, T = _analyse(helper, x)
+    ratio = torch.full((X.shape[1],), 2.0 ** (-semitones / 12.0), dtype=torch.float32, device=X.device)
+    out = _synthesise(helper, formant_shift(X, ratio, order), T * helper.hop_length)[:, :x.shape[1]].contiguous()
+    return out[0] if audio.dim() == 1 else out
+
+
+@torch.no_grad()
+def time_stretch(helper, audio: torch.Tensor, factor: float, keep_attack_s: float = 0.0, keep_release_s: float = 0.0,
+                 _formant=None) -> torch.Tensor:
     """audio [L] or [B, L] (float32, on the GPU) -> [.., T_out hop] with T = ceil(L / hop), T_out = max(1, round(T factor)):
     the sound `factor` times as long at its own pitch.  The first `keep_attack_s` and the last `keep_release_s` seconds keep
     their own rate.  The STFT is taken of the audio zero-padded by n_fft / hop - 1 hops, as `to_audio_spliced` does; those
     trailing frames follow the stretched ones at rate 1, so that the last samples meet complete overlap sums.  factor == 1
-    re-synthesises the sound from its own frames (the DC bin is dropped, nothing else)."""
+    re-synthesises the sound from its own frames (the DC bin is dropped, nothing else).  `_formant` = (rho, order) is
+    `transpose`'s hook: the stretched frames, the trailing ones included, pass `formant_shift` at that ratio."""
     if audio.dim() not in (1, 2) or audio.shape[-1] == 0:
         raise ValueError(f"expected audio [L] or [B, L] with L > 0, got {tuple(audio.shape)}")
     x = audio.unsqueeze(0) if audio.dim() == 1 else audio
@@ -128,6 +278,9 @@ def time_stretch(helper, audio: torch.Tensor, factor: float, keep_attack_s: floa
     if T_all < 2:                                        # hop == n_fft and a single frame: nothing to advance along
         raise ValueError("time_stretch needs at least two frames")
     Y = stft_stretch(X, pos.to(x.device), hop)
+    if _formant is not None:                             # (rho, order): `transpose` corrects the stretched frames
+        rho, order = _formant
+        Y = formant_shift(Y, torch.full((Y.shape[1],), rho, dtype=torch.float32, device=Y.device), order)
     out = _synthesise(helper, Y, T_out * hop)
     return out[0] if audio.dim() == 1 else out
 
@@ -167,14 +320,26 @@ def transpose_ratio(semitones: float, max_denominator: int = 512) -> Tuple[int, 
 
 
 @torch.no_grad()
-def transpose(helper, audio: torch.Tensor, semitones: float) -> torch.Tensor:
+def transpose(helper, audio: torch.Tensor, semitones: float, preserve_formants: bool = False,
+              formant_order: Optional[int] = None, pitch: Optional[float] = None) -> torch.Tensor:
     """audio [L] or [B, L] -> the same shape, `semitones` higher (lower when negative) at its own length: `time_stretch` by
     num / den = `transpose_ratio(semitones)`, then `resample(y, num, den)`, trimmed or zero-padded to L.  0 semitones
-    returns the input itself."""
+    returns the input itself.
+    preserve_formants: the stretched frames pass `formant_shift` with rho = num / den between the vocoder and the synthesis,
+    so that the resonances stay where they were.  The envelope's order, in this precedence: `formant_order`; `formant_order
+    (fs, f0)` of `pitch`, the source's MIDI number; of `estimate_pitch` of the sound (32 when it is unvoiced).  One order per
+    call: a batch takes its first voiced row's."""
     num, den, _ = transpose_ratio(semitones)
     if num == den:
         return audio
-    y = time_stretch(helper, audio, num / den)
+    hook = None
+    if preserve_formants:
+        if audio.dim() not in (1, 2) or audio.shape[-1] == 0:
+            raise ValueError(f"expected audio [L] or [B, L] with L > 0, got {tuple(audio.shape)}")
+        hook = (num / den, _envelope_order(helper, audio, formant_order, pitch))
+    elif formant_order is not None or pitch is not None:
+        raise ValueError("transpose: formant_order and pitch belong to preserve_formants=True")
+    y = time_stretch(helper, audio, num / den) if hook is None else time_stretch(helper, audio, num / den, _formant=hook)
     z = _resample.resample(y, num, den)
     L = audio.shape[-1]
     if z.shape[-1] < L:

@@ -323,6 +323,10 @@ int isi_stft_stretch_f32(const float *X, const float *pos, int pos_batch, float 
                          int B, int T, int T_out, int F, int hop, void *stream) {
   return stft_stretch_f32(X, pos, pos_batch, out, workspace, workspace_bytes, B, T, T_out, F, hop, S(stream));
 }
+int isi_formant_shift_f32(const float *Y, const float *ratio, int ratio_batch, const float *cos_table, float *out, float *env,
+                          int B, int T, int F, int order, int iterations, float depth, float max_gain, void *stream) {
+  return formant_shift_f32(Y, ratio, ratio_batch, cos_table, out, env, B, T, F, order, iterations, depth, max_gain, S(stream));
+}
 int isi_resample_geometry(int fs_in, int fs_out, int *orig, int *new_, int *width, int *taps) {
   return resample_geometry(fs_in, fs_out, orig, new_, width, taps);
 }

@@ -365,6 +365,9 @@ int spec_splice_blend_f32(const float *audio_orig, const float *audio_ola, const
 size_t stft_stretch_workspace_bytes(int B, int T, int F);
 int stft_stretch_f32(const float *X, const float *pos, int pos_batch, float *out, void *workspace, size_t workspace_bytes,
                      int B, int T, int T_out, int F, int hop, hipStream_t st);
+// formant.hip: true-envelope formant correction of STFT frames
+int formant_shift_f32(const float *Y, const float *ratio, int ratio_batch, const float *cos_table, float *out, float *env, int B,
+                      int T, int F, int order, int iterations, float depth, float max_gain, hipStream_t st);
 int resample_geometry(int fs_in, int fs_out, int *orig, int *new_, int *width, int *taps);
 int64_t resample_out_len(int64_t L, int orig, int new_);
 int resample_f32(const float *x, int64_t x_stride, float *y, int64_t y_stride, int B, int64_t L, int orig, int new_,

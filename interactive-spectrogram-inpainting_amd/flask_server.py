@@ -12,13 +12,16 @@ query arguments and JSON schema for the operations built on MI355X
        /analyze-audio takes it, converted to the models' rate), and `codes`, the JSON /get-audio takes (a form field or a
        file part) -> audio/wav: the upload's own samples wherever the codes are those of the upload, the decoded codes
        where they were edited, phase-locked to the upload at both seams (csrc/spec_splice.hip)
-  POST /transpose-audio?semitones= | ?to_pitch=   (not in the reference) multipart: file `audio` (as /analyze-audio takes
-       it) -> audio/wav at the models' rate: the sound `semitones` higher (fractional and negative values too), or at
-       the MIDI pitch `to_pitch` (its own pitch is estimated; 400 when it is unvoiced), at its own length
+  POST /transpose-audio?semitones= | ?to_pitch= [&preserve_formants=1]   (not in the reference) multipart: file `audio` (as
+       /analyze-audio takes it) -> audio/wav at the models' rate: the sound `semitones` higher (fractional and negative
+       values too), or at the MIDI pitch `to_pitch` (its own pitch is estimated; 400 when it is unvoiced), at its own
+       length; with preserve_formants=1 its resonances stay where they were (csrc/formant.hip)
+  POST /shift-formants?semitones=   (not in the reference) multipart: file `audio` -> audio/wav: the sound at its own pitch
+       and length, its formants `semitones` higher (GANsynth_pytorch/stretch.py `shift_formants`, csrc/formant.hip)
   POST /stretch-audio?factor=&keep_attack_s=&keep_release_s=   (not in the reference) multipart: file `audio` ->
        audio/wav: the sound `factor` times as long at its own pitch; the first / last seconds named keep their own rate
        (both: GANsynth_pytorch/stretch.py, csrc/stft_stretch.hip; the arguments may also be form fields)
-  POST /bend-audio?vibrato_hz=&vibrato_cents= | ?glide_from=&glide_to= | ?flatten=1[&to_pitch=]   (not in the reference)
+  POST /bend-audio?vibrato_hz=&vibrato_cents= | ?glide_from=&glide_to= | ?flatten=1[&to_pitch=] [&preserve_formants=1]   (not in the reference)
        multipart: file `audio` -> audio/wav at its own length: a vibrato added, a glide between two transpositions in
        semitones, or the sound's own vibrato and drift removed and the sound tuned to the MIDI pitch `to_pitch` (its own
        rounded pitch by default; 400 when it is unvoiced)   (GANsynth_pytorch/bend.py, csrc/warp_resample.hip)
@@ -46,6 +49,7 @@ from __future__ import annotations
 
 import io
 import json
+import math
 import struct
 import zipfile
 from typing import Mapping, Optional
@@ -212,10 +216,29 @@ def create_app(vqvae, transformer_top, transformer_bottom, label_encoders_per_mo
         semitones, to_pitch = number('semitones'), number('to_pitch')
         if (semitones is None) == (to_pitch is None):
             flask.abort(400, description="give exactly one of semitones and to_pitch")
+        keep = dict(preserve_formants=True) if number('preserve_formants', 0.0) != 0.0 else {}
         original = uploaded_audio()
         try:
             audio, _, _ = inpainting.transpose_sound(vqvae, spectrograms_helper, original.to(device), semitones=semitones,
-                                                     to_pitch=to_pitch, re_encode=False)
+                                                     to_pitch=to_pitch, re_encode=False, **keep)
+        except ValueError as e:
+            flask.abort(400, description=str(e))
+        return flask.send_file(io.BytesIO(_wav_bytes(audio.reshape(-1), spectrograms_helper.fs_hz)), mimetype="audio/wav",
+                               max_age=0)
+
+    @app.route('/shift-formants', methods=['POST'])
+    def shift_formants():
+        if spectrograms_helper is None:
+            flask.abort(501)
+        semitones = number('semitones')
+        if semitones is None:
+            flask.abort(400, description="semitones is missing")
+        if not math.isfinite(semitones) or abs(semitones) > 24.0:
+            flask.abort(400, description=f"semitones must be finite and within +-24, got {semitones}")
+        original = uploaded_audio()
+        try:
+            audio, _, _ = inpainting.shift_formants_sound(vqvae, spectrograms_helper, original.to(device), semitones,
+                                                          re_encode=False)
         except ValueError as e:
             flask.abort(400, description=str(e))
         return flask.send_file(io.BytesIO(_wav_bytes(audio.reshape(-1), spectrograms_helper.fs_hz)), mimetype="audio/wav",
@@ -234,12 +257,13 @@ def create_app(vqvae, transformer_top, transformer_bottom, label_encoders_per_mo
             flask.abort(400, description="give exactly one of vibrato_hz + vibrato_cents, glide_from + glide_to and flatten=1")
         if to_pitch is not None and not flatten:
             flask.abort(400, description="to_pitch belongs to flatten=1")
+        keep = dict(preserve_formants=True) if number('preserve_formants', 0.0) != 0.0 else {}
         original = uploaded_audio()
         try:
             audio, _, _ = inpainting.bend_sound(vqvae, spectrograms_helper, original.to(device),
                                                 vibrato=vib if vib[0] is not None else None,
                                                 glide=gl if gl[0] is not None else None, flatten=flatten, to_pitch=to_pitch,
-                                                re_encode=False)
+                                                re_encode=False, **keep)
         except ValueError as e:
             flask.abort(400, description=str(e))
         return flask.send_file(io.BytesIO(_wav_bytes(audio.reshape(-1), spectrograms_helper.fs_hz)), mimetype="audio/wav",

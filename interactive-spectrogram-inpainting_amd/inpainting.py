@@ -27,7 +27,9 @@ routes (flask_server.py), free of HTTP so that they can be called, tested and ti
   stretch_sound / transpose_sound   a sound (or decoded codes) at another length, a sound at another pitch -- by a number
                       of semitones, to a MIDI pitch, or to the estimated pitch of another sound -- with its codes, so that
                       morphs and searches can compare sounds at equal pitch (not in the reference: csrc/stft_stretch.hip,
-                      GANsynth_pytorch/stretch.py)
+                      GANsynth_pytorch/stretch.py); `preserve_formants=True` there and on `bend_sound` leaves the
+                      resonances where they were (csrc/formant.hip)
+  shift_formants_sound   a sound at its own pitch with its formants moved, with its codes
   spectrogram_png     the decoded log-mel magnitude as a viridis PNG (:103-143, 1024-1046)
 
 The heavy work is `sample.sample_model` (encoder pass + KV-cached native decoding loop),
@@ -631,12 +633,15 @@ def stretch_sound(vqvae, spectrograms_helper, audio: Optional[torch.Tensor] = No
 
 @torch.no_grad()
 def transpose_sound(vqvae, spectrograms_helper, audio: torch.Tensor, semitones: Optional[float] = None,
-                    to_pitch: Optional[float] = None, like: Optional[torch.Tensor] = None, re_encode: bool = True):
+                    to_pitch: Optional[float] = None, like: Optional[torch.Tensor] = None, re_encode: bool = True,
+                    preserve_formants: bool = False):
     """A sound at another pitch and its own length: (audio, top_code, bottom_code).  Exactly one of `semitones` (may be
     fractional), `to_pitch` (a MIDI number) and `like` (another sound, whose estimated pitch is the target).  The last two
     take the source's pitch from `GANsynth_pytorch.pitch.estimate_pitch`, unrounded; ValueError when a sound they need the
     pitch of is unvoiced.  Mono audio [samples] at the models' rate.  The codes come from `analyze_audio` of the result
-    (None, None with re_encode=False), so that it can be morphed, searched and inpainted like any other sound."""
+    (None, None with re_encode=False), so that it can be morphed, searched and inpainted like any other sound.
+    preserve_formants: the resonances stay where they were (`GANsynth_pytorch.stretch.transpose`); the envelope's order comes
+    from the source's pitch, the estimate made here where `to_pitch` or `like` needed one."""
     from GANsynth_pytorch import stretch
     from GANsynth_pytorch.pitch import estimate_pitch as estimate
     if sum(v is not None for v in (semitones, to_pitch, like)) != 1:
@@ -655,8 +660,29 @@ def transpose_sound(vqvae, spectrograms_helper, audio: torch.Tensor, semitones: 
             pitch_of(like.to(device=device, dtype=torch.float32).reshape(-1), "the sound to be like")
         if not math.isfinite(target):
             raise ValueError(f"transpose_sound: to_pitch must be finite, got {target}")
-        semitones = target - pitch_of(x, "the sound")
-    y = stretch.transpose(spectrograms_helper, x, float(semitones))
+        own = pitch_of(x, "the sound")
+        semitones = target - own
+    else:
+        own = None
+    if preserve_formants:
+        y = stretch.transpose(spectrograms_helper, x, float(semitones), preserve_formants=True, pitch=own)
+    else:
+        y = stretch.transpose(spectrograms_helper, x, float(semitones))
+    if not re_encode:
+        return y, None, None
+    top_code, bottom_code = analyze_audio(vqvae, spectrograms_helper, y, y.numel(), device)
+    return y, top_code, bottom_code
+
+
+@torch.no_grad()
+def shift_formants_sound(vqvae, spectrograms_helper, audio: torch.Tensor, semitones: float, re_encode: bool = True):
+    """A sound at its own pitch and length with its formants `semitones` higher (lower when negative): (audio, top_code,
+    bottom_code), like `transpose_sound` (`GANsynth_pytorch.stretch.shift_formants`: a darker or brighter instrument playing
+    the same note).  ValueError for a value that is not finite.  Mono audio [samples] at the models' rate."""
+    from GANsynth_pytorch import stretch
+    device = _sound_device(audio, vqvae, spectrograms_helper)
+    x = audio.to(device=device, dtype=torch.float32).reshape(-1)
+    y = stretch.shift_formants(spectrograms_helper, x, semitones)
     if not re_encode:
         return y, None, None
     top_code, bottom_code = analyze_audio(vqvae, spectrograms_helper, y, y.numel(), device)
@@ -682,7 +708,7 @@ def contour_curve(track, clip_pitch: float, n_samples: int, fs_hz: int, max_corr
 @torch.no_grad()
 def bend_sound(vqvae, spectrograms_helper, audio: torch.Tensor, curve=None, vibrato=None, glide=None, flatten: bool = False,
                to_pitch: Optional[float] = None, contour_of: Optional[torch.Tensor] = None, times_s=None,
-               max_correction: float = 1.5, re_encode: bool = True):
+               max_correction: float = 1.5, re_encode: bool = True, preserve_formants: bool = False):
     """A sound with its pitch contour redrawn, at its own length: (audio, top_code, bottom_code), like `transpose_sound`.
     Exactly one of
       curve       semitones over time: control points at `times_s` (seconds; linear between, held outside), or one value per sample
@@ -694,7 +720,9 @@ def bend_sound(vqvae, spectrograms_helper, audio: torch.Tensor, curve=None, vibr
     The contours come from `GANsynth_pytorch.pitch.pitch_contour` (`contour_curve`: frames that are unvoiced or further than
     `max_correction` semitones from their clip's pitch take the nearest accepted frame's value).  ValueError for an unvoiced
     sound where a contour is needed and for curves `GANsynth_pytorch.bend.curve` refuses.  Mono audio [samples] at the
-    models' rate; the codes come from `analyze_audio` of the result (None, None with re_encode=False)."""
+    models' rate; the codes come from `analyze_audio` of the result (None, None with re_encode=False).
+    preserve_formants: the resonances stay where they were (`GANsynth_pytorch.bend.bend`); the envelope's order comes from
+    the clip's pitch, the estimate made here where a contour needed one."""
     from GANsynth_pytorch import bend as _bend
     from GANsynth_pytorch.pitch import estimate_pitch as estimate, pitch_contour
     chosen = sum([curve is not None, vibrato is not None, glide is not None, bool(flatten), contour_of is not None])
@@ -712,22 +740,25 @@ def bend_sound(vqvae, spectrograms_helper, audio: torch.Tensor, curve=None, vibr
             raise ValueError(f"bend_sound: {name} is unvoiced, it has no pitch contour")
         return contour_curve(pitch_contour(sound, fs_hz), midi, x.numel(), fs_hz, max_correction), midi
 
+    keep = dict(preserve_formants=True) if preserve_formants else {}
     if vibrato is not None:
         rate_hz, depth_cents = vibrato
-        y = _bend.vibrato(spectrograms_helper, x, rate_hz, depth_cents)
+        y = _bend.vibrato(spectrograms_helper, x, rate_hz, depth_cents, **keep)
     elif glide is not None:
-        y = _bend.glide(spectrograms_helper, x, glide[0], glide[1])
+        y = _bend.glide(spectrograms_helper, x, glide[0], glide[1], **keep)
     elif curve is not None:
-        y = _bend.bend(spectrograms_helper, x, curve, times_s)
+        y = _bend.bend(spectrograms_helper, x, curve, times_s, **keep)
     elif flatten:
         own, clip = contour(x, "the sound")
         target = float(to_pitch) if to_pitch is not None else float(round(clip))
         if not math.isfinite(target):
             raise ValueError(f"bend_sound: to_pitch must be finite, got {target}")
-        y = _bend.bend(spectrograms_helper, x, target - own)
+        if preserve_formants:
+            keep["pitch"] = clip
+        y = _bend.bend(spectrograms_helper, x, target - own, **keep)
     else:
         other, _ = contour(contour_of.to(device=device, dtype=torch.float32).reshape(-1), "the sound whose contour is taken")
-        y = _bend.bend(spectrograms_helper, x, other - other.median())
+        y = _bend.bend(spectrograms_helper, x, other - other.median(), **keep)
     if not re_encode:
         return y, None, None
     top_code, bottom_code = analyze_audio(vqvae, spectrograms_helper, y, y.numel(), device)

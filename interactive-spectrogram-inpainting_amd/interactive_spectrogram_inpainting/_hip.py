@@ -19,6 +19,9 @@ _LIB_PATH = _PKG_DIR.parent / "lib" / "libisi_hip.so"
 ISI_MAX_STAGES = 4
 ISI_MAX_RES = 8
 MODE_ENCODE, MODE_DECODE, MODE_FORWARD = 1, 2, 3
+STFT_STRETCH_MAX_F = 2048            # ISI_STFT_STRETCH_MAX_F
+FORMANT_MAX_ORDER = 256              # ISI_FORMANT_MAX_ORDER
+FORMANT_MAX_ITERATIONS = 64          # ISI_FORMANT_MAX_ITERATIONS
 
 
 class HipLibraryError(RuntimeError):
@@ -271,6 +274,7 @@ SIGNATURES = {
     "isi_stft_stretch_f32": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "isi_resample_geometry": (C.c_int, [C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4),
     "isi_resample_out_len": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
+    "isi_formant_shift_f32": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P]),
     "isi_resample_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P]),
     "isi_warp_resample_f32": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, _P, C.c_int64, C.c_int, C.c_int64, C.c_int64, _P]),
     "isi_pitch_frames": (C.c_int64, [C.c_int64, C.c_int, C.c_int, C.c_int]),

@@ -639,6 +639,31 @@ int isi_conv_transpose2d_k4s2_gated_f32(const isi_src *src, const float *packed_
                                         const float *bias, const float *gate, const isi_dst *dst,
                                         int B, int H, int W, int Cout, int flags, void *stream);
 
+/* Which kernel would the call run?  The arguments of isi_conv2d_gated_f32 / isi_conv_transpose2d_k4s2_gated_f32 (`gate`
+ * may be NULL: the plain call), the same validation and planning, NOTHING launched and no device asked (pointers are
+ * looked at for null-ness and alignment only).  Returns a negative status where the call would be refused, else
+ *   family | (BN / 32) << 4 | MODE << 8 | PREC << 10 | OUTP << 13 | slice_major << 14
+ * family = ISI_CONV_ROUTE_IGEMM: the implicit-GEMM kernel's instance -- BN: tile width 32 / 64 / 128; MODE: loader,
+ * 0 uniform (vectorised channels-last sources, a 32-wide K chunk inside one source), 1 dual-source, 2 scalar gather;
+ * PREC: products, 0 exact fp32, 1 bf16x3, 2 bf16x6, 3 f16x3, 4 f16x3 with the pack-time weight pieces; OUTP: pair-format
+ * output; slice_major: K walked slice-major (for each 32-channel slice all taps) instead of tap-major.
+ * Every other family is a hand-off to a kernel of its own, reported and not looked into (the other fields are 0).
+ * Rules the answer makes visible: only the uniform loader runs split products -- a split flag on a dual-source or
+ * gather launch is IGNORED (PREC 0, exact fp32), as it is for K < 128 (bf16x3 at Cout > 32: K < 64; at Cout <= 32 bf16x3
+ * needs K >= 128 like the other modes); with Cout <= 32 there is no PREC 4 instance: ISI_CONV_W16 reports PREC 3 and the weight pieces are not read (same results bit for bit). */
+#define ISI_CONV_ROUTE_IGEMM 1            /* conv_igemm_f32_kernel                                                  */
+#define ISI_CONV_ROUTE_PAIR_DMA 2         /* the LDS-DMA kernel of the pair pipeline (isi_conv2d_pair_route shapes)   */
+#define ISI_CONV_ROUTE_FIRST 3            /* the 2-channel first layer's kernel                                     */
+#define ISI_CONV_ROUTE_GEMM 4             /* a dense 1x1 over rows: the linear layers' GEMM (isi_linear_route)      */
+#define ISI_CONV_ROUTE_CONVT_SMALL 5      /* transposed, few output channels: GEMM + col2im gather                  */
+#define ISI_CONV_ROUTE_CONVT_SMALL_PAIR 6 /* ... its pair-format-input form                                         */
+#define ISI_CONV_ROUTE_CONVT_PAIR 7       /* transposed: the fused-phase LDS-DMA kernel (isi_conv_transpose2d_pair_route) */
+int isi_conv2d_route(const isi_src *src0, const isi_src *src1, const float *packed_w, const float *bias,
+                     const isi_src *residual, const float *gate, const isi_dst *dst, int B, int H, int W, int Cout,
+                     int KH, int KW, int stride, int pad, int flags);
+int isi_conv_transpose2d_k4s2_route(const isi_src *src, const float *packed_w, const float *bias, const float *gate,
+                                    const isi_dst *dst, int B, int H, int W, int Cout, int flags);
+
 /* Weight gradient dW (packed like the forward weight: [nphase][Cout][Kpad]) of a
  * convolution (transposed = 0) or ConvTranspose2d(k4,s2,p1) (transposed = 1) whose input
  * was cat(src0, src1) [B,*,H,W] and whose output gradient is dy, dense channels-last

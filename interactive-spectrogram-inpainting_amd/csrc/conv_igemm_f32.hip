@@ -551,10 +551,25 @@ static int launch_cfg(const ConvKArgs &a, int nphase, hipStream_t stream) {
   return check_launch("conv_igemm_f32");
 }
 
-static int launch_conv(const ConvKArgs &a_in, bool scalar_a, int nphase, hipStream_t stream) {
-  ConvKArgs a = a_in;
+// Which kernel a filled ConvKArgs runs: the ONE place that decides (launch_conv switches on the answer, the route queries
+// isi_conv2d_route / isi_conv_transpose2d_k4s2_route report it).  Pure: reads its arguments and the knobs, touches no device.
+struct ConvRoute {
+  int family;        // ISI_CONV_ROUTE_IGEMM: this file's kernel <128, bn, MODE = mode, PREC = prec, OUTP = outp>;
+                     // ISI_CONV_ROUTE_PAIR_DMA: handed to conv_pair_f16.hip; 0: refused (`why`)
+  int bn, mode, prec, outp, chunk_major;
+  const char *why;
+};
+
+static int pack_route(const ConvRoute &r) {
+  return r.family | (r.bn / 32) << 4 | r.mode << 8 | r.prec << 10 | r.outp << 13 | r.chunk_major << 14;
+}
+
+static ConvRoute conv_route(const ConvKArgs &a, bool scalar_a, int nphase) {
+  ConvRoute r = {ISI_CONV_ROUTE_IGEMM, 0, 0, 0, 0, 0, nullptr};
+  const auto refuse = [&r](const char *why) { r.family = 0; r.why = why; return r; };
   const int mode = scalar_a ? 2 : (a.src_uniform ? 0 : 1);
-  a.chunk_major = (mode == 0 && a.KH * a.KW > 1 && a.C0 % kBK == 0 && a.Cin % kBK == 0) ? 1 : 0;
+  r.mode = mode;
+  r.chunk_major = (mode == 0 && a.KH * a.KW > 1 && a.C0 % kBK == 0 && a.Cin % kBK == 0) ? 1 : 0;
   const bool two = a.Cin > a.C0;
   // the LDS-DMA kernel of the pair pipeline (conv_pair_f16.hip): pair8 sources, blocked weight pieces, whole
   // 64-column output tiles, channels-last output, no residual
@@ -566,6 +581,55 @@ static int launch_conv(const ConvKArgs &a_in, bool scalar_a, int nphase, hipStre
   if (dma_shape && a.bf16x3 == 3 && a.w16 && mode == 0 && a.in0_pair && (!two || a.in1_pair) && !a.res && a.nz <= 1 && a.oc == 1 &&
       conv_pair_kernel_ok(a.C0, a.Cin - a.C0, a.Cout, a.KH * a.KW) && a.KH <= 4 && a.KW <= 4 && a.M < (1 << 24) &&
       a.in0_bytes < 0x70000000u && a.in1_bytes < 0x70000000u) {
+    r.family = ISI_CONV_ROUTE_PAIR_DMA;
+    r.mode = r.chunk_major = 0;   // (that kernel's own plan: not looked into)
+    return r;
+  }
+  if (a.twin) return refuse("conv: the fp32 twin of a pair-format output is written by the LDS-DMA kernel only "
+                            "(pair sources of 32-channel multiples, Cout % 64 == 0, K >= 256, dense channels-last output)");
+  if ((a.in0_pair || a.in1_pair || a.out_pair) && !(a.bf16x3 == 3 && a.w16 && mode == 0 && a.Cout > 32 && a.K >= 128))
+    return refuse("conv: pair-format tensors need the split-f16 kernels (ISI_CONV_F16X3 | ISI_CONV_W16, "
+                  "channels-last sources of 32-channel multiples, Cout > 32, K >= 128)");
+  if (a.bf16x3 && mode == 0 && a.Cout <= 32 && a.K >= 128 && !a.out_pair && !a.in0_pair && !a.in1_pair) {
+    // the residual blocks' 32-channel side (3x3 C -> 32 forward, 1x1 C -> 32 input gradient): 128 x 32 tiles, one
+    // 32 x 32 accumulator tile per wave.  On the fp32 matrix pipe these layers ran AT its peak (148 of 157 TFLOP/s
+    // for the 3x3 at B = 64) -- the split products have 5x that ceiling
+    r.bn = 32;
+    r.prec = a.bf16x3;   // (3: pieces prepared at pack time are not read at this width)
+    return r;
+  }
+  // (round 5: the three-term split-bf16 mode -- the training step's input gradients -- also takes K = 64..127: the 1x1
+  // quantiser convolutions' input gradients (K = embed_dim = 64, 192 output channels at the bottom resolution) ran on the
+  // fp32 matrix pipe, 142 us of a step)
+  if (a.bf16x3 && mode == 0 && a.Cout > 32 && (a.K >= 128 || (a.bf16x3 == 1 && a.K >= 64 && !a.in0_pair && !a.in1_pair && !a.out_pair))) {
+    // 128x64 tiles are ~20 % slower per FLOP than 128x128, but a GEMM that fills less than the chip's
+    // 3 workgroups per CU with 128x128 tiles (the prior's d x d linears at 8 k rows: 260 tiles) finishes
+    // sooner with twice as many, half as long, workgroups
+    const long tiles128 = (long)((a.M + 127) / 128) * ((a.Cout + 127) / 128) * nphase * (a.nz > 1 ? a.nz : 1);
+    const bool narrow = a.Cout <= 64 || tiles128 < 640;
+    r.bn = narrow ? 64 : 128;
+    // 2: six-term split, fp32-grade products; 3: split-f16, fp32-grade products from three terms, f16 range;
+    // 4: split-f16 with the weights' pieces prepared at pack time
+    r.prec = (a.bf16x3 == 3 && a.w16) ? 4 : a.bf16x3;
+    if (r.prec == 4 && a.out_pair) {
+      if (a.oc != 1 || (a.Cout & 7)) return refuse("conv: a pair-format output is channels-last with Cout % 8 == 0");
+      r.outp = 1;
+    }
+    return r;
+  }
+  r.bn = a.Cout <= 32 ? 32 : a.Cout <= 64 ? 64 : 128;
+  return r;
+}
+
+// route_out != nullptr: report the packed route (or the refusal's status) and launch nothing
+static int launch_conv(const ConvKArgs &a_in, bool scalar_a, int nphase, hipStream_t stream, int *route_out = nullptr) {
+  ConvKArgs a = a_in;
+  const ConvRoute r = conv_route(a, scalar_a, nphase);
+  if (!r.family) return unsupported(r.why);
+  if (route_out) { *route_out = pack_route(r); return ISI_OK; }
+  a.chunk_major = r.chunk_major;
+  if (r.family == ISI_CONV_ROUTE_PAIR_DMA) {
+    const bool two = a.Cin > a.C0;
     PairConvArgs c;
     memset(&c, 0, sizeof c);
     c.in0 = a.in0; c.in1 = two ? a.in1 : nullptr; c.w16 = a.w16; c.bias = a.bias; c.out = a.out;
@@ -579,59 +643,22 @@ static int launch_conv(const ConvKArgs &a_in, bool scalar_a, int nphase, hipStre
     c.out_pair = a.out_pair; c.twin = a.twin;
     return conv_pair_f16(c, stream);
   }
-  if (a.twin) return unsupported("conv: the fp32 twin of a pair-format output is written by the LDS-DMA kernel only "
-                                 "(pair sources of 32-channel multiples, Cout % 64 == 0, K >= 256, dense channels-last output)");
-  if ((a.in0_pair || a.in1_pair || a.out_pair) && !(a.bf16x3 == 3 && a.w16 && mode == 0 && a.Cout > 32 && a.K >= 128))
-    return unsupported("conv: pair-format tensors need the split-f16 kernels (ISI_CONV_F16X3 | ISI_CONV_W16, "
-                       "channels-last sources of 32-channel multiples, Cout > 32, K >= 128)");
-  if (a.bf16x3 && mode == 0 && a.Cout <= 32 && a.K >= 128 && !a.out_pair && !a.in0_pair && !a.in1_pair) {
-    // the residual blocks' 32-channel side (3x3 C -> 32 forward, 1x1 C -> 32 input gradient): 128 x 32 tiles, one
-    // 32 x 32 accumulator tile per wave.  On the fp32 matrix pipe these layers ran AT its peak (148 of 157 TFLOP/s
-    // for the 3x3 at B = 64) -- the split products have 5x that ceiling
-    if (a.bf16x3 == 2) return launch_cfg<128, 32, 4, 1, 0, 2>(a, nphase, stream);
-    if (a.bf16x3 == 3) return launch_cfg<128, 32, 4, 1, 0, 3>(a, nphase, stream);   // (pieces prepared at pack time: not built at this width)
-    return launch_cfg<128, 32, 4, 1, 0, 1>(a, nphase, stream);
-  }
-  // (round 5: the three-term split-bf16 mode -- the training step's input gradients -- also takes K = 64..127: the 1x1
-  // quantiser convolutions' input gradients (K = embed_dim = 64, 192 output channels at the bottom resolution) ran on the
-  // fp32 matrix pipe, 142 us of a step)
-  if (a.bf16x3 && mode == 0 && a.Cout > 32 && (a.K >= 128 || (a.bf16x3 == 1 && a.K >= 64 && !a.in0_pair && !a.in1_pair && !a.out_pair))) {
-    // 128x64 tiles are ~20 % slower per FLOP than 128x128, but a GEMM that fills less than the chip's
-    // 3 workgroups per CU with 128x128 tiles (the prior's d x d linears at 8 k rows: 260 tiles) finishes
-    // sooner with twice as many, half as long, workgroups
-    const long tiles128 = (long)((a.M + 127) / 128) * ((a.Cout + 127) / 128) * nphase * (a.nz > 1 ? a.nz : 1);
-    const bool narrow = a.Cout <= 64 || tiles128 < 640;
-    if (a.bf16x3 == 2) {   // six-term split: fp32-grade products
-      if (narrow) return launch_cfg<128, 64, 2, 2, 0, 2>(a, nphase, stream);
-      return launch_cfg<128, 128, 2, 2, 0, 2>(a, nphase, stream);
-    }
-    if (a.bf16x3 == 3 && a.w16) {   // split-f16 with the weights' pieces prepared at pack time
-      a.w = a.w16;
-      if (a.out_pair) {
-        if (a.oc != 1 || (a.Cout & 7)) return unsupported("conv: a pair-format output is channels-last with Cout % 8 == 0");
-        if (narrow) return launch_cfg<128, 64, 2, 2, 0, 4, true>(a, nphase, stream);
-        return launch_cfg<128, 128, 2, 2, 0, 4, true>(a, nphase, stream);
-      }
-      if (narrow) return launch_cfg<128, 64, 2, 2, 0, 4>(a, nphase, stream);
-      return launch_cfg<128, 128, 2, 2, 0, 4>(a, nphase, stream);
-    }
-    if (a.bf16x3 == 3) {   // split-f16: fp32-grade products from three terms, f16 range
-      if (narrow) return launch_cfg<128, 64, 2, 2, 0, 3>(a, nphase, stream);
-      return launch_cfg<128, 128, 2, 2, 0, 3>(a, nphase, stream);
-    }
-    if (narrow) return launch_cfg<128, 64, 2, 2, 0, 1>(a, nphase, stream);
-    return launch_cfg<128, 128, 2, 2, 0, 1>(a, nphase, stream);
-  }
-#define ISI_CONV_DISPATCH(MODE)                                                        \
-  do {                                                                                  \
-    if (a.Cout <= 32) return launch_cfg<128, 32, 4, 1, MODE>(a, nphase, stream);        \
-    if (a.Cout <= 64) return launch_cfg<128, 64, 2, 2, MODE>(a, nphase, stream);        \
-    return launch_cfg<128, 128, 2, 2, MODE>(a, nphase, stream);                         \
-  } while (0)
-  if (mode == 2) ISI_CONV_DISPATCH(2);
-  if (mode == 1) ISI_CONV_DISPATCH(1);
-  ISI_CONV_DISPATCH(0);
-#undef ISI_CONV_DISPATCH
+  if (r.prec == 4) a.w = a.w16;
+#define ISI_CONV_CASE(BN, WM, WN, MODE, PREC, OUTP)                                                      \
+  if (r.bn == BN && r.mode == MODE && r.prec == PREC && r.outp == (OUTP ? 1 : 0))                        \
+    return launch_cfg<128, BN, WM, WN, MODE, PREC, OUTP>(a, nphase, stream)
+  // exact fp32: every loader at every width
+  ISI_CONV_CASE(32, 4, 1, 0, 0, false);  ISI_CONV_CASE(64, 2, 2, 0, 0, false);  ISI_CONV_CASE(128, 2, 2, 0, 0, false);
+  ISI_CONV_CASE(32, 4, 1, 1, 0, false);  ISI_CONV_CASE(64, 2, 2, 1, 0, false);  ISI_CONV_CASE(128, 2, 2, 1, 0, false);
+  ISI_CONV_CASE(32, 4, 1, 2, 0, false);  ISI_CONV_CASE(64, 2, 2, 2, 0, false);  ISI_CONV_CASE(128, 2, 2, 2, 0, false);
+  // split products: the uniform loader only
+  ISI_CONV_CASE(32, 4, 1, 0, 1, false);  ISI_CONV_CASE(64, 2, 2, 0, 1, false);  ISI_CONV_CASE(128, 2, 2, 0, 1, false);
+  ISI_CONV_CASE(32, 4, 1, 0, 2, false);  ISI_CONV_CASE(64, 2, 2, 0, 2, false);  ISI_CONV_CASE(128, 2, 2, 0, 2, false);
+  ISI_CONV_CASE(32, 4, 1, 0, 3, false);  ISI_CONV_CASE(64, 2, 2, 0, 3, false);  ISI_CONV_CASE(128, 2, 2, 0, 3, false);
+  ISI_CONV_CASE(64, 2, 2, 0, 4, false);  ISI_CONV_CASE(128, 2, 2, 0, 4, false);
+  ISI_CONV_CASE(64, 2, 2, 0, 4, true);   ISI_CONV_CASE(128, 2, 2, 0, 4, true);
+#undef ISI_CONV_CASE
+  return unsupported("conv: no kernel instance for the planned route");
 }
 
 // flags -> 0 exact fp32 | 1 bf16x3 | 2 bf16x6 | 3 f16x3 (the most precise requested mode wins)
@@ -664,14 +691,12 @@ int conv2d_f32(const isi_src *s0, const isi_src *s1, const float *packed_w, cons
                             stream, gate, twin, zero, zero_words);
 }
 
-// nz independent convolutions of one shape in a single launch (grid z): set z reads source 0 at
-// ptr + z * zs_in0, the packed weight at packed_w + z * zs_w, the residual at + z * zs_res and writes
-// at dst + z * zs_out (element strides; the views describe one set).  One source only when nz > 1.
-int conv2d_batched_f32(const isi_src *s0, const isi_src *s1, const float *packed_w, const float *bias,
+// Validation and planning of conv2d_batched_f32 (below); route_out == nullptr: launch, else report the packed route there.
+static int conv2d_plan(const isi_src *s0, const isi_src *s1, const float *packed_w, const float *bias,
                        const isi_src *res, const isi_dst *dst, int B, int H, int W, int Cout, int KH,
                        int KW, int stride, int pad, int relu, int nz, int64_t zs_in0, int64_t zs_w,
                        int64_t zs_res, int64_t zs_out, hipStream_t stream, const float *gate, float *twin, int32_t *zero,
-                       int zero_words) {
+                       int zero_words, int *route_out) {
   if (nz < 1 || nz > 65535) return invalid("conv2d: bad batch count");
   if (twin && (gate || nz > 1 || !(relu & ISI_CONV_OUT_PAIR))) return unsupported("conv2d: an fp32 twin accompanies a single pair-format output");
   if (gate && (nz > 1 || (relu & (ISI_CONV_IN0_PAIR | ISI_CONV_IN1_PAIR | ISI_CONV_OUT_PAIR))))
@@ -683,7 +708,8 @@ int conv2d_batched_f32(const isi_src *s0, const isi_src *s1, const float *packed
     return invalid("conv2d: bad shape");
   const int OH = (H + 2 * pad - KH) / stride + 1;
   const int OW = (W + 2 * pad - KW) / stride + 1;
-  if (OH <= 0 || OW <= 0) return invalid("conv2d: empty output");
+  // (the quotients above truncate towards zero: a padded map one row short of the kernel at stride 2 would give OH = 1)
+  if (OH <= 0 || OW <= 0 || H + 2 * pad < KH || W + 2 * pad < KW) return invalid("conv2d: empty output");
   if ((int64_t)B * OH * OW > INT32_MAX) return unsupported("conv2d: more than 2^31 output pixels");
   const bool two = s1 && s1->ptr;
   if (two && s1->sc != 1) return unsupported("conv2d: second source must be channels-last");
@@ -697,9 +723,10 @@ int conv2d_batched_f32(const isi_src *s0, const isi_src *s1, const float *packed
       aligned16(packed_w) && conv_first_applicable(s0, s1, res, dst, Cout, KH, KW, stride, pad, OH, OW, nz)) {
     // the 2-channel first layer has its own HBM-oriented kernel (conv_first_f32.hip), bit-identical results
     if (relu & (ISI_CONV_IN0_PAIR | ISI_CONV_IN1_PAIR)) return unsupported("conv2d: pair-format source on the 2-channel layer");
+    if (route_out) { *route_out = ISI_CONV_ROUTE_FIRST; return ISI_OK; }
     return conv_first_f32(s0, packed_w, bias, dst, B, H, W, Cout, OH, OW, e0, relu, stream, twin, gate, zero, zero_words);
   }
-  if (zero) {   // no other kernel carries the request
+  if (zero && !route_out) {   // no other kernel carries the request
     if (const int rcz = vq_zero_counts(zero, zero_words, stream)) return rcz;
   }
   // the prior's linear layers: rows of a dense matrix, three-term products -> the GEMM kernel (gemm_split_f32.hip)
@@ -707,6 +734,7 @@ int conv2d_batched_f32(const isi_src *s0, const isi_src *s1, const float *packed
       dst->sc == 1 && (!res || !res->ptr || res->sc == 1) && !(relu & (ISI_CONV_IN0_PAIR | ISI_CONV_IN1_PAIR | ISI_CONV_OUT_PAIR)) &&
       gemm_split_applicable(W, Cout, s0->C, split_mode(relu)) && aligned16(s0->ptr) && aligned16(packed_w) && s0->sw % 4 == 0 &&
       !knobs().no_gemm_kernel) {
+    if (route_out) { *route_out = ISI_CONV_ROUTE_GEMM; return ISI_OK; }
     GemmExtra gx;
     memset(&gx, 0, sizeof gx);
     gx.nz = 1; gx.gate = gate; gx.ldg = dst->sw;          // (a gate is laid out like dst)
@@ -751,12 +779,33 @@ int conv2d_batched_f32(const isi_src *s0, const isi_src *s1, const float *packed
   if (twin && !(dst->sc == 1 && dst->sw == Cout && dst->sh == (int64_t)OW * Cout && (B == 1 || dst->sn == (int64_t)OH * OW * Cout) &&
                 aligned16(twin)))
     return unsupported("conv2d: the fp32 twin needs a dense channels-last output");
-  return launch_conv(a, !vec, 1, stream);
+  return launch_conv(a, !vec, 1, stream, route_out);
 }
 
-int conv_transpose2d_k4s2_f32(const isi_src *s, const float *packed_w, const float *bias,
-                              const isi_dst *dst, int B, int H, int W, int Cout, int relu,
-                              hipStream_t stream, const float *gate, float *twin) {
+// nz independent convolutions of one shape in a single launch (grid z): set z reads source 0 at
+// ptr + z * zs_in0, the packed weight at packed_w + z * zs_w, the residual at + z * zs_res and writes
+// at dst + z * zs_out (element strides; the views describe one set).  One source only when nz > 1.
+int conv2d_batched_f32(const isi_src *s0, const isi_src *s1, const float *packed_w, const float *bias,
+                       const isi_src *res, const isi_dst *dst, int B, int H, int W, int Cout, int KH,
+                       int KW, int stride, int pad, int relu, int nz, int64_t zs_in0, int64_t zs_w,
+                       int64_t zs_res, int64_t zs_out, hipStream_t stream, const float *gate, float *twin, int32_t *zero,
+                       int zero_words) {
+  return conv2d_plan(s0, s1, packed_w, bias, res, dst, B, H, W, Cout, KH, KW, stride, pad, relu, nz, zs_in0, zs_w, zs_res, zs_out,
+                     stream, gate, twin, zero, zero_words, nullptr);
+}
+
+int conv2d_route(const isi_src *s0, const isi_src *s1, const float *packed_w, const float *bias, const isi_src *res,
+                 const isi_dst *dst, int B, int H, int W, int Cout, int KH, int KW, int stride, int pad, int relu,
+                 const float *gate) {
+  int route = 0;
+  const int rc = conv2d_plan(s0, s1, packed_w, bias, res, dst, B, H, W, Cout, KH, KW, stride, pad, relu, 1, 0, 0, 0, 0, nullptr,
+                             gate, nullptr, nullptr, 0, &route);
+  return rc ? rc : route;
+}
+
+// Validation and planning of the four-phase launch; route_out as in conv2d_plan.
+static int convT_plan(const isi_src *s, const float *packed_w, const float *bias, const isi_dst *dst, int B, int H, int W,
+                      int Cout, int relu, hipStream_t stream, const float *gate, float *twin, int *route_out) {
   if (!s || !s->ptr || !packed_w || !dst || !dst->ptr) return invalid("convT: null pointer");
   if (twin && (gate || !(relu & ISI_CONV_OUT_PAIR) || !(relu & ISI_CONV_IN0_PAIR)))
     return unsupported("convT: an fp32 twin accompanies a pair-format output of the pair kernel");
@@ -777,11 +826,13 @@ int conv_transpose2d_k4s2_f32(const isi_src *s, const float *packed_w, const flo
           !convT_small_pair_ok(Cin, Cout) || !aligned16(s->ptr) || !aligned16(packed_w))
         return unsupported("convT: pair-format input on the few-channel kernel needs ISI_CONV_F16X3 | ISI_CONV_W16, "
                            "64 dense channels-last input channels, Cout <= 2 and an fp32 output");
+      if (route_out) { *route_out = ISI_CONV_ROUTE_CONVT_SMALL_PAIR; return ISI_OK; }
       return convT_k4s2_small_pair_f16(s->ptr, packed_w, bias, dst->ptr, B, H, W, Cin, Cout, (int)dst->sn, (int)dst->sc,
                                        (int)dst->sh, (int)dst->sw, relu & ISI_CONV_RELU, stream);
     }
     if (relu & ISI_CONV_OUT_PAIR) return unsupported("convT: pair-format output on the few-channel kernel");
     // few output channels: GEMM + col2im gather kernel (weights were packed in its layout)
+    if (route_out) { *route_out = ISI_CONV_ROUTE_CONVT_SMALL; return ISI_OK; }
     return convT_k4s2_small_f32(s->ptr, packed_w, bias, dst->ptr, B, H, W, s->C, Cout, e0, (int)s->sn,
                                 (int)s->sc, (int)s->sh, (int)s->sw, (int)dst->sn, (int)dst->sc,
                                 (int)dst->sh, (int)dst->sw, relu & ISI_CONV_RELU, stream);
@@ -796,6 +847,7 @@ int conv_transpose2d_k4s2_f32(const isi_src *s, const float *packed_w, const flo
                            (B == 1 || dst->sn == (int64_t)4 * H * W * Cout);
     if ((relu & ISI_CONV_IN0_PAIR) && (relu & ISI_CONV_W16) && split_mode(relu) == 3 && dense_in && dense_out &&
         convT_pair_ok(Cin, Cout) && aligned16(s->ptr) && aligned16(dst->ptr) && aligned16(packed_w)) {
+      if (route_out) { *route_out = ISI_CONV_ROUTE_CONVT_PAIR; return ISI_OK; }
       const size_t Kpad = round_up((size_t)4 * Cin, kBK);
       return convT_pair_f16(s->ptr, packed_w + (size_t)4 * Cout * Kpad, bias, dst->ptr, B, H, W, Cin, Cout, relu & 1,
                             (relu & ISI_CONV_OUT_PAIR) ? 1 : 0, stream, nullptr, 0, twin);
@@ -825,7 +877,20 @@ int conv_transpose2d_k4s2_f32(const isi_src *s, const float *packed_w, const flo
   const bool vec = s->sc == 1 && (a.C0 % 4 == 0) && aligned16(s->ptr) && (s->sn % 4 == 0) &&
                    (s->sh % 4 == 0) && (s->sw % 4 == 0);
   if (!aligned16(packed_w)) return invalid("convT: packed weight must be 16-byte aligned");
-  return launch_conv(a, !vec, 4, stream);
+  return launch_conv(a, !vec, 4, stream, route_out);
+}
+
+int conv_transpose2d_k4s2_f32(const isi_src *s, const float *packed_w, const float *bias,
+                              const isi_dst *dst, int B, int H, int W, int Cout, int relu,
+                              hipStream_t stream, const float *gate, float *twin) {
+  return convT_plan(s, packed_w, bias, dst, B, H, W, Cout, relu, stream, gate, twin, nullptr);
+}
+
+int conv_transpose2d_k4s2_route(const isi_src *s, const float *packed_w, const float *bias, const isi_dst *dst, int B, int H,
+                                int W, int Cout, int relu, const float *gate) {
+  int route = 0;
+  const int rc = convT_plan(s, packed_w, bias, dst, B, H, W, Cout, relu, nullptr, gate, nullptr, &route);
+  return rc ? rc : route;
 }
 
 }  // namespace isi

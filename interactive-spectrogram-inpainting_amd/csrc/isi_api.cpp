@@ -240,6 +240,15 @@ int isi_conv_transpose2d_k4s2_gated_f32(const isi_src *src, const float *packed_
   if (!gate) return ISI_E_INVALID;
   return conv_transpose2d_k4s2_f32(src, packed_w, bias, dst, B, H, W, Cout, flags, S(stream), gate);
 }
+int isi_conv2d_route(const isi_src *src0, const isi_src *src1, const float *packed_w, const float *bias,
+                     const isi_src *residual, const float *gate, const isi_dst *dst, int B, int H, int W, int Cout,
+                     int KH, int KW, int stride, int pad, int flags) {
+  return conv2d_route(src0, src1, packed_w, bias, residual, dst, B, H, W, Cout, KH, KW, stride, pad, flags, gate);
+}
+int isi_conv_transpose2d_k4s2_route(const isi_src *src, const float *packed_w, const float *bias, const float *gate,
+                                    const isi_dst *dst, int B, int H, int W, int Cout, int flags) {
+  return conv_transpose2d_k4s2_route(src, packed_w, bias, dst, B, H, W, Cout, flags, gate);
+}
 
 int isi_resblock_f32(const float *in, const float *packed_w3, const float *b3, const float *packed_w1,
                      const float *b1, float *out, int B, int H, int W, int C, int R, int relu,

@@ -72,6 +72,13 @@ int conv2d_batched_f32(const isi_src *s0, const isi_src *s1, const float *packed
 int conv_transpose2d_k4s2_f32(const isi_src *s, const float *packed_w, const float *bias,
                               const isi_dst *dst, int B, int H, int W, int Cout, int relu,
                               hipStream_t stream, const float *gate = nullptr, float *twin = nullptr);
+// isi_conv2d_route / isi_conv_transpose2d_k4s2_route: the validation and planning of the two calls above (one code path),
+// nothing launched; the packed route (ISI_CONV_ROUTE_*, include/isi_hip.h) or the negative status of a refusal
+int conv2d_route(const isi_src *s0, const isi_src *s1, const float *packed_w, const float *bias, const isi_src *res,
+                 const isi_dst *dst, int B, int H, int W, int Cout, int KH, int KW, int stride, int pad, int relu,
+                 const float *gate);
+int conv_transpose2d_k4s2_route(const isi_src *s, const float *packed_w, const float *bias, const isi_dst *dst, int B, int H,
+                                int W, int Cout, int relu, const float *gate);
 
 bool resblock_fusable(int C, int R);
 bool resblock_pair_ok(int C, int R);

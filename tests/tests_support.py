@@ -2717,3 +2717,693 @@ def attention_fwd_hold(got, refs, what, yard=None, margin=ROW_OPS_MARGIN):
                                                    torch.where(keep, _attn_finite(yard.logits2[:, :, rows]), zero),
                                                    f"{what} {name}logits", margin)
     return checks
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Float64 specification, float32 yardstick, split-product models, route mirror and case table of the implicit-GEMM
+# convolutions (csrc/conv_igemm_f32.hip through isi_conv2d_f32 / isi_conv2d_gated_f32 / isi_conv_transpose2d_k4s2_f32 and
+# its gated form), in the style of the blocks above: plain torch on the CPU, no autograd and none of the project's kernels.
+# A convolution is an im2col product followed by an epilogue,
+#     v = rows W2d^T + bias + residual;  ReLU;  gate > 0 ? v : 0                                  (the epilogue's order)
+# rows [M, K] with M = B OH OW pixels (image-major) and K = KH KW Cin in the packed weight's order k = (kh KW + kw) Cin + c
+# (taps outer, channels inner; channels = cat(x, x2)), W2d [Cout, K].  ConvTranspose2d(4, 2, 1) is four such products, one
+# per output phase (py, px) = (oy % 2, ox % 2) with M = B H W: tap (ty, tx) of a phase reads the input at
+# (my - (1 - py) + ty, mx - (1 - px) + tx) and is torch's tap (3 - py - 2 ty, 3 - px - 2 tx) (csrc/pack.hip).
+# Tensors are logical [B, C, H, W] whatever their storage.  A "row" for compare_rows is one output channel: `conv_rows`.
+# tests/test_conv_igemm_host.py holds the spec to torch's float64 convolutions and their autograd and shows what the
+# comparison rejects; tests/test_conv_igemm_gpu.py holds the kernels to it on every route.
+CONV_FLAGS = {"relu": 1, "bf16x3": 2, "bf16x6": 4, "f16x3": 8, "w16": 16, "in0_pair": 32, "in1_pair": 64, "out_pair": 128,
+              "gate_pair": 512}                                      # ISI_CONV_* of include/isi_hip.h
+CONV_PREC_FLAGS = {0: 0, 1: 2, 2: 4, 3: 8, 4: 24}                    # vqvae/_ops.py _prec_flag: the `bf16x3` argument -> flag bits
+CONV_E_INVALID, CONV_E_UNSUPPORTED = -1, -4
+CONV_FAMILIES = {1: "igemm", 2: "pair-dma", 3: "conv-first", 4: "gemm", 5: "convT-small", 6: "convT-small-pair", 7: "convT-pair"}
+CONV_LOADERS = ("uniform", "dual", "gather")
+CONV_BM = 128                                                        # rows of every tile of conv_igemm_f32_kernel
+ConvRoute = collections.namedtuple("ConvRoute", "family bn loader prec outp slice_major")
+
+
+def conv_route_pack(r):
+    """The int of isi_conv2d_route / isi_conv_transpose2d_k4s2_route (include/isi_hip.h)."""
+    return r.family | (r.bn // 32) << 4 | r.loader << 8 | r.prec << 10 | r.outp << 13 | r.slice_major << 14
+
+
+def conv_route_unpack(v):
+    assert v > 0, f"status {v}, not a route"
+    return ConvRoute(v & 15, (v >> 4 & 15) * 32, v >> 8 & 3, v >> 10 & 7, v >> 13 & 1, v >> 14 & 1)
+
+
+def conv_route_name(v):
+    if v <= 0:
+        return f"refused {v}"
+    r = conv_route_unpack(v)
+    if r.family != 1:
+        return CONV_FAMILIES[r.family]
+    return (f"igemm 128x{r.bn} {CONV_LOADERS[r.loader]} prec {r.prec}{' pair-out' if r.outp else ''}"
+            f"{' slice-major' if r.slice_major else ''}")
+
+
+# A case.  op "conv" | "convT" (k 4, stride 2, pad 1, one source); B, H, W: the layer INPUT; mode: the precision asked for
+# (the `bf16x3` argument of vqvae/_ops.py: 0 exact fp32, 1 bf16x3, 2 bf16x6, 3 f16x3, 4 f16x3 with pack-time weight pieces);
+# src0 / src1 / out / res: storage of that tensor (`conv_layout`): "nhwc" dense channels-last, "nchw" dense NCHW, "off1"
+# channels-last one float off a 16-byte boundary, "row" channels-last with two floats between rows (row stride % 4 != 0),
+# "slice" a channel slice [4, 4 + C) of a channels-last tensor of C + 8 channels; gate None | "f32" | "pair" (laid out like
+# the output); pairs: which of source 0 ("0"), source 1 ("1") and the output ("o") are in the pair format; knobs: execution
+# switches ((name, value), ...) set around the launch.
+ConvCase = collections.namedtuple("ConvCase", "op c0 c1 cout k stride pad B H W mode src0 src1 out res gate bias relu pairs knobs")
+ConvLayout = collections.namedtuple("ConvLayout", "shape strides offset storage")     # logical [B, C, H, W]; floats
+
+
+def _cv(c0, cout, k, stride, pad, B, H, W, mode=0, c1=0, src0="nhwc", src1="nhwc", out="nhwc", res=None, gate=None, bias=True,
+        relu=False, pairs="", knobs=()):
+    return ConvCase("conv", c0, c1, cout, k, stride, pad, B, H, W, mode, src0, src1 if c1 else None, out, res, gate, bias, relu, pairs,
+                    tuple(knobs))
+
+
+def _ct(cin, cout, B, H, W, mode=0, src0="nhwc", out="nhwc", gate=None, bias=True, relu=False, pairs="", knobs=()):
+    return ConvCase("convT", cin, 0, cout, 4, 2, 1, B, H, W, mode, src0, None, out, None, gate, bias, relu, pairs, tuple(knobs))
+
+
+def conv_out_hw(c):
+    if c.op == "convT":
+        return 2 * c.H, 2 * c.W
+    return (c.H + 2 * c.pad - c.k) // c.stride + 1, (c.W + 2 * c.pad - c.k) // c.stride + 1
+
+
+def conv_case_id(c):
+    src = f"{c.c0}+{c.c1}" if c.c1 else f"{c.c0}"
+    lay = c.src0 + (f"+{c.src1}" if c.c1 else "")
+    extra = "".join([f"-res_{c.res}" if c.res else "", f"-gate_{c.gate}" if c.gate else "", "" if c.bias else "-nobias",
+                     "-relu" if c.relu else "", f"-pairs_{c.pairs}" if c.pairs else "",
+                     "".join(f"-{n}={v}" for n, v in c.knobs)])
+    return f"{c.op}{src}to{c.cout}k{c.k}s{c.stride}p{c.pad}-{c.B}x{c.H}x{c.W}-m{c.mode}-{lay}-to_{c.out}{extra}"
+
+
+def _conv_tensor_layout(kind, B, Cc, H, W):
+    if kind == "nhwc":
+        return ConvLayout((B, Cc, H, W), (H * W * Cc, 1, W * Cc, Cc), 0, B * H * W * Cc)
+    if kind == "nchw":
+        return ConvLayout((B, Cc, H, W), (Cc * H * W, H * W, W, 1), 0, B * Cc * H * W)
+    if kind == "off1":
+        return ConvLayout((B, Cc, H, W), (H * W * Cc, 1, W * Cc, Cc), 1, B * H * W * Cc + 4)
+    if kind == "row":
+        sh = W * Cc + 2
+        return ConvLayout((B, Cc, H, W), (H * sh, 1, sh, Cc), 0, B * H * sh)
+    assert kind == "slice", kind
+    Cw = Cc + 8
+    return ConvLayout((B, Cc, H, W), (H * W * Cw, 1, W * Cw, Cw), 4, B * H * W * Cw)
+
+
+def conv_layout(c):
+    """{"src0", "src1", "out", "res", "gate": ConvLayout or None}: where every tensor of the case lies in its storage (a flat
+    buffer whose first float is 16-byte aligned).  The gate is laid out exactly like the output, as the C-ABI requires."""
+    OH, OW = conv_out_hw(c)
+    out = _conv_tensor_layout(c.out, c.B, c.cout, OH, OW)
+    return {"src0": _conv_tensor_layout(c.src0, c.B, c.c0, c.H, c.W),
+            "src1": _conv_tensor_layout(c.src1, c.B, c.c1, c.H, c.W) if c.c1 else None,
+            "out": out, "res": _conv_tensor_layout(c.res, c.B, c.cout, OH, OW) if c.res else None,
+            "gate": out if c.gate else None}
+
+
+def conv_case_flags(c, mode=None, gate="case", pairs=None):
+    """The flag word of the case's launch (other precision / gate / pair formats: those of the variant launch)."""
+    pairs = c.pairs if pairs is None else pairs
+    gate = c.gate if gate == "case" else gate
+    f = int(c.relu) | CONV_PREC_FLAGS[c.mode if mode is None else mode]
+    f |= (32 if "0" in pairs else 0) | (64 if "1" in pairs else 0) | (128 if "o" in pairs else 0)
+    return f | (512 if gate == "pair" else 0)
+
+
+def _extent(l):
+    return sum((n - 1) * s for n, s in zip(l.shape, l.strides)) + 1
+
+
+def conv_route(c, mode=None, gate="case", pairs=None, knobs=None):
+    """Mirror of the decisions of conv2d_batched_f32 / conv_transpose2d_k4s2_f32 and of conv_route (csrc/conv_igemm_f32.hip)
+    for a case with a 16-byte aligned packed weight: the int isi_conv2d_route / isi_conv_transpose2d_k4s2_route returns -- the
+    packed route, or the negative status of a refusal.  `knobs`: {name: value} of the execution switches in force (default:
+    the case's).  The rules it spells out: only the uniform loader runs split products (a split flag on a dual-source or
+    gather launch runs exact fp32); split products need K >= 128 (bf16x3: K >= 64 where Cout > 32); there is no
+    pack-time-pieces instance at Cout <= 32 (mode 4 runs PREC 3 there)."""
+    kn = dict(c.knobs if knobs is None else knobs)
+    flags = conv_case_flags(c, mode, gate, pairs)
+    has_gate = (c.gate if gate == "case" else gate) is not None
+    lay = conv_layout(c)
+    s0, s1, dst, res = lay["src0"], lay["src1"], lay["out"], lay["res"]
+    split = 2 if flags & 4 else 3 if flags & 8 else 1 if flags & 2 else 0
+    in0p, in1p, outp, w16, gate_pair = bool(flags & 32), bool(flags & 64 and c.c1), bool(flags & 128), bool(flags & 16), bool(flags & 512)
+    al = lambda l: l.offset % 4 == 0
+    big = 1 << 30
+    OH, OW = conv_out_hw(c)
+
+    def vec_of(l, Cc):
+        return l.strides[1] == 1 and Cc % 4 == 0 and al(l) and l.strides[0] % 4 == 0 and l.strides[2] % 4 == 0 and l.strides[3] % 4 == 0
+
+    def dense_nhwc(l, Cc, h, w):
+        return (l.strides[1] == 1 and (w == 1 or l.strides[3] == Cc) and (h == 1 or l.strides[2] == w * Cc)
+                and (c.B == 1 or l.strides[0] == h * w * Cc))
+
+    if c.op == "convT":
+        Cin, small = c.c0, 1 <= c.cout <= 4 and c.c0 in (32, 64)
+        if has_gate and (small or flags & (32 | 128)):
+            return CONV_E_UNSUPPORTED
+        if _extent(s0) >= big or _extent(dst) >= big:
+            return CONV_E_UNSUPPORTED
+        d_in = dense_nhwc(s0, Cin, c.H, c.W)
+        if small:
+            if flags & 32:
+                ok = not outp and w16 and split == 3 and d_in and Cin == 64 and c.cout <= 2 and al(s0)
+                return 6 if ok else CONV_E_UNSUPPORTED
+            return CONV_E_UNSUPPORTED if outp else 5
+        d_out = (dst.strides[1] == 1 and dst.strides[3] == c.cout and dst.strides[2] == 2 * c.W * c.cout
+                 and (c.B == 1 or dst.strides[0] == 4 * c.H * c.W * c.cout))
+        pair_ok = not kn.get("ISI_NO_CONVT_PAIR_KERNEL") and Cin >= 16 and Cin % 16 == 0 and c.cout % 64 == 0 and c.cout <= 1024
+        if flags & 32 and w16 and split == 3 and d_in and d_out and pair_ok and al(s0) and al(dst):
+            return 7
+        K, KH, KW, nphase, convT, two, C0, uniform = 4 * Cin, 2, 2, 4, True, False, Cin, True
+        scalar, M, in1p, has_res = not vec_of(s0, Cin), c.B * c.H * c.W, False, False
+    else:
+        if has_gate and flags & (32 | 64 | 128):
+            return CONV_E_UNSUPPORTED
+        if OH <= 0 or OW <= 0:
+            return CONV_E_INVALID
+        two = c.c1 > 0
+        if two and s1.strides[1] != 1:
+            return CONV_E_UNSUPPORTED
+        if max(_extent(s0), _extent(s1) if two else 1, _extent(dst), _extent(res) if res else 1) >= big:
+            return CONV_E_UNSUPPORTED
+        d_out = (dst.strides[1] == 1 and dst.strides[3] == c.cout and dst.strides[2] == OW * c.cout
+                 and dst.strides[0] == OH * OW * c.cout and al(dst))
+        if ((not has_gate or (not flags & (128 | 512))) and not kn.get("ISI_NO_CONV_FIRST") and not two and not res
+                and (c.c0, c.k, c.stride, c.pad) == (2, 4, 2, 1) and c.cout in (32, 64) and d_out):
+            return CONV_E_UNSUPPORTED if flags & (32 | 64) else 3
+        if (not (has_gate and gate_pair) and not two and (c.k, c.stride, c.pad, c.B, c.H) == (1, 1, 0, 1, 1) and s0.strides[1] == 1
+                and dst.strides[1] == 1 and (not res or res.strides[1] == 1) and not flags & (32 | 64 | 128)
+                and split in (1, 3) and c.c0 % 32 == 0 and c.c0 >= 128 and c.cout > 32 and c.W >= 256
+                and al(s0) and s0.strides[3] % 4 == 0 and not kn.get("ISI_NO_GEMM_KERNEL")):
+            return 4
+        if res and (in0p or in1p or outp):
+            return CONV_E_UNSUPPORTED
+        K, KH, KW, nphase, convT, C0 = c.k * c.k * (c.c0 + c.c1), c.k, c.k, 1, False, c.c0
+        uniform = not two or (c.c0 % 32 == 0 and c.c1 % 32 == 0)
+        scalar = not (vec_of(s0, c.c0) and c.c1 % 4 == 0 and (not two or vec_of(s1, c.c1)))
+        M, has_res = c.B * OH * OW, bool(res)
+    # ---- conv_route of csrc/conv_igemm_f32.hip
+    Cin, cout = c.c0 + c.c1, c.cout
+    loader = 2 if scalar else 0 if uniform else 1
+    slice_major = int(loader == 0 and KH * KW > 1 and C0 % 32 == 0 and Cin % 32 == 0)
+    dma_shape = bool(kn.get("ISI_CONV_PAIR_ALL")) or (not convT and K >= 256)
+    dma_kernel = (not kn.get("ISI_NO_CONV_PAIR_KERNEL") and C0 > 0 and C0 % 32 == 0 and (Cin - C0) % 32 == 0 and cout % 64 == 0
+                  and 1 <= KH * KW <= 16)
+    if (dma_shape and split == 3 and w16 and loader == 0 and in0p and (not two or in1p) and not has_res and dst.strides[1] == 1
+            and dma_kernel and KH <= 4 and KW <= 4 and M < 1 << 24):
+        return 2
+    if (in0p or in1p or outp) and not (split == 3 and w16 and loader == 0 and cout > 32 and K >= 128):
+        return CONV_E_UNSUPPORTED
+    if split and loader == 0 and cout <= 32 and K >= 128 and not (outp or in0p or in1p):
+        return conv_route_pack(ConvRoute(1, 32, 0, split, 0, slice_major))
+    if split and loader == 0 and cout > 32 and (K >= 128 or (split == 1 and K >= 64 and not (in0p or in1p or outp))):
+        tiles128 = -(-M // 128) * -(-cout // 128) * nphase
+        bn = 64 if cout <= 64 or tiles128 < 640 else 128
+        prec = 4 if split == 3 and w16 else split
+        if prec == 4 and outp and (dst.strides[1] != 1 or cout % 8):
+            return CONV_E_UNSUPPORTED
+        return conv_route_pack(ConvRoute(1, bn, 0, prec, int(prec == 4 and outp), slice_major))
+    return conv_route_pack(ConvRoute(1, 32 if cout <= 32 else 64 if cout <= 64 else 128, loader, 0, 0, slice_major))
+
+
+# ---- the specification
+def _conv_cat(x, x2, dtype, pair0=False, pair1=False, swap_sources=False):
+    """cat(x, x2) [B, Cin, H, W] in `dtype`; a pair-format source holds pair_decode_host(pair_encode_host(x)) (groups of 8
+    channels of channels-last storage)."""
+    def one(t, pair):
+        t = torch.as_tensor(t).detach().cpu()
+        if pair:
+            t = pair_decode_host(pair_encode_host(t.float().permute(0, 2, 3, 1).contiguous())).permute(0, 3, 1, 2)
+        return t.to(dtype)
+    x = one(x, pair0)
+    if x2 is None:
+        return x
+    x2 = one(x2, pair1)
+    return torch.cat([x2, x] if swap_sources else [x, x2], dim=1)
+
+
+def _conv_gemms(xc, w, k, stride, pad, transposed, pad_shift=False):
+    """The products of a convolution: [(rows [B, L, K], W2d [Cout, K], phase (py, px) or None)] in the dtype of xc, K in the
+    packed order.  `pad_shift` is a host-test mutant: the left padding one more, the right one less."""
+    B, Cin = xc.shape[:2]
+    w = torch.as_tensor(w).detach().cpu().to(xc.dtype)
+
+    def rows_of(src, kk, **kw):
+        cols = torch.nn.functional.unfold(src, kk, **kw)                             # [B, Cin kk kk, L], channel-major
+        return cols.reshape(B, Cin, kk * kk, -1).permute(0, 3, 2, 1).reshape(B, cols.shape[-1], kk * kk * Cin)
+    if not transposed:
+        if pad_shift:
+            assert pad >= 1
+            rows = rows_of(torch.nn.functional.pad(xc, (pad + 1, pad - 1, pad, pad)), k, stride=stride)
+        else:
+            rows = rows_of(xc, k, padding=pad, stride=stride)
+        return [(rows, w.permute(0, 2, 3, 1).reshape(w.shape[0], -1), None)]
+    assert (k, stride, pad) == (4, 2, 1)
+    out = []
+    for py in range(2):
+        for px in range(2):
+            xp = torch.nn.functional.pad(xc, (1 - px, px, 1 - py, py))
+            wp = w[:, :, [3 - py, 1 - py]][:, :, :, [3 - px, 1 - px]]                # [Cin, Cout, ty, tx]
+            out.append((rows_of(xp, 2), wp.permute(1, 2, 3, 0).reshape(w.shape[1], -1), (py, px)))
+    return out
+
+
+def _conv_eval(op_dtype, acc_dtype, x, x2, w, bias, k, stride, pad, transposed=False, res=None, relu=False, gate=None,
+               gate_pair=False, pair0=False, pair1=False, prod=None, drop_last_chunk=False, pad_shift=False, border_tap=False,
+               swap_sources=False, seam_tile=0, bias_tile=0, res_after_relu=False, gate_ge=False, gate_wrong_half=False,
+               swap_phases=False):
+    """[B, Cout, OH, OW] in acc_dtype: operands built in op_dtype, every product by `prod(rows2d, W2d)` (default: the matmul
+    in op_dtype), the epilogue in acc_dtype.  The switches from `drop_last_chunk` on are the host tests' mutants."""
+    xc = _conv_cat(x, x2, op_dtype, pair0, pair1, swap_sources)
+    B, _, H, W = xc.shape
+    OH, OW = (2 * H, 2 * W) if transposed else ((H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1)
+    out = None
+    for rows, W2d, phase in _conv_gemms(xc, w, k, stride, pad, transposed, pad_shift):
+        L, K = rows.shape[1:]
+        if border_tap:                                   # the pixels of the last output column lose their tap (0, kw) on column W - 1
+            assert not transposed
+            kw = W - 1 - ((OW - 1) * stride - pad)
+            assert 0 <= kw < k
+            rows = rows.clone()
+            Cin = K // (k * k)
+            rows[:, OW - 1::OW, kw * Cin:(kw + 1) * Cin] = 0
+        r2 = rows.reshape(B * L, K)
+        if seam_tile:                                    # every row of a tile reads the image of the tile's first row
+            m = torch.arange(B * L)
+            r2 = r2[(m // seam_tile * seam_tile) // L * L + m % L]
+        if drop_last_chunk:
+            r2, W2d = r2[:, :K // 32 * 32], W2d[:, :K // 32 * 32]
+        p = (r2 @ W2d.t() if prod is None else prod(r2, W2d)).to(acc_dtype)
+        if phase is None:
+            out = p.reshape(B, OH, OW, -1)
+        else:
+            if out is None:
+                out = torch.zeros(B, OH, OW, p.shape[-1], dtype=acc_dtype)
+            py, px = (phase[1], phase[0]) if swap_phases else phase
+            out[:, py::2, px::2] = p.reshape(B, H, W, -1)
+    cout = out.shape[-1]
+    nhwc = lambda t: torch.as_tensor(t).detach().cpu().to(acc_dtype).permute(0, 2, 3, 1)
+    if bias is not None:
+        b = torch.as_tensor(bias).detach().cpu().to(acc_dtype).clone()
+        if bias_tile:
+            b[(cout - 1) // bias_tile * bias_tile:] = 0
+        out = out + b
+    if res is not None and not res_after_relu:
+        out = out + nhwc(res)
+    if relu:
+        out = torch.where(out < 0, torch.zeros_like(out), out)          # (NaN stays NaN, as the kernel keeps it)
+    if res is not None and res_after_relu:
+        out = out + nhwc(res)
+    if gate is not None:
+        out = torch.where(conv_gate_mask(gate, gate_pair, gate_ge, gate_wrong_half).permute(0, 2, 3, 1), out, torch.zeros_like(out))
+    return out.permute(0, 3, 1, 2)
+
+
+def conv_gate_mask(gate, gate_pair=False, gate_ge=False, gate_wrong_half=False):
+    """[B, Cout, OH, OW] bool: where the gated epilogue lets a value through.  fp32 gate: gate > 0.  Pair-format gate: the
+    activation its pairs decode to, > 0 -- a value so small that its hi piece f16(4 x) rounds to zero decodes to zero and is
+    closed.  Mutants: `gate_ge` (>=), `gate_wrong_half` (an odd channel reads the half-word of the even channel below it)."""
+    g = torch.as_tensor(gate).detach().cpu().float()
+    if gate_pair:
+        g = pair_decode_host(pair_encode_host(g.permute(0, 2, 3, 1).contiguous())).permute(0, 3, 1, 2)
+    m = g >= 0 if gate_ge else g > 0
+    if gate_wrong_half:
+        m = m.clone()
+        m[:, 1::2] = m[:, 0::2][:, :m[:, 1::2].shape[1]]
+    return m
+
+
+def conv_spec(x, x2, w, bias, k, stride, pad, transposed=False, res=None, relu=False, gate=None, gate_pair=False, pair0=False,
+              pair1=False):
+    """Float64 closed form of isi_conv2d_f32 on cat(x, x2) (w [Cout, Cin, k, k]) and, `transposed`, of
+    isi_conv_transpose2d_k4s2_f32 (w [Cin, Cout, 4, 4]): bias, the residual added before the ReLU, the ReLU, the gate last.
+    A pair-format output holds the pair encoding of the float32 result: the spec is the same value (the comparison decodes)."""
+    return _conv_eval(torch.float64, torch.float64, x, x2, w, bias, k, stride, pad, transposed, res, relu, gate, gate_pair, pair0, pair1)
+
+
+def conv_f32(x, x2, w, bias, k, stride, pad, transposed=False, res=None, relu=False, gate=None, gate_pair=False, pair0=False,
+             pair1=False, out_pair=False, **mutants):
+    """The same in float32 torch: the yardstick of the exact-fp32 instances, half of the split instances', and what the host
+    tests apply their mutants to.  `out_pair`: rounded to what the pair format holds of it."""
+    v = _conv_eval(torch.float32, torch.float32, x, x2, w, bias, k, stride, pad, transposed, res, relu, gate, gate_pair, pair0, pair1,
+                   **mutants)
+    return pair_round_f16(v) if out_pair else v
+
+
+def conv_six_term_product(rows, W2d, drop_mid=False):
+    """Float64 value of the six terms PREC 2 keeps (conv_igemm_f32_kernel: "lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi"
+    of the three-piece bf16 split of both operands).  `drop_mid`: the three terms without a mid piece -- not the terms of any
+    mode (the three-term mode splits in TWO pieces), a host-test mutant."""
+    (ah, am, al), (bh, bm, bl) = bf16_pieces(rows, 3), bf16_pieces(W2d, 3)
+    s = ah @ bh.t() + ah @ bl.t() + al @ bh.t()
+    return s if drop_mid else s + ah @ bm.t() + am @ bh.t() + am @ bm.t()
+
+
+def conv_split_model(x, x2, w, bias, k, stride, pad, transposed=False, res=None, relu=False, gate=None, gate_pair=False,
+                     pair0=False, pair1=False, mode=1, drop=None):
+    """Float64 evaluation of the terms a split mode keeps of every product, on the float32 im2col rows and weights: modes 1
+    and 3 / 4 by `linear_split_model` ("bf16" / "f16": lo.hi + hi.lo + hi.hi), mode 2 by `conv_six_term_product`; the epilogue
+    in float64.  Its distance from conv_spec is the truncation the mode accepts by design.  `drop`: linear_split_model's
+    mutant switch (a two-term product)."""
+    if mode == 2:
+        prod = conv_six_term_product
+    else:
+        prod = lambda r, W2d: linear_split_model(r, W2d, {1: "bf16", 3: "f16", 4: "f16"}[mode], drop)
+    return _conv_eval(torch.float32, torch.float64, x, x2, w, bias, k, stride, pad, transposed, res, relu, gate, gate_pair, pair0,
+                      pair1, prod=prod)
+
+
+def conv_yardstick(prec, spec, f32, model=None):
+    """The yardstick of an instance's product mode (PREC of the route, not the mode asked for: a downgraded launch is held
+    to what it runs), after conv_wgrad_yardstick: 0 the float32 evaluation; 1, 3 and 4 per element the worse of the float32
+    evaluation and the three-term model; 2 the six-term model."""
+    if prec == 0:
+        return f32
+    if prec == 2:
+        return model
+    assert prec in (1, 3, 4), prec
+    return larger_error(f32, model, spec)
+
+
+def conv_rows(t):
+    """[B, Cout, OH, OW] -> [Cout, B OH OW]: a row for compare_rows is one output channel."""
+    t = torch.as_tensor(t).detach().cpu()
+    return t.permute(1, 0, 2, 3).reshape(t.shape[1], -1)
+
+
+CONV_GATE_TINY = (2.0 ** -26, 2.0 ** -27, 2.0 ** -30, 1e-12)     # 4 x 2^-26 = the smallest f16: open; the others' hi piece is 0
+
+
+def conv_case_data(c):
+    """{"x", "x2", "w", "bias", "res", "gate"} float32 on the CPU, logical [B, C, H, W], seeded from the case's shape: source 0
+    randn (an output gradient), source 1 rectified randn (an activation), w = randn / sqrt(K), and a gate of rectified randn
+    -- about half zeros -- with -0.0, negatives and CONV_GATE_TINY sprinkled over it, all four at the head and the tail."""
+    import zlib
+    g = torch.Generator().manual_seed(zlib.crc32(repr(c[:10]).encode()))
+    OH, OW = conv_out_hw(c)
+    Cin = c.c0 + c.c1
+    d = {"x": torch.randn(c.B, c.c0, c.H, c.W, generator=g),
+         "x2": torch.relu(torch.randn(c.B, c.c1, c.H, c.W, generator=g)) if c.c1 else None}
+    wshape = (c.c0, c.cout, 4, 4) if c.op == "convT" else (c.cout, Cin, c.k, c.k)
+    d["w"] = torch.randn(*wshape, generator=g) / math.sqrt((4 if c.op == "convT" else c.k * c.k) * Cin)
+    d["bias"] = torch.randn(c.cout, generator=g) if c.bias else None
+    d["res"] = torch.randn(c.B, c.cout, OH, OW, generator=g) if c.res else None
+    d["gate"] = None
+    if c.gate:
+        y = torch.relu(torch.randn(c.B, OH, OW, c.cout, generator=g)).reshape(-1)
+        special = torch.tensor([-0.0, -1.5, *CONV_GATE_TINY, 0.75])
+        n = y.numel()
+        where = torch.cat([torch.arange(min(n, 7)), torch.arange(7, max(n, 7), 11), torch.arange(max(n - 7, 0), n)])
+        y[where] = special[where % 7]
+        d["gate"] = y.reshape(c.B, OH, OW, c.cout).permute(0, 3, 1, 2)
+    return d
+
+
+ConvRefs = collections.namedtuple("ConvRefs", "spec f32 models")
+_conv_refs_cache = {}
+
+
+def conv_case_args(c, d, gate="case"):
+    """Positional and keyword arguments of conv_spec / conv_f32 / conv_split_model for a case's launch (gate=None: the plain
+    launch of a gated case)."""
+    gate_kind = c.gate if gate == "case" else gate
+    return ((d["x"], d["x2"], d["w"], d["bias"], c.k, c.stride, c.pad),
+            dict(transposed=c.op == "convT", res=d["res"], relu=c.relu, gate=d["gate"] if gate_kind else None,
+                 gate_pair=gate_kind == "pair", pair0="0" in c.pairs, pair1="1" in c.pairs))
+
+
+def conv_case_refs(c, modes=None):
+    """(spec, float32 evaluation, {mode: model}) of a case, each computed once per process and left unchanged.  `modes`: the
+    split modes whose model is wanted (default: the PREC the case's route runs)."""
+    key = c._replace(mode=0, knobs=())
+    if key not in _conv_refs_cache:
+        a, kw = conv_case_args(c, conv_case_data(c))
+        _conv_refs_cache[key] = ConvRefs(conv_spec(*a, **kw), conv_f32(*a, out_pair="o" in c.pairs, **kw), {})
+    refs = _conv_refs_cache[key]
+    if modes is None:
+        r = conv_route(c)
+        modes = [conv_route_unpack(r).prec] if r > 0 and r & 15 == 1 else []
+    for m in modes:
+        m = 3 if m == 4 else m                             # (the pack-time pieces are the same pieces)
+        if m and m not in refs.models:
+            a, kw = conv_case_args(c, conv_case_data(c))
+            refs.models[m] = conv_split_model(*a, mode=m, **kw)
+    return refs
+
+
+def conv_refs_yardstick(refs, prec):
+    return conv_yardstick(prec, refs.spec, refs.f32, refs.models.get(3 if prec == 4 else prec))
+
+
+# ---- the case table.  Shapes are the smallest that still reach what the comment names; M = B OH OW.
+CONV_BIG_CASES = [
+    # the narrow / wide switch at tiles128 = 640: four phases x 160 row tiles (M = 20447, odd map; Cin = 32: K = 128, Cout = 96:
+    # ragged weight rows in the 128-wide tile) = 640 -> wide; 1x1 128 -> 264 (three column tiles) x 213 row tiles = 639 -> narrow
+    # (the wide instances of modes 2 .. 4 and the wide pair-format output need 640 tiles too: the same data and spec again)
+    *[_ct(32, 96, 1, 127, 161, mode=m) for m in (1, 2, 3, 4)], _ct(32, 96, 1, 127, 161, mode=4, pairs="o"),
+    _cv(128, 264, 1, 1, 0, 1, 142, 192, mode=1),
+    # the epilogues of the wide split instance (two column tiles per wave; production: the 128 -> 128 input gradients at a
+    # large batch): 214 row tiles x three column tiles = 642, and the four phases once more with a gate
+    _cv(128, 264, 1, 1, 0, 1, 143, 191, mode=1, res="nchw", gate="f32", bias=False),
+    _cv(128, 264, 1, 1, 0, 1, 143, 191, mode=1, res="nhwc", gate="pair", relu=True),
+    _ct(32, 96, 1, 127, 161, mode=1, gate="pair", bias=False),
+]
+
+
+def _conv_table():
+    t = []
+    # -- loaders x tile widths, exact fp32 (and the Cout edges 1, 33, 40, 72, 130: unused columns / weight rows of the last tile)
+    t += [_cv(4, 1, 3, 1, 1, 1, 5, 7),                                  # uniform 128x32, K = 36: zero-padded tail, tap-major
+          _cv(8, 33, 3, 1, 1, 1, 5, 7), _cv(16, 40, 3, 1, 1, 2, 5, 7), _cv(32, 72, 3, 1, 1, 1, 5, 7), _cv(4, 130, 3, 1, 1, 1, 5, 7),
+          _cv(48, 16, 3, 1, 1, 1, 5, 7),                                # a chunk straddles taps: C = 48, tap-major
+          _cv(64, 40, 3, 1, 1, 1, 5, 7), _cv(32, 72, 3, 1, 1, 1, 5, 7, c1=64), _cv(64, 24, 4, 2, 1, 1, 9, 21)]   # slice-major
+    # dual-source loader (channel counts not both multiples of 32) at the three widths
+    t += [_cv(4, 8, 3, 1, 1, 1, 5, 7, c1=12), _cv(36, 40, 3, 1, 1, 1, 5, 7, c1=28), _cv(4, 72, 1, 1, 0, 2, 5, 7, c1=12),
+          _cv(36, 130, 3, 1, 1, 1, 5, 7, c1=28, relu=True)]
+    # scalar gather, each cause at some width: NCHW storage, C = 3 and 6, a pointer off by one float, a row stride % 4 != 0
+    t += [_cv(8, 8, 3, 1, 1, 2, 5, 7, src0="nchw"), _cv(3, 40, 3, 1, 1, 1, 5, 7), _cv(6, 72, 3, 1, 1, 1, 5, 7),
+          _cv(8, 33, 3, 1, 1, 1, 5, 7, src0="off1"), _cv(8, 130, 1, 1, 0, 1, 5, 7, src0="row"),
+          _cv(8, 16, 3, 1, 1, 1, 5, 7, c1=8, src1="row"), _cv(64, 72, 3, 1, 1, 1, 5, 7, src0="nchw", mode=1)]
+    # -- K edges, 1x1: K = 100 and 124 (tail), K = 64 and 96 (mode 1 takes them, mode 3 must not)
+    t += [_cv(100, 40, 1, 1, 0, 1, 5, 7, mode=m) for m in (0, 1)] + [_cv(124, 72, 1, 1, 0, 1, 5, 7, mode=1)]
+    t += [_cv(64, 192, 1, 1, 0, 2, 5, 7, mode=1), _cv(96, 40, 1, 1, 0, 1, 5, 7, mode=1), _cv(96, 40, 1, 1, 0, 1, 5, 7, mode=3),
+          _cv(64, 16, 1, 1, 0, 1, 5, 7, mode=1)]
+    # -- M edges (1x1 on 128 channels, mode 1 and exact): M = 1, 127, 128, 129; 7, 8 and 9 row tiles (the XCD remap's quotient
+    # and remainder); a batch seam inside a tile (B = 3 x 50 pixels)
+    for m in (0, 1):
+        t += [_cv(128, 40, 1, 1, 0, 1, h, w, mode=m) for h, w in ((1, 1), (1, 127), (8, 16), (3, 43))]
+        t += [_cv(32, 40, 3, 1, 1, 1, h, w, mode=m) for h, w in ((29, 29), (31, 33), (31, 37))]
+        t += [_cv(32, 40, 3, 1, 1, 3, 5, 10, mode=m)]
+    # -- geometry: pad 0, 1, 2 (pad 2: the input gradient of a 3x3 with padding 0); a map smaller than the kernel; stride 2 on odd maps
+    t += [_cv(32, 40, 3, 1, p, 2, 5, 7, mode=m) for p in (0, 2) for m in (0, 1)]
+    t += [_cv(32, 40, 3, 1, 1, 1, 1, 1, mode=1), _cv(32, 40, 4, 2, 1, 1, 2, 2, mode=1), _cv(32, 40, 4, 2, 1, 2, 9, 21, mode=1),
+          _cv(8, 8, 4, 2, 1, 2, 9, 21)]
+    # -- the split routes.  128x32: Cout <= 32, K >= 128, modes 1, 2, 3 (and 4: PREC 3, pieces unused)
+    t += [_cv(32, 32, 3, 1, 1, 2, 5, 7, mode=m) for m in (1, 2, 3, 4)] + [_cv(128, 8, 1, 1, 0, 2, 5, 7, mode=1)]
+    # Cout > 32 narrow in modes 1 .. 4 (wide: CONV_BIG_CASES for mode 1, below for 2 .. 4 through the four phases)
+    t += [_cv(32, 72, 3, 1, 1, 2, 5, 7, mode=m) for m in (1, 2, 3, 4)] + [_cv(64, 64, 3, 1, 1, 2, 5, 7, mode=m, c1=32) for m in (1, 4)]
+    # -- epilogues x tile widths x modes 0 and 1: no bias, ReLU, residual (NHWC and NCHW-strided), gates of both formats,
+    # gate + residual (the input gradient of a residual block's 3x3)
+    for m in (0, 1):
+        for cout in (32, 64, 72):
+            t += [_cv(32, cout, 3, 1, 1, 2, 5, 7, mode=m, bias=False, relu=True), _cv(32, cout, 3, 1, 1, 2, 5, 7, mode=m, res="nhwc", relu=True),
+                  _cv(32, cout, 3, 1, 1, 2, 5, 7, mode=m, res="nchw", gate="f32", bias=False),
+                  _cv(32, cout, 3, 1, 1, 2, 5, 7, mode=m, gate="pair", res="nhwc", bias=False)]
+    t += [_cv(32, 130, 3, 1, 1, 2, 5, 7, mode=1, gate="f32"), _cv(8, 8, 3, 1, 1, 2, 5, 7, src0="nchw", gate="pair", res="nhwc")]
+    # -- output layouts: NCHW through a direct call, a channel slice of a wider tensor (the gate laid out like it)
+    t += [_cv(32, 40, 3, 1, 1, 2, 5, 7, mode=m, out="nchw") for m in (0, 1)]
+    t += [_cv(32, 72, 3, 1, 1, 2, 5, 7, mode=1, out="slice", gate="f32"), _cv(32, 16, 3, 1, 1, 2, 5, 7, out="slice", res="nhwc"),
+          _cv(32, 40, 3, 1, 1, 2, 5, 7, mode=1, src0="slice")]
+    # -- mode 4 with pair formats, on shapes the LDS-DMA kernel does not take (128 <= K < 256 or Cout % 64 != 0) ...
+    t += [_cv(128, 72, 1, 1, 0, 2, 5, 7, mode=4, pairs="0"), _cv(32, 64, 1, 1, 0, 2, 5, 7, mode=4, c1=96, pairs="1"),
+          _cv(32, 72, 3, 1, 1, 2, 5, 7, mode=4, c1=32, pairs="01"), _cv(32, 72, 3, 1, 1, 2, 5, 7, mode=4, pairs="o", relu=True),
+          _cv(128, 128, 1, 1, 0, 2, 5, 7, mode=4, pairs="0o")]
+    # ... and on a shape it takes, with the kernel switched off; the same shape with it on is a hand-off
+    t += [_cv(32, 64, 3, 1, 1, 2, 5, 7, mode=4, pairs="0o", knobs=(("ISI_NO_CONV_PAIR_KERNEL", 1),)),
+          _cv(32, 64, 3, 1, 1, 2, 5, 7, mode=4, pairs="0o")]
+    # -- silent downgrades: a split flag on a dual-source or gather launch runs exact fp32
+    t += [_cv(36, 40, 3, 1, 1, 1, 5, 7, c1=28, mode=m) for m in (1, 2, 4)] + [_cv(6, 72, 3, 1, 1, 1, 5, 7, mode=m) for m in (1, 3)]
+    # -- the four-phase launch: Cin 16 (K = 64: mode 1's route), 32, 48; Cout 5 (just beyond the few-channel kernel), 64, 96;
+    # modes 0 .. 4; odd H and W; H = W = 1; NCHW output; gates of both formats; a pair-format source with the fused kernel off
+    t += [_ct(16, 64, 2, 3, 5, mode=m) for m in (0, 1, 3)] + [_ct(32, 5, 2, 3, 5, mode=m) for m in (0, 1)]
+    t += [_ct(32, 96, 2, 3, 5, mode=m) for m in (0, 1, 2, 3, 4)] + [_ct(48, 64, 1, 1, 1, mode=m) for m in (0, 1)]
+    t += [_ct(32, 96, 1, 9, 21, mode=m, out="nchw", relu=True) for m in (0, 1)]
+    t += [_ct(32, 64, 2, 3, 5, mode=1, gate="f32", bias=False), _ct(32, 64, 2, 3, 5, mode=0, gate="pair", bias=False),
+          _ct(48, 96, 2, 3, 5, mode=1, gate="pair", bias=False), _ct(6, 8, 2, 3, 5, gate="f32"), _ct(8, 72, 1, 3, 5, src0="nchw")]
+    t += [_ct(32, 64, 2, 3, 5, mode=4, pairs="0", knobs=(("ISI_NO_CONVT_PAIR_KERNEL", 1),)), _ct(32, 64, 2, 3, 5, mode=4, pairs="0"),
+          _ct(32, 72, 2, 3, 5, mode=4, pairs="0o")]
+    seen, out = set(), []
+    for c in t:
+        if c not in seen:
+            seen.add(c)
+            out.append(c)
+    return out
+
+
+CONV_IGEMM_CASES = _conv_table() + CONV_BIG_CASES
+
+
+def _conv_features(c):
+    r = conv_route(c)
+    f = set()
+    if r <= 0:
+        return {f"refused {r}"}
+    R = conv_route_unpack(r)
+    if R.family != 1:
+        f.add(f"hand-off {CONV_FAMILIES[R.family]}")
+        return f
+    OH, OW = conv_out_hw(c)
+    conv = c.op == "conv"
+    M = c.B * (OH * OW if conv else c.H * c.W)
+    Cin = c.c0 + c.c1
+    K = (c.k * c.k if conv else 4) * Cin
+    tiles = -(-M // CONV_BM)
+    width = 32 if c.cout <= 32 else 64 if c.cout <= 64 else 128
+    op = "conv" if conv else "four-phase"
+    f |= {f"inst 128x{R.bn} {CONV_LOADERS[R.loader]} prec {R.prec} outp {R.outp}", f"{CONV_LOADERS[R.loader]} at Cout width {width}",
+          f"{op}: prec {R.prec}", f"{op}: asked mode {c.mode}", f"M {M}", f"row tiles % 8 = {tiles % 8}" if tiles >= 7 else "few tiles",
+          f"Cout {c.cout}", f"K {K} prec {R.prec}", f"{op}: out {c.out}"}
+    if R.loader == 2:
+        f |= {f"gather: {c.src0}" if c.src0 != "nhwc" else (f"gather: src1 {c.src1}" if c.c1 and c.src1 != "nhwc" else f"gather: C {c.c0}")}
+    if R.prec and R.bn == 32:
+        f.add(f"split 128x32 mode {c.mode}")
+    if R.prec and R.bn > 32:
+        t128 = tiles * -(-c.cout // 128) * (1 if conv else 4)
+        f.add(f"split {'narrow' if R.bn == 64 else 'wide'} mode {c.mode}")
+        if c.cout > 64:
+            f.add(f"{op}: tiles128 {t128}")
+    if c.mode and not R.prec:
+        f.add(f"downgrade {CONV_LOADERS[R.loader]} mode {c.mode}" if R.loader else f"downgrade K {K} mode {c.mode}")
+    if c.mode == 4 and R.prec == 3:
+        f.add("mode 4 at Cout <= 32 runs prec 3")
+    if K % 32:
+        f.add(f"K tail {K}")
+    if conv and R.loader == 0 and not R.slice_major and c.k > 1 and Cin % 32 and Cin > 32:
+        f.add("chunk straddles taps")
+    if R.slice_major:
+        f.add(f"slice-major {'two sources' if c.c1 else 'k4 s2' if c.stride == 2 else 'one source'}" if conv else "slice-major four-phase")
+    if conv:
+        f.add(f"pad {c.pad}")
+        if c.H < c.k and c.W < c.k:
+            f.add(f"map smaller than the kernel k{c.k}")
+        if c.stride == 2 and c.H % 2 and c.W % 2:
+            f.add("stride 2 on an odd map")
+        if c.B > 1 and (OH * OW) % CONV_BM:
+            f.add("batch seam inside a tile")
+        if c.src0 == "slice":
+            f.add("source is a channel slice")
+    else:
+        f.add(f"four-phase: Cin {c.c0}")
+        f.add(f"four-phase: Cout {c.cout}")
+        if c.H % 2 and c.W % 2 and c.H > 1:
+            f.add("four-phase: odd H and W")
+        if c.H == 1 and c.W == 1:
+            f.add("four-phase: H = W = 1")
+    for p in c.pairs:
+        f.add(f"{op}: pair {'output' if p == 'o' else 'source ' + p}")
+    if c.pairs and c.knobs:
+        f.add(f"{op}: pairs with {c.knobs[0][0]}")
+    if "0" in c.pairs and "1" in c.pairs:
+        f.add("conv: pair both sources")
+    ep = f"{op} tile {R.bn} prec {min(R.prec, 1)}"          # (the tile the route runs, not the Cout class: 128 wide split = 640 tiles)
+    if not c.bias:
+        f.add(f"no bias: {ep}")
+    if c.relu:
+        f.add(f"relu: {ep}")
+    if c.res:
+        f.add(f"res {c.res}: {ep}")
+    if c.gate:
+        f.add(f"gate {c.gate}: {ep}")
+        if c.res:
+            f.add(f"gate + residual: {ep}")
+        if c.out == "slice":
+            f.add("gate on a sliced output")
+    return f
+
+
+def conv_igemm_requirements():
+    """What CONV_IGEMM_CASES must reach (tests/test_conv_igemm_host.py asserts that nothing is missing)."""
+    req = [f"inst 128x{bn} {ld} prec 0 outp 0" for bn in (32, 64, 128) for ld in CONV_LOADERS]
+    req += [f"inst 128x{bn} uniform prec {p} outp 0" for bn in (32, 64, 128) for p in (1, 2, 3)]
+    req += [f"inst 128x{bn} uniform prec 4 outp {o}" for bn in (64, 128) for o in (0, 1)]          # every instance launch_conv has
+    req += [f"{ld} at Cout width {w}" for ld in CONV_LOADERS for w in (32, 64, 128)]
+    req += ["gather: nchw", "gather: C 3", "gather: C 6", "gather: off1", "gather: row", "gather: src1 row"]
+    req += [f"split 128x32 mode {m}" for m in (1, 2, 3)] + ["mode 4 at Cout <= 32 runs prec 3"]
+    req += [f"split {nw} mode {m}" for nw in ("narrow", "wide") for m in (1, 2, 3, 4)]
+    req += ["conv: pair source 0", "conv: pair source 1", "conv: pair both sources", "conv: pair output",
+            "conv: pairs with ISI_NO_CONV_PAIR_KERNEL", "hand-off pair-dma"]
+    req += ["K 64 prec 1", "K 96 prec 1", "K 96 prec 0", "downgrade K 96 mode 3", "K tail 36", "K tail 100", "K tail 124",
+            "chunk straddles taps", "slice-major one source", "slice-major two sources", "slice-major k4 s2", "slice-major four-phase"]
+    req += ["four-phase: tiles128 640", "conv: tiles128 639"]
+    req += [f"M {m}" for m in (1, 127, 128, 129)] + [f"row tiles % 8 = {r}" for r in (7, 0, 1)] + ["batch seam inside a tile"]
+    req += ["pad 0", "pad 1", "pad 2", "map smaller than the kernel k3", "map smaller than the kernel k4", "stride 2 on an odd map"]
+    req += [f"Cout {n}" for n in (1, 33, 40, 72, 130)]
+    for w in (32, 64, 128):
+        for p in (0, 1):
+            ep = f"conv tile {w} prec {p}"
+            req += [f"no bias: {ep}", f"relu: {ep}", f"res nhwc: {ep}", f"res nchw: {ep}", f"gate f32: {ep}", f"gate pair: {ep}",
+                    f"gate + residual: {ep}"]
+    req += ["conv: out nhwc", "conv: out nchw", "conv: out slice", "four-phase: out nchw", "gate on a sliced output",
+            "source is a channel slice"]
+    req += [f"four-phase: Cin {n}" for n in (16, 32, 48)] + [f"four-phase: Cout {n}" for n in (5, 64, 96)]
+    req += [f"four-phase: asked mode {m}" for m in range(5)] + [f"four-phase: prec {p}" for p in range(5)]
+    req += ["four-phase: pair source 0", "four-phase: pairs with ISI_NO_CONVT_PAIR_KERNEL", "hand-off convT-pair", "four-phase: pair output",
+            "gate f32: four-phase tile 64 prec 1", "gate pair: four-phase tile 64 prec 0", "gate pair: four-phase tile 64 prec 1",
+            "gate pair: four-phase tile 128 prec 1",
+            "four-phase: odd H and W", "four-phase: H = W = 1"]
+    req += [f"downgrade dual mode {m}" for m in (1, 2, 4)] + [f"downgrade gather mode {m}" for m in (1, 3)]
+    return req
+
+
+def conv_hold(got, refs, prec, what, margin=ROW_OPS_MARGIN):
+    """The comparison of the convolution tests: compare_rows per output channel against the spec, by the yardstick of the
+    product mode `prec` the launch ran."""
+    return compare_rows(conv_rows(got), conv_rows(refs.spec), conv_rows(conv_refs_yardstick(refs, prec)), what, margin)
+
+
+CONV_FAKE_PTR = 0x10000        # non-null, 16-byte aligned, never dereferenced by a route query or a host-side refusal
+
+
+def conv_lib_views(c, ptrs=None):
+    """(src0, src1 or None, res or None, dst) ctypes views of a case over the storage addresses `ptrs` ({"src0", "src1",
+    "res", "out": address of the storage's first float}; default: CONV_FAKE_PTR for all)."""
+    from interactive_spectrogram_inpainting import _hip
+    lay = conv_layout(c)
+    at = lambda name: (ptrs or {}).get(name, CONV_FAKE_PTR) + 4 * lay[name].offset
+    src = lambda name: _hip.isi_src(at(name), lay[name].shape[1], *lay[name].strides) if lay[name] else None
+    return src("src0"), src("src1"), src("res"), _hip.isi_dst(at("out"), *lay["out"].strides)
+
+
+def conv_lib_route(L, c, ptrs=None, mode=None, gate="case", pairs=None):
+    """isi_conv2d_route / isi_conv_transpose2d_k4s2_route for a case (or the variant launch: another precision, gate or set
+    of pair formats), under the case's knobs.  Launches nothing; with `ptrs` None no pointer is real."""
+    import contextlib
+    import ctypes as C
+    from interactive_spectrogram_inpainting import _hip
+    s0, s1, res, dst = conv_lib_views(c, ptrs)
+    at = lambda name: (ptrs or {}).get(name, CONV_FAKE_PTR)
+    ref = lambda v: C.byref(v) if v is not None else None
+    gate_kind = c.gate if gate == "case" else gate
+    g = at("gate") + 4 * conv_layout(c)["out"].offset if gate_kind else None
+    flags = conv_case_flags(c, mode, gate, pairs)
+    with contextlib.ExitStack() as stack:
+        for name, value in c.knobs:
+            stack.enter_context(_hip.knob(name, value))
+        if c.op == "convT":
+            return L.isi_conv_transpose2d_k4s2_route(ref(s0), at("w"), at("bias") if c.bias else None, g, ref(dst), c.B, c.H, c.W,
+                                                     c.cout, flags)
+        return L.isi_conv2d_route(ref(s0), ref(s1), at("w"), at("bias") if c.bias else None, ref(res), g, ref(dst), c.B, c.H, c.W,
+                                  c.cout, c.k, c.k, c.stride, c.pad, flags)
+
+
+def conv_igemm_coverage_gaps(cases):
+    """The requirements above that no case of `cases` reaches."""
+    have = set()
+    for c in cases:
+        have |= _conv_features(c)
+    return [r for r in conv_igemm_requirements() if r not in have]

@@ -864,8 +864,13 @@ size_t isi_rel_attention_workspace_bytes(const isi_attn_args *args);
  * output and lse = the log-sum-exp it wrote.  d_out has the strides of out; dq / dk / dv
  * are written with the strides of q / k / v (e.g. slices of one [S,B,3d] buffer); d_rel
  * [H, rel_rows, head_dim] is overwritten (NULL iff rel_embeddings is NULL).  workspace:
- * isi_rel_attention_bwd_workspace_floats(&fwd) floats, 16-byte aligned.  dK, dV, dQ and dE
- * are reduced in a fixed order (no cross-wave float atomics). */
+ * isi_rel_attention_bwd_workspace_floats(&fwd) floats, 16-byte aligned.  dK and dV are
+ * reduced in a fixed order on every route (no atomics), dQ and dE whenever Ck == 1 or there is no
+ * table: every element of G then receives at most one term.  With several channels per key event
+ * (Ck > 1) the keys of one event are added into their element of G with float atomics -- by the
+ * lanes of one wave instruction, and in the split pair (precision >= 1) by two waves where an event
+ * straddles a 32-key tile (32 % Ck != 0) -- in an order the hardware chooses: dQ (through G E) and
+ * dE may then differ in their last bits between two calls. */
 typedef struct isi_attn_bwd_args {
   isi_attn_args fwd;
   const float *d_out;

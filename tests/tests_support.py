@@ -2720,6 +2720,571 @@ def attention_fwd_hold(got, refs, what, yard=None, margin=ROW_OPS_MARGIN):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Float64 specification, float32 yardstick, split-product model, route mirror and case table of the relative-attention
+# BACKWARD (isi_rel_attention_bwd_f32: csrc/rel_attention_bwd_f32.hip, planned by csrc/rel_attention_run.cpp), on the
+# helpers of the forward's block above.  The operation, as the header of rel_attention_bwd_f32.hip states it, is a function
+# of the GIVEN float32 tensors q, k, v, e, dense mask, scale, dO, out, lse and (kept-logits calls) logits -- not the
+# derivative of some forward run:
+#     P = exp(logit - lse)        logit recomputed as in the forward, or logits_given (base 2) for the SAVED kernels
+#     D_i = sum_d dO[i,d] out[i,d]         dS = P o (dO V^T - D) * scale
+#     dV = P^T dO    dK = dS^T Q    G[i,r] = sum_{j: r(i,j) = r} dS[i,j]    dQ = dS K + G E    dE = G^T Q
+# A row whose lse is ATTN_EMPTY_LSE, a pair the mask leaves out and a pair whose logit is -inf contribute exactly 0 (not
+# NaN); d_rel rows no allowed pair selects are exactly 0.
+# Tensors here: q / dO / out [Sq,B,H,hd], k / v [Sk,B,H,hd], lse [B,H,Sq], logits [B,H,Sq,>= Sk]; results dq [B,H,Sq,hd],
+# dk / dv [B,H,Sk,hd], d_rel [H,rel_rows,hd] (None without a table).
+# tests/test_attention_bwd_host.py holds the spec to float64 autograd and shows what the hold rejects;
+# tests/test_attention_bwd_gpu.py holds every kernel route to it.
+ATTN_KNOB_FULL_ZERO, ATTN_KNOB_NO_G_FROM_KV, ATTN_KNOB_NO_GEMM = 4, 8, 16      # bits of `knobs`, as in tests/attention_plan_tracer.cpp
+ATTN_BWD_KNOBS = {ATTN_KNOB_FULL_ZERO: ("ISI_ATTN_FULL_ZERO", 1), ATTN_KNOB_NO_G_FROM_KV: ("ISI_ATTN_G_FROM_KV", 0),
+                  ATTN_KNOB_NO_GEMM: ("ISI_NO_GEMM_KERNEL", 1)}               # bit -> (switch, the value the bit sets)
+ATTN_G_MARGIN = 160                                # kMargin of rel_attention_bwd_f32.hip: columns zeroed on either side of a row's band of G
+ATTN_BWD_FAMILIES = ("exact", "split", "saved")    # the exact-fp32 pair | the split pair recomputing its logits | reading kept ones
+AttnBwd = collections.namedtuple("AttnBwd", "dq dk dv d_rel")
+AttnBwdRoute = collections.namedtuple(
+    "AttnBwdRoute", "has_e split one saved unit gemm_path band_only g_from_kv tail_q tail_k rho Rp band g_off g_len")
+
+
+def _attention_bwd_eval(dtype, q, k, v, rel, H, Cq, Ck, Ek, mask_mode, dense_mask, scale, d_out, out, lse, logits=None, no_D=False,
+                        no_scale=False, scale_twice_ge=False, rel_shift=0, swap_c_in_g=False, strict_causal=False, drop_last_key=False,
+                        g_drop_last_query=False, de_drop_query=None, de_drop_last_batch=False, junk_outside_rho=None):
+    """The operation in `dtype`; every keyword behind `logits` is a mutant of the host tests (off: the operation as specified):
+    no_D: D left out of dS; no_scale: dS without `scale`; scale_twice_ge: the G E share of dQ scaled again; rel_shift: r(i,j)
+    off by that much; swap_c_in_g: Cq and Ck exchanged in G's index; strict_causal: the diagonal excluded; drop_last_key: the
+    last key of a ragged 32-key tile left out of dK / dV; g_drop_last_query: the last query's row of G left 0 (its dQ still
+    has dS K); de_drop_query: that query left out of dE; de_drop_last_batch: the last batch item left out of dE;
+    junk_outside_rho = (lo, n): the d_rel rows outside [lo, lo + n) not zeroed (they hold 1)."""
+    hq, hk, hv, hdo, ho = (_attn_heads(t, H).to(dtype) for t in (q, k, v, d_out, out))
+    B, _, Sq, _ = hq.shape
+    Sk = hk.shape[2]
+    lse = torch.as_tensor(lse).detach().cpu()
+    allowed = attention_allowed(Sq, Sk, mask_mode, strict=strict_causal)
+    e = None if rel is None else torch.as_tensor(rel).detach().cpu().to(dtype)
+
+    def index(cq, ck):
+        idx = attention_rel_index(Sq, Sk, cq, ck, Ek) + rel_shift
+        if rel_shift or (cq, ck) != (Cq, Ck):
+            idx = idx.clamp(0, e.shape[1] - 1)
+        assert int(idx.min()) >= 0 and int(idx.max()) < e.shape[1], "the table must cover every (query, key) pair"
+        return idx.expand(B, H, Sq, Sk)
+
+    if logits is None:
+        s = hq @ hk.transpose(-1, -2)
+        if e is not None:
+            s = s + torch.einsum("bhid,hrd->bhir", hq, e).gather(3, index(Cq, Ck))
+        l2 = s * (scale * ATTN_LOG2E)
+        if dense_mask is not None:
+            l2 = l2 + torch.as_tensor(dense_mask).detach().cpu().to(dtype) * ATTN_LOG2E
+    else:
+        l2 = torch.as_tensor(logits).detach().cpu()[..., :Sk].to(dtype)
+    empty = lse == ATTN_EMPTY_LSE
+    zero = torch.zeros((), dtype=dtype)
+    live = allowed & (l2 > float("-inf")) & ~empty[..., None]        # (a NaN of a kept-logits buffer compares false: never read)
+    lse2 = torch.where(empty, zero, lse.to(dtype) * ATTN_LOG2E)[..., None]
+    P = torch.where(live, torch.exp2(torch.where(live, l2, zero) - lse2), zero)
+    D = (hdo * ho).sum(-1, keepdim=True)
+    dS = P * (hdo @ hv.transpose(-1, -2) - (0.0 if no_D else D))
+    if not no_scale:
+        dS = dS * scale
+    Pk, dSk = P, dS
+    if drop_last_key and Sk % 32:
+        Pk, dSk = P.clone(), dS.clone()
+        Pk[..., Sk - 1] = 0
+        dSk[..., Sk - 1] = 0
+    dV, dK, dQ, dE = Pk.transpose(-1, -2) @ hdo, dSk.transpose(-1, -2) @ hq, dS @ hk, None
+    if e is not None:
+        R = e.shape[1]
+        G = torch.zeros(B, H, Sq, R, dtype=dtype).scatter_add_(3, index(*((Ck, Cq) if swap_c_in_g else (Cq, Ck))), dS)
+        if g_drop_last_query:
+            G[:, :, Sq - 1] = 0
+        ge = torch.einsum("bhir,hrd->bhid", G, e)
+        dQ = dQ + (ge * scale if scale_twice_ge else ge)
+        Gd = G
+        if de_drop_query is not None and de_drop_query < Sq:
+            Gd = Gd.clone()
+            Gd[:, :, de_drop_query] = 0
+        if de_drop_last_batch:
+            Gd = Gd.clone()
+            Gd[B - 1] = 0
+        dE = torch.einsum("bhir,bhid->hrd", Gd, hq)
+        if junk_outside_rho is not None:
+            lo, n = junk_outside_rho
+            dE[:, :lo] = 1
+            dE[:, lo + n:] = 1
+    return AttnBwd(dQ, dK, dV, dE)
+
+
+def attention_bwd_spec(q, k, v, rel, H, Cq, Ck, Ek, mask_mode, dense_mask, scale, d_out, out, lse, logits=None):
+    """The float64 specification: AttnBwd(dq, dk, dv, d_rel) of the given tensors (logits: the kept base-2 logits of a
+    SAVED call, else None and they are recomputed)."""
+    return _attention_bwd_eval(torch.float64, q, k, v, rel, H, Cq, Ck, Ek, mask_mode, dense_mask, scale, d_out, out, lse, logits)
+
+
+def attention_bwd_f32(q, k, v, rel, H, Cq, Ck, Ek, mask_mode, dense_mask, scale, d_out, out, lse, logits=None, **mutant):
+    """The same evaluation in float32 torch on the CPU: the yardstick (and what the host tests mutate)."""
+    return _attention_bwd_eval(torch.float32, q, k, v, rel, H, Cq, Ck, Ek, mask_mode, dense_mask, scale, d_out, out, lse, logits, **mutant)
+
+
+def attention_bwd_model(q, k, v, rel, H, Cq, Ck, Ek, mask_mode, dense_mask, scale, d_out, out, lse, logits, precision, saved, drop=None,
+                        tail_q=0, tail_k=0, g_from_kv=False, renorm_lse=False):
+    """Float64 evaluation on the operands the split pair multiplies; its distance from the spec is the truncation the mode
+    accepts by design.  Read from csrc/rel_attention_bwd_f32.hip (rel_attention_bwd_q_split_kernel /
+    rel_attention_bwd_kv_split_kernel) and csrc/rel_attention_run.cpp:
+      * precision 1 and 3 run the three-term kernels, precision 2 the single-term ones (run.cpp make_route: `r.one =
+        g->precision == 2`; launch_bwd_split_hd): hi = rne_bf16(x), lo = rne_bf16(x - hi) (split_f4 / split2, csrc/split_bf16.h),
+        terms `ISI_MFB(kl, qh); ISI_MFB(kh, qlo); ISI_MFB(kh, qh)` with the first two under `if constexpr (!ONE)`;
+      * Q and dO are converted AS THEY ARE (q kernel lines 622-637: `split_f4(buf_load4(rq, oq), h0, l0)`; kv kernel's commit,
+        lines 1139-1156), as are K and V (kv kernel lines 1044-1059; q kernel's commit, lines 691-716) and the table rows
+        (`put_e`, lines 684-690 and 1116-1122): `scale` is NOT folded into an operand -- the float32 sum is multiplied by
+        scale2 = scale * log2(e) afterwards (`sv[r] * sc2 - lse2`, lines 852-866 and 1319-1334) and the dense mask added in
+        float32 as mask * log2(e);
+      * S = Q K^T and the band product Q E^T: lines 806-848 and 1267-1312 (products "qk", "band");
+      * with `saved` the logits are the given float32 values, no product (`sc2 = saved ? 1.f : scale2`, lines 797-803, 1261-1265);
+      * P = exp2(logit2 - lse log2(e)) in float32; dP = dO V^T on converted operands (lines 870-879, 1361-1370: "dp"),
+        dS = P (dP - D) scale in float32 with D = sum dO out in float32 (attn_dsum_kernel);
+      * dV = P^T dO multiplies the converted float32 P (`split_acc16(sv, sh, sl)`, line 1339) with converted dO (lines
+        1341-1357: "dv"); dK = dS^T Q and dQ = dS K the converted float32 dS with converted Q / K (lines 1407-1425: "dk";
+        lines 886-905: "dq");
+      * G holds the float32 dS; both products over it run three-term products under EVERY precision >= 1 (run.cpp line 328:
+        `gemm_flags = r.split ? ISI_CONV_BF16X3 : 0`, also for precision 2): dQ += G E on gemm_split_f32 (split_mode 1) or
+        the 1x1 convolution ("ge"), dE = G^T Q on conv_wgrad_batched_f32 ("de").  (The convolution ignores the flag for
+        short contractions -- include/isi_hip.h, "K < 128" -- and is exact fp32 there: closer to the spec than this model.)
+      * the one-row kernels (attn_bwd_tail_row / attn_bwd_tail_key, lines 1505-1627) are exact fp32 on recomputed logits: the
+        last tail_q query rows of dS (their dQ = dS K and their rows of G) and the last tail_k keys (dK, dV; with g_from_kv
+        their columns of G, line 1606) are the unconverted float64 values here.  A tail query's dQ still receives G E from
+        the three-term product like every other row;
+      * g_from_kv: the query-stationary kernel reads dS back from G (lines 776-794), the tail keys' exact columns included.
+    `drop` = one of "qk" "band" "dp" "dv" "dk" "dq" "ge" "de": that product without its lo.hi term; renorm_lse: the given lse
+    replaced by the log-sum-exp of the model's own logits -- host-test mutants."""
+    assert precision in (1, 2, 3), precision
+    pp = 2 if precision == 2 else 1
+    hq, hk, hv, hdo, ho = (_attn_heads(t, H).float() for t in (q, k, v, d_out, out))
+    B, _, Sq, _ = hq.shape
+    Sk = hk.shape[2]
+    lse = torch.as_tensor(lse).detach().cpu()
+    T = lambda A, Bp, contract, name: _attn_terms(A, Bp, contract, "lo_hi" if drop == name else None)
+    Qp, Kp, Vp, DOp = (_attn_pieces(t, pp) for t in (hq, hk, hv, hdo))
+    allowed = attention_allowed(Sq, Sk, mask_mode)
+    e = idx = None
+    if rel is not None:
+        e = torch.as_tensor(rel).detach().cpu().float()
+        idx = attention_rel_index(Sq, Sk, Cq, Ck, Ek).expand(B, H, Sq, Sk)
+        assert int(idx.min()) >= 0 and int(idx.max()) < e.shape[1]
+    scale2 = float(np.float32(scale) * np.float32(ATTN_LOG2E))
+    dm = None if dense_mask is None else torch.as_tensor(dense_mask).detach().cpu().double() * ATTN_LOG2E
+
+    def logits2(Qx, Kx, Ex):
+        s = T(Kx, Qx, lambda a, b: b @ a.transpose(-1, -2), "qk")
+        if e is not None:
+            s = s + T(Ex, Qx, lambda a, b: torch.einsum("bhid,hrd->bhir", b, a), "band").gather(3, idx)
+        s = s * scale2
+        return s if dm is None else s + dm
+
+    empty = lse == ATTN_EMPTY_LSE
+    zero = torch.zeros((), dtype=torch.float64)
+    D = (hdo.double() * ho.double()).sum(-1, keepdim=True)
+
+    def p_ds(l2, dP):
+        live = allowed & (l2 > float("-inf"))
+        none, given = empty, lse.double() * ATTN_LOG2E
+        if renorm_lse:
+            none = ~live.any(-1)
+            given = torch.log2(torch.where(live, torch.exp2(torch.where(live, l2, zero)), zero).sum(-1).clamp(min=2.0 ** -1000))
+        live = live & ~none[..., None]
+        lse2 = torch.where(none, zero, given)[..., None]
+        P = torch.where(live, torch.exp2(torch.where(live, l2, zero) - lse2), zero)
+        return P, P * (dP - D) * scale
+
+    l2 = (torch.as_tensor(logits).detach().cpu()[..., :Sk].double() if saved
+          else logits2(Qp, Kp, None if e is None else _attn_pieces(e, pp)))
+    P, dS = p_ds(l2, T(Vp, DOp, lambda a, b: b @ a.transpose(-1, -2), "dp"))
+    dS_g = dS
+    if tail_q or tail_k:
+        one = lambda t: (t.double(),)
+        Px, dSx = p_ds(logits2(one(hq), one(hk), None if e is None else one(e)), hdo.double() @ hv.double().transpose(-1, -2))
+        dS_g = dS.clone()
+        if tail_q:
+            dS_g[:, :, Sq - tail_q:] = dSx[:, :, Sq - tail_q:]
+        if tail_k and g_from_kv:
+            dS_g[..., Sk - tail_k:] = dSx[..., Sk - tail_k:]
+    Pp, dSp = _attn_pieces(P.float(), pp), _attn_pieces(dS.float(), pp)
+    dV = T(DOp, Pp, lambda a, b: b.transpose(-1, -2) @ a, "dv")
+    dK = T(Qp, dSp, lambda a, b: b.transpose(-1, -2) @ a, "dk")
+    dQ = T(Kp, _attn_pieces(dS_g.float(), pp) if g_from_kv else dSp, lambda a, b: b @ a, "dq")
+    if tail_k:
+        dV[:, :, Sk - tail_k:] = (Px.transpose(-1, -2) @ hdo.double())[:, :, Sk - tail_k:]
+        dK[:, :, Sk - tail_k:] = (dSx.transpose(-1, -2) @ hq.double())[:, :, Sk - tail_k:]
+    if tail_q:
+        dQ[:, :, Sq - tail_q:] = (dSx @ hk.double())[:, :, Sq - tail_q:]
+    dE = None
+    if e is not None:
+        G = torch.zeros(B, H, Sq, e.shape[1], dtype=torch.float64).scatter_add_(3, idx, dS_g.float().double())
+        Gp, E1, Q1 = _attn_pieces(G.float(), 1), _attn_pieces(e, 1), _attn_pieces(hq, 1)
+        dQ = dQ + T(E1, Gp, lambda a, b: torch.einsum("bhir,hrd->bhid", b, a), "ge")
+        dE = T(Q1, Gp, lambda a, b: torch.einsum("bhir,bhid->hrd", b, a), "de")
+    return AttnBwd(dQ, dK, dV, dE)
+
+
+def gemm_split_applicable(M, N, K, split_mode=1):
+    """gemm_split_applicable of csrc/gemm_split_f32.hip"""
+    return split_mode in (1, 3) and K % 32 == 0 and K >= 128 and N > 32 and M >= 256
+
+
+def attention_bwd_route(hd, precision, Cq, Ck, table, Sq, Sk, B, H, mask_mode, dense, logits, q_uniform, knobs, Ek, rel_rows,
+                        gemm_ok=None):
+    """Restatement of rho_range, g_band, carve (G's place), make_route and attention_tail_rows of csrc/rel_attention_run.cpp
+    for an accepted backward call.  logits: kept logits are handed over; q_uniform: q_ss == B * q_sb; knobs: bits
+    ATTN_KNOB_FULL_ZERO | ATTN_KNOB_NO_G_FROM_KV | ATTN_KNOB_NO_GEMM; gemm_ok: the answer of gemm_split_applicable(Sq B, hd,
+    Rp, 1), asked here when None.  rho = (lo, n): the table rows G covers; Rp: n padded to the 32-row K chunk; band =
+    (lo_slope, lo_base, hi_slope, hi_base): query i of a unit-channel call is non-zero in columns [lo_slope i + lo_base,
+    hi_slope i + hi_base] of G; g_off, g_len: G's place in the workspace in floats, laid out [H][Sq][B][Rp]."""
+    R = rel_rows if table else 0
+    has_e = R > 0
+    lo, n = 0, R
+    if has_e and Cq == Ck and not dense:
+        if mask_mode == 1:
+            lo = min(max(Ek - 1, 0), R - 1)
+            n = R - lo
+        if mask_mode == 2:
+            n = max(1, min(R, Ek))
+    Rp = -(-max(n, 1) // 32) * 32
+    split, one, unit = precision >= 1, precision == 2, Cq == 1 and Ck == 1
+    saved = split and bool(logits)
+    if gemm_ok is None:
+        gemm_ok = gemm_split_applicable(Sq * B, hd, Rp, 1)
+    gemm_path = bool(has_e and split and q_uniform and gemm_ok and not knobs & ATTN_KNOB_NO_GEMM)
+    band_only = bool(unit and gemm_path and not knobs & ATTN_KNOB_FULL_ZERO)
+    g_from_kv = bool(band_only and saved and not knobs & ATTN_KNOB_NO_G_FROM_KV)
+    tail_q = attention_tail_rows(Sq, mask_mode, dense) if split and (not has_e or Ck == 1) else 0
+    tail_k = attention_tail_rows(Sk, mask_mode, dense) if split else 0
+    top, bot = Ek - 1 - lo, Ek - Sk - lo
+    band = (0 if mask_mode == 1 else 1, top if mask_mode == 1 else bot, 0 if mask_mode == 2 else 1, top)
+    return AttnBwdRoute(has_e, split, one, saved, unit, gemm_path, band_only, g_from_kv, tail_q, tail_k, (lo, n), Rp, band,
+                        -(-(B * H * Sq) // 64) * 64, H * B * Sq * Rp if has_e else 0)
+
+
+def attention_bwd_launches(r):
+    """launches per launcher of an accepted call on route r, as tests/attention_plan_tracer.cpp counts them"""
+    want = {"attn_dsum": 1}
+    if r.split:
+        want["attn_bwd_split"] = 2 if r.g_from_kv else 1
+        if r.tail_q or r.tail_k:
+            want["attn_bwd_tails"] = 1
+    else:
+        want["attn_bwd_exact"] = 1
+    if r.has_e:
+        want["attn_zero_g_margins" if r.band_only else "attn_zero_g"] = 1
+        want["gemm_split" if r.gemm_path else "conv2d_batched"] = 1
+        want.update(pack_rel_T=1, conv_wgrad_batched=1, unpack_drel=1)
+    return want
+
+
+# ---- the cases.  B = H = 0 with `persistent` set: the pair count is derived from the device (attention_fwd_case_resolve)
+AttnBwdCase = collections.namedtuple(
+    "AttnBwdCase", "hd prec Sq Sk B H Cq Ck mask dense table saved knobs layout wide ld_extra kind ek_extra persistent scale_mul")
+ATTN_BWD_KINDS = ("plain", "peaked", "flat", "shifted")
+ATTN_BWD_TAIL_SIZES = (257, 258, 385)
+
+
+def attention_bwd_case_id(c):
+    return (f"hd{c.hd}-p{c.prec}{'s' if c.saved else ''}-s{c.Sq}.{c.Sk}-b{c.B}h{c.H}-c{c.Cq}.{c.Ck}-m{c.mask}d{int(c.dense)}t{int(c.table)}-"
+            f"k{c.knobs}-{c.layout}{'+wide' if c.wide else ''}-ld{c.ld_extra}-{c.kind}-e{c.ek_extra}-x{c.scale_mul:g}"
+            + (f"-{c.persistent}" if c.persistent else ""))
+
+
+def attention_bwd_case_resolve(c, cus=ATTN_DEFAULT_CUS):
+    """A persistent case with the forward's device-derived pair count: "one": cus + 1 (batch, head) pairs, "snake": cus // 2."""
+    if not c.persistent:
+        return c
+    r = attention_fwd_case_resolve(_attention_bwd_fwd_case(c), cus)
+    return c._replace(B=r.B, H=r.H)
+
+
+def _attention_bwd_fwd_case(c):
+    """the forward case whose data (attention_fwd_case_data) the backward case differentiates"""
+    return AttnFwdCase(c.hd, c.prec, c.Sq, c.Sk, c.B, c.H, c.Cq, c.Ck, c.mask, c.dense, c.table, "none", 0, c.layout, c.wide, c.ld_extra,
+                       c.kind, "lse", c.ek_extra, c.persistent)
+
+
+def attention_bwd_case_route(c, cus=ATTN_DEFAULT_CUS, gemm_ok=None):
+    c = attention_bwd_case_resolve(c, cus)
+    Ek = -(-c.Sk // c.Ck) + c.ek_extra
+    return attention_bwd_route(c.hd, c.prec, c.Cq, c.Ck, c.table, c.Sq, c.Sk, c.B, c.H, c.mask, c.dense, c.saved,
+                               c.layout != "batch_first", c.knobs, Ek, -(-c.Sq // c.Cq) + Ek - 1, gemm_ok)
+
+
+def attention_bwd_family(c):
+    return "exact" if c.prec == 0 else "saved" if c.saved else "split"
+
+
+def _attention_bwd_table():
+    def bc(hd, prec, Sq, Sk, mask=0, dense=False, B=2, H=3, Cq=1, Ck=1, table=True, saved=False, knobs=0, layout="contig", wide=False,
+           ld_extra=0, kind="plain", ek_extra=0, persistent="", scale_mul=1.0):
+        return AttnBwdCase(hd, prec, Sq, Sk, B, H, Cq, Ck, mask, dense, table, bool(saved and prec), knobs, layout, wide,
+                           ld_extra if saved and prec else 0, kind, ek_extra, persistent, scale_mul)
+    # (Sq, Sk, mask, dense): every ragged length, mask and mask combination once per family, as in the forward's table
+    slots = [(1, 1, 0, False), (33, 31, 0, False), (127, 32, 1, False), (128, 33, 2, False), (129, 97, 0, True), (257, 65, 1, False),
+             (258, 130, 2, False), (259, 257, 0, False), (33, 63, 1, False), (129, 130, 1, True), (129, 129, 2, False),
+             (257, 130, 2, False), (258, 97, 1, False)]
+    insts = {"exact": [(hd, 0) for hd in (16, 32, 64)], "split": [(hd, p) for p in (1, 2, 3) for hd in (16, 32, 64)]}
+    insts["saved"] = insts["split"]
+    cases = []
+    for fam in ATTN_BWD_FAMILIES:
+        general = 0
+        for i, (Sq, Sk, mask, dense) in enumerate(slots):
+            hd, prec = insts[fam][i % len(insts[fam])]
+            Cq, Ck = 1, 1
+            if i % 2:
+                Cq, Ck = ATTN_CHANNELS[general % len(ATTN_CHANNELS)]
+                general += 1
+            cases.append(bc(hd, prec, Sq, Sk, mask, dense, B=2 + i % 3, H=3 if i % 2 else 2, Cq=Cq, Ck=Ck, table=i % 4 != 3,
+                            saved=fam == "saved", layout="fused" if (Sq, Sk) == (129, 129) else ATTN_LAYOUTS[i % 4], wide=i % 2 == 1,
+                            ld_extra=32 * (i // 2 % 2), kind=ATTN_BWD_KINDS[i % 4], ek_extra=3 if i in (5, 6) else 0))
+    # dQ += G E on the banded GEMM: head_dim 64, Sq B >= 256, Rp >= 128, one channel per event; every mask; the three
+    # switches; kept logits with and without g_from_kv.  129 x 129 is the smallest such shape, 385 x 385 the smallest whose
+    # G has elements further than kMargin from a row's band (and, unmasked, a one-row / one-key tail)
+    for mask in (0, 1, 2):
+        for j, (saved, knobs) in enumerate([(False, 0), (False, ATTN_KNOB_FULL_ZERO), (False, ATTN_KNOB_NO_GEMM), (True, 0),
+                                            (True, ATTN_KNOB_NO_G_FROM_KV)]):
+            cases.append(bc(64, 1 + (mask + j) % 3, 129, 129, mask, saved=saved, knobs=knobs, H=2, kind=ATTN_BWD_KINDS[(mask + j) % 4],
+                            layout=("contig", "fused", "head2")[(mask + j) % 3]))
+    for mask, saved, knobs in [(0, False, 0), (1, True, 0), (2, False, 0), (0, False, ATTN_KNOB_FULL_ZERO), (1, False, ATTN_KNOB_NO_GEMM),
+                               (0, True, 0), (2, True, ATTN_KNOB_NO_G_FROM_KV)]:
+        cases.append(bc(64, 1 if mask != 1 else 2, 385, 385, mask, saved=saved, knobs=knobs, H=2))
+    # the same shapes where gemm_split_applicable declines: head_dim 32 and 16 (N > 32), Sq B < 256 (M >= 256), and q rows
+    # that are no [Sq B, .] matrix (batch_first); 385 x 385 shows the full zero on the device
+    cases += [bc(32, 1, 129, 129, 0), bc(16, 2, 129, 129, 1, saved=True), bc(32, 3, 385, 385, 0, H=2), bc(16, 1, 385, 385, 2, H=2, saved=True),
+              bc(64, 1, 127, 127, 0, B=2), bc(64, 1, 129, 129, 0, layout="batch_first"), bc(64, 2, 385, 385, 1, H=2, layout="batch_first", saved=True)]
+    # tails (unmasked, no dense mask, split pair): 257, 258 and 385 on either side, 259 a block again; Ck = 2 declines the
+    # tail query; one side alone; without a table; kept logits with g_from_kv (the one-key kernel stores its column of G)
+    cases += [bc(64, 1, 257, 257), bc(32, 2, 258, 258, kind="peaked"), bc(16, 3, 259, 259), bc(32, 1, 257, 257, Cq=2, Ck=2),
+              bc(32, 3, 257, 130, Cq=4, Ck=1, kind="shifted"), bc(64, 2, 130, 258, kind="flat"), bc(16, 1, 258, 257, table=False),
+              bc(64, 1, 257, 257, saved=True, ld_extra=32), bc(64, 2, 258, 258, saved=True, kind="peaked"),
+              bc(32, 1, 258, 257, saved=True, wide=True), bc(64, 3, 257, 130, saved=True, layout="head2"),
+              bc(16, 2, 130, 257, saved=True, table=False)]
+    # the split pair's grid: one 512-thread workgroup per (batch, head, block), 8 ceil(pairs / 8) blocks of them (xcd_grid); a
+    # workgroup holds ~160 KB of LDS, so a CU runs one: more items than CUs run in rounds ("one": cus + 1 pairs, pairs % 8 != 0,
+    # some workgroups leave at once), fewer in one ("snake": cus // 2 pairs of one block each)
+    cases += [bc(16, 1, 129, 129, 1, B=0, H=0, persistent="one"), bc(32, 2, 97, 97, 2, B=0, H=0, persistent="snake", saved=True)]
+    # a scale that is not 1 / sqrt(head_dim)
+    cases.append(bc(32, 1, 129, 97, 1, Cq=2, Ck=1, scale_mul=0.7, kind="peaked"))
+    return cases
+
+
+ATTENTION_BWD_CASES = _attention_bwd_table()
+ATTENTION_BWD_ENTRY_CASES = [c for c in ATTENTION_BWD_CASES if not c.persistent and c.saved and not c.wide and not c.ld_extra and not c.knobs
+                             and c.scale_mul == 1.0 and c.table and (c.layout == "contig" or (c.layout == "fused" and c.Sq == c.Sk))]
+ATTENTION_BWD_ENTRY_CASES = ([c for c in ATTENTION_BWD_ENTRY_CASES if c.layout == "contig"][:2]
+                             + [c for c in ATTENTION_BWD_ENTRY_CASES if c.layout == "fused"][:2])
+
+
+def _attention_bwd_features(c, cus):
+    fam, r = attention_bwd_family(c), attention_bwd_case_route(c, cus)
+    rc = attention_bwd_case_resolve(c, cus)
+    f = {f"inst {fam} hd{c.hd} p{c.prec}", f"{fam}: Sq {c.Sq}", f"{fam}: Sk {c.Sk}", f"{fam}: mask {c.mask}", f"{fam}: layout {c.layout}",
+         f"{fam}: kind {c.kind}", f"{fam}: table {int(c.table)}"}
+    if c.dense:
+        f.add(f"{fam}: dense mask")
+    if not r.unit:
+        f.add(f"{fam}: channels {c.Cq}.{c.Ck}")
+    if c.ek_extra and c.table:
+        f.add(f"{fam}: Ek above the key events")
+    if c.wide:
+        f.add(f"{fam}: out in a wider buffer")
+    if c.saved:
+        f.add(f"saved: logits_ld +{c.ld_extra}")
+    if c.scale_mul != 1.0:
+        f.add("scale is not 1 / sqrt(head_dim)")
+    # the products over G
+    Rp_ok = r.Rp >= 128
+    if c.table and c.prec and r.unit and Rp_ok and c.Sq * rc.B >= 256:
+        if c.hd == 64 and c.layout != "batch_first":
+            how = ("ISI_NO_GEMM_KERNEL" if c.knobs & ATTN_KNOB_NO_GEMM else "ISI_ATTN_FULL_ZERO" if c.knobs & ATTN_KNOB_FULL_ZERO else
+                   "ISI_ATTN_G_FROM_KV=0" if c.knobs & ATTN_KNOB_NO_G_FROM_KV else "g_from_kv" if c.saved else "margins only")
+            assert r.gemm_path == (how != "ISI_NO_GEMM_KERNEL") and r.band_only == (how not in ("ISI_NO_GEMM_KERNEL", "ISI_ATTN_FULL_ZERO"))
+            assert r.g_from_kv == (how == "g_from_kv")
+            if how != "ISI_ATTN_G_FROM_KV=0" or c.saved:
+                f.add(f"gemm mask {c.mask}: {how}")
+            if c.Sq > 2 * ATTN_G_MARGIN + 1:
+                f.add(f"device evidence: {'margins only' if r.band_only else 'full zero'}")
+        elif c.hd == 64:
+            assert not r.gemm_path
+            f.add("no gemm: q_ss != B q_sb")
+        else:
+            assert not r.gemm_path
+            f.add(f"no gemm: head_dim {c.hd}")
+            if c.Sq > 2 * ATTN_G_MARGIN + 1:
+                f.add("device evidence: full zero where the GEMM declines")
+    if c.table and c.prec and r.unit and Rp_ok and c.hd == 64 and c.Sq * rc.B < 256:
+        assert not r.gemm_path
+        f.add("no gemm: Sq B < 256")
+    # tails
+    if c.prec and c.mask == 0 and not c.dense:
+        if r.tail_q:
+            f.add(f"tail query Sq {c.Sq}")
+        if r.tail_k:
+            f.add(f"tail key Sk {c.Sk}")
+        if c.Sq == 259 and c.Sk == 259:
+            assert not (r.tail_q or r.tail_k)
+            f.add("no tail at 259")
+        if c.Sq in ATTN_BWD_TAIL_SIZES and c.table and c.Ck == 2 and not r.tail_q and r.tail_k:
+            f.add("tail query declined by Ck = 2")
+        if r.tail_q and not r.unit:
+            f.add("tail query, several channels per query event")
+        if r.tail_q and not r.tail_k:
+            f.add("tail query without tail key")
+        if r.tail_k and not r.tail_q and c.Ck == 1:
+            f.add("tail key without tail query")
+        if (r.tail_q or r.tail_k) and not c.table:
+            f.add("tail without a table")
+        if r.tail_k and r.g_from_kv:
+            f.add("tail key with g_from_kv")
+        if r.tail_q and r.band_only:
+            f.add("tail query into a band-only G")
+        if (r.tail_q or r.tail_k) and c.saved and not r.g_from_kv:
+            f.add("tail with kept logits, without g_from_kv")
+    if c.persistent:
+        items = rc.B * rc.H * -(-c.Sq // ATTN_QB)
+        f.add("split grid: more items than CUs" if items > cus else "split grid: fewer items than CUs")
+        if rc.B * rc.H % 8:
+            f.add("split grid: pairs % 8 != 0")
+    return f
+
+
+def attention_bwd_requirements():
+    req = [f"inst exact hd{hd} p0" for hd in (16, 32, 64)]
+    req += [f"inst {fam} hd{hd} p{p}" for fam in ("split", "saved") for hd in (16, 32, 64) for p in (1, 2, 3)]
+    for fam in ATTN_BWD_FAMILIES:
+        req += [f"{fam}: Sq {s}" for s in ATTN_SQ] + [f"{fam}: Sk {s}" for s in ATTN_SK] + [f"{fam}: mask {m}" for m in (0, 1, 2)]
+        req += [f"{fam}: dense mask", f"{fam}: table 0", f"{fam}: table 1", f"{fam}: Ek above the key events", f"{fam}: out in a wider buffer"]
+        req += [f"{fam}: channels {a}.{b}" for a, b in ATTN_CHANNELS] + [f"{fam}: layout {l}" for l in ATTN_LAYOUTS]
+        req += [f"{fam}: kind {k}" for k in ATTN_BWD_KINDS]
+    req += ["saved: logits_ld +0", "saved: logits_ld +32", "scale is not 1 / sqrt(head_dim)"]
+    req += [f"gemm mask {m}: {how}" for m in (0, 1, 2)
+            for how in ("margins only", "ISI_ATTN_FULL_ZERO", "ISI_NO_GEMM_KERNEL", "g_from_kv", "ISI_ATTN_G_FROM_KV=0")]
+    req += ["device evidence: margins only", "device evidence: full zero", "device evidence: full zero where the GEMM declines"]
+    req += ["no gemm: head_dim 32", "no gemm: head_dim 16", "no gemm: Sq B < 256", "no gemm: q_ss != B q_sb"]
+    req += [f"tail query Sq {s}" for s in ATTN_BWD_TAIL_SIZES] + [f"tail key Sk {s}" for s in ATTN_BWD_TAIL_SIZES]
+    req += ["no tail at 259", "tail query declined by Ck = 2", "tail query, several channels per query event", "tail query without tail key",
+            "tail key without tail query", "tail without a table", "tail key with g_from_kv", "tail query into a band-only G",
+            "tail with kept logits, without g_from_kv"]
+    req += ["split grid: more items than CUs", "split grid: fewer items than CUs", "split grid: pairs % 8 != 0"]
+    return req
+
+
+def attention_bwd_coverage_gaps(cases, cus=ATTN_DEFAULT_CUS):
+    """The requirements of the backward's case table (every instantiation; per family the ragged lengths, masks, channel and
+    buffer layouts, data kinds; every route of the products over G with the switches; the tails; the grid) no case covers."""
+    have = set()
+    for c in cases:
+        have |= _attention_bwd_features(c, cus)
+    return [r for r in attention_bwd_requirements() if r not in have]
+
+
+AttnBwdData = collections.namedtuple("AttnBwdData", "q k v rel dense scale Ek rel_rows empty_rows dout out lse logits ld forced_row")
+
+
+def attention_bwd_case_data(c, forced=True):
+    """The inputs of a (resolved) case: q, k, v, the table and the dense mask of attention_fwd_case_data (kinds plain, flat,
+    shifted; peaked is q x 3 here, and x 1 for a query the mask mode leaves fewer than 8 keys: the forward's q x 6 saturates
+    the softmax, as does any factor on a row of two keys, and the gradient of a saturated row vanishes through cancellation --
+    its row error, of order 1 for the float32 evaluation too, would be the whole tensor's); dO = randn; out, lse and the kept logits from attention_fwd_spec in FLOAT64, rounded to float32 -- the
+    backward is handed tensors no kernel of the project made.  logits [B,H,Sq,ld] hold NaN at every pair the mask mode
+    leaves out and in the columns from Sk on ("entries of masked pairs are never read"), -inf where the dense mask is.
+    forced: one more row (Sq // 3, for Sq >= 33) is made empty by lse = ATTN_EMPTY_LSE alone, and the given `out` of a row
+    with a single live key (the first causal row, every row of a one-key call) is HALF the forward's: with the forward's own
+    out such a row has P = 1 and dO v = D identically, so dS = 0 and its dq would hold rounding noise of size 1e-8 against a
+    float64 reference of size 1e-17 -- a row that measures nothing and, as the largest row error of the tensor, hides every
+    other row.  The operation is a function of the given tensors; with out / 2 that row's dS = P (dO v) scale / 2 is as well
+    conditioned as any other and shows that the given out is what is read."""
+    import zlib
+    fc = _attention_bwd_fwd_case(c)
+    d = attention_fwd_case_data(fc._replace(kind="plain") if c.kind == "peaked" else fc)
+    if c.kind == "peaked":
+        few = attention_allowed(c.Sq, c.Sk, c.mask).sum(-1) < 8
+        d = d._replace(q=d.q * torch.where(few, 1.0, 3.0)[:, None, None, None])
+    scale = float(np.float32(d.scale * c.scale_mul))
+    fwd = attention_fwd_spec(d.q, d.k, d.v, d.rel, c.H, c.Cq, c.Ck, d.Ek, c.mask, d.dense, scale)
+    gen = torch.Generator().manual_seed(zlib.crc32(("dO " + attention_bwd_case_id(c._replace(B=0, H=0) if c.persistent else c)).encode()))
+    dout = torch.randn(c.Sq, c.B, c.H, c.hd, generator=gen)
+    out = fwd.out.float().clone()
+    lse = fwd.lse.float().clone()
+    empty, forced_row = set(d.empty_rows), None
+    if forced:
+        out[(fwd.allowed & (fwd.logits2 > float("-inf"))).sum(-1) == 1] *= 0.5
+        if c.Sq >= 33:
+            forced_row = c.Sq // 3
+            lse[:, :, forced_row] = ATTN_EMPTY_LSE
+            empty.add(forced_row)
+    out = out.permute(2, 0, 1, 3).contiguous()
+    ld = (c.Sk + 31) // 32 * 32 + c.ld_extra
+    logits = torch.full((c.B, c.H, c.Sq, ld), float("nan"))
+    logits[..., :c.Sk] = torch.where(fwd.allowed, fwd.logits2.float(), torch.full((), float("nan")))
+    return AttnBwdData(d.q, d.k, d.v, d.rel, d.dense, scale, d.Ek, d.rel_rows, sorted(empty), dout, out, lse, logits, ld, forced_row)
+
+
+AttnBwdRefs = collections.namedtuple("AttnBwdRefs", "spec f32 model yard route")
+
+
+def attention_bwd_args(c, d, saved):
+    return (d.q, d.k, d.v, d.rel, c.H, c.Cq, c.Ck, d.Ek, c.mask, d.dense, d.scale, d.dout, d.out, d.lse, d.logits if saved else None)
+
+
+def attention_bwd_refs(c, d, route, models=True):
+    """spec, float32 evaluation, the split pair's model (None on the exact route) and the yardstick of the hold: the float32
+    evaluation on the exact route; on the split routes per element the worse of it and the model -- but the float32
+    evaluation ALONE on what the exact-fp32 one-row kernels produce by themselves: dk and dv of the last route.tail_k keys,
+    and dq of the last route.tail_q queries where there is no table (with one, the row also receives G E from the three-term
+    product like every other row: the model says so and the larger of the two applies)."""
+    a = attention_bwd_args(c, d, route.saved)
+    spec = attention_bwd_spec(*a)
+    f32 = AttnBwd(*(None if t is None else t.double() for t in attention_bwd_f32(*a)))
+    assert all(t is None or bool(torch.isfinite(t).all()) for t in f32), "the float32 yardstick is not finite on this data"
+    model, yard = None, f32
+    if route.split and models:
+        model = attention_bwd_model(*a, c.prec, route.saved, tail_q=route.tail_q, tail_k=route.tail_k, g_from_kv=route.g_from_kv)
+        yard = AttnBwd(*(None if s is None else larger_error(f, m, s) for f, m, s in zip(f32, model, spec)))
+        if route.tail_k:
+            yard.dk[:, :, -route.tail_k:], yard.dv[:, :, -route.tail_k:] = f32.dk[:, :, -route.tail_k:], f32.dv[:, :, -route.tail_k:]
+        if route.tail_q and not route.has_e:
+            yard.dq[:, :, -route.tail_q:] = f32.dq[:, :, -route.tail_q:]
+    return AttnBwdRefs(spec, f32, model, yard, route)
+
+
+@functools.lru_cache(maxsize=2)
+def attention_bwd_case_refs(c, cus=ATTN_DEFAULT_CUS):
+    """(resolved case, data, refs) of a case on a device of `cus` CUs; computed once per case."""
+    r = attention_bwd_case_resolve(c, cus)
+    d = attention_bwd_case_data(r)
+    return r, d, attention_bwd_refs(r, d, attention_bwd_case_route(c, cus))
+
+
+def attention_bwd_hold(got, refs, what, yard=None, margin=ROW_OPS_MARGIN):
+    """The hold of the attention backward: per output (dq, dk, dv, d_rel; rows = the hd values of one query / key / table
+    row) every element finite, a row the spec finds exactly 0 (an empty query row, a key no live query reaches, a table
+    row no allowed pair selects) exactly 0, and compare_rows with the project's margin and floor.  The rows of the one-row
+    kernels (the last route.tail_q queries of dq, the last route.tail_k keys of dk and dv) are blocks of their own.
+    Returns {"dq" | "tail dq" | ...: RowCheck}; raises AssertionError at the first failure."""
+    spec, yard, r = refs.spec, yard or refs.yard, refs.route
+    checks = {}
+    for name, tail in (("dq", r.tail_q), ("dk", r.tail_k), ("dv", r.tail_k), ("d_rel", 0)):
+        s, y, g = getattr(spec, name), getattr(yard, name), getattr(got, name)
+        if s is None:
+            assert g is None, f"{what}: {name} without a table"
+            continue
+        assert g is not None, f"{what}: no {name}"
+        g = torch.as_tensor(g).detach().cpu()
+        assert g.shape == s.shape, f"{what}: {name} {tuple(g.shape)} against {tuple(s.shape)}"
+        assert bool(torch.isfinite(g).all()), f"{what}: {name} is not finite"
+        zero = (s == 0).all(-1)
+        assert bool((g[zero] == 0).all()), f"{what}: a row of {name} the spec finds exactly 0 is not 0"
+        n = s.shape[-2]
+        for block, rows in (("", slice(0, n - tail)), ("tail ", slice(n - tail, n))):
+            if rows.start != rows.stop:
+                checks[block + name] = compare_rows(g[..., rows, :], s[..., rows, :], y[..., rows, :], f"{what} {block}{name}", margin)
+    return checks
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Float64 specification, float32 yardstick, split-product models, route mirror and case table of the implicit-GEMM
 # convolutions (csrc/conv_igemm_f32.hip through isi_conv2d_f32 / isi_conv2d_gated_f32 / isi_conv_transpose2d_k4s2_f32 and
 # its gated form), in the style of the blocks above: plain torch on the CPU, no autograd and none of the project's kernels.
